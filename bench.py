@@ -11,7 +11,11 @@ no collective on the data path -> weak scaling); `value` = faces of all ranks / 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 200 --warmup 5
 
-Rank 0 prints ONE JSON line (contract in the task description) including
+A plain run does only what the headline needs: data, the model (one training pass), W warm-up steps, K timed steps, then
+ONE JSON line from rank 0 with metric / value / unit / higher_is_better / dtype / ms_per_step.  --dump-outputs DIR writes the
+landmarks of the last timed step (float32 .npy) before that line; the inputs are seeded, so two builds can be compared output
+for output.  --full adds every other leg to the line:
+  "train", "rcr68_*", "config3_train", "sustained", "e2e_with_h2d", "fused_apply", "cpu_baseline_train" -- see below
   "roofline"     -- HOG kernel: algorithmic HBM bytes / HIP-event-timed kernel duration vs 8 TB/s
   "cpu_baseline" -- the CPU oracle (the reference's algorithm restated, oracle/; its HOG back-end is the reference's own
                     hog.c when oracle/_ref is present) timed on this box's cores on a bounded sample of the same workload
@@ -118,7 +122,16 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--rcr68-shard", type=int, default=8192,
                     help="faces per GPU of the RCR-68 detect leg (BASELINE config 4: 65 536 faces over 8 GPUs); 0 skips the RCR-68 legs")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: training times, RCR-68, config 3, rooflines, sustained and "
+                         "input-inclusive rates, CPU baselines and parity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the landmarks of the last timed step to DIR/landmarks.npy (float32; DIR/landmarks_rank<r>.npy with "
+                         "several GPUs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def relaunch_under_torchrun(args):
@@ -150,24 +163,36 @@ def main():
     # ---- training rows of THIS rank (metric "train sec/cascade 100k faces"): images x (1 + 9 perturbed boxes) as in
     # rcr-train.cpp:421-431.  Generated first, in forked numpy workers, before torch / HIP are initialised.
     from superviseddescent_amd import ibug, parallel, synth
+    try:
+        from threadpoolctl import threadpool_limits
+    except ImportError:
+        import contextlib
+        threadpool_limits = lambda limits: contextlib.nullcontext()    # noqa: E731
     t0 = time.time()
     ids = ibug.RCR22_IDS
     rows_per_image = 10
     n_img_total = max(args.train_rows // rows_per_image, 8 * world)
     ia, ib = parallel.shard_range(n_img_total, rank, world)
     workers = max(1, min(16, (os.cpu_count() or 1) // (2 * world)))
-    timg, tbox, tgt = synth.make_faces(ib - ia, seed=synth.SEED + 1000 + rank, chunk=32,
-                                       workers=workers if ib - ia >= 1024 else 0)
+    # One BLAS thread per forked worker: each would otherwise start a thread pool as wide as the machine, and the workers' pools
+    # oversubscribe the CPUs many times over (generation an order of magnitude slower).  The images are bit-identical either way.
+    with threadpool_limits(limits=1):
+        timg, tbox, tgt = synth.make_faces(ib - ia, seed=synth.SEED + 1000 + rank, chunk=32,
+                                           workers=workers if ib - ia >= 1024 else 0)
     txs, tx0, tidx = synth.make_samples(tbox, tgt, ids, n_perturb=rows_per_image - 1, seed=synth.SEED + 2000 + rank)
     n_train_global = n_img_total * rows_per_image
     # RCR-68 rows on the SAME images (BASELINE config 5: RCR-68 train, 100k faces): 68 landmarks, same boxes and perturbations
     ids68 = ibug.IBUG68_IDS
-    if args.rcr68_shard > 0:
+    if args.full and args.rcr68_shard > 0:
         txs68, tx068, tidx68 = synth.make_samples(tbox, tgt, ids68, n_perturb=rows_per_image - 1, seed=synth.SEED + 2000 + rank)
-    # detect faces of this rank: the headline batch = the first args.batch of them, the RCR-68 shard = all of them
+    # detect faces of this rank: the headline batch = the first args.batch of them, the RCR-68 shard = all of them.  The
+    # stream of a face depends on its 32-face chunk and on n_detect (which picks the generator), so a plain run draws only the
+    # chunks that hold the batch and gets the same batch as --full
     n_detect = max(args.batch, args.rcr68_shard)
-    images, boxes, gt = synth.make_faces(n_detect, seed=synth.SEED + 17 * rank, chunk=32,
-                                         workers=workers if n_detect >= 1024 else 0)
+    n_draw = n_detect if args.full else min(n_detect, -(-args.batch // 32) * 32)
+    with threadpool_limits(limits=1):
+        images, boxes, gt = synth.make_faces(n_draw, seed=synth.SEED + 17 * rank, chunk=32,
+                                             workers=workers if n_detect >= 1024 else 0)
     datagen_s = time.time() - t0
 
     import torch
@@ -242,11 +267,11 @@ def main():
     reduce_scatter = parallel.make_torch_reduce_scatter(local_rank) if (use_dist and not native) else None
     via = ("RCCL called by the library on its own streams (sdm_set_*_rccl, own ncclCommInitRank)" if native else
            "torch.distributed %s through the sdm_set_* callbacks" % backend)
-    def train_rcr22(collective, sdo=sdo, hog=hog):
-        """Two passes of sdo.train (the second one timed).  collective=False: every rank on its own rows, no exchange -- the
-        model the detect legs run with several GPUs (see defer below)."""
+    def train_rcr22(collective, sdo=sdo, hog=hog, passes=2):
+        """Two passes of sdo.train (the second one timed; one pass when only the model is wanted).  collective=False: every rank
+        on its own rows, no exchange -- the model the detect legs run with several GPUs (see defer below)."""
         nlsr_, wall_, timing_ = [], [], None
-        for rep in range(2):    # the second pass is the measured one (buffers allocated, code loaded)
+        for rep in range(passes):    # the second pass is the measured one (buffers allocated, code loaded)
             sdo.ctx.enable_timing(True)
             sdo.ctx.get_timing(reset=True)
             if use_dist and collective:
@@ -287,7 +312,7 @@ def main():
     # of the scaling run with it.  The detect legs then run with a model every rank trained on its own rows (its coefficients do not
     # enter the timing; the parity block compares against the oracle with the same coefficients).
     defer68 = world > 1 or os.environ.get("SDM_BENCH_DEFER_RCR68", "0") == "1"      # (the switch: the several-GPU order on one GPU, for the test)
-    nlsr, train_wall, train_timing = train_rcr22(collective=not defer68)
+    nlsr, train_wall, train_timing = train_rcr22(collective=not defer68, passes=2 if args.full else 1)
     train_s = time.time() - t0
     regressors = [r.x for r in sdo.regressors]
     ctx = sdo.ctx
@@ -356,7 +381,7 @@ def main():
     # run with ranks as threads on one GPU (tests/test_gpu_sharded_solve.py), and a collective that hangs on real links must not
     # take the headline of the scaling run with it.
     rcr68 = None
-    if args.rcr68_shard > 0 and not defer68:
+    if args.full and args.rcr68_shard > 0 and not defer68:
         rcr68, ctx68, F68, L68, M68, sdo68 = train_rcr68()
 
     # ---- workload: this rank's shard of synthetic faces, resident in HBM --------------------------------
@@ -373,39 +398,40 @@ def main():
         ctx.set_x_device(d_x0.data_ptr(), args.batch)     # 720 KB device-to-device: hand the batch over
         ctx.detect_batch(fetch=False)
 
-    # ---- algorithmic HBM bytes of the HOG launches: per level, per face,
-    #      L*(2h)^2 ROI bytes + F*4 feature bytes written + 2L*4 landmark bytes read ------------------------
     ctx.enable_timing(False)
-    ctx.set_x_device(d_x0.data_ptr(), args.batch)
-    hog_bytes = 0          # SURVEY.md 8d per level: patch bytes + feature row written + landmarks read (the unfused launch)
-    patch_bytes = 0        # ... the patch bytes alone
-    for l in range(n_levels):
-        ctx.hog_features(l)
-        h = ctx.patch_indices()[:, 0].astype(np.int64)
-        patch_bytes += int((L * (2 * h) ** 2).sum())
-        hog_bytes += int((L * (2 * h) ** 2).sum()) + args.batch * (ctx.feature_dim(l) * 4 + M * 4)
-        ctx.apply(l)
-    x_final = ctx.get_x()
-    apply_flops = sum(2.0 * args.batch * ctx.feature_dim(l) * M for l in range(n_levels))
-    # sdm_detect_batch is fused (the descriptors are multiplied by the regressor on the chip): SURVEY 8d -- "if HOG is fused with the
-    # apply GEMM, the feature write term drops out and is reported as such".  Algorithmic bytes of a level = patch bytes + the
-    # landmark rows read and written.
-    fused_bytes = patch_bytes + n_levels * args.batch * 2 * M * 4
-    from superviseddescent_amd.engine import hog_plan
+    if args.full:      # (the byte counts of the roofline figures: one stepwise cascade, --full only)
+        # ---- algorithmic HBM bytes of the HOG launches: per level, per face,
+        #      L*(2h)^2 ROI bytes + F*4 feature bytes written + 2L*4 landmark bytes read ------------------------
+        ctx.set_x_device(d_x0.data_ptr(), args.batch)
+        hog_bytes = 0          # SURVEY.md 8d per level: patch bytes + feature row written + landmarks read (the unfused launch)
+        patch_bytes = 0        # ... the patch bytes alone
+        for l in range(n_levels):
+            ctx.hog_features(l)
+            h = ctx.patch_indices()[:, 0].astype(np.int64)
+            patch_bytes += int((L * (2 * h) ** 2).sum())
+            hog_bytes += int((L * (2 * h) ** 2).sum()) + args.batch * (ctx.feature_dim(l) * 4 + M * 4)
+            ctx.apply(l)
+        x_final = ctx.get_x()
+        apply_flops = sum(2.0 * args.batch * ctx.feature_dim(l) * M for l in range(n_levels))
+        # sdm_detect_batch is fused (the descriptors are multiplied by the regressor on the chip): SURVEY 8d -- "if HOG is fused with the
+        # apply GEMM, the feature write term drops out and is reported as such".  Algorithmic bytes of a level = patch bytes + the
+        # landmark rows read and written.
+        fused_bytes = patch_bytes + n_levels * args.batch * 2 * M * 4
+        from superviseddescent_amd.engine import hog_plan
 
-    def cut_fraction(cell, nl=L):      # share of the landmarks whose patch is cut by a pass boundary of the packed launch (two parts of cells)
-        pl = hog_plan(5, cell, 4, nl)
-        if pl is None:
-            return 0.0
-        def cuts(passes):
-            seen = {}
-            for pt in passes:
-                for d in pl["lane_tab"][pt]:
-                    if (int(d) >> 17) & 1:
-                        seen.setdefault(int(d) & 0xff, set()).add(pt)
-            return sum(1 for v in seen.values() if len(v) > 1)
-        return (pl["n_main"] * cuts(range(pl["P"])) + cuts(range(pl["P"], pl["P"] + pl["Pt"]))) / float(nl)
-    cut_frac = float(np.mean([cut_fraction(p.cell_size) for p in params]))
+        def cut_fraction(cell, nl=L):      # share of the landmarks whose patch is cut by a pass boundary of the packed launch (two parts of cells)
+            pl = hog_plan(5, cell, 4, nl)
+            if pl is None:
+                return 0.0
+            def cuts(passes):
+                seen = {}
+                for pt in passes:
+                    for d in pl["lane_tab"][pt]:
+                        if (int(d) >> 17) & 1:
+                            seen.setdefault(int(d) & 0xff, set()).add(pt)
+                return sum(1 for v in seen.values() if len(v) > 1)
+            return (pl["n_main"] * cuts(range(pl["P"])) + cuts(range(pl["P"], pl["P"] + pl["Pt"]))) / float(nl)
+        cut_frac = float(np.mean([cut_fraction(p.cell_size) for p in params]))
 
     # ---- W untimed warm-up steps, then exactly K timed steps between barrier + synchronize on both sides.  (Rounds 2-4 ran 40
     # untimed "pre-roll" steps first; round 4's own A/B showed no effect -- 3.61 M against 3.55 M faces/s without it -- so it is gone.)
@@ -431,11 +457,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    # ---- what the timed path computed in its last step: the landmarks a caller of detect_batch receives.  At most 64 MB over all
+    # ranks: a larger batch is written as every k-th face (a fixed sample, the same in every run with the same arguments)
+    if args.dump_outputs:
+        x_out = ctx.get_x()
+        stride = max(1, -(-x_out.nbytes * world // 64000000))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "landmarks.npy" if world == 1 else "landmarks_rank%d.npy" % rank), x_out[::stride])
+
     # ---- the same step loop for at least one second of timed work (the 20-step headline window is 23 ms and moves with
     # the clock the chip happens to hold): steps of the headline's kind until >= 1 s has passed, the sustained rate and the clock
     # the GPU reports at its end (rocm-smi; None when the tool is not there) --------------------------------------------------------
     sustained = None
-    if rank == 0:
+    if args.full and rank == 0:
         n_sus = max(args.steps, int(1.25 / max(dt / args.steps, 1e-6)))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -461,7 +495,7 @@ def main():
     # the uploads are double buffered against the cascade of the previous batch: a copy stream fills one of two device buffers while
     # the compute stream runs the cascade on the other.  The headline `value` stays the resident-input rate.
     e2e = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             h_images = torch.from_numpy(images[:args.batch]).pin_memory()
             h_x0 = torch.from_numpy(x0).pin_memory()
@@ -518,7 +552,7 @@ def main():
     # ---- several GPUs: the RCR-68 legs now, under a watchdog.  If they have not finished after RCR68_DEADLINE_S seconds every rank
     # leaves (os._exit) and rank 0 prints the headline line it already has, with the legs marked as timed out.
     watchdog = None
-    if defer68:
+    if args.full and defer68:
         import threading
         ms_e = dt / args.steps * 1e3
         hog_e = timing["hog"][0] / max(timing["hog"][1], 1)
@@ -618,15 +652,46 @@ def main():
     if watchdog is not None:
         watchdog.cancel()
 
-    if rank != 0:
+    def shutdown():
         if lazy_rccl is not None:
             lazy_rccl.destroy()
         if use_dist:
             dist.destroy_process_group()
+
+    if rank != 0:
+        shutdown()
         return
 
     ms_per_step = dt / args.steps * 1e3
     faces_per_s = args.batch * world * args.steps / dt
+    out = {
+        "metric": "faces/sec RCR-22 detect (batch 4096)",
+        "value": faces_per_s,
+        "unit": "faces/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": "RCR-22 detect, batch %d synthetic 256x256 u8 faces per GPU, 4 cascade levels "
+                        "(UoCTTI HOG 5x5 cells, cell 11/10/8/6, 4 orientations, F=8801, M=44), model trained "
+                        "on-GPU on %d synthetic faces (shipped .bin absent from the reference checkout)"
+                        % (args.batch, n_train_global),
+            "batch_per_gpu": args.batch,
+            "levels": n_levels,
+            "sharding": "faces sharded by rank, no collective on the detect path",
+        },
+    }
+    if not args.full:
+        print(json.dumps(out))
+        shutdown()
+        return
+
     hog_ms, hog_n = timing["hog"]
     app_ms, app_n = timing["apply"]
     hog_avg_ms = hog_ms / max(hog_n, 1)
@@ -694,28 +759,7 @@ def main():
     F22 = ctx.feature_dim(0)
     T22 = (F22 + 127) // 128
     pair_ms = hog_avg_ms + app_ms / max(app_n, 1)
-    out = {
-        "metric": "faces/sec RCR-22 detect (batch 4096)",
-        "value": faces_per_s,
-        "unit": "faces/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic",
-        "config": {
-            "workload": "RCR-22 detect, batch %d synthetic 256x256 u8 faces per GPU, 4 cascade levels "
-                        "(UoCTTI HOG 5x5 cells, cell 11/10/8/6, 4 orientations, F=8801, M=44), model trained "
-                        "on-GPU on %d synthetic faces (shipped .bin absent from the reference checkout)"
-                        % (args.batch, n_train_global),
-            "batch_per_gpu": args.batch,
-            "levels": n_levels,
-            "sharding": "faces sharded by rank, no collective on the detect path",
-        },
+    out.update({
         "roofline": {
             "kernel": hog_kernel,
             "bound": "hbm",
@@ -768,7 +812,7 @@ def main():
             "seconds_total_two_passes": train_s,
             "seconds_data_generation": datagen_s,
         },
-    }
+    })
 
     if rcr68 is not None:
         out["rcr68_train"] = rcr68["train"]
@@ -1006,10 +1050,7 @@ def main():
             "note": "CPU stages as the reference's VerbosePartialPivLUSolver prints them (verbose_solver.hpp:66-97): Eigen's f32 GEMM / "
                     "PartialPivLU restated with numpy sgemm / LAPACK sgetrf on all cores; never extrapolated to the full row count"}
     print(json.dumps(out))
-    if lazy_rccl is not None:
-        lazy_rccl.destroy()
-    if use_dist:
-        dist.destroy_process_group()
+    shutdown()
 
 
 if __name__ == "__main__":

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$REPO/gpurun_out/profile_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $REPO/bench.py --steps 20 --warmup 2 --no-cpu --train-rows 20000 --rcr68-shard 0"
+CMD="python $REPO/bench.py --steps 20 --warmup 2 --no-cpu --full --train-rows 20000 --rcr68-shard 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- $CMD > $OUT/bench_under_trace.json 2> $OUT/trace_stderr.log
 cp $OUT/trace/t_kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null
 i=0
@@ -17,7 +17,7 @@ for pmc in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GR
   rocprofv3 --kernel-trace --pmc $pmc --output-format csv -d $OUT/p$i -o pmc -- $CMD > /dev/null 2> $OUT/p${i}_stderr.log
 done
 # the full default command (RCR-22 headline + RCR-68 train 100k rows + RCR-68 detect shard): kernel stats only
-CMD68="python $REPO/bench.py --steps 20 --warmup 2 --no-cpu"
+CMD68="python $REPO/bench.py --steps 20 --warmup 2 --no-cpu --full"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace68 -o t -- $CMD68 > $OUT/bench_full_under_trace.json 2> $OUT/trace68_stderr.log
 python - <<PY
 import csv, glob, collections, re
@@ -26,7 +26,7 @@ def short(n):
     m=re.search(r'(\w+_kernel)', n); return m.group(1) if m else n.split("(")[0][:40]
 try:
     with open(out+"/summary_full_bench.txt","w") as fh:
-        fh.write("== rocprofv3 --kernel-trace --stats : python bench.py --steps 20 --warmup 2 --no-cpu  (RCR-22 train 100k + detect 4096, RCR-68 train 100k + detect 8192) ==\n")
+        fh.write("== rocprofv3 --kernel-trace --stats : python bench.py --steps 20 --warmup 2 --no-cpu --full  (RCR-22 train 100k + detect 4096, RCR-68 train 100k + detect 8192) ==\n")
         fh.write("%-32s %7s %13s %11s %7s\n" % ("kernel","calls","total_us","avg_us","%"))
         for r in list(csv.DictReader(open(out+"/trace68/t_kernel_stats.csv")))[:18]:
             fh.write("%-32s %7s %13.1f %11.2f %7.2f\n" % (short(r["Name"]), r["Calls"], float(r["TotalDurationNs"])/1e3, float(r["AverageNs"])/1e3, float(r["Percentage"])))
@@ -52,7 +52,7 @@ out="$OUT"
 def short(n):
     m=re.search(r'(\w+_kernel)', n); return m.group(1) if m else n.split("(")[0][:40]
 with open(out+"/summary.txt","w") as fh:
-    fh.write("== rocprofv3 --kernel-trace --stats : python bench.py --steps 20 --warmup 2 --no-cpu --train-rows 20000 --rcr68-shard 0 ==\n")
+    fh.write("== rocprofv3 --kernel-trace --stats : python bench.py --steps 20 --warmup 2 --no-cpu --full --train-rows 20000 --rcr68-shard 0 ==\n")
     fh.write("%-28s %7s %13s %11s %7s\n" % ("kernel","calls","total_us","avg_us","%"))
     for r in list(csv.DictReader(open(out+"/kernel_stats.csv")))[:14]:
         fh.write("%-28s %7s %13.1f %11.2f %7.2f\n" % (short(r["Name"]), r["Calls"], float(r["TotalDurationNs"])/1e3, float(r["AverageNs"])/1e3, float(r["Percentage"])))
@@ -106,7 +106,7 @@ for k,v in rows.items():
                                    "launch_geometry": k.split(" grid=")[1], "dispatches": cnt[(k,"FETCH_SIZE")]}
         for c in ("SQ_INSTS_VALU","SQ_INSTS_SALU","SQ_INSTS_LDS","SQ_WAVES","SQ_ACTIVE_INST_VALU","SQ_LDS_BANK_CONFLICT","SQ_LDS_IDX_ACTIVE","SQ_VALU_MFMA_BUSY_CYCLES","SQ_BUSY_CYCLES","GRBM_GUI_ACTIVE"):
             if c in v: hbm[k.split(" grid=")[0]][c]=v[c]/cnt[(k,c)]
-json.dump({"batch": 4096, "source": "scripts/profile_bench.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of python bench.py --steps 20 --warmup 2 --no-cpu --train-rows 20000 --rcr68-shard 0; FETCH_SIZE x2 (gfx950), KB units", "kernels": hbm}, open(out+"/hbm_traffic.json","w"), indent=1)
+json.dump({"batch": 4096, "source": "scripts/profile_bench.sh: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of python bench.py --steps 20 --warmup 2 --no-cpu --full --train-rows 20000 --rcr68-shard 0; FETCH_SIZE x2 (gfx950), KB units", "kernels": hbm}, open(out+"/hbm_traffic.json","w"), indent=1)
 print(open(out+"/summary.txt").read())
 PY
 # the raw traces are tens of megabytes: only the summaries travel back (gpurun merges at most 64 MiB)

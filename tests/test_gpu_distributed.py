@@ -42,7 +42,7 @@ def test_bench_under_torchrun(built):
     import torch
     n = min(torch.cuda.device_count(), 2)
     r = _torchrun(n, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "256",
-                  "--train-rows", "800", "--no-cpu", SDM_BENCH_SHARD_SOLVE="1")
+                  "--train-rows", "800", "--no-cpu", "--full", SDM_BENCH_SHARD_SOLVE="1")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
@@ -58,7 +58,8 @@ def test_bench_several_gpu_order_and_watchdog(built):
     import json
     import torch
     n = min(torch.cuda.device_count(), 2)
-    common = ("--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "256", "--train-rows", "800", "--rcr68-shard", "256", "--no-cpu")
+    common = ("--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "256", "--train-rows", "800", "--rcr68-shard", "256", "--no-cpu",
+              "--full")
     r = _torchrun(n, os.path.join(ROOT, "bench.py"), *common, SDM_BENCH_DEFER_RCR68="1")
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -92,7 +93,7 @@ def test_bench_with_two_real_processes(built):
     factorisation sharded over the two ranks."""
     import json
     r = _torchrun(2, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "512", "--train-rows", "4000",
-                  "--rcr68-shard", "256", "--no-cpu", SDM_BENCH_BACKEND="gloo", timeout=900)
+                  "--rcr68-shard", "256", "--no-cpu", "--full", SDM_BENCH_BACKEND="gloo", timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -114,7 +115,7 @@ def test_bench_relaunches_itself_for_several_gpus(built):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", SDM_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "256",
-                        "--train-rows", "800", "--rcr68-shard", "0", "--no-cpu"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--train-rows", "800", "--rcr68-shard", "0", "--no-cpu", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -131,7 +132,8 @@ def test_bench_collectives_are_issued_by_the_library(built):
     import json
     import torch
     n = min(torch.cuda.device_count(), 2)
-    common = ("--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "256", "--train-rows", "800", "--rcr68-shard", "256", "--no-cpu")
+    common = ("--gpus", str(n), "--steps", "2", "--warmup", "1", "--batch", "256", "--train-rows", "800", "--rcr68-shard", "256", "--no-cpu",
+              "--full")
     outs = {}
     for how in ("rccl", "torch"):
         r = _torchrun(n, os.path.join(ROOT, "bench.py"), *common, SDM_BENCH_COLLECTIVES=how, SDM_BENCH_SHARD_SOLVE="1")

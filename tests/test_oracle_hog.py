@@ -1,7 +1,7 @@
 """Pins oracle/sdm_oracle.c (the C restatement of the HOG feature path) against
 (1) the committed golden vectors produced by the reference's own hog.c (tests/golden/make_golden.py), and
-(2) when oracle/_ref exists (build container, or shipped prebuilt to the GPU box), the reference's hog.c
-    itself on fresh random patches -- bit for bit in both cases."""
+(2) the reference's hog.c outputs on seeded random patches, recorded in tests/golden/hog_ref_random_patches.npz
+    (tests/golden/make_golden_ref_hog_random.py) -- bit for bit in both cases."""
 import os
 
 import numpy as np
@@ -46,13 +46,23 @@ def test_threaded_batch_equals_serial():
     assert np.array_equal(bits(a), bits(b))
 
 
-@pytest.mark.skipif(orc.ref_lib() is None, reason="oracle/_ref/libref_hog.so not built (no /root/reference)")
-def test_restated_hog_matches_reference_library_on_random_patches():
+RANDOM_PATCH_CASES = [(55, 11, 4, 1), (50, 10, 4, 1), (40, 8, 9, 1), (30, 6, 4, 0), (36, 6, 16, 1)]
+
+
+def random_patches():
+    """(case, patch) in a fixed order: 8 seeded random patches per case."""
     rng = np.random.default_rng(3)
-    for (S, c, O, var) in [(55, 11, 4, 1), (50, 10, 4, 1), (40, 8, 9, 1), (30, 6, 4, 0), (36, 6, 16, 1)]:
+    for case in RANDOM_PATCH_CASES:
         for _ in range(8):
-            img = rng.integers(0, 256, (S, S)).astype(np.float32)
-            assert np.array_equal(bits(orc.hog(img, c, O, var)), bits(orc.ref_hog(img, c, O, var)))
+            yield case, rng.integers(0, 256, (case[0], case[0])).astype(np.float32)
+
+
+def test_restated_hog_matches_reference_library_on_random_patches():
+    """Against the reference's hog.c outputs on these patches, recorded by tests/golden/make_golden_ref_hog_random.py."""
+    ref = np.load(os.path.join(os.path.dirname(__file__), "golden", "hog_ref_random_patches.npz"))
+    assert np.array_equal(ref["cases"], np.array([case for case, _ in random_patches()], np.int32))
+    for i, ((S, c, O, var), img) in enumerate(random_patches()):
+        assert np.array_equal(bits(orc.hog(img, c, O, var)), bits(ref[f"out_{i}"])), (i, S, c, O, var)
 
 
 def test_resize_identity_and_area_fast_path():
