@@ -322,6 +322,45 @@ int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_l
  * of the four clamped block terms). */
 int sdm_debug_set_detect_path(sdm_ctx* ctx, int fused, int split_store);
 
+/* Head pose from 2D landmarks: the ModelProjection cascade of the reference's examples/pose_estimation.cpp -- a known-template
+ * SupervisedDescentOptimiser (superviseddescent.hpp:195-197, 287-292) over LinearRegressor<> levels (:281-283), NoNormalisation.
+ * Its state lives in the handle beside the landmark state, so that a detect batch's landmarks reach it without leaving the device.
+ *   parameter row  x = [r_x, r_y, r_z, t_x, t_y, t_z], angles in degrees (deg2rad, :41)
+ *   projection     MVP = P * T(t) * R_y * R_x * R_z (:222, rotations :58-98), P the perspective of :142-154 with
+ *                  fovy = rad2deg(2 atan2(height, 2 focal)) (:46), aspect = width / height; clip = MVP (X, Y, Z, 1), divide by w,
+ *                  viewport (:164-174), u = (x_ss - width/2) / focal, v = (y_ss - height/2) / focal (:232)
+ *   feature row    [u_0..u_{K-1}, v_0..v_{K-1}] (F = 2K, no bias column, regressors.hpp:345-350); observed = features - templates;
+ *                  x_{k+1} = x_k - observed * R_k (R_k: 2K x 6)
+ * Limits (SDM_ERR_INVALID otherwise): 1 <= K <= 64 model points, 6 parameters, levels 0..15, N >= 1. */
+/* points: K x 3 model coordinates (the homogeneous w = 1 is implied).  The example uses focal 1800, 1000 x 1000, near 1, far 5000.
+ * A different K drops the pose regressors and templates. */
+int sdm_pose_set_model(sdm_ctx* ctx, const float* points, int K, float focal, float width, float height, float near_, float far_);
+/* current_x of the pose cascade: N x 6 (host, or a device-to-device copy) */
+int sdm_pose_set_x(sdm_ctx* ctx, const float* x_host, int n_samples);
+int sdm_pose_get_x(sdm_ctx* ctx, float* x_host);
+int sdm_pose_set_x_device(sdm_ctx* ctx, const float* x_dev, int n_samples);
+/* the known templates y (the observed landmarks, normalised as :327): n_samples x 2K, [u_0..u_{K-1}, v_0..v_{K-1}] */
+int sdm_pose_set_templates(sdm_ctx* ctx, const float* templates, int n_samples, int feature_dim);
+/* Detect -> pose on the device: the templates of all N rows of the LANDMARK state x (N x 2L pixel coordinates, e.g. after
+ * sdm_detect_batch): template[n] = [(x_n[idx_k] - W_n / 2) / focal .., (y_n[idx_k] - H_n / 2) / focal ..] with W_n x H_n the size of
+ * row n's image (sdm_set_sample_image_index).  K must equal the pose model's K; 0 <= landmark_index[k] < L. */
+int sdm_pose_templates_from_landmarks(sdm_ctx* ctx, const int* landmark_index, int K, float focal);
+/* training targets x*: N x 6 for the current rows (`parameters`, superviseddescent.hpp:165) */
+int sdm_pose_set_targets(sdm_ctx* ctx, const float* xstar_host, int n_samples);
+/* the observed values of the current x: N x 2K (features - templates when templates are set for these rows).  Tests. */
+int sdm_pose_features(sdm_ctx* ctx, int level, float* out_host);
+/* One training level (superviseddescent.hpp:170-218): projection, b = x - x*, [A|b]^T [A|b] summed in double in a fixed order
+ * (bit-identical runs for the same N), Regulariser::get_matrix (regressors.hpp:126-148; lambda as sdm_solve reports it), LU with
+ * partial pivoting in double (regressors.hpp:199-234) -- a singular system returns what the factorisation gives, not an error --
+ * then x <- x_{k+1} with the regressor of this level (the launch of sdm_pose_test).  R_host (2K x 6) and lambda_out may be NULL. */
+int sdm_pose_train_level(sdm_ctx* ctx, int level, int reg_type, float reg_param, int regularise_last_row, float* R_host, float* lambda_out);
+/* the regressor of a pose level, 2K x 6 row-major */
+int sdm_pose_set_regressor(sdm_ctx* ctx, int level, const float* R_host);
+int sdm_pose_get_regressor(sdm_ctx* ctx, int level, float* R_host);
+/* Levels first_level .. first_level + n_levels - 1 on all rows in ONE launch (test / predict, superviseddescent.hpp:262-344):
+ * a row's result is bit-identical whatever the batch and whether the levels run in one call or one call each. */
+int sdm_pose_test(sdm_ctx* ctx, int first_level, int n_levels);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,23 @@ struct sdm_ctx {
     bool g_scattered = false;                     // the Gram matrix holds the summed tiles of the OWNED tile columns only
     DevBuf<float> gsmall;                         // summed diagonal + the Frobenius share (the small all-reduce of that exchange)
 
+    // head pose (sdm_capi_pose.hip): the ModelProjection cascade, state of its own beside the landmark state above, so that a
+    // detect batch's landmarks reach it without leaving the device (sdm_pose_templates_from_landmarks)
+    struct Pose {
+        PoseCamDev cam{};                  // cam.K == 0: no model set
+        DevBuf<float> pts;                 // K x 3 model points
+        int N = 0;                         // rows of x
+        DevBuf<float> x, xstar, tmpl;      // N x 6, N x 6, tmpl_N x 2K
+        int tmpl_N = 0;
+        bool have_targets = false;
+        DevBuf<float> R;                   // SDM_POSE_MAX_LEVELS x 2K x 6, level l at l * 2K * 6
+        unsigned have_R = 0;               // bit l: level l holds a regressor
+        DevBuf<float> Ab;                  // training scratch: N x (2K + 6)
+        DevBuf<double> partial, G;
+        DevBuf<int> lm;                    // landmark index map of the gather
+        void release() { pts.release(); x.release(); xstar.release(); tmpl.release(); R.release(); Ab.release(); partial.release(); G.release(); lm.release(); }
+    } pose;
+
     // timing
     bool timing = false;
     float t_ms[SDM_T_COUNT] = {0};

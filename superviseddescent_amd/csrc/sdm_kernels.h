@@ -300,3 +300,27 @@ inline size_t sdm_backsolve_flag_floats(int Fp) { return sdm_backsolve_flag_ints
 int sdm_launch_cholesky_solve(float* G, long long ldg, int F, int rhs0, int nrhs, float* R_out,
                               long long ldr, float* work, int* status, hipStream_t stream, const SolveAux* aux = nullptr,
                               const SolveShard* shard = nullptr);
+
+// ---- head pose (sdm_pose.hip): the ModelProjection cascade of the reference's examples/pose_estimation.cpp ----
+#define SDM_POSE_MAX_K 64          // model points
+#define SDM_POSE_MAX_LEVELS 16
+#define SDM_POSE_MAX_T (2 * SDM_POSE_MAX_K + 6)   // columns of [A | b]
+// camera of one pose context: the perspective matrix of pose_estimation.cpp:142-154 (row-major, built on the host in float),
+// the viewport W x H (:164-174), the focal length the projections are normalised by (:232) and the number of model points
+struct PoseCamDev {
+    float P[16];
+    float f, W, H;
+    int K;
+};
+size_t sdm_pose_cascade_lds_bytes(int K, int n_levels);
+void sdm_launch_pose_cascade(float* x, const float* tmpl, const float* R, const float* pts, const PoseCamDev& cam, int N, int n_levels,
+                             hipStream_t s);
+// out: N x width, width = 2K (features) or 2K + 6 (with xstar: [features - templates | x - x*])
+void sdm_launch_pose_project(const float* x, const float* xstar, const float* tmpl, const float* pts, const PoseCamDev& cam, int N,
+                             float* out, int width, hipStream_t s);
+int sdm_pose_gram_blocks(int N);   // workgroups (partials) of the normal equations for N rows: a function of N alone
+void sdm_launch_pose_gram(const float* Ab, int N, int T, double* partial, double* G, hipStream_t s);
+void sdm_launch_pose_solve(const double* G, int F, int T, int reg_type, float param, int n_train, int regularise_last_row, float* R,
+                           float* lambda_out, hipStream_t s);
+void sdm_launch_pose_gather(const float* xl, int L, int N, const int* lm, int K, const int* img_idx, const int* img_w, const int* img_h,
+                            float f, float* tmpl, hipStream_t s);

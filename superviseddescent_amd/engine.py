@@ -10,6 +10,7 @@ Class and method names follow the reference so that the parity tests read like i
 ``Regulariser`` / ``LinearRegressor``          include/superviseddescent/regressors.hpp:87-169, 318-400
 ``SupervisedDescentOptimiser.train/test/predict``  include/superviseddescent/superviseddescent.hpp:165-344
 ``detection_model.detect``                     include/rcr/model.hpp:122-183
+``ModelProjection``                            examples/pose_estimation.cpp:187-240 (head pose, csrc/sdm_pose.hip)
 =============================================  =====================================================
 
 Everything numeric happens on the MI355X: HOG extraction, regressor apply, Gram/RHS build and the
@@ -410,6 +411,76 @@ class Context:
         check(self._lib.sdm_train_level(self._h, level, reg_type, reg_param, int(regularise_last_row),
                                         n_train_global))
 
+    # -- head pose (sdm_pose_*: the ModelProjection cascade, state beside the landmark state) -------------------------------
+    def pose_set_model(self, points: np.ndarray, focal: float = 1800.0, width: float = 1000.0, height: float = 1000.0,
+                       near: float = 1.0, far: float = 5000.0):
+        """``points``: K x 3 model coordinates.  Camera defaults: examples/pose_estimation.cpp:205-211."""
+        p = np.ascontiguousarray(points, np.float32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("pose model points must be K x 3")
+        check(self._lib.sdm_pose_set_model(self._h, p.ctypes.data, p.shape[0], focal, width, height, near, far))
+        self.pose_K = p.shape[0]
+
+    def pose_set_x(self, x: np.ndarray):
+        x = np.ascontiguousarray(x, np.float32)
+        if x.ndim != 2 or x.shape[1] != 6:
+            raise ValueError("pose parameters must be N x 6")
+        check(self._lib.sdm_pose_set_x(self._h, x.ctypes.data, x.shape[0]))
+        self.pose_N = x.shape[0]
+
+    def pose_set_x_device(self, dev_ptr: int, n: int):
+        check(self._lib.sdm_pose_set_x_device(self._h, ctypes.c_void_p(dev_ptr), n))
+        self.pose_N = n
+
+    def pose_get_x(self) -> np.ndarray:
+        out = np.empty((self.pose_N, 6), np.float32)
+        check(self._lib.sdm_pose_get_x(self._h, out.ctypes.data))
+        return out
+
+    def pose_set_templates(self, templates: np.ndarray):
+        t = np.ascontiguousarray(templates, np.float32)
+        if t.ndim != 2:
+            raise ValueError("pose templates must be N x 2K")
+        check(self._lib.sdm_pose_set_templates(self._h, t.ctypes.data, t.shape[0], t.shape[1]))
+
+    def pose_templates_from_landmarks(self, landmark_index: Sequence[int], focal: float):
+        """Templates of every row of the LANDMARK state (e.g. after ``detect_batch``), gathered and normalised by each row's
+        image centre on the device."""
+        idx = np.ascontiguousarray(landmark_index, np.int32)
+        check(self._lib.sdm_pose_templates_from_landmarks(self._h, idx.ctypes.data, idx.size, float(focal)))
+
+    def pose_set_targets(self, xstar: np.ndarray):
+        xs = np.ascontiguousarray(xstar, np.float32)
+        check(self._lib.sdm_pose_set_targets(self._h, xs.ctypes.data, xs.shape[0]))
+
+    def pose_features(self, level: int = 0) -> np.ndarray:
+        out = np.empty((self.pose_N, 2 * self.pose_K), np.float32)
+        check(self._lib.sdm_pose_features(self._h, level, out.ctypes.data))
+        return out
+
+    def pose_train_level(self, level: int, reg_type: int, reg_param: float, regularise_last_row: bool):
+        """One training level on the device; returns (R (2K x 6), lambda).  x becomes x_{k+1}."""
+        R = np.empty((2 * self.pose_K, 6), np.float32)
+        lam = ctypes.c_float(0.0)
+        check(self._lib.sdm_pose_train_level(self._h, level, int(reg_type), float(reg_param), int(bool(regularise_last_row)),
+                                             R.ctypes.data, ctypes.byref(lam)))
+        return R, lam.value
+
+    def pose_set_regressor(self, level: int, R: np.ndarray):
+        R = np.ascontiguousarray(R, np.float32)
+        if R.shape != (2 * self.pose_K, 6):
+            raise ValueError(f"pose regressor must be {2 * self.pose_K} x 6")
+        check(self._lib.sdm_pose_set_regressor(self._h, level, R.ctypes.data))
+
+    def pose_get_regressor(self, level: int) -> np.ndarray:
+        out = np.empty((2 * self.pose_K, 6), np.float32)
+        check(self._lib.sdm_pose_get_regressor(self._h, level, out.ctypes.data))
+        return out
+
+    def pose_test(self, first_level: int, n_levels: int):
+        """Levels first_level .. first_level + n_levels - 1 in one launch."""
+        check(self._lib.sdm_pose_test(self._h, first_level, n_levels))
+
     # -- misc ------------------------------------------------------------------------------------------
     def synchronize(self):
         check(self._lib.sdm_synchronize(self._h))
@@ -641,6 +712,78 @@ class HogTransform:
         self.img_index = img_index
 
 
+def _mat4_mul(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """Batched 4 x 4 product (..., 4, 4) in float32, every entry summed k = 0..3 in order (the device kernel's order)."""
+    c = np.empty(np.broadcast_shapes(a.shape, b.shape), np.float32)
+    for i in range(4):
+        for j in range(4):
+            c[..., i, j] = a[..., i, 0] * b[..., 0, j] + a[..., i, 1] * b[..., 1, j] + a[..., i, 2] * b[..., 2, j] + a[..., i, 3] * b[..., 3, j]
+    return c
+
+
+class ModelProjection:
+    """The ModelProjection function object of the reference's examples/pose_estimation.cpp:187-240: projects a 3D model with the
+    6-DOF parameters x = [r_x, r_y, r_z, t_x, t_y, t_z] (degrees) through a pinhole camera and returns the normalised 2D points
+    [u_0..u_{K-1}, v_0..v_{K-1}].
+
+    ``model``: 4 x K homogeneous points as in the example (:257-267), or 3 x K.  The camera defaults are the example's (focal
+    1800, a 1000 x 1000 screen, near 1, far 5000); u and v do not depend on them (the field of view is derived from the focal
+    length, :46), which is why landmarks in any image can be normalised by their own image centre (``estimate_pose``).
+    Passed to :class:`SupervisedDescentOptimiser` the cascade runs on the device (csrc/sdm_pose.hip); ``__call__`` is the host
+    evaluation (float32) users synthesise training data with (:305-309)."""
+
+    def __init__(self, model, focal: float = 1800.0, width: float = 1000.0, height: float = 1000.0, near: float = 1.0,
+                 far: float = 5000.0):
+        m = np.asarray(model, np.float32)
+        if m.ndim != 2 or m.shape[0] not in (3, 4) or not 1 <= m.shape[1] <= 64:
+            raise ValueError("the model must be 4 x K (homogeneous) or 3 x K, 1 <= K <= 64")
+        self.points = np.ascontiguousarray(m[:3].T)                      # K x 3
+        self.focal, self.width, self.height, self.near, self.far = (float(v) for v in (focal, width, height, near, far))
+
+    @property
+    def K(self) -> int:
+        return self.points.shape[0]
+
+    def projection_matrix(self) -> np.ndarray:
+        """createPerspectiveProjectionMatrix (:142-154) with fovy = focalLengthToFovy (:46), in float32."""
+        f32 = np.float32
+        fovy = (f32(2.0) * np.arctan2(f32(self.height), f32(2.0) * f32(self.focal))) * f32(180 / np.pi)
+        rad = (fovy / f32(2.0)) * f32(np.pi) / f32(180.0)
+        cotan = np.cos(rad) / np.sin(rad)
+        aspect = f32(self.width) / f32(self.height)
+        n, fa = f32(self.near), f32(self.far)
+        P = np.zeros((4, 4), np.float32)
+        P[0, 0], P[1, 1] = cotan / aspect, cotan
+        P[2, 2], P[2, 3] = -(n + fa) / (fa - n), (f32(-2.0) * n * fa) / (fa - n)
+        P[3, 2] = -1.0
+        return P
+
+    def __call__(self, parameters, regressor_level: int = 0, training_index: int = 0) -> np.ndarray:
+        """1 x 6 (or N x 6) parameters -> 1 x 2K (N x 2K) normalised projections.  regressor_level / training_index are not
+        used, as in the example."""
+        x = np.atleast_2d(np.asarray(parameters, np.float32))
+        if x.shape[1] != 6:
+            raise ValueError("parameters must be rows [r_x, r_y, r_z, t_x, t_y, t_z]")
+        f32, n = np.float32, x.shape[0]
+        d2r = f32(np.pi / 180)
+        c, s = np.cos(x[:, :3] * d2r), np.sin(x[:, :3] * d2r)
+        one, zero = np.ones(n, np.float32), np.zeros(n, np.float32)
+        mk = lambda *rows: np.stack([np.stack(r, -1) for r in rows], -2)   # noqa: E731
+        T = mk((one, zero, zero, x[:, 3]), (zero, one, zero, x[:, 4]), (zero, zero, one, x[:, 5]), (zero, zero, zero, one))
+        Ry = mk((c[:, 1], zero, s[:, 1], zero), (zero, one, zero, zero), (-s[:, 1], zero, c[:, 1], zero), (zero, zero, zero, one))
+        Rx = mk((one, zero, zero, zero), (zero, c[:, 0], -s[:, 0], zero), (zero, s[:, 0], c[:, 0], zero), (zero, zero, zero, one))
+        Rz = mk((c[:, 2], -s[:, 2], zero, zero), (s[:, 2], c[:, 2], zero, zero), (zero, zero, one, zero), (zero, zero, zero, one))
+        mvp = _mat4_mul(self.projection_matrix()[None], _mat4_mul(_mat4_mul(_mat4_mul(T, Ry), Rx), Rz))
+        X, Y, Z = (self.points[:, k][None, :] for k in range(3))
+        clip = [mvp[:, r, 0:1] * X + mvp[:, r, 1:2] * Y + mvp[:, r, 2:3] * Z + mvp[:, r, 3:4] for r in (0, 1, 3)]
+        nx, ny = clip[0] / clip[2], clip[1] / clip[2]
+        hw, hh = f32(self.width) / f32(2.0), f32(self.height) / f32(2.0)
+        x_ss = (nx + f32(1.0)) * hw
+        y_ss = f32(self.height) - (ny + f32(1.0)) * hh
+        u, v = (x_ss - hw) / f32(self.focal), (y_ss - hh) / f32(self.focal)
+        return np.concatenate([u, v], axis=1).astype(np.float32)
+
+
 class SupervisedDescentOptimiser:
     """superviseddescent.hpp:85-361 for RegressorType = LinearRegressor and ProjectionFunction =
     HogTransform: the per-level work runs as batched HIP kernels.
@@ -689,6 +832,10 @@ class SupervisedDescentOptimiser:
         ``rccl`` (a ``parallel.RcclCommunicator``) takes the place of all three callbacks: the library then issues the collectives
         itself through RCCL on its own streams (``rccl_shard_solve``: sharded factorisation + reduce-scatter exchange); the
         callbacks remain for backends without RCCL (the gloo tests)."""
+        if isinstance(projection, ModelProjection):
+            if allreduce is not None or rccl is not None or solve_collectives is not None or reduce_scatter is not None:
+                raise ValueError("pose training runs on one device")
+            return self._pose_train(parameters, initialisations, templates, projection, on_training_epoch_callback)
         x0 = np.asarray(initialisations, np.float32)
         self._bind(projection, x0.shape[0])
         c = self.ctx
@@ -763,6 +910,8 @@ class SupervisedDescentOptimiser:
 
     def test(self, initialisations, templates, projection: HogTransform,
              on_regressor_iteration_callback: Optional[Callable[[np.ndarray], None]] = None) -> np.ndarray:
+        if isinstance(projection, ModelProjection):
+            return self._pose_test(initialisations, templates, projection, on_regressor_iteration_callback)
         x0 = np.atleast_2d(np.asarray(initialisations, np.float32))
         self._bind(projection, x0.shape[0])
         self._load_regressors()
@@ -777,7 +926,58 @@ class SupervisedDescentOptimiser:
         return c.get_x()
 
     def predict(self, initialisation, templates, projection: HogTransform) -> np.ndarray:
+        if isinstance(projection, ModelProjection):
+            return self.test(np.atleast_2d(initialisation), np.atleast_2d(templates), projection)
         return self.test(np.atleast_2d(initialisation), templates, projection)  # :323-344
+
+    # -- ModelProjection (examples/pose_estimation.cpp): known-template SDM, NoNormalisation, on csrc/sdm_pose.hip ------------------
+    def _pose_bind(self, projection: "ModelProjection", ctx=None):
+        if self.normalisation is not None:
+            raise TypeError("the pose cascade takes no normalisation (NoNormalisation, pose_estimation.cpp:285)")
+        if not 1 <= len(self.regressors) <= 16:
+            raise ValueError("the pose cascade runs 1 ... 16 regressor levels")
+        c = ctx or self.ctx
+        c.pose_set_model(projection.points, projection.focal, projection.width, projection.height, projection.near, projection.far)
+        return c
+
+    def _pose_train(self, parameters, initialisations, templates, projection, on_training_epoch_callback):
+        if templates is None or np.size(templates) == 0:
+            raise ValueError("the pose cascade is a known-template SDM: pass the observed landmarks as templates")
+        c = self._pose_bind(projection)
+        for reg in self.regressors:
+            if getattr(reg.solver, "kind", 0) != 0:
+                raise TypeError("the device pose path solves with PartialPivLUSolver (the LU family)")
+        c.pose_set_x(np.asarray(initialisations, np.float32))
+        c.pose_set_templates(np.asarray(templates, np.float32))
+        c.pose_set_targets(np.asarray(parameters, np.float32))
+        for level, reg in enumerate(self.regressors):
+            r = reg.regulariser
+            reg.x, reg.last_lambda = c.pose_train_level(level, r.regularisation_type, r.param, r.regularise_last_row)   # :170-216
+            if on_training_epoch_callback is not None:
+                on_training_epoch_callback(c.pose_get_x())                   # :217
+        return c.pose_get_x()
+
+    def _pose_upload(self, c):
+        for level, reg in enumerate(self.regressors):
+            if reg.x is None:
+                raise RuntimeError("regressor level %d has not been learned" % level)
+            c.pose_set_regressor(level, reg.x)
+
+    def _pose_test(self, initialisations, templates, projection, on_regressor_iteration_callback=None):
+        if templates is None or np.size(templates) == 0:
+            raise ValueError("the pose cascade is a known-template SDM: pass the observed landmarks as templates")
+        c = self._pose_bind(projection)
+        self._pose_upload(c)
+        c.pose_set_x(np.atleast_2d(np.asarray(initialisations, np.float32)))
+        c.pose_set_templates(np.atleast_2d(np.asarray(templates, np.float32)))
+        n = len(self.regressors)
+        if on_regressor_iteration_callback is None:
+            c.pose_test(0, n)                                                # all levels in one launch
+        else:
+            for level in range(n):
+                c.pose_test(level, 1)                                        # (the same kernel per level: same bits)
+                on_regressor_iteration_callback(c.pose_get_x())              # superviseddescent.hpp:303
+        return c.pose_get_x()
 
 
 class detection_model:
@@ -820,6 +1020,30 @@ class detection_model:
         hog = HogTransform(images, self.hog_params, self.landmark_ids, self.right_eye_ids, self.left_eye_ids,
                            img_index)
         return self.optimised_model.test(init, None, hog)
+
+    def estimate_pose(self, pose_model: SupervisedDescentOptimiser, projection: ModelProjection, landmark_ids: Sequence[str],
+                      focal: Optional[float] = None, initialisation=None) -> np.ndarray:
+        """Head pose of every face of the last ``detect_batch`` (N x 6, [r_x, r_y, r_z, t_x, t_y, t_z]) without taking the
+        landmarks off the device: the K landmarks named by ``landmark_ids`` (ids of this model, one per model point of
+        ``projection``, in its order) are gathered from the detect state and normalised by each row's image centre and ``focal``
+        (default: the projection's), then ``pose_model``'s trained cascade runs on them.  ``initialisation``: one parameter row
+        for every face (default [0, 0, 0, 0, 0, -2000], examples/pose_estimation.cpp:329-330)."""
+        c = self.optimised_model.ctx
+        missing = [i for i in landmark_ids if str(i) not in self.landmark_ids]
+        if missing:
+            raise ValueError(f"landmark ids not in this model: {missing}")
+        idx = [self.landmark_ids.index(str(i)) for i in landmark_ids]
+        if len(idx) != projection.K:
+            raise ValueError("one landmark id per model point of the projection expected")
+        if not getattr(c, "N", 0):
+            raise RuntimeError("run detect_batch first")
+        pose_model._pose_bind(projection, c)
+        c.pose_templates_from_landmarks(idx, projection.focal if focal is None else focal)
+        x0 = np.array([0, 0, 0, 0, 0, -2000], np.float32) if initialisation is None else np.asarray(initialisation, np.float32).reshape(6)
+        c.pose_set_x(np.tile(x0, (c.N, 1)))
+        pose_model._pose_upload(c)
+        c.pose_test(0, len(pose_model.regressors))
+        return c.pose_get_x()
 
     def get_mean(self) -> np.ndarray:
         return self.mean
