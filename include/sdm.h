@@ -361,6 +361,56 @@ int sdm_pose_get_regressor(sdm_ctx* ctx, int level, float* R_host);
  * a row's result is bit-identical whatever the batch and whether the levels run in one call or one call each. */
 int sdm_pose_test(sdm_ctx* ctx, int first_level, int n_levels);
 
+/* Multi-stream face tracking: rcr::detection_model::detect(image, initialisation) (include/rcr/model.hpp:146-157) frame after frame
+ * for many faces at once, the loop apps/rcr/rcr-track.cpp:133-177 sketches.  The handle holds a table of `capacity` stream slots in
+ * HBM: per slot the landmark row (2L floats, the layout of x), the face box it was started from and a status.  A step runs the
+ * cascade of sdm_detect_batch, unchanged, on n rows taken from the slots, and writes the results back into them: a stream's
+ * landmarks never leave the device between frames.  Row i of a step belongs to stream ids[i], its image is the current image
+ * set's entry for row i (sdm_set_sample_image_index; identity by default) -- several faces in one frame are several streams on
+ * the same image.  After a step the current rows x are the step's results in ids order, as after sdm_detect_batch: sdm_get_x,
+ * sdm_pose_templates_from_landmarks and the other entry points of the landmark state see them.
+ *   init of row i   STARTED slot (sdm_track_start since its last step): align_mean(mean, box), bit-identical to
+ *                   sdm_init_from_boxes, so the first step equals sdm_detect_batch from the box;
+ *                   SDM_TRACK_INIT_PREVIOUS: the slot's landmarks (detect(image, initialisation));
+ *                   SDM_TRACK_INIT_REALIGN: the mean in the enclosing box of the slot's landmarks, float32, every operation rounded:
+ *                   x0_j = ((m_j - min m_x) / (max m_x - min m_x)) * (max x - min x) + min x, y the same with the y quantities
+ *   lost rule       bit mask of the result row, 0 = tracked (SDM_TRACK_LOST_*):
+ *                   NONFINITE  a coordinate is not finite (then no other bit is evaluated)
+ *                   SMALL      the enclosing box is narrower or lower than min_size pixels
+ *                   OUTSIDE    the box centre ((x0 + x1) * 0.5f, (y0 + y1) * 0.5f) lies outside [0, W) x [0, H) of the row's image
+ *                   SCALE      eye landmarks set and max_scale_change > 0: IED(result) > IED(init) * k or IED(result) * k < IED(init),
+ *                              in double (get_ied, include/rcr/helpers.hpp:136-160)
+ *                   A slot with a non-zero mask becomes LOST: it keeps its last landmarks and is refused by later steps until
+ *                   sdm_track_start gives it a new box (rcr-track.cpp's have_face = false -> face detector -> restart).
+ * Argument errors (SDM_ERR_INVALID) change no state and launch nothing: no geometry, a level without regressor, tracker not
+ * configured, the geometry's L changed since sdm_track_configure, n < 1, an id out of range or repeated within the call, a step
+ * on a FREE or LOST slot, templates set (sdm_set_templates), or images that do not cover the n rows. */
+#define SDM_TRACK_FREE 0
+#define SDM_TRACK_STARTED 1
+#define SDM_TRACK_TRACKED 2
+#define SDM_TRACK_LOST 3
+#define SDM_TRACK_INIT_PREVIOUS 0
+#define SDM_TRACK_INIT_REALIGN 1
+#define SDM_TRACK_LOST_NONFINITE 1
+#define SDM_TRACK_LOST_SMALL 2
+#define SDM_TRACK_LOST_OUTSIDE 4
+#define SDM_TRACK_LOST_SCALE 8
+/* capacity >= 1 slots, all FREE; mean: 2L floats in the unit box (the model's mean, width and height > 0); init_mode
+ * SDM_TRACK_INIT_*; min_size >= 0 pixels; max_scale_change >= 0 (0: no scale rule).  Needs the geometry; drops every slot. */
+int sdm_track_configure(sdm_ctx* ctx, int capacity, const float* mean, int init_mode, float min_size, float max_scale_change);
+/* (Re)start slots from face boxes (n x {x, y, width, height} ints, width and height > 0), whatever their status: STARTED. */
+int sdm_track_start(sdm_ctx* ctx, const int* ids, const int* boxes, int n);
+/* Slots become FREE (host bookkeeping only, nothing is launched). */
+int sdm_track_stop(sdm_ctx* ctx, const int* ids, int n);
+/* One frame for n STARTED or TRACKED streams: gather + init -> the cascade of sdm_detect_batch -> commit + lost rule.  One copy
+ * of the ids to the device, one of the masks (and of the n x 2L results when landmarks_host is given) back, one synchronise.
+ * landmarks_host (n x 2L) and lost_host (n masks) may be NULL.  SDM_ERR_EMPTY_PATCH as sdm_get_x reports it, after the step has
+ * been committed. */
+int sdm_track_step(sdm_ctx* ctx, const int* ids, int n, float* landmarks_host, int* lost_host);
+/* The slots' landmark rows (n x 2L; a STARTED slot gives its align_mean(mean, box)) and statuses (SDM_TRACK_FREE ...); either
+ * output may be NULL.  The current rows x are not touched. */
+int sdm_track_get(sdm_ctx* ctx, const int* ids, int n, float* landmarks_host, int* status_host);
+
 #ifdef __cplusplus
 }
 #endif

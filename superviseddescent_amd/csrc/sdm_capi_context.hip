@@ -75,6 +75,7 @@ void sdm_destroy(sdm_ctx* c)
     c->cells.release(); c->qr_work.release();
     c->Rmax.release();
     c->pose.release();
+    c->track.release();
     for (auto& r : c->Rt) r.release();
     for (auto& q : c->plans) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); }
     if (c->own_stream) e = hipStreamDestroy(c->stream);

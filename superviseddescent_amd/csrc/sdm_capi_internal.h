@@ -4,7 +4,7 @@
 // device sdm_create() fails.
 //   sdm_capi_context.hip   lifetime, geometry, images, samples            sdm_capi_detect.hip    features, regressors, apply, detect
 //   sdm_capi_train.hip     targets, Gram / right-hand side, solvers       sdm_capi_exchange.hip  the several-GPU exchange of the normal equations
-//   sdm_capi_debug.hip     device pointers, timing, debug entry points
+//   sdm_capi_debug.hip     device pointers, timing, debug entry points   sdm_capi_pose.hip / sdm_capi_track.hip  head pose, tracking
 #pragma once
 #include "../../include/sdm.h"
 #include "sdm_kernels.h"
@@ -220,6 +220,32 @@ struct sdm_ctx {
         DevBuf<int> lm;                    // landmark index map of the gather
         void release() { pts.release(); x.release(); xstar.release(); tmpl.release(); R.release(); Ab.release(); partial.release(); G.release(); lm.release(); }
     } pose;
+
+    // multi-stream tracking (sdm_capi_track.hip): a table of S stream slots beside the landmark state; a step gathers its rows into
+    // x, runs the detect cascade and commits the results back, so that a stream's landmarks stay in HBM between frames
+    struct Track {
+        int S = 0;                         // capacity; 0: not configured
+        int L = 0;                         // landmarks of the geometry at sdm_track_configure
+        int mode = 0;                      // SDM_TRACK_INIT_*
+        float min_size = 0.f, max_scale = 0.f;
+        float mean_bounds[4] = {0.f, 0.f, 0.f, 0.f};    // min, max of the mean's x; min, max of its y
+        DevBuf<float> mean;                // 2L
+        DevBuf<float> x;                   // S x 2L slot landmarks
+        DevBuf<int> box, status;           // S x 4 start boxes, S device statuses (read by the gather: STARTED or not)
+        DevBuf<float> init;                // n x 2L: the rows the cascade started from (the scale rule), scratch of sdm_track_get
+        DevBuf<int> ids, masks;            // n ids; n masks + the kernel status word
+        std::vector<int> host_status;      // mirror of the slots' statuses, refreshed from the masks every step
+        std::vector<unsigned> seen;        // per slot: stamp of the last call that named it (duplicate check)
+        unsigned stamp = 0;
+        int* pin = nullptr;                // pinned staging of the ids / boxes in and the masks out
+        size_t pin_cap = 0;                // ints
+        void release()
+        {
+            mean.release(); x.release(); box.release(); status.release(); init.release(); ids.release(); masks.release();
+            if (pin) { hipError_t e = hipHostFree(pin); (void)e; }
+            pin = nullptr; pin_cap = 0; S = 0;
+        }
+    } track;
 
     // timing
     bool timing = false;

@@ -1,0 +1,191 @@
+// sdm_capi_track.hip -- C-ABI of multi-stream face tracking (include/sdm.h, sdm_track_*): a table of stream slots in sdm_ctx::track,
+// and a step that gathers n slots into the landmark state x, runs the detect cascade of sdm_detect_batch on them, and commits the
+// results back with the lost decision (csrc/sdm_track.hip).  Every argument is checked before anything is launched.
+#include "sdm_capi_internal.h"
+
+#include <algorithm>
+#include <cmath>
+
+namespace {
+
+int track_ready(sdm_ctx* c)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    if (c->track.S < 1) return fail(SDM_ERR_INVALID, "tracker not configured (sdm_track_configure)");
+    if (c->L != c->track.L) return fail(SDM_ERR_INVALID, "the geometry's landmark count changed since sdm_track_configure");
+    return SDM_OK;
+}
+
+// ids in [0, S), none twice within the call
+int check_ids(sdm_ctx* c, const int* ids, int n)
+{
+    sdm_ctx::Track& t = c->track;
+    if (!ids || n < 1) return fail(SDM_ERR_INVALID, "no stream ids (n >= 1)");
+    if (++t.stamp == 0) { std::fill(t.seen.begin(), t.seen.end(), 0u); t.stamp = 1; }
+    for (int i = 0; i < n; ++i) {
+        if (ids[i] < 0 || ids[i] >= t.S) return fail(SDM_ERR_INVALID, "stream id " + std::to_string(ids[i]) + " out of range");
+        if (t.seen[ids[i]] == t.stamp) return fail(SDM_ERR_INVALID, "stream id " + std::to_string(ids[i]) + " named twice in one call");
+        t.seen[ids[i]] = t.stamp;
+    }
+    return SDM_OK;
+}
+
+int ensure_pinned(sdm_ctx::Track& t, size_t n_ints)
+{
+    if (n_ints <= t.pin_cap) return SDM_OK;
+    if (t.pin) { HIP_TRY(hipHostFree(t.pin)); t.pin = nullptr; t.pin_cap = 0; }
+    HIP_TRY(hipHostMalloc((void**)&t.pin, n_ints * sizeof(int), hipHostMallocDefault));
+    t.pin_cap = n_ints;
+    return SDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdm_track_configure(sdm_ctx* c, int capacity, const float* mean, int init_mode, float min_size, float max_scale_change)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    if (c->L <= 0) return fail(SDM_ERR_INVALID, "geometry not set");
+    if (capacity < 1) return fail(SDM_ERR_INVALID, "capacity must be >= 1");
+    if (!mean) return fail(SDM_ERR_INVALID, "no mean shape");
+    if (init_mode != SDM_TRACK_INIT_PREVIOUS && init_mode != SDM_TRACK_INIT_REALIGN) return fail(SDM_ERR_INVALID, "unknown init mode");
+    if (!(min_size >= 0.f) || !std::isfinite(min_size)) return fail(SDM_ERR_INVALID, "min_size must be finite and >= 0");
+    if (!(max_scale_change >= 0.f) || !std::isfinite(max_scale_change)) return fail(SDM_ERR_INVALID, "max_scale_change must be finite and >= 0");
+    const int L = c->L, M = 2 * L;
+    float mb[4] = {mean[0], mean[0], mean[L], mean[L]};
+    for (int j = 0; j < L; ++j) {
+        if (!std::isfinite(mean[j]) || !std::isfinite(mean[L + j])) return fail(SDM_ERR_INVALID, "the mean shape is not finite");
+        mb[0] = std::min(mb[0], mean[j]); mb[1] = std::max(mb[1], mean[j]);
+        mb[2] = std::min(mb[2], mean[L + j]); mb[3] = std::max(mb[3], mean[L + j]);
+    }
+    if (!(mb[1] - mb[0] > 0.f) || !(mb[3] - mb[2] > 0.f)) return fail(SDM_ERR_INVALID, "the mean shape has no width or no height");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    sdm_ctx::Track& t = c->track;
+    int rc;
+    if ((rc = t.mean.ensure(M)) || (rc = t.x.ensure((size_t)capacity * M)) || (rc = t.box.ensure((size_t)capacity * 4)) ||
+        (rc = t.status.ensure((size_t)capacity)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(t.mean.p, mean, M * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(t.x.p, 0, (size_t)capacity * M * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(t.box.p, 0, (size_t)capacity * 4 * sizeof(int), c->stream));
+    HIP_TRY(hipMemsetAsync(t.status.p, 0, (size_t)capacity * sizeof(int), c->stream));     // SDM_TRACK_FREE
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    t.S = capacity; t.L = L; t.mode = init_mode; t.min_size = min_size; t.max_scale = max_scale_change;
+    memcpy(t.mean_bounds, mb, sizeof(mb));
+    t.host_status.assign(capacity, SDM_TRACK_FREE);
+    t.seen.assign(capacity, 0u); t.stamp = 0;
+    return SDM_OK;
+}
+
+int sdm_track_start(sdm_ctx* c, const int* ids, const int* boxes, int n)
+{
+    int rc = track_ready(c);
+    if (rc) return rc;
+    if ((rc = check_ids(c, ids, n))) return rc;
+    if (!boxes) return fail(SDM_ERR_INVALID, "no face boxes");
+    for (int i = 0; i < n; ++i)
+        if (boxes[4 * i + 2] <= 0 || boxes[4 * i + 3] <= 0) return fail(SDM_ERR_INVALID, "a face box needs width and height > 0");
+    sdm_ctx::Track& t = c->track;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = ensure_pinned(t, (size_t)5 * n)) || (rc = t.ids.ensure((size_t)5 * n))) return rc;
+    memcpy(t.pin, ids, (size_t)n * sizeof(int));
+    memcpy(t.pin + n, boxes, (size_t)4 * n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (size_t)5 * n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    sdm_launch_track_start(t.ids.p, t.ids.p + n, n, t.box.p, t.status.p, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));      // (the pinned staging is reused by the next call)
+    for (int i = 0; i < n; ++i) t.host_status[ids[i]] = SDM_TRACK_STARTED;
+    return SDM_OK;
+}
+
+int sdm_track_stop(sdm_ctx* c, const int* ids, int n)
+{
+    int rc = track_ready(c);
+    if (rc) return rc;
+    if ((rc = check_ids(c, ids, n))) return rc;
+    for (int i = 0; i < n; ++i) c->track.host_status[ids[i]] = SDM_TRACK_FREE;
+    return SDM_OK;
+}
+
+int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int* lost_host)
+{
+    int rc = track_ready(c);
+    if (rc) return rc;
+    sdm_ctx::Track& t = c->track;
+    if (c->levels.empty()) return fail(SDM_ERR_INVALID, "geometry not set");
+    for (size_t l = 0; l < c->levels.size(); ++l)
+        if (!c->have_R[l]) return fail(SDM_ERR_INVALID, "no regressor set for level " + std::to_string(l));
+    if ((rc = check_ids(c, ids, n))) return rc;
+    for (int i = 0; i < n; ++i) {
+        const int st = t.host_status[ids[i]];
+        if (st == SDM_TRACK_FREE) return fail(SDM_ERR_INVALID, "stream " + std::to_string(ids[i]) + " is not started");
+        if (st == SDM_TRACK_LOST) return fail(SDM_ERR_INVALID, "stream " + std::to_string(ids[i]) + " is lost: start it again from a face box");
+    }
+    if (c->tmpl_N > 0) return fail(SDM_ERR_INVALID, "templates are set: the tracker runs the cascade without (sdm_set_templates(NULL))");
+    if (!c->img_base || c->n_images < 1) return fail(SDM_ERR_INVALID, "no images set");
+    if (c->idx_identity && n > c->n_images) return fail(SDM_ERR_INVALID, "more rows than images and no sample->image index set");
+    if (!c->idx_identity && n > c->n_idx) return fail(SDM_ERR_INVALID, "sample->image index is shorter than the step's rows");
+    if (!c->idx_identity && c->max_idx >= c->n_images)
+        return fail(SDM_ERR_INVALID, "sample->image index refers to an image beyond the current image set");
+    HIP_TRY(hipSetDevice(c->device));
+    const int M = c->M;
+    if ((rc = ensure_sample_buffers(c, n)) || (rc = t.init.ensure((size_t)n * M)) || (rc = t.ids.ensure((size_t)n)) ||
+        (rc = t.masks.ensure((size_t)n + 1)) || (rc = ensure_pinned(t, (size_t)2 * n + 1)))
+        return rc;
+    // the rows become the current x, as after sdm_set_x + sdm_detect_batch
+    if (n != c->N) { c->have_targets = false; c->feat_level = -1; c->have_patch_idx = false; }
+    c->N = n; c->cur = 0;
+    memcpy(t.pin, ids, (size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    sdm_launch_track_gather(t.ids.p, n, c->L, t.mode, t.status.p, t.box.p, t.x.p, t.mean.p, t.mean_bounds, c->x[0].p, t.init.p, c->stream);
+    HIP_TRY(hipGetLastError());
+    // the cascade: exactly sdm_detect_batch's level sequence (fused or unfused per level)
+    c->chain_timers = true; c->ev_fresh = false;
+    for (int l = 0; l < (int)c->levels.size() && !rc; ++l) rc = detect_level(c, l);
+    c->chain_timers = false; c->ev_fresh = false;
+    if (rc) return rc;
+    sdm_launch_track_commit(t.ids.p, n, c->L, c->x[c->cur].p, t.init.p, c->idx_identity ? nullptr : c->img_idx.p, c->img_w.p, c->img_h.p,
+                            c->eyes, t.min_size, t.max_scale, t.x.p, t.status.p, t.masks.p, c->status.p, c->stream);
+    HIP_TRY(hipGetLastError());
+    int* masks = t.pin + n;
+    HIP_TRY(hipMemcpyAsync(masks, t.masks.p, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (landmarks_host)
+        HIP_TRY(hipMemcpyAsync(landmarks_host, c->x[c->cur].p, (size_t)n * M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; ++i) t.host_status[ids[i]] = masks[i] ? SDM_TRACK_LOST : SDM_TRACK_TRACKED;
+    if (lost_host) memcpy(lost_host, masks, (size_t)n * sizeof(int));
+    const int st = masks[n];
+    if (st) {
+        HIP_TRY(hipMemsetAsync(c->status.p, 0, sizeof(int), c->stream));
+        if (st & SDM_DEV_ERR_EMPTY_PATCH)
+            return fail(SDM_ERR_EMPTY_PATCH, "patch_width_half <= 0 for at least one row (inter-eye distance too small)");
+        return fail(SDM_ERR_HIP, "a kernel reported status " + std::to_string(st));
+    }
+    return SDM_OK;
+}
+
+int sdm_track_get(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int* status_host)
+{
+    int rc = track_ready(c);
+    if (rc) return rc;
+    if ((rc = check_ids(c, ids, n))) return rc;
+    sdm_ctx::Track& t = c->track;
+    if (landmarks_host) {
+        HIP_TRY(hipSetDevice(c->device));
+        if ((rc = t.init.ensure((size_t)n * c->M)) || (rc = t.ids.ensure((size_t)n)) || (rc = ensure_pinned(t, (size_t)n))) return rc;
+        memcpy(t.pin, ids, (size_t)n * sizeof(int));
+        HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        sdm_launch_track_gather(t.ids.p, n, c->L, SDM_TRACK_INIT_PREVIOUS, t.status.p, t.box.p, t.x.p, t.mean.p, t.mean_bounds, t.init.p,
+                                nullptr, c->stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(landmarks_host, t.init.p, (size_t)n * c->M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (status_host)
+        for (int i = 0; i < n; ++i) status_host[i] = t.host_status[ids[i]];
+    return SDM_OK;
+}
+
+}  // extern "C"

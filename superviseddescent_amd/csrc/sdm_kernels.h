@@ -324,3 +324,14 @@ void sdm_launch_pose_solve(const double* G, int F, int T, int reg_type, float pa
                            float* lambda_out, hipStream_t s);
 void sdm_launch_pose_gather(const float* xl, int L, int N, const int* lm, int K, const int* img_idx, const int* img_w, const int* img_h,
                             float f, float* tmpl, hipStream_t s);
+
+// ---- multi-stream tracking (sdm_track.hip): the hand-offs between the slot table and the detect cascade's state x ----
+// slot table: slot_x S x 2L, slot_box S x 4 (x, y, w, h), slot_status S (SDM_TRACK_*, include/sdm.h)
+void sdm_launch_track_start(const int* ids, const int* boxes, int n, int* slot_box, int* slot_status, hipStream_t s);
+// x (and init, when not null): n x 2L; mean_bounds = {min, max of the mean's x, min, max of its y}
+void sdm_launch_track_gather(const int* ids, int n, int L, int mode, const int* slot_status, const int* slot_box, const float* slot_x,
+                             const float* mean, const float mean_bounds[4], float* x, float* init, hipStream_t s);
+// masks: n + 1 ints, masks[n] = *status_word (the context's kernel status, read behind the cascade)
+void sdm_launch_track_commit(const int* ids, int n, int L, const float* x, const float* init, const int* img_idx, const int* img_w,
+                             const int* img_h, const EyeIdxDev& eyes, float min_size, float max_scale_change, float* slot_x,
+                             int* slot_status, int* masks, const int* status_word, hipStream_t s);

@@ -11,6 +11,7 @@ Class and method names follow the reference so that the parity tests read like i
 ``SupervisedDescentOptimiser.train/test/predict``  include/superviseddescent/superviseddescent.hpp:165-344
 ``detection_model.detect``                     include/rcr/model.hpp:122-183
 ``ModelProjection``                            examples/pose_estimation.cpp:187-240 (head pose, csrc/sdm_pose.hip)
+``detection_model.tracker`` / ``Tracker``       apps/rcr/rcr-track.cpp:133-177 (multi-stream tracking, csrc/sdm_track.hip)
 =============================================  =====================================================
 
 Everything numeric happens on the MI355X: HOG extraction, regressor apply, Gram/RHS build and the
@@ -480,6 +481,48 @@ class Context:
     def pose_test(self, first_level: int, n_levels: int):
         """Levels first_level .. first_level + n_levels - 1 in one launch."""
         check(self._lib.sdm_pose_test(self._h, first_level, n_levels))
+
+    # -- multi-stream tracking (csrc/sdm_track.hip) ---------------------------------------------------
+    @staticmethod
+    def _ids(ids) -> np.ndarray:
+        return np.ascontiguousarray(np.atleast_1d(np.asarray(ids)), np.int32).reshape(-1)
+
+    def track_configure(self, capacity: int, mean: np.ndarray, init_mode: int, min_size: float, max_scale_change: float):
+        m = np.ascontiguousarray(mean, np.float32).reshape(-1)
+        if m.size != 2 * self.L:
+            raise ValueError("the mean must hold 2L coordinates")
+        check(self._lib.sdm_track_configure(self._h, int(capacity), m.ctypes.data, int(init_mode), float(min_size),
+                                            float(max_scale_change)))
+
+    def track_start(self, ids, boxes: np.ndarray):
+        i = self._ids(ids)
+        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        if b.shape[0] != i.size:
+            raise ValueError("one face box (x, y, w, h) per stream id expected")
+        check(self._lib.sdm_track_start(self._h, i.ctypes.data, b.ctypes.data, i.size))
+
+    def track_stop(self, ids):
+        i = self._ids(ids)
+        check(self._lib.sdm_track_stop(self._h, i.ctypes.data, i.size))
+
+    def track_step(self, ids, fetch: bool = True):
+        """One frame for the streams ``ids`` (row i of the current images belongs to ids[i]): returns (landmarks n x 2L or None,
+        lost masks n).  The rows are the current x afterwards."""
+        i = self._ids(ids)
+        out = np.empty((i.size, 2 * self.L), np.float32) if fetch else None
+        lost = np.empty(i.size, np.int32)
+        rc = self._lib.sdm_track_step(self._h, i.ctypes.data, i.size, out.ctypes.data if fetch else None, lost.ctypes.data)
+        if rc in (_lib.SDM_OK, _lib.SDM_ERR_EMPTY_PATCH):      # (the step was committed)
+            self.N = i.size
+        check(rc)
+        return out, lost
+
+    def track_get(self, ids):
+        i = self._ids(ids)
+        out = np.empty((i.size, 2 * self.L), np.float32)
+        st = np.empty(i.size, np.int32)
+        check(self._lib.sdm_track_get(self._h, i.ctypes.data, i.size, out.ctypes.data, st.ctypes.data))
+        return out, st
 
     # -- misc ------------------------------------------------------------------------------------------
     def synchronize(self):
@@ -1045,5 +1088,76 @@ class detection_model:
         c.pose_test(0, len(pose_model.regressors))
         return c.pose_get_x()
 
+    def tracker(self, capacity: int, init: str = "realign", min_size: float = 8.0, max_scale_change: float = 1.5) -> "Tracker":
+        """Multi-stream tracking on the optimiser's context: ``capacity`` stream slots whose landmarks stay on the device from
+        frame to frame (see :class:`Tracker`).  ``init``: how a tracked stream's next frame starts -- "previous" (its landmarks,
+        the reference's ``detect(image, initialisation)``) or "realign" (the mean shape in their enclosing box).  A stream is
+        lost when its result is not finite, its enclosing box is smaller than ``min_size`` pixels, the box centre leaves the
+        image, or its inter-eye distance changes by more than the factor ``max_scale_change`` in one step (0: no such rule)."""
+        return Tracker(self, capacity, init, min_size, max_scale_change)
+
     def get_mean(self) -> np.ndarray:
         return self.mean
+
+
+class Tracker:
+    """Faces followed through video, many streams at once (the loop the reference's apps/rcr/rcr-track.cpp:133-177 sketches):
+    ``start`` a stream from a face box, ``step`` the streams on their next frames, restart the ones reported lost from a new box.
+    The landmark state of every stream lives in a slot table on the device (include/sdm.h, sdm_track_*); a step runs
+    ``detect_batch``'s cascade on the stepped streams and leaves its rows as the context's current x, so ``estimate_pose``
+    works on tracked faces as on detected ones."""
+
+    _MODES = {"previous": _lib.SDM_TRACK_INIT_PREVIOUS, "realign": _lib.SDM_TRACK_INIT_REALIGN}
+
+    def __init__(self, model: detection_model, capacity: int, init: str = "realign", min_size: float = 8.0,
+                 max_scale_change: float = 1.5):
+        if init not in self._MODES:
+            raise ValueError('init must be "previous" or "realign"')
+        self.model, self.capacity, self.init = model, int(capacity), init
+        self._bind()
+        self.ctx.track_configure(self.capacity, model.mean, self._MODES[init], min_size, max_scale_change)
+
+    @property
+    def ctx(self) -> Context:
+        return self.model.optimised_model.ctx
+
+    def _bind(self):
+        """The model's geometry on the context (a no-op when it is already there) and its regressors (not uploaded again when the
+        device holds them: SupervisedDescentOptimiser._load_regressors)."""
+        m, opt = self.model, self.model.optimised_model
+        norm = opt.normalisation or InterEyeDistanceNormalisation(m.landmark_ids, m.right_eye_ids, m.left_eye_ids)
+        self.ctx.set_model_geometry(len(m.landmark_ids), norm.right_eye, norm.left_eye, m.hog_params)
+        opt._load_regressors()
+
+    def start(self, ids, boxes):
+        """(Re)start streams from face boxes (n x (x, y, w, h)), live or lost."""
+        self.ctx.track_start(ids, boxes)
+
+    def stop(self, ids):
+        self.ctx.track_stop(ids)
+
+    def step(self, ids, frames=None, image_index=None, fetch: bool = True):
+        """One frame for the streams ``ids``: row i belongs to stream ids[i] and reads frame ``image_index[i]`` (default i).
+        ``frames``: host images (a list or an n x H x W stack, uploaded), a uint8 n x H x W tensor on the device (used in place),
+        or None (the images already set on the context).  Returns (landmarks n x 2L -- None unless ``fetch`` --, lost masks n:
+        0 = tracked, else the SDM_TRACK_LOST_* bits)."""
+        c = self.ctx
+        self._bind()
+        if frames is not None:
+            if hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False):
+                if frames.dtype.itemsize != 1 or frames.dim() != 3 or not frames.is_contiguous():
+                    raise ValueError("device frames must be a contiguous uint8 n x H x W tensor")
+                import torch
+                torch.cuda.current_stream(frames.device).synchronize()      # (the library runs on its own stream)
+                n, h, w = (int(v) for v in frames.shape)
+                c.set_images_device(frames.data_ptr(), n, w, h, w)
+            else:
+                c.upload_images(frames)
+            self.model.optimised_model._bound = None                        # (the context's images are no longer a bound projection's)
+        c.set_templates(None)
+        c.set_sample_image_index(image_index)
+        return c.track_step(ids, fetch)
+
+    def get(self, ids):
+        """(landmarks n x 2L, status n: SDM_TRACK_FREE / STARTED / TRACKED / LOST) of the streams ``ids``."""
+        return self.ctx.track_get(ids)

@@ -240,6 +240,8 @@ public:
     cv::Mat get_mean() { return mean; }
     const std::vector<std::string>& get_landmark_ids() const { return landmark_ids; }
     const std::vector<rcr::HoGParam>& get_hog_params() const { return hog_params; }
+    const std::vector<std::string>& get_right_eye_ids() const { return right_eye_ids; }
+    const std::vector<std::string>& get_left_eye_ids() const { return left_eye_ids; }
     model_type& get_optimised_model() { return optimised_model; }
 
     template <class Archive>

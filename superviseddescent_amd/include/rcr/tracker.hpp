@@ -1,0 +1,115 @@
+// rcr/tracker.hpp -- multi-stream face tracking with the landmark state kept on the device (include/sdm.h, sdm_track_*): the loop
+// the reference's apps/rcr/rcr-track.cpp:133-177 sketches -- start a face from a detector box, follow it frame by frame with
+// detect(image, initialisation) (include/rcr/model.hpp:146-157), restart it from a new box once it is lost -- for many faces at
+// once, without the landmarks of a stream leaving the device between frames.
+//
+//     rcr::tracker tr(model, 64);                       // 64 stream slots, realign initialisation
+//     tr.start({0, 1}, {box_a, box_b});                 // boxes from a face detector
+//     auto lms = tr.step({0, 1}, {frame, frame});       // two faces in one frame: two streams on the same image
+//     if (tr.lost()[1]) tr.start({1}, {new_box});       // have_face = false -> detector -> restart
+#pragma once
+
+#ifndef RCR_TRACKER_HPP_
+#define RCR_TRACKER_HPP_
+
+#include "rcr/model.hpp"
+
+#include <stdexcept>
+#include <utility>
+#include <vector>
+
+namespace rcr {
+
+class tracker {
+public:
+    enum class init_mode { previous = SDM_TRACK_INIT_PREVIOUS, realign = SDM_TRACK_INIT_REALIGN };
+    enum status { free_slot = SDM_TRACK_FREE, started = SDM_TRACK_STARTED, tracked = SDM_TRACK_TRACKED, lost_slot = SDM_TRACK_LOST };
+
+    /** `capacity` stream slots on the device of superviseddescent::hip::device().  A stream is lost when its result is not finite,
+     *  its enclosing box is smaller than min_size pixels, the box centre leaves the image, or its inter-eye distance changes by more
+     *  than the factor max_scale_change in one step (0: no such rule).  The model's regressors are uploaded here, once. */
+    tracker(detection_model& model, int capacity, init_mode init = init_mode::realign, float min_size = 8.0f, float max_scale_change = 1.5f)
+        : model(model)
+    {
+        using superviseddescent::hip::check;
+        sdm_ctx* c = handle.get();
+        detail::configure(handle, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(),
+                          false);
+        auto& regressors = model.get_optimised_model().get_regressors();
+        if (regressors.size() != model.get_hog_params().size()) throw std::runtime_error("tracker: one regressor per HoGParam expected");
+        for (size_t level = 0; level < regressors.size(); ++level) {
+            cv::Mat R = regressors[level].x.isContinuous() ? regressors[level].x : regressors[level].x.clone();
+            if (R.empty() || R.rows != sdm_feature_dim(c, (int)level) || R.cols != 2 * num_landmarks())
+                throw std::runtime_error("tracker: the regressor of level " + std::to_string(level) + " does not match the HOG geometry");
+            check(sdm_set_regressor(c, (int)level, R.ptr<float>(0)), "sdm_set_regressor");
+        }
+        cv::Mat mean = model.get_mean().isContinuous() ? model.get_mean() : model.get_mean().clone();
+        if ((int)mean.total() != 2 * num_landmarks()) throw std::runtime_error("tracker: the mean must hold 2L coordinates");
+        check(sdm_track_configure(c, capacity, mean.ptr<float>(0), (int)init, min_size, max_scale_change), "sdm_track_configure");
+    }
+
+    /** (Re)start streams from face boxes, live or lost. */
+    void start(const std::vector<int>& ids, const std::vector<cv::Rect>& boxes)
+    {
+        if (ids.size() != boxes.size()) throw std::runtime_error("tracker::start: one box per stream id expected");
+        std::vector<int> b;
+        for (const auto& r : boxes) { b.push_back(r.x); b.push_back(r.y); b.push_back(r.width); b.push_back(r.height); }
+        superviseddescent::hip::check(sdm_track_start(handle.get(), ids.data(), b.data(), (int)ids.size()), "sdm_track_start");
+    }
+
+    void stop(const std::vector<int>& ids)
+    {
+        superviseddescent::hip::check(sdm_track_stop(handle.get(), ids.data(), (int)ids.size()), "sdm_track_stop");
+    }
+
+    /** One frame for the streams `ids`: row i belongs to stream ids[i] and reads frames[image_index[i]] (default: frames[i]).
+     *  Returns the landmarks of every row; lost() holds the rows' lost masks (0 = tracked, else SDM_TRACK_LOST_* bits) and rows()
+     *  the n x 2L result. */
+    std::vector<LandmarkCollection<cv::Vec2f>> step(const std::vector<int>& ids, const std::vector<cv::Mat>& frames,
+                                                    const std::vector<int>& image_index = {})
+    {
+        using superviseddescent::hip::check;
+        sdm_ctx* c = handle.get();
+        const int n = (int)ids.size();
+        detail::upload_images(handle, frames);
+        check(sdm_set_templates(c, nullptr, 0, 0), "sdm_set_templates");
+        if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+        else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+        cv::Mat rows(n, 2 * num_landmarks(), CV_32FC1);
+        std::vector<int> masks(ids.size());
+        check(sdm_track_step(c, ids.data(), n, rows.ptr<float>(0), masks.data()), "sdm_track_step");
+        last_rows = rows;
+        last_lost = masks;
+        return collections(rows);
+    }
+
+    /** The streams' landmarks (a started stream: its aligned mean) and statuses. */
+    std::pair<std::vector<LandmarkCollection<cv::Vec2f>>, std::vector<int>> get(const std::vector<int>& ids)
+    {
+        cv::Mat rows((int)ids.size(), 2 * num_landmarks(), CV_32FC1);
+        std::vector<int> st(ids.size());
+        superviseddescent::hip::check(sdm_track_get(handle.get(), ids.data(), (int)ids.size(), rows.ptr<float>(0), st.data()), "sdm_track_get");
+        return {collections(rows), st};
+    }
+
+    const std::vector<int>& lost() const { return last_lost; }
+    const cv::Mat& rows() const { return last_rows; }
+    sdm_ctx* context() const { return handle.get(); }
+
+private:
+    int num_landmarks() const { return (int)model.get_landmark_ids().size(); }
+    std::vector<LandmarkCollection<cv::Vec2f>> collections(const cv::Mat& rows) const
+    {
+        std::vector<LandmarkCollection<cv::Vec2f>> out;
+        for (int r = 0; r < rows.rows; ++r) out.push_back(to_landmark_collection(rows.row(r), model.get_landmark_ids()));
+        return out;
+    }
+
+    detection_model& model;
+    superviseddescent::hip::Handle handle;
+    cv::Mat last_rows;
+    std::vector<int> last_lost;
+};
+
+}  // namespace rcr
+#endif /* RCR_TRACKER_HPP_ */

@@ -43,7 +43,6 @@ def perturb(box, tx: float, ty: float, s: float = 1.0):
 
 def _face_chunk(rng, n: int, size: int):
     """One chunk of make_faces: (images [n,size,size] u8, boxes [n,4], gt68 [n,136]) drawn from ``rng``."""
-    coords = np.arange(size, dtype=np.float32)
     wh = rng.integers(160, 209, size=n)
     bx = (rng.random(n) * (size - wh)).astype(np.int32)
     by = (rng.random(n) * (size - wh)).astype(np.int32)
@@ -53,21 +52,34 @@ def _face_chunk(rng, n: int, size: int):
     gcy = rng.random((n, 6)).astype(np.float32) * size
     gsig = (12 + 28 * rng.random((n, 6))).astype(np.float32)
     gamp = (48 * (2 * rng.random((n, 6)) - 1)).astype(np.float32)
-    ex = np.exp(-0.5 * ((coords[None, None, :] - gcx[:, :, None]) / gsig[:, :, None]) ** 2)
-    ey = np.exp(-0.5 * ((coords[None, None, :] - gcy[:, :, None]) / gsig[:, :, None]) ** 2)
-    field = np.matmul((ey * gamp[:, :, None]).transpose(0, 2, 1), ex)          # [n, y, x]
+    field = _background(gcx, gcy, gsig, gamp, size)
     # landmark blobs at the ground-truth shape (rigid mean + 1.5 px jitter)
     gt68 = np.empty((n, 136), np.float32)
     for i in range(n):
         gt68[i] = align_mean(ibug.MEAN_IBUG_LFPW_68, boxes[i])
     gt68 += (1.5 * rng.standard_normal((n, 136))).astype(np.float32)
+    return _draw_faces(rng, field, gt68, size), boxes, gt68
+
+
+def _background(gcx, gcy, gsig, gamp, size: int):
+    """Smooth background of n faces [n, y, x] from their 6 Gaussians each (centres, sigmas, amplitudes)."""
+    coords = np.arange(size, dtype=np.float32)
+    ex = np.exp(-0.5 * ((coords[None, None, :] - gcx[:, :, None]) / gsig[:, :, None]) ** 2)
+    ey = np.exp(-0.5 * ((coords[None, None, :] - gcy[:, :, None]) / gsig[:, :, None]) ** 2)
+    return np.matmul((ey * gamp[:, :, None]).transpose(0, 2, 1), ex)          # [n, y, x]
+
+
+def _draw_faces(rng, field, gt68, size: int):
+    """Landmark blobs at gt68 [n, 136] on the background ``field`` (modified), per-pixel noise drawn from ``rng``, as u8 images."""
+    coords = np.arange(size, dtype=np.float32)
+    n = field.shape[0]
     lx, ly = gt68[:, :68], gt68[:, 68:]
     lamp = np.where(np.arange(68) % 2 == 0, 70.0, -70.0).astype(np.float32)
     bxk = np.exp(-0.5 * ((coords[None, None, :] - lx[:, :, None]) / 3.0) ** 2).astype(np.float32)
     byk = np.exp(-0.5 * ((coords[None, None, :] - ly[:, :, None]) / 3.0) ** 2).astype(np.float32)
     field += np.matmul((byk * lamp[None, :, None]).transpose(0, 2, 1), bxk)
     noise = (24 * (2 * rng.random((n, size, size), dtype=np.float32) - 1))
-    return np.clip(128 + field + noise, 0, 255).astype(np.uint8), boxes, gt68
+    return np.clip(128 + field + noise, 0, 255).astype(np.uint8)
 
 
 def make_faces(n_images: int, seed: int = SEED, size: int = IMAGE_SIZE, chunk: int = 256, workers: int = 0):
@@ -126,3 +138,51 @@ def make_samples(boxes: np.ndarray, gt68: np.ndarray, landmark_ids, n_perturb: i
             box = perturb(box, t[r, 0], t[r, 1], s[r])
         x0[r] = align_mean(mean_sel, box)
     return x_star, x0, img_index
+
+
+def make_tracks(n_streams: int, n_frames: int, seed: int = SEED + 7, size: int = IMAGE_SIZE):
+    """Synthetic video for the tracker: ``n_streams`` faces, each drawn as ``make_faces`` draws one (its own smooth background,
+    landmark blobs, fresh per-pixel noise every frame), whose box moves by up to 3 pixels and scales by up to 3 % per frame and
+    stays at least 10 pixels inside the frame together with every ground-truth landmark.  The boxes stand in for a face
+    detector.  Returns (frames uint8 [n_frames, n_streams, size, size], gt68 float32 [n_frames, n_streams, 136], boxes int32
+    [n_frames, n_streams, 4] (x, y, w, h)); stream s of frame t is image s of frames[t]."""
+    rng = np.random.default_rng(seed)
+    m = np.asarray(ibug.MEAN_IBUG_LFPW_68, np.float32)
+    margin = 10
+    # a box (x, y, w, w) keeps its landmarks inside [x + (0.5 + min m_x) w, ...] -- the mean reaches below the box (m_y up to 0.6)
+    lo_x, hi_x, lo_y, hi_y = (float(v) + 0.5 for v in (m[:68].min(), m[:68].max(), m[68:].min(), m[68:].max()))
+    w_max = int((size - 2 * margin - 10) / max(hi_x - lo_x, hi_y - lo_y, 1.0))
+
+    def clamp(x, y, w):
+        x = int(min(max(x, margin - lo_x * w), size - margin - hi_x * w))
+        y = int(min(max(y, margin - lo_y * w), size - margin - hi_y * w))
+        return x, y
+
+    w = rng.integers(136, 177, size=n_streams).astype(np.float64)
+    cx, cy = rng.random(n_streams), rng.random(n_streams)
+    gcx = rng.random((n_streams, 6)).astype(np.float32) * size
+    gcy = rng.random((n_streams, 6)).astype(np.float32) * size
+    gsig = (12 + 28 * rng.random((n_streams, 6))).astype(np.float32)
+    gamp = (48 * (2 * rng.random((n_streams, 6)) - 1)).astype(np.float32)
+    shape = np.clip(1.5 * rng.standard_normal((n_streams, 136)), -4.5, 4.5).astype(np.float32)   # each face's own shape
+    background = _background(gcx, gcy, gsig, gamp, size)
+    pos = np.empty((n_streams, 2))
+    for s in range(n_streams):
+        wi = int(w[s])
+        pos[s] = clamp(margin + cx[s] * (size - 2 * margin - wi), margin + cy[s] * (size - 2 * margin - wi), wi)
+    frames = np.empty((n_frames, n_streams, size, size), np.uint8)
+    gt68 = np.empty((n_frames, n_streams, 136), np.float32)
+    boxes = np.empty((n_frames, n_streams, 4), np.int32)
+    for t in range(n_frames):
+        if t > 0:
+            step = rng.uniform(-3.0, 3.0, (n_streams, 2))
+            scale = rng.uniform(0.97, 1.03, n_streams)
+        for s in range(n_streams):
+            if t > 0:
+                w[s] = min(max(w[s] * scale[s], 112.0), float(w_max))
+                pos[s] = clamp(pos[s, 0] + step[s, 0], pos[s, 1] + step[s, 1], int(w[s]))
+            box = (int(pos[s, 0]), int(pos[s, 1]), int(w[s]), int(w[s]))
+            boxes[t, s] = box
+            gt68[t, s] = align_mean(m, box) + shape[s]
+        frames[t] = _draw_faces(rng, background.copy(), gt68[t], size)
+    return frames, gt68, boxes
