@@ -411,6 +411,44 @@ int sdm_track_step(sdm_ctx* ctx, const int* ids, int n, float* landmarks_host, i
  * output may be NULL.  The current rows x are not touched. */
 int sdm_track_get(sdm_ctx* ctx, const int* ids, int n, float* landmarks_host, int* status_host);
 
+/* Aligned face crops of the current rows (after sdm_detect_batch, sdm_track_step or sdm_set_x): for every row n of x (N x 2L, what
+ * sdm_get_x returns) an out_width x out_height x C u8 crop in which the face stands in a canonical position -- the input of
+ * recognition, expression or attribute networks -- without the landmarks or the frames leaving the device.
+ *   fit     the least-squares similarity without reflection that maps the row's K landmarks p_k = (x[idx_k], x[L + idx_k]) onto
+ *           the template points q_k (crop pixel coordinates), in double: centre both sets, a = sum(p~.q~) / sum|p~|^2,
+ *           b = sum(p~x q~y - p~y q~x) / sum|p~|^2, t = q_bar - [[a, -b], [b, a]] p_bar (summation order free).  Its inverse, the crop
+ *           -> source matrix M (2 x 3), is [[a, b], [-b, a]] / (a^2 + b^2) with the translation p_bar - [[a, b], [-b, a]] q_bar /
+ *           (a^2 + b^2), rounded to float32.
+ *   sample  output pixel (column j, row i), integer coordinates at the pixel centres (the cv::warpAffine convention):
+ *           sx = (M00 j + M01 i) + M02, sy = (M10 j + M11 i) + M12 in float32, every operation rounded, nothing contracted.
+ *           X = floor(sx * 32 + 0.5f) in float32, x0 = X >> 5, fx = X & 31, y the same; per channel
+ *           (w00 p(x0, y0) + w10 p(x0 + 1, y0) + w01 p(x0, y0 + 1) + w11 p(x0 + 1, y0 + 1) + 512) >> 10 with w00 = (32 - fx)(32 - fy),
+ *           w10 = fx (32 - fy), w01 = (32 - fx) fy, w11 = fx fy.  A tap outside the image reads 0; a non-finite position, or one
+ *           with |sx| or |sy| > 2^20, gives 0.  Plain bilinear, no antialiasing.
+ *   flags   SDM_ALIGN_DEGENERATE: a selected landmark is not finite, or sum|p~|^2 == 0 -- the crop is all zeros, M six NaNs, and no
+ *           other bit is evaluated.  SDM_ALIGN_PARTIAL: a crop corner (column 0 or out_width - 1, row 0 or out_height - 1) samples
+ *           outside [0, W - 1] x [0, H - 1] of the row's image, on the float32 positions above.
+ *   source  default: the context's own images (single-channel, the ones detect and track read; sizes may differ; rows map to images
+ *           through sdm_set_sample_image_index as in detect).  sdm_align_set_source: a stack of n_images equally sized interleaved
+ *           u8 images of C in {1, 3, 4} channels, channel order kept (BGR stays BGR) -- e.g. the colour frames whose gray version the
+ *           cascade ran on.  In host memory it is copied once, here; in device memory (on_device) it is used in place and must stay
+ *           valid while crops are made from it.  base NULL: back to the context's images.
+ * Argument errors (SDM_ERR_INVALID) change no state and launch nothing: no geometry (sdm_set_model_geometry), no current rows, K
+ * outside [2, L], a landmark index out of range or repeated, a template point not finite or all K template points equal,
+ * out_width or out_height outside [1, 1024], out NULL (or, on the device, not 4-byte aligned; 16 when C = 4), channels outside
+ * {1, 3, 4}, stride_bytes < width * channels, n_images / width / height < 1, a source that does not cover every row's image index,
+ * and an external stack whose width and height are not those of the context image a row maps to.  Every offset is 64-bit. */
+#define SDM_ALIGN_DEGENERATE 1
+#define SDM_ALIGN_PARTIAL 2
+int sdm_align_set_source(sdm_ctx* ctx, const uint8_t* base, int n_images, int width, int height, int stride_bytes, int channels,
+                         int on_device);
+/* One call for all N current rows: the K indices and the K x 2 template in (one copy), the fit, the warp, the matrices and flags out
+ * (one copy), the crops out when out is host memory (out_on_device 0), one stream synchronise.  out: N x out_height x out_width x C
+ * bytes, C the source's channels; matrices_host (N x 6: M00 M01 M02 M10 M11 M12) and flags_host (N) may be NULL.  Neither the
+ * landmark state, the images nor the tracker's slots are changed. */
+int sdm_align_crops(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int out_width, int out_height,
+                    uint8_t* out, int out_on_device, float* matrices_host, int* flags_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,12 +34,16 @@ EXPORTED = [
     "sdm_pose_templates_from_landmarks", "sdm_pose_set_targets", "sdm_pose_features", "sdm_pose_train_level",
     "sdm_pose_set_regressor", "sdm_pose_get_regressor", "sdm_pose_test",
     "sdm_track_configure", "sdm_track_start", "sdm_track_stop", "sdm_track_step", "sdm_track_get",
+    "sdm_align_set_source", "sdm_align_crops",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
 SDM_TRACK_FREE, SDM_TRACK_STARTED, SDM_TRACK_TRACKED, SDM_TRACK_LOST = 0, 1, 2, 3
 SDM_TRACK_INIT_PREVIOUS, SDM_TRACK_INIT_REALIGN = 0, 1
 SDM_TRACK_LOST_NONFINITE, SDM_TRACK_LOST_SMALL, SDM_TRACK_LOST_OUTSIDE, SDM_TRACK_LOST_SCALE = 1, 2, 4, 8
+
+# aligned face crops (include/sdm.h, sdm_align_*)
+SDM_ALIGN_DEGENERATE, SDM_ALIGN_PARTIAL = 1, 2
 
 
 class SdmHogParam(ctypes.Structure):
@@ -184,6 +188,8 @@ def lib() -> ctypes.CDLL:
             "sdm_track_stop": [c_void_p, c_void_p, c_int],
             "sdm_track_step": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
             "sdm_track_get": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+            "sdm_align_set_source": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int],
+            "sdm_align_crops": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

@@ -76,6 +76,7 @@ void sdm_destroy(sdm_ctx* c)
     c->Rmax.release();
     c->pose.release();
     c->track.release();
+    c->align.release();
     for (auto& r : c->Rt) r.release();
     for (auto& q : c->plans) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); }
     if (c->own_stream) e = hipStreamDestroy(c->stream);
@@ -302,6 +303,7 @@ int sdm_upload_images_u8(sdm_ctx* c, const uint8_t* const* images, const int* w,
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->img_base = c->img_owned.p;
     c->n_images = n;
+    c->img_w_host.assign(w, w + n); c->img_h_host.assign(h, h + n);
     c->narrow_images = false;
     for (int i = 0; i < n; ++i) c->narrow_images = c->narrow_images || w[i] < 2 || h[i] > 65535;
     return SDM_OK;
@@ -347,6 +349,7 @@ int sdm_upload_images_bgr_u8(sdm_ctx* c, const uint8_t* const* images, const int
     staging.release();
     c->img_base = c->img_owned.p;
     c->n_images = n;
+    c->img_w_host.assign(w, w + n); c->img_h_host.assign(h, h + n);
     c->narrow_images = false;
     for (int i = 0; i < n; ++i) c->narrow_images = c->narrow_images || w[i] < 2 || h[i] > 65535;
     return SDM_OK;
@@ -378,6 +381,7 @@ int sdm_set_images_device(sdm_ctx* c, const uint8_t* dev_base, int n, int w, int
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->img_base = dev_base;
     c->n_images = n;
+    c->img_w_host.assign(n, w); c->img_h_host.assign(n, h);
     c->narrow_images = w < 2 || h > 65535;
     return SDM_OK;
 }
@@ -398,6 +402,7 @@ int sdm_set_sample_image_index(sdm_ctx* c, const int* idx, int n)
     HIP_TRY(hipMemcpyAsync(c->img_idx.p, idx, n * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->idx_identity = false; c->n_idx = n; c->max_idx = mx;
+    c->img_idx_host.assign(idx, idx + n);
     return SDM_OK;
 }
 

@@ -5,6 +5,7 @@
 //   sdm_capi_context.hip   lifetime, geometry, images, samples            sdm_capi_detect.hip    features, regressors, apply, detect
 //   sdm_capi_train.hip     targets, Gram / right-hand side, solvers       sdm_capi_exchange.hip  the several-GPU exchange of the normal equations
 //   sdm_capi_debug.hip     device pointers, timing, debug entry points   sdm_capi_pose.hip / sdm_capi_track.hip  head pose, tracking
+//   sdm_capi_align.hip     aligned face crops
 #pragma once
 #include "../../include/sdm.h"
 #include "sdm_kernels.h"
@@ -246,6 +247,20 @@ struct sdm_ctx {
             pin = nullptr; pin_cap = 0; S = 0;
         }
     } track;
+
+    // aligned face crops (sdm_capi_align.hip): the source of the taps -- the images above (base null) or an external stack -- and
+    // the per-call scratch
+    struct Align {
+        const uint8_t* base = nullptr;     // external stack; null: the context's images
+        int n = 0, w = 0, h = 0, stride = 0, C = 1;
+        DevBuf<uint8_t> owned;             // a host stack's copy
+        DevBuf<int> in;                    // K indices + K x 2 template floats
+        DevBuf<AlignFace> faces;           // N records
+        DevBuf<uint8_t> crops;             // the crops of a host-memory out
+        void release() { in.release(); faces.release(); crops.release(); owned.release(); base = nullptr; n = 0; C = 1; }
+    } align;
+    // host copies of the image sizes and of the sample -> image index (the checks of an external crop source)
+    std::vector<int> img_w_host, img_h_host, img_idx_host;
 
     // timing
     bool timing = false;

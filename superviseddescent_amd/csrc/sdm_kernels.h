@@ -335,3 +335,22 @@ void sdm_launch_track_gather(const int* ids, int n, int L, int mode, const int* 
 void sdm_launch_track_commit(const int* ids, int n, int L, const float* x, const float* init, const int* img_idx, const int* img_w,
                              const int* img_h, const EyeIdxDev& eyes, float min_size, float max_scale_change, float* slot_x,
                              int* slot_status, int* masks, const int* status_word, hipStream_t s);
+
+// ---- aligned face crops (sdm_align.hip) ----
+// per row: the crop -> source matrix (float32, rounded from the double fit), the SDM_ALIGN_* flags and the row's image
+struct AlignFace {
+    float m[6];                // M00 M01 M02 M10 M11 M12
+    int flags;
+    int w, h, stride;          // the row's image: pixels, rows, bytes per row
+    long long off;             // its first byte, from the source base
+};
+// the source of the taps: the context's image set (ctx.base != null) or an external stack of equally sized images
+struct AlignSourceDev {
+    ImageSetDev ctx;
+    int width, height, stride;
+};
+// x: N x 2L; lm: K landmark indices; tmpl: K x 2 template points (crop pixels); img_idx: row -> image (null: identity)
+void sdm_launch_align_fit(const float* x, int N, int L, const int* lm, const float* tmpl, int K, const AlignSourceDev& src,
+                          const int* img_idx, int out_w, int out_h, AlignFace* faces, hipStream_t s);
+// out: N x out_h x out_w x C bytes (C = 1, 3 or 4), 4-byte aligned (16 when C = 4)
+void sdm_launch_align_warp(const uint8_t* img, const AlignFace* faces, int N, int out_w, int out_h, int C, uint8_t* out, hipStream_t s);

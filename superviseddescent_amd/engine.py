@@ -12,6 +12,7 @@ Class and method names follow the reference so that the parity tests read like i
 ``detection_model.detect``                     include/rcr/model.hpp:122-183
 ``ModelProjection``                            examples/pose_estimation.cpp:187-240 (head pose, csrc/sdm_pose.hip)
 ``detection_model.tracker`` / ``Tracker``       apps/rcr/rcr-track.cpp:133-177 (multi-stream tracking, csrc/sdm_track.hip)
+``detection_model.aligned_crops``              (extension) aligned face crops of the current rows, csrc/sdm_align.hip
 =============================================  =====================================================
 
 Everything numeric happens on the MI355X: HOG extraction, regressor apply, Gram/RHS build and the
@@ -81,6 +82,7 @@ class Context:
             check(self._lib.sdm_set_stream(self._h, ctypes.c_void_p(stream)))
         self.L = 0
         self.n_levels = 0
+        self.align_channels = 1     # C of the crop source installed by align_set_source (the library writes N x H x W x C bytes)
         # level -> token of the regressor the DEVICE holds (None: unknown).  Kept here, next to the device copy, so that
         # two optimisers sharing this context cannot mistake each other's upload for their own.
         self._resident = {}
@@ -523,6 +525,64 @@ class Context:
         st = np.empty(i.size, np.int32)
         check(self._lib.sdm_track_get(self._h, i.ctypes.data, i.size, out.ctypes.data, st.ctypes.data))
         return out, st
+
+    # -- aligned face crops (csrc/sdm_align.hip) -------------------------------------------------------
+    def align_set_source(self, source=None):
+        """The images the crops are cut from: None (the context's own images), a host uint8 array n x H x W [x C] (copied once),
+        or a contiguous uint8 n x H x W [x C] tensor on the device (used in place; it must stay alive while crops are made).
+        Returns C, which the next ``align_crops`` writes per pixel."""
+        if source is None:
+            check(self._lib.sdm_align_set_source(self._h, None, 0, 0, 0, 0, 0, 0))
+            self.align_channels = 1
+            return 1
+        if hasattr(source, "data_ptr") and getattr(source, "is_cuda", False):
+            import torch
+            if source.dtype != torch.uint8 or source.dim() not in (3, 4) or not source.is_contiguous():
+                raise ValueError("a device source must be a contiguous uint8 n x H x W [x C] tensor")
+            torch.cuda.current_stream(source.device).synchronize()          # (the library runs on its own stream)
+            shape, ptr, on_device = tuple(int(v) for v in source.shape), source.data_ptr(), 1
+        else:
+            if np.asarray(source).dtype != np.uint8:
+                raise ValueError("a host source must be a uint8 array")
+            source = np.ascontiguousarray(source)
+            if source.ndim not in (3, 4):
+                raise ValueError("a host source must be an n x H x W [x C] uint8 array")
+            shape, ptr, on_device = source.shape, source.ctypes.data, 0
+        n, h, w = shape[:3]
+        C = shape[3] if len(shape) == 4 else 1
+        check(self._lib.sdm_align_set_source(self._h, ctypes.c_void_p(ptr), n, w, h, w * C, C, on_device))
+        self.align_channels = C
+        return C
+
+    def align_crops(self, landmark_index, template: np.ndarray, width: int, height: int, channels: Optional[int] = None, out=None):
+        """Crops of the N current rows (include/sdm.h, sdm_align_crops) from the source set by ``align_set_source``: returns (crops
+        N x height x width x C uint8 -- ``out`` itself when a device tensor is given, written in place and not fetched --,
+        matrices N x 2 x 3 float32 (crop -> source), flags N int32: SDM_ALIGN_* bits).  C is the source's; ``channels``, when
+        given, must equal it."""
+        C = self.align_channels
+        if channels is not None and int(channels) != C:
+            raise ValueError(f"the crop source has {C} channel(s), not {channels}")
+        idx = np.ascontiguousarray(landmark_index, np.int32).reshape(-1)
+        t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
+        if t.shape[0] != idx.size:
+            raise ValueError("one template point (x, y) per landmark index expected")
+        n = int(getattr(self, "N", 0))          # (0: no rows yet -- the library refuses the call)
+        mats = np.empty((n, 2, 3), np.float32)
+        flags = np.empty(n, np.int32)
+        if out is not None:
+            import torch
+            if not (isinstance(out, torch.Tensor) and out.is_cuda) or out.dtype != torch.uint8 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous uint8 tensor on the device")
+            if tuple(out.shape) != (n, int(height), int(width), C):
+                raise ValueError(f"out must be a {n} x {height} x {width} x {C} tensor")
+            torch.cuda.current_stream(out.device).synchronize()
+            check(self._lib.sdm_align_crops(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height),
+                                            ctypes.c_void_p(out.data_ptr()), 1, mats.ctypes.data, flags.ctypes.data))
+            return out, mats, flags
+        crops = np.empty((n, int(height), int(width), C), np.uint8)
+        check(self._lib.sdm_align_crops(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height),
+                                        crops.ctypes.data, 0, mats.ctypes.data, flags.ctypes.data))
+        return crops, mats, flags
 
     # -- misc ------------------------------------------------------------------------------------------
     def synchronize(self):
@@ -1096,8 +1156,52 @@ class detection_model:
         image, or its inter-eye distance changes by more than the factor ``max_scale_change`` in one step (0: no such rule)."""
         return Tracker(self, capacity, init, min_size, max_scale_change)
 
+    def aligned_crops(self, size, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
+                      margin: float = 0.2, source=None, out=None):
+        """Aligned face crops of the current rows -- the last ``detect_batch`` or ``Tracker.step`` -- without taking the landmarks or
+        the frames off the device (include/sdm.h, sdm_align_*).  ``size``: an int (square) or (width, height).  ``landmark_ids``:
+        the landmarks the similarity is fitted to (default: all of this model's).  ``template``: their K x 2 positions in crop
+        pixels (default: :func:`alignment_template` of the mean with ``margin``).  ``source``: None (the context's gray images), a
+        host array n x H x W [x C] or a contiguous uint8 device tensor of the same shape, e.g. the colour frames of the gray ones
+        the cascade ran on (C in {1, 3, 4}, channel order kept).  ``out``: a uint8 device tensor of N x H x W x C bytes, written in
+        place.  Returns (crops N x H x W x C uint8 -- or ``out`` --, matrices N x 2 x 3 crop -> source, flags N: SDM_ALIGN_*)."""
+        c = self.optimised_model.ctx
+        if not getattr(c, "N", 0):
+            raise RuntimeError("run detect_batch or Tracker.step first")
+        width, height = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        ids = self.landmark_ids if landmark_ids is None else [str(i) for i in landmark_ids]
+        missing = [i for i in ids if i not in self.landmark_ids]
+        if missing:
+            raise ValueError(f"landmark ids not in this model: {missing}")
+        idx = [self.landmark_ids.index(i) for i in ids]
+        if template is None:
+            template = alignment_template(self.mean, idx, width, height, margin)
+        c.align_set_source(source)
+        try:
+            return c.align_crops(idx, template, width, height, out=out)
+        finally:
+            if source is not None:
+                c.align_set_source(None)                                  # (no pointer to the caller's frames stays behind)
+
     def get_mean(self) -> np.ndarray:
         return self.mean
+
+
+def alignment_template(mean: np.ndarray, landmark_index: Sequence[int], width: int, height: int, margin: float = 0.2) -> np.ndarray:
+    """The default crop template (K x 2 float32, crop pixels), computed in float64: the mean's selected points with their enclosing
+    box centred in the crop ((width - 1) / 2, (height - 1) / 2) and scaled so that its larger side is (1 - 2 margin) of the crop's
+    smaller side."""
+    m = np.asarray(mean, np.float64).reshape(-1)
+    L = m.size // 2
+    idx = np.asarray(landmark_index, np.int64)
+    px, py = m[idx], m[L + idx]
+    extent = max(px.max() - px.min(), py.max() - py.min())
+    if not extent > 0:
+        raise ValueError("the selected mean points have no extent")
+    s = (1.0 - 2.0 * margin) * min(width, height) / extent
+    tx = (px - (px.min() + px.max()) / 2) * s + (width - 1) / 2
+    ty = (py - (py.min() + py.max()) / 2) * s + (height - 1) / 2
+    return np.stack([tx, ty], 1).astype(np.float32)
 
 
 class Tracker:

@@ -1,0 +1,135 @@
+// rcr/alignment.hpp -- aligned face crops from landmarks kept on the device (include/sdm.h, sdm_align_*): a similarity fitted to a
+// few landmarks of every face puts the face in a canonical position in an out_width x out_height crop -- the input of recognition,
+// expression or attribute networks -- without copying the landmarks or the frames to the host for an image library.
+//
+//     rcr::tracker tr(model, 64);
+//     auto lms = tr.step(ids, frames);                                         // gray frames: what the cascade runs on
+//     cv::Mat tmpl = rcr::alignment_template(model.get_mean(), idx, 112, 112); // or the template of a recognition network
+//     auto a = rcr::aligned_crops(tr, idx, tmpl, 112, 112, colour_frames);     // CV_8UC3 crops of the BGR frames
+//     // a.crops[i]: stream ids[i]; a.matrices.row(i): its crop -> source map (M00 M01 M02 M10 M11 M12); a.flags[i]: SDM_ALIGN_*
+//
+// The rows of detection_model::detect_batch work the same way (the overload taking the images and the rows).
+#pragma once
+
+#ifndef RCR_ALIGNMENT_HPP_
+#define RCR_ALIGNMENT_HPP_
+
+#include "rcr/model.hpp"
+#include "rcr/tracker.hpp"
+
+#include <algorithm>
+#include <cstring>
+#include <stdexcept>
+#include <vector>
+
+namespace rcr {
+
+struct aligned_crops_result {
+    std::vector<cv::Mat> crops;    // one out_height x out_width CV_8UC1 / CV_8UC3 image per row
+    cv::Mat matrices;              // rows x 6 CV_32FC1: the crop -> source map of every row (NaN for a degenerate row)
+    std::vector<int> flags;        // SDM_ALIGN_DEGENERATE / SDM_ALIGN_PARTIAL bits
+};
+
+/** The default template (K x 2 CV_32FC1, crop pixels; computed in double): the mean's landmarks `landmark_index` with their
+ *  enclosing box centred in the crop and scaled so that its larger side is (1 - 2 margin) of the crop's smaller side. */
+inline cv::Mat alignment_template(cv::Mat mean, const std::vector<int>& landmark_index, int width, int height, double margin = 0.2)
+{
+    const int L = (int)mean.total() / 2;
+    if (landmark_index.empty()) throw std::runtime_error("alignment_template: no landmarks");
+    std::vector<double> px, py;
+    for (int i : landmark_index) {
+        if (i < 0 || i >= L) throw std::runtime_error("alignment_template: landmark index out of range");
+        px.push_back(mean.at<float>(i));
+        py.push_back(mean.at<float>(i + L));
+    }
+    const double x0 = *std::min_element(px.begin(), px.end()), x1 = *std::max_element(px.begin(), px.end());
+    const double y0 = *std::min_element(py.begin(), py.end()), y1 = *std::max_element(py.begin(), py.end());
+    const double extent = std::max(x1 - x0, y1 - y0);
+    if (!(extent > 0)) throw std::runtime_error("alignment_template: the selected mean points have no extent");
+    const double s = (1.0 - 2.0 * margin) * std::min(width, height) / extent;
+    cv::Mat t((int)px.size(), 2, CV_32FC1);
+    for (size_t k = 0; k < px.size(); ++k) {
+        t.at<float>((int)k, 0) = (float)((px[k] - (x0 + x1) / 2) * s + (width - 1) / 2.0);
+        t.at<float>((int)k, 1) = (float)((py[k] - (y0 + y1) / 2) * s + (height - 1) / 2.0);
+    }
+    return t;
+}
+
+namespace detail {
+
+// crops of the n current rows of the handle `c`, from its own images or -- `colour` not empty -- from equally sized CV_8UC1 / CV_8UC3
+// images that stand in for them (one per image of the context, in its order)
+inline aligned_crops_result align_current_rows(sdm_ctx* c, int n, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
+                                               int height, const std::vector<cv::Mat>& colour)
+{
+    using superviseddescent::hip::check;
+    if (tmpl.rows != (int)landmark_index.size() || tmpl.cols != 2) throw std::runtime_error("aligned_crops: one template point (x, y) per landmark");
+    cv::Mat t = tmpl.isContinuous() ? tmpl : tmpl.clone();
+    int C = 1;
+    std::vector<uint8_t> stack;
+    if (!colour.empty()) {
+        const int w = colour[0].cols, h = colour[0].rows, type = colour[0].type();
+        if (type != CV_8UC1 && type != CV_8UC3) throw std::runtime_error("aligned_crops: the source images must be CV_8UC1 or CV_8UC3");
+        C = type == CV_8UC3 ? 3 : 1;
+        const size_t row_bytes = (size_t)w * C;
+        stack.resize(colour.size() * (size_t)h * row_bytes);
+        for (size_t i = 0; i < colour.size(); ++i) {
+            if (colour[i].cols != w || colour[i].rows != h || colour[i].type() != type)
+                throw std::runtime_error("aligned_crops: the source images must be equally sized, of one type");
+            for (int r = 0; r < h; ++r) std::memcpy(&stack[(i * h + r) * row_bytes], colour[i].ptr<uint8_t>(r), row_bytes);
+        }
+        check(sdm_align_set_source(c, stack.data(), (int)colour.size(), w, h, (int)row_bytes, C, 0), "sdm_align_set_source");
+    } else {
+        check(sdm_align_set_source(c, nullptr, 0, 0, 0, 0, 0, 0), "sdm_align_set_source");
+    }
+    aligned_crops_result res;
+    std::vector<uint8_t> out((size_t)n * width * height * C);
+    res.matrices = cv::Mat(n, 6, CV_32FC1);
+    res.flags.resize((size_t)n);
+    const int rc = sdm_align_crops(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, out.data(), 0,
+                                   res.matrices.ptr<float>(0), res.flags.data());
+    if (!colour.empty()) sdm_align_set_source(c, nullptr, 0, 0, 0, 0, 0, 0);     // (back to the context's images)
+    check(rc, "sdm_align_crops");
+    const size_t crop_bytes = (size_t)width * height * C;
+    for (int r = 0; r < n; ++r) {
+        cv::Mat m(height, width, C == 3 ? CV_8UC3 : CV_8UC1);
+        std::memcpy(m.ptr<uint8_t>(0), out.data() + r * crop_bytes, crop_bytes);
+        res.crops.push_back(m);
+    }
+    return res;
+}
+
+}  // namespace detail
+
+/** Crops of the streams of the tracker's last step (tracker::step), from the step's frames (gray) or from `colour_frames`: one
+ *  CV_8UC3 (or CV_8UC1) image per frame of that step, same size, same order -- e.g. the BGR frames the gray ones came from. */
+inline aligned_crops_result aligned_crops(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                          const std::vector<cv::Mat>& colour_frames = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("aligned_crops: step the tracker first");
+    return detail::align_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, colour_frames);
+}
+
+/** Crops of landmark rows on their images, e.g. the N x 2L result of detection_model::detect_batch(images, boxes, image_index):
+ *  row i is cut from images[image_index[i]] (default: images[i]), or from the same entry of `colour_images`.  The C++
+ *  detection_model keeps no device context between calls (each detect_batch runs on a handle of its own), so this overload
+ *  uploads the images and the rows to a handle of its own as well: unlike the tracker overload, the frames and the landmarks
+ *  cross the host link here.  Streams whose landmarks should stay on the device go through rcr::tracker. */
+inline aligned_crops_result aligned_crops(detection_model& model, const std::vector<cv::Mat>& images, cv::Mat rows,
+                                          const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl,
+                                          int width, int height, const std::vector<cv::Mat>& colour_images = {})
+{
+    using superviseddescent::hip::check;
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    sdm_ctx* c = h.get();
+    detail::configure(h, images, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), true);
+    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
+    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("aligned_crops: rows must hold 2L coordinates");
+    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
+    return detail::align_current_rows(c, x.rows, landmark_index, tmpl, width, height, colour_images);
+}
+
+}  // namespace rcr
+#endif /* RCR_ALIGNMENT_HPP_ */
