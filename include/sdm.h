@@ -310,7 +310,7 @@ int sdm_debug_update_fallbacks(sdm_ctx* ctx);
 int sdm_debug_hog_plan(int num_cells, int cell_size, int num_bins, int num_landmarks, int* info5, unsigned* lane_tab,
                        float* wb, int* pass_info, int max_passes);
 /* cut[num_landmarks]: 1 where the landmark's patch is cut by a pass boundary of that plan (its raw cell histograms arrive in two
- * parts, csrc/sdm_hog_fast.hip CELLS form); host only.  Returns SDM_ERR_INVALID when the geometry has no packed instance. */
+ * parts, csrc/sdm_hog_packed.hip CELLS form); host only.  Returns SDM_ERR_INVALID when the geometry has no packed instance. */
 int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_landmarks, int* cut);
 /* Round 4, A/B and tests: which launches the packed default mode uses.  fused != 0 (default; sdm_debug_set_option "detect_unfused" turns it
  * off): sdm_detect_batch runs  pixel kernel -> raw cell histograms -> descriptors x regressor slices on the 16-bit matrix cores

@@ -1,5 +1,5 @@
 """Compute-side roofline of the pixel kernel ("sum of class count x measured issue clocks / SIMD clocks"):
-compiles csrc/sdm_hog_fast.hip to gfx950 assembly, takes the four raw-cells instances the shipped RCR-22 model runs (cell sizes
+compiles csrc/sdm_hog_packed.hip to gfx950 assembly, takes the four raw-cells instances the shipped RCR-22 model runs (cell sizes
 11 / 10 / 8 / 6; their pixel-row loops are fully unrolled, so a static count IS the dynamic count of a pass), classifies every
 instruction between the first and the last image load + the band folds behind them, and prices the classes with the issue clocks
 measured on this chip (profiles/r03_ubench_valu_rates.txt, 8 waves per SIMD column; v_mfma_f32_16x16x4_f32: 8 passes = 32 clocks).
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASM = "/tmp/isa/issue_model.s"
 os.makedirs("/tmp/isa", exist_ok=True)
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w", "-S",
-                       "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "superviseddescent_amd/csrc/sdm_hog_fast.hip"), "-o", ASM])
+                       "--cuda-device-only", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "superviseddescent_amd/csrc/sdm_hog_packed.hip"), "-o", ASM])
 FAST = {"v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mul_f32", "v_add_u32", "v_sub_u32", "v_subrev_u32", "v_and_b32", "v_or_b32", "v_xor_b32",
         "v_lshrrev_b32", "v_lshlrev_b32", "v_ashrrev_i32", "v_mov_b32", "v_max_f32", "v_min_f32", "v_max_i32", "v_min_i32", "v_max_u32", "v_min_u32", "v_accvgpr_write_b32"}
 TRANS = {"v_sqrt_f32", "v_rsq_f32", "v_rcp_f32", "v_rcp_iflag_f32", "v_exp_f32", "v_log_f32"}

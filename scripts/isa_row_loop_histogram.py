@@ -1,6 +1,6 @@
 """Instruction histogram of the row loop of hog_packed_kernel (two pixel rows per trip), from the compiler's own assembly:
     python scripts/isa_row_loop_histogram.py > profiles/r02_isa_row_loop_histogram.txt
-Compiles superviseddescent_amd/csrc/sdm_hog_fast.hip to gfx950 assembly, takes the innermost row loop of the packed kernel
+Compiles superviseddescent_amd/csrc/sdm_hog_packed.hip to gfx950 assembly, takes the innermost row loop of the packed kernel
 (the basic blocks between its loop header and back edge, band folds included) and counts mnemonics per class."""
 import collections
 import os
@@ -10,7 +10,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "superviseddescent_amd", "csrc", "sdm_hog_fast.hip")
+src = os.path.join(ROOT, "superviseddescent_amd", "csrc", "sdm_hog_packed.hip")
 with tempfile.TemporaryDirectory() as d:
     out = os.path.join(d, "k.s")
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-w", "-S",

@@ -1,7 +1,7 @@
 // sdm_desc.hip -- from raw cell histograms to descriptors, and (detect) straight on to the regressor update, for gfx950.
 //
 // Second half of the HOG transform of the default (column-sum) mode, split off the pixel kernel in round 4:
-//   hog_packed_kernel<..., CELLS> (sdm_hog_fast.hip) leaves cells[sample][landmark][part][C*C][2O] in HBM (vl_hog_put_image,
+//   hog_packed_kernel<..., CELLS> (sdm_hog_packed.hip) leaves cells[sample][landmark][part][C*C][2O] in HBM (vl_hog_put_image,
 //   include/rcr/hog.c:595-728); this file is vl_hog_extract (hog.c:857-1062) + the Matlab cell order of
 //   rcr::HogTransform::operator() (include/rcr/adaptive_vlhog.hpp:166-175), and in detect also
 //   LinearRegressor::predict (include/superviseddescent/regressors.hpp:377-381) for the landmark's rows of the regressor.

@@ -67,7 +67,7 @@ void sdm_launch_hog(const ImageSetDev& imgs, const int* img_idx, const float* x,
                     const EyeIdxDev& eyes, const HogLevelDev& lv, float* feat, long long ldf,
                     int* idx_out, int* status, hipStream_t stream);
 
-// Production kernel (sdm_hog_fast.hip), S <= 64.  acc_mode (= SDM_HOG_*): 0 accumulate with ds_add_f32 in the reference's
+// One-patch-per-wave kernels (sdm_hog_fast.hip), S <= 64.  acc_mode (= SDM_HOG_*): 0 accumulate with ds_add_f32 in the reference's
 // raster order (bit-identical histogram), 1 the exact 2^-36 fixed-point sum, 2 per-pixel-column f32 sums folded into
 // cells on the matrix cores (specialised geometries only; others fall back to 1); fast_bins: use the
 // cheaper orientation binning (1 = un-normalised arg-max, 2 = first-quadrant sector count; each only when
@@ -82,7 +82,7 @@ void sdm_launch_hog_fast(const ImageSetDev& imgs, const int* img_idx, const floa
                          const EyeIdxDev& eyes, const HogLevelDev& lv, float* feat, long long ldf, int* idx_out,
                          int* status, int acc_mode, int fast_bins, hipStream_t stream);
 
-// ---- lane-packed launch plan of one level (sdm_hog_fast.hip::hog_packed_kernel) --------------------------------------
+// ---- lane-packed launch plan of one level (sdm_hog_packed.hip::hog_packed_kernel; built by sdm_hog_plan.hip) ----
 // The L patches of a sample are split into groups of G consecutive landmarks (n_main groups, then one tail group of
 // Gt = L - n_main * G patches, 0 = none).  One wave walks a group in P (Pt) passes; in a pass every lane owns one pixel
 // column of one patch of the group, so a 50-column ROI no longer leaves 14 lanes idle: five of them share four passes.
@@ -100,10 +100,16 @@ struct HogPlanDev {
     int raw_sqrt;              // v_sqrt_f32 found exact-or-one-ulp-low on all 511^2 gradients on THIS device (else: repaired root)
     const unsigned* lane_tab;
     const float* wb;
-    const unsigned short* wb16; // [pass][lane][2 k-blocks][2 pieces][8] float16 bits: the same weights x 2^10 as two float16 pieces in the layout of v_mfma_f32_16x16x32_f16's B operand (HP_F16FOLD)
+    const unsigned short* wb16; // [pass][lane][2 k-blocks][2 pieces][8] float16 bits: the same weights x 2^10 as two float16 pieces in the layout of v_mfma_f32_16x16x32_f16's B operand (the float16 band folds of the specialised instances)
     const int* pass_info;
     const int* taps;           // [SDM_SCALE_TAB half-widths][64 coordinates][8] cv::resize taps of the level (sdm_launch_taps_table); null = computed per wave
 };
+// Cell row (band) of resized-ROI row d: floor((d + 0.5) / cell - 0.5) (hog.c:697-704) in integers, for the instances specialised
+// on the cell size; sdm_hog_plan_build checks it against the level's float table before such an instance is chosen.
+__host__ __device__ constexpr int packed_band_of(int d, int cell)
+{
+    return (2 * d + 1 - cell >= 0) ? (2 * d + 1 - cell) / (2 * cell) : -1;      // (d >= 0, cell >= 1: the only negative value is -1)
+}
 #ifdef __cplusplus
 #include <vector>
 struct HogPlanHost {

@@ -3,7 +3,7 @@
 //
 // Same constructor and call signature as the reference.  The arithmetic (IED-adaptive ROI, zero-padded crop,
 // cv::resize 8U bilinear, VLFeat HOG, Matlab-order flatten, bias) runs in the gfx950 kernel
-// superviseddescent_amd/csrc/sdm_hog_fast.hip through the C-ABI:
+// superviseddescent_amd/csrc/sdm_hog_packed.hip (sdm_hog_fast.hip for the exact modes) through the C-ABI:
 //   * inside SupervisedDescentOptimiser::{train,test,predict} the whole batch of one cascade level is ONE
 //     kernel launch (detail::BatchedBackend in rcr/model.hpp) and operator() is never called;
 //   * operator()(parameters, level, training_index) itself -- the reference's per-sample entry point -- runs the

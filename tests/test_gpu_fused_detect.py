@@ -185,7 +185,7 @@ def test_apply_of_rows_that_are_not_hog_output(ctx):
 
 @pytest.mark.parametrize("level", [0, 3])
 def test_band_folds_at_the_largest_possible_column_sums(ctx, level):
-    """The band folds run on float16 pieces of the column sums x 8 (csrc/sdm_hog_fast.hip, HP_F16FOLD): the largest sum a band slot
+    """The band folds run on float16 pieces of the column sums x 8 (csrc/sdm_hog_packed.hip, F16F): the largest sum a band slot
     can hold is cell x 255 sqrt(2) (a full-contrast checkerboard under the triangular row weights) = 3 967 at cell 11, x 8 = 31 736 <
     65 504.  Images of 0 / 255 noise and of a one-pixel checkerboard drive the sums to that corner: features finite and as close to
     the oracle as on natural images."""

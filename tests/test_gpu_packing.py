@@ -1,4 +1,4 @@
-"""The lane-packed HOG launch (sdm_hog_fast.hip::hog_packed_kernel, on by default in SDM_HOG_COLUMNS mode) against the
+"""The lane-packed HOG launch (sdm_hog_packed.hip::hog_packed_kernel, on by default in SDM_HOG_COLUMNS mode) against the
 one-patch-per-wave launch and against the CPU oracle: identical integer decisions, features within the columns-mode
 tolerance (a patch cut by a pass boundary sums its cells from two partial folds, nothing else changes)."""
 import os
