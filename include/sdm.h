@@ -312,6 +312,12 @@ int sdm_debug_hog_plan(int num_cells, int cell_size, int num_bins, int num_landm
 /* cut[num_landmarks]: 1 where the landmark's patch is cut by a pass boundary of that plan (its raw cell histograms arrive in two
  * parts, csrc/sdm_hog_packed.hip CELLS form); host only.  Returns SDM_ERR_INVALID when the geometry has no packed instance. */
 int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_landmarks, int* cut);
+/* Tests: the level's table of cv::resize taps as the device built it at sdm_set_model_geometry (csrc/sdm_hog_packed.hip,
+ * taps_table_kernel): table[128 half-widths][64 coordinates][8] ints = {s0, c0 | c1 << 16, sy0, sy1, b0 << 12, b1 << 12, carry mask of
+ * the row, half-width is one-load eligible}.  info3 = {the level's HOG launch of detect is the raw-cells launch as the context stands
+ * (packed plan, SDM_HOG_COLUMNS, descriptor kernel available), that launch is an instance with the one-load row loop, option
+ * hog_two_load}.  SDM_ERR_INVALID when the level has no packed plan. */
+int sdm_debug_hog_taps(sdm_ctx* ctx, int level, int* table, int* info3);
 /* Round 4, A/B and tests: which launches the packed default mode uses.  fused != 0 (default; sdm_debug_set_option "detect_unfused" turns it
  * off): sdm_detect_batch runs  pixel kernel -> raw cell histograms -> descriptors x regressor slices on the 16-bit matrix cores
  * (csrc/sdm_desc.hip) -> landmark update, and never writes the N x F feature matrix (LinearRegressor::predict,

@@ -141,6 +141,19 @@ int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_l
     return SDM_OK;
 }
 
+int sdm_debug_hog_taps(sdm_ctx* c, int level, int* table, int* info3)
+{
+    if (!c || level < 0 || level >= (int)c->levels.size() || !table || !info3) return fail(SDM_ERR_INVALID, "bad arguments");
+    if (!c->plans[level].ok || !c->plans[level].taps.p) return fail(SDM_ERR_INVALID, "no packed plan for this level");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(table, c->plans[level].taps.p, (size_t)SDM_SCALE_TAB * 64 * 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    info3[0] = split_ok(c, level) ? 1 : 0;
+    info3[1] = sdm_hog_cells_row_carry(c->levels[level], c->plans[level].dev) ? 1 : 0;
+    info3[2] = c->hog_two_load ? 1 : 0;
+    return SDM_OK;
+}
+
 int sdm_debug_set_detect_path(sdm_ctx* c, int fused, int split_store)
 {
     if (!c) return fail(SDM_ERR_INVALID, "null context");
@@ -170,7 +183,7 @@ int sdm_debug_gradient_table(sdm_ctx* c, int level, float* g, int* bin)
 // Development switches (A/B handles of kernels that remain as fallbacks, knobs the tests turn): the library itself reads no environment
 // variable; the Python mirror forwards SDM_<NAME>=<value> of ITS environment through this call when it creates a context
 // (superviseddescent_amd/engine.py), which is what the A/B scripts and two tests use.  Names (value 0 / 1 unless noted):
-//   hog_no_pack (one patch per wave), hog_split_store (feature rows through cells + descriptor kernel), detect_unfused, detect_fuse_wide,
+//   hog_no_pack (one patch per wave), hog_two_load (the detect path's pixel kernel loads both source rows of every pixel row), hog_split_store (feature rows through cells + descriptor kernel), detect_unfused, detect_fuse_wide,
 //   apply_f32, gram_f32, gram_bf16x3, update_f32 (the f32 matrix-core kernels of rounds 1-2 / the three-bf16 form),
 //   gram_xblocks (n: exchange ranges behind the Gram kernel; -1 automatic), solve_upd_min_tiles (n), solve_fine_head (n),
 //   solve_bs_cap (n: right-hand-side column tiles per back-substitution workgroup), solve_shard_emulate (timing harness)
@@ -179,6 +192,7 @@ int sdm_debug_set_option(sdm_ctx* c, const char* name, int value)
     if (!c || !name) return fail(SDM_ERR_INVALID, "bad arguments");
     const std::string n(name);
     if (n == "hog_no_pack") c->packing = value == 0;
+    else if (n == "hog_two_load") c->hog_two_load = value != 0;
     else if (n == "hog_split_store") c->split_store = value != 0;
     else if (n == "detect_unfused") c->fuse_apply = value == 0;
     else if (n == "detect_fuse_wide") c->env_fuse_wide = value != 0;

@@ -106,13 +106,21 @@ int hog_checks(sdm_ctx* c, int level)
     return check_sample_index(c);
 }
 
+// the level's plan as the cells launch takes it (option hog_two_load)
+static HogPlanDev cells_plan(const sdm_ctx* c, int level)
+{
+    HogPlanDev pd = c->plans[level].dev;
+    pd.two_load = c->hog_two_load ? 1 : 0;
+    return pd;
+}
+
 // pixel kernel of the split launch: images -> raw cell histograms of every (sample, landmark)
 int launch_cells(sdm_ctx* c, int level)
 {
     int rc = c->cells.ensure(sdm_cells_floats(c->levels[level], c->N, c->L));
     if (rc) return rc;
     sdm_launch_hog_cells(image_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->x[c->cur].p, c->N, c->L, c->eyes,
-                         c->levels[level], c->plans[level].dev, c->cells.p, c->patch_idx.p, c->status.p, c->stream);
+                         c->levels[level], cells_plan(c, level), c->cells.p, c->patch_idx.p, c->status.p, c->stream);
     return SDM_OK;
 }
 
@@ -224,7 +232,7 @@ int detect_level_fused(sdm_ctx* c, int l)
     {
         Timer t(c, SDM_T_HOG);
         sdm_launch_hog_cells(image_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->x[c->cur].p, c->N, c->L, c->eyes, lv,
-                             c->plans[l].dev, c->cells.p, c->patch_idx.p, c->status.p, c->stream);
+                             cells_plan(c, l), c->cells.p, c->patch_idx.p, c->status.p, c->stream);
     }
     {
         Timer t(c, SDM_T_APPLY);

@@ -105,6 +105,7 @@ struct sdm_ctx {
     bool split_store = false;       // option hog_split_store: feature rows through cells + sdm_desc.hip's store form (A/B, tests)
     bool fuse_apply = true;         // option detect_unfused: sdm_detect_batch through the feature matrix + apply GEMM (A/B)
     bool fuse_wide = false;         // sdm_debug_set_detect_path(fused = 2): fuse also when 2L > 64 (tests of the wide launch)
+    bool hog_two_load = false;      // option hog_two_load: the CELLS pixel kernel never takes its one-load row loop (A/B, tests)
     bool packing = true;            // sdm_debug_set_hog_packing / option hog_no_pack: run the one-patch-per-wave kernel instead
     // development switches, set by sdm_debug_set_option (the library reads no environment variable; names in sdm_capi_debug.hip)
     bool env_fuse_wide = false;     // option detect_fuse_wide: fuse descriptor + apply also when 2L > 64
@@ -311,6 +312,7 @@ ImageSetDev image_set(const sdm_ctx* c);
 int ensure_sample_buffers(sdm_ctx* c, int N);
 int check_sample_index(const sdm_ctx* c);
 bool packed_ok(const sdm_ctx* c, int level);
+bool split_ok(const sdm_ctx* c, int level);
 int hog_checks(sdm_ctx* c, int level);
 int launch_cells(sdm_ctx* c, int level);
 int do_hog(sdm_ctx* c, int level);

@@ -17,6 +17,7 @@
 // of a cut patch are the sum of two partial folds.
 #include "sdm_kernels.h"
 #include "sdm_hog_device.h"
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -25,6 +26,14 @@
 #define HP_ST 66                    /* column-row stride: 64 pixel columns + 2 (2 * 66 = 4 mod 32 dwords: the sixteen bin rows of a fold read fall into 8 banks) */
 #define HP_MINW 6                   /* __launch_bounds__ minimum waves per SIMD: <= 80 registers, with 6.6 KB of LDS per wave six waves fit */
 #define HP_MINW_CELLS 6             /* the CELLS form needs 5.1 KB of LDS per wave: seven waves per SIMD fit if the registers do (<= 72) */
+// Row carry (the CELLS instances specialised on the cell size): where the patch is enlarged, the lower source row of resized row y
+// is one of the two rows that row y - 1 already loaded and filtered, so a second row loop loads and filters the UPPER source row
+// only and selects the lower one from the two values it holds (a bit-field select, v_bitop3_b32 on gfx950, with a mask from the row table).  Which half-widths
+// qualify is decided per (level, h) by taps_table_kernel from the taps themselves; a wave picks its loop once, above the loop.
+// Per cell size: whether the instance carries the second loop (it adds 60 - 70 % to the instance's code), by measurement
+// (profiles/hog_row_carry.txt): cells 10 / 8 / 6 run 12 / 13 / 8 % faster with it at the shipped levels.  Cell 11 with it: 331.1 us
+// per launch against 331.1 without (at relative patch size 1.0, S = 55, 1 % of the faces have an enlarged patch) -- left out.
+__host__ __device__ constexpr bool hp_row_carry(int cell) { return cell == 10 || cell == 8 || cell == 6; }
 // (The ablation switches of rounds 3-6 -- HP_ABL = 1 ... 15: no folds, no read-modify-write, no image loads, conflict-free operand
 //  reads, ... -- are scripts/experiments/hog_packed_ablations.patch; scripts/r6_hog_lds_variants.sh applies it to a copy and builds
 //  the variants.  Their measurements: profiles/r04_hog_ablations.txt, profiles/r06_hog_lds.txt.)
@@ -235,6 +244,9 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
 
     // ---- per-coordinate taps of cv::resize: lane d computes coordinate d once (shared by rows and columns, by all patches) ----
     int tab_s, tab_w;                 // unclamped source index floor((d + 0.5) scale - 0.5), 11-bit weights c0 | c1 << 16
+    constexpr bool CARRY = CELLS && RAW && CELL > 0 && hp_row_carry(CELL);      // the instance has the one-load row loop
+    int carry_mask = 0;               // row d takes its lower source row from row d - 1's upper one (all ones) or lower one (zero)
+    bool carry = false;               // this wave's half-width is one-load eligible (wave-uniform)
     i32x4 row_ent;                    // vertical taps of row d as the row loop wants them: byte offsets of the two source rows
                                       // RELATIVE to the patch origin (rows clipped to the patch), the two weights << 12
     if (CELLS && plan.taps && h < SDM_SCALE_TAB) {      // the level's table of taps by half-width (taps_table_kernel): two 16-byte loads
@@ -242,6 +254,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         const i32x4 e0 = e[0], e1 = e[1];
         tab_s = e0.x; tab_w = e0.y;
         row_ent = (i32x4){e0.z * istride, e0.w * istride, e1.x, e1.y};
+        if (CARRY) { carry_mask = e1.z; carry = uni(e1.w) != 0 && !plan.two_load; }
     } else {
         const double scale = resize_scale(lv, h, sw);
         const ResizeTaps tp = resize_taps(lane < S ? lane : S - 1, scale, sw, area2);
@@ -264,9 +277,11 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     if (SPEC) {
         // specialised layout: entry e = {offsets of row e + 2, weights of row e}: the row loop wants exactly that pair at row e, in
         // ONE 16-byte broadcast read; the offsets of rows 0 and 1 (issued before the loop) sit in the last two entries
+        // (one-load loop: entry e = {offset of the UPPER source row of row e + 2, carry mask of row e, weights of row e})
         if (lane < S) {
             const int eo = lane >= 2 ? lane - 2 : lane + S - 2;
-            *(i32x2*)&rowtab[eo] = (i32x2){row_ent.x, row_ent.y};
+            if (CARRY && carry) { ((int*)&rowtab[eo])[0] = row_ent.y; ((int*)&rowtab[lane])[1] = carry_mask; }
+            else *(i32x2*)&rowtab[eo] = (i32x2){row_ent.x, row_ent.y};
             *((i32x2*)&rowtab[lane] + 1) = (i32x2){row_ent.z, row_ent.w};
         }
     } else if (lane < S + 2) rowtab[lane] = row_ent;
@@ -355,15 +370,27 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
             q0 = __builtin_amdgcn_raw_buffer_load_b16(img_rsrc, vb + rr.x, 0, 0);
             q1 = __builtin_amdgcn_raw_buffer_load_b16(img_rsrc, vb + rr.y, 0, 0);
         };
+        // (the two-load loop's rows keep their low four bits here: vertical() clears them; the one-load loop's filtered() clears them itself)
         auto horizontal = [&](unsigned short q0, unsigned short q1, int& H0, int& H1) {
             H0 = (int)__builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, spread_bytes(q0, spread_sel)), wpk2, 0u, false);
             H1 = (int)__builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, spread_bytes(q1, spread_sel)), wpk2, 0u, false);
         };
-        auto vertical = [&](int H0, int H1, int y) -> float {
+        // (`cut`: the low four bits of H0 and H1 are already cleared -- the one-load loop clears them once, when a row is filtered)
+        auto vertical = [&](int H0, int H1, int y, const bool cut = false) -> float {
             const i32x2 bb = *((const i32x2*)&rowtab[y] + 1);      // the row's two weights << 12
-            const int out = (int)((mul_hi_u24_vv((unsigned)bb.x, (unsigned)H0 & ~15u) + mul_hi_u24_vv((unsigned)bb.y, (unsigned)H1 & ~15u) + 2u) >> 2);
+            const unsigned m = cut ? ~0u : ~15u;
+            const int out = (int)((mul_hi_u24_vv((unsigned)bb.x, (unsigned)H0 & m) + mul_hi_u24_vv((unsigned)bb.y, (unsigned)H1 & m) + 2u) >> 2);
             return (float)out;
         };
+        // one-load loop: the image load of row y's upper source row, and the filtered rows it carries from pixel row to pixel row
+        auto issue_upper = [&](int y, unsigned short& q) {
+            q = __builtin_amdgcn_raw_buffer_load_b16(img_rsrc, vb + ((const int*)&rowtab[y >= 2 ? y - 2 : y + S - 2])[0], 0, 0);
+        };
+        auto filtered = [&](unsigned short q) -> int {
+            return (int)(__builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, spread_bytes(q, spread_sel)), wpk2, 0u, false) & ~15u);
+        };
+        int Hc0 = 0, Hc1 = 0;
+        unsigned short qlow = 0;      // the lower source row of row 0: the only row that loads two
         float rm2 = 0.0f, rm1 = 0.0f;
         constexpr unsigned bin_stride = ST * 8;
         unsigned char* const cbase0 = (unsigned char*)colrows + lane * 8;
@@ -493,15 +520,25 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
             wave_sync();
         };
         unsigned short q0[2], q1[2];
-        issue_row(0, q0[0], q1[0]);
-        issue_row(1, q0[1], q1[1]);
-        auto row_step = [&](const int j, const int y, const bool grad) __attribute__((always_inline)) {
+        auto row_step = [&](const int j, const int y, const bool grad, auto one_load) __attribute__((always_inline)) {
             int H0, H1;
-            horizontal(q0[j], q1[j], H0, H1);
-            if (!SPEC || y + 2 < S) issue_row(y + 2, q0[j], q1[j]);      // (generic: past the last row a harmless extra load of the last row)
+            if constexpr (decltype(one_load)::value) {
+                // no branch, lane read or compare here: the mask comes with the weights in the row's one broadcast LDS read
+                const int Hn = filtered(q1[j]);
+                if (y == 0) Hc0 = filtered(qlow);
+                else {
+                    const unsigned mk = (unsigned)((const int*)&rowtab[y])[1];
+                    Hc0 = (int)(((unsigned)Hc1 & mk) | ((unsigned)Hc0 & ~mk));
+                }
+                Hc1 = Hn; H0 = Hc0; H1 = Hc1;
+                if (y + 2 < S) issue_upper(y + 2, q1[j]);
+            } else {
+                horizontal(q0[j], q1[j], H0, H1);
+                if (!SPEC || y + 2 < S) issue_row(y + 2, q0[j], q1[j]);      // (generic: past the last row a harmless extra load of the last row)
+            }
             f32x2 qv = {0.0f, 0.0f};
             if (grad) qv = *pend_p;
-            const float r0 = vertical(H0, H1, y);
+            const float r0 = vertical(H0, H1, y, decltype(one_load)::value);
             if (grad) {
                 const int yy = y - 1;                      // gradient of row y - 1 (hog.c:616-672)
                 const float gx = from_right(rm1) - from_left(rm1);
@@ -549,19 +586,36 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
             }
             rm2 = rm1; rm1 = r0;
         };
-        row_step(0, 0, false);
-        row_step(1, 1, false);
-        if constexpr (CELL > 0) {
+        constexpr std::false_type two_loads{};
+        auto two_load_rows = [&]() __attribute__((always_inline)) {
+            issue_row(0, q0[0], q1[0]);
+            issue_row(1, q0[1], q1[1]);
+            row_step(0, 0, false, two_loads);
+            row_step(1, 1, false, two_loads);
+            if constexpr (CELL > 0) {
 #pragma unroll
-            for (int yrow = 2; yrow < SC; ++yrow) row_step(yrow & 1, yrow, true);
-        } else {
-            int yrow = 2;
-            for (; yrow + 1 < S; yrow += 2) {
-                row_step(0, yrow, true);
-                row_step(1, yrow + 1, true);
+                for (int yrow = 2; yrow < SC; ++yrow) row_step(yrow & 1, yrow, true, two_loads);
+            } else {
+                int yrow = 2;
+                for (; yrow + 1 < S; yrow += 2) {
+                    row_step(0, yrow, true, two_loads);
+                    row_step(1, yrow + 1, true, two_loads);
+                }
+                if (yrow < S) row_step(0, yrow, true, two_loads);
             }
-            if (yrow < S) row_step(0, yrow, true);
-        }
+        };
+        if constexpr (CARRY) {
+            if (carry) {      // wave-uniform, once per pass: the loops themselves hold no branch
+                constexpr std::true_type one_load{};
+                qlow = __builtin_amdgcn_raw_buffer_load_b16(img_rsrc, vb + __builtin_amdgcn_readlane(row_ent.x, 0), 0, 0);
+                issue_upper(0, q1[0]);
+                issue_upper(1, q1[1]);
+                row_step(0, 0, false, one_load);
+                row_step(1, 1, false, one_load);
+#pragma unroll
+                for (int yrow = 2; yrow < SC; ++yrow) row_step(yrow & 1, yrow, true, one_load);
+            } else two_load_rows();
+        } else two_load_rows();
         *pend_p = __builtin_elementwise_fma(pend_v, (f32x2){pend_g, pend_g}, *pend_p);
         if (CELLS && TO == 4 && prev_by >= 0 && prev_by + 1 <= C - 1) fold_band(prev_by, true);
         else {
@@ -593,9 +647,12 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
 }
 
 // cv::resize's taps depend on the level and on the patch half-width h only: one table per level, [h < SDM_SCALE_TAB][64 coordinates]
-// x {s0, c0 | c1 << 16, sy0, sy1, b0 << 12, b1 << 12, 0, 0}, built once per geometry by the device function the kernels used to call
+// x {s0, c0 | c1 << 16, sy0, sy1, b0 << 12, b1 << 12, carry mask, one-load eligible}, built once per geometry by the device function the kernels used to call
 // per wave (so the bits are the ones they computed).  Round 4: ~80 vector instructions (double-precision coordinate arithmetic,
 // conversions, clamps) per wave leave the pixel kernel's set-up -- a third of its instructions outside the row loop at the small levels.
+// Row carry: half-width h is one-load eligible when the lower source row sy0 of every resized row d >= 1 is one of the two rows
+// (sy0, sy1) of row d - 1 -- decided from the taps as computed here, clamped first row and clipped last rows included; never for an
+// empty patch or the exact-2x reduction.  The mask of row d says which: all ones = row d - 1's sy1, zero = its sy0.
 __global__ void taps_table_kernel(HogLevelDev lv, int* __restrict__ table)
 {
     const int h = blockIdx.x, d = threadIdx.x;
@@ -607,7 +664,10 @@ __global__ void taps_table_kernel(HogLevelDev lv, int* __restrict__ table)
     const ResizeTaps tp = resize_taps(d < S ? d : S - 1, scale, sw, area2);
     i32x4* e = (i32x4*)(table + ((size_t)h * 64 + d) * 8);
     e[0] = (i32x4){tp.s0, (tp.c0 & 0xffff) | (tp.c1 << 16), tp.sy0, tp.sy1};
-    e[1] = (i32x4){tp.b0 << 12, tp.b1 << 12, 0, 0};
+    const int p0 = __shfl_up(tp.sy0, 1), p1 = __shfl_up(tp.sy1, 1);      // (one wave per half-width)
+    const bool held = d == 0 || d >= S || tp.sy0 == p0 || tp.sy0 == p1;
+    const bool eligible = !empty && !area2 && __ballot(!held) == 0;
+    e[1] = (i32x4){tp.b0 << 12, tp.b1 << 12, (d >= 1 && tp.sy0 == p1) ? -1 : 0, eligible ? 1 : 0};
 }
 
 }  // namespace
@@ -662,6 +722,12 @@ void sdm_launch_hog_cells(const ImageSetDev& imgs, const int* img_idx, const flo
                           int* idx_out, int* status, hipStream_t stream)
 {
     launch_hog_packed<true>(imgs, img_idx, x, N, L, eyes, lv, plan, cells, 0, idx_out, status, stream);
+}
+
+// whether sdm_launch_hog_cells runs this level on an instance that holds the one-load row loop (the dispatch above)
+bool sdm_hog_cells_row_carry(const HogLevelDev& lv, const HogPlanDev& plan)
+{
+    return lv.O == 4 && plan.raw_sqrt && plan.taps && hp_row_carry(lv.cell);
 }
 
 void sdm_launch_taps_table(const HogLevelDev& lv, int* table, hipStream_t stream)

@@ -103,6 +103,7 @@ struct HogPlanDev {
     const unsigned short* wb16; // [pass][lane][2 k-blocks][2 pieces][8] float16 bits: the same weights x 2^10 as two float16 pieces in the layout of v_mfma_f32_16x16x32_f16's B operand (the float16 band folds of the specialised instances)
     const int* pass_info;
     const int* taps;           // [SDM_SCALE_TAB half-widths][64 coordinates][8] cv::resize taps of the level (sdm_launch_taps_table); null = computed per wave
+    int two_load;              // option hog_two_load: every wave takes the two-load row loop (A/B, tests); 0 = one-load loop where the half-width is eligible
 };
 // Cell row (band) of resized-ROI row d: floor((d + 0.5) / cell - 0.5) (hog.c:697-704) in integers, for the instances specialised
 // on the cell size; sdm_hog_plan_build checks it against the level's float table before such an instance is chosen.
@@ -132,6 +133,8 @@ void sdm_launch_hog_packed(const ImageSetDev& imgs, const int* img_idx, const fl
 void sdm_launch_hog_cells(const ImageSetDev& imgs, const int* img_idx, const float* x, int N, int L,
                           const EyeIdxDev& eyes, const HogLevelDev& lv, const HogPlanDev& plan, float* cells,
                           int* idx_out, int* status, hipStream_t stream);
+// the cells launch of this level runs an instance with the one-load row loop (sdm_hog_packed.hip: hp_row_carry)
+bool sdm_hog_cells_row_carry(const HogLevelDev& lv, const HogPlanDev& plan);
 
 // ---- raw cells -> descriptors (sdm_desc.hip) ----
 bool sdm_desc_supported(const HogLevelDev& lv);

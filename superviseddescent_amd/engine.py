@@ -59,7 +59,7 @@ def _ip(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
 
 
-_DEV_OPTIONS = ("hog_no_pack", "hog_split_store", "detect_unfused", "detect_fuse_wide", "apply_f32", "gram_f32", "gram_bf16x3", "update_f32",
+_DEV_OPTIONS = ("hog_no_pack", "hog_two_load", "hog_split_store", "detect_unfused", "detect_fuse_wide", "apply_f32", "gram_f32", "gram_bf16x3", "update_f32",
                 "gram_xblocks", "solve_upd_min_tiles", "solve_fine_head", "solve_bs_cap", "solve_shard_emulate")
 
 
@@ -637,6 +637,14 @@ class Context:
         n = max(int(out[7]), 1)
         names = ["setup", "clear", "rows", "barrier", "normalise", "store"]
         return {names[i]: out[i] / n for i in range(6)}, n
+
+    def debug_hog_taps(self, level: int):
+        """The level's cv::resize taps table as the device built it, [128 half-widths][64 coordinates][8], and
+        {cells_launch, one_load_instance, two_load_option} (include/sdm.h: sdm_debug_hog_taps)."""
+        table = np.empty((128, 64, 8), np.int32)
+        info = np.zeros(3, np.int32)
+        check(self._lib.sdm_debug_hog_taps(self._h, level, _ip(table), _ip(info)))
+        return table, dict(cells_launch=bool(info[0]), one_load_instance=bool(info[1]), two_load_option=bool(info[2]))
 
     def set_hog_packing(self, on: bool):
         """Lane packing of the HOG launch (include/sdm.h: sdm_debug_set_hog_packing); on by default."""
