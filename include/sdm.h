@@ -264,6 +264,33 @@ int sdm_solve_normal_equations_with(sdm_ctx* ctx, int solver, const float* A_hos
 int sdm_train_level(sdm_ctx* ctx, int level, int reg_type, float reg_param, int regularise_last_row,
                     long long n_train_global);
 
+/* Regulariser sweep of one level: K candidates of the one tuning parameter LinearRegressor has (Regulariser's param,
+ * regressors.hpp:126-148; set by hand in the reference, apps/rcr/data/rcr_training_22.cfg) for the price of one feature extraction and
+ * one Gram product.  Rows [0, n_fit_rows) of the current samples are the fit rows, rows [n_fit_rows, N) are held out
+ * (1 <= n_fit_rows < N, 1 <= K <= 32).  In order:
+ *   1. sdm_hog_features(level) and the targets for all N rows;
+ *   2. [A^T A | A^T b] over the fit rows only (sdm_gram_rhs' launches with n_fit_rows rows, its bf16 repeat included);
+ *   3. the tiles the product wrote are copied beside G; ||G||_F^2 (MatrixNorm) is taken once, from the unregularised matrix;
+ *   4. per candidate k: G restored, reg_params[k] added to the diagonal with n = n_train_global > 0 ? n_train_global : n_fit_rows,
+ *      factored and solved by sdm_solve's launches (either solver) -- R_k, lambdas[k] and status[k] are what sdm_solve would give on a
+ *      context holding the fit rows alone, bit for bit.  status[k] == SDM_ERR_NOT_SPD marks the candidate failed, the sweep goes on;
+ *   5. per solved candidate: R_k applied to the current x into scratch rows (sdm_apply's launch; the state x is not touched) and
+ *      holdout_err[k] = the mean of sdm_normalised_errors' matrix over the held-out rows, fit_err[k] (may be NULL) over the fit
+ *      rows: float32 entries as sdm_normalised_errors computes them, summed in double in a fixed order (two runs: the same bits).  A
+ *      failed candidate gets +inf;
+ *   6. *best = arg-min of holdout_err, ties to the lowest k; slot `best` becomes the level's regressor (a device copy) and is applied
+ *      to all N rows, as sdm_train_level ends.  If every candidate failed: SDM_ERR_NOT_SPD, *best = -1, and x, the level's regressor
+ *      and whether it has one stay as before the call.
+ * The Gram matrix does not survive the call (sdm_solve afterwards needs sdm_gram_rhs again).  Single rank only: with an all-reduce, a
+ * reduce-scatter or solve sharding installed on the handle the call returns SDM_ERR_INVALID (a multi-rank sweep would have to reduce the
+ * held-out sums as well).  The passes are timed under SDM_T_REG / SDM_T_FACTOR (scoring: SDM_T_APPLY), the snapshot under SDM_T_GRAM. */
+int sdm_train_level_sweep(sdm_ctx* ctx, int level, int reg_type, const float* reg_params, int K, int regularise_last_row,
+                          long long n_train_global, int n_fit_rows, double* holdout_err /* K */, double* fit_err /* K or NULL */,
+                          float* lambdas /* K */, int* status /* K */, int* best);
+/* Candidate k of the last sweep of this handle, F x M row-major like sdm_get_regressor (SDM_ERR_NOT_SPD for a failed candidate;
+ * SDM_ERR_INVALID when there is none: no sweep yet, k out of range, or the geometry was changed since). */
+int sdm_sweep_get_regressor(sdm_ctx* ctx, int k, float* R_host);
+
 /* Device views for collectives / zero-copy interop (valid until the next allocation-changing call). */
 int sdm_gram_device_ptr(sdm_ctx* ctx, void** dev_ptr, size_t* count_f32);
 int sdm_x_device_ptr(sdm_ctx* ctx, void** dev_ptr, size_t* count_f32);

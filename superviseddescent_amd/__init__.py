@@ -5,9 +5,9 @@ Product code.  The HIP kernels live in ``csrc/`` and are reached only through th
 ``include/sdm.h``; this package is the Python mirror of the reference's operator surface on top of it.
 """
 from .engine import (ColPivHouseholderQRSolver, Context, HoGParam, HogTransform, InterEyeDistanceNormalisation, LinearRegressor,
-                     ModelProjection, PartialPivLUSolver, Regulariser, SupervisedDescentOptimiser, Tracker, alignment_template,
+                     ModelProjection, PartialPivLUSolver, Regulariser, RegulariserSweep, SupervisedDescentOptimiser, Tracker, alignment_template,
                      detection_model)
 from ._lib import SdmError
 
 __all__ = ["ColPivHouseholderQRSolver", "PartialPivLUSolver", "Context", "HoGParam", "HogTransform", "InterEyeDistanceNormalisation", "LinearRegressor",
-           "ModelProjection", "Regulariser", "SupervisedDescentOptimiser", "Tracker", "alignment_template", "detection_model", "SdmError"]
+           "ModelProjection", "Regulariser", "RegulariserSweep", "SupervisedDescentOptimiser", "Tracker", "alignment_template", "detection_model", "SdmError"]

@@ -35,6 +35,7 @@ EXPORTED = [
     "sdm_pose_set_regressor", "sdm_pose_get_regressor", "sdm_pose_test",
     "sdm_track_configure", "sdm_track_start", "sdm_track_stop", "sdm_track_step", "sdm_track_get",
     "sdm_align_set_source", "sdm_align_crops",
+    "sdm_train_level_sweep", "sdm_sweep_get_regressor",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -191,6 +192,9 @@ def lib() -> ctypes.CDLL:
             "sdm_track_get": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
             "sdm_align_set_source": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int],
             "sdm_align_crops": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
+            "sdm_train_level_sweep": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int_p],
+            "sdm_sweep_get_regressor": [c_void_p, c_int, c_float_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

@@ -77,6 +77,7 @@ void sdm_destroy(sdm_ctx* c)
     c->pose.release();
     c->track.release();
     c->align.release();
+    c->sweep.release();
     for (auto& r : c->Rt) r.release();
     for (auto& q : c->plans) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); }
     if (c->own_stream) e = hipStreamDestroy(c->stream);
@@ -244,6 +245,7 @@ int sdm_set_model_geometry(sdm_ctx* c, int L, const int* re, int nre, const int*
     c->have_R.assign(n_levels, false);
     c->feat.release(); c->feat_level = -1; c->feat_wide_F = 0; c->feat_wide_N = 0; c->have_patch_idx = false;
     c->N = 0; c->have_targets = false; c->g_level = -1;
+    c->sweep.K = 0; c->sweep.level = -1; c->sweep.ok = 0;      // (the slots of the last sweep were laid out for the previous geometry)
     return SDM_OK;
 }
 

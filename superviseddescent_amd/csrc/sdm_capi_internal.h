@@ -5,7 +5,7 @@
 //   sdm_capi_context.hip   lifetime, geometry, images, samples            sdm_capi_detect.hip    features, regressors, apply, detect
 //   sdm_capi_train.hip     targets, Gram / right-hand side, solvers       sdm_capi_exchange.hip  the several-GPU exchange of the normal equations
 //   sdm_capi_debug.hip     device pointers, timing, debug entry points   sdm_capi_pose.hip / sdm_capi_track.hip  head pose, tracking
-//   sdm_capi_align.hip     aligned face crops
+//   sdm_capi_align.hip     aligned face crops                          sdm_capi_sweep.hip     regulariser sweep on one Gram product
 #pragma once
 #include "../../include/sdm.h"
 #include "sdm_kernels.h"
@@ -260,6 +260,21 @@ struct sdm_ctx {
         DevBuf<uint8_t> crops;             // the crops of a host-memory out
         void release() { in.release(); faces.release(); crops.release(); owned.release(); base = nullptr; n = 0; C = 1; }
     } align;
+    // regulariser sweep (sdm_capi_sweep.hip): the unregularised normal equations kept as packed tiles, one regressor slot per
+    // candidate (the apply GEMM's operand Rt + its float16 planes + their scale words) and the scoring scratch; allocated at the
+    // first sweep
+    struct Sweep {
+        DevBuf<float> snap;                // upper Gram tiles + right-hand-side tiles (the exchange buffer's layout)
+        DevBuf<float> Rt;                  // K slots of Mp x ldf
+        DevBuf<unsigned char> Rp;          // K slots of sdm_apply_planes_bytes
+        DevBuf<unsigned> Rmax;             // K slots of Mp scale words
+        DevBuf<float> x;                   // N x 2L: x_{k+1} of the candidate being scored (the state x is not touched)
+        DevBuf<double> score;              // 2 K means (held-out, fit) + the score kernel's partial sums
+        DevBuf<unsigned> arrived;          // per row range: workgroups of the score kernel that have delivered their partial sum
+        int K = 0, level = -1;             // candidates and level of the last sweep (K == 0: none); ok: bit k = candidate k solved
+        unsigned ok = 0;
+        void release() { snap.release(); Rt.release(); Rp.release(); Rmax.release(); x.release(); score.release(); arrived.release(); K = 0; level = -1; ok = 0; }
+    } sweep;
     // host copies of the image sizes and of the sample -> image index (the checks of an external crop source)
     std::vector<int> img_w_host, img_h_host, img_idx_host;
 
@@ -322,6 +337,8 @@ bool fused_ok(const sdm_ctx* c, int level);
 int detect_level_fused(sdm_ctx* c, int l);
 int detect_level(sdm_ctx* c, int l);
 int solve_update_scratch(sdm_ctx* c, int ncols);      // (sdm_capi_train.hip)
+int gram_rhs_rows(sdm_ctx* c, int level, int rows);   // (sdm_capi_train.hip)
+int qr_solve(sdm_ctx* c, float* G, int ncols, int F, int Fp, int Mp, float* R_out);      // (sdm_capi_train.hip)
 int shard_bcast_thunk(void* self, float* buf, size_t count, int root, hipStream_t stream);      // (sdm_capi_exchange.hip)
 int shard_allgather_thunk(void* self, const float* send, float* recv, size_t count, hipStream_t stream);
 

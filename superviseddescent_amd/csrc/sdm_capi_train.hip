@@ -14,6 +14,111 @@ int solve_update_scratch(sdm_ctx* c, int ncols)
     return SDM_OK;
 }
 
+// The body of sdm_gram_rhs for the first `rows` feature rows: the targets of ALL c->N rows are written, [A^T A | A^T b] is formed over
+// rows 0 .. rows - 1 (sdm_gram_rhs: rows = c->N; sdm_train_level_sweep: the fit rows, the held-out rows behind them stay out of the sums)
+int gram_rhs_rows(sdm_ctx* c, int level, int rows)
+{
+    const int F = level_F(c, level);
+    const int Fp = round_up(F, 128), ncols = Fp + 128 * c->rhs_tiles;
+    int rc = c->G.ensure((size_t)ncols * ncols);
+    if (rc) return rc;
+    c->g_scattered = false;
+    c->gram_blocks = 0;
+    Timer t(c, SDM_T_GRAM);
+    // the tail tile of every feature row holds b; clear it first (columns beyond 2L must be 0)
+    HIP_TRY(hipMemset2DAsync(c->feat.p + Fp, (size_t)c->ldf * sizeof(float), 0, 128 * c->rhs_tiles * sizeof(float), c->N, c->stream));
+    sdm_launch_targets(c->x[c->cur].p, c->xstar.p, c->N, c->L, c->eyes, c->feat.p, c->ldf, Fp, c->stream);
+    // Round 3: the Gram launch runs on the 16-bit matrix cores with float32 accuracy (sdm_gram_bf16.hip): every operand split into two
+    // float16 pieces (x 2^12), three piece products per product; should an operand leave float16's range -- a training target beyond
+    // 14 inter-eye distances -- the launch is repeated with three bf16 pieces (float32's range, six products).  SDM_GRAM_F32=1: the
+    // f32 matrix-core kernel of rounds 1-2 (A/B); SDM_GRAM_BF16X3=1: always the three-bf16 form.
+    const bool gram_f32 = c->env_gram_f32, gram_bf16 = c->env_gram_bf16;
+    // Scratch (ADVICE r03): the float16 form needs two planes (4 bytes per feature-matrix element); the third (bf16 repeat) is
+    // allocated only when a launch actually overflowed.  If the scratch cannot be had (the feature matrix of 100 000 x 27 392 is
+    // 11 GB, its planes another 11 / 16 GB) the f32 matrix-core kernel forms the Gram matrix from the rows in place.
+    int form = gram_f32 ? 0 : (gram_bf16 ? 3 : 2);      // pieces per operand; 0 = the f32 matrix-core kernel
+    if (form && c->gram_planes.ensure(sdm_gram_bf16x3_plane_bytes(rows, ncols, form))) { (void)hipGetLastError(); form = 0; c->gram_f32_fallbacks += 1; }
+    if (form == 3) sdm_launch_gram_bf16x3(c->feat.p, c->ldf, rows, ncols, c->gram_planes.p, c->G.p, ncols, c->stream);
+    else if (form == 2) {
+        if ((rc = c->gram_flag.ensure(1))) return rc;
+        HIP_TRY(hipMemsetAsync(c->gram_flag.p, 0, sizeof(int), c->stream));
+        // Ranges for the exchange behind the kernel: only when the level's exchange will be the reduce-scatter of owned tile columns
+        // (sdm_allreduce_gram_rhs decides by the same conditions).  Boundaries in owned column numbers, at equal shares of the tiles
+        // (the tiles of the first c columns grow with c^2).
+        const int Ttot = ncols / 128, Wx = c->shard_world;
+        const bool will_scatter = Wx >= 2 && (c->shard_comm || c->shard_bcast) && Wx == c->world_size &&
+                                  (c->reduce_scatter || (c->rccl_reduce_scatter && c->rccl_comm)) && c->solver_kind == SDM_SOLVER_CHOLESKY;
+        int nb = 1;
+        if (will_scatter) nb = c->env_xblocks > 0 ? c->env_xblocks : (c->env_xblocks < 0 && Ttot >= 128 ? 4 : 1);
+        const int ncolw = will_scatter ? (Ttot + Wx - 1) / Wx : 0;
+        if (nb > sdm_ctx::XBLOCKS_MAX) nb = sdm_ctx::XBLOCKS_MAX;
+        if (nb > ncolw) nb = ncolw > 0 ? ncolw : 1;
+        if (nb > 1) {
+            sdm_launch_gram_f16_split(c->feat.p, c->ldf, rows, ncols, c->gram_planes.p, c->stream, c->gram_flag.p);
+            int over = 0;
+            HIP_TRY(hipMemcpyAsync(&over, c->gram_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));      // (behind the split only: the products below are queued without a host wait)
+            if (!over) {
+                c->gram_block_c[0] = 0;
+                for (int b = 1; b < nb; ++b) {
+                    int cb = (int)(ncolw * sqrt((double)b / nb) + 0.5);
+                    if (cb <= c->gram_block_c[b - 1]) cb = c->gram_block_c[b - 1] + 1;
+                    c->gram_block_c[b] = cb < ncolw ? cb : ncolw;
+                }
+                c->gram_block_c[nb] = ncolw;
+                int off = 0;
+                for (int b = 0; b < nb; ++b) {
+                    const int j_lo = c->gram_block_c[b] * Wx, j_hi = b + 1 < nb ? c->gram_block_c[b + 1] * Wx : Ttot;
+                    off += sdm_launch_gram_f16_product(c->gram_planes.p, rows, ncols, c->G.p, ncols, j_lo, j_hi < Ttot ? j_hi : Ttot, off, c->stream);
+                    HIP_TRY(hipEventRecord(c->gram_ev[b], c->stream));
+                }
+                HIP_TRY(hipGetLastError());
+                c->gram_blocks = nb;
+                c->g_ncols = ncols; c->g_fp = Fp; c->g_level = level;
+                return SDM_OK;
+            }
+            // (an operand left float16's range: the bf16 repeat below, in one piece)
+            c->gram_fallbacks += 1;
+            if (c->gram_planes.ensure(sdm_gram_bf16x3_plane_bytes(rows, ncols, 3))) { (void)hipGetLastError(); form = 0; c->gram_f32_fallbacks += 1; }
+            else sdm_launch_gram_bf16x3(c->feat.p, c->ldf, rows, ncols, c->gram_planes.p, c->G.p, ncols, c->stream);
+            if (form == 0) sdm_launch_syrk_tn(c->feat.p, c->ldf, rows, ncols, c->G.p, ncols, 1.0f, 0, 0, c->stream);
+            HIP_TRY(hipGetLastError());
+            c->g_ncols = ncols; c->g_fp = Fp; c->g_level = level;
+            return SDM_OK;
+        }
+        sdm_launch_gram_bf16x3(c->feat.p, c->ldf, rows, ncols, c->gram_planes.p, c->G.p, ncols, c->stream, c->gram_flag.p);
+        // (one 4-byte read-back per level: the only host wait of sdm_train_level; the queue is idle for ~0.1 ms of a 40 ... 300 ms level)
+        int over = 0;
+        HIP_TRY(hipMemcpyAsync(&over, c->gram_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (over) {
+            c->gram_fallbacks += 1;
+            if (c->gram_planes.ensure(sdm_gram_bf16x3_plane_bytes(rows, ncols, 3))) { (void)hipGetLastError(); form = 0; c->gram_f32_fallbacks += 1; }
+            else sdm_launch_gram_bf16x3(c->feat.p, c->ldf, rows, ncols, c->gram_planes.p, c->G.p, ncols, c->stream);
+        }
+    }
+    if (form == 0) sdm_launch_syrk_tn(c->feat.p, c->ldf, rows, ncols, c->G.p, ncols, 1.0f, 0, 0, c->stream);
+    HIP_TRY(hipGetLastError());
+    c->g_ncols = ncols; c->g_fp = Fp; c->g_level = level;
+    return SDM_OK;
+}
+
+// ColPivHouseholderQRSolver (regressors.hpp:287-296) on [G | At b]; the rank is read back (one int) for sdm_last_rank
+int qr_solve(sdm_ctx* c, float* G, int ncols, int F, int Fp, int Mp, float* R_out)
+{
+    if (!sdm_colpiv_qr_supported(F)) return fail(SDM_ERR_INVALID, "column-pivoted QR: at most 38 400 features (a solution column is kept in LDS)");
+    int rc;
+    if ((rc = c->qr_work.ensure(sdm_colpiv_qr_work_floats(F)))) return rc;
+    int* rank_dev = nullptr;
+    sdm_launch_colpiv_qr_solve(G, ncols, F, Fp, Mp, R_out, Mp, Fp, c->qr_work.p, &rank_dev, c->stream);
+    HIP_TRY(hipGetLastError());
+    int rank = -1;
+    HIP_TRY(hipMemcpyAsync(&rank, rank_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_rank = rank; c->last_rank_full = F;
+    return SDM_OK;
+}
+
 }  // namespace sdm_capi
 
 extern "C" {
@@ -36,109 +141,8 @@ int sdm_gram_rhs(sdm_ctx* c, int level)
     if (c->feat_level != level) return fail(SDM_ERR_INVALID, "sdm_gram_rhs: features of this level not extracted");
     if (!c->have_targets) return fail(SDM_ERR_INVALID, "sdm_gram_rhs: no targets set");
     HIP_TRY(hipSetDevice(c->device));
-    const int F = level_F(c, level);
-    const int Fp = round_up(F, 128), ncols = Fp + 128 * c->rhs_tiles;
-    int rc = c->G.ensure((size_t)ncols * ncols);
-    if (rc) return rc;
-    c->g_scattered = false;
-    c->gram_blocks = 0;
-    Timer t(c, SDM_T_GRAM);
-    // the tail tile of every feature row holds b; clear it first (columns beyond 2L must be 0)
-    HIP_TRY(hipMemset2DAsync(c->feat.p + Fp, (size_t)c->ldf * sizeof(float), 0, 128 * c->rhs_tiles * sizeof(float), c->N, c->stream));
-    sdm_launch_targets(c->x[c->cur].p, c->xstar.p, c->N, c->L, c->eyes, c->feat.p, c->ldf, Fp, c->stream);
-    // Round 3: the Gram launch runs on the 16-bit matrix cores with float32 accuracy (sdm_gram_bf16.hip): every operand split into two
-    // float16 pieces (x 2^12), three piece products per product; should an operand leave float16's range -- a training target beyond
-    // 14 inter-eye distances -- the launch is repeated with three bf16 pieces (float32's range, six products).  SDM_GRAM_F32=1: the
-    // f32 matrix-core kernel of rounds 1-2 (A/B); SDM_GRAM_BF16X3=1: always the three-bf16 form.
-    const bool gram_f32 = c->env_gram_f32, gram_bf16 = c->env_gram_bf16;
-    // Scratch (ADVICE r03): the float16 form needs two planes (4 bytes per feature-matrix element); the third (bf16 repeat) is
-    // allocated only when a launch actually overflowed.  If the scratch cannot be had (the feature matrix of 100 000 x 27 392 is
-    // 11 GB, its planes another 11 / 16 GB) the f32 matrix-core kernel forms the Gram matrix from the rows in place.
-    int form = gram_f32 ? 0 : (gram_bf16 ? 3 : 2);      // pieces per operand; 0 = the f32 matrix-core kernel
-    if (form && c->gram_planes.ensure(sdm_gram_bf16x3_plane_bytes(c->N, ncols, form))) { (void)hipGetLastError(); form = 0; c->gram_f32_fallbacks += 1; }
-    if (form == 3) sdm_launch_gram_bf16x3(c->feat.p, c->ldf, c->N, ncols, c->gram_planes.p, c->G.p, ncols, c->stream);
-    else if (form == 2) {
-        if ((rc = c->gram_flag.ensure(1))) return rc;
-        HIP_TRY(hipMemsetAsync(c->gram_flag.p, 0, sizeof(int), c->stream));
-        // Ranges for the exchange behind the kernel: only when the level's exchange will be the reduce-scatter of owned tile columns
-        // (sdm_allreduce_gram_rhs decides by the same conditions).  Boundaries in owned column numbers, at equal shares of the tiles
-        // (the tiles of the first c columns grow with c^2).
-        const int Ttot = ncols / 128, Wx = c->shard_world;
-        const bool will_scatter = Wx >= 2 && (c->shard_comm || c->shard_bcast) && Wx == c->world_size &&
-                                  (c->reduce_scatter || (c->rccl_reduce_scatter && c->rccl_comm)) && c->solver_kind == SDM_SOLVER_CHOLESKY;
-        int nb = 1;
-        if (will_scatter) nb = c->env_xblocks > 0 ? c->env_xblocks : (c->env_xblocks < 0 && Ttot >= 128 ? 4 : 1);
-        const int ncolw = will_scatter ? (Ttot + Wx - 1) / Wx : 0;
-        if (nb > sdm_ctx::XBLOCKS_MAX) nb = sdm_ctx::XBLOCKS_MAX;
-        if (nb > ncolw) nb = ncolw > 0 ? ncolw : 1;
-        if (nb > 1) {
-            sdm_launch_gram_f16_split(c->feat.p, c->ldf, c->N, ncols, c->gram_planes.p, c->stream, c->gram_flag.p);
-            int over = 0;
-            HIP_TRY(hipMemcpyAsync(&over, c->gram_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(hipStreamSynchronize(c->stream));      // (behind the split only: the products below are queued without a host wait)
-            if (!over) {
-                c->gram_block_c[0] = 0;
-                for (int b = 1; b < nb; ++b) {
-                    int cb = (int)(ncolw * sqrt((double)b / nb) + 0.5);
-                    if (cb <= c->gram_block_c[b - 1]) cb = c->gram_block_c[b - 1] + 1;
-                    c->gram_block_c[b] = cb < ncolw ? cb : ncolw;
-                }
-                c->gram_block_c[nb] = ncolw;
-                int off = 0;
-                for (int b = 0; b < nb; ++b) {
-                    const int j_lo = c->gram_block_c[b] * Wx, j_hi = b + 1 < nb ? c->gram_block_c[b + 1] * Wx : Ttot;
-                    off += sdm_launch_gram_f16_product(c->gram_planes.p, c->N, ncols, c->G.p, ncols, j_lo, j_hi < Ttot ? j_hi : Ttot, off, c->stream);
-                    HIP_TRY(hipEventRecord(c->gram_ev[b], c->stream));
-                }
-                HIP_TRY(hipGetLastError());
-                c->gram_blocks = nb;
-                c->g_ncols = ncols; c->g_fp = Fp; c->g_level = level;
-                return SDM_OK;
-            }
-            // (an operand left float16's range: the bf16 repeat below, in one piece)
-            c->gram_fallbacks += 1;
-            if (c->gram_planes.ensure(sdm_gram_bf16x3_plane_bytes(c->N, ncols, 3))) { (void)hipGetLastError(); form = 0; c->gram_f32_fallbacks += 1; }
-            else sdm_launch_gram_bf16x3(c->feat.p, c->ldf, c->N, ncols, c->gram_planes.p, c->G.p, ncols, c->stream);
-            if (form == 0) sdm_launch_syrk_tn(c->feat.p, c->ldf, c->N, ncols, c->G.p, ncols, 1.0f, 0, 0, c->stream);
-            HIP_TRY(hipGetLastError());
-            c->g_ncols = ncols; c->g_fp = Fp; c->g_level = level;
-            return SDM_OK;
-        }
-        sdm_launch_gram_bf16x3(c->feat.p, c->ldf, c->N, ncols, c->gram_planes.p, c->G.p, ncols, c->stream, c->gram_flag.p);
-        // (one 4-byte read-back per level: the only host wait of sdm_train_level; the queue is idle for ~0.1 ms of a 40 ... 300 ms level)
-        int over = 0;
-        HIP_TRY(hipMemcpyAsync(&over, c->gram_flag.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (over) {
-            c->gram_fallbacks += 1;
-            if (c->gram_planes.ensure(sdm_gram_bf16x3_plane_bytes(c->N, ncols, 3))) { (void)hipGetLastError(); form = 0; c->gram_f32_fallbacks += 1; }
-            else sdm_launch_gram_bf16x3(c->feat.p, c->ldf, c->N, ncols, c->gram_planes.p, c->G.p, ncols, c->stream);
-        }
-    }
-    if (form == 0) sdm_launch_syrk_tn(c->feat.p, c->ldf, c->N, ncols, c->G.p, ncols, 1.0f, 0, 0, c->stream);
-    HIP_TRY(hipGetLastError());
-    c->g_ncols = ncols; c->g_fp = Fp; c->g_level = level;
-    return SDM_OK;
+    return gram_rhs_rows(c, level, c->N);
 }
-
-
-namespace {
-// ColPivHouseholderQRSolver (regressors.hpp:287-296) on [G | At b]; the rank is read back (one int) for sdm_last_rank
-int qr_solve(sdm_ctx* c, float* G, int ncols, int F, int Fp, int Mp, float* R_out)
-{
-    if (!sdm_colpiv_qr_supported(F)) return fail(SDM_ERR_INVALID, "column-pivoted QR: at most 38 400 features (a solution column is kept in LDS)");
-    int rc;
-    if ((rc = c->qr_work.ensure(sdm_colpiv_qr_work_floats(F)))) return rc;
-    int* rank_dev = nullptr;
-    sdm_launch_colpiv_qr_solve(G, ncols, F, Fp, Mp, R_out, Mp, Fp, c->qr_work.p, &rank_dev, c->stream);
-    HIP_TRY(hipGetLastError());
-    int rank = -1;
-    HIP_TRY(hipMemcpyAsync(&rank, rank_dev, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->last_rank = rank; c->last_rank_full = F;
-    return SDM_OK;
-}
-}  // namespace
 
 int sdm_set_solver(sdm_ctx* c, int solver)
 {

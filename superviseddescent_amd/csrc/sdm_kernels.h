@@ -237,6 +237,18 @@ void sdm_launch_small_exchange_pack(const double* fro2, float* d_tail, int unpac
 void sdm_launch_add_diag(float* G, long long ldg, int F, const double* fro2, int reg_type, float param,
                          int n_train, int regularise_last_row, float* lambda_out, hipStream_t stream);
 
+// ---- regulariser sweep (sdm_sweep.hip) ----
+// The tiles of sdm_packed_tiles_count() in the exchange buffer's order (tile row ti: tiles tj >= ti, then the right-hand-side tiles;
+// each tile row-major) -> snap, and back into G (restore): one workgroup per tile, 16-byte accesses on both sides.
+void sdm_launch_sweep_snapshot(const float* G, long long ldg, int F, int rhs_tiles, float* snap, hipStream_t stream);
+void sdm_launch_sweep_restore(float* G, long long ldg, int F, int rhs_tiles, const float* snap, hipStream_t stream);
+// Means of err[n][i] = ||x_i - xstar_i|| / IED(x[n]) (sdm_launch_landmark_errors' float32 arithmetic) over the rows [n_fit, N)
+// -> out[0] and [0, n_fit) -> out[1], summed in double in a fixed order, in ONE launch.  part: 2 * SDM_SWEEP_SCORE_PARTS doubles;
+// arrived: 2 counters, zero before the first launch (the kernel leaves them zero).
+#define SDM_SWEEP_SCORE_PARTS 128
+void sdm_launch_sweep_score(const float* x, const float* xstar, int N, int n_fit, int L, const EyeIdxDev& eyes, double* part,
+                            unsigned* arrived, double* out, hipStream_t stream);
+
 // Blocked Cholesky G = U^T U on the upper triangle of the leading F x F block, with the
 // forward substitution fused into the panel updates for the extra columns [rhs0, rhs0+nrhs),
 // then back substitution; R_out [F][ldr].  work: ceil(F/128) * 128 * 128 floats (inverted diagonal tiles) + sdm_backsolve_flag_floats(Fp)

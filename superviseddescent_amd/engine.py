@@ -414,6 +414,32 @@ class Context:
         check(self._lib.sdm_train_level(self._h, level, reg_type, reg_param, int(regularise_last_row),
                                         n_train_global))
 
+    def train_level_sweep(self, level: int, reg_type: int, reg_params, regularise_last_row: bool, n_fit_rows: int,
+                          n_train_global: int = 0):
+        """One training level with K regulariser candidates on ONE feature extraction and Gram product (include/sdm.h:
+        sdm_train_level_sweep): rows [0, n_fit_rows) are fitted, the rows behind them held out; the candidate with the lowest
+        held-out mean normalised error becomes the level's regressor and is applied to all rows.  Returns a dict: ``params``,
+        ``lambdas``, ``holdout_errors``, ``fit_errors`` (float64, +inf for a failed candidate), ``status`` (0 or SDM_ERR_NOT_SPD per
+        candidate), ``best``.  If every candidate failed the call raises SdmError(SDM_ERR_NOT_SPD) and the state is untouched."""
+        params = np.ascontiguousarray(np.atleast_1d(np.asarray(reg_params, np.float32)).reshape(-1))
+        K = int(params.size)
+        hold, fit = np.full(max(K, 1), np.inf, np.float64), np.full(max(K, 1), np.inf, np.float64)
+        lam, status = np.zeros(max(K, 1), np.float32), np.zeros(max(K, 1), np.int32)
+        best = ctypes.c_int(-1)
+        self._resident.pop(level, None)                     # the device copy of this level is overwritten
+        check(self._lib.sdm_train_level_sweep(self._h, level, int(reg_type), params.ctypes.data, K, int(bool(regularise_last_row)),
+                                              int(n_train_global), int(n_fit_rows), hold.ctypes.data, fit.ctypes.data,
+                                              lam.ctypes.data, status.ctypes.data, ctypes.byref(best)))
+        self._sweep_level = level
+        return {"params": params, "lambdas": lam[:K], "holdout_errors": hold[:K], "fit_errors": fit[:K], "status": status[:K],
+                "best": int(best.value)}
+
+    def sweep_regressor(self, k: int) -> np.ndarray:
+        """Candidate ``k`` of the last ``train_level_sweep`` (F x 2L, as ``get_regressor``)."""
+        out = np.empty((self.feature_dim(getattr(self, "_sweep_level", 0)), 2 * self.L), np.float32)
+        check(self._lib.sdm_sweep_get_regressor(self._h, int(k), _fp(out)))
+        return out
+
     # -- head pose (sdm_pose_*: the ModelProjection cascade, state beside the landmark state) -------------------------------
     def pose_set_model(self, points: np.ndarray, focal: float = 1800.0, width: float = 1000.0, height: float = 1000.0,
                        near: float = 1.0, far: float = 5000.0):
@@ -707,6 +733,20 @@ class Regulariser:
         self.regularise_last_row = bool(regularise_last_row)
 
 
+class RegulariserSweep(Regulariser):
+    """K candidates of ``Regulariser``'s one parameter, chosen per level by the error on held-out rows
+    (``SupervisedDescentOptimiser.train(..., holdout=h)``; include/sdm.h: sdm_train_level_sweep).  Usable wherever a
+    ``Regulariser`` is: after training ``param`` is the winner's, so the object then reads as the plain regulariser that was
+    picked."""
+
+    def __init__(self, regularisation_type: int = 0, params: Sequence[float] = (0.0,), regularise_last_row: bool = True):
+        params = [float(p) for p in np.atleast_1d(np.asarray(params, np.float64)).reshape(-1)]
+        if not 1 <= len(params) <= 32:
+            raise ValueError("a RegulariserSweep holds 1 ... 32 candidate parameters")
+        super().__init__(regularisation_type, params[0], regularise_last_row)
+        self.params = params
+
+
 class _ResidentToken:
     """What a Context's device copy of one level holds: THE array object (a strong reference, so its id cannot be reused by
     another array) and the regressor's version when it was uploaded."""
@@ -760,6 +800,7 @@ class LinearRegressor:
         self._frozen = None          # (array, its original writeable flag) while a device copy exists
         self.regulariser = regulariser or Regulariser()
         self.last_lambda: Optional[float] = None
+        self.sweep: Optional[dict] = None       # the record of train(..., holdout=h): Context.train_level_sweep's dict
 
     @property
     def x(self) -> Optional[np.ndarray]:
@@ -935,19 +976,37 @@ class SupervisedDescentOptimiser:
     def train(self, parameters, initialisations, templates, projection: HogTransform,
               on_training_epoch_callback: Optional[Callable[[np.ndarray], None]] = None,
               allreduce=None, world_size: int = 1, n_train_global: int = 0, rank: Optional[int] = None,
-              solve_collectives=None, reduce_scatter=None, rccl=None, rccl_shard_solve: bool = False):
-        """``rank`` + ``solve_collectives = (bcast, allgather)`` (parallel.make_torch_solve_collectives) additionally shard the
+              solve_collectives=None, reduce_scatter=None, rccl=None, rccl_shard_solve: bool = False, holdout: int = 0):
+        """``holdout = h`` holds the LAST ``h`` rows out of every level's fit: a level whose regressor carries a ``RegulariserSweep``
+        tries all its candidates on one Gram product and keeps the one with the lowest mean normalised error on those rows
+        (``reg.sweep`` records params, lambdas, holdout_errors, fit_errors, status, best); a level with a plain ``Regulariser`` is
+        a sweep of one candidate, so the cascade sees one split.  Single device only (no collective arguments).
+
+        ``rank`` + ``solve_collectives = (bcast, allgather)`` (parallel.make_torch_solve_collectives) additionally shard the
         factorisation of the summed system over the ranks (Context.set_solve_sharding); without them every rank solves it.
         ``reduce_scatter`` (parallel.make_torch_reduce_scatter) then replaces the all-reduce of the whole Gram matrix by a
         reduce-scatter of the owned tile columns + a small all-reduce (Context.set_reduce_scatter).
         ``rccl`` (a ``parallel.RcclCommunicator``) takes the place of all three callbacks: the library then issues the collectives
         itself through RCCL on its own streams (``rccl_shard_solve``: sharded factorisation + reduce-scatter exchange); the
         callbacks remain for backends without RCCL (the gloo tests)."""
+        sweeping = any(isinstance(reg.regulariser, RegulariserSweep) for reg in self.regressors)
+        collective = allreduce is not None or rccl is not None or solve_collectives is not None or reduce_scatter is not None
+        holdout = int(holdout or 0)
+        if holdout < 0:
+            raise ValueError("holdout must be a row count >= 0")
+        if sweeping and not holdout:
+            raise ValueError("a RegulariserSweep needs held-out rows to choose by: train(..., holdout=h)")
+        if (sweeping or holdout) and collective:
+            raise ValueError("a regulariser sweep / holdout runs on one device: no collective arguments")
+        if (sweeping or holdout) and isinstance(projection, ModelProjection):
+            raise ValueError("the pose cascade has no regulariser sweep / holdout")
         if isinstance(projection, ModelProjection):
-            if allreduce is not None or rccl is not None or solve_collectives is not None or reduce_scatter is not None:
+            if collective:
                 raise ValueError("pose training runs on one device")
             return self._pose_train(parameters, initialisations, templates, projection, on_training_epoch_callback)
         x0 = np.asarray(initialisations, np.float32)
+        if holdout and not 1 <= holdout < x0.shape[0]:
+            raise ValueError("holdout must leave at least one row to fit and hold at least one out")
         self._bind(projection, x0.shape[0])
         c = self.ctx
         c.set_templates(templates)                                           # superviseddescent.hpp:195-197
@@ -969,6 +1028,8 @@ class SupervisedDescentOptimiser:
                         c.set_solve_sharding(0, 0, None, None)
                 if hasattr(c, "set_reduce_scatter"):
                     c.set_reduce_scatter(reduce_scatter if (solve_collectives is not None and rank is not None) else None)
+            if holdout:
+                return self._train_levels_holdout(c, x0.shape[0] - holdout, n_train_global, on_training_epoch_callback)
             return self._train_levels(c, n_glob, on_training_epoch_callback)
         finally:
             if hasattr(c, "set_solver"):
@@ -993,6 +1054,27 @@ class SupervisedDescentOptimiser:
             c.apply(level)                                                   # :209-216
             if on_training_epoch_callback is not None:
                 on_training_epoch_callback(c.get_x())                        # :217
+        return c.get_x()
+
+    def _train_levels_holdout(self, c, n_fit, n_train_global, on_training_epoch_callback):
+        """Every level fits rows [0, n_fit) and is scored on the rows behind them (Context.train_level_sweep); the winner is
+        installed and applied on the device, its coefficients fetched once."""
+        for level, reg in enumerate(self.regressors):
+            kind = getattr(reg.solver, "kind", 0)
+            c.set_solver(kind)
+            r = reg.regulariser
+            params = r.params if isinstance(r, RegulariserSweep) else [r.param]
+            rec = c.train_level_sweep(level, r.regularisation_type, params, r.regularise_last_row, n_fit, n_train_global)
+            best = rec["best"]
+            reg.x, reg.last_lambda = c.get_regressor(level), float(rec["lambdas"][best])
+            if isinstance(r, RegulariserSweep):
+                r.param = float(r.params[best])
+            reg.sweep = rec
+            if kind == 1 and hasattr(c, "last_rank"):
+                reg.solver._report(c)
+            self._mark_resident(level, reg)                                  # (the sweep installed the winner on the device)
+            if on_training_epoch_callback is not None:
+                on_training_epoch_callback(c.get_x())
         return c.get_x()
 
     def _mark_resident(self, level: int, reg: LinearRegressor):

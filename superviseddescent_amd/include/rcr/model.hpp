@@ -140,6 +140,7 @@ struct HogBackend {
         hip::install_data_parallel(c);
         const long long n_global = hip::data_parallel().n_train_global > 0 ? hip::data_parallel().n_train_global : x0.rows;
         for (size_t level = 0; level < regressors.size(); ++level) {
+            if (regressors[level].has_sweep()) throw std::invalid_argument("a RegulariserSweep needs held-out rows to choose by: train(..., callback, holdout)");
             const Regulariser& r = regressors[level].get_regulariser();
             hip::check(sdm_hog_features(c, (int)level, nullptr), "sdm_hog_features");
             hip::check(sdm_gram_rhs(c, (int)level), "sdm_gram_rhs");
@@ -151,6 +152,43 @@ struct HogBackend {
                        "sdm_solve");
             regressors[level].x = R;
             hip::check(sdm_apply(c, (int)level), "sdm_apply");
+            on_training_epoch_callback(fetch_x(c, x0.rows, x0.cols));
+        }
+    }
+
+    /** train() with the last `holdout` rows held out of every level's fit: per level one sdm_train_level_sweep over the regressor's
+     *  candidates (a plain Regulariser: its one parameter), the winner installed and applied on the device.  One rank only. */
+    static constexpr bool supports_holdout = true;
+    template <class Callback>
+    static void train_holdout(Regressors& regressors, Normalisation&, cv::Mat parameters, cv::Mat initialisations,
+                              cv::Mat templates, Hog& hog, Callback on_training_epoch_callback, int holdout)
+    {
+        const hip::DataParallel& dp = hip::data_parallel();
+        if (dp.fn || dp.rccl_comm || dp.rank >= 0) throw std::invalid_argument("train(..., holdout): a regulariser sweep runs on one rank (clear_data_parallel)");
+        if (holdout < 1 || holdout >= initialisations.rows) throw std::invalid_argument("train(..., holdout): 1 <= holdout < rows required");
+        hip::Handle h(hip::device());
+        sdm_ctx* c = h.get();
+        cv::Mat x0 = initialisations.isContinuous() ? initialisations : initialisations.clone();
+        cv::Mat xs = parameters.isContinuous() ? parameters : parameters.clone();
+        bind(h, hog, x0.rows, x0.cols / 2, regressors.size());
+        set_templates(c, templates, x0.rows);
+        hip::check(sdm_set_x(c, x0.ptr<float>(0), x0.rows), "sdm_set_x");
+        hip::check(sdm_set_targets(c, xs.ptr<float>(0), xs.rows), "sdm_set_targets");
+        for (size_t level = 0; level < regressors.size(); ++level) {
+            const Regulariser& r = regressors[level].get_regulariser();
+            SweepRecord rec;
+            rec.params = regressors[level].has_sweep() ? regressors[level].get_sweep_params() : std::vector<float>(1, r.param());
+            const int K = (int)rec.params.size();
+            rec.lambdas.assign((size_t)K, 0.0f); rec.holdout_errors.assign((size_t)K, 0.0); rec.fit_errors.assign((size_t)K, 0.0);
+            rec.status.assign((size_t)K, 0);
+            hip::check(sdm_train_level_sweep(c, (int)level, reg_type_of(r), rec.params.data(), K, r.regularises_last_row() ? 1 : 0, 0,
+                                             x0.rows - holdout, rec.holdout_errors.data(), rec.fit_errors.data(), rec.lambdas.data(),
+                                             rec.status.data(), &rec.best),
+                       "sdm_train_level_sweep");
+            cv::Mat R(sdm_feature_dim(c, (int)level), x0.cols, CV_32FC1);
+            hip::check(sdm_get_regressor(c, (int)level, R.ptr<float>(0)), "sdm_get_regressor");
+            regressors[level].x = R;
+            regressors[level].set_sweep(std::move(rec));
             on_training_epoch_callback(fetch_x(c, x0.rows, x0.cols));
         }
     }

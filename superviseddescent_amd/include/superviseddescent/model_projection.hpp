@@ -152,6 +152,7 @@ struct BatchedBackend<ModelProjection, LinearRegressor<Solver>, NoNormalisation,
         bind(c, projection, x0, templates, regressors.size());
         hip::check(sdm_pose_set_targets(c, xs.ptr<float>(0), xs.rows), "sdm_pose_set_targets");
         for (size_t level = 0; level < regressors.size(); ++level) {
+            if (regressors[level].has_sweep()) throw std::invalid_argument("the pose cascade has no regulariser sweep");
             const Regulariser& r = regressors[level].get_regulariser();
             cv::Mat R(2 * projection.num_points(), 6, CV_32FC1);
             hip::check(sdm_pose_train_level(c, (int)level, r.type() == Regulariser::RegularisationType::MatrixNorm ? SDM_REG_MATRIX_NORM : SDM_REG_MANUAL,

@@ -30,6 +30,8 @@
 #include <cmath>
 #include <iostream>
 #include <limits>
+#include <stdexcept>
+#include <utility>
 #include <vector>
 
 namespace superviseddescent {
@@ -89,6 +91,37 @@ private:
     RegularisationType regularisation_type;
     float lambda;
     bool regularise_last_row;
+};
+
+/** K candidates of Regulariser's one parameter for one cascade level (an extension: the reference sets the value by hand,
+ *  apps/rcr/data/rcr_training_22.cfg).  A LinearRegressor constructed from it is trained by the batched device path with
+ *  SupervisedDescentOptimiser::train(..., callback, holdout): all candidates share one feature extraction and one Gram product, the
+ *  one with the lowest mean normalised error on the held-out rows is kept (include/sdm.h: sdm_train_level_sweep). */
+class RegulariserSweep {
+public:
+    RegulariserSweep(Regulariser::RegularisationType regularisation_type, std::vector<float> params, bool regularise_last_row = true)
+        : regularisation_type(regularisation_type), candidates(std::move(params)), regularise_last_row(regularise_last_row)
+    {
+        if (candidates.empty() || candidates.size() > 32) throw std::invalid_argument("RegulariserSweep: 1 ... 32 candidate parameters");
+    }
+    Regulariser::RegularisationType type() const { return regularisation_type; }
+    const std::vector<float>& params() const { return candidates; }
+    bool regularises_last_row() const { return regularise_last_row; }
+
+private:
+    Regulariser::RegularisationType regularisation_type;
+    std::vector<float> candidates;
+    bool regularise_last_row;
+};
+
+/** What a sweep leaves on its regressor: per candidate the parameter, the lambda added to the diagonal, the mean normalised error
+ *  on the held-out and on the fit rows (+inf for a failed candidate) and the solve's status (SDM_OK or SDM_ERR_NOT_SPD); best = the
+ *  arg-min of holdout_errors (ties: the lowest index), -1 before any sweep. */
+struct SweepRecord {
+    std::vector<float> params, lambdas;
+    std::vector<double> holdout_errors, fit_errors;
+    std::vector<int> status;
+    int best = -1;
 };
 
 namespace detail {
@@ -330,9 +363,14 @@ template <class Solver = PartialPivLUSolver>
 class LinearRegressor : public Regressor {
 public:
     LinearRegressor(Regulariser regulariser = Regulariser()) : x(), regulariser(regulariser) {}
+    /** A level whose regulariser is chosen among `sweep`'s candidates by held-out error (batched device path only). */
+    LinearRegressor(RegulariserSweep sweep)
+        : x(), regulariser(sweep.type(), sweep.params()[0], sweep.regularises_last_row()), sweep_candidates(sweep.params()) {}
 
     bool learn(cv::Mat data, cv::Mat labels) override
     {
+        // (the host-only generic path hands a regressor its rows one level at a time: there is no batched state to split)
+        if (has_sweep()) throw std::invalid_argument("LinearRegressor: a RegulariserSweep is trained by the batched device path, train(..., holdout)");
         cv::Mat x = solver.solve(data, labels, regulariser);
         this->x = x;
         return true;   // regressors.hpp:349
@@ -351,6 +389,18 @@ public:
 
     const Regulariser& get_regulariser() const { return regulariser; }
 
+    /** constructed from a RegulariserSweep; its candidates; the record of the last sweep (best == -1: none yet) */
+    bool has_sweep() const { return !sweep_candidates.empty(); }
+    const std::vector<float>& get_sweep_params() const { return sweep_candidates; }
+    const SweepRecord& get_sweep() const { return sweep_record; }
+    /** the batched backend's report: the record, and the winner's parameter becomes the regulariser's (what is serialised) */
+    void set_sweep(SweepRecord record)
+    {
+        if (record.best >= 0 && (size_t)record.best < record.params.size())
+            regulariser = Regulariser(regulariser.type(), record.params[(size_t)record.best], regulariser.regularises_last_row());
+        sweep_record = std::move(record);
+    }
+
     template <class Archive>
     void serialize(Archive& ar)
     {
@@ -359,6 +409,8 @@ public:
 
 private:
     Regulariser regulariser;
+    std::vector<float> sweep_candidates;
+    SweepRecord sweep_record;
     Solver solver;
 };
 

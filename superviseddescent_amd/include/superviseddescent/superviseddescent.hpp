@@ -25,6 +25,7 @@
 #include "sdm_cv/core.hpp"
 
 #include <atomic>
+#include <stdexcept>
 #include <thread>
 #include <type_traits>
 #include <utility>
@@ -50,6 +51,12 @@ template <class ProjectionFunction, class RegressorType, class NormalisationStra
 struct BatchedBackend {
     static constexpr bool available = false;
 };
+
+// a backend that can hold rows out of the fit declares `static constexpr bool supports_holdout = true` + static train_holdout
+template <class Backend, class = void>
+struct backend_supports_holdout : std::false_type {};
+template <class Backend>
+struct backend_supports_holdout<Backend, std::void_t<decltype(Backend::supports_holdout)>> : std::true_type {};
 
 inline cv::Mat to_row_mat(float v)
 {
@@ -148,6 +155,24 @@ public:
             regressors[regressor_level].learn(observed_values, b);
             current_x = apply_level(regressor_level, observed_values, current_x);
             on_training_epoch_callback(current_x);
+        }
+    }
+
+    /** Train with the LAST `holdout` rows held out of every level's fit (an extension; batched device path only): a level whose
+     *  regressor was constructed from a RegulariserSweep tries all its candidates on one Gram product and keeps the one with the
+     *  lowest mean normalised error on the held-out rows, a level with a plain Regulariser is a sweep of one candidate -- the
+     *  cascade sees one split.  The record is on the regressor (LinearRegressor::get_sweep).  Any other projection functor has no
+     *  batched state to split: std::invalid_argument. */
+    template <class ProjectionFunction, class OnTrainingEpochCallback>
+    void train(cv::Mat parameters, cv::Mat initialisations, cv::Mat templates, ProjectionFunction projection,
+               OnTrainingEpochCallback on_training_epoch_callback, int holdout)
+    {
+        using Backend = detail::BatchedBackend<ProjectionFunction, RegressorType, NormalisationStrategy>;
+        if constexpr (detail::backend_supports_holdout<Backend>::value) {
+            Backend::train_holdout(regressors, normalisation_strategy, parameters, initialisations, templates, projection,
+                                   on_training_epoch_callback, holdout);
+        } else {
+            throw std::invalid_argument("train(..., holdout): held-out rows need the batched device path (rcr::HogTransform + LinearRegressor + InterEyeDistanceNormalisation)");
         }
     }
 
