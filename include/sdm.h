@@ -127,6 +127,31 @@ int sdm_upload_images_bgr_u8(sdm_ctx* ctx, const uint8_t* const* images, const i
 /* Device-resident stack of equally sized images (image i at base + i*height*stride_bytes); not copied. */
 int sdm_set_images_device(sdm_ctx* ctx, const uint8_t* dev_base, int n_images, int width, int height,
                           int stride_bytes);
+/* Frames that are ALREADY on the device -- a hardware decoder's output, torch tensors, regions of a larger frame -- as the image
+ * set, each with its own size, pitch, pointer (any alignment) and format.  The call replaces the context's image set: image i is
+ * frame i for sdm_set_sample_image_index, sdm_hog_features, sdm_detect_batch, sdm_track_step, sdm_pose_templates_from_landmarks
+ * and sdm_align_crops' default source.
+ *   one-byte formats (GRAY, NV12)  used IN PLACE: the call neither copies nor reads them, it writes the image table only.  The memory
+ *       must stay valid until the image set is replaced (the contract of sdm_set_images_device).  NV12:
+ *       data = the Y plane, height rows of stride_bytes; Y is taken as it is (no range expansion), the chroma plane behind it is
+ *       never read.
+ *   colour formats  converted to gray images the CONTEXT owns, all colour frames of the call in ONE launch on the handle's stream,
+ *       with sdm_upload_images_bgr_u8's arithmetic (gray_shift 14 | 15 selects its two weight sets; RGB / RGBA swap the weights
+ *       of byte 0 and byte 2; alpha is ignored).  The source is only read and may be released after the call.
+ *   mixed sets are allowed: in-place and owned images share the one image table (its base is the lowest address of the set).
+ * Argument errors (SDM_ERR_INVALID) change no state and launch nothing -- the previous image set stays the one in use: NULL,
+ * n_frames < 1, width or height < 1, stride_bytes < width * bytes per pixel, an unknown format, gray_shift not 14 or 15, and
+ * colour frames of 2^31 or more 16-pixel row chunks in one call.  (As with the other image entry points, an image less than 2
+ * pixels wide or 65 536+ rows high -- or one whose height * stride_bytes does not fit 31 bits -- selects the generic HOG kernel.) */
+#define SDM_FRAME_GRAY 0   /* 1 byte per pixel, used in place                                  */
+#define SDM_FRAME_BGR  1   /* 3 bytes, cv::imread order                                        */
+#define SDM_FRAME_RGB  2
+#define SDM_FRAME_BGRA 3   /* 4 bytes, alpha ignored                                           */
+#define SDM_FRAME_RGBA 4
+#define SDM_FRAME_NV12 5   /* data = the Y plane (height rows of stride_bytes), used in place;
+                              the chroma plane behind it is never read; Y is taken as it is    */
+typedef struct sdm_frame { const void* data; int width, height, stride_bytes, format; } sdm_frame;
+int sdm_set_frames_device(sdm_ctx* ctx, const sdm_frame* frames, int n_frames, int gray_shift);
 /* `training_index` of HogTransform::operator() (adaptive_vlhog.hpp:109): sample -> image.
  * idx == NULL means sample i uses image i. */
 int sdm_set_sample_image_index(sdm_ctx* ctx, const int* idx, int n_samples);
@@ -318,6 +343,9 @@ int sdm_debug_set_option(sdm_ctx* ctx, const char* name, int value);
 int sdm_debug_update_f16(sdm_ctx* ctx, const float* P_host, int rows, int wcols, int wcols_factor, float factor_bound, float* C_host);
 /* The first n images (all width x height) of the context-owned single-channel image set, back to the host. */
 int sdm_debug_download_images(sdm_ctx* ctx, uint8_t* out, int n, int width, int height);
+/* Image i of ANY image set (owned, sdm_set_images_device, sdm_set_frames_device), read through the image table: out receives
+ * width x height bytes, dense. */
+int sdm_debug_download_image(sdm_ctx* ctx, int i, uint8_t* out);
 /* Lane packing of the HOG launch (default on; also sdm_debug_set_option(ctx, "hog_no_pack", 1)): in SDM_HOG_COLUMNS
  * mode a wave walks a GROUP of patches of one sample in passes of 64 pixel columns instead of one patch per wave (a 50-column
  * ROI then fills the wave).  Same integer decisions; a patch cut by a pass boundary sums its cells from two partial folds.

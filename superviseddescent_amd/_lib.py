@@ -36,6 +36,7 @@ EXPORTED = [
     "sdm_track_configure", "sdm_track_start", "sdm_track_stop", "sdm_track_step", "sdm_track_get",
     "sdm_align_set_source", "sdm_align_crops",
     "sdm_train_level_sweep", "sdm_sweep_get_regressor",
+    "sdm_set_frames_device", "sdm_debug_download_image",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -45,6 +46,105 @@ SDM_TRACK_LOST_NONFINITE, SDM_TRACK_LOST_SMALL, SDM_TRACK_LOST_OUTSIDE, SDM_TRAC
 
 # aligned face crops (include/sdm.h, sdm_align_*)
 SDM_ALIGN_DEGENERATE, SDM_ALIGN_PARTIAL = 1, 2
+
+# frames on the device (include/sdm.h, sdm_set_frames_device)
+SDM_FRAME_GRAY, SDM_FRAME_BGR, SDM_FRAME_RGB, SDM_FRAME_BGRA, SDM_FRAME_RGBA, SDM_FRAME_NV12 = range(6)
+FRAME_FORMATS = {"gray": SDM_FRAME_GRAY, "bgr": SDM_FRAME_BGR, "rgb": SDM_FRAME_RGB, "bgra": SDM_FRAME_BGRA, "rgba": SDM_FRAME_RGBA,
+                 "nv12": SDM_FRAME_NV12}
+_FRAME_CHANNELS = {SDM_FRAME_GRAY: 1, SDM_FRAME_NV12: 1, SDM_FRAME_BGR: 3, SDM_FRAME_RGB: 3, SDM_FRAME_BGRA: 4, SDM_FRAME_RGBA: 4}
+
+
+class SdmFrame(ctypes.Structure):
+    """``sdm_frame``: one device-resident frame of sdm_set_frames_device."""
+
+    _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_int), ("height", ctypes.c_int), ("stride_bytes", ctypes.c_int),
+                ("format", ctypes.c_int)]
+
+
+def _frame_format(fmt) -> int:
+    if isinstance(fmt, str):
+        if fmt.lower() not in FRAME_FORMATS:
+            raise ValueError(f"unknown frame format {fmt!r}: one of {sorted(FRAME_FORMATS)}")
+        return FRAME_FORMATS[fmt.lower()]
+    return int(fmt)
+
+
+def _is_tensor(obj) -> bool:
+    return hasattr(obj, "data_ptr") and hasattr(obj, "stride") and hasattr(obj, "shape")
+
+
+def _tensor_frame(ptr: int, shape, stride, fmt):
+    """One H x W or H x W x C view (sizes and strides in elements = bytes) -> (ptr, w, h, stride_bytes, format)."""
+    if len(shape) == 2:
+        (h, w), c = shape, 1
+        row, px, ch = stride[0], stride[1], 1
+        code = SDM_FRAME_GRAY if fmt is None else _frame_format(fmt)
+        if _FRAME_CHANNELS.get(code) != 1:
+            raise ValueError("an H x W frame is gray (or NV12 luma)")
+    elif len(shape) == 3:
+        h, w, c = shape
+        row, px, ch = stride
+        if c not in (3, 4):
+            raise ValueError("a colour frame is H x W x 3 (bgr, rgb) or H x W x 4 (bgra, rgba)")
+        code = (SDM_FRAME_BGR if c == 3 else SDM_FRAME_BGRA) if fmt is None else _frame_format(fmt)
+        if _FRAME_CHANNELS.get(code) != c:
+            raise ValueError(f"format {fmt!r} does not have {c} channels")
+    else:
+        raise ValueError("a frame is H x W or H x W x C")
+    if h < 1 or w < 1:
+        raise ValueError("empty frame")
+    # (the stride of a dimension of size 1 is never used to form an address: whatever the producer left there is accepted)
+    if (c > 1 and ch != 1) or (w > 1 and px != c):
+        raise ValueError("frames must be interleaved and dense within a row: stride(-1) == 1 and a pixel stride of C bytes")
+    if h > 1 and row < w * c:
+        raise ValueError("the row stride is smaller than a row")
+    return (int(ptr), int(w), int(h), int(row) if h > 1 else int(w * c), code)
+
+
+def frame_descriptors(frames, formats=None):
+    """The ``sdm_frame`` list of ``frames`` as (ptr, width, height, stride_bytes, format) tuples.  Pure host code on duck-typed
+    objects (``data_ptr()``, ``shape``, ``stride()``, ``dtype``): no device, no torch needed.
+    ``frames``: a list whose members are uint8 tensors -- H x W (gray), H x W x 3 ("bgr", the default, or "rgb"), H x W x 4 ("bgra",
+    the default, or "rgba") -- or ready (ptr, w, h, stride, format) tuples (NV12 luma, foreign allocators), which pass through
+    unchanged but for a format given by name; or ONE stacked tensor n x H x W [x C].  A tensor only needs stride(-1) == 1 and a pixel
+    stride of C: the row stride is free, so views into larger frames work.  ``formats``: None, one name for all tensors, or one per
+    frame (None entries = the default)."""
+    if _is_tensor(frames):
+        shape, stride = tuple(int(v) for v in frames.shape), tuple(int(v) for v in frames.stride())
+        if len(shape) not in (3, 4):
+            raise ValueError("a stacked tensor is n x H x W or n x H x W x C")
+        _check_u8(frames)
+        base = int(frames.data_ptr())
+        items = [("t", base + i * stride[0], shape[1:], stride[1:]) for i in range(shape[0])]
+    else:
+        items = []
+        for f in frames:
+            if _is_tensor(f):
+                _check_u8(f)
+                items.append(("t", int(f.data_ptr()), tuple(int(v) for v in f.shape), tuple(int(v) for v in f.stride())))
+            else:
+                if len(f) != 5:
+                    raise ValueError("a frame tuple is (ptr, width, height, stride_bytes, format)")
+                items.append(("d", f))
+    if not items:
+        raise ValueError("no frames")
+    if formats is None or isinstance(formats, (str, int)):
+        formats = [formats] * len(items)
+    if len(formats) != len(items):
+        raise ValueError("one format per frame expected")
+    out = []
+    for it, fmt in zip(items, formats):
+        if it[0] == "d":
+            ptr, w, h, st, code = it[1]
+            out.append((int(ptr), int(w), int(h), int(st), _frame_format(code)))
+        else:
+            out.append(_tensor_frame(it[1], it[2], it[3], fmt))
+    return out
+
+
+def _check_u8(t):
+    if str(t.dtype).split(".")[-1] != "uint8":
+        raise ValueError(f"frames must be uint8, not {t.dtype}")
 
 
 class SdmHogParam(ctypes.Structure):
@@ -195,6 +295,8 @@ def lib() -> ctypes.CDLL:
             "sdm_train_level_sweep": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int_p],
             "sdm_sweep_get_regressor": [c_void_p, c_int, c_float_p],
+            "sdm_set_frames_device": [c_void_p, ctypes.POINTER(SdmFrame), c_int, c_int],
+            "sdm_debug_download_image": [c_void_p, c_int, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

@@ -1,0 +1,101 @@
+// sdm_capi_frames.hip -- frames that are already on the device as the context's image set: gray and NV12 luma in place, colour
+// converted into context-owned gray images by one launch (sdm_frames.hip) (C-ABI of include/sdm.h; shared declarations: sdm_capi_internal.h)
+#include "sdm_capi_internal.h"
+
+#include <limits.h>
+
+static int frame_bpp(int format)
+{
+    switch (format) {
+    case SDM_FRAME_GRAY: case SDM_FRAME_NV12: return 1;
+    case SDM_FRAME_BGR: case SDM_FRAME_RGB: return 3;
+    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return 4;
+    default: return 0;
+    }
+}
+
+extern "C" {
+
+int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_shift)
+{
+    if (!c || !frames || n < 1) return fail(SDM_ERR_INVALID, "bad frame list");
+    if (gray_shift != 14 && gray_shift != 15) return fail(SDM_ERR_INVALID, "gray_shift must be 14 (OpenCV 2.4 - 3.x) or 15");
+    // ---- every argument is checked before anything is allocated, copied or launched ----
+    std::vector<FrameConvDev> conv;
+    long long owned = 0, blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const sdm_frame& f = frames[i];
+        const int bpp = frame_bpp(f.format);
+        if (!bpp) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": unknown format");
+        if (!f.data) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": null pointer");
+        if (f.width < 1 || f.height < 1) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": width and height must be >= 1");
+        if ((long long)f.stride_bytes < (long long)f.width * bpp)
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < width * bytes per pixel");
+        if (bpp == 1) continue;
+        FrameConvDev d{};
+        d.src = (const uint8_t*)f.data; d.dst_off = owned; d.w = f.width; d.h = f.height; d.pitch = f.stride_bytes;
+        d.gstride = sdm_frames_gray_stride(f.width); d.bpp = bpp;
+        d.swap_rb = f.format == SDM_FRAME_RGB || f.format == SDM_FRAME_RGBA;
+        d.block0 = (unsigned)blocks;
+        // (a lane numbers its chunk within the frame in 32 bits, the launch its workgroups in 31)
+        if (sdm_frames_blocks(f.width, f.height) * 256 > (long long)INT_MAX || blocks + sdm_frames_blocks(f.width, f.height) > (long long)INT_MAX)
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": more than 2^31 pixel chunks in one call");
+        blocks += sdm_frames_blocks(f.width, f.height);
+        owned += (long long)d.gstride * f.height;      // (a multiple of 16: the next image starts aligned)
+        conv.push_back(d);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc;
+    if (!conv.empty() && ((rc = c->frames.gray.ensure((size_t)owned)) || (rc = c->frames.desc.ensure(conv.size())))) return rc;
+    if ((rc = c->img_off.ensure(n)) || (rc = c->img_w.ensure(n)) || (rc = c->img_h.ensure(n)) || (rc = c->img_stride.ensure(n)))
+        return rc;
+    // ---- the one table: in-place images at their own addresses, owned ones inside frames.gray; base = the lowest address ----
+    std::vector<const uint8_t*> addr(n);
+    std::vector<int> vw(n), vh(n), vs(n);
+    bool narrow = false;
+    for (int i = 0, k = 0; i < n; ++i) {
+        const sdm_frame& f = frames[i];
+        vw[i] = f.width; vh[i] = f.height;
+        if (frame_bpp(f.format) == 1) { addr[i] = (const uint8_t*)f.data; vs[i] = f.stride_bytes; }
+        else { addr[i] = c->frames.gray.p + conv[k].dst_off; vs[i] = conv[k].gstride; ++k; }
+        // the rule of the other image entry points, and -- an image taller than 2 GiB of rows, which they cannot meet with their
+        // int sizes either way -- the fused kernels' 32-bit num_records
+        narrow = narrow || f.width < 2 || f.height > 65535 || (long long)vs[i] * f.height > (long long)INT_MAX;
+    }
+    const uint8_t* base = addr[0];
+    for (int i = 1; i < n; ++i) if (addr[i] < base) base = addr[i];
+    std::vector<long long> off(n);
+    for (int i = 0; i < n; ++i) off[i] = (long long)(addr[i] - base);
+    HIP_TRY(hipMemcpyAsync(c->img_off.p, off.data(), n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->img_w.p, vw.data(), n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->img_h.p, vh.data(), n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->img_stride.p, vs.data(), n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (!conv.empty()) {
+        HIP_TRY(hipMemcpyAsync(c->frames.desc.p, conv.data(), conv.size() * sizeof(FrameConvDev), hipMemcpyHostToDevice, c->stream));
+        sdm_launch_frames_to_gray(c->frames.desc.p, (int)conv.size(), (unsigned)blocks, c->frames.gray.p, gray_shift, c->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->img_base = base;
+    c->n_images = n;
+    c->img_w_host.swap(vw); c->img_h_host.swap(vh);
+    c->narrow_images = narrow;
+    return SDM_OK;
+}
+
+int sdm_debug_download_image(sdm_ctx* c, int i, uint8_t* out)
+{
+    if (!c || !out || !c->img_base || i < 0 || i >= c->n_images) return fail(SDM_ERR_INVALID, "bad arguments");
+    HIP_TRY(hipSetDevice(c->device));
+    long long off = 0;
+    int stride = 0;
+    HIP_TRY(hipMemcpyAsync(&off, c->img_off.p + i, sizeof(off), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(&stride, c->img_stride.p + i, sizeof(stride), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const int w = c->img_w_host[i], h = c->img_h_host[i];
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)w, c->img_base + off, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDM_OK;
+}
+
+}  // extern "C"

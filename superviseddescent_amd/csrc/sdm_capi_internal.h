@@ -6,6 +6,7 @@
 //   sdm_capi_train.hip     targets, Gram / right-hand side, solvers       sdm_capi_exchange.hip  the several-GPU exchange of the normal equations
 //   sdm_capi_debug.hip     device pointers, timing, debug entry points   sdm_capi_pose.hip / sdm_capi_track.hip  head pose, tracking
 //   sdm_capi_align.hip     aligned face crops                          sdm_capi_sweep.hip     regulariser sweep on one Gram product
+//   sdm_capi_frames.hip    device-resident frames as the image set
 #pragma once
 #include "../../include/sdm.h"
 #include "sdm_kernels.h"
@@ -275,6 +276,13 @@ struct sdm_ctx {
         unsigned ok = 0;
         void release() { snap.release(); Rt.release(); Rp.release(); Rmax.release(); x.release(); score.release(); arrived.release(); K = 0; level = -1; ok = 0; }
     } sweep;
+    // frames on the device (sdm_capi_frames.hip): the gray images converted from a call's colour frames -- each starts on a 16-byte
+    // boundary, row stride sdm_frames_gray_stride(w) -- and the conversion launch's descriptor table
+    struct Frames {
+        DevBuf<uint8_t> gray;
+        DevBuf<FrameConvDev> desc;
+        void release() { gray.release(); desc.release(); }
+    } frames;
     // host copies of the image sizes and of the sample -> image index (the checks of an external crop source)
     std::vector<int> img_w_host, img_h_host, img_idx_host;
 

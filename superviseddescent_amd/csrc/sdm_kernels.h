@@ -190,6 +190,23 @@ void sdm_launch_subtract_templates(float* feat, long long ldf, const float* tmpl
 // BGR (3 bytes per pixel, dense) -> gray (dense) with cv::cvtColor's fixed-point weights; shift = 14 | 15
 void sdm_launch_bgr2gray(const uint8_t* bgr, uint8_t* gray, long long n_pixels, int shift, hipStream_t stream);
 
+// ---- colour frames on the device -> owned gray images (sdm_frames.hip; sdm_set_frames_device) ----
+// one colour frame of a call: interleaved u8 pixels of bpp = 3 or 4 bytes, byte 0 = blue (swap_rb 0) or red (swap_rb 1); its gray
+// image goes to gray + dst_off (a multiple of 16) with a row stride of gstride = sdm_frames_gray_stride(w) bytes; block0 = the first
+// workgroup of the frame in the launch (256 chunks of 16 pixels per workgroup, ascending over the table)
+struct FrameConvDev {
+    const uint8_t* src;
+    long long dst_off;
+    int w, h, pitch, gstride;
+    int bpp, swap_rb;
+    unsigned block0;
+    int pad_;
+};
+inline int sdm_frames_gray_stride(int w) { return (int)(((long long)w + 15) / 16 * 16); }
+inline long long sdm_frames_blocks(int w, int h) { return (((long long)w + 15) / 16 * h + 255) / 256; }
+// frames_dev: n_frames descriptors on the device; n_blocks = the sum of sdm_frames_blocks over them; shift = 14 | 15
+void sdm_launch_frames_to_gray(const FrameConvDev* frames_dev, int n_frames, unsigned n_blocks, uint8_t* gray, int shift, hipStream_t stream);
+
 // ---- before / after the path ----------------------------------------------------
 // x[n] = align_mean(mean, perturb(box[n], pert[n]))   (model.hpp:64-76, rcr-train.cpp:130-146); pert may be null
 void sdm_launch_init_boxes(const float* mean, const int* boxes, const float* pert, int N, int L, float* x, hipStream_t stream);

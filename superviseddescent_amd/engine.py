@@ -51,6 +51,16 @@ class HoGParam:
         return self.num_cells * self.num_cells * self.dim
 
 
+def _device_frames(images) -> bool:
+    """``images`` is device input for ``Context.set_frames_device``: a tensor on the device, or a list whose first member is one
+    or is a (ptr, w, h, stride, format) tuple."""
+    if getattr(images, "is_cuda", False):
+        return True
+    if isinstance(images, (list, tuple)) and len(images):
+        return bool(getattr(images[0], "is_cuda", False)) or isinstance(images[0], tuple)
+    return False
+
+
 def _fp(a: np.ndarray):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
@@ -155,6 +165,8 @@ class Context:
             check(self._lib.sdm_upload_images_bgr_u8(self._h, ptrs, _ip(w), _ip(h), _ip(s), n, int(gray_shift)))
         else:
             check(self._lib.sdm_upload_images_u8(self._h, ptrs, _ip(w), _ip(h), _ip(s), n))
+        self._image_sizes = list(zip(w.tolist(), h.tolist()))
+        self._frames_keep = None
 
     def download_images(self, n: int, width: int, height: int) -> np.ndarray:
         """The first ``n`` equally sized images of the context's single-channel image set (tests of the gray conversion)."""
@@ -164,6 +176,40 @@ class Context:
 
     def set_images_device(self, dev_ptr: int, n_images: int, width: int, height: int, stride: int):
         check(self._lib.sdm_set_images_device(self._h, ctypes.c_void_p(dev_ptr), n_images, width, height, stride))
+        self._image_sizes = [(int(width), int(height))] * int(n_images)
+        self._frames_keep = None
+
+    def set_frames_device(self, frames, formats=None, gray_shift: int = 14):
+        """Frames that are already on the device as the image set (sdm_set_frames_device): image i is frame i.  ``frames``: a list
+        of uint8 device tensors -- H x W gray, H x W x 3 ("bgr", default, or "rgb"), H x W x 4 ("bgra", default, or "rgba"); any row
+        stride, so views into larger frames work -- and / or (ptr, w, h, stride_bytes, format) tuples (format by name or
+        SDM_FRAME_*: "nv12" with ptr = the Y plane; foreign allocators); or one stacked tensor n x H x W [x C].  ``formats``: one
+        name for all tensors or one per frame.  Gray and NV12 frames are used in place -- the context keeps a reference to the
+        tensors until the image set is replaced; memory behind a tuple is the caller's to keep alive -- colour frames are converted
+        once, in one launch, with ``upload_images``' arithmetic.  torch's current stream is synchronised first: the library runs
+        on a stream of its own."""
+        desc = _lib.frame_descriptors(frames, formats)
+        for t in ([frames] if _lib._is_tensor(frames) else frames):
+            if getattr(t, "is_cuda", False):
+                import torch
+                torch.cuda.current_stream(t.device).synchronize()
+                break
+        arr = (_lib.SdmFrame * len(desc))(*[_lib.SdmFrame(ctypes.c_void_p(p), w, h, st, f) for p, w, h, st, f in desc])
+        check(self._lib.sdm_set_frames_device(self._h, arr, len(desc), int(gray_shift)))
+        self._image_sizes = [(w, h) for _, w, h, _, _ in desc]
+        self._frames_keep = frames
+
+    def download_image(self, i: int, width: Optional[int] = None, height: Optional[int] = None) -> np.ndarray:
+        """Image ``i`` of the current image set, whichever call installed it, read back through the image table (H x W uint8).
+        Its size is known after ``set_frames_device`` / ``set_images_device``; otherwise give ``width`` and ``height``."""
+        if width is None or height is None:
+            sizes = getattr(self, "_image_sizes", None)
+            if not sizes or not 0 <= i < len(sizes):
+                raise ValueError("give width and height: the size of this image is not known to the Python layer")
+            width, height = sizes[i]
+        out = np.empty((int(height), int(width)), np.uint8)
+        check(self._lib.sdm_debug_download_image(self._h, int(i), out.ctypes.data))
+        return out
 
     def set_sample_image_index(self, idx: Optional[np.ndarray]):
         if idx is None:
@@ -850,7 +896,8 @@ class InterEyeDistanceNormalisation:
 class HogTransform:
     """rcr::HogTransform (adaptive_vlhog.hpp:70-195): holds the images and per-level HoG parameters.
 
-    ``images`` is a list / stack of single-channel uint8 images; ``img_index`` maps a sample row to its
+    ``images`` is a list / stack of single-channel uint8 images (or device-resident frames, see
+    ``Context.set_frames_device``); ``img_index`` maps a sample row to its
     image (the reference's ``training_index``; perturbed copies share an image)."""
 
     def __init__(self, images, hog_params: Sequence[HoGParam], model_landmarks: Sequence[str],
@@ -969,7 +1016,10 @@ class SupervisedDescentOptimiser:
         # every bind -- unless the caller declares them resident (HogTransform(..., images_resident=True)) and passes the
         # very same projection object again, which this optimiser then holds a strong reference to.
         if not (projection.images_resident and self._bound is projection):
-            self.ctx.upload_images(projection.images)
+            if _device_frames(projection.images):
+                self.ctx.set_frames_device(projection.images)
+            else:
+                self.ctx.upload_images(projection.images)
         self._bound = projection
         self.ctx.set_sample_image_index(projection.img_index)
 
@@ -1207,7 +1257,9 @@ class detection_model:
         return self.optimised_model.predict(np.atleast_2d(init), None, hog)[0]
 
     def detect_batch(self, images, faceboxes: np.ndarray, img_index: Optional[np.ndarray] = None) -> np.ndarray:
-        """Batched ``detect``: row i starts from align_mean(mean, faceboxes[i]) on image img_index[i]."""
+        """Batched ``detect``: row i starts from align_mean(mean, faceboxes[i]) on image img_index[i].  ``images``: host images, or
+        frames on the device as ``Context.set_frames_device`` takes them (gray, "bgr" / "bgra" tensors of any size and row stride;
+        (ptr, w, h, stride, format) tuples for the other formats) -- those are not downloaded."""
         from .synth import align_mean
         init = np.stack([align_mean(self.mean, tuple(int(v) for v in b)) for b in np.asarray(faceboxes)])
         hog = HogTransform(images, self.hog_params, self.landmark_ids, self.right_eye_ids, self.left_eye_ids,
@@ -1330,21 +1382,25 @@ class Tracker:
     def stop(self, ids):
         self.ctx.track_stop(ids)
 
-    def step(self, ids, frames=None, image_index=None, fetch: bool = True):
+    def step(self, ids, frames=None, image_index=None, fetch: bool = True, formats=None, gray_shift: int = 14):
         """One frame for the streams ``ids``: row i belongs to stream ids[i] and reads frame ``image_index[i]`` (default i).
         ``frames``: host images (a list or an n x H x W stack, uploaded), a uint8 n x H x W tensor on the device (used in place),
+        any other device input of ``Context.set_frames_device`` -- a list of gray or colour tensors of different sizes, pitched
+        views, a stacked n x H x W x C tensor, (ptr, w, h, stride, format) tuples; ``formats`` and ``gray_shift`` go with it --
         or None (the images already set on the context).  Returns (landmarks n x 2L -- None unless ``fetch`` --, lost masks n:
         0 = tracked, else the SDM_TRACK_LOST_* bits)."""
         c = self.ctx
         self._bind()
         if frames is not None:
-            if hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False):
-                if frames.dtype.itemsize != 1 or frames.dim() != 3 or not frames.is_contiguous():
-                    raise ValueError("device frames must be a contiguous uint8 n x H x W tensor")
+            if hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False) and frames.dim() == 3 and frames.is_contiguous():
+                if frames.dtype.itemsize != 1:
+                    raise ValueError("device frames must be uint8")
                 import torch
                 torch.cuda.current_stream(frames.device).synchronize()      # (the library runs on its own stream)
                 n, h, w = (int(v) for v in frames.shape)
                 c.set_images_device(frames.data_ptr(), n, w, h, w)
+            elif _device_frames(frames):
+                c.set_frames_device(frames, formats, gray_shift)            # (colour, ragged, pitched: sdm_set_frames_device)
             else:
                 c.upload_images(frames)
             self.model.optimised_model._bound = None                        # (the context's images are no longer a bound projection's)

@@ -42,7 +42,23 @@ struct HoGParam {
     }
 };
 
+/** A frame that is already on the device (sdm_frame of include/sdm.h): `data` is a device pointer of any alignment, `format` one of
+ *  SDM_FRAME_GRAY / BGR / RGB / BGRA / RGBA / NV12 (data = the Y plane).  Gray and NV12 frames are read in place and must stay valid
+ *  while they are the image set; colour frames are converted to gray once, on the device. */
+struct DeviceFrame {
+    const void* data;
+    int width, height, stride_bytes, format;
+};
+
 namespace detail {
+
+// frames on the device -> the handle's image set (sdm_set_frames_device): nothing crosses the host link
+inline void set_device_frames(superviseddescent::hip::Handle& h, const std::vector<DeviceFrame>& frames, int gray_shift = 14)
+{
+    std::vector<sdm_frame> f;
+    for (const auto& d : frames) f.push_back(sdm_frame{d.data, d.width, d.height, d.stride_bytes, d.format});
+    superviseddescent::hip::check(sdm_set_frames_device(h.get(), f.data(), (int)f.size(), gray_shift), "sdm_set_frames_device");
+}
 
 // single-channel u8 view of an image on the HOST (used only for lists that mix gray and colour images; all-colour lists are
 // converted by the device kernel behind sdm_upload_images_bgr_u8): OpenCV's fixed-point weights
@@ -129,6 +145,14 @@ public:
     {
     }
 
+    /** The same transform on frames that are already on the device (extension: the reference has host images only). */
+    HogTransform(std::vector<DeviceFrame> frames, std::vector<HoGParam> hog_params, std::vector<std::string> modelLandmarksList,
+                 std::vector<std::string> rightEyeIdentifiers, std::vector<std::string> leftEyeIdentifiers)
+        : images(no_images()), hog_params(hog_params), modelLandmarksList(modelLandmarksList), rightEyeIdentifiers(rightEyeIdentifiers),
+          leftEyeIdentifiers(leftEyeIdentifiers), state(std::make_shared<detail::HogDeviceState>()), device_frames(std::move(frames))
+    {
+    }
+
     /** Features of ONE sample at its current landmark estimate (reference :109-185): 1 x (L*C*C*D + 1). */
     cv::Mat operator()(cv::Mat parameters, size_t regressorLevel, int trainingIndex = 0)
     {
@@ -138,7 +162,8 @@ public:
         if (!state->handle) state->handle.reset(new superviseddescent::hip::Handle(superviseddescent::hip::device()));
         sdm_ctx* c = state->handle->get();
         if (!state->images_uploaded) {
-            detail::configure(*state->handle, images, hog_params, modelLandmarksList, rightEyeIdentifiers, leftEyeIdentifiers, true);
+            detail::configure(*state->handle, images, hog_params, modelLandmarksList, rightEyeIdentifiers, leftEyeIdentifiers, device_frames.empty());
+            if (!device_frames.empty()) detail::set_device_frames(*state->handle, device_frames);
             state->images_uploaded = true;
         }
         cv::Mat row = parameters.isContinuous() ? parameters : parameters.clone();
@@ -153,6 +178,8 @@ public:
 
     // read access for the batched backend
     const std::vector<cv::Mat>& get_images() const { return images; }
+    /** not empty: the transform reads these device frames instead of `images` */
+    const std::vector<DeviceFrame>& get_device_frames() const { return device_frames; }
     const std::vector<HoGParam>& get_hog_params() const { return hog_params; }
     const std::vector<std::string>& get_landmark_ids() const { return modelLandmarksList; }
     const std::vector<std::string>& get_right_eye_ids() const { return rightEyeIdentifiers; }
@@ -168,6 +195,12 @@ private:
     std::vector<std::string> rightEyeIdentifiers;
     std::vector<std::string> leftEyeIdentifiers;
     std::shared_ptr<detail::HogDeviceState> state;
+    std::vector<DeviceFrame> device_frames;
+    static const std::vector<cv::Mat>& no_images()
+    {
+        static const std::vector<cv::Mat> none;
+        return none;
+    }
 };
 
 /** The HogTransform of the reference's examples/landmark_detection.cpp:158-269 -- the example defines it in its own source file;

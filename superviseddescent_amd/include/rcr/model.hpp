@@ -78,7 +78,8 @@ inline void bind_transform(hip::Handle& h, rcr::HogTransform& hog, int /*num_lan
 {
     if (hog.get_hog_params().size() != n_levels) throw std::runtime_error("one HoGParam per regressor level expected");
     rcr::detail::configure(h, hog.get_images(), hog.get_hog_params(), hog.get_landmark_ids(), hog.get_right_eye_ids(),
-                           hog.get_left_eye_ids(), true);
+                           hog.get_left_eye_ids(), hog.get_device_frames().empty());
+    if (!hog.get_device_frames().empty()) rcr::detail::set_device_frames(h, hog.get_device_frames());
 }
 inline void bind_transform(hip::Handle& h, rcr::FixedHogTransform& hog, int num_landmarks, size_t n_levels)
 {
@@ -271,6 +272,17 @@ public:
         cv::Mat init;
         for (const auto& box : faceboxes) init.push_back(rcr::align_mean(mean, box));
         rcr::HogTransform hog(images, hog_params, landmark_ids, right_eye_ids, left_eye_ids);
+        hog.sample_image_index = image_index;
+        return optimised_model.test(init, cv::Mat(), hog);
+    }
+
+    /** The same on frames that are already on the device (gray, NV12 luma, BGR / RGB / BGRA / RGBA; each with its own size and
+     *  pitch): no pixel crosses the host link.  Colour is converted with the weights of the cv::Mat overload's device path. */
+    cv::Mat detect_batch(const std::vector<DeviceFrame>& frames, const std::vector<cv::Rect>& faceboxes, const std::vector<int>& image_index = {})
+    {
+        cv::Mat init;
+        for (const auto& box : faceboxes) init.push_back(rcr::align_mean(mean, box));
+        rcr::HogTransform hog(frames, hog_params, landmark_ids, right_eye_ids, left_eye_ids);
         hog.sample_image_index = image_index;
         return optimised_model.test(init, cv::Mat(), hog);
     }

@@ -68,19 +68,17 @@ public:
     std::vector<LandmarkCollection<cv::Vec2f>> step(const std::vector<int>& ids, const std::vector<cv::Mat>& frames,
                                                     const std::vector<int>& image_index = {})
     {
-        using superviseddescent::hip::check;
-        sdm_ctx* c = handle.get();
-        const int n = (int)ids.size();
         detail::upload_images(handle, frames);
-        check(sdm_set_templates(c, nullptr, 0, 0), "sdm_set_templates");
-        if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
-        else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
-        cv::Mat rows(n, 2 * num_landmarks(), CV_32FC1);
-        std::vector<int> masks(ids.size());
-        check(sdm_track_step(c, ids.data(), n, rows.ptr<float>(0), masks.data()), "sdm_track_step");
-        last_rows = rows;
-        last_lost = masks;
-        return collections(rows);
+        return step_on_current_images(ids, image_index);
+    }
+
+    /** The same on frames that are already on the device (rcr::DeviceFrame: gray and NV12 luma in place, colour converted once on the
+     *  device; every frame with its own size and pitch). */
+    std::vector<LandmarkCollection<cv::Vec2f>> step(const std::vector<int>& ids, const std::vector<DeviceFrame>& frames,
+                                                    const std::vector<int>& image_index = {})
+    {
+        detail::set_device_frames(handle, frames);
+        return step_on_current_images(ids, image_index);
     }
 
     /** The streams' landmarks (a started stream: its aligned mean) and statuses. */
@@ -97,6 +95,22 @@ public:
     sdm_ctx* context() const { return handle.get(); }
 
 private:
+    std::vector<LandmarkCollection<cv::Vec2f>> step_on_current_images(const std::vector<int>& ids, const std::vector<int>& image_index)
+    {
+        using superviseddescent::hip::check;
+        sdm_ctx* c = handle.get();
+        const int n = (int)ids.size();
+        check(sdm_set_templates(c, nullptr, 0, 0), "sdm_set_templates");
+        if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+        else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+        cv::Mat rows(n, 2 * num_landmarks(), CV_32FC1);
+        std::vector<int> masks(ids.size());
+        check(sdm_track_step(c, ids.data(), n, rows.ptr<float>(0), masks.data()), "sdm_track_step");
+        last_rows = rows;
+        last_lost = masks;
+        return collections(rows);
+    }
+
     int num_landmarks() const { return (int)model.get_landmark_ids().size(); }
     std::vector<LandmarkCollection<cv::Vec2f>> collections(const cv::Mat& rows) const
     {
