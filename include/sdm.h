@@ -510,6 +510,63 @@ int sdm_align_set_source(sdm_ctx* ctx, const uint8_t* base, int n_images, int wi
 int sdm_align_crops(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int out_width, int out_height,
                     uint8_t* out, int out_on_device, float* matrices_host, int* flags_host);
 
+/* Crops as a network's input tensor, straight from frames on the device: one launch behind the fit goes from the frames in place to
+ * N x C x H x W (or N x H x W x C) elements of u8, float16 or float32, channel order, mean and std applied.
+ *
+ * sdm_align_set_source_frames: a frame list as the crop source, used IN PLACE (nothing copied, nothing converted; the memory must stay
+ * valid while crops are made from it).  frames: as for sdm_set_frames_device, all six formats.  chroma: NULL, or n_frames pointers;
+ * entry i is the interleaved UV plane of an NV12 frame i (ignored for other formats); a NULL entry, or chroma == NULL, means
+ * (const uint8_t*)data + (size_t)height * stride_bytes.  The UV plane has (height + 1) / 2 rows of stride_bytes.
+ * n_frames == 0 / frames == NULL: back to the context's images.  Replaces an sdm_align_set_source stack and is replaced by one.
+ * Refused (SDM_ERR_INVALID, no state changed): what sdm_set_frames_device refuses of a frame (n_frames < 0, a NULL data pointer, width or
+ * height < 1, stride_bytes < width * bytes per pixel, an unknown format), and an NV12 frame with stride_bytes < 2 * ((width + 1) / 2).
+ *
+ * sdm_align_crops_tensor, for every current row n (rows map to images / frames through sdm_set_sample_image_index; a frame must have the
+ * width and height of the context image its row maps to):
+ *   1. fit, positions, quantisation, weights, flags   sdm_align_crops', unchanged: the same fit kernel, sx = (M00 j + M01 i) + M02, 1/32-pixel
+ *      positions, (... + 512) >> 10, a tap outside the image reads 0, the 2^20 rule, DEGENERATE, PARTIAL.
+ *   2. warped pixel by source format
+ *        GRAY                      one value g
+ *        BGR / RGB / BGRA / RGBA   three values (B, G, R) by byte position; alpha is never read
+ *        NV12   Y = the gray warp of the Y plane (sdm_align_crops' bits on that luma).  U, V: warped from the UV plane of
+ *               cw = (w + 1) >> 1 by ch = (h + 1) >> 1 byte pairs at cx = sx * 0.5f, cy = sy * 0.5f (exact; chroma co-sited with the even
+ *               luma sample), same quantisation and weights; a chroma tap outside [0, cw) x [0, ch) reads 128.  Then BT.601 limited
+ *               range in int32, the constants of OpenCV's COLOR_YUV2BGR_NV12: y = max(0, Y - 16) * 1220542,
+ *               R = (y + 1673527 (V - 128) + 2^19) >> 20, G = (y - 852492 (V - 128) - 409993 (U - 128) + 2^19) >> 20,
+ *               B = (y + 2116026 (U - 128) + 2^19) >> 20, arithmetic shift, clamped to [0, 255].  A position refused by the 2^20 rule
+ *               gives (0, 0, 0).
+ *        The source is the frame list, else the sdm_align_set_source stack (C = 1: GRAY, 3: BGR, 4: BGRA), else the context's images (GRAY).
+ *   3. output channels   channels == 3: a gray source replicates g; a colour source gives (B, G, R) or (R, G, B) by `order`.
+ *        channels == 1: a gray source gives g; an NV12 source gives Y as it is (no conversion, the UV plane is not read); the other
+ *        colour formats give (B wb + G wg + R wr + (1 << (gray_shift - 1))) >> gray_shift with sdm_upload_images_bgr_u8's weights
+ *        (14: 1868, 9617, 4899; 15: 3735, 19235, 9798), applied to the warped values.
+ *   4. element   U8: the value v.  F32: (float)v * scale[c] + bias[c], the product rounded, then the sum rounded.  F16: that float32
+ *        converted round-to-nearest-even.  c is the OUTPUT channel.
+ *   5. layout   NHWC: out[((n H + i) W + j) C + c].  NCHW: out[((n C + c) H + i) W + j].
+ *   6. a DEGENERATE row's elements are those of v = 0 (bias[c] for the float dtypes); its M is six NaNs.
+ *   7. refused (SDM_ERR_INVALID, no state changed, nothing launched): everything sdm_align_crops refuses; spec NULL; an unknown dtype,
+ *      layout or order; channels not 1 or 3; gray_shift not 14 or 15; a non-finite scale or bias with a float dtype; out_dev NULL or not
+ *      16-byte aligned.
+ * sdm_align_crops on a frame-list source: frames of ONE pixel size (all GRAY, all 3-byte or all 4-byte) give the interleaved warp as for a
+ * stack, alpha included; NV12 or mixed pixel sizes are refused (use sdm_align_crops_tensor). */
+int sdm_align_set_source_frames(sdm_ctx* ctx, const sdm_frame* frames, const void* const* chroma, int n_frames);
+
+#define SDM_ALIGN_U8         0   /* dtype                                    */
+#define SDM_ALIGN_F16        1
+#define SDM_ALIGN_F32        2
+#define SDM_ALIGN_NHWC       0   /* layout                                   */
+#define SDM_ALIGN_NCHW       1
+#define SDM_ALIGN_ORDER_BGR  0   /* order of a 3-channel output              */
+#define SDM_ALIGN_ORDER_RGB  1
+typedef struct sdm_align_tensor {
+    int dtype, layout, channels /* 1 or 3 */, order;
+    float scale[3], bias[3];      /* float dtypes, per OUTPUT channel; ignored for U8 */
+    int gray_shift;               /* 14 | 15: the weights of a colour -> 1 channel output */
+} sdm_align_tensor;
+/* out_dev: device memory, N * channels * out_height * out_width elements, 16-byte aligned. */
+int sdm_align_crops_tensor(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int out_width,
+                           int out_height, const sdm_align_tensor* spec, void* out_dev, float* matrices_host, int* flags_host);
+
 #ifdef __cplusplus
 }
 #endif

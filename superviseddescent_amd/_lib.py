@@ -34,7 +34,7 @@ EXPORTED = [
     "sdm_pose_templates_from_landmarks", "sdm_pose_set_targets", "sdm_pose_features", "sdm_pose_train_level",
     "sdm_pose_set_regressor", "sdm_pose_get_regressor", "sdm_pose_test",
     "sdm_track_configure", "sdm_track_start", "sdm_track_stop", "sdm_track_step", "sdm_track_get",
-    "sdm_align_set_source", "sdm_align_crops",
+    "sdm_align_set_source", "sdm_align_crops", "sdm_align_set_source_frames", "sdm_align_crops_tensor",
     "sdm_train_level_sweep", "sdm_sweep_get_regressor",
     "sdm_set_frames_device", "sdm_debug_download_image",
 ]
@@ -46,6 +46,14 @@ SDM_TRACK_LOST_NONFINITE, SDM_TRACK_LOST_SMALL, SDM_TRACK_LOST_OUTSIDE, SDM_TRAC
 
 # aligned face crops (include/sdm.h, sdm_align_*)
 SDM_ALIGN_DEGENERATE, SDM_ALIGN_PARTIAL = 1, 2
+
+# crops as network input tensors (include/sdm.h, sdm_align_crops_tensor)
+SDM_ALIGN_U8, SDM_ALIGN_F16, SDM_ALIGN_F32 = 0, 1, 2
+SDM_ALIGN_NHWC, SDM_ALIGN_NCHW = 0, 1
+SDM_ALIGN_ORDER_BGR, SDM_ALIGN_ORDER_RGB = 0, 1
+ALIGN_DTYPES = {"uint8": SDM_ALIGN_U8, "float16": SDM_ALIGN_F16, "float32": SDM_ALIGN_F32}
+ALIGN_LAYOUTS = {"nhwc": SDM_ALIGN_NHWC, "nchw": SDM_ALIGN_NCHW}
+ALIGN_ORDERS = {"bgr": SDM_ALIGN_ORDER_BGR, "rgb": SDM_ALIGN_ORDER_RGB}
 
 # frames on the device (include/sdm.h, sdm_set_frames_device)
 SDM_FRAME_GRAY, SDM_FRAME_BGR, SDM_FRAME_RGB, SDM_FRAME_BGRA, SDM_FRAME_RGBA, SDM_FRAME_NV12 = range(6)
@@ -59,6 +67,75 @@ class SdmFrame(ctypes.Structure):
 
     _fields_ = [("data", ctypes.c_void_p), ("width", ctypes.c_int), ("height", ctypes.c_int), ("stride_bytes", ctypes.c_int),
                 ("format", ctypes.c_int)]
+
+
+class SdmAlignTensor(ctypes.Structure):
+    """``sdm_align_tensor``: element type, layout, channels, order, per-channel scale and bias of sdm_align_crops_tensor."""
+
+    _fields_ = [("dtype", ctypes.c_int), ("layout", ctypes.c_int), ("channels", ctypes.c_int), ("order", ctypes.c_int),
+                ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3), ("gray_shift", ctypes.c_int)]
+
+
+def _three(v, what):
+    """A scalar or 3 values as 3 float64 numbers."""
+    import numpy as np
+    a = np.asarray(v, np.float64).reshape(-1)
+    if a.size == 1:
+        a = np.repeat(a, 3)
+    if a.size != 3:
+        raise ValueError(f"{what} must be a scalar or 3 values")
+    return a
+
+
+def align_tensor_spec(dtype="float16", layout="nchw", channels=3, order="rgb", scale=None, bias=None, mean=None, std=None,
+                      gray_shift=14) -> SdmAlignTensor:
+    """The ``sdm_align_tensor`` of the named options.  Pure host code.  ``dtype``: "uint8" | "float16" | "float32" (or a numpy / torch
+    dtype of that name); ``layout``: "nchw" | "nhwc"; ``order``: "rgb" | "bgr".  Element = float32(v) * scale[c] + bias[c] per OUTPUT
+    channel c.  ``scale`` / ``bias``: a scalar or 3 values, given to the library as float32 (defaults 1 and 0).  ``mean`` / ``std``
+    (0-255 units, a scalar or 3 values) are sugar for ``scale = float32(1 / std)``, ``bias = float32(-mean / std)``, both quotients
+    computed in float64 and rounded once; giving them together with ``scale`` or ``bias`` is an error."""
+    import numpy as np
+    name = str(dtype).split(".")[-1].lower() if not isinstance(dtype, type) else np.dtype(dtype).name
+    if name not in ALIGN_DTYPES:
+        raise ValueError(f"unknown dtype {dtype!r}: one of {sorted(ALIGN_DTYPES)}")
+    if not isinstance(layout, str) or layout.lower() not in ALIGN_LAYOUTS:
+        raise ValueError(f"unknown layout {layout!r}: one of {sorted(ALIGN_LAYOUTS)}")
+    if not isinstance(order, str) or order.lower() not in ALIGN_ORDERS:
+        raise ValueError(f"unknown channel order {order!r}: one of {sorted(ALIGN_ORDERS)}")
+    if int(channels) not in (1, 3):
+        raise ValueError("channels must be 1 or 3")
+    if int(gray_shift) not in (14, 15):
+        raise ValueError("gray_shift must be 14 or 15")
+    if (mean is not None or std is not None) and (scale is not None or bias is not None):
+        raise ValueError("give either scale / bias or mean / std, not both")
+    if mean is not None or std is not None:
+        m = _three(0.0 if mean is None else mean, "mean")
+        sd = _three(1.0 if std is None else std, "std")
+        if not (sd != 0).all():
+            raise ValueError("std must not be 0")
+        sc, bi = (1.0 / sd).astype(np.float32), (-m / sd).astype(np.float32)
+    else:
+        sc = _three(1.0 if scale is None else scale, "scale").astype(np.float32)
+        bi = _three(0.0 if bias is None else bias, "bias").astype(np.float32)
+    return SdmAlignTensor(ALIGN_DTYPES[name], ALIGN_LAYOUTS[layout.lower()], int(channels), ALIGN_ORDERS[order.lower()],
+                          (ctypes.c_float * 3)(*sc.tolist()), (ctypes.c_float * 3)(*bi.tolist()), int(gray_shift))
+
+
+def align_tensor_shape(n: int, width: int, height: int, layout: int, channels: int):
+    return (n, channels, height, width) if layout == SDM_ALIGN_NCHW else (n, height, width, channels)
+
+
+def check_align_out(out, shape, dtype_name: str):
+    """``out`` of aligned_crops_tensor: a contiguous device tensor of the requested dtype and shape (duck-typed: dtype, shape,
+    is_contiguous(), is_cuda)."""
+    if str(out.dtype).split(".")[-1] != dtype_name:
+        raise ValueError(f"out must be a {dtype_name} tensor, not {out.dtype}")
+    if tuple(int(v) for v in out.shape) != tuple(shape):
+        raise ValueError(f"out must have the shape {tuple(shape)}, not {tuple(out.shape)}")
+    if not out.is_contiguous():
+        raise ValueError("out must be contiguous")
+    if not getattr(out, "is_cuda", False):
+        raise ValueError("out must be on the device")
 
 
 def _frame_format(fmt) -> int:
@@ -292,6 +369,9 @@ def lib() -> ctypes.CDLL:
             "sdm_track_get": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
             "sdm_align_set_source": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int],
             "sdm_align_crops": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p],
+            "sdm_align_set_source_frames": [c_void_p, ctypes.POINTER(SdmFrame), c_void_p, c_int],
+            "sdm_align_crops_tensor": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p, c_void_p,
+                                       c_void_p],
             "sdm_train_level_sweep": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int_p],
             "sdm_sweep_get_regressor": [c_void_p, c_int, c_float_p],

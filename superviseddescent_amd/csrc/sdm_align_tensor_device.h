@@ -1,0 +1,193 @@
+// sdm_align_tensor_device.h -- the per-pixel arithmetic of sdm_align_crops_tensor (include/sdm.h): positions, taps, the integer
+// bilinear blend, the NV12 conversion, the channel rules and the element formula.  Plain C++ behind one macro, so the same text is
+// the device code of csrc/sdm_align_tensor.hip and -- compiled for the host, tests/cpp/align_tensor_host.cpp -- a program that runs
+// under the host sanitizers on source buffers of exactly the frames' bytes.
+//
+// Every float operation is rounded on its own (no contraction: the pragma below under clang, -ffp-contract=off elsewhere); everything
+// else is int32 / uint32 arithmetic.
+#pragma once
+#include "../../include/sdm.h"
+
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#if defined(__HIPCC__)
+#define ALIGN_HD __device__ __forceinline__
+#else
+#define ALIGN_HD static inline
+#endif
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+
+#define ALIGN_T_MAX_POS 1048576.0f      // 2^20: a position beyond gives 0 (sdm_align_crops' rule)
+
+// one row's source, as the warp reads it
+struct AlignRow {
+    float m[6];                 // crop -> source
+    int w, h, stride;           // plane 0: pixels, rows, bytes per row
+    int cstride;                // NV12: bytes per row of the UV plane
+    int format;                 // SDM_FRAME_*
+    const uint8_t* p0;          // plane 0 (gray, Y or interleaved pixels)
+    const uint8_t* p1;          // NV12: the interleaved UV plane
+};
+
+struct AlignPos { int x0, fx, y0, fy; };
+
+// 1/32-pixel position of (sx, sy); false: refused by the 2^20 rule (also NaN: a degenerate row's M)
+ALIGN_HD bool align_quantise(float sx, float sy, AlignPos& q)
+{
+    if (!(fabsf(sx) <= ALIGN_T_MAX_POS) || !(fabsf(sy) <= ALIGN_T_MAX_POS)) return false;
+    const int X = (int)floorf(sx * 32.0f + 0.5f), Y = (int)floorf(sy * 32.0f + 0.5f);
+    q.x0 = X >> 5; q.fx = X & 31; q.y0 = Y >> 5; q.fy = Y & 31;
+    return true;
+}
+
+// byte offset of (row y, byte xb) inside a plane: 32-bit when the plane's rows * stride fit 31 bits (y < rows, xb < stride)
+template <bool WIDE>
+ALIGN_HD const uint8_t* align_at(const uint8_t* p, int y, int stride, int xb)
+{
+    if constexpr (WIDE) return p + ((long long)y * stride + xb);
+    else return p + (uint32_t)(y * stride + xb);
+}
+
+ALIGN_HD uint32_t align_byte(const uint32_t v[2], int b) { return (b < 4 ? v[0] >> (8 * b) : v[1] >> (8 * (b - 4))) & 255u; }
+
+// the taps (x0, y) and (x0 + 1, y) of a plane of w x h elements of B bytes: 2B bytes packed into v, FILL for a tap outside.  The last
+// byte read is the last byte of an element inside the plane.
+template <int B, bool WIDE, uint32_t FILL>
+ALIGN_HD void align_tap_row(const uint8_t* p, int w, int h, int stride, int x0, int y, uint32_t v[2])
+{
+    v[0] = FILL * 0x01010101u; v[1] = FILL * 0x01010101u;
+    if (y < 0 || y >= h) return;
+    if (x0 >= 0 && x0 + 1 < w) {
+        const uint8_t* s = align_at<WIDE>(p, y, stride, x0 * B);
+        if constexpr (B == 1) {
+            uint16_t t; memcpy(&t, s, 2); v[0] = t;
+        } else if constexpr (B == 2) {
+            uint32_t t; memcpy(&t, s, 4); v[0] = t;
+        } else if constexpr (B == 3) {
+            uint32_t lo; uint16_t hi; memcpy(&lo, s, 4); memcpy(&hi, s + 4, 2); v[0] = lo; v[1] = hi;
+        } else {
+            uint32_t lo, hi; memcpy(&lo, s, 4); memcpy(&hi, s + 4, 4); v[0] = lo; v[1] = hi;
+        }
+        return;
+    }
+    // border: each tap on its own
+    uint32_t a = 0u, b = 0u;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int xx = x0 + t;
+        const bool in = xx >= 0 && xx < w;
+#pragma unroll
+        for (int c = 0; c < B; ++c) {
+            const uint32_t byte = in ? (uint32_t)*align_at<WIDE>(p, y, stride, xx * B + c) : FILL;
+            const int k = t * B + c;
+            if (k < 4) a |= byte << (8 * k);
+            else b |= byte << (8 * (k - 4));
+        }
+    }
+    v[0] = a; v[1] = b;
+}
+
+// NCH values of the element at q: (w00 p00 + w10 p10 + w01 p01 + w11 p11 + 512) >> 10 per byte position
+template <int B, int NCH, bool WIDE, uint32_t FILL>
+ALIGN_HD void align_bilinear(const uint8_t* p, int w, int h, int stride, const AlignPos& q, uint32_t out[NCH])
+{
+    uint32_t r0[2], r1[2];
+    align_tap_row<B, WIDE, FILL>(p, w, h, stride, q.x0, q.y0, r0);
+    align_tap_row<B, WIDE, FILL>(p, w, h, stride, q.x0, q.y0 + 1, r1);
+    const uint32_t w00 = (32 - q.fx) * (32 - q.fy), w10 = q.fx * (32 - q.fy), w01 = (32 - q.fx) * q.fy, w11 = q.fx * q.fy;
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+        out[c] = (w00 * align_byte(r0, c) + w10 * align_byte(r0, B + c) + w01 * align_byte(r1, c) + w11 * align_byte(r1, B + c) + 512u) >> 10;
+}
+
+ALIGN_HD uint32_t align_clamp255(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+// BT.601 limited range, the constants of OpenCV's COLOR_YUV2BGR_NV12 (20 fractional bits).  Every term stays below 2^30 in magnitude:
+// y <= 239 * 1220542 = 2.92e8, |1673527 (V - 128)| <= 2.15e8, |2116026 (U - 128)| <= 2.71e8, |852492 (V - 128)| <= 1.10e8,
+// |409993 (U - 128)| <= 5.3e7, and every sum below 2^31 (largest: y + 2116026 * 127 + 2^19 = 5.61e8).
+ALIGN_HD void align_nv12_to_bgr(uint32_t Y, uint32_t U, uint32_t V, uint32_t bgr[3])
+{
+    const int yy = (int)Y - 16, y = (yy < 0 ? 0 : yy) * 1220542, u = (int)U - 128, v = (int)V - 128;
+    bgr[0] = align_clamp255((y + 2116026 * u + (1 << 19)) >> 20);
+    bgr[1] = align_clamp255((y - 852492 * v - 409993 * u + (1 << 19)) >> 20);
+    bgr[2] = align_clamp255((y + 1673527 * v + (1 << 19)) >> 20);
+}
+
+// the warped pixel of up to 4 consecutive crop pixels (row i, columns j0 ... j0 + npx - 1) as (B, G, R); a gray source gives (g, g, g).
+// The source format is switched on once, outside the pixel work.
+template <bool WIDE>
+ALIGN_HD void align_segment(const AlignRow& r, int i, int j0, int npx, uint32_t px[4][3])
+{
+    const float fi = (float)i;
+    const float ax = r.m[1] * fi, ay = r.m[4] * fi;
+    AlignPos q[4];
+    bool ok[4];
+    float sx[4], sy[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float fj = (float)(j0 + k);
+        sx[k] = (r.m[0] * fj + ax) + r.m[2];
+        sy[k] = (r.m[3] * fj + ay) + r.m[5];
+        q[k].x0 = q[k].fx = q[k].y0 = q[k].fy = 0;
+        ok[k] = k < npx && align_quantise(sx[k], sy[k], q[k]);
+        px[k][0] = px[k][1] = px[k][2] = 0u;
+    }
+    switch (r.format) {
+    case SDM_FRAME_GRAY:
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ok[k]) {
+                uint32_t g[1];
+                align_bilinear<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q[k], g);
+                px[k][0] = px[k][1] = px[k][2] = g[0];
+            }
+        break;
+    case SDM_FRAME_BGR: case SDM_FRAME_RGB:
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ok[k]) align_bilinear<3, 3, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q[k], px[k]);
+        break;
+    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA:
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ok[k]) align_bilinear<4, 3, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q[k], px[k]);
+        break;
+    default: {   // SDM_FRAME_NV12
+        const int cw = (r.w + 1) >> 1, ch = (r.h + 1) >> 1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ok[k]) {
+                uint32_t y[1], uv[2] = {128u, 128u};
+                align_bilinear<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q[k], y);
+                AlignPos qc;
+                if (align_quantise(sx[k] * 0.5f, sy[k] * 0.5f, qc))       // (exact halves: never refused behind an accepted luma position)
+                    align_bilinear<2, 2, WIDE, 128u>(r.p1, cw, ch, r.cstride, qc, uv);
+                align_nv12_to_bgr(y[0], uv[0], uv[1], px[k]);
+            }
+        break;
+    }
+    }
+    if (r.format == SDM_FRAME_RGB || r.format == SDM_FRAME_RGBA) {          // byte 0 is R: (B, G, R) by byte position
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { const uint32_t t = px[k][0]; px[k][0] = px[k][2]; px[k][2] = t; }
+    }
+}
+
+// output channel c of CH from a warped (B, G, R); weigh: the source is BGR / RGB / BGRA / RGBA (a gray or luma-only value passes)
+template <int CH>
+ALIGN_HD uint32_t align_channel(const uint32_t bgr[3], int c, bool weigh, int order, int wb, int wg, int wr, int shift)
+{
+    if constexpr (CH == 3) return order == SDM_ALIGN_ORDER_RGB ? bgr[2 - c] : bgr[c];
+    else return weigh ? (bgr[0] * wb + bgr[1] * wg + bgr[2] * wr + (1u << (shift - 1))) >> shift : bgr[0];
+}
+
+// (float)v * scale + bias: the product rounded, then the sum rounded
+ALIGN_HD float align_element(uint32_t v, float scale, float bias)
+{
+    const float p = (float)v * scale;
+    return p + bias;
+}

@@ -1,41 +1,26 @@
 // sdm_capi_align.hip -- C-ABI of the aligned face crops (include/sdm.h, sdm_align_*): the source of the taps in sdm_ctx::align, and a
 // call that fits every current row's similarity and warps its image into a crop (csrc/sdm_align.hip).  Every argument is checked
-// before anything is launched; the landmark state, the images and the tracker's slots are only read.
+// before anything is launched; the landmark state, the images and the tracker's slots are only read.  sdm_align_set_source_frames and
+// sdm_align_crops_tensor (csrc/sdm_align_tensor.hip): a frame list used in place as the source, and the crops as a network's input tensor.
 #include "sdm_capi_internal.h"
 
 #include <cmath>
+#include <limits.h>
 
-extern "C" {
-
-int sdm_align_set_source(sdm_ctx* c, const uint8_t* base, int n_images, int width, int height, int stride_bytes, int channels,
-                         int on_device)
+static int align_frame_bpp(int format)
 {
-    if (!c) return fail(SDM_ERR_INVALID, "null context");
-    sdm_ctx::Align& a = c->align;
-    if (!base) { a.base = nullptr; a.n = 0; a.C = 1; return SDM_OK; }          // the context's images
-    if (n_images < 1 || width < 1 || height < 1) return fail(SDM_ERR_INVALID, "an image stack needs n_images, width and height >= 1");
-    if (channels != 1 && channels != 3 && channels != 4) return fail(SDM_ERR_INVALID, "channels must be 1, 3 or 4");
-    if ((long long)stride_bytes < (long long)width * channels) return fail(SDM_ERR_INVALID, "stride_bytes < width * channels");
-    HIP_TRY(hipSetDevice(c->device));
-    const uint8_t* dev = base;
-    if (!on_device) {
-        // the bytes the warp can reach: up to the last pixel of the last row (a caller's row padding behind it need not exist)
-        const size_t bytes = ((size_t)n_images * height - 1) * (size_t)stride_bytes + (size_t)width * channels;
-        if (a.base == a.owned.p) { a.base = nullptr; a.n = 0; a.C = 1; }   // (the copy may be reallocated below: never left dangling)
-        int rc = a.owned.ensure(bytes);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(a.owned.p, base, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        dev = a.owned.p;
+    switch (format) {
+    case SDM_FRAME_GRAY: case SDM_FRAME_NV12: return 1;
+    case SDM_FRAME_BGR: case SDM_FRAME_RGB: return 3;
+    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return 4;
+    default: return 0;
     }
-    a.base = dev; a.n = n_images; a.w = width; a.h = height; a.stride = stride_bytes; a.C = channels;
-    return SDM_OK;
 }
 
-int sdm_align_crops(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h, uint8_t* out, int out_on_device,
-                    float* matrices_host, int* flags_host)
+// what sdm_align_crops and sdm_align_crops_tensor check alike, before anything is launched: geometry, rows, indices, template, crop
+// size, and that the source covers every row's image with that image's size
+static int align_check_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h)
 {
-    if (!c) return fail(SDM_ERR_INVALID, "null context");
     if (c->L <= 0) return fail(SDM_ERR_INVALID, "geometry not set");
     const int L = c->L, N = c->N;
     if (N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
@@ -53,15 +38,17 @@ int sdm_align_crops(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out
     for (int k = 1; k < K && !spread; ++k) spread = tmpl[2 * k] != tmpl[0] || tmpl[2 * k + 1] != tmpl[1];
     if (!spread) return fail(SDM_ERR_INVALID, "the K template points coincide");
     if (out_w < 1 || out_w > 1024 || out_h < 1 || out_h > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
-    sdm_ctx::Align& a = c->align;
-    const bool external = a.base != nullptr;
-    const int C = external ? a.C : 1;
-    if (!out) return fail(SDM_ERR_INVALID, "no output");
-    if (out_on_device && ((uintptr_t)out % (C == 4 ? 16 : 4)) != 0)
-        return fail(SDM_ERR_INVALID, "a device output must be 4-byte aligned (16 when C = 4)");
-    // every row's image: in the context's set, and -- external stack -- in the stack with that image's size
+    return SDM_OK;
+}
+
+static int align_check_rows(sdm_ctx* c)
+{
+    const sdm_ctx::Align& a = c->align;
+    const int N = c->N;
+    const bool external = a.base != nullptr, list = !a.fr.empty();
+    // every row's image: in the context's set, and -- external stack or frame list -- in the source with that image's size
     if (!c->img_base || c->n_images < 1) return fail(SDM_ERR_INVALID, "no images set");
-    const int n_src = external ? std::min(a.n, c->n_images) : c->n_images;
+    const int n_src = external ? std::min(a.n, c->n_images) : list ? std::min((int)a.fr.size(), c->n_images) : c->n_images;
     if (c->idx_identity && N > n_src) return fail(SDM_ERR_INVALID, "more rows than source images and no sample->image index set");
     if (!c->idx_identity && N > c->n_idx) return fail(SDM_ERR_INVALID, "sample->image index is shorter than the rows");
     for (int r = 0; r < N; ++r) {
@@ -69,44 +56,186 @@ int sdm_align_crops(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out
         if (im >= n_src) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to image " + std::to_string(im) + ", beyond the source");
         if (external && (c->img_w_host[im] != a.w || c->img_h_host[im] != a.h))
             return fail(SDM_ERR_INVALID, "the source stack's image size differs from image " + std::to_string(im) + " of the context");
+        if (list && (c->img_w_host[im] != a.fr[im].width || c->img_h_host[im] != a.fr[im].height))
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(im) + " of the source differs in size from image " + std::to_string(im) + " of the context");
     }
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t crop_bytes = (size_t)N * out_w * out_h * C;
-    int rc;
-    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure((size_t)N)) || (!out_on_device && (rc = a.crops.ensure(crop_bytes))))
-        return rc;
+    return SDM_OK;
+}
+
+// the K indices and the template in, the fit of every row into a.faces (the buffers are there)
+static int align_fit_rows(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h)
+{
+    sdm_ctx::Align& a = c->align;
     std::vector<int> in((size_t)3 * K);
     memcpy(in.data(), lm, (size_t)K * sizeof(int));
     memcpy(in.data() + K, tmpl, (size_t)2 * K * sizeof(float));
     HIP_TRY(hipMemcpyAsync(a.in.p, in.data(), in.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     AlignSourceDev src{};
-    const uint8_t* img;
-    if (external) {
+    if (a.base) {
         src.ctx.base = nullptr;
         src.width = a.w; src.height = a.h; src.stride = a.stride;
-        img = a.base;
     } else {
-        src.ctx = image_set(c);
-        img = c->img_base;
+        src.ctx = image_set(c);          // (a frame list: sizes from the context's images, which are the frames'; the rest from the table)
     }
-    sdm_launch_align_fit(c->x[c->cur].p, N, L, a.in.p, (const float*)(a.in.p + K), K, src, c->idx_identity ? nullptr : c->img_idx.p,
+    sdm_launch_align_fit(c->x[c->cur].p, c->N, c->L, a.in.p, (const float*)(a.in.p + K), K, src, c->idx_identity ? nullptr : c->img_idx.p,
                          out_w, out_h, a.faces.p, c->stream);
     HIP_TRY(hipGetLastError());
-    uint8_t* dst = out_on_device ? out : a.crops.p;
-    sdm_launch_align_warp(img, a.faces.p, N, out_w, out_h, C, dst, c->stream);
-    HIP_TRY(hipGetLastError());
+    return SDM_OK;
+}
+
+static int align_fetch_rows(sdm_ctx* c, float* matrices_host, int* flags_host)
+{
     std::vector<AlignFace> faces;
     if (matrices_host || flags_host) {
-        faces.resize((size_t)N);
-        HIP_TRY(hipMemcpyAsync(faces.data(), a.faces.p, (size_t)N * sizeof(AlignFace), hipMemcpyDeviceToHost, c->stream));
+        faces.resize((size_t)c->N);
+        HIP_TRY(hipMemcpyAsync(faces.data(), c->align.faces.p, (size_t)c->N * sizeof(AlignFace), hipMemcpyDeviceToHost, c->stream));
     }
-    if (!out_on_device) HIP_TRY(hipMemcpyAsync(out, a.crops.p, crop_bytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int r = 0; r < (int)faces.size(); ++r) {
         if (matrices_host) memcpy(matrices_host + (size_t)6 * r, faces[r].m, 6 * sizeof(float));
         if (flags_host) flags_host[r] = faces[r].flags;
     }
     return SDM_OK;
+}
+
+extern "C" {
+
+int sdm_align_set_source(sdm_ctx* c, const uint8_t* base, int n_images, int width, int height, int stride_bytes, int channels,
+                         int on_device)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    sdm_ctx::Align& a = c->align;
+    if (!base) { a.base = nullptr; a.n = 0; a.C = 1; a.fr.clear(); return SDM_OK; }          // the context's images
+    if (n_images < 1 || width < 1 || height < 1) return fail(SDM_ERR_INVALID, "an image stack needs n_images, width and height >= 1");
+    if (channels != 1 && channels != 3 && channels != 4) return fail(SDM_ERR_INVALID, "channels must be 1, 3 or 4");
+    if ((long long)stride_bytes < (long long)width * channels) return fail(SDM_ERR_INVALID, "stride_bytes < width * channels");
+    HIP_TRY(hipSetDevice(c->device));
+    const uint8_t* dev = base;
+    if (!on_device) {
+        // the bytes the warp can reach: up to the last pixel of the last row (a caller's row padding behind it need not exist)
+        const size_t bytes = ((size_t)n_images * height - 1) * (size_t)stride_bytes + (size_t)width * channels;
+        if (a.base == a.owned.p) { a.base = nullptr; a.n = 0; a.C = 1; }   // (the copy may be reallocated below: never left dangling)
+        int rc = a.owned.ensure(bytes);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(a.owned.p, base, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        dev = a.owned.p;
+    }
+    a.base = dev; a.n = n_images; a.w = width; a.h = height; a.stride = stride_bytes; a.C = channels;
+    a.fr.clear();                                                             // (a stack replaces a frame list)
+    return SDM_OK;
+}
+
+int sdm_align_set_source_frames(sdm_ctx* c, const sdm_frame* frames, const void* const* chroma, int n)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    sdm_ctx::Align& a = c->align;
+    if (n < 0) return fail(SDM_ERR_INVALID, "bad frame list");
+    if (!frames || n == 0) { a.base = nullptr; a.n = 0; a.C = 1; a.fr.clear(); return SDM_OK; }     // the context's images
+    // ---- every argument is checked before anything is allocated or copied ----
+    std::vector<AlignFrameDev> tab((size_t)n);
+    int bpp_all = -1;
+    const uint8_t* lowest = nullptr;
+    for (int i = 0; i < n; ++i) {
+        const sdm_frame& f = frames[i];
+        const int bpp = align_frame_bpp(f.format);
+        if (!bpp) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": unknown format");
+        if (!f.data) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": null pointer");
+        if (f.width < 1 || f.height < 1) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": width and height must be >= 1");
+        if ((long long)f.stride_bytes < (long long)f.width * bpp)
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < width * bytes per pixel");
+        AlignFrameDev& d = tab[i];
+        d.p0 = (const uint8_t*)f.data; d.p1 = nullptr; d.stride = f.stride_bytes; d.cstride = 0; d.format = f.format; d.pad = 0;
+        if (f.format == SDM_FRAME_NV12) {
+            if ((long long)f.stride_bytes < 2ll * ((f.width + 1) / 2))
+                return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": an NV12 frame needs stride_bytes >= 2 * ((width + 1) / 2)");
+            const void* uv = chroma ? chroma[i] : nullptr;
+            d.p1 = uv ? (const uint8_t*)uv : (const uint8_t*)f.data + (size_t)f.height * (size_t)f.stride_bytes;
+            d.cstride = f.stride_bytes;
+        }
+        const int kind = f.format == SDM_FRAME_NV12 ? 0 : bpp;
+        bpp_all = bpp_all < 0 ? kind : (bpp_all == kind ? kind : 0);
+        if (!lowest || d.p0 < lowest) lowest = d.p0;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = a.fr_dev.ensure((size_t)n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(a.fr_dev.p, tab.data(), (size_t)n * sizeof(AlignFrameDev), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    a.base = nullptr; a.n = 0; a.C = bpp_all > 0 ? bpp_all : 1;                // (a frame list replaces a stack)
+    a.fr.assign(frames, frames + n);
+    a.fr_base = lowest; a.fr_bpp = bpp_all;
+    return SDM_OK;
+}
+
+int sdm_align_crops(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h, uint8_t* out, int out_on_device,
+                    float* matrices_host, int* flags_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    int rc;
+    if ((rc = align_check_call(c, lm, tmpl, K, out_w, out_h))) return rc;
+    const int N = c->N;
+    sdm_ctx::Align& a = c->align;
+    const bool external = a.base != nullptr, list = !a.fr.empty();
+    if (list && a.fr_bpp == 0)
+        return fail(SDM_ERR_INVALID, "the frame-list source holds NV12 frames or frames of different pixel sizes: use sdm_align_crops_tensor");
+    const int C = external ? a.C : list ? a.fr_bpp : 1;
+    if (!out) return fail(SDM_ERR_INVALID, "no output");
+    if (out_on_device && ((uintptr_t)out % (C == 4 ? 16 : 4)) != 0)
+        return fail(SDM_ERR_INVALID, "a device output must be 4-byte aligned (16 when C = 4)");
+    if ((rc = align_check_rows(c))) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t crop_bytes = (size_t)N * out_w * out_h * C;
+    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure((size_t)N)) || (!out_on_device && (rc = a.crops.ensure(crop_bytes))))
+        return rc;
+    if ((rc = align_fit_rows(c, lm, tmpl, K, out_w, out_h))) return rc;
+    const uint8_t* img = external ? a.base : c->img_base;
+    if (list) {
+        img = a.fr_base;
+        sdm_launch_align_frame_rows(a.faces.p, a.fr_dev.p, c->idx_identity ? nullptr : c->img_idx.p, img, N, c->stream);
+        HIP_TRY(hipGetLastError());
+    }
+    uint8_t* dst = out_on_device ? out : a.crops.p;
+    sdm_launch_align_warp(img, a.faces.p, N, out_w, out_h, C, dst, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (!out_on_device) HIP_TRY(hipMemcpyAsync(out, a.crops.p, crop_bytes, hipMemcpyDeviceToHost, c->stream));
+    return align_fetch_rows(c, matrices_host, flags_host);
+}
+
+int sdm_align_crops_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h, const sdm_align_tensor* spec,
+                           void* out_dev, float* matrices_host, int* flags_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    int rc;
+    if ((rc = align_check_call(c, lm, tmpl, K, out_w, out_h))) return rc;
+    if (!spec) return fail(SDM_ERR_INVALID, "no tensor specification");
+    if (spec->dtype != SDM_ALIGN_U8 && spec->dtype != SDM_ALIGN_F16 && spec->dtype != SDM_ALIGN_F32) return fail(SDM_ERR_INVALID, "unknown dtype");
+    if (spec->layout != SDM_ALIGN_NHWC && spec->layout != SDM_ALIGN_NCHW) return fail(SDM_ERR_INVALID, "unknown layout");
+    if (spec->order != SDM_ALIGN_ORDER_BGR && spec->order != SDM_ALIGN_ORDER_RGB) return fail(SDM_ERR_INVALID, "unknown channel order");
+    if (spec->channels != 1 && spec->channels != 3) return fail(SDM_ERR_INVALID, "channels must be 1 or 3");
+    if (spec->gray_shift != 14 && spec->gray_shift != 15) return fail(SDM_ERR_INVALID, "gray_shift must be 14 (OpenCV 2.4 - 3.x) or 15");
+    if (spec->dtype != SDM_ALIGN_U8)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(spec->scale[k]) || !std::isfinite(spec->bias[k])) return fail(SDM_ERR_INVALID, "a scale or bias is not finite");
+    if (!out_dev) return fail(SDM_ERR_INVALID, "no output");
+    if ((uintptr_t)out_dev % 16 != 0) return fail(SDM_ERR_INVALID, "the output must be 16-byte aligned");
+    if ((rc = align_check_rows(c))) return rc;
+    const int N = c->N;
+    sdm_ctx::Align& a = c->align;
+    const bool external = a.base != nullptr, list = !a.fr.empty();
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure((size_t)N))) return rc;
+    if ((rc = align_fit_rows(c, lm, tmpl, K, out_w, out_h))) return rc;
+    AlignTensorDev t{};
+    for (int k = 0; k < 3; ++k) { t.scale[k] = spec->scale[k]; t.bias[k] = spec->bias[k]; }
+    t.order = spec->order; t.gray_shift = spec->gray_shift;
+    if (spec->gray_shift == 14) { t.wb = 1868; t.wg = 9617; t.wr = 4899; }        // sdm_upload_images_bgr_u8's two weight sets
+    else { t.wb = 3735; t.wg = 19235; t.wr = 9798; }
+    const int stack_format = !external ? SDM_FRAME_GRAY : a.C == 1 ? SDM_FRAME_GRAY : a.C == 3 ? SDM_FRAME_BGR : SDM_FRAME_BGRA;
+    sdm_launch_align_tensor(external ? a.base : c->img_base, a.faces.p, list ? a.fr_dev.p : nullptr, c->idx_identity ? nullptr : c->img_idx.p,
+                            stack_format, N, out_w, out_h, spec->dtype, spec->layout, spec->channels, t, out_dev, c->stream);
+    HIP_TRY(hipGetLastError());
+    return align_fetch_rows(c, matrices_host, flags_host);
 }
 
 }  // extern "C"

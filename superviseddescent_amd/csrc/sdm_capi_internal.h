@@ -259,7 +259,17 @@ struct sdm_ctx {
         DevBuf<int> in;                    // K indices + K x 2 template floats
         DevBuf<AlignFace> faces;           // N records
         DevBuf<uint8_t> crops;             // the crops of a host-memory out
-        void release() { in.release(); faces.release(); crops.release(); owned.release(); base = nullptr; n = 0; C = 1; }
+        // a frame list as the source (sdm_align_set_source_frames; base stays null): the frames as given, their device table, the
+        // lowest plane-0 address and the bytes per pixel all frames share (0: NV12 among them, or mixed)
+        std::vector<sdm_frame> fr;
+        DevBuf<AlignFrameDev> fr_dev;
+        const uint8_t* fr_base = nullptr;
+        int fr_bpp = 0;
+        void release()
+        {
+            in.release(); faces.release(); crops.release(); owned.release(); fr_dev.release();
+            base = nullptr; n = 0; C = 1; fr.clear();
+        }
     } align;
     // regulariser sweep (sdm_capi_sweep.hip): the unregularised normal equations kept as packed tiles, one regressor slot per
     // candidate (the apply GEMM's operand Rt + its float16 planes + their scale words) and the scoring scratch; allocated at the

@@ -392,3 +392,26 @@ void sdm_launch_align_fit(const float* x, int N, int L, const int* lm, const flo
                           const int* img_idx, int out_w, int out_h, AlignFace* faces, hipStream_t s);
 // out: N x out_h x out_w x C bytes (C = 1, 3 or 4), 4-byte aligned (16 when C = 4)
 void sdm_launch_align_warp(const uint8_t* img, const AlignFace* faces, int N, int out_w, int out_h, int C, uint8_t* out, hipStream_t s);
+
+// ---- crops as network input tensors (sdm_align_tensor.hip) ----
+// one frame of a frame-list crop source, used in place: plane 0 (Y, gray or the interleaved pixels), the interleaved UV plane of an
+// NV12 frame (null otherwise), their strides in bytes and the SDM_FRAME_* format
+struct AlignFrameDev {
+    const uint8_t* p0;
+    const uint8_t* p1;
+    int stride, cstride, format, pad;
+};
+// what the element stage needs: per OUTPUT channel scale and bias, the channel order and the colour -> gray weights
+struct AlignTensorDev {
+    float scale[3], bias[3];
+    int order;                 // SDM_ALIGN_ORDER_*
+    int wb, wg, wr, gray_shift;
+};
+// faces: the fit's records (M, flags, size; offset and stride against `base` unless `frames` is given).  frames: the frame table, or
+// null -- then every row's image is `src_format` (GRAY, BGR or BGRA) at base + faces[n].off.  img_idx: row -> frame (null: identity).
+// out: N * channels * out_h * out_w elements of `dtype` in `layout` (SDM_ALIGN_*), 16-byte aligned.
+void sdm_launch_align_tensor(const uint8_t* base, const AlignFace* faces, const AlignFrameDev* frames, const int* img_idx, int src_format,
+                             int N, int out_w, int out_h, int dtype, int layout, int channels, const AlignTensorDev& spec, void* out,
+                             hipStream_t s);
+// the fit's records re-pointed at a frame list of one pixel size, for align_warp_kernel: off = frames[im].p0 - base, stride = the frame's
+void sdm_launch_align_frame_rows(AlignFace* faces, const AlignFrameDev* frames, const int* img_idx, const uint8_t* base, int N, hipStream_t s);

@@ -13,6 +13,7 @@ Class and method names follow the reference so that the parity tests read like i
 ``ModelProjection``                            examples/pose_estimation.cpp:187-240 (head pose, csrc/sdm_pose.hip)
 ``detection_model.tracker`` / ``Tracker``       apps/rcr/rcr-track.cpp:133-177 (multi-stream tracking, csrc/sdm_track.hip)
 ``detection_model.aligned_crops``              (extension) aligned face crops of the current rows, csrc/sdm_align.hip
+``detection_model.aligned_crops_tensor``       (extension) the crops as a network's input tensor, csrc/sdm_align_tensor.hip
 =============================================  =====================================================
 
 Everything numeric happens on the MI355X: HOG extraction, regressor apply, Gram/RHS build and the
@@ -655,6 +656,65 @@ class Context:
         check(self._lib.sdm_align_crops(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height),
                                         crops.ctypes.data, 0, mats.ctypes.data, flags.ctypes.data))
         return crops, mats, flags
+
+    def align_set_source_frames(self, frames=None, formats=None, chroma=None):
+        """A frame list as the crop source, used in place (sdm_align_set_source_frames): ``frames`` and ``formats`` as for
+        ``set_frames_device`` -- all six formats --, ``chroma``: None or one entry per frame, the device pointer (or a uint8 tensor) of
+        an NV12 frame's interleaved UV plane; None entries mean "directly behind the Y plane".  ``frames`` None: back to the
+        context's images.  The memory must stay valid while crops are made from it.  Returns C of ``align_crops`` on this source
+        (the bytes per pixel all frames share), or None when only ``align_crops_tensor`` can read it (NV12, mixed pixel sizes)."""
+        if frames is None:
+            check(self._lib.sdm_align_set_source_frames(self._h, None, None, 0))
+            self.align_channels = 1
+            return 1
+        desc = _lib.frame_descriptors(frames, formats)
+        tensors = [frames] if _lib._is_tensor(frames) else list(frames)
+        uv = None
+        if chroma is not None:
+            if len(chroma) != len(desc):
+                raise ValueError("one chroma entry (or None) per frame expected")
+            tensors += [u for u in chroma if _lib._is_tensor(u)]
+            uv = (ctypes.c_void_p * len(desc))(*[None if u is None else int(u.data_ptr()) if _lib._is_tensor(u) else int(u) for u in chroma])
+        for t in tensors:
+            if getattr(t, "is_cuda", False):
+                import torch
+                torch.cuda.current_stream(t.device).synchronize()          # (the library runs on its own stream)
+                break
+        arr = (_lib.SdmFrame * len(desc))(*[_lib.SdmFrame(ctypes.c_void_p(p), w, h, st, f) for p, w, h, st, f in desc])
+        check(self._lib.sdm_align_set_source_frames(self._h, arr, uv, len(desc)))
+        kinds = {0 if f == _lib.SDM_FRAME_NV12 else _lib._FRAME_CHANNELS[f] for _, _, _, _, f in desc}
+        C = kinds.pop() if len(kinds) == 1 else 0
+        self.align_channels = C if C else 1
+        return C if C else None
+
+    def align_crops_tensor(self, landmark_index, template: np.ndarray, width: int, height: int, spec=None, out=None, **options):
+        """Crops of the N current rows as a network's input tensor (include/sdm.h, sdm_align_crops_tensor) from the source set by
+        ``align_set_source_frames`` / ``align_set_source`` (default: the context's images).  ``spec``: an ``_lib.SdmAlignTensor``, or
+        the ``options`` of ``_lib.align_tensor_spec`` (dtype, layout, channels, order, scale, bias, mean, std, gray_shift).  ``out``:
+        a contiguous device tensor of the requested dtype and shape, written in place; default: a new one.  Returns (tensor
+        N x C x H x W or N x H x W x C, matrices N x 2 x 3 float32, flags N int32)."""
+        if spec is None:
+            spec = _lib.align_tensor_spec(**options)
+        elif options:
+            raise ValueError("give either spec or the named options")
+        idx = np.ascontiguousarray(landmark_index, np.int32).reshape(-1)
+        t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
+        if t.shape[0] != idx.size:
+            raise ValueError("one template point (x, y) per landmark index expected")
+        n = int(getattr(self, "N", 0))          # (0: no rows yet -- the library refuses the call)
+        shape = _lib.align_tensor_shape(n, int(width), int(height), spec.layout, spec.channels)
+        name = {v: k for k, v in _lib.ALIGN_DTYPES.items()}[spec.dtype]
+        import torch
+        if out is None:
+            out = torch.empty(shape, dtype=getattr(torch, name), device=f"cuda:{self.device}")
+        else:
+            _lib.check_align_out(out, shape, name)
+        mats = np.empty((n, 2, 3), np.float32)
+        flags = np.empty(n, np.int32)
+        torch.cuda.current_stream(out.device).synchronize()
+        check(self._lib.sdm_align_crops_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height), ctypes.byref(spec),
+                                               ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
+        return out, mats, flags
 
     # -- misc ------------------------------------------------------------------------------------------
     def synchronize(self):
@@ -1324,6 +1384,40 @@ class detection_model:
         finally:
             if source is not None:
                 c.align_set_source(None)                                  # (no pointer to the caller's frames stays behind)
+
+    def aligned_crops_tensor(self, size, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
+                             margin: float = 0.2, frames=None, formats=None, chroma=None, dtype="float16", layout="nchw", channels=3,
+                             order="rgb", scale=None, bias=None, mean=None, std=None, gray_shift=14, out=None):
+        """Aligned face crops of the current rows as a network's input tensor, in one launch from the frames where they lie on the
+        device (include/sdm.h, sdm_align_crops_tensor).  ``size``, ``landmark_ids``, ``template``, ``margin``: as for
+        :meth:`aligned_crops`.  ``frames``: what ``detect_batch`` and ``Tracker.step`` accept as device frames -- uint8 tensors of any
+        size and row stride (gray, "bgr" / "rgb", "bgra" / "rgba" by ``formats``), (ptr, w, h, stride, format) tuples ("nv12": ptr = the
+        Y plane; ``chroma``: per frame the UV plane's pointer or tensor, None = directly behind Y), one stacked tensor -- used in place,
+        each with the size of the context image its row maps to; None: the context's own gray images.  ``dtype``: "float16" |
+        "float32" | "uint8"; ``layout``: "nchw" | "nhwc"; ``channels``: 3 (a gray source is replicated) or 1 (colour is weighed with
+        the gray weights of ``gray_shift``; NV12 gives Y); ``order``: "rgb" | "bgr".  Element = float32(v) * scale[c] + bias[c] per
+        output channel c, the product and the sum each rounded to float32, then once to float16.  ``scale`` / ``bias``: a scalar or 3
+        values, passed as float32.  ``mean`` / ``std`` (0-255 units) are sugar for ``scale = float32(1 / std)``,
+        ``bias = float32(-mean / std)``; giving both pairs is an error.  ``out``: a contiguous device tensor of that dtype and shape.
+        Returns (tensor, matrices N x 2 x 3 crop -> source, flags N: SDM_ALIGN_*).  No pointer to the frames stays behind."""
+        c = self.optimised_model.ctx
+        if not getattr(c, "N", 0):
+            raise RuntimeError("run detect_batch or Tracker.step first")
+        spec = _lib.align_tensor_spec(dtype, layout, channels, order, scale, bias, mean, std, gray_shift)
+        width, height = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        ids = self.landmark_ids if landmark_ids is None else [str(i) for i in landmark_ids]
+        missing = [i for i in ids if i not in self.landmark_ids]
+        if missing:
+            raise ValueError(f"landmark ids not in this model: {missing}")
+        idx = [self.landmark_ids.index(i) for i in ids]
+        if template is None:
+            template = alignment_template(self.mean, idx, width, height, margin)
+        c.align_set_source_frames(frames, formats, chroma)
+        try:
+            return c.align_crops_tensor(idx, template, width, height, spec=spec, out=out)
+        finally:
+            if frames is not None:
+                c.align_set_source_frames(None)                           # (no pointer to the caller's frames stays behind)
 
     def get_mean(self) -> np.ndarray:
         return self.mean

@@ -131,5 +131,88 @@ inline aligned_crops_result aligned_crops(detection_model& model, const std::vec
     return detail::align_current_rows(c, x.rows, landmark_index, tmpl, width, height, colour_images);
 }
 
+/** What sdm_align_crops_tensor writes (sdm_align_tensor of include/sdm.h): the element type, the layout, 1 or 3 channels, their order,
+ *  and element = float32(v) * scale[c] + bias[c] per output channel c (ignored for SDM_ALIGN_U8). */
+struct TensorSpec {
+    int dtype = SDM_ALIGN_F16, layout = SDM_ALIGN_NCHW, channels = 3, order = SDM_ALIGN_ORDER_RGB;
+    float scale[3] = {1.0f, 1.0f, 1.0f}, bias[3] = {0.0f, 0.0f, 0.0f};
+    int gray_shift = 14;
+    /** mean and std in 0-255 units: scale = float(1 / std), bias = float(-mean / std), the quotients computed in double */
+    TensorSpec& normalise(const double (&mean)[3], const double (&std)[3])
+    {
+        for (int c = 0; c < 3; ++c) { scale[c] = (float)(1.0 / std[c]); bias[c] = (float)(-mean[c] / std[c]); }
+        return *this;
+    }
+    size_t element_size() const { return dtype == SDM_ALIGN_U8 ? 1 : dtype == SDM_ALIGN_F16 ? 2 : 4; }
+};
+
+struct aligned_tensor_result {
+    cv::Mat matrices;              // rows x 6 CV_32FC1: the crop -> source map of every row (NaN for a degenerate row)
+    std::vector<int> flags;        // SDM_ALIGN_DEGENERATE / SDM_ALIGN_PARTIAL bits
+};
+
+namespace detail {
+
+// the n current rows of the handle `c` as a tensor in device memory, cut from `frames` in place (`chroma`: empty, or per frame the UV
+// plane of an NV12 frame, nullptr = behind its Y plane) or -- no frames -- from the handle's own images
+inline aligned_tensor_result align_tensor_current_rows(sdm_ctx* c, int n, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
+                                                       int height, const std::vector<DeviceFrame>& frames, const std::vector<const void*>& chroma,
+                                                       const TensorSpec& spec, void* out_dev)
+{
+    using superviseddescent::hip::check;
+    if (tmpl.rows != (int)landmark_index.size() || tmpl.cols != 2) throw std::runtime_error("aligned_crops_tensor: one template point (x, y) per landmark");
+    if (!chroma.empty() && chroma.size() != frames.size()) throw std::runtime_error("aligned_crops_tensor: one chroma pointer (or nullptr) per frame");
+    cv::Mat t = tmpl.isContinuous() ? tmpl : tmpl.clone();
+    std::vector<sdm_frame> f;
+    for (const auto& d : frames) f.push_back(sdm_frame{d.data, d.width, d.height, d.stride_bytes, d.format});
+    check(sdm_align_set_source_frames(c, f.empty() ? nullptr : f.data(), chroma.empty() ? nullptr : chroma.data(), (int)f.size()),
+          "sdm_align_set_source_frames");
+    sdm_align_tensor s{};
+    s.dtype = spec.dtype; s.layout = spec.layout; s.channels = spec.channels; s.order = spec.order; s.gray_shift = spec.gray_shift;
+    for (int k = 0; k < 3; ++k) { s.scale[k] = spec.scale[k]; s.bias[k] = spec.bias[k]; }
+    aligned_tensor_result res;
+    res.matrices = cv::Mat(n, 6, CV_32FC1);
+    res.flags.resize((size_t)n);
+    const int rc = sdm_align_crops_tensor(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s, out_dev,
+                                          res.matrices.ptr<float>(0), res.flags.data());
+    if (!frames.empty()) sdm_align_set_source_frames(c, nullptr, nullptr, 0);     // (no pointer to the caller's frames stays behind)
+    check(rc, "sdm_align_crops_tensor");
+    return res;
+}
+
+}  // namespace detail
+
+/** The streams of the tracker's last step as a network's input tensor, written to `out_dev` (device memory, rows * channels * height *
+ *  width elements of spec.dtype, 16-byte aligned): cut in one launch from `frames` where they lie on the device -- the frames of that
+ *  step, any of the six formats, same sizes, same order -- or, `frames` empty, from the step's gray images. */
+inline aligned_tensor_result aligned_crops_tensor(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                                  const TensorSpec& spec, void* out_dev, const std::vector<DeviceFrame>& frames = {},
+                                                  const std::vector<const void*>& chroma = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("aligned_crops_tensor: step the tracker first");
+    return detail::align_tensor_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, frames, chroma, spec, out_dev);
+}
+
+/** The same for landmark rows on device frames, e.g. the result of detection_model::detect_batch(frames, boxes, image_index): row i is
+ *  cut from frames[image_index[i]] (default: frames[i]).  As the cv::Mat overload of aligned_crops, this one works on a handle of its
+ *  own: the frames become its image set (colour converted to gray once, which the crops do not read) and the rows are uploaded. */
+inline aligned_tensor_result aligned_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                                  const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl,
+                                                  int width, int height, const TensorSpec& spec, void* out_dev,
+                                                  const std::vector<const void*>& chroma = {})
+{
+    using superviseddescent::hip::check;
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    sdm_ctx* c = h.get();
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::set_device_frames(h, frames);
+    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
+    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("aligned_crops_tensor: rows must hold 2L coordinates");
+    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
+    return detail::align_tensor_current_rows(c, x.rows, landmark_index, tmpl, width, height, frames, chroma, spec, out_dev);
+}
+
 }  // namespace rcr
 #endif /* RCR_ALIGNMENT_HPP_ */
