@@ -113,8 +113,23 @@ int sdm_set_hog_mode(sdm_ctx* ctx, int mode);
 int sdm_get_hog_info(sdm_ctx* ctx, int level, int* fast_kernel, int* fast_bins);
 
 /* Images: the `const std::vector<cv::Mat>& images` of HogTransform (adaptive_vlhog.hpp:92,188),
- * single channel u8.  Host images are copied to HBM once.  (Images less than 2 pixels wide or 65 536+ rows high run the
- * generic HOG kernel instead of the fused one: same results, slower.) */
+ * single channel u8.  Host images are copied to HBM once.
+ *
+ * Frame geometry, the same for every image entry point below (tests/test_gpu_frame_geometry.py pins each line):
+ *   width, height        any positive int (run: 70 000 columns, 65 600 rows).  stride_bytes: any int >= the row's bytes.
+ *   fused pixel kernels  serve a set whose every image has width >= 2, height <= 65 535, stride_bytes <= 2^20 and
+ *                        height * stride_bytes <= INT_MAX (run: stride 2^20 under 2 047 rows, a byte offset inside the image of
+ *                        2 146 435 135).  One image beyond any of the four sends the WHOLE set to the generic HOG kernel: same
+ *                        integer decisions, features within the same tolerance, slower (run: strides 26 843 545 and 26 843 547
+ *                        under 80 rows, with faces 175 rows above and below the image).
+ *                        A patch may lie partly or wholly outside its image: it reads black there.  With the fused kernels this
+ *                        holds while (rows it reaches above or below the image) * stride_bytes < 2^31 -- 2 048 rows at the
+ *                        largest stride (run: 2 000 rows), 131 072 rows at a stride of 16 384; a patch further out is not supported.
+ *   distance of frames   images of one set may lie anywhere in the device's address space, in any order (run: 2^32 + 2^28 bytes
+ *                        apart, the first frame the highest); sdm_set_images_device's image i lies i * height * stride_bytes
+ *                        behind the base, in 64 bits (run: above 2^31).
+ *   crops, tracker       read the same table with 64-bit offsets; sdm_align_crops_tensor uses 32-bit offsets inside a plane of at
+ *                        most INT_MAX bytes (NV12: both planes) and 64-bit ones beyond. */
 int sdm_upload_images_u8(sdm_ctx* ctx, const uint8_t* const* images, const int* width, const int* height,
                          const int* stride_bytes, int n_images);
 /* The same for 3-channel images in cv::imread's BGR byte order (stride_bytes >= 3 * width): converted to gray ONCE per image
@@ -124,7 +139,7 @@ int sdm_upload_images_u8(sdm_ctx* ctx, const uint8_t* const* images, const int* 
  * unpinned for this step, like cv::resize.) */
 int sdm_upload_images_bgr_u8(sdm_ctx* ctx, const uint8_t* const* images, const int* width, const int* height,
                              const int* stride_bytes, int n_images, int gray_shift);
-/* Device-resident stack of equally sized images (image i at base + i*height*stride_bytes); not copied. */
+/* Device-resident stack of equally sized images (image i at base + i*height*stride_bytes, a 64-bit product); not copied. */
 int sdm_set_images_device(sdm_ctx* ctx, const uint8_t* dev_base, int n_images, int width, int height,
                           int stride_bytes);
 /* Frames that are ALREADY on the device -- a hardware decoder's output, torch tensors, regions of a larger frame -- as the image
@@ -141,8 +156,9 @@ int sdm_set_images_device(sdm_ctx* ctx, const uint8_t* dev_base, int n_images, i
  *   mixed sets are allowed: in-place and owned images share the one image table (its base is the lowest address of the set).
  * Argument errors (SDM_ERR_INVALID) change no state and launch nothing -- the previous image set stays the one in use: NULL,
  * n_frames < 1, width or height < 1, stride_bytes < width * bytes per pixel, an unknown format, gray_shift not 14 or 15, and
- * colour frames of 2^31 or more 16-pixel row chunks in one call.  (As with the other image entry points, an image less than 2
- * pixels wide or 65 536+ rows high -- or one whose height * stride_bytes does not fit 31 bits -- selects the generic HOG kernel.) */
+ * colour frames of 2^31 or more 16-pixel row chunks in one call.  (The frame geometry rule above holds: an image less than 2
+ * pixels wide, 65 536+ rows high, of a stride above 2^20 or of more than INT_MAX bytes of height * stride_bytes selects the
+ * generic HOG kernel.) */
 #define SDM_FRAME_GRAY 0   /* 1 byte per pixel, used in place                                  */
 #define SDM_FRAME_BGR  1   /* 3 bytes, cv::imread order                                        */
 #define SDM_FRAME_RGB  2

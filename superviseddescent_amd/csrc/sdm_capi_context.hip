@@ -308,7 +308,7 @@ int sdm_upload_images_u8(sdm_ctx* c, const uint8_t* const* images, const int* w,
     c->n_images = n;
     c->img_w_host.assign(w, w + n); c->img_h_host.assign(h, h + n);
     c->narrow_images = false;
-    for (int i = 0; i < n; ++i) c->narrow_images = c->narrow_images || w[i] < 2 || h[i] > 65535;
+    for (int i = 0; i < n; ++i) c->narrow_images = c->narrow_images || image_needs_generic(w[i], h[i], w[i]);
     return SDM_OK;
 }
 
@@ -354,7 +354,7 @@ int sdm_upload_images_bgr_u8(sdm_ctx* c, const uint8_t* const* images, const int
     c->n_images = n;
     c->img_w_host.assign(w, w + n); c->img_h_host.assign(h, h + n);
     c->narrow_images = false;
-    for (int i = 0; i < n; ++i) c->narrow_images = c->narrow_images || w[i] < 2 || h[i] > 65535;
+    for (int i = 0; i < n; ++i) c->narrow_images = c->narrow_images || image_needs_generic(w[i], h[i], w[i]);
     return SDM_OK;
 }
 
@@ -385,7 +385,7 @@ int sdm_set_images_device(sdm_ctx* c, const uint8_t* dev_base, int n, int w, int
     c->img_base = dev_base;
     c->n_images = n;
     c->img_w_host.assign(n, w); c->img_h_host.assign(n, h);
-    c->narrow_images = w < 2 || h > 65535;
+    c->narrow_images = image_needs_generic(w, h, stride);
     return SDM_OK;
 }
 

@@ -58,9 +58,7 @@ int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_s
         vw[i] = f.width; vh[i] = f.height;
         if (frame_bpp(f.format) == 1) { addr[i] = (const uint8_t*)f.data; vs[i] = f.stride_bytes; }
         else { addr[i] = c->frames.gray.p + conv[k].dst_off; vs[i] = conv[k].gstride; ++k; }
-        // the rule of the other image entry points, and -- an image taller than 2 GiB of rows, which they cannot meet with their
-        // int sizes either way -- the fused kernels' 32-bit num_records
-        narrow = narrow || f.width < 2 || f.height > 65535 || (long long)vs[i] * f.height > (long long)INT_MAX;
+        narrow = narrow || image_needs_generic(f.width, f.height, vs[i]);      // (the rule of every image entry point)
     }
     const uint8_t* base = addr[0];
     for (int i = 1; i < n; ++i) if (addr[i] < base) base = addr[i];

@@ -12,6 +12,7 @@
 #include "sdm_kernels.h"
 
 #include <dlfcn.h>
+#include <limits.h>
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,6 +30,17 @@ inline int fail(int code, const std::string& msg)
 {
     err_string() = msg;
     return code;
+}
+
+// The one rule of every image entry point: an image the fused pixel kernels cannot serve sends its whole set to the generic kernel
+// (same results, slower).  Their paired-byte loads need 2 columns, their packed row tables rows below 2^16, their buffer
+// descriptor (num_records) a plane of at most INT_MAX bytes.  They form (row of the patch) * stride in 32 bits, for rows above and
+// below the image too, and rely on the range check against num_records to read those as black: a product that passes 2^31 outside
+// the plane wraps back into it.  The stride bound keeps that 2 048 rows away at the least (include/sdm.h, "Frame geometry").
+constexpr long long SDM_FUSED_MAX_STRIDE = 1ll << 20;
+inline bool image_needs_generic(int w, int h, long long stride)
+{
+    return w < 2 || h > 65535 || stride > SDM_FUSED_MAX_STRIDE || stride * h > (long long)INT_MAX;
 }
 
 #define HIP_TRY(expr)                                                                          \
