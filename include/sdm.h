@@ -501,7 +501,8 @@ int sdm_track_get(sdm_ctx* ctx, const int* ids, int n, float* landmarks_host, in
  *           X = floor(sx * 32 + 0.5f) in float32, x0 = X >> 5, fx = X & 31, y the same; per channel
  *           (w00 p(x0, y0) + w10 p(x0 + 1, y0) + w01 p(x0, y0 + 1) + w11 p(x0 + 1, y0 + 1) + 512) >> 10 with w00 = (32 - fx)(32 - fy),
  *           w10 = fx (32 - fy), w01 = (32 - fx) fy, w11 = fx fy.  A tap outside the image reads 0; a non-finite position, or one
- *           with |sx| or |sy| > 2^20, gives 0.  Plain bilinear, no antialiasing.
+ *           with |sx| or |sy| > 2^20, gives 0.  Plain bilinear, no antialiasing: this interleaved u8 form, alpha included, stays
+ *           bilinear (sdm_align_crops_tensor_filtered averages a minifying row's footprint).
  *   flags   SDM_ALIGN_DEGENERATE: a selected landmark is not finite, or sum|p~|^2 == 0 -- the crop is all zeros, M six NaNs, and no
  *           other bit is evaluated.  SDM_ALIGN_PARTIAL: a crop corner (column 0 or out_width - 1, row 0 or out_height - 1) samples
  *           outside [0, W - 1] x [0, H - 1] of the row's image, on the float32 positions above.
@@ -582,6 +583,40 @@ typedef struct sdm_align_tensor {
 /* out_dev: device memory, N * channels * out_height * out_width elements, 16-byte aligned. */
 int sdm_align_crops_tensor(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int out_width,
                            int out_height, const sdm_align_tensor* spec, void* out_dev, float* matrices_host, int* flags_host);
+
+/* sdm_align_crops_tensor with area-averaged sampling where a row's similarity minifies: a face 300 to 1000 pixels wide in a 112-pixel crop
+ * puts 3 to 9 source pixels under every crop pixel, of which four bilinear taps see a fraction.  Here every output pixel of such a row is
+ * the average of S x S bilinear sub-samples spread over its footprint, S chosen per row from the fitted scale, all in the integer arithmetic
+ * of the crop path.  One launch for all rows behind the fit kernel; rows with S = 1 run sdm_align_crops_tensor's code and give its bits.
+ *   1. unchanged from sdm_align_crops_tensor: the fit, M, the flags (PARTIAL is still judged on the corner pixel CENTRES), the source
+ *      rules, the channel, element and layout rules (its items 3 to 6) and its refusals.  Refused in addition: filter NULL, an unknown
+ *      mode, max_samples outside [1, 16], min_scale not finite or below 1.  Every refusal returns SDM_ERR_INVALID, changes no state and
+ *      launches nothing.
+ *   2. S of row n   s2 = M00 M00 + M10 M10 in float32, each operation rounded, nothing contracted.  S = 1 for mode BILINEAR, for
+ *      s2 < min_scale * min_scale (float32), for a non-finite s2 and for a DEGENERATE row; otherwise the smallest integer in
+ *      [1, max_samples] with (float)(S S) >= s2, and max_samples when there is none.  samples_host[n] = S.
+ *   3. sub-sample positions   for u, v in 0 ... S - 1: fj = (float)j + o[u], fi = (float)i + o[v] with o[u] = (float)(2u + 1 - S) /
+ *      (float)(2S), a correctly rounded float32 division; then sx = (M00 fj + M01 fi) + M02 and sy likewise: sdm_align_crops' expression
+ *      at a fractional (j, i).  S = 1: o = 0, the position of sdm_align_crops.
+ *   4. sub-sample value   sdm_align_crops' quantisation to 1/32 pixel, taps and weights, without the final rounding: per byte position
+ *      q = w00 p00 + w10 p10 + w01 p01 + w11 p11 <= 255 * 1024.  A tap outside the image reads 0, an NV12 chroma tap outside reads 128.
+ *   5. pixel value   v = (sum of q over the S S sub-samples + 512 S S) / (1024 S S), an unsigned integer division; the sum stays below
+ *      2^26 + 2^17.  S = 1: (q + 512) >> 10.  If any sub-sample of the pixel is refused by the 2^20 rule the pixel is 0 -- (0, 0, 0) for
+ *      NV12 with three output channels.
+ *   6. NV12   Y is averaged as in 5; U and V the same way over the same S S sub-samples at cx = sx * 0.5f, cy = sy * 0.5f; the BT.601
+ *      conversion is applied once, to the averaged (Y, U, V).  channels == 1 gives the averaged Y as it is, and the UV plane is not read.
+ *   7. a colour source to one channel: the gray weights apply to the averaged (B, G, R).
+ * samples_host (N) may be NULL; it comes back with the matrices and flags in the same copy. */
+#define SDM_ALIGN_FILTER_BILINEAR  0   /* mode                                     */
+#define SDM_ALIGN_FILTER_AREA      1
+typedef struct sdm_align_filter {
+    int   mode;         /* SDM_ALIGN_FILTER_*                                                         */
+    int   max_samples;  /* cap on S, the sub-samples per axis: 1 .. 16                                */
+    float min_scale;    /* finite, >= 1: rows whose scale^2 < min_scale * min_scale (float32) take S = 1 */
+} sdm_align_filter;
+int sdm_align_crops_tensor_filtered(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int out_width,
+                                    int out_height, const sdm_align_tensor* spec, const sdm_align_filter* filter, void* out_dev,
+                                    float* matrices_host, int* flags_host, int* samples_host);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,127 @@
+"""Time of the area-averaged crop tensors (Context.align_crops_tensor(filter="area"), csrc/sdm_align_area.hip) against the plain bilinear
+call (csrc/sdm_align_tensor.hip): N = 4 096 rows, float16 N x 3 x 112 x 112 RGB with mean / std, everything resident on the device, from
+  bgr    64 BGR frames of 256 x 256, used in place
+  nv12   8 NV12 surfaces of 1920 x 1080 (Y plane and interleaved UV plane), used in place
+at crop -> source scales of 0.95, 1.95, 3.9 and 7.8 (+-20 degrees, crop centres around the frame centre), which give every row S = 1, 2,
+4 and 8 (at exactly 2, 4 or 8 the float32 s2 of a rotated row falls on either side of S S and about half of the rows take S + 1; the
+result records the range of S).  Host clock around a call that ends in the library's own synchronise; per case REPEATS repeats of CALLS calls behind 5 warm-up calls, the median of every
+repeat, and over the repeats their median and their spread (max - min).  Sub-samples per second = 112 112 (sum over the rows of S S) / median.
+
+Every measurement runs in a child process of its own, one after the other.  --parent-tree DIR (a checkout of the parent commit with its
+library built, inside the repository directory) adds children that time the parent's sdm_align_crops_tensor, alternating with this
+tree's: the scale-0.95 comparison "filtered call, all rows S = 1" against "the parent's call" with the parent's own run-to-run spread.
+Writes profiles/align_area_timing.json (or --out)."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N, SIZE, REPEATS = 4096, 112, 5
+SCALES = (0.95, 1.95, 3.9, 7.8)
+MEAN, STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
+
+
+def child(tree, filtered):
+    sys.path.insert(0, tree)
+    import torch
+    from superviseddescent_amd import Context, HoGParam, alignment_template, ibug
+    ids = ibug.RCR22_IDS
+    L = len(ids)
+    re, le = ibug.eye_indices(ids)
+    ctx = Context(0)
+    ctx.set_model_geometry(L, re, le, [HoGParam(1, 5, 6, 4, 0.6)])
+    rng = np.random.default_rng(7)
+    lm = np.arange(L)
+    tmpl = alignment_template(ibug.select_mean(ids), lm, SIZE, SIZE, 0.2).astype(np.float64)
+    bgr = torch.from_numpy(rng.integers(0, 256, (64, 256, 256, 3), dtype=np.uint8)).cuda()
+    nv = torch.from_numpy(rng.integers(0, 256, (8, 1080 + 540, 1920), dtype=np.uint8)).cuda()
+    sources = {"bgr": ([(bgr[i].data_ptr(), 256, 256, 256 * 3, "bgr") for i in range(64)], 256, 256),
+               "nv12": ([(nv[i].data_ptr(), 1920, 1080, 1920, "nv12") for i in range(8)], 1920, 1080)}
+    out = torch.empty((N, 3, SIZE, SIZE), dtype=torch.float16, device="cuda")
+    res = {"device": torch.cuda.get_device_name(0)}
+    for name, (frames, W, H) in sources.items():
+        ctx.set_frames_device(frames)
+        idx = np.arange(N) % len(frames)
+        ctx.set_sample_image_index(idx)
+        ctx.align_set_source_frames(frames)
+        for s in SCALES:
+            x = np.zeros((N, 2 * L), np.float32)
+            ang = np.deg2rad(rng.uniform(-20, 20, N))
+            c, sn = s * np.cos(ang), s * np.sin(ang)
+            centre = np.array([(W - 1) / 2, (H - 1) / 2]) + rng.uniform(-0.1, 0.1, (N, 2)) * (W, H)
+            q = tmpl - (SIZE - 1) / 2
+            x[:, :L] = c[:, None] * q[:, 0] - sn[:, None] * q[:, 1] + centre[:, :1]
+            x[:, L:] = sn[:, None] * q[:, 0] + c[:, None] * q[:, 1] + centre[:, 1:]
+            ctx.set_x(x)
+            calls = 40 if s <= 2 else 15
+            variants = {"plain": {}}
+            if filtered:
+                variants["area"] = {"filter": "area"}
+                if s < 1.0:
+                    variants["filter_bilinear"] = {"filter": "bilinear"}
+            for vname, kw in variants.items():
+                fn = lambda: ctx.align_crops_tensor(lm, tmpl, SIZE, SIZE, out=out, mean=MEAN, std=STD, **kw)
+                for _ in range(5):
+                    r = fn()
+                medians = []
+                for _ in range(REPEATS):
+                    ts = []
+                    for _ in range(calls):
+                        t0 = time.perf_counter()
+                        fn()                                             # (ends in the library's stream synchronise)
+                        ts.append(time.perf_counter() - t0)
+                    medians.append(float(np.median(ts)) * 1e3)
+                e = {"repeat_medians_ms": medians, "median_ms": float(np.median(medians)), "spread_ms": max(medians) - min(medians),
+                     "calls_per_repeat": calls}
+                if vname == "area":
+                    S = np.asarray(r[3])
+                    e["S_min"], e["S_max"] = int(S.min()), int(S.max())
+                    e["sub_samples_per_s"] = float((S.astype(np.float64) ** 2).sum() * SIZE * SIZE / (e["median_ms"] * 1e-3))
+                res["%s scale %g %s" % (name, s, vname)] = e
+        ctx.align_set_source_frames(None)
+    print("RESULT " + json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--parent-tree", default=None)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_area_timing.json"))
+    ap.add_argument("--child", default=None)
+    ap.add_argument("--filtered", type=int, default=1)
+    a = ap.parse_args()
+    if a.child:
+        return child(a.child, a.filtered)
+    order = [("this", ROOT, 1)]
+    if a.parent_tree:
+        p = os.path.abspath(a.parent_tree)
+        order = [("parent", p, 0), ("this", ROOT, 1), ("parent", p, 0), ("this", ROOT, 1), ("parent", p, 0)]
+    runs = []
+    for label, tree, filtered in order:
+        env = dict(os.environ)
+        env.pop("SDM_HIP_LIB", None)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", tree, "--filtered", str(filtered)], capture_output=True,
+                           text=True, timeout=900, env=env)
+        if r.returncode != 0:
+            sys.stderr.write(r.stdout + r.stderr)
+            raise SystemExit("the %s child failed with status %d" % (label, r.returncode))
+        line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")][-1]
+        runs.append({"tree": label, "result": json.loads(line[7:])})
+        print(label, "done", flush=True)
+    doc = {"rows": N, "crop": "112 x 112 x 3 float16 NCHW", "unit": "ms per call, host clock, the call ends in a stream synchronise",
+           "repeats": REPEATS, "runs": runs}
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    for run in runs:
+        for k, v in run["result"].items():
+            if isinstance(v, dict):
+                print("%-7s %-32s median %8.3f ms  spread %6.3f ms%s" % (run["tree"], k, v["median_ms"], v["spread_ms"],
+                      "  %.3g sub-samples/s" % v["sub_samples_per_s"] if "sub_samples_per_s" in v else ""))
+
+
+if __name__ == "__main__":
+    main()

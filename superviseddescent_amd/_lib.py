@@ -34,7 +34,7 @@ EXPORTED = [
     "sdm_pose_templates_from_landmarks", "sdm_pose_set_targets", "sdm_pose_features", "sdm_pose_train_level",
     "sdm_pose_set_regressor", "sdm_pose_get_regressor", "sdm_pose_test",
     "sdm_track_configure", "sdm_track_start", "sdm_track_stop", "sdm_track_step", "sdm_track_get",
-    "sdm_align_set_source", "sdm_align_crops", "sdm_align_set_source_frames", "sdm_align_crops_tensor",
+    "sdm_align_set_source", "sdm_align_crops", "sdm_align_set_source_frames", "sdm_align_crops_tensor", "sdm_align_crops_tensor_filtered",
     "sdm_train_level_sweep", "sdm_sweep_get_regressor",
     "sdm_set_frames_device", "sdm_debug_download_image",
 ]
@@ -54,6 +54,9 @@ SDM_ALIGN_ORDER_BGR, SDM_ALIGN_ORDER_RGB = 0, 1
 ALIGN_DTYPES = {"uint8": SDM_ALIGN_U8, "float16": SDM_ALIGN_F16, "float32": SDM_ALIGN_F32}
 ALIGN_LAYOUTS = {"nhwc": SDM_ALIGN_NHWC, "nchw": SDM_ALIGN_NCHW}
 ALIGN_ORDERS = {"bgr": SDM_ALIGN_ORDER_BGR, "rgb": SDM_ALIGN_ORDER_RGB}
+# area-averaged sampling of minified rows (include/sdm.h, sdm_align_crops_tensor_filtered)
+SDM_ALIGN_FILTER_BILINEAR, SDM_ALIGN_FILTER_AREA = 0, 1
+ALIGN_FILTERS = {"bilinear": SDM_ALIGN_FILTER_BILINEAR, "area": SDM_ALIGN_FILTER_AREA}
 
 # frames on the device (include/sdm.h, sdm_set_frames_device)
 SDM_FRAME_GRAY, SDM_FRAME_BGR, SDM_FRAME_RGB, SDM_FRAME_BGRA, SDM_FRAME_RGBA, SDM_FRAME_NV12 = range(6)
@@ -74,6 +77,26 @@ class SdmAlignTensor(ctypes.Structure):
 
     _fields_ = [("dtype", ctypes.c_int), ("layout", ctypes.c_int), ("channels", ctypes.c_int), ("order", ctypes.c_int),
                 ("scale", ctypes.c_float * 3), ("bias", ctypes.c_float * 3), ("gray_shift", ctypes.c_int)]
+
+
+class SdmAlignFilter(ctypes.Structure):
+    """``sdm_align_filter``: the sampling of sdm_align_crops_tensor_filtered -- mode, the cap on the sub-samples per axis, the scale gate."""
+
+    _fields_ = [("mode", ctypes.c_int), ("max_samples", ctypes.c_int), ("min_scale", ctypes.c_float)]
+
+
+def align_filter(mode="area", max_samples=16, min_scale=1.0) -> SdmAlignFilter:
+    """The ``sdm_align_filter`` of the named options.  Pure host code.  ``mode``: "area" (a row whose similarity minifies averages
+    S x S bilinear sub-samples per pixel, S the smallest integer with S^2 >= scale^2) | "bilinear" (S = 1 everywhere);
+    ``max_samples``: the cap on S, 1 ... 16; ``min_scale`` (finite, >= 1): rows with scale^2 < min_scale^2 keep S = 1."""
+    import math
+    if not isinstance(mode, str) or mode.lower() not in ALIGN_FILTERS:
+        raise ValueError(f"unknown filter mode {mode!r}: one of {sorted(ALIGN_FILTERS)}")
+    if int(max_samples) != max_samples or not 1 <= int(max_samples) <= 16:
+        raise ValueError("max_samples must be an integer in [1, 16]")
+    if not math.isfinite(min_scale) or min_scale < 1:
+        raise ValueError("min_scale must be finite and >= 1")
+    return SdmAlignFilter(ALIGN_FILTERS[mode.lower()], int(max_samples), float(min_scale))
 
 
 def _three(v, what):
@@ -372,6 +395,8 @@ def lib() -> ctypes.CDLL:
             "sdm_align_set_source_frames": [c_void_p, ctypes.POINTER(SdmFrame), c_void_p, c_int],
             "sdm_align_crops_tensor": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p, c_void_p,
                                        c_void_p],
+            "sdm_align_crops_tensor_filtered": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor),
+                                                ctypes.POINTER(SdmAlignFilter), c_void_p, c_void_p, c_void_p, c_void_p],
             "sdm_train_level_sweep": [c_void_p, c_int, c_int, c_void_p, c_int, c_int, ctypes.c_longlong, c_int, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_int_p],
             "sdm_sweep_get_regressor": [c_void_p, c_int, c_float_p],

@@ -10,53 +10,11 @@
 //                       4-element vectors (dword / 8 bytes / 16 bytes) when the element index is a multiple of 4, one by one otherwise.
 //   align_frame_rows_kernel   sdm_align_crops on a frame list of one pixel size: the fit's records re-pointed at the frames
 //
-// The per-pixel arithmetic is sdm_align_tensor_device.h (also compiled for the host by tests/cpp/align_tensor_host.cpp).  No LDS.
-#include "sdm_kernels.h"
-#include "sdm_align_tensor_device.h"
-
-#include <limits.h>
-
-#pragma clang fp contract(off)
+// The per-pixel arithmetic is sdm_align_tensor_device.h (also compiled for the host by tests/cpp/align_tensor_host.cpp); the element types
+// and the stores are sdm_align_tensor_kernel.h, shared with csrc/sdm_align_area.hip.  No LDS.
+#include "sdm_align_tensor_kernel.h"
 
 namespace {
-
-#define ALIGN_T_BLOCK 256
-
-template <int DT> struct AlignElem;
-template <> struct AlignElem<SDM_ALIGN_U8> { typedef uint8_t T; };
-template <> struct AlignElem<SDM_ALIGN_F16> { typedef _Float16 T; };
-template <> struct AlignElem<SDM_ALIGN_F32> { typedef float T; };
-
-template <int DT>
-__device__ __forceinline__ typename AlignElem<DT>::T make_elem(uint32_t v, float scale, float bias)
-{
-    if constexpr (DT == SDM_ALIGN_U8) return (uint8_t)v;
-    else if constexpr (DT == SDM_ALIGN_F32) return align_element(v, scale, bias);
-    else return (_Float16)align_element(v, scale, bias);          // round to nearest even
-}
-
-// cnt <= CNT consecutive elements from element index e of out (16-byte aligned): whole groups of 4 as one vector store when e is a
-// multiple of 4, the rest element by element
-template <class T, int CNT>
-__device__ __forceinline__ void store_run(void* out, long long e, const T (&vals)[CNT], int cnt)
-{
-    struct alignas(4 * sizeof(T)) Vec { T v[4]; };
-    T* o = (T*)out + e;
-    const bool aligned = (e & 3) == 0;
-#pragma unroll
-    for (int g = 0; g < CNT / 4; ++g) {
-        if (aligned && cnt >= 4 * g + 4) {
-            Vec v;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) v.v[b] = vals[4 * g + b];
-            *(Vec*)(o + 4 * g) = v;
-        } else {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (4 * g + b < cnt) o[4 * g + b] = vals[4 * g + b];
-        }
-    }
-}
 
 template <int DT, int LAYOUT, int CH>
 __global__ __launch_bounds__(ALIGN_T_BLOCK) void align_tensor_kernel(const uint8_t* __restrict__ base, const AlignFace* __restrict__ faces,

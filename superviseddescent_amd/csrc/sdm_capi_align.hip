@@ -1,7 +1,8 @@
 // sdm_capi_align.hip -- C-ABI of the aligned face crops (include/sdm.h, sdm_align_*): the source of the taps in sdm_ctx::align, and a
 // call that fits every current row's similarity and warps its image into a crop (csrc/sdm_align.hip).  Every argument is checked
 // before anything is launched; the landmark state, the images and the tracker's slots are only read.  sdm_align_set_source_frames and
-// sdm_align_crops_tensor (csrc/sdm_align_tensor.hip): a frame list used in place as the source, and the crops as a network's input tensor.
+// sdm_align_crops_tensor (csrc/sdm_align_tensor.hip): a frame list used in place as the source, and the crops as a network's input tensor;
+// sdm_align_crops_tensor_filtered (csrc/sdm_align_area.hip): that tensor with a minifying row's pixels averaged over their footprint.
 #include "sdm_capi_internal.h"
 
 #include <cmath>
@@ -83,19 +84,83 @@ static int align_fit_rows(sdm_ctx* c, const int* lm, const float* tmpl, int K, i
     return SDM_OK;
 }
 
-static int align_fetch_rows(sdm_ctx* c, float* matrices_host, int* flags_host)
+// the records -- and, behind them in the same buffer, the rows' S when `samples_host` is given -- in one copy, one synchronise
+static int align_fetch_rows(sdm_ctx* c, float* matrices_host, int* flags_host, int* samples_host = nullptr)
 {
-    std::vector<AlignFace> faces;
-    if (matrices_host || flags_host) {
-        faces.resize((size_t)c->N);
-        HIP_TRY(hipMemcpyAsync(faces.data(), c->align.faces.p, (size_t)c->N * sizeof(AlignFace), hipMemcpyDeviceToHost, c->stream));
+    const size_t rec = (size_t)c->N * sizeof(AlignFace), bytes = rec + (samples_host ? (size_t)c->N * sizeof(int) : 0);
+    std::vector<unsigned char> host;
+    if (matrices_host || flags_host || samples_host) {
+        host.resize(bytes);
+        HIP_TRY(hipMemcpyAsync(host.data(), c->align.faces.p, bytes, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < (int)faces.size(); ++r) {
+    if (host.empty()) return SDM_OK;
+    const AlignFace* faces = (const AlignFace*)host.data();
+    for (int r = 0; r < c->N; ++r) {
         if (matrices_host) memcpy(matrices_host + (size_t)6 * r, faces[r].m, 6 * sizeof(float));
         if (flags_host) flags_host[r] = faces[r].flags;
     }
+    if (samples_host) memcpy(samples_host, host.data() + rec, (size_t)c->N * sizeof(int));
     return SDM_OK;
+}
+
+// records of N rows with room for N ints behind them
+static size_t align_records_with_samples(int N) { return (size_t)N + ((size_t)N * sizeof(int) + sizeof(AlignFace) - 1) / sizeof(AlignFace); }
+
+// sdm_align_crops_tensor (filter null) and sdm_align_crops_tensor_filtered: the same checks, the same fit, one launch behind it
+static int align_tensor_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h, const sdm_align_tensor* spec,
+                             const sdm_align_filter* filter, bool filtered, void* out_dev, float* matrices_host, int* flags_host,
+                             int* samples_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    int rc;
+    if ((rc = align_check_call(c, lm, tmpl, K, out_w, out_h))) return rc;
+    if (!spec) return fail(SDM_ERR_INVALID, "no tensor specification");
+    if (spec->dtype != SDM_ALIGN_U8 && spec->dtype != SDM_ALIGN_F16 && spec->dtype != SDM_ALIGN_F32) return fail(SDM_ERR_INVALID, "unknown dtype");
+    if (spec->layout != SDM_ALIGN_NHWC && spec->layout != SDM_ALIGN_NCHW) return fail(SDM_ERR_INVALID, "unknown layout");
+    if (spec->order != SDM_ALIGN_ORDER_BGR && spec->order != SDM_ALIGN_ORDER_RGB) return fail(SDM_ERR_INVALID, "unknown channel order");
+    if (spec->channels != 1 && spec->channels != 3) return fail(SDM_ERR_INVALID, "channels must be 1 or 3");
+    if (spec->gray_shift != 14 && spec->gray_shift != 15) return fail(SDM_ERR_INVALID, "gray_shift must be 14 (OpenCV 2.4 - 3.x) or 15");
+    if (spec->dtype != SDM_ALIGN_U8)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(spec->scale[k]) || !std::isfinite(spec->bias[k])) return fail(SDM_ERR_INVALID, "a scale or bias is not finite");
+    if (filtered) {
+        if (!filter) return fail(SDM_ERR_INVALID, "no filter");
+        if (filter->mode != SDM_ALIGN_FILTER_BILINEAR && filter->mode != SDM_ALIGN_FILTER_AREA) return fail(SDM_ERR_INVALID, "unknown filter mode");
+        if (filter->max_samples < 1 || filter->max_samples > 16) return fail(SDM_ERR_INVALID, "max_samples must be in [1, 16]");
+        if (!std::isfinite(filter->min_scale) || filter->min_scale < 1.0f) return fail(SDM_ERR_INVALID, "min_scale must be finite and >= 1");
+    }
+    if (!out_dev) return fail(SDM_ERR_INVALID, "no output");
+    if ((uintptr_t)out_dev % 16 != 0) return fail(SDM_ERR_INVALID, "the output must be 16-byte aligned");
+    if ((rc = align_check_rows(c))) return rc;
+    const int N = c->N;
+    sdm_ctx::Align& a = c->align;
+    const bool external = a.base != nullptr, list = !a.fr.empty();
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(filtered ? align_records_with_samples(N) : (size_t)N))) return rc;
+    if ((rc = align_fit_rows(c, lm, tmpl, K, out_w, out_h))) return rc;
+    AlignTensorDev t{};
+    for (int k = 0; k < 3; ++k) { t.scale[k] = spec->scale[k]; t.bias[k] = spec->bias[k]; }
+    t.order = spec->order; t.gray_shift = spec->gray_shift;
+    if (spec->gray_shift == 14) { t.wb = 1868; t.wg = 9617; t.wr = 4899; }        // sdm_upload_images_bgr_u8's two weight sets
+    else { t.wb = 3735; t.wg = 19235; t.wr = 9798; }
+    const int stack_format = !external ? SDM_FRAME_GRAY : a.C == 1 ? SDM_FRAME_GRAY : a.C == 3 ? SDM_FRAME_BGR : SDM_FRAME_BGRA;
+    const uint8_t* base = external ? a.base : c->img_base;
+    const AlignFrameDev* frames = list ? a.fr_dev.p : nullptr;
+    const int* img_idx = c->idx_identity ? nullptr : c->img_idx.p;
+    if (!filtered) {
+        sdm_launch_align_tensor(base, a.faces.p, frames, img_idx, stack_format, N, out_w, out_h, spec->dtype, spec->layout, spec->channels, t,
+                                out_dev, c->stream);
+        HIP_TRY(hipGetLastError());
+        return align_fetch_rows(c, matrices_host, flags_host);
+    }
+    AlignAreaDev area{};
+    area.mode = filter->mode; area.max_samples = filter->max_samples;
+    area.min2 = filter->min_scale * filter->min_scale;                              // (float32, rounded once; may be inf: then every S is 1)
+    sdm_launch_align_area(base, a.faces.p, frames, img_idx, stack_format, N, out_w, out_h, spec->dtype, spec->layout, spec->channels, t, area,
+                          (int*)(a.faces.p + N), out_dev, c->stream);
+    HIP_TRY(hipGetLastError());
+    return align_fetch_rows(c, matrices_host, flags_host, samples_host);
 }
 
 extern "C" {
@@ -205,37 +270,13 @@ int sdm_align_crops(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out
 int sdm_align_crops_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h, const sdm_align_tensor* spec,
                            void* out_dev, float* matrices_host, int* flags_host)
 {
-    if (!c) return fail(SDM_ERR_INVALID, "null context");
-    int rc;
-    if ((rc = align_check_call(c, lm, tmpl, K, out_w, out_h))) return rc;
-    if (!spec) return fail(SDM_ERR_INVALID, "no tensor specification");
-    if (spec->dtype != SDM_ALIGN_U8 && spec->dtype != SDM_ALIGN_F16 && spec->dtype != SDM_ALIGN_F32) return fail(SDM_ERR_INVALID, "unknown dtype");
-    if (spec->layout != SDM_ALIGN_NHWC && spec->layout != SDM_ALIGN_NCHW) return fail(SDM_ERR_INVALID, "unknown layout");
-    if (spec->order != SDM_ALIGN_ORDER_BGR && spec->order != SDM_ALIGN_ORDER_RGB) return fail(SDM_ERR_INVALID, "unknown channel order");
-    if (spec->channels != 1 && spec->channels != 3) return fail(SDM_ERR_INVALID, "channels must be 1 or 3");
-    if (spec->gray_shift != 14 && spec->gray_shift != 15) return fail(SDM_ERR_INVALID, "gray_shift must be 14 (OpenCV 2.4 - 3.x) or 15");
-    if (spec->dtype != SDM_ALIGN_U8)
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(spec->scale[k]) || !std::isfinite(spec->bias[k])) return fail(SDM_ERR_INVALID, "a scale or bias is not finite");
-    if (!out_dev) return fail(SDM_ERR_INVALID, "no output");
-    if ((uintptr_t)out_dev % 16 != 0) return fail(SDM_ERR_INVALID, "the output must be 16-byte aligned");
-    if ((rc = align_check_rows(c))) return rc;
-    const int N = c->N;
-    sdm_ctx::Align& a = c->align;
-    const bool external = a.base != nullptr, list = !a.fr.empty();
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure((size_t)N))) return rc;
-    if ((rc = align_fit_rows(c, lm, tmpl, K, out_w, out_h))) return rc;
-    AlignTensorDev t{};
-    for (int k = 0; k < 3; ++k) { t.scale[k] = spec->scale[k]; t.bias[k] = spec->bias[k]; }
-    t.order = spec->order; t.gray_shift = spec->gray_shift;
-    if (spec->gray_shift == 14) { t.wb = 1868; t.wg = 9617; t.wr = 4899; }        // sdm_upload_images_bgr_u8's two weight sets
-    else { t.wb = 3735; t.wg = 19235; t.wr = 9798; }
-    const int stack_format = !external ? SDM_FRAME_GRAY : a.C == 1 ? SDM_FRAME_GRAY : a.C == 3 ? SDM_FRAME_BGR : SDM_FRAME_BGRA;
-    sdm_launch_align_tensor(external ? a.base : c->img_base, a.faces.p, list ? a.fr_dev.p : nullptr, c->idx_identity ? nullptr : c->img_idx.p,
-                            stack_format, N, out_w, out_h, spec->dtype, spec->layout, spec->channels, t, out_dev, c->stream);
-    HIP_TRY(hipGetLastError());
-    return align_fetch_rows(c, matrices_host, flags_host);
+    return align_tensor_call(c, lm, tmpl, K, out_w, out_h, spec, nullptr, false, out_dev, matrices_host, flags_host, nullptr);
+}
+
+int sdm_align_crops_tensor_filtered(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h, const sdm_align_tensor* spec,
+                                    const sdm_align_filter* filter, void* out_dev, float* matrices_host, int* flags_host, int* samples_host)
+{
+    return align_tensor_call(c, lm, tmpl, K, out_w, out_h, spec, filter, true, out_dev, matrices_host, flags_host, samples_host);
 }
 
 }  // extern "C"

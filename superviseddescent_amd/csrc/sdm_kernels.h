@@ -415,3 +415,14 @@ void sdm_launch_align_tensor(const uint8_t* base, const AlignFace* faces, const 
                              hipStream_t s);
 // the fit's records re-pointed at a frame list of one pixel size, for align_warp_kernel: off = frames[im].p0 - base, stride = the frame's
 void sdm_launch_align_frame_rows(AlignFace* faces, const AlignFrameDev* frames, const int* img_idx, const uint8_t* base, int N, hipStream_t s);
+
+// ---- area-averaged crop tensors (sdm_align_area.hip) ----
+// the filter of sdm_align_crops_tensor_filtered as the kernel reads it: min2 = min_scale * min_scale in float32
+struct AlignAreaDev {
+    int mode, max_samples;     // SDM_ALIGN_FILTER_*; the cap on S, 1 ... 16
+    float min2;
+};
+// sdm_launch_align_tensor with every pixel of row n averaged over S_n x S_n sub-samples; S_n, from the row's M, goes to samples[n] (N ints)
+void sdm_launch_align_area(const uint8_t* base, const AlignFace* faces, const AlignFrameDev* frames, const int* img_idx, int src_format,
+                           int N, int out_w, int out_h, int dtype, int layout, int channels, const AlignTensorDev& spec,
+                           const AlignAreaDev& area, int* samples, void* out, hipStream_t s);

@@ -13,7 +13,8 @@ Class and method names follow the reference so that the parity tests read like i
 ``ModelProjection``                            examples/pose_estimation.cpp:187-240 (head pose, csrc/sdm_pose.hip)
 ``detection_model.tracker`` / ``Tracker``       apps/rcr/rcr-track.cpp:133-177 (multi-stream tracking, csrc/sdm_track.hip)
 ``detection_model.aligned_crops``              (extension) aligned face crops of the current rows, csrc/sdm_align.hip
-``detection_model.aligned_crops_tensor``       (extension) the crops as a network's input tensor, csrc/sdm_align_tensor.hip
+``detection_model.aligned_crops_tensor``       (extension) the crops as a network's input tensor, csrc/sdm_align_tensor.hip,
+                                               csrc/sdm_align_area.hip (``filter="area"``: minified faces averaged per footprint)
 =============================================  =====================================================
 
 Everything numeric happens on the MI355X: HOG extraction, regressor apply, Gram/RHS build and the
@@ -687,12 +688,19 @@ class Context:
         self.align_channels = C if C else 1
         return C if C else None
 
-    def align_crops_tensor(self, landmark_index, template: np.ndarray, width: int, height: int, spec=None, out=None, **options):
+    def align_crops_tensor(self, landmark_index, template: np.ndarray, width: int, height: int, spec=None, out=None, filter=None,
+                           **options):
         """Crops of the N current rows as a network's input tensor (include/sdm.h, sdm_align_crops_tensor) from the source set by
         ``align_set_source_frames`` / ``align_set_source`` (default: the context's images).  ``spec``: an ``_lib.SdmAlignTensor``, or
         the ``options`` of ``_lib.align_tensor_spec`` (dtype, layout, channels, order, scale, bias, mean, std, gray_shift).  ``out``:
         a contiguous device tensor of the requested dtype and shape, written in place; default: a new one.  Returns (tensor
-        N x C x H x W or N x H x W x C, matrices N x 2 x 3 float32, flags N int32)."""
+        N x C x H x W or N x H x W x C, matrices N x 2 x 3 float32, flags N int32).  ``filter``: None (plain bilinear), or "area" / an
+        ``_lib.SdmAlignFilter`` (``_lib.align_filter``) for sdm_align_crops_tensor_filtered -- rows whose similarity minifies average
+        S x S sub-samples per pixel -- which returns (tensor, matrices, flags, samples N int32: S of every row)."""
+        if isinstance(filter, str):
+            filter = _lib.align_filter(filter)
+        elif filter is not None and not isinstance(filter, _lib.SdmAlignFilter):
+            raise ValueError('filter must be None, "area", "bilinear" or an SdmAlignFilter')
         if spec is None:
             spec = _lib.align_tensor_spec(**options)
         elif options:
@@ -712,9 +720,15 @@ class Context:
         mats = np.empty((n, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
         torch.cuda.current_stream(out.device).synchronize()
-        check(self._lib.sdm_align_crops_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height), ctypes.byref(spec),
-                                               ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
-        return out, mats, flags
+        if filter is None:
+            check(self._lib.sdm_align_crops_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height), ctypes.byref(spec),
+                                                   ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
+            return out, mats, flags
+        samples = np.empty(n, np.int32)
+        check(self._lib.sdm_align_crops_tensor_filtered(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height),
+                                                        ctypes.byref(spec), ctypes.byref(filter), ctypes.c_void_p(out.data_ptr()),
+                                                        mats.ctypes.data, flags.ctypes.data, samples.ctypes.data))
+        return out, mats, flags, samples
 
     # -- misc ------------------------------------------------------------------------------------------
     def synchronize(self):
@@ -1387,7 +1401,7 @@ class detection_model:
 
     def aligned_crops_tensor(self, size, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
                              margin: float = 0.2, frames=None, formats=None, chroma=None, dtype="float16", layout="nchw", channels=3,
-                             order="rgb", scale=None, bias=None, mean=None, std=None, gray_shift=14, out=None):
+                             order="rgb", scale=None, bias=None, mean=None, std=None, gray_shift=14, out=None, filter=None):
         """Aligned face crops of the current rows as a network's input tensor, in one launch from the frames where they lie on the
         device (include/sdm.h, sdm_align_crops_tensor).  ``size``, ``landmark_ids``, ``template``, ``margin``: as for
         :meth:`aligned_crops`.  ``frames``: what ``detect_batch`` and ``Tracker.step`` accept as device frames -- uint8 tensors of any
@@ -1399,7 +1413,10 @@ class detection_model:
         output channel c, the product and the sum each rounded to float32, then once to float16.  ``scale`` / ``bias``: a scalar or 3
         values, passed as float32.  ``mean`` / ``std`` (0-255 units) are sugar for ``scale = float32(1 / std)``,
         ``bias = float32(-mean / std)``; giving both pairs is an error.  ``out``: a contiguous device tensor of that dtype and shape.
-        Returns (tensor, matrices N x 2 x 3 crop -> source, flags N: SDM_ALIGN_*).  No pointer to the frames stays behind."""
+        Returns (tensor, matrices N x 2 x 3 crop -> source, flags N: SDM_ALIGN_*).  No pointer to the frames stays behind.
+        ``filter``: None (plain bilinear) | "area" | an ``SdmAlignFilter`` (``align_filter``): with a filter, a face that is larger in
+        the frame than in the crop is averaged over every pixel's footprint (sdm_align_crops_tensor_filtered) and the return value is
+        (tensor, matrices, flags, samples N: the sub-samples per axis of every row)."""
         c = self.optimised_model.ctx
         if not getattr(c, "N", 0):
             raise RuntimeError("run detect_batch or Tracker.step first")
@@ -1414,7 +1431,7 @@ class detection_model:
             template = alignment_template(self.mean, idx, width, height, margin)
         c.align_set_source_frames(frames, formats, chroma)
         try:
-            return c.align_crops_tensor(idx, template, width, height, spec=spec, out=out)
+            return c.align_crops_tensor(idx, template, width, height, spec=spec, out=out, filter=filter)
         finally:
             if frames is not None:
                 c.align_set_source_frames(None)                           # (no pointer to the caller's frames stays behind)

@@ -146,18 +146,28 @@ struct TensorSpec {
     size_t element_size() const { return dtype == SDM_ALIGN_U8 ? 1 : dtype == SDM_ALIGN_F16 ? 2 : 4; }
 };
 
+/** The sampling of sdm_align_crops_tensor_filtered (sdm_align_filter of include/sdm.h): with SDM_ALIGN_FILTER_AREA a row whose similarity
+ *  minifies averages S x S bilinear sub-samples per pixel, S the smallest integer with S^2 >= scale^2, at most max_samples (1 ... 16);
+ *  rows with scale^2 < min_scale^2 (min_scale finite, >= 1) keep S = 1, the bits of the unfiltered call. */
+struct AlignFilter {
+    int mode = SDM_ALIGN_FILTER_AREA, max_samples = 16;
+    float min_scale = 1.0f;
+};
+
 struct aligned_tensor_result {
     cv::Mat matrices;              // rows x 6 CV_32FC1: the crop -> source map of every row (NaN for a degenerate row)
     std::vector<int> flags;        // SDM_ALIGN_DEGENERATE / SDM_ALIGN_PARTIAL bits
+    std::vector<int> samples;      // the overloads taking an AlignFilter: S of every row; empty otherwise
 };
 
 namespace detail {
 
 // the n current rows of the handle `c` as a tensor in device memory, cut from `frames` in place (`chroma`: empty, or per frame the UV
-// plane of an NV12 frame, nullptr = behind its Y plane) or -- no frames -- from the handle's own images
+// plane of an NV12 frame, nullptr = behind its Y plane) or -- no frames -- from the handle's own images; `filter`: nullptr, or the
+// sampling of sdm_align_crops_tensor_filtered
 inline aligned_tensor_result align_tensor_current_rows(sdm_ctx* c, int n, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
                                                        int height, const std::vector<DeviceFrame>& frames, const std::vector<const void*>& chroma,
-                                                       const TensorSpec& spec, void* out_dev)
+                                                       const TensorSpec& spec, void* out_dev, const AlignFilter* filter = nullptr)
 {
     using superviseddescent::hip::check;
     if (tmpl.rows != (int)landmark_index.size() || tmpl.cols != 2) throw std::runtime_error("aligned_crops_tensor: one template point (x, y) per landmark");
@@ -173,10 +183,18 @@ inline aligned_tensor_result align_tensor_current_rows(sdm_ctx* c, int n, const 
     aligned_tensor_result res;
     res.matrices = cv::Mat(n, 6, CV_32FC1);
     res.flags.resize((size_t)n);
-    const int rc = sdm_align_crops_tensor(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s, out_dev,
-                                          res.matrices.ptr<float>(0), res.flags.data());
+    int rc;
+    if (filter) {
+        const sdm_align_filter f{filter->mode, filter->max_samples, filter->min_scale};
+        res.samples.resize((size_t)n);
+        rc = sdm_align_crops_tensor_filtered(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s, &f, out_dev,
+                                             res.matrices.ptr<float>(0), res.flags.data(), res.samples.data());
+    } else {
+        rc = sdm_align_crops_tensor(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s, out_dev,
+                                    res.matrices.ptr<float>(0), res.flags.data());
+    }
     if (!frames.empty()) sdm_align_set_source_frames(c, nullptr, nullptr, 0);     // (no pointer to the caller's frames stays behind)
-    check(rc, "sdm_align_crops_tensor");
+    check(rc, filter ? "sdm_align_crops_tensor_filtered" : "sdm_align_crops_tensor");
     return res;
 }
 
@@ -193,13 +211,24 @@ inline aligned_tensor_result aligned_crops_tensor(tracker& tr, const std::vector
     return detail::align_tensor_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, frames, chroma, spec, out_dev);
 }
 
+/** The same with the sampling of `filter`: faces that are larger in the frame than in the crop are averaged over every pixel's footprint;
+ *  the result's `samples` holds S of every stream. */
+inline aligned_tensor_result aligned_crops_tensor(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                                  const TensorSpec& spec, const AlignFilter& filter, void* out_dev,
+                                                  const std::vector<DeviceFrame>& frames = {}, const std::vector<const void*>& chroma = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("aligned_crops_tensor: step the tracker first");
+    return detail::align_tensor_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, frames, chroma, spec, out_dev,
+                                             &filter);
+}
+
 /** The same for landmark rows on device frames, e.g. the result of detection_model::detect_batch(frames, boxes, image_index): row i is
  *  cut from frames[image_index[i]] (default: frames[i]).  As the cv::Mat overload of aligned_crops, this one works on a handle of its
  *  own: the frames become its image set (colour converted to gray once, which the crops do not read) and the rows are uploaded. */
 inline aligned_tensor_result aligned_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
                                                   const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl,
                                                   int width, int height, const TensorSpec& spec, void* out_dev,
-                                                  const std::vector<const void*>& chroma = {})
+                                                  const std::vector<const void*>& chroma = {}, const AlignFilter* filter = nullptr)
 {
     using superviseddescent::hip::check;
     superviseddescent::hip::Handle h(superviseddescent::hip::device());
@@ -211,7 +240,16 @@ inline aligned_tensor_result aligned_crops_tensor(detection_model& model, const 
     if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
     else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
     check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
-    return detail::align_tensor_current_rows(c, x.rows, landmark_index, tmpl, width, height, frames, chroma, spec, out_dev);
+    return detail::align_tensor_current_rows(c, x.rows, landmark_index, tmpl, width, height, frames, chroma, spec, out_dev, filter);
+}
+
+/** The same with the sampling of `filter` (the result's `samples`: S of every row). */
+inline aligned_tensor_result aligned_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                                  const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl,
+                                                  int width, int height, const TensorSpec& spec, const AlignFilter& filter, void* out_dev,
+                                                  const std::vector<const void*>& chroma = {})
+{
+    return aligned_crops_tensor(model, frames, rows, image_index, landmark_index, tmpl, width, height, spec, out_dev, chroma, &filter);
 }
 
 }  // namespace rcr
