@@ -389,6 +389,12 @@ int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_l
  * (packed plan, SDM_HOG_COLUMNS, descriptor kernel available), that launch is an instance with the one-load row loop, option
  * hog_two_load}.  SDM_ERR_INVALID when the level has no packed plan. */
 int sdm_debug_hog_taps(sdm_ctx* ctx, int level, int* table, int* info3);
+/* Tests: the level's pair-loop table as the device built it from the same taps (csrc/sdm_hog_packed.hip, pair_taps_table_kernel):
+ * table[128 half-widths][64][4] ints = {row d takes its lower source row from the pair's spare (all ones) or from row d - 1's upper row
+ * (zero), source row of the spare of pixel rows (2d + 1, 2d + 2) or -1 where the pair needs none, half-width is pair eligible, orphan
+ * rows of the patch}.  info2 = {the level's raw-cells launch is an instance with the pair loop, option hog_two_load}.
+ * SDM_ERR_INVALID when the level has no packed plan. */
+int sdm_debug_hog_pair_taps(sdm_ctx* ctx, int level, int* table, int* info2);
 /* Round 4, A/B and tests: which launches the packed default mode uses.  fused != 0 (default; sdm_debug_set_option "detect_unfused" turns it
  * off): sdm_detect_batch runs  pixel kernel -> raw cell histograms -> descriptors x regressor slices on the 16-bit matrix cores
  * (csrc/sdm_desc.hip) -> landmark update, and never writes the N x F feature matrix (LinearRegressor::predict,

@@ -80,7 +80,7 @@ void sdm_destroy(sdm_ctx* c)
     c->sweep.release();
     c->frames.release();
     for (auto& r : c->Rt) r.release();
-    for (auto& q : c->plans) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); }
+    for (auto& q : c->plans) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); q.pair_taps.release(); }
     if (c->own_stream) e = hipStreamDestroy(c->stream);
     delete c;
 }
@@ -205,7 +205,7 @@ int sdm_set_model_geometry(sdm_ctx* c, int L, const int* re, int nre, const int*
     // early returns leaked them), the context's previous tables after the swap at the commit
     struct PlanGuard {
         std::vector<sdm_ctx::Plan>& v;
-        ~PlanGuard() { for (auto& q : v) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); } }
+        ~PlanGuard() { for (auto& q : v) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); q.pair_taps.release(); } }
     } plan_guard{n_plans};
     for (int l = 0; l < n_levels; ++l) {
         HogPlanHost hp;
@@ -218,6 +218,8 @@ int sdm_set_model_geometry(sdm_ctx* c, int L, const int* re, int nre, const int*
         HIP_TRY(hipMemcpyAsync(pl.cut.p, hp.cut.data(), hp.cut.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
         if ((rcp = pl.taps.ensure((size_t)SDM_SCALE_TAB * 64 * 8))) return rcp;
         sdm_launch_taps_table(n_levels_dev[l], pl.taps.p, c->stream);
+        if ((rcp = pl.pair_taps.ensure((size_t)SDM_SCALE_TAB * 64 * 4))) return rcp;
+        sdm_launch_pair_taps_table(n_levels_dev[l], pl.pair_taps.p, c->stream);
         HIP_TRY(hipMemcpyAsync(pl.lane_tab.p, hp.lane_tab.data(), hp.lane_tab.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(pl.wb.p, hp.wb.data(), hp.wb.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(pl.wb16.p, hp.wb16.data(), hp.wb16.size() * sizeof(unsigned short), hipMemcpyHostToDevice, c->stream));
@@ -225,7 +227,7 @@ int sdm_set_model_geometry(sdm_ctx* c, int L, const int* re, int nre, const int*
         HIP_TRY(hipStreamSynchronize(c->stream));      // (the host vectors go out of scope)
         pl.dev.G = hp.G; pl.dev.P = hp.P; pl.dev.n_main = hp.n_main; pl.dev.Gt = hp.Gt; pl.dev.Pt = hp.Pt; pl.dev.hist_slots = hp.hist_slots;
         pl.dev.raw_sqrt = n_raw_sqrt[l];
-        pl.dev.lane_tab = pl.lane_tab.p; pl.dev.wb = pl.wb.p; pl.dev.wb16 = pl.wb16.p; pl.dev.pass_info = pl.pass_info.p; pl.dev.taps = pl.taps.p;
+        pl.dev.lane_tab = pl.lane_tab.p; pl.dev.wb = pl.wb.p; pl.dev.wb16 = pl.wb16.p; pl.dev.pass_info = pl.pass_info.p; pl.dev.taps = pl.taps.p; pl.dev.pair_taps = pl.pair_taps.p;
         pl.ok = true;
     }
     // ---- commit ----

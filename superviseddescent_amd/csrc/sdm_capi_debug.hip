@@ -154,6 +154,18 @@ int sdm_debug_hog_taps(sdm_ctx* c, int level, int* table, int* info3)
     return SDM_OK;
 }
 
+int sdm_debug_hog_pair_taps(sdm_ctx* c, int level, int* table, int* info2)
+{
+    if (!c || level < 0 || level >= (int)c->levels.size() || !table || !info2) return fail(SDM_ERR_INVALID, "bad arguments");
+    if (!c->plans[level].ok || !c->plans[level].pair_taps.p) return fail(SDM_ERR_INVALID, "no packed plan for this level");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipMemcpyAsync(table, c->plans[level].pair_taps.p, (size_t)SDM_SCALE_TAB * 64 * 4 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    info2[0] = sdm_hog_cells_pair_carry(c->levels[level], c->plans[level].dev) ? 1 : 0;
+    info2[1] = c->hog_two_load ? 1 : 0;
+    return SDM_OK;
+}
+
 int sdm_debug_set_detect_path(sdm_ctx* c, int fused, int split_store)
 {
     if (!c) return fail(SDM_ERR_INVALID, "null context");

@@ -105,7 +105,7 @@ struct sdm_ctx {
     std::vector<int> fast_kernel;   // per level: fused S<=64 kernel usable
     std::vector<int> fast_bins;     // per level: un-normalised arg-max verified on all 511x511 gradients
     // per level: lane-packed launch plan (sdm_hog_packed.hip::hog_packed_kernel), device tables owned here
-    struct Plan { bool ok = false; HogPlanDev dev{}; DevBuf<unsigned> lane_tab; DevBuf<float> wb; DevBuf<unsigned short> wb16; DevBuf<int> pass_info; DevBuf<int> cut; DevBuf<int> taps; };
+    struct Plan { bool ok = false; HogPlanDev dev{}; DevBuf<unsigned> lane_tab; DevBuf<float> wb; DevBuf<unsigned short> wb16; DevBuf<int> pass_info; DevBuf<int> cut; DevBuf<int> taps; DevBuf<int> pair_taps; };
     std::vector<Plan> plans;
     // round 4: the packed launch stops at the raw cell histograms (cells[N][L][2 parts][C*C][2O]); sdm_desc.hip normalises them into the
     // feature rows, or -- sdm_detect_batch -- multiplies the descriptors by the regressor without writing the feature matrix

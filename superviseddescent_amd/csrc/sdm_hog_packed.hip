@@ -1,6 +1,6 @@
 // sdm_hog_packed.hip -- the lane-packed HOG kernel for gfx950 (hog_packed_kernel: the default pixel kernel of the detect and
-// training paths), its normalisation (hog_finish_direct), the per-level table of resize taps (taps_table_kernel) and their
-// launchers sdm_launch_hog_packed / sdm_launch_hog_cells / sdm_launch_taps_table.  The launch plan it walks is built on the
+// training paths), its normalisation (hog_finish_direct), the per-level tables of resize taps (taps_table_kernel, pair_taps_table_kernel) and their
+// launchers sdm_launch_hog_packed / sdm_launch_hog_cells / sdm_launch_taps_table / sdm_launch_pair_taps_table.  The launch plan it walks is built on the
 // host by sdm_hog_plan.hip; the device helpers it shares with the one-patch-per-wave family (sdm_hog_fast.hip) are
 // sdm_hog_device.h.
 //
@@ -34,6 +34,19 @@
 // (profiles/hog_row_carry.txt): cells 10 / 8 / 6 run 12 / 13 / 8 % faster with it at the shipped levels.  Cell 11 with it: 331.1 us
 // per launch against 331.1 without (at relative patch size 1.0, S = 55, 1 % of the faces have an enlarged patch) -- left out.
 __host__ __device__ constexpr bool hp_row_carry(int cell) { return cell == 10 || cell == 8 || cell == 6; }
+// Pair carry (the CELLS instance of cell 11, where the patch is REDUCED by less than 1.5: S < 2h < 1.5 S): every pixel row d >= 1 is
+// a SHIFT row (its lower source row is row d - 1's upper one) or an ORPHAN row (its lower source row is the one after row d - 1's
+// upper one: both of its rows are new), and no pair of pixel rows (2p + 1, 2p + 2) holds two orphans.  A third row loop then loads
+// THREE source rows per pair of pixel rows instead of four: the upper row of both, and one spare that serves whichever row of the pair
+// is the orphan (its address is put out of the buffer's range where the pair has none: nothing is fetched).  The lower row of every
+// pixel row is one bit select between the previous upper row and the spare.  Eligibility, the per-row "take the spare" masks and the
+// per-pair spare rows come from pair_taps_table_kernel.  Per cell size, by measurement (profiles/hog_pair_carry.txt).
+#ifndef HP_PAIR_CARRY_11
+#define HP_PAIR_CARRY_11 1
+#endif
+__host__ __device__ constexpr bool hp_pair_carry(int cell) { return HP_PAIR_CARRY_11 && cell == 11; }
+// spare offsets of the pair loop: one int per pair of pixel rows (2p + 1, 2p + 2), per wave, behind the row table
+__host__ __device__ constexpr int hp_pair_slots(int cell, int C, bool cells, bool raw) { return cells && raw && hp_pair_carry(cell) ? (C * cell - 1) / 2 : 0; }
 // (The ablation switches of rounds 3-6 -- HP_ABL = 1 ... 15: no folds, no read-modify-write, no image loads, conflict-free operand
 //  reads, ... -- are scripts/experiments/hog_packed_ablations.patch; scripts/r6_hog_lds_variants.sh applies it to a copy and builds
 //  the variants.  Their measurements: profiles/r04_hog_ablations.txt, profiles/r06_hog_lds.txt.)
@@ -62,23 +75,24 @@ __host__ __device__ inline size_t packed_scratch_bytes(int C, int O = 4)
 {
     return al16((size_t)C * C * 4) + al16((size_t)(C + 1) * (C + 1) * 8) + al16((size_t)4 * O * C * C * 8);
 }
-// per wave: [ column rows | per-row table of the vertical taps, S + 2 entries of 16 bytes | hist_slots histograms ]
+// per wave: [ column rows | per-row table of the vertical taps, S + 2 entries of 16 bytes | spare offsets of the pair loop | hist_slots histograms ]
 // (the finish scratch overlays the column rows, which are all zero between two passes)
 // (the generic instance issues its image loads two rows ahead without looking: entries S and S + 1 repeat the last row; the
 //  instances specialised on the cell size know at compile time where the ROI ends and keep S entries)
 __host__ __device__ inline size_t packed_rowtab_bytes(int S, bool spec = false) { return (size_t)(S + (spec ? 0 : 2)) * 16; }
-__host__ __device__ inline size_t packed_lds_bytes(int C, int O, int S, int hist_slots, bool spec = false)
+__host__ __device__ inline size_t packed_lds_bytes(int C, int O, int S, int hist_slots, bool spec = false, int pair_slots = 0)
 {
-    return al16(HP_ROWS_BYTES(O)) + packed_rowtab_bytes(S, spec) + hist_slots * al16(HP_HIST_BYTES(O, C * C));
+    return al16(HP_ROWS_BYTES(O)) + packed_rowtab_bytes(S, spec) + al16((size_t)pair_slots * 4) + hist_slots * al16(HP_HIST_BYTES(O, C * C));
 }
 // specialised instances: the band-slot weights {ws0, ws1} of every pixel row (level constants, hog.c:697-704) in ONE table per
 // workgroup behind the waves' regions, read per row with a broadcast 8-byte LDS read straight into the register pair the
 // packed multiply-add takes (scalar loads of them cannot stay in SGPRs over an unrolled ROI: the compiler spilled them to
 // vector lanes and paid two v_readlane per row)
-__host__ __device__ inline size_t packed_wstab_bytes(int S) { return al16((size_t)S * 8); }
-__host__ __device__ inline size_t packed_wg_lds_bytes(int C, int O, int S, int hist_slots, bool spec)
+// (rows 0 and S - 1 have no gradient: the table holds rows 1 .. S - 2 -- at S = 50 the 16 bytes that let eight workgroups share a CU's LDS)
+__host__ __device__ inline size_t packed_wstab_bytes(int S) { return al16((size_t)(S - 2) * 8); }
+__host__ __device__ inline size_t packed_wg_lds_bytes(int C, int O, int S, int hist_slots, bool spec, int pair_slots = 0)
 {
-    return packed_lds_bytes(C, O, S, hist_slots, spec) * HP_WAVES + (spec ? packed_wstab_bytes(S) : 0);
+    return packed_lds_bytes(C, O, S, hist_slots, spec, pair_slots) * HP_WAVES + (spec ? packed_wstab_bytes(S) : 0);
 }
 
 // arithmetic type of the packed kernel's normalisation (hog.c:930-1052 computes the block factors and the clamped products in
@@ -218,11 +232,15 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     const int nslots = CELLS ? 0 : plan.hist_slots;                                   // 2, or 3 for ROIs under 22 columns; none when the cells go to HBM
     constexpr bool SPEC = CELL > 0;
     constexpr bool ROTB = RAW && TO == 4;          // octant code on rotated coordinates (bin_rot4_row); the folds read rows HP_ROW_OF_BIN(bin)
-    unsigned char* lds = smem + (size_t)wave * packed_lds_bytes(C, O, S, nslots, SPEC);
+    constexpr int NPAIR = hp_pair_slots(CELL, TC, CELLS, RAW);      // > 0: the instance has the pair loop
+    constexpr bool PAIR = NPAIR > 0;
+    static_assert(!PAIR || (TC * CELL) % 2 == 1, "pair loop: rows 1 .. S - 1 in pairs");
+    unsigned char* lds = smem + (size_t)wave * packed_lds_bytes(C, O, S, nslots, SPEC, NPAIR);
     float* colrows = (float*)lds;                                                    // [2O][ST][2 band slots]
     i32x4* rowtab = (i32x4*)(lds + al16(HP_ROWS_BYTES(O)));                          // [S (+ 2)] {row offset 0, row offset 1, weight 0 << 12, weight 1 << 12}
-    float* hist = (float*)(lds + al16(HP_ROWS_BYTES(O)) + packed_rowtab_bytes(S, SPEC));   // [nslots][2O][CC]
-    f32x2* wstab = (f32x2*)(smem + (size_t)HP_WAVES * packed_lds_bytes(C, O, S, nslots, SPEC));      // [S] per workgroup (SPEC)
+    int* sptab = (int*)(lds + al16(HP_ROWS_BYTES(O)) + packed_rowtab_bytes(S, SPEC));      // [NPAIR] byte offset of the pair's spare source row (PAIR)
+    float* hist = (float*)(lds + al16(HP_ROWS_BYTES(O)) + packed_rowtab_bytes(S, SPEC) + al16((size_t)NPAIR * 4));   // [nslots][2O][CC]
+    f32x2* wstab = (f32x2*)(smem + (size_t)HP_WAVES * packed_lds_bytes(C, O, S, nslots, SPEC, NPAIR));      // [S - 2] per workgroup (SPEC): rows 1 .. S - 2
     constexpr int HSTR = (2 * O * CC * 4 + 15) / 16 * 4;      // floats per histogram slot (16-byte multiple)
     unsigned char* scratch = lds;      // the finish scratch overlays the column rows, which are all zero between two passes
     auto hist_slot = [&](int patch_slot) { return nslots == 2 ? (patch_slot & 1) : patch_slot % 3; };
@@ -246,7 +264,9 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     int tab_s, tab_w;                 // unclamped source index floor((d + 0.5) scale - 0.5), 11-bit weights c0 | c1 << 16
     constexpr bool CARRY = CELLS && RAW && CELL > 0 && hp_row_carry(CELL);      // the instance has the one-load row loop
     int carry_mask = 0;               // row d takes its lower source row from row d - 1's upper one (all ones) or lower one (zero)
-    bool carry = false;               // this wave's half-width is one-load eligible (wave-uniform)
+                                      // (PAIR: from the pair's spare (all ones) or row d - 1's upper one (zero))
+    bool carry = false;               // this wave's half-width is one-load (PAIR: pair) eligible (wave-uniform)
+    int spare_off = 0;                // PAIR: lane p holds the byte offset of the spare row of pixel rows (2p + 1, 2p + 2)
     i32x4 row_ent;                    // vertical taps of row d as the row loop wants them: byte offsets of the two source rows
                                       // RELATIVE to the patch origin (rows clipped to the patch), the two weights << 12
     if (CELLS && plan.taps && h < SDM_SCALE_TAB) {      // the level's table of taps by half-width (taps_table_kernel): two 16-byte loads
@@ -255,6 +275,13 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         tab_s = e0.x; tab_w = e0.y;
         row_ent = (i32x4){e0.z * istride, e0.w * istride, e1.x, e1.y};
         if (CARRY) { carry_mask = e1.z; carry = uni(e1.w) != 0 && !plan.two_load; }
+        if (PAIR && plan.pair_taps) {
+            const i32x4 e2 = *(const i32x4*)(plan.pair_taps + ((size_t)(h > 0 ? h : 0) * 64 + lane) * 4);
+            carry_mask = e2.x; carry = uni(e2.z) != 0 && !plan.two_load;
+            // a pair without an orphan: the address is 2^31 bytes off, outside the buffer's range -- the load returns 0 without a fetch
+            // (and whatever it returned, the masks of both rows are zero)
+            spare_off = e2.y >= 0 ? e2.y * istride : (int)0x80000000;
+        }
     } else {
         const double scale = resize_scale(lv, h, sw);
         const ResizeTaps tp = resize_taps(lane < S ? lane : S - 1, scale, sw, area2);
@@ -280,10 +307,11 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         // (one-load loop: entry e = {offset of the UPPER source row of row e + 2, carry mask of row e, weights of row e})
         if (lane < S) {
             const int eo = lane >= 2 ? lane - 2 : lane + S - 2;
-            if (CARRY && carry) { ((int*)&rowtab[eo])[0] = row_ent.y; ((int*)&rowtab[lane])[1] = carry_mask; }
+            if ((CARRY || PAIR) && carry) { ((int*)&rowtab[eo])[0] = row_ent.y; ((int*)&rowtab[lane])[1] = carry_mask; }
             else *(i32x2*)&rowtab[eo] = (i32x2){row_ent.x, row_ent.y};
             *((i32x2*)&rowtab[lane] + 1) = (i32x2){row_ent.z, row_ent.w};
         }
+        if (PAIR && carry && lane < NPAIR) sptab[lane] = spare_off;
     } else if (lane < S + 2) rowtab[lane] = row_ent;
     // (every wave of the workgroup writes the same values; a wave's own LDS accesses execute in order, so it reads what it -- or
     //  a neighbour, identically -- wrote: no workgroup barrier)
@@ -291,7 +319,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     // pieces each, all four piece products)
     constexpr bool F16F = TO == 4 && CELL > 0;
     static_assert(!F16F || CELL * 361 * 8 < 65504, "float16 folds: a band slot's column sum (<= cell x 255 sqrt 2) x 8 must stay a float16 number");      // (column sums carry a factor 8: exact, undone with the weights' 2^10 after the fold)
-    if (SPEC && lane < S) wstab[lane] = (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]} * (F16F ? 8.0f : 1.0f);
+    if (SPEC && lane >= 1 && lane < S - 1) wstab[lane - 1] = (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]} * (F16F ? 8.0f : 1.0f);
     if (!SPEC && S + 2 > 64 && lane < S + 2 - 64) {
         i32x4 last;
 #pragma unroll
@@ -391,6 +419,10 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         };
         int Hc0 = 0, Hc1 = 0;
         unsigned short qlow = 0;      // the lower source row of row 0: the only row that loads two
+        // pair loop: the spare source row of pixel rows (2p + 1, 2p + 2), and what it filters to
+        unsigned short qspare = 0;
+        int Hsp = 0;
+        auto issue_spare = [&](int p) { qspare = __builtin_amdgcn_raw_buffer_load_b16(img_rsrc, vb + sptab[p], 0, 0); };
         float rm2 = 0.0f, rm1 = 0.0f;
         constexpr unsigned bin_stride = ST * 8;
         unsigned char* const cbase0 = (unsigned char*)colrows + lane * 8;
@@ -520,9 +552,25 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
             wave_sync();
         };
         unsigned short q0[2], q1[2];
-        auto row_step = [&](const int j, const int y, const bool grad, auto one_load) __attribute__((always_inline)) {
+        // `loop`: 0 = two loads per pixel row, 1 = one load (row carry), 2 = three loads per two pixel rows (pair carry)
+        auto row_step = [&](const int j, const int y, const bool grad, auto loop) __attribute__((always_inline)) {
             int H0, H1;
-            if constexpr (decltype(one_load)::value) {
+            constexpr int LOOP = decltype(loop)::value;
+            if constexpr (LOOP == 2) {
+                // as below; the first row of a pair (odd y) filters the pair's spare and issues the next pair's
+                const int Hn = filtered(q1[j]);
+                if (y == 0) Hc0 = filtered(qlow);
+                else {
+                    if (y & 1) {
+                        Hsp = filtered(qspare);
+                        if (y + 2 < S) issue_spare((y + 2) >> 1);
+                    }
+                    const unsigned mk = (unsigned)((const int*)&rowtab[y])[1];
+                    Hc0 = (int)(((unsigned)Hsp & mk) | ((unsigned)Hc1 & ~mk));
+                }
+                Hc1 = Hn; H0 = Hc0; H1 = Hc1;
+                if (y + 2 < S) issue_upper(y + 2, q1[j]);
+            } else if constexpr (LOOP == 1) {
                 // no branch, lane read or compare here: the mask comes with the weights in the row's one broadcast LDS read
                 const int Hn = filtered(q1[j]);
                 if (y == 0) Hc0 = filtered(qlow);
@@ -538,7 +586,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
             }
             f32x2 qv = {0.0f, 0.0f};
             if (grad) qv = *pend_p;
-            const float r0 = vertical(H0, H1, y, decltype(one_load)::value);
+            const float r0 = vertical(H0, H1, y, LOOP != 0);
             if (grad) {
                 const int yy = y - 1;                      // gradient of row y - 1 (hog.c:616-672)
                 const float gx = from_right(rm1) - from_left(rm1);
@@ -564,7 +612,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
                 *pend_p = __builtin_elementwise_fma(pend_v, (f32x2){pend_g, pend_g}, qv);
                 const float* rt = lv.row_tab[yy];
                 f32x2 wsv;
-                if (SPEC) wsv = wstab[yy];
+                if (SPEC) wsv = wstab[yy - 1];
                 else wsv = (f32x2){rt[0], rt[1]};
                 const float ws0 = wsv.x, ws1 = wsv.y;
                 // (specialised instance: yy and with it the band are constants after unrolling; prev_by folds away)
@@ -586,7 +634,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
             }
             rm2 = rm1; rm1 = r0;
         };
-        constexpr std::false_type two_loads{};
+        constexpr std::integral_constant<int, 0> two_loads{};
         auto two_load_rows = [&]() __attribute__((always_inline)) {
             issue_row(0, q0[0], q1[0]);
             issue_row(1, q0[1], q1[1]);
@@ -606,7 +654,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         };
         if constexpr (CARRY) {
             if (carry) {      // wave-uniform, once per pass: the loops themselves hold no branch
-                constexpr std::true_type one_load{};
+                constexpr std::integral_constant<int, 1> one_load{};
                 qlow = __builtin_amdgcn_raw_buffer_load_b16(img_rsrc, vb + __builtin_amdgcn_readlane(row_ent.x, 0), 0, 0);
                 issue_upper(0, q1[0]);
                 issue_upper(1, q1[1]);
@@ -614,6 +662,18 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
                 row_step(1, 1, false, one_load);
 #pragma unroll
                 for (int yrow = 2; yrow < SC; ++yrow) row_step(yrow & 1, yrow, true, one_load);
+            } else two_load_rows();
+        } else if constexpr (PAIR) {
+            if (carry) {      // wave-uniform, once per pass, as above
+                constexpr std::integral_constant<int, 2> pair_load{};
+                qlow = __builtin_amdgcn_raw_buffer_load_b16(img_rsrc, vb + __builtin_amdgcn_readlane(row_ent.x, 0), 0, 0);
+                issue_upper(0, q1[0]);
+                issue_upper(1, q1[1]);
+                issue_spare(0);
+                row_step(0, 0, false, pair_load);
+                row_step(1, 1, false, pair_load);
+#pragma unroll
+                for (int yrow = 2; yrow < SC; ++yrow) row_step(yrow & 1, yrow, true, pair_load);
             } else two_load_rows();
         } else two_load_rows();
         *pend_p = __builtin_elementwise_fma(pend_v, (f32x2){pend_g, pend_g}, *pend_p);
@@ -670,6 +730,36 @@ __global__ void taps_table_kernel(HogLevelDev lv, int* __restrict__ table)
     e[1] = (i32x4){tp.b0 << 12, tp.b1 << 12, (d >= 1 && tp.sy0 == p1) ? -1 : 0, eligible ? 1 : 0};
 }
 
+// Pair carry: per (level, h) a table of its own, [h < SDM_SCALE_TAB][64] x {take-the-spare mask of row d, source row of the spare of
+// pair d = pixel rows (2d + 1, 2d + 2) or -1 where the pair has no orphan, half-width is pair eligible, orphan rows of the patch}, from
+// the same taps.  Row d >= 1 is a shift row when sy0 equals row d - 1's sy1, an orphan row when it is the row after that; h is pair
+// eligible when the patch is neither empty nor the exact-2x reduction, every row d >= 1 is one of the two, no pair (2p + 1, 2p + 2)
+// holds two orphans and a last row without a partner (even S) is a shift row.  Row 0 loads its two rows itself.
+__global__ void pair_taps_table_kernel(HogLevelDev lv, int* __restrict__ table)
+{
+    const int h = blockIdx.x, d = threadIdx.x;
+    const int S = lv.S;
+    const bool empty = h <= 0;
+    const int sw = empty ? 1 : 2 * h;
+    const bool area2 = (sw == 2 * S);
+    const double scale = resize_scale(lv, h, sw);
+    const ResizeTaps tp = resize_taps(d < S ? d : S - 1, scale, sw, area2);
+    const int p1 = __shfl_up(tp.sy1, 1);      // (one wave per half-width)
+    const bool row = d >= 1 && d < S;
+    const bool orphan = row && tp.sy0 == p1 + 1;
+    const bool shift = row && tp.sy0 == p1;
+    const int npairs = (S - 1) / 2;
+    const unsigned long long orphans = __ballot(orphan);
+    const bool two = (d & 1) && d <= 2 * npairs && orphan && ((orphans >> (d + 1)) & 1);      // both rows of pair (d, d + 1)
+    const bool bad = (row && !shift && !orphan) || two || (d > 2 * npairs && d < S && !shift);
+    const bool eligible = !empty && !area2 && __ballot(bad) == 0;
+    // lane p: the spare of pixel rows (2p + 1, 2p + 2)
+    const int ra = __shfl(tp.sy0, (2 * d + 1) & 63), rb = __shfl(tp.sy0, (2 * d + 2) & 63);
+    int spare = -1;
+    if (d < npairs) spare = ((orphans >> (2 * d + 1)) & 1) ? ra : (((orphans >> (2 * d + 2)) & 1) ? rb : -1);
+    ((i32x4*)table)[(size_t)h * 64 + d] = (i32x4){orphan ? -1 : 0, spare, eligible ? 1 : 0, (int)__popcll(orphans)};
+}
+
 }  // namespace
 
 template <bool CELLS>
@@ -683,7 +773,7 @@ static void launch_hog_packed(const ImageSetDev& imgs, const int* img_idx, const
     const unsigned grid = (unsigned)((total + HP_WAVES - 1) / HP_WAVES);
 #define HP_LAUNCH_O(TO, CELL, RAW)                                                                                              \
     hipLaunchKernelGGL((hog_packed_kernel<TO, 5, CELL, RAW, CELLS>), dim3(grid), dim3(HP_WAVES * 64),                              \
-                       packed_wg_lds_bytes(5, TO, lv.S, CELLS ? 0 : plan.hist_slots, CELL > 0), stream, imgs, img_idx, x, N, L,  \
+                       packed_wg_lds_bytes(5, TO, lv.S, CELLS ? 0 : plan.hist_slots, CELL > 0, hp_pair_slots(CELL, 5, CELLS, RAW)), stream, imgs, img_idx, x, N, L,  \
                        eyes, lv, plan, feat, ldf, idx_out, status)
 #define HP_LAUNCH(CELL, RAW) HP_LAUNCH_O(4, CELL, RAW)
     if (lv.O == 9) {      // "31-bin" HOG (9 orientations, hog.c:212-215): 18 bin rows = two matrix-core row tiles per band fold
@@ -733,4 +823,15 @@ bool sdm_hog_cells_row_carry(const HogLevelDev& lv, const HogPlanDev& plan)
 void sdm_launch_taps_table(const HogLevelDev& lv, int* table, hipStream_t stream)
 {
     hipLaunchKernelGGL(taps_table_kernel, dim3(SDM_SCALE_TAB), dim3(64), 0, stream, lv, table);
+}
+
+// whether sdm_launch_hog_cells runs this level on an instance that holds the pair loop
+bool sdm_hog_cells_pair_carry(const HogLevelDev& lv, const HogPlanDev& plan)
+{
+    return lv.O == 4 && lv.C == 5 && plan.raw_sqrt && plan.taps && plan.pair_taps && hp_pair_carry(lv.cell);
+}
+
+void sdm_launch_pair_taps_table(const HogLevelDev& lv, int* table, hipStream_t stream)
+{
+    hipLaunchKernelGGL(pair_taps_table_kernel, dim3(SDM_SCALE_TAB), dim3(64), 0, stream, lv, table);
 }

@@ -78,6 +78,9 @@ bool sdm_hog_fast_supported(const HogLevelDev& lv);
 void sdm_launch_verify_fast_bins(const HogLevelDev& lv, int* mismatches_dev, hipStream_t stream);
 // table[SDM_SCALE_TAB][64][8] ints: the level's cv::resize taps for every patch half-width below SDM_SCALE_TAB
 void sdm_launch_taps_table(const HogLevelDev& lv, int* table, hipStream_t stream);
+// table[SDM_SCALE_TAB][64][4] ints: the pair loop's data from the same taps -- {take-the-spare mask of row d, source row of the spare of
+// pixel rows (2d + 1, 2d + 2) or -1, half-width is pair eligible, orphan rows of the patch} (sdm_hog_packed.hip: hp_pair_carry)
+void sdm_launch_pair_taps_table(const HogLevelDev& lv, int* table, hipStream_t stream);
 void sdm_launch_hog_fast(const ImageSetDev& imgs, const int* img_idx, const float* x, int N, int L,
                          const EyeIdxDev& eyes, const HogLevelDev& lv, float* feat, long long ldf, int* idx_out,
                          int* status, int acc_mode, int fast_bins, hipStream_t stream);
@@ -103,7 +106,8 @@ struct HogPlanDev {
     const unsigned short* wb16; // [pass][lane][2 k-blocks][2 pieces][8] float16 bits: the same weights x 2^10 as two float16 pieces in the layout of v_mfma_f32_16x16x32_f16's B operand (the float16 band folds of the specialised instances)
     const int* pass_info;
     const int* taps;           // [SDM_SCALE_TAB half-widths][64 coordinates][8] cv::resize taps of the level (sdm_launch_taps_table); null = computed per wave
-    int two_load;              // option hog_two_load: every wave takes the two-load row loop (A/B, tests); 0 = one-load loop where the half-width is eligible
+    int two_load;              // option hog_two_load: every wave takes the two-load row loop (A/B, tests); 0 = one-load / pair loop where the half-width is eligible
+    const int* pair_taps;      // [SDM_SCALE_TAB half-widths][64][4] the pair loop's masks and spare rows (sdm_launch_pair_taps_table); null = no wave takes the pair loop
 };
 // Cell row (band) of resized-ROI row d: floor((d + 0.5) / cell - 0.5) (hog.c:697-704) in integers, for the instances specialised
 // on the cell size; sdm_hog_plan_build checks it against the level's float table before such an instance is chosen.
@@ -135,6 +139,8 @@ void sdm_launch_hog_cells(const ImageSetDev& imgs, const int* img_idx, const flo
                           int* idx_out, int* status, hipStream_t stream);
 // the cells launch of this level runs an instance with the one-load row loop (sdm_hog_packed.hip: hp_row_carry)
 bool sdm_hog_cells_row_carry(const HogLevelDev& lv, const HogPlanDev& plan);
+// the cells launch of this level runs an instance with the pair loop (sdm_hog_packed.hip: hp_pair_carry)
+bool sdm_hog_cells_pair_carry(const HogLevelDev& lv, const HogPlanDev& plan);
 
 // ---- raw cells -> descriptors (sdm_desc.hip) ----
 bool sdm_desc_supported(const HogLevelDev& lv);

@@ -792,6 +792,15 @@ class Context:
         check(self._lib.sdm_debug_hog_taps(self._h, level, _ip(table), _ip(info)))
         return table, dict(cells_launch=bool(info[0]), one_load_instance=bool(info[1]), two_load_option=bool(info[2]))
 
+    def debug_hog_pair_taps(self, level: int):
+        """The level's pair-loop table as the device built it, [128 half-widths][64][4] = {take-the-spare mask of row d, spare source
+        row of pixel rows (2d + 1, 2d + 2) or -1, pair eligible, orphan rows}, and {pair_instance, two_load_option}
+        (include/sdm.h: sdm_debug_hog_pair_taps)."""
+        table = np.empty((128, 64, 4), np.int32)
+        info = np.zeros(2, np.int32)
+        check(self._lib.sdm_debug_hog_pair_taps(self._h, level, _ip(table), _ip(info)))
+        return table, dict(pair_instance=bool(info[0]), two_load_option=bool(info[1]))
+
     def set_hog_packing(self, on: bool):
         """Lane packing of the HOG launch (include/sdm.h: sdm_debug_set_hog_packing); on by default."""
         check(self._lib.sdm_debug_set_hog_packing(self._h, int(on)))
