@@ -494,6 +494,62 @@ int sdm_track_step(sdm_ctx* ctx, const int* ids, int n, float* landmarks_host, i
  * output may be NULL.  The current rows x are not touched. */
 int sdm_track_get(sdm_ctx* ctx, const int* ids, int n, float* landmarks_host, int* status_host);
 
+/* Rolled faces: upright-normalised detect and tracking.  A cascade tolerates the roll its training set held and no more: from a box
+ * on a face rolled by 30 degrees an upright-trained cascade ends where it started.  Here every row's face is cut out of its frame
+ * as a chip x chip gray image in which it stands upright -- one launch for all rows --, the unchanged cascade of sdm_detect_batch
+ * runs on that stack of chips (one image per row), and one small launch maps the result rows back into frame coordinates: after
+ * either call below the current rows x are in FRAME coordinates, and sdm_get_x, sdm_align_crops*, sdm_pose_templates_from_landmarks
+ * and the tracker's lost rule work on them unchanged.
+ *   roll      positive = clockwise on screen (x right, y down): a face with roll t has its eye line, from the subject's right eye to
+ *             their left eye (left to right in the image), along (cos t, sin t).
+ *   inputs    per row doubles c, s with c^2 + s^2 = 1 and an integer centre (ix, iy); hc = chip / 2 (integer division).
+ *   M         chip -> frame, float32, the translations evaluated in double and rounded once:
+ *               M00 = c, M01 = -s, M02 = ix - (c hc - s hc);  M10 = s, M11 = c, M12 = iy - (s hc + c hc)
+ *   W         frame -> chip (the tracker only): W00 = c, W01 = s, W02 = hc - (c ix + s iy);  W10 = -s, W11 = c, W12 = hc - (c iy - s ix)
+ *   points    through a matrix A: ((A00 x + A01 y) + A02, (A10 x + A11 y) + A12) in float32, every operation rounded, nothing contracted.
+ *   chip      pixel (column j, row i) is the `sample` rule of sdm_align_crops with M, out_width = out_height = chip, one channel, on the
+ *             row's gray context image (sdm_set_sample_image_index; gray and NV12 luma in place, colour as sdm_set_frames_device
+ *             converted it): 1/32-pixel positions, (.. + 512) >> 10, a tap outside the frame reads 0.  At roll 0 the chip is a byte copy
+ *             of the frame region, at 90, 180 and 270 degrees an exact rotation.  Row n's chip is image n of a stack the context
+ *             owns: each chip starts on a 16-byte boundary, row stride (chip + 15) & ~15 (the padding is zero), 64-bit offsets.
+ *   detect    box (x, y, w, h) and roll_deg: ix = x + w / 2, iy = y + h / 2 (integer division); c, s on the host in double -- a multiple
+ *             of 90 degrees gives exactly 0 / +-1, otherwise cos / sin of (double)roll_deg * pi / 180.  The initialisation is
+ *             align_mean(mean, (hc - w / 2, hc - h / 2, w, h)), bit-identical to sdm_init_from_boxes on that box; the cascade runs all
+ *             levels on the chips; the result is the rows through M.
+ *   tracker   (sdm_track_configure_upright) a STARTED slot behaves as detect, with the roll of sdm_track_start_rolled (sdm_track_start:
+ *             roll 0).  A TRACKED slot with landmarks p takes its roll from its eye line: the eye centres as the inter-eye distance
+ *             forms them (float32 sums in index order, divided by the count), dx = lx - rx, dy = ly - ry in float32, then in double
+ *             n = sqrt(dx^2 + dy^2), c = dx / n, s = dy / n (n == 0 or not finite: c = 1, s = 0); ix = (int)floorf((min x + max x) * 0.5f)
+ *             with the float clamped to +-2^20 first, iy likewise.  The row's init is the SDM_TRACK_INIT_REALIGN rule, same arithmetic,
+ *             applied to q = W p (whatever init_mode the tracker was configured with).  Behind the cascade and the back-map the commit
+ *             and the lost rule run unchanged on the frame-coordinate result, the frames' sizes and the chip-coordinate init (of which
+ *             the SCALE rule takes the inter-eye distance).  The first step of a started stream equals sdm_detect_batch_upright.
+ *   flags     per row, kept with M until the next upright call (sdm_upright_get):
+ *             SDM_UPRIGHT_PARTIAL    a chip corner samples outside [0, W - 1] x [0, H - 1] (the rule of SDM_ALIGN_PARTIAL; informational)
+ *             SDM_UPRIGHT_NEAR_EDGE  a result landmark q (chip coordinates, float32) has less than `guard` pixels to the border of the
+ *                                    chip: not (qx >= guard, qy >= guard, (chip - 1) - qx >= guard, (chip - 1) - qy >= guard).  Patches
+ *                                    may have read black where the frame has pixels: the chip is too small for this face.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched: chip outside [32, 1024], guard outside [0, chip / 2), a non-finite
+ * roll, a box without area, n < 1, no geometry, a level without regressor, no images, templates set, an image index that does not
+ * cover the rows, eye indices missing where a level's patches need them, an upright call before sdm_upright_configure; upright
+ * tracking without both eye index sets, without sdm_upright_configure or before sdm_track_configure; and everything sdm_detect_batch
+ * and sdm_track_step refuse.  sdm_track_configure itself is unchanged. */
+#define SDM_UPRIGHT_PARTIAL 1
+#define SDM_UPRIGHT_NEAR_EDGE 2
+/* chip in [32, 1024] pixels, guard in [0, chip / 2). */
+int sdm_upright_configure(sdm_ctx* ctx, int chip, int guard);
+/* mean: 2L floats; boxes: n x {x, y, width, height}; roll_deg: n angles.  One copy in, one synchronise.  x_host (n x 2L, frame
+ * coordinates) may be NULL.  SDM_ERR_EMPTY_PATCH as sdm_get_x reports it. */
+int sdm_detect_batch_upright(sdm_ctx* ctx, const float* mean, const int* boxes, const float* roll_deg, int n, float* x_host);
+/* Of the last upright call (detect or tracker step): matrices_host N x 6 (M00 M01 M02 M10 M11 M12), flags_host N, chips_host
+ * N x chip x chip bytes, dense.  Each may be NULL. */
+int sdm_upright_get(sdm_ctx* ctx, float* matrices_host, int* flags_host, uint8_t* chips_host);
+/* Upright mode of the tracker on (enable != 0) or off.  Needs sdm_track_configure, sdm_upright_configure and both eye index sets.
+ * After a later sdm_track_configure with more slots, call it again before the next start or step (they are refused until then). */
+int sdm_track_configure_upright(sdm_ctx* ctx, int enable);
+/* sdm_track_start with a roll per stream (degrees; the rule of sdm_detect_batch_upright).  Needs upright mode. */
+int sdm_track_start_rolled(sdm_ctx* ctx, const int* ids, const int* boxes, const float* roll_deg, int n);
+
 /* Aligned face crops of the current rows (after sdm_detect_batch, sdm_track_step or sdm_set_x): for every row n of x (N x 2L, what
  * sdm_get_x returns) an out_width x out_height x C u8 crop in which the face stands in a canonical position -- the input of
  * recognition, expression or attribute networks -- without the landmarks or the frames leaving the device.

@@ -37,12 +37,16 @@ EXPORTED = [
     "sdm_align_set_source", "sdm_align_crops", "sdm_align_set_source_frames", "sdm_align_crops_tensor", "sdm_align_crops_tensor_filtered",
     "sdm_train_level_sweep", "sdm_sweep_get_regressor",
     "sdm_set_frames_device", "sdm_debug_download_image",
+    "sdm_upright_configure", "sdm_detect_batch_upright", "sdm_upright_get", "sdm_track_configure_upright", "sdm_track_start_rolled",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
 SDM_TRACK_FREE, SDM_TRACK_STARTED, SDM_TRACK_TRACKED, SDM_TRACK_LOST = 0, 1, 2, 3
 SDM_TRACK_INIT_PREVIOUS, SDM_TRACK_INIT_REALIGN = 0, 1
 SDM_TRACK_LOST_NONFINITE, SDM_TRACK_LOST_SMALL, SDM_TRACK_LOST_OUTSIDE, SDM_TRACK_LOST_SCALE = 1, 2, 4, 8
+
+# upright-normalised detect and tracking (include/sdm.h, "Rolled faces")
+SDM_UPRIGHT_PARTIAL, SDM_UPRIGHT_NEAR_EDGE = 1, 2
 
 # aligned face crops (include/sdm.h, sdm_align_*)
 SDM_ALIGN_DEGENERATE, SDM_ALIGN_PARTIAL = 1, 2
@@ -403,6 +407,11 @@ def lib() -> ctypes.CDLL:
             "sdm_sweep_get_regressor": [c_void_p, c_int, c_float_p],
             "sdm_set_frames_device": [c_void_p, ctypes.POINTER(SdmFrame), c_int, c_int],
             "sdm_debug_download_image": [c_void_p, c_int, c_void_p],
+            "sdm_upright_configure": [c_void_p, c_int, c_int],
+            "sdm_detect_batch_upright": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
+            "sdm_upright_get": [c_void_p, c_void_p, c_void_p, c_void_p],
+            "sdm_track_configure_upright": [c_void_p, c_int],
+            "sdm_track_start_rolled": [c_void_p, c_void_p, c_void_p, c_void_p, c_int],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

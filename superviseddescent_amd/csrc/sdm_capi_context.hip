@@ -79,6 +79,7 @@ void sdm_destroy(sdm_ctx* c)
     c->align.release();
     c->sweep.release();
     c->frames.release();
+    c->upright.release();
     for (auto& r : c->Rt) r.release();
     for (auto& q : c->plans) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); q.pair_taps.release(); }
     if (c->own_stream) e = hipStreamDestroy(c->stream);

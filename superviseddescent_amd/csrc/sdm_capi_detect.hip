@@ -52,13 +52,27 @@ int check_status(sdm_ctx* c)
 
 // feature row length: L patches + the bias of the adaptive transform (the non-adaptive example transform has none)
 
-ImageSetDev image_set(const sdm_ctx* c)
+ImageSetDev frame_set(const sdm_ctx* c)
 {
     ImageSetDev s;
     s.base = c->img_base; s.offset = c->img_off.p; s.w = c->img_w.p; s.h = c->img_h.p;
     s.stride = c->img_stride.p; s.n_images = c->n_images;
     return s;
 }
+
+// The images the cascade reads and the rows' index into them: the context's, or -- while an upright call is in flight
+// (sdm_capi_upright.hip) -- the stack of chips, one per row.  With no such call every launch is what it was.
+ImageSetDev image_set(const sdm_ctx* c)
+{
+    if (!c->upright.active) return frame_set(c);
+    const sdm_ctx::Upright& u = c->upright;
+    ImageSetDev s;
+    s.base = u.chips.p; s.offset = u.off.p; s.w = u.w.p; s.h = u.h.p; s.stride = u.stride.p; s.n_images = u.N;
+    return s;
+}
+const int* sample_index(const sdm_ctx* c) { return (c->upright.active || c->idx_identity) ? nullptr : c->img_idx.p; }
+// (a chip is never one of the images the fused pixel kernels cannot serve)
+static bool narrow_set(const sdm_ctx* c) { return !c->upright.active && c->narrow_images; }
 
 int ensure_sample_buffers(sdm_ctx* c, int N)
 {
@@ -80,6 +94,7 @@ int ensure_sample_buffers(sdm_ctx* c, int N)
 // because the index, the images and x may be set in any order.
 int check_sample_index(const sdm_ctx* c)
 {
+    if (c->upright.active) return SDM_OK;      // (one chip per row, identity index)
     if (c->idx_identity && c->N > c->n_images)
         return fail(SDM_ERR_INVALID, "more samples than images and no sample->image index set");
     if (!c->idx_identity && c->N > c->n_idx)
@@ -92,7 +107,7 @@ int check_sample_index(const sdm_ctx* c)
 // the default mode's lane-packed launch is usable for this level
 bool packed_ok(const sdm_ctx* c, int level)
 {
-    return c->fast_kernel[level] && !c->narrow_images && c->packing && c->hog_mode == SDM_HOG_COLUMNS &&
+    return c->fast_kernel[level] && !narrow_set(c) && c->packing && c->hog_mode == SDM_HOG_COLUMNS &&
            c->fast_bins[level] == 2 && c->plans[level].ok;
 }
 bool split_ok(const sdm_ctx* c, int level) { return packed_ok(c, level) && sdm_desc_supported(c->levels[level]); }
@@ -119,7 +134,7 @@ int launch_cells(sdm_ctx* c, int level)
 {
     int rc = c->cells.ensure(sdm_cells_floats(c->levels[level], c->N, c->L));
     if (rc) return rc;
-    sdm_launch_hog_cells(image_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->x[c->cur].p, c->N, c->L, c->eyes,
+    sdm_launch_hog_cells(image_set(c), sample_index(c), c->x[c->cur].p, c->N, c->L, c->eyes,
                          c->levels[level], cells_plan(c, level), c->cells.p, c->patch_idx.p, c->status.p, c->stream);
     return SDM_OK;
 }
@@ -142,15 +157,15 @@ int do_hog(sdm_ctx* c, int level)
             if (rcc) return rcc;
             sdm_launch_desc_store(c->levels[level], c->cells.p, c->plans[level].cut.p, c->N, c->L, c->feat.p, c->ldf, c->stream);
         } else if (packed_ok(c, level))
-            sdm_launch_hog_packed(image_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->x[c->cur].p, c->N, c->L,
+            sdm_launch_hog_packed(image_set(c), sample_index(c), c->x[c->cur].p, c->N, c->L,
                                   c->eyes, c->levels[level], c->plans[level].dev, c->feat.p, c->ldf, c->patch_idx.p,
                                   c->status.p, c->stream);
-        else if (c->fast_kernel[level] && !c->narrow_images)
-            sdm_launch_hog_fast(image_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->x[c->cur].p, c->N, c->L,
+        else if (c->fast_kernel[level] && !narrow_set(c))
+            sdm_launch_hog_fast(image_set(c), sample_index(c), c->x[c->cur].p, c->N, c->L,
                                 c->eyes, c->levels[level], c->feat.p, c->ldf, c->patch_idx.p, c->status.p,
                                 c->hog_mode /* = the kernel's ACC_* value */, c->fast_bins[level], c->stream);
         else   // generic S > 64 geometry: the reference-order kernel
-            sdm_launch_hog(image_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->x[c->cur].p, c->N, c->L,
+            sdm_launch_hog(image_set(c), sample_index(c), c->x[c->cur].p, c->N, c->L,
                            c->eyes, c->levels[level], c->feat.p, c->ldf, c->patch_idx.p, c->status.p, c->stream);
     }
     if (c->tmpl_N > 0) {   // known-template mode: the regressors see features - templates (superviseddescent.hpp:195-197)
@@ -231,7 +246,7 @@ int detect_level_fused(sdm_ctx* c, int l)
     const HogLevelDev& lv = c->levels[l];
     {
         Timer t(c, SDM_T_HOG);
-        sdm_launch_hog_cells(image_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->x[c->cur].p, c->N, c->L, c->eyes, lv,
+        sdm_launch_hog_cells(image_set(c), sample_index(c), c->x[c->cur].p, c->N, c->L, c->eyes, lv,
                              cells_plan(c, l), c->cells.p, c->patch_idx.p, c->status.p, c->stream);
     }
     {

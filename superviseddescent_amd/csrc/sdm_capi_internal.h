@@ -6,7 +6,7 @@
 //   sdm_capi_train.hip     targets, Gram / right-hand side, solvers       sdm_capi_exchange.hip  the several-GPU exchange of the normal equations
 //   sdm_capi_debug.hip     device pointers, timing, debug entry points   sdm_capi_pose.hip / sdm_capi_track.hip  head pose, tracking
 //   sdm_capi_align.hip     aligned face crops                          sdm_capi_sweep.hip     regulariser sweep on one Gram product
-//   sdm_capi_frames.hip    device-resident frames as the image set
+//   sdm_capi_frames.hip    device-resident frames as the image set     sdm_capi_upright.hip   upright chips for rolled faces
 #pragma once
 #include "../../include/sdm.h"
 #include "sdm_kernels.h"
@@ -249,6 +249,8 @@ struct sdm_ctx {
         DevBuf<int> box, status;           // S x 4 start boxes, S device statuses (read by the gather: STARTED or not)
         DevBuf<float> init;                // n x 2L: the rows the cascade started from (the scale rule), scratch of sdm_track_get
         DevBuf<int> ids, masks;            // n ids; n masks + the kernel status word
+        bool upright = false;              // sdm_track_configure_upright: a step cuts upright chips (sdm_capi_upright.hip)
+        DevBuf<double> cs;                 // S x (cos, sin) of the roll a slot was started with (upright mode)
         std::vector<int> host_status;      // mirror of the slots' statuses, refreshed from the masks every step
         std::vector<unsigned> seen;        // per slot: stamp of the last call that named it (duplicate check)
         unsigned stamp = 0;
@@ -256,7 +258,8 @@ struct sdm_ctx {
         size_t pin_cap = 0;                // ints
         void release()
         {
-            mean.release(); x.release(); box.release(); status.release(); init.release(); ids.release(); masks.release();
+            mean.release(); x.release(); box.release(); status.release(); init.release(); ids.release(); masks.release(); cs.release();
+            upright = false;
             if (pin) { hipError_t e = hipHostFree(pin); (void)e; }
             pin = nullptr; pin_cap = 0; S = 0;
         }
@@ -305,6 +308,19 @@ struct sdm_ctx {
         DevBuf<FrameConvDev> desc;
         void release() { gray.release(); desc.release(); }
     } frames;
+    // upright-normalised detect and tracking (sdm_capi_upright.hip): the stack of chips with its image table, and the rows' records.
+    // While `active` the cascade's launches read the chips, one per row, in place of the context's images (sdm_capi_detect.hip).
+    struct Upright {
+        int chip = 0, guard = 0;           // chip == 0: sdm_upright_configure not called
+        bool active = false;
+        int N = 0;                         // rows of the last upright call (the records and chips sdm_upright_get returns)
+        DevBuf<uint8_t> chips;
+        DevBuf<long long> off;
+        DevBuf<int> w, h, stride;
+        DevBuf<UprightRow> rows;
+        DevBuf<double> in;                 // a detect call's (cos, sin) pairs, boxes and mean
+        void release() { chips.release(); off.release(); w.release(); h.release(); stride.release(); rows.release(); in.release(); chip = 0; N = 0; }
+    } upright;
     // host copies of the image sizes and of the sample -> image index (the checks of an external crop source)
     std::vector<int> img_w_host, img_h_host, img_idx_host;
 
@@ -354,6 +370,14 @@ void fill_row_tab(HogLevelDev& lv);
 void drain_timing(sdm_ctx* c);
 int check_status(sdm_ctx* c);
 ImageSetDev image_set(const sdm_ctx* c);
+const int* sample_index(const sdm_ctx* c);
+ImageSetDev frame_set(const sdm_ctx* c);              // the context's images, whatever is in flight
+// (sdm_capi_upright.hip) what an upright call of n rows checks before anything is launched, its buffers, and the launches behind the
+// set-up kernel: chips, the cascade on them, the back-map
+int upright_check(sdm_ctx* c, int n);
+int upright_ensure(sdm_ctx* c, int n);
+int upright_run(sdm_ctx* c, int n);
+int upright_roll_cs(float roll_deg, double* cs);
 int ensure_sample_buffers(sdm_ctx* c, int N);
 int check_sample_index(const sdm_ctx* c);
 bool packed_ok(const sdm_ctx* c, int level);

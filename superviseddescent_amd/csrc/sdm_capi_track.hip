@@ -79,25 +79,49 @@ int sdm_track_configure(sdm_ctx* c, int capacity, const float* mean, int init_mo
     return SDM_OK;
 }
 
-int sdm_track_start(sdm_ctx* c, const int* ids, const int* boxes, int n)
+// sdm_track_start (roll_deg null) and sdm_track_start_rolled: with the upright mode's per-slot (cos, sin) allocated every start writes
+// the slot's pair as well -- (1, 0) without a roll
+static int track_start_common(sdm_ctx* c, const int* ids, const int* boxes, const float* roll_deg, int n)
 {
     int rc = track_ready(c);
     if (rc) return rc;
+    sdm_ctx::Track& t = c->track;
+    if (roll_deg && !t.upright) return fail(SDM_ERR_INVALID, "a rolled start needs upright mode (sdm_track_configure_upright)");
+    if (t.upright && t.cs.cap < (size_t)2 * t.S)
+        return fail(SDM_ERR_INVALID, "the tracker was configured again: call sdm_track_configure_upright again");
     if ((rc = check_ids(c, ids, n))) return rc;
     if (!boxes) return fail(SDM_ERR_INVALID, "no face boxes");
     for (int i = 0; i < n; ++i)
         if (boxes[4 * i + 2] <= 0 || boxes[4 * i + 3] <= 0) return fail(SDM_ERR_INVALID, "a face box needs width and height > 0");
-    sdm_ctx::Track& t = c->track;
+    std::vector<double> cs;
+    if (roll_deg) {
+        cs.resize((size_t)2 * n);
+        for (int i = 0; i < n; ++i)
+            if ((rc = upright_roll_cs(roll_deg[i], &cs[(size_t)2 * i]))) return rc;
+    }
+    const bool slots_cs = t.cs.cap >= (size_t)2 * t.S;
+    // staging: (cos, sin) pairs first (8-byte aligned), then the ids and the boxes
+    const size_t cs_ints = roll_deg ? (size_t)4 * n : 0;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = ensure_pinned(t, (size_t)5 * n)) || (rc = t.ids.ensure((size_t)5 * n))) return rc;
-    memcpy(t.pin, ids, (size_t)n * sizeof(int));
-    memcpy(t.pin + n, boxes, (size_t)4 * n * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (size_t)5 * n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    sdm_launch_track_start(t.ids.p, t.ids.p + n, n, t.box.p, t.status.p, c->stream);
+    if ((rc = ensure_pinned(t, cs_ints + (size_t)5 * n)) || (rc = t.ids.ensure(cs_ints + (size_t)5 * n + 1))) return rc;
+    if (roll_deg) memcpy(t.pin, cs.data(), cs_ints * sizeof(int));
+    memcpy(t.pin + cs_ints, ids, (size_t)n * sizeof(int));
+    memcpy(t.pin + cs_ints + n, boxes, (size_t)4 * n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (cs_ints + (size_t)5 * n) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    sdm_launch_track_start(t.ids.p + cs_ints, t.ids.p + cs_ints + n, n, t.box.p, t.status.p, c->stream);
+    if (slots_cs) sdm_launch_upright_slot_cs(t.ids.p + cs_ints, roll_deg ? (const double*)t.ids.p : nullptr, n, t.cs.p, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));      // (the pinned staging is reused by the next call)
     for (int i = 0; i < n; ++i) t.host_status[ids[i]] = SDM_TRACK_STARTED;
     return SDM_OK;
+}
+
+int sdm_track_start(sdm_ctx* c, const int* ids, const int* boxes, int n) { return track_start_common(c, ids, boxes, nullptr, n); }
+
+int sdm_track_start_rolled(sdm_ctx* c, const int* ids, const int* boxes, const float* roll_deg, int n)
+{
+    if (!roll_deg) return fail(SDM_ERR_INVALID, "no rolls");
+    return track_start_common(c, ids, boxes, roll_deg, n);
 }
 
 int sdm_track_stop(sdm_ctx* c, const int* ids, int n)
@@ -124,6 +148,11 @@ int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int
         if (st == SDM_TRACK_LOST) return fail(SDM_ERR_INVALID, "stream " + std::to_string(ids[i]) + " is lost: start it again from a face box");
     }
     if (c->tmpl_N > 0) return fail(SDM_ERR_INVALID, "templates are set: the tracker runs the cascade without (sdm_set_templates(NULL))");
+    if (t.upright) {
+        if (t.cs.cap < (size_t)2 * t.S) return fail(SDM_ERR_INVALID, "the tracker was configured again: call sdm_track_configure_upright again");
+        if (c->eyes.nre <= 0 || c->eyes.nle <= 0) return fail(SDM_ERR_INVALID, "upright tracking needs both eye landmark index sets");
+        if ((rc = upright_check(c, n))) return rc;
+    }
     if (!c->img_base || c->n_images < 1) return fail(SDM_ERR_INVALID, "no images set");
     if (c->idx_identity && n > c->n_images) return fail(SDM_ERR_INVALID, "more rows than images and no sample->image index set");
     if (!c->idx_identity && n > c->n_idx) return fail(SDM_ERR_INVALID, "sample->image index is shorter than the step's rows");
@@ -134,11 +163,23 @@ int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int
     if ((rc = ensure_sample_buffers(c, n)) || (rc = t.init.ensure((size_t)n * M)) || (rc = t.ids.ensure((size_t)n)) ||
         (rc = t.masks.ensure((size_t)n + 1)) || (rc = ensure_pinned(t, (size_t)2 * n + 1)))
         return rc;
+    if (t.upright && (rc = upright_ensure(c, n))) return rc;
     // the rows become the current x, as after sdm_set_x + sdm_detect_batch
     if (n != c->N) { c->have_targets = false; c->feat_level = -1; c->have_patch_idx = false; }
     c->N = n; c->cur = 0;
     memcpy(t.pin, ids, (size_t)n * sizeof(int));
     HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (t.upright) {
+        // upright mode: the rows' chips and their init in chip coordinates, the cascade on the chips, the result back in the frame
+        UprightSetupDev a{};
+        a.ids = t.ids.p; a.slot_status = t.status.p; a.slot_box = t.box.p; a.slot_cs = t.cs.p; a.slot_x = t.x.p; a.mean = t.mean.p;
+        a.mb = make_float4(t.mean_bounds[0], t.mean_bounds[1], t.mean_bounds[2], t.mean_bounds[3]);
+        sdm_ctx::Upright& u = c->upright;
+        sdm_launch_upright_setup(a, n, c->L, u.chip, frame_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->eyes, u.rows.p, u.off.p,
+                                 u.w.p, u.h.p, u.stride.p, c->x[0].p, t.init.p, c->stream);
+        HIP_TRY(hipGetLastError());
+        if ((rc = upright_run(c, n))) return rc;
+    } else {
     sdm_launch_track_gather(t.ids.p, n, c->L, t.mode, t.status.p, t.box.p, t.x.p, t.mean.p, t.mean_bounds, c->x[0].p, t.init.p, c->stream);
     HIP_TRY(hipGetLastError());
     // the cascade: exactly sdm_detect_batch's level sequence (fused or unfused per level)
@@ -146,6 +187,7 @@ int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int
     for (int l = 0; l < (int)c->levels.size() && !rc; ++l) rc = detect_level(c, l);
     c->chain_timers = false; c->ev_fresh = false;
     if (rc) return rc;
+    }
     sdm_launch_track_commit(t.ids.p, n, c->L, c->x[c->cur].p, t.init.p, c->idx_identity ? nullptr : c->img_idx.p, c->img_w.p, c->img_h.p,
                             c->eyes, t.min_size, t.max_scale, t.x.p, t.status.p, t.masks.p, c->status.p, c->stream);
     HIP_TRY(hipGetLastError());

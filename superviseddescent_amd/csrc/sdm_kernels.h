@@ -432,3 +432,32 @@ struct AlignAreaDev {
 void sdm_launch_align_area(const uint8_t* base, const AlignFace* faces, const AlignFrameDev* frames, const int* img_idx, int src_format,
                            int N, int out_w, int out_h, int dtype, int layout, int channels, const AlignTensorDev& spec,
                            const AlignAreaDev& area, int* samples, void* out, hipStream_t s);
+
+// ---- upright-normalised detect and tracking (sdm_upright.hip) ----
+// per row: the chip -> frame matrix M and its inverse W (float32, rounded from the double rotation), the SDM_UPRIGHT_* flags and the
+// row's frame in the context's image set
+struct UprightRow {
+    float m[6];                // M00 M01 M02 M10 M11 M12
+    float w[6];                // W00 W01 W02 W10 W11 W12
+    long long off;             // the frame's first byte, from the image set's base
+    int iw, ih, stride;        // its pixels, rows, bytes per row
+    int flags;
+};
+// where a row's rotation and centre come from: the call's boxes and (cos, sin) pairs (ids null), or the tracker's slots -- a STARTED
+// slot its box and stored (cos, sin), a TRACKED one its landmarks; mean: 2L floats, mb: the mean's bounds (tracked slots only)
+struct UprightSetupDev {
+    const int* boxes; const double* cs;
+    const int* ids; const int* slot_status; const int* slot_box; const double* slot_cs; const float* slot_x;
+    const float* mean; float4 mb;
+};
+inline int sdm_upright_chip_stride(int chip) { return (chip + 15) & ~15; }
+// rows: n records; chip_*: entries 0 .. n - 1 of the chips' image table (chip i at i * stride * chip); x, init (may be null): n x 2L
+void sdm_launch_upright_setup(const UprightSetupDev& a, int n, int L, int chip, const ImageSetDev& frames, const int* img_idx,
+                              const EyeIdxDev& eyes, UprightRow* rows, long long* chip_off, int* chip_w, int* chip_h, int* chip_stride,
+                              float* x, float* init, hipStream_t s);
+// chips: n x chip rows of sdm_upright_chip_stride(chip) bytes, 16-byte aligned
+void sdm_launch_upright_chips(const uint8_t* img, const UprightRow* rows, int n, int chip, uint8_t* chips, hipStream_t s);
+// x (n x 2L, chip coordinates) through M in place; NEAR_EDGE into the records
+void sdm_launch_upright_back(UprightRow* rows, int n, int L, int chip, int guard, float* x, hipStream_t s);
+// slot_cs[ids[i]] = cs[i] (cs null: (1, 0))
+void sdm_launch_upright_slot_cs(const int* ids, const double* cs, int n, double* slot_cs, hipStream_t s);

@@ -590,6 +590,8 @@ class Context:
         rc = self._lib.sdm_track_step(self._h, i.ctypes.data, i.size, out.ctypes.data if fetch else None, lost.ctypes.data)
         if rc in (_lib.SDM_OK, _lib.SDM_ERR_EMPTY_PATCH):      # (the step was committed)
             self.N = i.size
+            if getattr(self, "track_upright", False):
+                self.upright_N = i.size
         check(rc)
         return out, lost
 
@@ -599,6 +601,53 @@ class Context:
         st = np.empty(i.size, np.int32)
         check(self._lib.sdm_track_get(self._h, i.ctypes.data, i.size, out.ctypes.data, st.ctypes.data))
         return out, st
+
+    # -- upright-normalised detect and tracking (csrc/sdm_upright.hip) ------------------------------
+    def upright_configure(self, chip: int, guard: int):
+        """The size of the upright chips (32 ... 1024 pixels) and the NEAR_EDGE guard band (0 ... chip / 2 - 1 pixels)."""
+        check(self._lib.sdm_upright_configure(self._h, int(chip), int(guard)))
+        self.upright_chip = int(chip)
+
+    def detect_batch_upright(self, mean: np.ndarray, boxes: np.ndarray, roll_deg, fetch: bool = True) -> Optional[np.ndarray]:
+        """``detect_batch`` for rolled faces (include/sdm.h, sdm_detect_batch_upright): row i's face, in box i with a roll of
+        ``roll_deg[i]`` degrees (clockwise positive), is cut upright from its frame, the cascade runs on the chips, the result comes
+        back in frame coordinates and is the current x."""
+        m = np.ascontiguousarray(mean, np.float32).reshape(-1)
+        if m.size != 2 * self.L:
+            raise ValueError("the mean must hold 2L coordinates")
+        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(roll_deg, np.float32).reshape(-1), (b.shape[0],)), np.float32)
+        out = np.empty((b.shape[0], 2 * self.L), np.float32) if fetch else None
+        rc = self._lib.sdm_detect_batch_upright(self._h, m.ctypes.data, b.ctypes.data, r.ctypes.data, b.shape[0],
+                                                out.ctypes.data if fetch else None)
+        if rc in (_lib.SDM_OK, _lib.SDM_ERR_EMPTY_PATCH):
+            self.N = b.shape[0]
+            self.upright_N = b.shape[0]
+        check(rc)
+        return out
+
+    def upright_get(self, chips: bool = False):
+        """Of the last upright call (detect or tracker step): (M n x 2 x 3 float32, chip -> frame; flags n int32, SDM_UPRIGHT_* bits)
+        and, with ``chips``, the n x chip x chip uint8 chips the cascade ran on."""
+        n = int(getattr(self, "upright_N", 0))
+        mats = np.empty((n, 2, 3), np.float32)
+        flags = np.empty(n, np.int32)
+        chip = int(getattr(self, "upright_chip", 0))
+        ch = np.empty((n, chip, chip), np.uint8) if chips and n else None
+        check(self._lib.sdm_upright_get(self._h, mats.ctypes.data, flags.ctypes.data, ch.ctypes.data if ch is not None else None))
+        return (mats, flags, ch) if chips else (mats, flags)
+
+    def track_configure_upright(self, enable: bool = True):
+        check(self._lib.sdm_track_configure_upright(self._h, 1 if enable else 0))
+        self.track_upright = bool(enable)
+
+    def track_start_rolled(self, ids, boxes: np.ndarray, roll_deg):
+        i = self._ids(ids)
+        b = np.ascontiguousarray(boxes, np.int32).reshape(-1, 4)
+        if b.shape[0] != i.size:
+            raise ValueError("one face box (x, y, w, h) per stream id expected")
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(roll_deg, np.float32).reshape(-1), (i.size,)), np.float32)
+        check(self._lib.sdm_track_start_rolled(self._h, i.ctypes.data, b.ctypes.data, r.ctypes.data, i.size))
 
     # -- aligned face crops (csrc/sdm_align.hip) -------------------------------------------------------
     def align_set_source(self, source=None):
@@ -1339,15 +1388,48 @@ class detection_model:
         hog = HogTransform([image], self.hog_params, self.landmark_ids, self.right_eye_ids, self.left_eye_ids)
         return self.optimised_model.predict(np.atleast_2d(init), None, hog)[0]
 
-    def detect_batch(self, images, faceboxes: np.ndarray, img_index: Optional[np.ndarray] = None) -> np.ndarray:
+    def detect_batch(self, images, faceboxes: np.ndarray, img_index: Optional[np.ndarray] = None, roll=None, chip: Optional[int] = None,
+                     guard: Optional[int] = None) -> np.ndarray:
         """Batched ``detect``: row i starts from align_mean(mean, faceboxes[i]) on image img_index[i].  ``images``: host images, or
         frames on the device as ``Context.set_frames_device`` takes them (gray, "bgr" / "bgra" tensors of any size and row stride;
-        (ptr, w, h, stride, format) tuples for the other formats) -- those are not downloaded."""
+        (ptr, w, h, stride, format) tuples for the other formats) -- those are not downloaded.
+        ``roll`` (degrees, clockwise positive; one value or one per row) selects the upright path for rolled faces: every face is cut
+        upright from its frame as a ``chip`` x ``chip`` image on the device, the cascade runs on the chips and the landmarks come
+        back in frame coordinates (include/sdm.h, "Rolled faces").  ``chip`` defaults to the smallest multiple of 32 that is
+        >= 1.75 x the largest box side, ``guard`` to ``chip // 8``; ``upright_info()`` returns the matrices and flags."""
+        if roll is not None:
+            return self._detect_batch_upright(images, faceboxes, img_index, roll, chip, guard)
+        if chip is not None or guard is not None:
+            raise ValueError("chip and guard go with roll")
         from .synth import align_mean
         init = np.stack([align_mean(self.mean, tuple(int(v) for v in b)) for b in np.asarray(faceboxes)])
         hog = HogTransform(images, self.hog_params, self.landmark_ids, self.right_eye_ids, self.left_eye_ids,
                            img_index)
         return self.optimised_model.test(init, None, hog)
+
+    @staticmethod
+    def default_chip(faceboxes) -> int:
+        """The smallest multiple of 32 that is >= 1.75 x the largest box side (at least 32)."""
+        side = int(np.asarray(faceboxes).reshape(-1, 4)[:, 2:].max())
+        return max(32, -(-(7 * side) // (4 * 32)) * 32)
+
+    def _detect_batch_upright(self, images, faceboxes, img_index, roll, chip, guard):
+        opt = self.optimised_model
+        boxes = np.asarray(faceboxes).reshape(-1, 4)
+        chip = self.default_chip(boxes) if chip is None else int(chip)
+        guard = chip // 8 if guard is None else int(guard)
+        hog = HogTransform(images, self.hog_params, self.landmark_ids, self.right_eye_ids, self.left_eye_ids, img_index)
+        opt._bind(hog, boxes.shape[0])
+        opt._load_regressors()
+        c = opt.ctx
+        c.set_templates(None)
+        c.upright_configure(chip, guard)
+        return c.detect_batch_upright(self.mean, boxes, roll)
+
+    def upright_info(self):
+        """(M n x 2 x 3, chip -> frame; flags n: SDM_UPRIGHT_PARTIAL / SDM_UPRIGHT_NEAR_EDGE bits) of the last upright detect or
+        tracker step."""
+        return self.optimised_model.ctx.upright_get()
 
     def estimate_pose(self, pose_model: SupervisedDescentOptimiser, projection: ModelProjection, landmark_ids: Sequence[str],
                       focal: Optional[float] = None, initialisation=None) -> np.ndarray:
@@ -1373,13 +1455,17 @@ class detection_model:
         c.pose_test(0, len(pose_model.regressors))
         return c.pose_get_x()
 
-    def tracker(self, capacity: int, init: str = "realign", min_size: float = 8.0, max_scale_change: float = 1.5) -> "Tracker":
+    def tracker(self, capacity: int, init: str = "realign", min_size: float = 8.0, max_scale_change: float = 1.5,
+                chip: Optional[int] = None, guard: Optional[int] = None) -> "Tracker":
         """Multi-stream tracking on the optimiser's context: ``capacity`` stream slots whose landmarks stay on the device from
         frame to frame (see :class:`Tracker`).  ``init``: how a tracked stream's next frame starts -- "previous" (its landmarks,
         the reference's ``detect(image, initialisation)``) or "realign" (the mean shape in their enclosing box).  A stream is
         lost when its result is not finite, its enclosing box is smaller than ``min_size`` pixels, the box centre leaves the
-        image, or its inter-eye distance changes by more than the factor ``max_scale_change`` in one step (0: no such rule)."""
-        return Tracker(self, capacity, init, min_size, max_scale_change)
+        image, or its inter-eye distance changes by more than the factor ``max_scale_change`` in one step (0: no such rule).
+        ``init="upright"`` follows rolled faces: every step cuts each stream's face upright as a ``chip`` x ``chip`` image (the roll
+        from the stream's own previous eye line), realigns in the chip, runs the cascade there and maps the result back; ``chip``
+        (required) and ``guard`` (default ``chip // 8``) as for ``detect_batch(roll=...)``."""
+        return Tracker(self, capacity, init, min_size, max_scale_change, chip, guard)
 
     def aligned_crops(self, size, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
                       margin: float = 0.2, source=None, out=None):
@@ -1476,12 +1562,20 @@ class Tracker:
     _MODES = {"previous": _lib.SDM_TRACK_INIT_PREVIOUS, "realign": _lib.SDM_TRACK_INIT_REALIGN}
 
     def __init__(self, model: detection_model, capacity: int, init: str = "realign", min_size: float = 8.0,
-                 max_scale_change: float = 1.5):
-        if init not in self._MODES:
-            raise ValueError('init must be "previous" or "realign"')
+                 max_scale_change: float = 1.5, chip: Optional[int] = None, guard: Optional[int] = None):
+        if init not in self._MODES and init != "upright":
+            raise ValueError('init must be "previous", "realign" or "upright"')
+        if init == "upright" and chip is None:
+            raise ValueError('init="upright" needs the chip size')
+        if init != "upright" and (chip is not None or guard is not None):
+            raise ValueError('chip and guard go with init="upright"')
         self.model, self.capacity, self.init = model, int(capacity), init
         self._bind()
-        self.ctx.track_configure(self.capacity, model.mean, self._MODES[init], min_size, max_scale_change)
+        self.ctx.track_configure(self.capacity, model.mean, self._MODES.get(init, _lib.SDM_TRACK_INIT_REALIGN), min_size, max_scale_change)
+        if init == "upright":
+            self.ctx.upright_configure(int(chip), int(chip) // 8 if guard is None else int(guard))
+        if init == "upright" or getattr(self.ctx, "track_upright", False):      # (off again for a plain tracker on the same context)
+            self.ctx.track_configure_upright(init == "upright")
 
     @property
     def ctx(self) -> Context:
@@ -1495,9 +1589,13 @@ class Tracker:
         self.ctx.set_model_geometry(len(m.landmark_ids), norm.right_eye, norm.left_eye, m.hog_params)
         opt._load_regressors()
 
-    def start(self, ids, boxes):
-        """(Re)start streams from face boxes (n x (x, y, w, h)), live or lost."""
-        self.ctx.track_start(ids, boxes)
+    def start(self, ids, boxes, roll=None):
+        """(Re)start streams from face boxes (n x (x, y, w, h)), live or lost.  ``roll`` (degrees, one value or one per stream;
+        ``init="upright"`` only): the roll of the faces in their boxes."""
+        if roll is None:
+            self.ctx.track_start(ids, boxes)
+        else:
+            self.ctx.track_start_rolled(ids, boxes, roll)
 
     def stop(self, ids):
         self.ctx.track_stop(ids)

@@ -287,6 +287,31 @@ public:
         return optimised_model.test(init, cv::Mat(), hog);
     }
 
+    /** Batched detect of ROLLED faces (include/sdm.h, "Rolled faces"): row i's face, in faceboxes[i] with a roll of rolls[i] degrees
+     *  (clockwise positive on screen), is cut upright from its image as a chip x chip gray image on the device, the cascade runs on
+     *  the chips and the landmarks come back in image coordinates.  guard: the NEAR_EDGE band in chip pixels.  Returns N x 2L;
+     *  upright_matrices() (N x 6, chip -> image) and upright_flags() (SDM_UPRIGHT_* bits) describe the call. */
+    cv::Mat detect_batch_upright(const std::vector<cv::Mat>& images, const std::vector<cv::Rect>& faceboxes, const std::vector<float>& rolls,
+                                 int chip, int guard, const std::vector<int>& image_index = {})
+    {
+        superviseddescent::hip::Handle h(superviseddescent::hip::device());
+        rcr::detail::configure(h, images, hog_params, landmark_ids, right_eye_ids, left_eye_ids, true);
+        return upright_on(h, faceboxes, rolls, chip, guard, image_index);
+    }
+
+    /** The same on frames that are already on the device. */
+    cv::Mat detect_batch_upright(const std::vector<DeviceFrame>& frames, const std::vector<cv::Rect>& faceboxes, const std::vector<float>& rolls,
+                                 int chip, int guard, const std::vector<int>& image_index = {})
+    {
+        superviseddescent::hip::Handle h(superviseddescent::hip::device());
+        rcr::detail::configure(h, {}, hog_params, landmark_ids, right_eye_ids, left_eye_ids, false);
+        rcr::detail::set_device_frames(h, frames);
+        return upright_on(h, faceboxes, rolls, chip, guard, image_index);
+    }
+
+    const cv::Mat& upright_matrices() const { return last_upright_matrices; }
+    const std::vector<int>& upright_flags() const { return last_upright_flags; }
+
     cv::Mat get_mean() { return mean; }
     const std::vector<std::string>& get_landmark_ids() const { return landmark_ids; }
     const std::vector<rcr::HoGParam>& get_hog_params() const { return hog_params; }
@@ -301,6 +326,39 @@ public:
     }
 
 private:
+    // regressors, index, chip size -> sdm_detect_batch_upright on a handle whose geometry and images are set
+    cv::Mat upright_on(superviseddescent::hip::Handle& h, const std::vector<cv::Rect>& faceboxes, const std::vector<float>& rolls, int chip,
+                       int guard, const std::vector<int>& image_index)
+    {
+        using superviseddescent::hip::check;
+        sdm_ctx* c = h.get();
+        const int n = (int)faceboxes.size(), M = 2 * (int)landmark_ids.size();
+        if (rolls.size() != faceboxes.size()) throw std::runtime_error("detect_batch_upright: one roll per face box expected");
+        auto& regressors = optimised_model.get_regressors();
+        if (regressors.size() != hog_params.size()) throw std::runtime_error("detect_batch_upright: one regressor per HoGParam expected");
+        for (size_t level = 0; level < regressors.size(); ++level) {
+            cv::Mat R = regressors[level].x.isContinuous() ? regressors[level].x : regressors[level].x.clone();
+            if (R.empty() || R.rows != sdm_feature_dim(c, (int)level) || R.cols != M)
+                throw std::runtime_error("detect_batch_upright: the regressor of level " + std::to_string(level) + " does not match the HOG geometry");
+            check(sdm_set_regressor(c, (int)level, R.ptr<float>(0)), "sdm_set_regressor");
+        }
+        cv::Mat m = mean.isContinuous() ? mean : mean.clone();
+        if ((int)m.total() != M) throw std::runtime_error("detect_batch_upright: the mean must hold 2L coordinates");
+        if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+        else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+        check(sdm_upright_configure(c, chip, guard), "sdm_upright_configure");
+        std::vector<int> b;
+        for (const auto& r : faceboxes) { b.push_back(r.x); b.push_back(r.y); b.push_back(r.width); b.push_back(r.height); }
+        cv::Mat x(n > 0 ? n : 1, M, CV_32FC1);
+        check(sdm_detect_batch_upright(c, m.ptr<float>(0), b.data(), rolls.data(), n, x.ptr<float>(0)), "sdm_detect_batch_upright");
+        last_upright_matrices = cv::Mat(n, 6, CV_32FC1);
+        last_upright_flags.assign((size_t)n, 0);
+        check(sdm_upright_get(c, last_upright_matrices.ptr<float>(0), last_upright_flags.data(), nullptr), "sdm_upright_get");
+        return x;
+    }
+
+    cv::Mat last_upright_matrices;
+    std::vector<int> last_upright_flags;
     model_type optimised_model;
     cv::Mat mean;
     std::vector<rcr::HoGParam> hog_params;

@@ -7,6 +7,10 @@
 //     tr.start({0, 1}, {box_a, box_b});                 // boxes from a face detector
 //     auto lms = tr.step({0, 1}, {frame, frame});       // two faces in one frame: two streams on the same image
 //     if (tr.lost()[1]) tr.start({1}, {new_box});       // have_face = false -> detector -> restart
+//
+// Rolled faces (phone video, ceiling cameras, tilted heads): tr.upright(288) makes every step cut each stream's face upright as a
+// 288 x 288 chip -- the roll from the stream's own previous eye line --, run the cascade there and map the result back
+// (include/sdm.h, "Rolled faces"); tr.start(ids, boxes, rolls) starts streams whose faces are rolled in their boxes.
 #pragma once
 
 #ifndef RCR_TRACKER_HPP_
@@ -55,6 +59,24 @@ public:
         std::vector<int> b;
         for (const auto& r : boxes) { b.push_back(r.x); b.push_back(r.y); b.push_back(r.width); b.push_back(r.height); }
         superviseddescent::hip::check(sdm_track_start(handle.get(), ids.data(), b.data(), (int)ids.size()), "sdm_track_start");
+    }
+
+    /** Upright mode for rolled faces: chip x chip pixels per face, guard = the NEAR_EDGE band (default chip / 8).  chip == 0: off. */
+    void upright(int chip, int guard = -1)
+    {
+        using superviseddescent::hip::check;
+        if (chip == 0) { check(sdm_track_configure_upright(handle.get(), 0), "sdm_track_configure_upright"); return; }
+        check(sdm_upright_configure(handle.get(), chip, guard < 0 ? chip / 8 : guard), "sdm_upright_configure");
+        check(sdm_track_configure_upright(handle.get(), 1), "sdm_track_configure_upright");
+    }
+
+    /** (Re)start streams whose faces are rolled by rolls[i] degrees (clockwise positive) in their boxes; upright mode only. */
+    void start(const std::vector<int>& ids, const std::vector<cv::Rect>& boxes, const std::vector<float>& rolls)
+    {
+        if (ids.size() != boxes.size() || ids.size() != rolls.size()) throw std::runtime_error("tracker::start: one box and one roll per stream id expected");
+        std::vector<int> b;
+        for (const auto& r : boxes) { b.push_back(r.x); b.push_back(r.y); b.push_back(r.width); b.push_back(r.height); }
+        superviseddescent::hip::check(sdm_track_start_rolled(handle.get(), ids.data(), b.data(), rolls.data(), (int)ids.size()), "sdm_track_start_rolled");
     }
 
     void stop(const std::vector<int>& ids)
