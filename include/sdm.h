@@ -680,6 +680,66 @@ int sdm_align_crops_tensor_filtered(sdm_ctx* ctx, const int* landmark_index, con
                                     int out_height, const sdm_align_tensor* spec, const sdm_align_filter* filter, void* out_dev,
                                     float* matrices_host, int* flags_host, int* samples_host);
 
+/* Warped faces: the piecewise-affine warp of every current row onto a template shape (the shape-normalised texture of AAM / CLNF
+ * pipelines).  The crops above are rigid: one similarity per face, so the landmarks still sit somewhere else in every crop.  Here the
+ * template is triangulated over K landmarks and every triangle carries its own affine map, so that every landmark lands on its template
+ * point.  Two launches for all rows (the triangles' matrices, the pixels), written as sdm_align_crops_tensor writes its tensor.
+ *   mesh     K landmark indices, K template points q_k (crop pixel coordinates, float32), T triangles -- triples (a, b, c) of positions
+ *            0 .. K - 1 --, an output size out_width x out_height.  Triangles may overlap, and need not cover the template's hull.
+ *   D        of a triangle, in double on the float32 template points, every operation rounded, nothing contracted (this holds for every
+ *            expression of this block): u = q_b - q_a, v = q_c - q_a, D = u.x v.y - u.y v.x.  A triangle with D > 0 is called
+ *            counter-clockwise here (image coordinates: x right, y down).
+ *   labels   out_height x out_width bytes, a function of the mesh alone; the host computes them once, in sdm_warp_set_mesh.  A triangle
+ *            with D < 0 has b and c exchanged first (for the labels only).  With x = (double)j, y = (double)i the edge functions are
+ *              e0 = (b.x - a.x) (y - a.y) - (b.y - a.y) (x - a.x)
+ *              e1 = (c.x - b.x) (y - b.y) - (c.y - b.y) (x - b.x)
+ *              e2 = (a.x - c.x) (y - c.y) - (a.y - c.y) (x - c.x)
+ *            (two differences, two products, one difference each) and pixel (column j, row i) takes the lowest-numbered triangle t with
+ *            e0 >= 0, e1 >= 0 and e2 >= 0 -- also on an edge two triangles share --, or 255 when there is none.
+ *   G        per triangle, on the host: G00 = v.y / D, G01 = -v.x / D, G10 = -u.y / D, G11 = u.x / D; q_a is kept beside it.
+ *   A_t      per row n and triangle t, from the row's landmarks p_k = (x[idx_k], x[L + idx_k]), in double:
+ *              E00 = p_b.x - p_a.x, E01 = p_c.x - p_a.x, E10 = p_b.y - p_a.y, E11 = p_c.y - p_a.y
+ *              L_rc = E_r0 G_0c + E_r1 G_1c                    (both products and the sum rounded)
+ *              t_r  = p_a[r] - (L_r0 q_a.x + L_r1 q_a.y)       (both products, the sum and the difference rounded)
+ *            A_t = (L00, L01, t_0, L10, L11, t_1), each rounded once to float32: M00 M01 M02 M10 M11 M12 of sdm_align_crops, crop -> source.
+ *   pixel    (column j, row i) with label t: sx = (A_t00 j + A_t01 i) + A_t02, sy = (A_t10 j + A_t11 i) + A_t12 in float32, every operation
+ *            rounded; from that position on it is items 1 to 5 of sdm_align_crops_tensor, unchanged: the 1/32-pixel quantisation, the taps,
+ *            the weights, (... + 512) >> 10, the 2^20 rule, the source formats, the channel rules, the element, the layout.  A pixel with
+ *            label 255 takes the elements of v = 0 (bias[c] for the float dtypes) and reads no source byte.  Sampling is plain bilinear:
+ *            the area filter of sdm_align_crops_tensor_filtered does not apply here.
+ *   flags    per row:
+ *            SDM_WARP_DEGENERATE  one of the mesh's K landmarks is not finite: every element is that of v = 0, every matrix of the row is
+ *                                 six NaNs, and no other bit is evaluated.
+ *            SDM_WARP_PARTIAL     one of the K landmarks lies outside [0, W - 1] x [0, H - 1] of the row's image, compared in float32
+ *                                 (informational).
+ *            SDM_WARP_FOLDED      for some triangle det(E) = E00 E11 - E01 E10 (double, each operation rounded) is 0 or has the sign
+ *                                 opposite to D's: the fitted shape folds over there (informational; the pixels follow the formula).
+ *   source   what sdm_align_crops_tensor reads: the sdm_align_set_source_frames list, else the sdm_align_set_source stack, else the
+ *            context's images; the same row -> image mapping and the same size rule.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched -- sdm_warp_set_mesh: no geometry, K outside [3, L], an index out of
+ * range or repeated, a template point that is not finite, T outside [1, 254], a triangle position outside 0 .. K - 1 or repeated within
+ * its triangle, D == 0 or not finite, out_width or out_height outside [1, 1024].  sdm_warp_crops_tensor: no mesh (none set, or
+ * sdm_set_model_geometry has changed L since), no current rows, and everything sdm_align_crops_tensor refuses of spec, out_dev and the source.
+ * The mesh stays in the context until the next sdm_warp_set_mesh or sdm_destroy. */
+#define SDM_WARP_DEGENERATE 1
+#define SDM_WARP_PARTIAL 2
+#define SDM_WARP_FOLDED 4
+#define SDM_WARP_NO_TRIANGLE 255   /* label of a pixel no triangle covers */
+/* The Delaunay triangulation of K points (xy: K x 2 float32), host only, no context: the default mesh of the layers above.  triangles
+ * receives n_triangles triples of point positions, every one counter-clockwise (D > 0) -- none has zero area.  The same input always gives
+ * the same output; of cocircular points any valid choice may come out (an in-circle determinant within 1e-12 of its terms' magnitude
+ * counts as zero).  SDM_ERR_INVALID: K < 3 or > 255, a point not finite or given twice, all points on one line, capacity (in triangles;
+ * 2K - 5 always suffice) too small. */
+int sdm_warp_delaunay(const float* xy, int K, int* triangles, int capacity, int* n_triangles);
+int sdm_warp_set_mesh(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, const int* triangles, int T,
+                      int out_width, int out_height);
+/* the label map of the mesh: out_height x out_width bytes, dense (SDM_ERR_INVALID without a mesh) */
+int sdm_warp_get_labels(sdm_ctx* ctx, uint8_t* labels_host);
+/* One call for all N current rows.  out_dev: device memory, N * channels * out_height * out_width elements, 16-byte aligned;
+ * matrices_host (N x T x 6) and flags_host (N) may be NULL; they come back in one copy, behind one synchronise.  Neither the landmark
+ * state, the images, the crop source nor the tracker's slots are changed. */
+int sdm_warp_crops_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, void* out_dev, float* matrices_host, int* flags_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,7 @@ EXPORTED = [
     "sdm_train_level_sweep", "sdm_sweep_get_regressor",
     "sdm_set_frames_device", "sdm_debug_download_image",
     "sdm_upright_configure", "sdm_detect_batch_upright", "sdm_upright_get", "sdm_track_configure_upright", "sdm_track_start_rolled",
+    "sdm_warp_delaunay", "sdm_warp_set_mesh", "sdm_warp_get_labels", "sdm_warp_crops_tensor",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -61,6 +62,10 @@ ALIGN_ORDERS = {"bgr": SDM_ALIGN_ORDER_BGR, "rgb": SDM_ALIGN_ORDER_RGB}
 # area-averaged sampling of minified rows (include/sdm.h, sdm_align_crops_tensor_filtered)
 SDM_ALIGN_FILTER_BILINEAR, SDM_ALIGN_FILTER_AREA = 0, 1
 ALIGN_FILTERS = {"bilinear": SDM_ALIGN_FILTER_BILINEAR, "area": SDM_ALIGN_FILTER_AREA}
+
+# piecewise-affine warped faces (include/sdm.h, "Warped faces")
+SDM_WARP_DEGENERATE, SDM_WARP_PARTIAL, SDM_WARP_FOLDED = 1, 2, 4
+SDM_WARP_NO_TRIANGLE = 255
 
 # frames on the device (include/sdm.h, sdm_set_frames_device)
 SDM_FRAME_GRAY, SDM_FRAME_BGR, SDM_FRAME_RGB, SDM_FRAME_BGRA, SDM_FRAME_RGBA, SDM_FRAME_NV12 = range(6)
@@ -412,6 +417,10 @@ def lib() -> ctypes.CDLL:
             "sdm_upright_get": [c_void_p, c_void_p, c_void_p, c_void_p],
             "sdm_track_configure_upright": [c_void_p, c_int],
             "sdm_track_start_rolled": [c_void_p, c_void_p, c_void_p, c_void_p, c_int],
+            "sdm_warp_delaunay": [c_void_p, c_int, c_void_p, c_int, c_int_p],
+            "sdm_warp_set_mesh": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int],
+            "sdm_warp_get_labels": [c_void_p, c_void_p],
+            "sdm_warp_crops_tensor": [c_void_p, ctypes.POINTER(SdmAlignTensor), c_void_p, c_void_p, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)
@@ -426,3 +435,15 @@ def check(rc: int) -> int:
     if rc < 0:
         raise SdmError(rc, lib().sdm_last_error().decode("utf-8", "replace"))
     return rc
+
+
+def delaunay(xy):
+    """The Delaunay triangulation of K x 2 points (sdm_warp_delaunay; host code of the library, no device needed): T x 3 int32 positions
+    into ``xy``, every triangle counter-clockwise in the header's sense (D > 0), the same output for the same input."""
+    import numpy as np
+    p = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    k = p.shape[0]
+    tri = np.empty((max(2 * k, 1), 3), np.int32)
+    n = ctypes.c_int(0)
+    check(lib().sdm_warp_delaunay(p.ctypes.data, k, tri.ctypes.data, tri.shape[0], ctypes.byref(n)))
+    return tri[:n.value].copy()

@@ -42,7 +42,39 @@ static int align_check_call(sdm_ctx* c, const int* lm, const float* tmpl, int K,
     return SDM_OK;
 }
 
-static int align_check_rows(sdm_ctx* c)
+// what sdm_align_crops_tensor refuses of its specification and of its output (sdm_warp_crops_tensor refuses the same)
+int sdm_capi::align_check_spec(const sdm_align_tensor* spec)
+{
+    if (!spec) return fail(SDM_ERR_INVALID, "no tensor specification");
+    if (spec->dtype != SDM_ALIGN_U8 && spec->dtype != SDM_ALIGN_F16 && spec->dtype != SDM_ALIGN_F32) return fail(SDM_ERR_INVALID, "unknown dtype");
+    if (spec->layout != SDM_ALIGN_NHWC && spec->layout != SDM_ALIGN_NCHW) return fail(SDM_ERR_INVALID, "unknown layout");
+    if (spec->order != SDM_ALIGN_ORDER_BGR && spec->order != SDM_ALIGN_ORDER_RGB) return fail(SDM_ERR_INVALID, "unknown channel order");
+    if (spec->channels != 1 && spec->channels != 3) return fail(SDM_ERR_INVALID, "channels must be 1 or 3");
+    if (spec->gray_shift != 14 && spec->gray_shift != 15) return fail(SDM_ERR_INVALID, "gray_shift must be 14 (OpenCV 2.4 - 3.x) or 15");
+    if (spec->dtype != SDM_ALIGN_U8)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(spec->scale[k]) || !std::isfinite(spec->bias[k])) return fail(SDM_ERR_INVALID, "a scale or bias is not finite");
+    return SDM_OK;
+}
+
+int sdm_capi::align_check_out(const void* out_dev)
+{
+    if (!out_dev) return fail(SDM_ERR_INVALID, "no output");
+    if ((uintptr_t)out_dev % 16 != 0) return fail(SDM_ERR_INVALID, "the output must be 16-byte aligned");
+    return SDM_OK;
+}
+
+AlignTensorDev sdm_capi::align_tensor_dev(const sdm_align_tensor* spec)
+{
+    AlignTensorDev t{};
+    for (int k = 0; k < 3; ++k) { t.scale[k] = spec->scale[k]; t.bias[k] = spec->bias[k]; }
+    t.order = spec->order; t.gray_shift = spec->gray_shift;
+    if (spec->gray_shift == 14) { t.wb = 1868; t.wg = 9617; t.wr = 4899; }        // sdm_upload_images_bgr_u8's two weight sets
+    else { t.wb = 3735; t.wg = 19235; t.wr = 9798; }
+    return t;
+}
+
+int sdm_capi::align_check_rows(sdm_ctx* c)
 {
     const sdm_ctx::Align& a = c->align;
     const int N = c->N;
@@ -115,23 +147,14 @@ static int align_tensor_call(sdm_ctx* c, const int* lm, const float* tmpl, int K
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     int rc;
     if ((rc = align_check_call(c, lm, tmpl, K, out_w, out_h))) return rc;
-    if (!spec) return fail(SDM_ERR_INVALID, "no tensor specification");
-    if (spec->dtype != SDM_ALIGN_U8 && spec->dtype != SDM_ALIGN_F16 && spec->dtype != SDM_ALIGN_F32) return fail(SDM_ERR_INVALID, "unknown dtype");
-    if (spec->layout != SDM_ALIGN_NHWC && spec->layout != SDM_ALIGN_NCHW) return fail(SDM_ERR_INVALID, "unknown layout");
-    if (spec->order != SDM_ALIGN_ORDER_BGR && spec->order != SDM_ALIGN_ORDER_RGB) return fail(SDM_ERR_INVALID, "unknown channel order");
-    if (spec->channels != 1 && spec->channels != 3) return fail(SDM_ERR_INVALID, "channels must be 1 or 3");
-    if (spec->gray_shift != 14 && spec->gray_shift != 15) return fail(SDM_ERR_INVALID, "gray_shift must be 14 (OpenCV 2.4 - 3.x) or 15");
-    if (spec->dtype != SDM_ALIGN_U8)
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(spec->scale[k]) || !std::isfinite(spec->bias[k])) return fail(SDM_ERR_INVALID, "a scale or bias is not finite");
+    if ((rc = align_check_spec(spec))) return rc;
     if (filtered) {
         if (!filter) return fail(SDM_ERR_INVALID, "no filter");
         if (filter->mode != SDM_ALIGN_FILTER_BILINEAR && filter->mode != SDM_ALIGN_FILTER_AREA) return fail(SDM_ERR_INVALID, "unknown filter mode");
         if (filter->max_samples < 1 || filter->max_samples > 16) return fail(SDM_ERR_INVALID, "max_samples must be in [1, 16]");
         if (!std::isfinite(filter->min_scale) || filter->min_scale < 1.0f) return fail(SDM_ERR_INVALID, "min_scale must be finite and >= 1");
     }
-    if (!out_dev) return fail(SDM_ERR_INVALID, "no output");
-    if ((uintptr_t)out_dev % 16 != 0) return fail(SDM_ERR_INVALID, "the output must be 16-byte aligned");
+    if ((rc = align_check_out(out_dev))) return rc;
     if ((rc = align_check_rows(c))) return rc;
     const int N = c->N;
     sdm_ctx::Align& a = c->align;
@@ -139,11 +162,7 @@ static int align_tensor_call(sdm_ctx* c, const int* lm, const float* tmpl, int K
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(filtered ? align_records_with_samples(N) : (size_t)N))) return rc;
     if ((rc = align_fit_rows(c, lm, tmpl, K, out_w, out_h))) return rc;
-    AlignTensorDev t{};
-    for (int k = 0; k < 3; ++k) { t.scale[k] = spec->scale[k]; t.bias[k] = spec->bias[k]; }
-    t.order = spec->order; t.gray_shift = spec->gray_shift;
-    if (spec->gray_shift == 14) { t.wb = 1868; t.wg = 9617; t.wr = 4899; }        // sdm_upload_images_bgr_u8's two weight sets
-    else { t.wb = 3735; t.wg = 19235; t.wr = 9798; }
+    const AlignTensorDev t = align_tensor_dev(spec);
     const int stack_format = !external ? SDM_FRAME_GRAY : a.C == 1 ? SDM_FRAME_GRAY : a.C == 3 ? SDM_FRAME_BGR : SDM_FRAME_BGRA;
     const uint8_t* base = external ? a.base : c->img_base;
     const AlignFrameDev* frames = list ? a.fr_dev.p : nullptr;

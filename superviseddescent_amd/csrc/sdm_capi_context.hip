@@ -80,6 +80,7 @@ void sdm_destroy(sdm_ctx* c)
     c->sweep.release();
     c->frames.release();
     c->upright.release();
+    c->warp.release();
     for (auto& r : c->Rt) r.release();
     for (auto& q : c->plans) { q.lane_tab.release(); q.wb.release(); q.wb16.release(); q.pass_info.release(); q.cut.release(); q.taps.release(); q.pair_taps.release(); }
     if (c->own_stream) e = hipStreamDestroy(c->stream);
@@ -233,6 +234,7 @@ int sdm_set_model_geometry(sdm_ctx* c, int L, const int* re, int nre, const int*
     }
     // ---- commit ----
     c->plans.swap(n_plans);          // (the previous tables leave with plan_guard)
+    if (L != c->L) c->warp.drop();   // (a mesh names landmarks of the geometry it was set under)
     c->L = L; c->M = 2 * L;
     c->eyes = eyes;
     c->levels.swap(n_levels_dev); c->params.swap(n_params); c->fast_kernel.swap(n_fast_kernel); c->fast_bins.swap(n_fast_bins);

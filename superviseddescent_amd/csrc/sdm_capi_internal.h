@@ -7,6 +7,7 @@
 //   sdm_capi_debug.hip     device pointers, timing, debug entry points   sdm_capi_pose.hip / sdm_capi_track.hip  head pose, tracking
 //   sdm_capi_align.hip     aligned face crops                          sdm_capi_sweep.hip     regulariser sweep on one Gram product
 //   sdm_capi_frames.hip    device-resident frames as the image set     sdm_capi_upright.hip   upright chips for rolled faces
+//   sdm_capi_warp.hip      piecewise-affine warped faces
 #pragma once
 #include "../../include/sdm.h"
 #include "sdm_kernels.h"
@@ -321,6 +322,19 @@ struct sdm_ctx {
         DevBuf<double> in;                 // a detect call's (cos, sin) pairs, boxes and mean
         void release() { chips.release(); off.release(); w.release(); h.release(); stride.release(); rows.release(); in.release(); chip = 0; N = 0; }
     } upright;
+    // piecewise-affine warped faces (sdm_capi_warp.hip): the mesh of sdm_warp_set_mesh -- label map, triangle table, landmark indices --
+    // and the per-call records with the N x T x 6 matrices behind them
+    struct Warp {
+        int K = 0, T = 0, L = 0;           // T == 0: no mesh; L: landmarks of the geometry at sdm_warp_set_mesh
+        int out_w = 0, out_h = 0;
+        std::vector<uint8_t> labels_host;  // out_h x out_w
+        DevBuf<uint8_t> labels;
+        DevBuf<unsigned char> tri;         // T WarpTri records (csrc/sdm_warp_device.h)
+        DevBuf<int> lm;                    // K
+        DevBuf<unsigned char> rows;        // N WarpFace records, then N x T x 6 floats
+        void drop() { K = T = L = out_w = out_h = 0; labels_host.clear(); }
+        void release() { drop(); labels.release(); tri.release(); lm.release(); rows.release(); }
+    } warp;
     // host copies of the image sizes and of the sample -> image index (the checks of an external crop source)
     std::vector<int> img_w_host, img_h_host, img_idx_host;
 
@@ -378,6 +392,12 @@ int upright_check(sdm_ctx* c, int n);
 int upright_ensure(sdm_ctx* c, int n);
 int upright_run(sdm_ctx* c, int n);
 int upright_roll_cs(float roll_deg, double* cs);
+// (sdm_capi_align.hip) the checks and the element stage's constants that sdm_align_crops_tensor and sdm_warp_crops_tensor share: the
+// specification, the output pointer, and that the crop source covers every row's image with that image's size
+int align_check_spec(const sdm_align_tensor* spec);
+int align_check_out(const void* out_dev);
+int align_check_rows(sdm_ctx* c);
+AlignTensorDev align_tensor_dev(const sdm_align_tensor* spec);
 int ensure_sample_buffers(sdm_ctx* c, int N);
 int check_sample_index(const sdm_ctx* c);
 bool packed_ok(const sdm_ctx* c, int level);

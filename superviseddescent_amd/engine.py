@@ -779,6 +779,51 @@ class Context:
                                                         mats.ctypes.data, flags.ctypes.data, samples.ctypes.data))
         return out, mats, flags, samples
 
+    # -- piecewise-affine warped faces (csrc/sdm_warp.hip) ---------------------------------------------
+    def warp_set_mesh(self, landmark_index, template: np.ndarray, triangles: np.ndarray, width: int, height: int):
+        """The mesh of ``warp_crops_tensor`` (include/sdm.h, sdm_warp_set_mesh): K landmark indices, their K x 2 template points in crop
+        pixels, T x 3 triangles over the positions 0 .. K - 1 (e.g. ``_lib.delaunay(template)``) and the crop size.  The label map is
+        computed once, here."""
+        idx = np.ascontiguousarray(landmark_index, np.int32).reshape(-1)
+        t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
+        if t.shape[0] != idx.size:
+            raise ValueError("one template point (x, y) per landmark index expected")
+        tri = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        check(self._lib.sdm_warp_set_mesh(self._h, idx.ctypes.data, t.ctypes.data, idx.size, tri.ctypes.data, tri.shape[0], int(width),
+                                          int(height)))
+        self.warp_mesh = (tri.shape[0], int(width), int(height))
+
+    def warp_labels(self) -> np.ndarray:
+        """The mesh's label map, height x width uint8: the triangle every crop pixel belongs to, 255 = none."""
+        _, w, h = getattr(self, "warp_mesh", (0, 0, 0))
+        out = np.empty((h, w), np.uint8)
+        check(self._lib.sdm_warp_get_labels(self._h, out.ctypes.data))
+        return out
+
+    def warp_crops_tensor(self, spec=None, out=None, **options):
+        """The N current rows warped piecewise-affinely onto the mesh's template, as a network's input tensor (include/sdm.h,
+        sdm_warp_crops_tensor), from the source ``align_crops_tensor`` reads.  ``spec`` / ``options`` / ``out``: as for
+        ``align_crops_tensor``.  Returns (tensor N x C x H x W or N x H x W x C, matrices N x T x 2 x 3 float32 crop -> source, one per
+        triangle, flags N int32: SDM_WARP_* bits)."""
+        if spec is None:
+            spec = _lib.align_tensor_spec(**options)
+        elif options:
+            raise ValueError("give either spec or the named options")
+        T, width, height = getattr(self, "warp_mesh", (0, 0, 0))
+        n = int(getattr(self, "N", 0))          # (0: no rows yet -- the library refuses the call)
+        shape = _lib.align_tensor_shape(n, width, height, spec.layout, spec.channels)
+        name = {v: k for k, v in _lib.ALIGN_DTYPES.items()}[spec.dtype]
+        import torch
+        if out is None:
+            out = torch.empty(shape, dtype=getattr(torch, name), device=f"cuda:{self.device}")
+        else:
+            _lib.check_align_out(out, shape, name)
+        mats = np.empty((n, T, 2, 3), np.float32)
+        flags = np.empty(n, np.int32)
+        torch.cuda.current_stream(out.device).synchronize()
+        check(self._lib.sdm_warp_crops_tensor(self._h, ctypes.byref(spec), ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
+        return out, mats, flags
+
     # -- misc ------------------------------------------------------------------------------------------
     def synchronize(self):
         check(self._lib.sdm_synchronize(self._h))
@@ -1530,6 +1575,44 @@ class detection_model:
         finally:
             if frames is not None:
                 c.align_set_source_frames(None)                           # (no pointer to the caller's frames stays behind)
+
+    def warped_crops_tensor(self, size, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
+                            triangles: Optional[np.ndarray] = None, margin: float = 0.1, frames=None, formats=None, chroma=None,
+                            dtype="float16", layout="nchw", channels=3, order="rgb", scale=None, bias=None, mean=None, std=None,
+                            gray_shift=14, out=None):
+        """The faces of the current rows warped piecewise-affinely onto a template shape -- every landmark lands on its template point:
+        the shape-normalised texture -- as a network's input tensor, in two launches from the frames where they lie on the device
+        (include/sdm.h, "Warped faces").  ``size``, ``landmark_ids``, ``frames``, ``formats``, ``chroma``, the tensor options and ``out``: as
+        for :meth:`aligned_crops_tensor`.  ``template``: the K x 2 positions of the landmarks in crop pixels (default:
+        :func:`alignment_template` of the mean with ``margin``).  ``triangles``: T x 3 positions 0 .. K - 1, T <= 254 (default: the
+        Delaunay triangulation of the template; a list of one's own may e.g. leave the mouth's interior out).  Pixels that no triangle
+        covers are 0 before scale and bias; :meth:`warp_mask` tells them apart.  Returns (tensor, matrices N x T x 2 x 3 crop -> source,
+        flags N: SDM_WARP_* bits).  No pointer to the frames stays behind."""
+        c = self.optimised_model.ctx
+        if not getattr(c, "N", 0):
+            raise RuntimeError("run detect_batch or Tracker.step first")
+        spec = _lib.align_tensor_spec(dtype, layout, channels, order, scale, bias, mean, std, gray_shift)
+        width, height = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        ids = self.landmark_ids if landmark_ids is None else [str(i) for i in landmark_ids]
+        missing = [i for i in ids if i not in self.landmark_ids]
+        if missing:
+            raise ValueError(f"landmark ids not in this model: {missing}")
+        idx = [self.landmark_ids.index(i) for i in ids]
+        if template is None:
+            template = alignment_template(self.mean, idx, width, height, margin)
+        if triangles is None:
+            triangles = _lib.delaunay(template)
+        c.warp_set_mesh(idx, template, triangles, width, height)
+        c.align_set_source_frames(frames, formats, chroma)
+        try:
+            return c.warp_crops_tensor(spec=spec, out=out)
+        finally:
+            if frames is not None:
+                c.align_set_source_frames(None)                           # (no pointer to the caller's frames stays behind)
+
+    def warp_mask(self) -> np.ndarray:
+        """height x width bool of the last :meth:`warped_crops_tensor`'s mesh: True where a triangle covers the crop pixel."""
+        return self.optimised_model.ctx.warp_labels() != _lib.SDM_WARP_NO_TRIANGLE
 
     def get_mean(self) -> np.ndarray:
         return self.mean

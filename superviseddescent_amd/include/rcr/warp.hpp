@@ -1,0 +1,137 @@
+// rcr/warp.hpp -- piecewise-affine warped faces from landmarks kept on the device (include/sdm.h, "Warped faces", sdm_warp_*): the
+// template is triangulated over the landmarks and every triangle is mapped by its own affine transform, so every landmark lands on its
+// template point -- the shape-normalised texture that expression, action-unit, liveness and face-swap networks take as input --
+// without copying the landmarks or the frames to the host for an image library.
+//
+//     rcr::tracker tr(model, 64);
+//     auto lms = tr.step(ids, frames);
+//     rcr::WarpMesh mesh = rcr::WarpMesh::of_mean(model.get_mean(), idx, 112, 112);      // default template, Delaunay triangles
+//     auto w = rcr::warped_crops_tensor(tr, mesh, rcr::TensorSpec(), out_dev, device_frames);
+//     // out_dev: rows x 3 x 112 x 112 float16; w.matrices.row(i): stream ids[i]'s T crop -> source maps; w.flags[i]: SDM_WARP_*
+//
+// The rows of detection_model::detect_batch work the same way (the overload taking the frames and the rows).
+#pragma once
+
+#ifndef RCR_WARP_HPP_
+#define RCR_WARP_HPP_
+
+#include "rcr/alignment.hpp"
+
+#include <stdexcept>
+#include <vector>
+
+namespace rcr {
+
+/** The Delaunay triangulation of K x 2 CV_32FC1 points (sdm_warp_delaunay; host code): triples of point positions, counter-clockwise in
+ *  the header's sense, the same for the same input. */
+inline std::vector<int> delaunay(cv::Mat points)
+{
+    if (points.cols != 2 || points.type() != CV_32FC1) throw std::runtime_error("delaunay: K x 2 CV_32FC1 points expected");
+    cv::Mat p = points.isContinuous() ? points : points.clone();
+    std::vector<int> tri((size_t)6 * std::max(p.rows, 1));
+    int n = 0;
+    superviseddescent::hip::check(sdm_warp_delaunay(p.ptr<float>(0), p.rows, tri.data(), 2 * std::max(p.rows, 1), &n), "sdm_warp_delaunay");
+    tri.resize((size_t)3 * n);
+    return tri;
+}
+
+/** The mesh of a warp: K landmark indices, their template points (K x 2 CV_32FC1, crop pixels), triangles over the positions
+ *  0 .. K - 1 (three ints each, at most 254 triangles) and the crop size. */
+struct WarpMesh {
+    std::vector<int> landmark_index;
+    cv::Mat tmpl;
+    std::vector<int> triangles;
+    int width = 0, height = 0;
+
+    int n_triangles() const { return (int)triangles.size() / 3; }
+
+    /** template given, triangles = its Delaunay triangulation (or a list of one's own, e.g. one that leaves the mouth's interior out) */
+    static WarpMesh of_template(const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height, const std::vector<int>& triangles = {})
+    {
+        WarpMesh m;
+        m.landmark_index = landmark_index;
+        m.tmpl = tmpl.isContinuous() ? tmpl : tmpl.clone();
+        m.triangles = triangles.empty() ? delaunay(m.tmpl) : triangles;
+        m.width = width; m.height = height;
+        return m;
+    }
+    /** the default: alignment_template of the mean with `margin`, Delaunay triangles */
+    static WarpMesh of_mean(cv::Mat mean, const std::vector<int>& landmark_index, int width, int height, double margin = 0.1)
+    {
+        return of_template(landmark_index, alignment_template(mean, landmark_index, width, height, margin), width, height);
+    }
+};
+
+struct warped_tensor_result {
+    cv::Mat matrices;              // rows x (6 T) CV_32FC1: per row the T crop -> source maps M00 M01 M02 M10 M11 M12 (NaN for a degenerate row)
+    std::vector<int> flags;        // SDM_WARP_DEGENERATE / SDM_WARP_PARTIAL / SDM_WARP_FOLDED bits
+    cv::Mat labels;                // height x width CV_8UC1: the triangle of every crop pixel, SDM_WARP_NO_TRIANGLE = none
+};
+
+namespace detail {
+
+// the n current rows of the handle `c` warped onto the mesh's template, as a tensor in device memory, from `frames` in place or -- no
+// frames -- from the handle's own images
+inline warped_tensor_result warp_tensor_current_rows(sdm_ctx* c, int n, const WarpMesh& mesh, const std::vector<DeviceFrame>& frames,
+                                                     const std::vector<const void*>& chroma, const TensorSpec& spec, void* out_dev)
+{
+    using superviseddescent::hip::check;
+    if (mesh.tmpl.rows != (int)mesh.landmark_index.size() || mesh.tmpl.cols != 2 || mesh.tmpl.type() != CV_32FC1)
+        throw std::runtime_error("warped_crops_tensor: one template point (x, y) per landmark");
+    if (mesh.triangles.size() % 3 != 0) throw std::runtime_error("warped_crops_tensor: three positions per triangle");
+    if (!chroma.empty() && chroma.size() != frames.size()) throw std::runtime_error("warped_crops_tensor: one chroma pointer (or nullptr) per frame");
+    cv::Mat t = mesh.tmpl.isContinuous() ? mesh.tmpl : mesh.tmpl.clone();
+    check(sdm_warp_set_mesh(c, mesh.landmark_index.data(), t.ptr<float>(0), (int)mesh.landmark_index.size(), mesh.triangles.data(),
+                            mesh.n_triangles(), mesh.width, mesh.height), "sdm_warp_set_mesh");
+    std::vector<sdm_frame> f;
+    for (const auto& d : frames) f.push_back(sdm_frame{d.data, d.width, d.height, d.stride_bytes, d.format});
+    check(sdm_align_set_source_frames(c, f.empty() ? nullptr : f.data(), chroma.empty() ? nullptr : chroma.data(), (int)f.size()),
+          "sdm_align_set_source_frames");
+    sdm_align_tensor s{};
+    s.dtype = spec.dtype; s.layout = spec.layout; s.channels = spec.channels; s.order = spec.order; s.gray_shift = spec.gray_shift;
+    for (int k = 0; k < 3; ++k) { s.scale[k] = spec.scale[k]; s.bias[k] = spec.bias[k]; }
+    warped_tensor_result res;
+    res.matrices = cv::Mat(n, 6 * mesh.n_triangles(), CV_32FC1);
+    res.flags.resize((size_t)n);
+    const int rc = sdm_warp_crops_tensor(c, &s, out_dev, res.matrices.ptr<float>(0), res.flags.data());
+    if (!frames.empty()) sdm_align_set_source_frames(c, nullptr, nullptr, 0);     // (no pointer to the caller's frames stays behind)
+    check(rc, "sdm_warp_crops_tensor");
+    res.labels = cv::Mat(mesh.height, mesh.width, CV_8UC1);
+    check(sdm_warp_get_labels(c, res.labels.ptr<uint8_t>(0)), "sdm_warp_get_labels");
+    return res;
+}
+
+}  // namespace detail
+
+/** The streams of the tracker's last step warped onto the mesh's template, written to `out_dev` (device memory, rows * channels *
+ *  height * width elements of spec.dtype, 16-byte aligned): two launches from `frames` where they lie on the device -- the frames of
+ *  that step, any of the six formats, same sizes, same order -- or, `frames` empty, from the step's gray images. */
+inline warped_tensor_result warped_crops_tensor(tracker& tr, const WarpMesh& mesh, const TensorSpec& spec, void* out_dev,
+                                                const std::vector<DeviceFrame>& frames = {}, const std::vector<const void*>& chroma = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("warped_crops_tensor: step the tracker first");
+    return detail::warp_tensor_current_rows(tr.context(), tr.rows().rows, mesh, frames, chroma, spec, out_dev);
+}
+
+/** The same for landmark rows on device frames, e.g. the result of detection_model::detect_batch(frames, boxes, image_index): row i is
+ *  warped from frames[image_index[i]] (default: frames[i]).  As aligned_crops_tensor's overload of this shape, it works on a handle
+ *  of its own: the frames become its image set and the rows are uploaded. */
+inline warped_tensor_result warped_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                                const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec, void* out_dev,
+                                                const std::vector<const void*>& chroma = {})
+{
+    using superviseddescent::hip::check;
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    sdm_ctx* c = h.get();
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::set_device_frames(h, frames);
+    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
+    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("warped_crops_tensor: rows must hold 2L coordinates");
+    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
+    return detail::warp_tensor_current_rows(c, x.rows, mesh, frames, chroma, spec, out_dev);
+}
+
+}  // namespace rcr
+#endif /* RCR_WARP_HPP_ */
