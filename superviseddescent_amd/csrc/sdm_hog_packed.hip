@@ -250,6 +250,22 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     float* out_row = feat + (long long)s * ldf;
     int* idx_row = idx_out ? idx_out + (long long)s * (1 + 2 * L) : nullptr;
 
+    // ---- CELLS: what depends on (level, pass, lane) only is requested first and arrives under the geometry's arithmetic ------------
+    constexpr bool F16F = TO == 4 && CELL > 0;      // band folds on the 16-bit matrix cores (below)
+    unsigned desc1 = 0;
+    f32x4 wq1[4];
+    i32x4 pinfo1 = {0, 0, 0, 0};
+    f32x2 wsrow = {0.0f, 0.0f};
+    if constexpr (CELLS) {
+        const int pt1 = pass0 + t_first;      // the wave's one pass
+        desc1 = plan.lane_tab[pt1 * 64 + lane];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            wq1[i] = F16F ? ((const f32x4*)(plan.wb16 + ((size_t)pt1 * 64 + lane) * 32))[i] : ((const f32x4*)(plan.wb + ((size_t)pt1 * 64 + lane) * 16))[i];
+        pinfo1 = *(const i32x4*)(plan.pass_info + pt1 * 4);      // wave-uniform, 16 bytes
+        if (CELL > 0) wsrow = (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]};
+    }
+
     // ---- group geometry (wave-uniform; adaptive_vlhog.hpp:123) ----------------------------------------------------------
     const int h = lv.fixed_h > 0 ? lv.fixed_h : uni((int)round((double)lv.rel * ied_of(xr, L, eyes) / 2));
     const bool empty = h <= 0;
@@ -296,7 +312,10 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     // ---- clear the column rows and the histogram slots --------------------------------------------------------------------
     {
         const f32x4 z4 = {0.0f, 0.0f, 0.0f, 0.0f};
-        for (int i = lane; i < (int)(al16(HP_ROWS_BYTES(O)) / 16); i += 64) ((f32x4*)lds)[i] = z4;      // (the histograms are stored before they are added to)
+        constexpr int NZ = (int)((HP_ROWS_BYTES(O) + 15) / 16);      // 16-byte stores at constant offsets, the last trip on its first lanes
+#pragma unroll
+        for (int k = 0; k < (NZ + 63) / 64; ++k)
+            if (64 * k + 63 < NZ || lane < NZ - 64 * k) ((f32x4*)lds)[64 * k + lane] = z4;      // (the histograms are stored before they are added to)
     }
     wave_sync();
     // the per-row table: every lane reads entry y with ONE broadcast LDS read per row (no v_readlane, no scalar decoding);
@@ -317,9 +336,8 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     //  a neighbour, identically -- wrote: no workgroup barrier)
     // 4 orientations, specialised instances: band folds on the 16-bit matrix cores (column sums x 8 and weights x 2^10 as two float16
     // pieces each, all four piece products)
-    constexpr bool F16F = TO == 4 && CELL > 0;
     static_assert(!F16F || CELL * 361 * 8 < 65504, "float16 folds: a band slot's column sum (<= cell x 255 sqrt 2) x 8 must stay a float16 number");      // (column sums carry a factor 8: exact, undone with the weights' 2^10 after the fold)
-    if (SPEC && lane >= 1 && lane < S - 1) wstab[lane - 1] = (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]} * (F16F ? 8.0f : 1.0f);
+    if (SPEC && lane >= 1 && lane < S - 1) wstab[lane - 1] = (CELLS ? wsrow : (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]}) * (F16F ? 8.0f : 1.0f);
     if (!SPEC && S + 2 > 64 && lane < S + 2 - 64) {
         i32x4 last;
 #pragma unroll
@@ -335,7 +353,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     for (int t = t_first; t < npass; ++t) {
         const int pt = pass0 + t;
         // ---- this lane's column in this pass -----------------------------------------------------------------------------
-        const unsigned desc = plan.lane_tab[pt * 64 + lane];
+        const unsigned desc = CELLS ? desc1 : plan.lane_tab[pt * 64 + lane];
         const int slot = (int)(desc & 0xffu), col = (int)((desc >> 8) & 0xffu);
         const bool in_use = (desc >> 17) & 1u;
         const int cs = __builtin_amdgcn_ds_bpermute(col * 4, tab_s);
@@ -373,12 +391,13 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         f32x4 wq[4];      // (F16F: the same sixteen registers hold the float16 pieces, [k-block][piece] x 8 halfs)
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            wq[i] = F16F ? ((const f32x4*)(plan.wb16 + ((size_t)pt * 64 + lane) * 32))[i] : ((const f32x4*)(plan.wb + ((size_t)pt * 64 + lane) * 16))[i];
-        const int* pinfo = plan.pass_info + pt * 4;
+            wq[i] = CELLS ? wq1[i] : (F16F ? ((const f32x4*)(plan.wb16 + ((size_t)pt * 64 + lane) * 32))[i] : ((const f32x4*)(plan.wb + ((size_t)pt * 64 + lane) * 16))[i]);
+        // the pass's four words in registers (one 16-byte load, no load per segment), the lane's segment picked by selects
+        const i32x4 pinfo = CELLS ? pinfo1 : *(const i32x4*)(plan.pass_info + pt * 4);
         const int sg = li < C ? 0 : (li < 2 * C ? 1 : (li < 3 * C ? 2 : 3));
-        const int seg_slot = sg == 0 ? pinfo[0] : (sg == 1 ? pinfo[1] : (sg == 2 ? pinfo[2] : -1));
+        const int seg_slot = sg == 0 ? pinfo.x : (sg == 1 ? pinfo.y : (sg == 2 ? pinfo.z : -1));
         const bool recv = seg_slot >= 0;                                   // (rows 16 mt + 4 lq + e >= 2O are skipped at the store)
-        const int done = pinfo[3];
+        const int done = pinfo.w;
         const int nkp = (done >> 16) & 0xff;          // k-step pairs (8 lanes each) that hold columns in this pass
         // the first pass that touches a patch STORES its cells, a later one (the patch was cut) adds to them: the histogram
         // slots need no clearing, and the uncut patches no read-modify-write
