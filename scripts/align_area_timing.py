@@ -7,9 +7,13 @@ at crop -> source scales of 0.95, 1.95, 3.9 and 7.8 (+-20 degrees, crop centres 
 result records the range of S).  Host clock around a call that ends in the library's own synchronise; per case REPEATS repeats of CALLS calls behind 5 warm-up calls, the median of every
 repeat, and over the repeats their median and their spread (max - min).  Sub-samples per second = 112 112 (sum over the rows of S S) / median.
 
+The piecewise-affine warp (Context.warp_crops_tensor, csrc/sdm_warp.hip) is timed in the same children the way scripts/warp_timing.py sets
+it up: 64 BGR frames of synthetic faces, the RCR-22 template with its Delaunay mesh, the rows on the faces' landmarks.
+
 Every measurement runs in a child process of its own, one after the other.  --parent-tree DIR (a checkout of the parent commit with its
-library built, inside the repository directory) adds children that time the parent's sdm_align_crops_tensor, alternating with this
-tree's: the scale-0.95 comparison "filtered call, all rows S = 1" against "the parent's call" with the parent's own run-to-run spread.
+library built, inside the repository directory) adds children that time the parent's calls, alternating with this tree's.  The result then
+holds, per case, the parent's median and its own run-to-run spread (max - min over all of its repeats), this tree's median, and whether
+this tree stays within the bound "parent's median + parent's spread".
 Writes profiles/align_area_timing.json (or --out)."""
 import argparse
 import json
@@ -26,10 +30,26 @@ SCALES = (0.95, 1.95, 3.9, 7.8)
 MEAN, STD = [123.675, 116.28, 103.53], [58.395, 57.12, 57.375]
 
 
-def child(tree, filtered):
+def timed(fn, calls):
+    """5 warm-up calls, then REPEATS repeats of `calls` calls: the last result and the repeats' medians, median and spread in ms"""
+    for _ in range(5):
+        r = fn()
+    medians = []
+    for _ in range(REPEATS):
+        ts = []
+        for _ in range(calls):
+            t0 = time.perf_counter()
+            fn()                                             # (ends in the library's stream synchronise)
+            ts.append(time.perf_counter() - t0)
+        medians.append(float(np.median(ts)) * 1e3)
+    return r, {"repeat_medians_ms": medians, "median_ms": float(np.median(medians)), "spread_ms": max(medians) - min(medians),
+               "calls_per_repeat": calls}
+
+
+def child(tree):
     sys.path.insert(0, tree)
     import torch
-    from superviseddescent_amd import Context, HoGParam, alignment_template, ibug
+    from superviseddescent_amd import Context, HoGParam, alignment_template, delaunay, ibug, synth
     ids = ibug.RCR22_IDS
     L = len(ids)
     re, le = ibug.eye_indices(ids)
@@ -59,31 +79,32 @@ def child(tree, filtered):
             x[:, L:] = sn[:, None] * q[:, 0] + c[:, None] * q[:, 1] + centre[:, 1:]
             ctx.set_x(x)
             calls = 40 if s <= 2 else 15
-            variants = {"plain": {}}
-            if filtered:
-                variants["area"] = {"filter": "area"}
-                if s < 1.0:
-                    variants["filter_bilinear"] = {"filter": "bilinear"}
+            variants = {"plain": {}, "area": {"filter": "area"}}
+            if s < 1.0:
+                variants["filter_bilinear"] = {"filter": "bilinear"}
             for vname, kw in variants.items():
-                fn = lambda: ctx.align_crops_tensor(lm, tmpl, SIZE, SIZE, out=out, mean=MEAN, std=STD, **kw)
-                for _ in range(5):
-                    r = fn()
-                medians = []
-                for _ in range(REPEATS):
-                    ts = []
-                    for _ in range(calls):
-                        t0 = time.perf_counter()
-                        fn()                                             # (ends in the library's stream synchronise)
-                        ts.append(time.perf_counter() - t0)
-                    medians.append(float(np.median(ts)) * 1e3)
-                e = {"repeat_medians_ms": medians, "median_ms": float(np.median(medians)), "spread_ms": max(medians) - min(medians),
-                     "calls_per_repeat": calls}
+                r, e = timed(lambda: ctx.align_crops_tensor(lm, tmpl, SIZE, SIZE, out=out, mean=MEAN, std=STD, **kw), calls)
                 if vname == "area":
                     S = np.asarray(r[3])
                     e["S_min"], e["S_max"] = int(S.min()), int(S.max())
                     e["sub_samples_per_s"] = float((S.astype(np.float64) ** 2).sum() * SIZE * SIZE / (e["median_ms"] * 1e-3))
                 res["%s scale %g %s" % (name, s, vname)] = e
         ctx.align_set_source_frames(None)
+    # the warp, as scripts/warp_timing.py runs it
+    gray, _, gt68 = synth.make_faces(64, seed=84)
+    sel = np.array([ibug.IBUG68_IDS.index(i) for i in ids] + [68 + ibug.IBUG68_IDS.index(i) for i in ids])
+    colour = np.random.default_rng(85).integers(0, 256, gray.shape + (3,), dtype=np.uint8)
+    colour[..., 1] = gray
+    faces = [torch.from_numpy(c).cuda() for c in colour]
+    idx = np.arange(N) % len(faces)
+    tmpl_warp = alignment_template(ibug.select_mean(ids), lm, SIZE, SIZE, 0.1)
+    ctx.set_frames_device(faces)
+    ctx.set_sample_image_index(idx)
+    ctx.set_x(np.ascontiguousarray(gt68[:, sel], np.float32)[idx] + np.random.default_rng(N).normal(0, 2, (N, 2 * L)).astype(np.float32))
+    ctx.align_set_source_frames(faces)
+    ctx.warp_set_mesh(lm, tmpl_warp, delaunay(tmpl_warp), SIZE, SIZE)
+    res["warp bgr faces"] = timed(lambda: ctx.warp_crops_tensor(out=out, mean=MEAN, std=STD), 40)[1]
+    ctx.align_set_source_frames(None)
     print("RESULT " + json.dumps(res))
 
 
@@ -92,19 +113,18 @@ def main():
     ap.add_argument("--parent-tree", default=None)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_area_timing.json"))
     ap.add_argument("--child", default=None)
-    ap.add_argument("--filtered", type=int, default=1)
     a = ap.parse_args()
     if a.child:
-        return child(a.child, a.filtered)
-    order = [("this", ROOT, 1)]
+        return child(a.child)
+    order = [("this", ROOT)]
     if a.parent_tree:
         p = os.path.abspath(a.parent_tree)
-        order = [("parent", p, 0), ("this", ROOT, 1), ("parent", p, 0), ("this", ROOT, 1), ("parent", p, 0)]
+        order = [("parent", p), ("this", ROOT), ("parent", p), ("this", ROOT), ("parent", p)]
     runs = []
-    for label, tree, filtered in order:
+    for label, tree in order:
         env = dict(os.environ)
         env.pop("SDM_HIP_LIB", None)
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", tree, "--filtered", str(filtered)], capture_output=True,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", tree], capture_output=True,
                            text=True, timeout=900, env=env)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
@@ -114,6 +134,17 @@ def main():
         print(label, "done", flush=True)
     doc = {"rows": N, "crop": "112 x 112 x 3 float16 NCHW", "unit": "ms per call, host clock, the call ends in a stream synchronise",
            "repeats": REPEATS, "runs": runs}
+    if a.parent_tree:
+        doc["against_parent"] = cmp = {}
+        for case in [k for k, v in runs[0]["result"].items() if isinstance(v, dict)]:
+            mine = [m for r in runs if r["tree"] == "this" for m in r["result"][case]["repeat_medians_ms"]]
+            theirs = [m for r in runs if r["tree"] == "parent" for m in r["result"][case]["repeat_medians_ms"]]
+            e = {"parent_median_ms": float(np.median(theirs)), "parent_spread_ms": max(theirs) - min(theirs), "this_median_ms": float(np.median(mine))}
+            e["bound_ms"] = e["parent_median_ms"] + e["parent_spread_ms"]
+            e["within_bound"] = e["this_median_ms"] <= e["bound_ms"]
+            cmp[case] = e
+            print("%-32s parent %8.3f ms  spread %6.3f ms  this %8.3f ms  %s" % (case, e["parent_median_ms"], e["parent_spread_ms"],
+                  e["this_median_ms"], "within" if e["within_bound"] else "EXCEEDS the bound"))
     with open(a.out, "w") as f:
         json.dump(doc, f, indent=1)
     for run in runs:

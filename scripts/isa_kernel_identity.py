@@ -8,6 +8,8 @@ working tree -- to gfx950 assembly with the Makefile's FLAGS plus --cuda-device-
     only on the position in the file: comments, .file / .loc / .ident / .section lines, the function ordinal in local labels,
   * every kernel's .amdhsa_* descriptor block and its register / LDS / scratch entries in the metadata.
 The base is compiled twice first: two compilations of the same source must compare equal, or the comparison means nothing.
+--rename OLD=NEW (repeatable) pairs kernels whose symbol changed: a base kernel whose symbol contains OLD is compared with, and listed
+under, the working tree's one kernel whose symbol contains NEW and carries the same integer template arguments.
 Needs no GPU.  Exit status 0 = identical."""
 import argparse
 import hashlib
@@ -82,6 +84,19 @@ def parse(asm):
     return funcs, desc, meta
 
 
+def renamed(base, new, renames):
+    """the base's (functions, descriptors, metadata) with every kernel symbol that --rename pairs with a kernel of the working tree replaced by it"""
+    ints = lambda n: re.findall(r"Li(\d+)E", n)
+    to = {}
+    for r in renames:
+        old, _, repl = r.partition("=")
+        for n in base[1]:
+            hits = [m for m in new[1] if old in n and repl in m and ints(m) == ints(n)]
+            if len(hits) == 1:
+                to[n] = hits[0]
+    return tuple({to.get(n, n): v for n, v in part.items()} for part in base), to
+
+
 def differences(a, b):
     out = []
     for what, x, y in zip(("function", "descriptor", "metadata"), a, b):
@@ -98,6 +113,7 @@ def main():
     ap.add_argument("--base", default="HEAD", help="git revision to compare against")
     ap.add_argument("--base-src", nargs="+", required=True, help="files of %s at the base revision" % CSRC)
     ap.add_argument("--src", nargs="+", required=True, help="files of %s in the working tree" % CSRC)
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW", help="pair kernels whose symbol changed")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as d:
         base_tree = os.path.join(d, "base")
@@ -112,6 +128,9 @@ def main():
     rev = subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short", args.base], text=True).strip()
     print("base %s: %s        working tree: %s" % (rev, " ".join(args.base_src), " ".join(args.src)))
     unstable = differences(base1, base2)
+    base1, pairs = renamed(base1, new, args.rename)
+    for old, to in sorted(pairs.items()):
+        print("renamed: %s -> %s" % (old, to))
     print("base compiled twice: %s" % ("identical" if not unstable else "DIFFERENT -- the comparison is not stable"))
     diffs = differences(base1, new)
     funcs, desc, meta = new

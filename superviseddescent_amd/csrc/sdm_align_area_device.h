@@ -1,6 +1,6 @@
 // sdm_align_area_device.h -- the per-pixel arithmetic of sdm_align_crops_tensor_filtered (include/sdm.h) where a row minifies: S of a
 // row, the sub-sample offsets, the un-rounded bilinear value q of a sub-sample and the average of S x S of them.  Built on
-// sdm_align_tensor_device.h (quantisation, taps, NV12 conversion), plain C++ behind ALIGN_HD like it: the device code of
+// sdm_align_tensor_device.h (quantisation, the tap sum align_taps, NV12 conversion), plain C++ behind ALIGN_HD like it: the device code of
 // csrc/sdm_align_area.hip and -- compiled for the host, tests/cpp/align_area_host.cpp -- a program that runs under the host sanitizers.
 //
 // Float operations are rounded one by one (no contraction); sums and the average are uint32.
@@ -52,17 +52,14 @@ ALIGN_HD uint32_t align_area_divide(uint32_t x, uint32_t rcp) { return (uint32_t
 // (sum of S S values q <= 255 * 1024 + 512 S S) / (1024 S S): the sum stays below 2^26 + 2^17, the shifted sum below 2^16
 ALIGN_HD uint32_t align_area_average(uint32_t sum, uint32_t n, uint32_t rcp) { return align_area_divide((sum + 512u * n) >> 10, rcp); }
 
-// the NCH un-rounded values q = w00 p00 + w10 p10 + w01 p01 + w11 p11 of the element at q, added to acc
+// the NCH un-rounded values q of the element at q (align_taps), added to acc
 template <int B, int NCH, bool WIDE, uint32_t FILL>
 ALIGN_HD void align_area_add(const uint8_t* p, int w, int h, int stride, const AlignPos& q, uint32_t acc[NCH])
 {
-    uint32_t r0[2], r1[2];
-    align_tap_row<B, WIDE, FILL>(p, w, h, stride, q.x0, q.y0, r0);
-    align_tap_row<B, WIDE, FILL>(p, w, h, stride, q.x0, q.y0 + 1, r1);
-    const uint32_t w00 = (32 - q.fx) * (32 - q.fy), w10 = q.fx * (32 - q.fy), w01 = (32 - q.fx) * q.fy, w11 = q.fx * q.fy;
+    uint32_t v[NCH];
+    align_taps<B, NCH, WIDE, FILL>(p, w, h, stride, q, v);
 #pragma unroll
-    for (int c = 0; c < NCH; ++c)
-        acc[c] += w00 * align_byte(r0, c) + w10 * align_byte(r0, B + c) + w01 * align_byte(r1, c) + w11 * align_byte(r1, B + c);
+    for (int c = 0; c < NCH; ++c) acc[c] += v[c];
 }
 
 // KIND: the source as the taps see it

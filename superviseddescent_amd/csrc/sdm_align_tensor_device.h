@@ -1,7 +1,10 @@
-// sdm_align_tensor_device.h -- the per-pixel arithmetic of sdm_align_crops_tensor (include/sdm.h): positions, taps, the integer
-// bilinear blend, the NV12 conversion, the channel rules and the element formula.  Plain C++ behind one macro, so the same text is
-// the device code of csrc/sdm_align_tensor.hip and -- compiled for the host, tests/cpp/align_tensor_host.cpp -- a program that runs
-// under the host sanitizers on source buffers of exactly the frames' bytes.
+// sdm_align_tensor_device.h -- the per-pixel arithmetic of the crop tensors (include/sdm.h: sdm_align_crops_tensor, its filtered form and
+// sdm_warp_crops_tensor): positions, taps, the integer bilinear blend, the NV12 conversion, the channel rules and the element formula.
+// The one pixel fetch of the three calls is here: align_fetch_segment takes four source positions (the warp's, one matrix per pixel),
+// align_segment forms them from a row's one matrix, and align_taps is the weighted tap sum under both align_bilinear and the area
+// sums of sdm_align_area_device.h.  Plain C++ behind one macro, so the same text is the device code of the kernel frame
+// (csrc/sdm_align_tensor_kernel.h) and -- compiled for the host, tests/cpp/align_tensor_host.cpp -- a program that runs under the host
+// sanitizers on source buffers of exactly the frames' bytes.
 //
 // Every float operation is rounded on its own (no contraction: the pragma below under clang, -ffp-contract=off elsewhere); everything
 // else is int32 / uint32 arithmetic.
@@ -91,9 +94,9 @@ ALIGN_HD void align_tap_row(const uint8_t* p, int w, int h, int stride, int x0, 
     v[0] = a; v[1] = b;
 }
 
-// NCH values of the element at q: (w00 p00 + w10 p10 + w01 p01 + w11 p11 + 512) >> 10 per byte position
+// the NCH un-rounded sums w00 p00 + w10 p10 + w01 p01 + w11 p11 of the element at q, per byte position: at most 255 * 1024
 template <int B, int NCH, bool WIDE, uint32_t FILL>
-ALIGN_HD void align_bilinear(const uint8_t* p, int w, int h, int stride, const AlignPos& q, uint32_t out[NCH])
+ALIGN_HD void align_taps(const uint8_t* p, int w, int h, int stride, const AlignPos& q, uint32_t sum[NCH])
 {
     uint32_t r0[2], r1[2];
     align_tap_row<B, WIDE, FILL>(p, w, h, stride, q.x0, q.y0, r0);
@@ -101,7 +104,16 @@ ALIGN_HD void align_bilinear(const uint8_t* p, int w, int h, int stride, const A
     const uint32_t w00 = (32 - q.fx) * (32 - q.fy), w10 = q.fx * (32 - q.fy), w01 = (32 - q.fx) * q.fy, w11 = q.fx * q.fy;
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
-        out[c] = (w00 * align_byte(r0, c) + w10 * align_byte(r0, B + c) + w01 * align_byte(r1, c) + w11 * align_byte(r1, B + c) + 512u) >> 10;
+        sum[c] = w00 * align_byte(r0, c) + w10 * align_byte(r0, B + c) + w01 * align_byte(r1, c) + w11 * align_byte(r1, B + c);
+}
+
+// NCH values of the element at q: (align_taps + 512) >> 10
+template <int B, int NCH, bool WIDE, uint32_t FILL>
+ALIGN_HD void align_bilinear(const uint8_t* p, int w, int h, int stride, const AlignPos& q, uint32_t out[NCH])
+{
+    align_taps<B, NCH, WIDE, FILL>(p, w, h, stride, q, out);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) out[c] = (out[c] + 512u) >> 10;
 }
 
 ALIGN_HD uint32_t align_clamp255(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
@@ -117,23 +129,17 @@ ALIGN_HD void align_nv12_to_bgr(uint32_t Y, uint32_t U, uint32_t V, uint32_t bgr
     bgr[2] = align_clamp255((y + 1673527 * v + (1 << 19)) >> 20);
 }
 
-// the warped pixel of up to 4 consecutive crop pixels (row i, columns j0 ... j0 + npx - 1) as (B, G, R); a gray source gives (g, g, g).
-// The source format is switched on once, outside the pixel work.
+// the warped pixel of up to 4 crop pixels at the source positions (sx[k], sy[k]) as (B, G, R); a gray source gives (g, g, g).  A pixel with
+// on[k] false is (0, 0, 0) and reads no source byte.  The source format is switched on once, outside the pixel work.  r.m is not used.
 template <bool WIDE>
-ALIGN_HD void align_segment(const AlignRow& r, int i, int j0, int npx, uint32_t px[4][3])
+ALIGN_HD void align_fetch_segment(const AlignRow& r, const float sx[4], const float sy[4], const bool on[4], uint32_t px[4][3])
 {
-    const float fi = (float)i;
-    const float ax = r.m[1] * fi, ay = r.m[4] * fi;
     AlignPos q[4];
     bool ok[4];
-    float sx[4], sy[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float fj = (float)(j0 + k);
-        sx[k] = (r.m[0] * fj + ax) + r.m[2];
-        sy[k] = (r.m[3] * fj + ay) + r.m[5];
         q[k].x0 = q[k].fx = q[k].y0 = q[k].fy = 0;
-        ok[k] = k < npx && align_quantise(sx[k], sy[k], q[k]);
+        ok[k] = on[k] && align_quantise(sx[k], sy[k], q[k]);
         px[k][0] = px[k][1] = px[k][2] = 0u;
     }
     switch (r.format) {
@@ -175,6 +181,25 @@ ALIGN_HD void align_segment(const AlignRow& r, int i, int j0, int npx, uint32_t 
 #pragma unroll
         for (int k = 0; k < 4; ++k) { const uint32_t t = px[k][0]; px[k][0] = px[k][2]; px[k][2] = t; }
     }
+}
+
+// align_fetch_segment for the consecutive crop pixels (row i, columns j0 ... j0 + npx - 1) of a similarity row: the positions through r.m,
+// the products M01 i, M11 i shared
+template <bool WIDE>
+ALIGN_HD void align_segment(const AlignRow& r, int i, int j0, int npx, uint32_t px[4][3])
+{
+    const float fi = (float)i;
+    const float ax = r.m[1] * fi, ay = r.m[4] * fi;
+    float sx[4], sy[4];
+    bool on[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float fj = (float)(j0 + k);
+        sx[k] = (r.m[0] * fj + ax) + r.m[2];
+        sy[k] = (r.m[3] * fj + ay) + r.m[5];
+        on[k] = k < npx;
+    }
+    align_fetch_segment<WIDE>(r, sx, sy, on, px);
 }
 
 // output channel c of CH from a warped (B, G, R); weigh: the source is BGR / RGB / BGRA / RGBA (a gray or luma-only value passes)

@@ -23,22 +23,29 @@ static int align_frame_bpp(int format)
 static int align_check_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h)
 {
     if (c->L <= 0) return fail(SDM_ERR_INVALID, "geometry not set");
-    const int L = c->L, N = c->N;
-    if (N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
+    if (c->N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
     if (!lm || !tmpl) return fail(SDM_ERR_INVALID, "no landmark indices or template");
-    if (K < 2 || K > L) return fail(SDM_ERR_INVALID, "K must be in [2, L]");
+    int rc;
+    if ((rc = check_landmark_subset(c, lm, tmpl, K, 2))) return rc;
+    bool spread = false;
+    for (int k = 1; k < K && !spread; ++k) spread = tmpl[2 * k] != tmpl[0] || tmpl[2 * k + 1] != tmpl[1];
+    if (!spread) return fail(SDM_ERR_INVALID, "the K template points coincide");
+    if (out_w < 1 || out_w > 1024 || out_h < 1 || out_h > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
+    return SDM_OK;
+}
+
+int sdm_capi::check_landmark_subset(const sdm_ctx* c, const int* lm, const float* tmpl, int K, int Kmin)
+{
+    const int L = c->L;
+    if (K < Kmin || K > L) return fail(SDM_ERR_INVALID, "K must be in [" + std::to_string(Kmin) + ", L]");
     std::vector<char> seen(L, 0);
     for (int k = 0; k < K; ++k) {
         if (lm[k] < 0 || lm[k] >= L) return fail(SDM_ERR_INVALID, "landmark index " + std::to_string(lm[k]) + " out of range");
         if (seen[lm[k]]) return fail(SDM_ERR_INVALID, "landmark index " + std::to_string(lm[k]) + " named twice");
         seen[lm[k]] = 1;
     }
-    bool spread = false;
     for (int k = 0; k < 2 * K; ++k)
         if (!std::isfinite(tmpl[k])) return fail(SDM_ERR_INVALID, "a template point is not finite");
-    for (int k = 1; k < K && !spread; ++k) spread = tmpl[2 * k] != tmpl[0] || tmpl[2 * k + 1] != tmpl[1];
-    if (!spread) return fail(SDM_ERR_INVALID, "the K template points coincide");
-    if (out_w < 1 || out_w > 1024 || out_h < 1 || out_h > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
     return SDM_OK;
 }
 
@@ -74,6 +81,27 @@ AlignTensorDev sdm_capi::align_tensor_dev(const sdm_align_tensor* spec)
     return t;
 }
 
+AlignSourceDev sdm_capi::align_source_dev(const sdm_ctx* c)
+{
+    const sdm_ctx::Align& a = c->align;
+    AlignSourceDev src{};
+    if (a.base) {
+        src.ctx.base = nullptr;
+        src.width = a.w; src.height = a.h; src.stride = a.stride;
+    } else {
+        src.ctx = image_set(c);          // (a frame list: sizes from the context's images, which are the frames'; the rest from the table)
+    }
+    return src;
+}
+
+AlignTapSource sdm_capi::align_tap_source(const sdm_ctx* c)
+{
+    const sdm_ctx::Align& a = c->align;
+    const bool external = a.base != nullptr;
+    return {external ? a.base : c->img_base, a.fr.empty() ? nullptr : a.fr_dev.p,
+            !external ? SDM_FRAME_GRAY : a.C == 1 ? SDM_FRAME_GRAY : a.C == 3 ? SDM_FRAME_BGR : SDM_FRAME_BGRA};
+}
+
 int sdm_capi::align_check_rows(sdm_ctx* c)
 {
     const sdm_ctx::Align& a = c->align;
@@ -103,15 +131,8 @@ static int align_fit_rows(sdm_ctx* c, const int* lm, const float* tmpl, int K, i
     memcpy(in.data(), lm, (size_t)K * sizeof(int));
     memcpy(in.data() + K, tmpl, (size_t)2 * K * sizeof(float));
     HIP_TRY(hipMemcpyAsync(a.in.p, in.data(), in.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    AlignSourceDev src{};
-    if (a.base) {
-        src.ctx.base = nullptr;
-        src.width = a.w; src.height = a.h; src.stride = a.stride;
-    } else {
-        src.ctx = image_set(c);          // (a frame list: sizes from the context's images, which are the frames'; the rest from the table)
-    }
-    sdm_launch_align_fit(c->x[c->cur].p, c->N, c->L, a.in.p, (const float*)(a.in.p + K), K, src, c->idx_identity ? nullptr : c->img_idx.p,
-                         out_w, out_h, a.faces.p, c->stream);
+    sdm_launch_align_fit(c->x[c->cur].p, c->N, c->L, a.in.p, (const float*)(a.in.p + K), K, align_source_dev(c),
+                         c->idx_identity ? nullptr : c->img_idx.p, out_w, out_h, a.faces.p, c->stream);
     HIP_TRY(hipGetLastError());
     return SDM_OK;
 }
@@ -158,26 +179,23 @@ static int align_tensor_call(sdm_ctx* c, const int* lm, const float* tmpl, int K
     if ((rc = align_check_rows(c))) return rc;
     const int N = c->N;
     sdm_ctx::Align& a = c->align;
-    const bool external = a.base != nullptr, list = !a.fr.empty();
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(filtered ? align_records_with_samples(N) : (size_t)N))) return rc;
     if ((rc = align_fit_rows(c, lm, tmpl, K, out_w, out_h))) return rc;
     const AlignTensorDev t = align_tensor_dev(spec);
-    const int stack_format = !external ? SDM_FRAME_GRAY : a.C == 1 ? SDM_FRAME_GRAY : a.C == 3 ? SDM_FRAME_BGR : SDM_FRAME_BGRA;
-    const uint8_t* base = external ? a.base : c->img_base;
-    const AlignFrameDev* frames = list ? a.fr_dev.p : nullptr;
+    const AlignTapSource src = align_tap_source(c);
     const int* img_idx = c->idx_identity ? nullptr : c->img_idx.p;
     if (!filtered) {
-        sdm_launch_align_tensor(base, a.faces.p, frames, img_idx, stack_format, N, out_w, out_h, spec->dtype, spec->layout, spec->channels, t,
-                                out_dev, c->stream);
+        sdm_launch_align_tensor(src.base, a.faces.p, src.frames, img_idx, src.stack_format, N, out_w, out_h, spec->dtype, spec->layout,
+                                spec->channels, t, out_dev, c->stream);
         HIP_TRY(hipGetLastError());
         return align_fetch_rows(c, matrices_host, flags_host);
     }
     AlignAreaDev area{};
     area.mode = filter->mode; area.max_samples = filter->max_samples;
     area.min2 = filter->min_scale * filter->min_scale;                              // (float32, rounded once; may be inf: then every S is 1)
-    sdm_launch_align_area(base, a.faces.p, frames, img_idx, stack_format, N, out_w, out_h, spec->dtype, spec->layout, spec->channels, t, area,
-                          (int*)(a.faces.p + N), out_dev, c->stream);
+    sdm_launch_align_area(src.base, a.faces.p, src.frames, img_idx, src.stack_format, N, out_w, out_h, spec->dtype, spec->layout,
+                          spec->channels, t, area, (int*)(a.faces.p + N), out_dev, c->stream);
     HIP_TRY(hipGetLastError());
     return align_fetch_rows(c, matrices_host, flags_host, samples_host);
 }

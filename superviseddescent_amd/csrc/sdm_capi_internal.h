@@ -393,11 +393,18 @@ int upright_ensure(sdm_ctx* c, int n);
 int upright_run(sdm_ctx* c, int n);
 int upright_roll_cs(float roll_deg, double* cs);
 // (sdm_capi_align.hip) the checks and the element stage's constants that sdm_align_crops_tensor and sdm_warp_crops_tensor share: the
-// specification, the output pointer, and that the crop source covers every row's image with that image's size
+// specification, the output pointer, that the crop source covers every row's image with that image's size, the source itself and the
+// landmark subset of a template
 int align_check_spec(const sdm_align_tensor* spec);
 int align_check_out(const void* out_dev);
 int align_check_rows(sdm_ctx* c);
 AlignTensorDev align_tensor_dev(const sdm_align_tensor* spec);
+// the current crop source as the two fits and the tensor kernels read it
+AlignSourceDev align_source_dev(const sdm_ctx* c);
+struct AlignTapSource { const uint8_t* base; const AlignFrameDev* frames; int stack_format; };     // (frames null: stack_format at base + off)
+AlignTapSource align_tap_source(const sdm_ctx* c);
+// K in [Kmin, L], K distinct landmark indices in [0, L), a finite template of K points
+int check_landmark_subset(const sdm_ctx* c, const int* lm, const float* tmpl, int K, int Kmin);
 int ensure_sample_buffers(sdm_ctx* c, int N);
 int check_sample_index(const sdm_ctx* c);
 bool packed_ok(const sdm_ctx* c, int level);

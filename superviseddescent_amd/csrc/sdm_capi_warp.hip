@@ -138,15 +138,8 @@ int sdm_warp_set_mesh(sdm_ctx* c, const int* lm, const float* tmpl, int K, const
     if (c->L <= 0) return fail(SDM_ERR_INVALID, "geometry not set");
     const int L = c->L;
     if (!lm || !tmpl || !triangles) return fail(SDM_ERR_INVALID, "no landmark indices, template or triangles");
-    if (K < 3 || K > L) return fail(SDM_ERR_INVALID, "K must be in [3, L]");
-    std::vector<char> seen(L, 0);
-    for (int k = 0; k < K; ++k) {
-        if (lm[k] < 0 || lm[k] >= L) return fail(SDM_ERR_INVALID, "landmark index " + std::to_string(lm[k]) + " out of range");
-        if (seen[lm[k]]) return fail(SDM_ERR_INVALID, "landmark index " + std::to_string(lm[k]) + " named twice");
-        seen[lm[k]] = 1;
-    }
-    for (int k = 0; k < 2 * K; ++k)
-        if (!std::isfinite(tmpl[k])) return fail(SDM_ERR_INVALID, "a template point is not finite");
+    int rc;
+    if ((rc = check_landmark_subset(c, lm, tmpl, K, 3))) return rc;
     if (T < 1 || T > SDM_WARP_MAX_TRIANGLES) return fail(SDM_ERR_INVALID, "T must be in [1, 254]");
     if (out_w < 1 || out_w > 1024 || out_h < 1 || out_h > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
     std::vector<WarpTri> tab((size_t)T);
@@ -190,7 +183,6 @@ int sdm_warp_set_mesh(sdm_ctx* c, const int* lm, const float* tmpl, int K, const
     sdm_ctx::Warp& w = c->warp;
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));                  // (a warp in flight still reads the previous tables)
-    int rc;
     if ((rc = w.labels.ensure((labels.size() + 3) & ~(size_t)3)) || (rc = w.tri.ensure((size_t)SDM_WARP_MAX_TRIANGLES * sizeof(WarpTri))) ||
         (rc = w.lm.ensure((size_t)L)))
         { w.drop(); return rc; }
@@ -224,25 +216,17 @@ int sdm_warp_crops_tensor(sdm_ctx* c, const sdm_align_tensor* spec, void* out_de
     if (N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
     int rc;
     if ((rc = align_check_spec(spec)) || (rc = align_check_out(out_dev)) || (rc = align_check_rows(c))) return rc;
-    const sdm_ctx::Align& a = c->align;
-    const bool external = a.base != nullptr, list = !a.fr.empty();
     HIP_TRY(hipSetDevice(c->device));
     const size_t rec = (size_t)N * sizeof(WarpFace), bytes = rec + (size_t)N * T * 6 * sizeof(float);
     if ((rc = w.rows.ensure(bytes))) return rc;
     WarpFace* faces = (WarpFace*)w.rows.p;
     float* matrices = (float*)(w.rows.p + rec);
-    AlignSourceDev src{};
-    if (external) {
-        src.ctx.base = nullptr;
-        src.width = a.w; src.height = a.h; src.stride = a.stride;
-    } else {
-        src.ctx = image_set(c);          // (a frame list: sizes from the context's images, which are the frames'; the rest from the table)
-    }
     const int* img_idx = c->idx_identity ? nullptr : c->img_idx.p;
-    sdm_launch_warp_fit(c->x[c->cur].p, N, L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, src, img_idx, faces, matrices, c->stream);
+    sdm_launch_warp_fit(c->x[c->cur].p, N, L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, align_source_dev(c), img_idx, faces, matrices,
+                        c->stream);
     HIP_TRY(hipGetLastError());
-    const int stack_format = !external ? SDM_FRAME_GRAY : a.C == 1 ? SDM_FRAME_GRAY : a.C == 3 ? SDM_FRAME_BGR : SDM_FRAME_BGRA;
-    sdm_launch_warp_tensor(external ? a.base : c->img_base, faces, matrices, T, w.labels.p, list ? a.fr_dev.p : nullptr, img_idx, stack_format,
+    const AlignTapSource src = align_tap_source(c);
+    sdm_launch_warp_tensor(src.base, faces, matrices, T, w.labels.p, src.frames, img_idx, src.stack_format,
                            N, w.out_w, w.out_h, spec->dtype, spec->layout, spec->channels, align_tensor_dev(spec), out_dev, c->stream);
     HIP_TRY(hipGetLastError());
     // the records and the matrices in one copy, one synchronise

@@ -5,14 +5,15 @@
 //                       DEGENERATE, PARTIAL --, then every lane forms its triangle's matrix in double (warp_fit_triangle) and writes
 //                       six floats of the N x T x 6 table; FOLDED and the other bits are ORed across the wave by ballot, and lane 0
 //                       writes the row's record: the flag word does not depend on any execution order, nothing is atomic.
-//   warp_tensor_kernel<DT, LAYOUT, CH>   the shape of align_tensor_kernel: workgroups of face n (blockIdx.x), a lane owns 4 consecutive
-//                       pixels of one crop row, the row's record or frame entry is read once per workgroup.  The workgroup first stages
-//                       its face's T x 6 floats in LDS (records of 6 floats, at most 6 096 bytes); a lane reads its 4 labels (one dword
-//                       when the four lie in the crop row and the address is a multiple of 4, bytes otherwise) and fetches each pixel's
-//                       matrix from LDS by its label -- neighbouring lanes mostly share a triangle, so most reads are broadcasts.  A
-//                       pixel without a triangle reads no source byte.  Stores: store_run, as the crop tensor's.
+//   align_tensor_kernel<WarpMesh, DT, LAYOUT, CH>   the kernel frame of sdm_align_tensor_kernel.h: workgroups of face n (blockIdx.x), a lane
+//                       owns 4 consecutive pixels of one crop row, the row's record or frame entry is read once per workgroup.  The
+//                       workgroup first stages its face's T x 6 floats in LDS (records of 6 floats, at most 6 096 bytes), every lane
+//                       in front of the barrier; a lane reads its 4 labels (one dword when the four lie in the crop row and the address
+//                       is a multiple of 4, bytes otherwise) and fetches each pixel's matrix from LDS by its label -- neighbouring lanes
+//                       mostly share a triangle, so most reads are broadcasts.  A pixel without a triangle reads no source byte.
 //
-// The per-pixel arithmetic is sdm_warp_device.h on top of sdm_align_tensor_device.h (also compiled for the host by tests/cpp/warp_host.cpp).
+// The frame (grid, row source, channel / element stage, stores, dispatch) is sdm_align_tensor_kernel.h; the per-pixel arithmetic is
+// sdm_warp_device.h on top of align_fetch_segment of sdm_align_tensor_device.h (also compiled for the host by tests/cpp/warp_host.cpp).
 #include "sdm_warp.h"
 #include "sdm_align_tensor_kernel.h"
 
@@ -70,104 +71,52 @@ __global__ __launch_bounds__(WARP_FIT_BLOCK) void warp_fit_kernel(const float* _
     }
 }
 
-template <int DT, int LAYOUT, int CH>
-__global__ __launch_bounds__(ALIGN_T_BLOCK) void warp_tensor_kernel(const uint8_t* __restrict__ base, const WarpFace* __restrict__ faces,
-                                                                    const float* __restrict__ matrices, int T,
-                                                                    const uint8_t* __restrict__ labels, const AlignFrameDev* __restrict__ frames,
-                                                                    const int* __restrict__ img_idx, int src_format, int out_w, int out_h,
-                                                                    AlignTensorDev t, void* __restrict__ out)
-{
-    typedef typename AlignElem<DT>::T E;
-    __shared__ float tm[SDM_WARP_MAX_TRIANGLES * WARP_LDS_REC];
-    const int n = blockIdx.x;
+struct WarpMesh {
+    typedef WarpFace Face;
+    struct Args { const float* matrices; int T; const uint8_t* labels; };
+    const float* tm;
     // the face's matrices: T x 6 floats into LDS
-    const float* mrow = matrices + (long long)n * T * 6;
-    for (int e = threadIdx.x; e < T * 6; e += ALIGN_T_BLOCK) {
-        const int tt = e / 6;
-        tm[tt * WARP_LDS_REC + (e - tt * 6)] = mrow[e];
-    }
-    __syncthreads();
-    const int segs = (out_w + 3) >> 2;                               // 4-pixel segments of a crop row
-    const int lane = blockIdx.y * ALIGN_T_BLOCK + threadIdx.x;       // (at most 1024 * 256 segments per face)
-    if (lane >= segs * out_h) return;
-    const int i = lane / segs, j0 = (lane - i * segs) * 4;
-    const int npx = out_w - j0 < 4 ? out_w - j0 : 4;
-    // the row's record: uniform for the workgroup
-    const WarpFace f = faces[n];
-    AlignRow r;
-    r.w = f.w; r.h = f.h;
-    if (frames) {
-        const AlignFrameDev fr = frames[img_idx ? img_idx[n] : n];
-        r.p0 = fr.p0; r.p1 = fr.p1; r.stride = fr.stride; r.cstride = fr.cstride; r.format = fr.format;
-    } else {
-        r.p0 = base + f.off; r.p1 = nullptr; r.stride = f.stride; r.cstride = 0; r.format = src_format;
-    }
-    if (CH == 1 && r.format == SDM_FRAME_NV12) r.format = SDM_FRAME_GRAY;        // Y as it is: the chroma plane is not read
-    const bool weigh = r.format >= SDM_FRAME_BGR && r.format <= SDM_FRAME_RGBA;
-    const bool narrow = (long long)r.h * r.stride <= (long long)INT_MAX &&
-                        (r.format != SDM_FRAME_NV12 || (long long)((r.h + 1) >> 1) * r.cstride <= (long long)INT_MAX);
-    // the 4 labels (out_w * out_h <= 2^20)
-    const int at = i * out_w + j0;
-    uint32_t lab[4];
-    if (npx == 4 && (at & 3) == 0) {
-        const uint32_t v = *(const uint32_t*)(labels + at);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lab[k] = (v >> (8 * k)) & 255u;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) lab[k] = k < npx ? (uint32_t)labels[at + k] : (uint32_t)SDM_WARP_NO_TRIANGLE;
-    }
-    float sx[4], sy[4];
-    bool on[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        on[k] = lab[k] != SDM_WARP_NO_TRIANGLE;
-        sx[k] = sy[k] = 0.0f;
-        if (on[k]) {
-            float m[6];
-#pragma unroll
-            for (int e = 0; e < 6; ++e) m[e] = tm[lab[k] * WARP_LDS_REC + e];
-            warp_position(m, j0 + k, i, sx[k], sy[k]);
+    __device__ __forceinline__ void enter(const Args& a, const WarpFace&, int n, int)
+    {
+        __shared__ float lds[SDM_WARP_MAX_TRIANGLES * WARP_LDS_REC];
+        const float* mrow = a.matrices + (long long)n * a.T * 6;
+        for (int e = threadIdx.x; e < a.T * 6; e += ALIGN_T_BLOCK) {
+            const int tt = e / 6;
+            lds[tt * WARP_LDS_REC + (e - tt * 6)] = mrow[e];
         }
+        __syncthreads();
+        tm = lds;
     }
-    uint32_t px[4][3];
-    if (narrow) warp_segment<false>(r, sx, sy, on, px);
-    else warp_segment<true>(r, sx, sy, on, px);
-
-    if constexpr (LAYOUT == SDM_ALIGN_NCHW) {
+    template <bool WIDE>
+    __device__ __forceinline__ void pixels(const Args& a, const WarpFace&, AlignRow& r, int i, int j0, int npx, int out_w, uint32_t px[4][3])
+    {
+        // the 4 labels (out_w * out_h <= 2^20)
+        const int at = i * out_w + j0;
+        uint32_t lab[4];
+        if (npx == 4 && (at & 3) == 0) {
+            const uint32_t v = *(const uint32_t*)(a.labels + at);
 #pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            E vals[4];
+            for (int k = 0; k < 4; ++k) lab[k] = (v >> (8 * k)) & 255u;
+        } else {
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                vals[k] = make_elem<DT>(align_channel<CH>(px[k], c, weigh, t.order, t.wb, t.wg, t.wr, t.gray_shift), t.scale[c], t.bias[c]);
-            store_run<E, 4>(out, (((long long)n * CH + c) * out_h + i) * out_w + j0, vals, npx);
+            for (int k = 0; k < 4; ++k) lab[k] = k < npx ? (uint32_t)a.labels[at + k] : (uint32_t)SDM_WARP_NO_TRIANGLE;
         }
-    } else {
-        E vals[4 * CH];
+        float sx[4], sy[4];
+        bool on[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < 4; ++k) {
+            on[k] = lab[k] != SDM_WARP_NO_TRIANGLE;
+            sx[k] = sy[k] = 0.0f;
+            if (on[k]) {
+                float m[6];
 #pragma unroll
-            for (int c = 0; c < CH; ++c)
-                vals[k * CH + c] = make_elem<DT>(align_channel<CH>(px[k], c, weigh, t.order, t.wb, t.wg, t.wr, t.gray_shift), t.scale[c], t.bias[c]);
-        store_run<E, 4 * CH>(out, (((long long)n * out_h + i) * out_w + j0) * CH, vals, npx * CH);
+                for (int e = 0; e < 6; ++e) m[e] = tm[lab[k] * WARP_LDS_REC + e];
+                warp_position(m, j0 + k, i, sx[k], sy[k]);
+            }
+        }
+        align_fetch_segment<WIDE>(r, sx, sy, on, px);
     }
-}
-
-#define WARP_LAUNCH(DT, LAYOUT, CH) \
-    hipLaunchKernelGGL((warp_tensor_kernel<DT, LAYOUT, CH>), grid, dim3(ALIGN_T_BLOCK), 0, s, base, faces, matrices, T, labels, frames, img_idx, \
-                       src_format, out_w, out_h, t, out)
-
-template <int DT>
-void launch_layout(int layout, int channels, dim3 grid, hipStream_t s, const uint8_t* base, const WarpFace* faces, const float* matrices, int T,
-                   const uint8_t* labels, const AlignFrameDev* frames, const int* img_idx, int src_format, int out_w, int out_h,
-                   const AlignTensorDev& t, void* out)
-{
-    // one channel: the two layouts are the same addresses
-    if (channels == 1) WARP_LAUNCH(DT, SDM_ALIGN_NCHW, 1);
-    else if (layout == SDM_ALIGN_NCHW) WARP_LAUNCH(DT, SDM_ALIGN_NCHW, 3);
-    else WARP_LAUNCH(DT, SDM_ALIGN_NHWC, 3);
-}
+};
 
 }  // namespace
 
@@ -183,9 +132,5 @@ void sdm_launch_warp_tensor(const uint8_t* base, const WarpFace* faces, const fl
                             const AlignFrameDev* frames, const int* img_idx, int src_format, int N, int out_w, int out_h, int dtype,
                             int layout, int channels, const AlignTensorDev& spec, void* out, hipStream_t s)
 {
-    const int lanes = ((out_w + 3) / 4) * out_h;
-    const dim3 grid((unsigned)N, (unsigned)((lanes + ALIGN_T_BLOCK - 1) / ALIGN_T_BLOCK));
-    if (dtype == SDM_ALIGN_U8) launch_layout<SDM_ALIGN_U8>(layout, channels, grid, s, base, faces, matrices, T, labels, frames, img_idx, src_format, out_w, out_h, spec, out);
-    else if (dtype == SDM_ALIGN_F16) launch_layout<SDM_ALIGN_F16>(layout, channels, grid, s, base, faces, matrices, T, labels, frames, img_idx, src_format, out_w, out_h, spec, out);
-    else launch_layout<SDM_ALIGN_F32>(layout, channels, grid, s, base, faces, matrices, T, labels, frames, img_idx, src_format, out_w, out_h, spec, out);
+    align_tensor_launch<WarpMesh>(base, faces, frames, img_idx, src_format, N, out_w, out_h, dtype, layout, channels, spec, {matrices, T, labels}, out, s);
 }

@@ -737,6 +737,25 @@ class Context:
         self.align_channels = C if C else 1
         return C if C else None
 
+    def _crop_tensor_out(self, spec, options, width, height, out):
+        """What ``align_crops_tensor`` and ``warp_crops_tensor`` do alike before their call: the specification (``spec`` or the
+        ``options`` of ``_lib.align_tensor_spec``), the output tensor (``out`` checked, or a new one) with torch's stream on its device
+        synchronised -- the library runs on its own.  Returns (spec, out, rows)."""
+        if spec is None:
+            spec = _lib.align_tensor_spec(**options)
+        elif options:
+            raise ValueError("give either spec or the named options")
+        n = int(getattr(self, "N", 0))          # (0: no rows yet -- the library refuses the call)
+        shape = _lib.align_tensor_shape(n, width, height, spec.layout, spec.channels)
+        name = {v: k for k, v in _lib.ALIGN_DTYPES.items()}[spec.dtype]
+        import torch
+        if out is None:
+            out = torch.empty(shape, dtype=getattr(torch, name), device=f"cuda:{self.device}")
+        else:
+            _lib.check_align_out(out, shape, name)
+        torch.cuda.current_stream(out.device).synchronize()
+        return spec, out, n
+
     def align_crops_tensor(self, landmark_index, template: np.ndarray, width: int, height: int, spec=None, out=None, filter=None,
                            **options):
         """Crops of the N current rows as a network's input tensor (include/sdm.h, sdm_align_crops_tensor) from the source set by
@@ -750,25 +769,13 @@ class Context:
             filter = _lib.align_filter(filter)
         elif filter is not None and not isinstance(filter, _lib.SdmAlignFilter):
             raise ValueError('filter must be None, "area", "bilinear" or an SdmAlignFilter')
-        if spec is None:
-            spec = _lib.align_tensor_spec(**options)
-        elif options:
-            raise ValueError("give either spec or the named options")
         idx = np.ascontiguousarray(landmark_index, np.int32).reshape(-1)
         t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
         if t.shape[0] != idx.size:
             raise ValueError("one template point (x, y) per landmark index expected")
-        n = int(getattr(self, "N", 0))          # (0: no rows yet -- the library refuses the call)
-        shape = _lib.align_tensor_shape(n, int(width), int(height), spec.layout, spec.channels)
-        name = {v: k for k, v in _lib.ALIGN_DTYPES.items()}[spec.dtype]
-        import torch
-        if out is None:
-            out = torch.empty(shape, dtype=getattr(torch, name), device=f"cuda:{self.device}")
-        else:
-            _lib.check_align_out(out, shape, name)
+        spec, out, n = self._crop_tensor_out(spec, options, int(width), int(height), out)
         mats = np.empty((n, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
-        torch.cuda.current_stream(out.device).synchronize()
         if filter is None:
             check(self._lib.sdm_align_crops_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height), ctypes.byref(spec),
                                                    ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
@@ -805,22 +812,10 @@ class Context:
         sdm_warp_crops_tensor), from the source ``align_crops_tensor`` reads.  ``spec`` / ``options`` / ``out``: as for
         ``align_crops_tensor``.  Returns (tensor N x C x H x W or N x H x W x C, matrices N x T x 2 x 3 float32 crop -> source, one per
         triangle, flags N int32: SDM_WARP_* bits)."""
-        if spec is None:
-            spec = _lib.align_tensor_spec(**options)
-        elif options:
-            raise ValueError("give either spec or the named options")
         T, width, height = getattr(self, "warp_mesh", (0, 0, 0))
-        n = int(getattr(self, "N", 0))          # (0: no rows yet -- the library refuses the call)
-        shape = _lib.align_tensor_shape(n, width, height, spec.layout, spec.channels)
-        name = {v: k for k, v in _lib.ALIGN_DTYPES.items()}[spec.dtype]
-        import torch
-        if out is None:
-            out = torch.empty(shape, dtype=getattr(torch, name), device=f"cuda:{self.device}")
-        else:
-            _lib.check_align_out(out, shape, name)
+        spec, out, n = self._crop_tensor_out(spec, options, width, height, out)
         mats = np.empty((n, T, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
-        torch.cuda.current_stream(out.device).synchronize()
         check(self._lib.sdm_warp_crops_tensor(self._h, ctypes.byref(spec), ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
         return out, mats, flags
 

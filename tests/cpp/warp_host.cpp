@@ -8,7 +8,8 @@
 //   out.bin     per fit: float32 A_t[6], int32 folded
 //               per case: out_h x out_w x 3 bytes (B, G, R), out_h x out_w bytes (1 channel, gray_shift 14), out_h x out_w bytes
 //               (gray_shift 15), 3 x out_h x out_w float32 (RGB planes, v * scale + bias)
-// A lane's work is a segment of 4 pixels, as in warp_tensor_kernel: labels, positions through each pixel's own matrix, warp_segment.
+// A lane's work is a segment of 4 pixels, as in the warp's kernel (WarpMesh, csrc/sdm_warp.hip): labels, positions through each pixel's own
+// matrix, align_fetch_segment.
 // exits 1 when the 32-bit and the 64-bit offset paths disagree
 #include "../../superviseddescent_amd/csrc/sdm_warp_device.h"
 
@@ -84,10 +85,10 @@ int main(int argc, char** argv)
                     }
                 }
                 uint32_t px[4][3], wide[4][3], one[4][3], one_wide[4][3];
-                warp_segment<false>(r, sx, sy, on, px);
-                warp_segment<true>(r, sx, sy, on, wide);
-                warp_segment<false>(luma, sx, sy, on, one);
-                warp_segment<true>(luma, sx, sy, on, one_wide);
+                align_fetch_segment<false>(r, sx, sy, on, px);
+                align_fetch_segment<true>(r, sx, sy, on, wide);
+                align_fetch_segment<false>(luma, sx, sy, on, one);
+                align_fetch_segment<true>(luma, sx, sy, on, one_wide);
                 for (int q = 0; q < npx; ++q) {
                     const size_t at = (size_t)i * ow + j0 + q;
                     for (int c = 0; c < 3; ++c) {
