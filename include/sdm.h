@@ -740,6 +740,70 @@ int sdm_warp_get_labels(sdm_ctx* ctx, uint8_t* labels_host);
  * state, the images, the crop source nor the tracker's slots are changed. */
 int sdm_warp_crops_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, void* out_dev, float* matrices_host, int* flags_host);
 
+/* Pasting crops back: the inverse path of sdm_align_crops_tensor.  A network's output y = net(x) on the crops x -- a restored, swapped,
+ * re-lit, blurred or pixelated face -- is warped back through the row's similarity and blended into the frames where they lie on the
+ * device, in place, in one launch behind the fit for all rows, in the integer arithmetic of the crop path.  Every float operation is
+ * rounded on its own, nothing is contracted.
+ *   destination   dst_frames[i].data is WRITTEN in place: the const of sdm_frame, the read-only view of the crop calls, is cast away
+ *           here.  Formats GRAY, BGR, RGB, BGRA, RGBA; any pointer alignment, any stride_bytes >= width * bytes per pixel; every offset
+ *           is 64-bit.  Row n maps to a frame through sdm_set_sample_image_index (sdm_align_paste_tensor) or image_index
+ *           (sdm_align_paste_tensor_at; NULL: row i -> frame i).  In the fit form a frame must have the width and height of the context
+ *           image its row maps to (sdm_align_crops_tensor's rule for a frame-list source).  The frames may be the very memory the
+ *           context's images or the crop source read in place: that is the caller's business.  in_dev or an opacity map overlapping a
+ *           destination frame, and two frame entries that alias each other, are undefined.
+ *   M, W    M (crop -> frame) is the fit of sdm_align_crops -- the same kernel, the same M, the same flags -- or row n of matrices_host.
+ *           Its inverse W (frame -> crop) is computed from the float32 M in double: d = M00 M11 - M01 M10, W00 = M11 / d, W01 = -M01 / d,
+ *           W10 = -M10 / d, W11 = M00 / d, W02 = -(W00 M02 + W01 M12), W12 = -(W10 M02 + W11 M12), each of the six rounded once to
+ *           float32.
+ *   flags   SDM_ALIGN_DEGENERATE -- the row pastes nothing --: the fit flags it DEGENERATE, an entry of M is not finite, d == 0, or an
+ *           entry of W is not finite.  SDM_ALIGN_PARTIAL: the fit's rule on M (a crop corner's pixel centre maps outside
+ *           [0, W - 1] x [0, H - 1] of the frame); the _at form evaluates the same rule from M and the frame's size.  Beside an M that
+ *           is not finite no other bit is evaluated, as in the fit.
+ *   position   frame pixel (column X, row Y), in float32: u = (W00 X + W01 Y) + W02, v = (W10 X + W11 Y) + W12;
+ *           U = floor(u * 32 + 0.5f), u0 = U >> 5, fu = U & 31, v the same: sdm_align_crops' quantisation and its four weights out of
+ *           1024.  The pixel is IN THE FOOTPRINT of row n when u and v are finite, |u|, |v| <= 2^20, -1 <= u0 <= crop_width - 1 and
+ *           -1 <= v0 <= crop_height - 1: at least one tap lies in the crop.
+ *   tap     the tensor element of output channel c at (column, row), both clamped into the crop, decoded by dtype.  U8: the byte.
+ *           F32: f = e * scale[c] + bias[c], the product rounded, then the sum rounded; F16: converted exactly to float32 first.  Then
+ *           p = 0 for a NaN, else rintf(min(max(f, 0), 255)), ties to even.  scale / bias are therefore the INVERSE of the crop call's:
+ *           scale = std, bias = mean in 0-255 units.  channels == 3: `order` says which tensor channel is B, G or R; channels == 1: the
+ *           one value serves all three.  Layouts as in sdm_align_crops_tensor.
+ *   colour  per B, G and R: q = (w00 p00 + w10 p10 + w01 p01 + w11 p11 + 512) >> 10.
+ *   opacity the same four weights on the row's opacity map (sdm_align_paste: crop_height x crop_width bytes, one map for all rows or
+ *           row n's at n * H * W); a tap outside the crop reads 0; with alpha_dev NULL a tap inside reads 255; a = (... + 512) >> 10.
+ *           The crop's border therefore fades over one pixel by itself; a caller's feathered map fades wider.
+ *   write   a == 0: no byte of the pixel is written.  Otherwise per destination byte with the old value o:
+ *           o' = (a q + (255 - a) o + 127) / 255, an unsigned integer division.  BGR / BGRA: bytes 0, 1, 2 take B, G, R; RGB / RGBA the
+ *           reverse; GRAY: from a 3-channel tensor (B wb + G wg + R wr + (1 << (gray_shift - 1))) >> gray_shift of the sampled q with
+ *           sdm_upload_images_bgr_u8's weights, from a 1-channel tensor q.  The alpha byte of BGRA / RGBA is neither read nor written:
+ *           three bytes are stored.
+ *   several rows on one frame   the result is that of pasting the rows one after another in increasing row number, each reading what the
+ *           previous one left, whatever the launch order: a pixel is loaded once, every row whose footprint holds it is applied in
+ *           registers in row order, and it is stored once.
+ *   never stored to, not even with their old value: pitch padding, pixels outside every footprint, pixels whose every a is 0, alpha bytes.
+ * Out of scope, and not half-built: NV12 destinations (refused), the piecewise-affine paste (the inverse of sdm_warp_crops_tensor), and
+ * any antialiasing when the face in the frame is smaller than the crop -- the paste is plain bilinear, as sdm_align_crops is.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched: what sdm_align_crops_tensor refuses of landmark_index, template_xy,
+ * K, the crop size, spec and the rows' source (fit form); in_dev NULL or not 16-byte aligned; paste NULL; alpha_per_row not 0 or 1;
+ * dst_frames NULL or n_frames < 1; what sdm_set_frames_device refuses of a frame; an NV12 frame; a row whose image index is outside
+ * [0, n_frames); the size mismatch above; _at form: matrices_host NULL, n_rows < 1, crop_width or crop_height outside [1, 1024]. */
+typedef struct sdm_align_paste {
+    const uint8_t* alpha_dev;   /* crop-space opacity, u8, device memory; NULL: 255 everywhere inside the crop      */
+    int alpha_per_row;          /* 0: one crop_height x crop_width map for all rows; 1: N maps, row n at n * H * W  */
+} sdm_align_paste;
+/* the current rows: the fit of sdm_align_crops (same kernel, same M, same flags), then the paste.  in_dev: N * channels * crop_height *
+ * crop_width elements.  matrices_host (N x 6) and flags_host (N) may be NULL; they come back in one copy behind the call's one
+ * synchronise. */
+int sdm_align_paste_tensor(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int crop_width, int crop_height,
+                           const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste,
+                           const sdm_frame* dst_frames, int n_frames, float* matrices_host /* out, N x 6, may be NULL */,
+                           int* flags_host /* out, may be NULL */);
+/* explicit crop -> frame matrices (what an earlier crop call returned): no landmark state, no geometry, no context images needed -- the
+ * network may run on frame t while the tracker has stepped to t + 1 */
+int sdm_align_paste_tensor_at(sdm_ctx* ctx, const float* matrices_host /* in, n_rows x 6 */, const int* image_index /* NULL: row i -> frame i */,
+                              int n_rows, int crop_width, int crop_height, const sdm_align_tensor* spec, const void* in_dev,
+                              const sdm_align_paste* paste, const sdm_frame* dst_frames, int n_frames, int* flags_host);
+
 #ifdef __cplusplus
 }
 #endif

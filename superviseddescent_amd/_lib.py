@@ -39,6 +39,7 @@ EXPORTED = [
     "sdm_set_frames_device", "sdm_debug_download_image",
     "sdm_upright_configure", "sdm_detect_batch_upright", "sdm_upright_get", "sdm_track_configure_upright", "sdm_track_start_rolled",
     "sdm_warp_delaunay", "sdm_warp_set_mesh", "sdm_warp_get_labels", "sdm_warp_crops_tensor",
+    "sdm_align_paste_tensor", "sdm_align_paste_tensor_at",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -92,6 +93,13 @@ class SdmAlignFilter(ctypes.Structure):
     """``sdm_align_filter``: the sampling of sdm_align_crops_tensor_filtered -- mode, the cap on the sub-samples per axis, the scale gate."""
 
     _fields_ = [("mode", ctypes.c_int), ("max_samples", ctypes.c_int), ("min_scale", ctypes.c_float)]
+
+
+class SdmAlignPaste(ctypes.Structure):
+    """``sdm_align_paste``: the crop-space opacity of sdm_align_paste_tensor -- a device pointer (None: 255 inside the crop) and whether
+    there is one map per row."""
+
+    _fields_ = [("alpha_dev", ctypes.c_void_p), ("alpha_per_row", ctypes.c_int)]
 
 
 def align_filter(mode="area", max_samples=16, min_scale=1.0) -> SdmAlignFilter:
@@ -151,6 +159,18 @@ def align_tensor_spec(dtype="float16", layout="nchw", channels=3, order="rgb", s
         bi = _three(0.0 if bias is None else bias, "bias").astype(np.float32)
     return SdmAlignTensor(ALIGN_DTYPES[name], ALIGN_LAYOUTS[layout.lower()], int(channels), ALIGN_ORDERS[order.lower()],
                           (ctypes.c_float * 3)(*sc.tolist()), (ctypes.c_float * 3)(*bi.tolist()), int(gray_shift))
+
+
+def paste_tensor_spec(dtype, layout="nchw", channels=3, order="rgb", scale=None, bias=None, mean=None, std=None,
+                      gray_shift=14) -> SdmAlignTensor:
+    """The ``sdm_align_tensor`` of a paste (sdm_align_paste_tensor): a tensor element e is decoded as float32(e) * scale[c] + bias[c], the
+    INVERSE of the crop call's element -- so ``mean`` / ``std`` (0-255 units, a scalar or 3 values) here mean ``scale = float32(std)``,
+    ``bias = float32(mean)``: the same ``mean`` / ``std`` as in the crop call undo it.  Everything else as ``align_tensor_spec``."""
+    if (mean is not None or std is not None) and (scale is not None or bias is not None):
+        raise ValueError("give either scale / bias or mean / std, not both")
+    if mean is not None or std is not None:
+        scale, bias = (1.0 if std is None else std), (0.0 if mean is None else mean)
+    return align_tensor_spec(dtype, layout, channels, order, scale, bias, None, None, gray_shift)
 
 
 def align_tensor_shape(n: int, width: int, height: int, layout: int, channels: int):
@@ -421,6 +441,10 @@ def lib() -> ctypes.CDLL:
             "sdm_warp_set_mesh": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int],
             "sdm_warp_get_labels": [c_void_p, c_void_p],
             "sdm_warp_crops_tensor": [c_void_p, ctypes.POINTER(SdmAlignTensor), c_void_p, c_void_p, c_void_p],
+            "sdm_align_paste_tensor": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,
+                                       ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_int, c_void_p, c_void_p],
+            "sdm_align_paste_tensor_at": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,
+                                          ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_int, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

@@ -1,0 +1,77 @@
+// sdm_align_paste.hip -- crop tensors pasted back into frames on gfx950 (include/sdm.h, "Pasting crops back"), behind the fit of
+// sdm_align_crops or a caller's matrices.
+//
+//   paste_prepare_kernel   one lane per row: the inverse map W (double, rounded once to float32), the flags and the footprint's box in
+//                          the row's frame, written as one PasteRow record; the final flags go back into the fit's record
+//   paste_kernel           grid (row list entry, PASTE_GROUPS workgroups): the workgroups of an entry stride over the 64 x 4 pixel tiles
+//                          of its row's box -- a wave covers 64 consecutive pixels of one frame row --, so the box never reaches the
+//                          host.  A lane's pixel is pasted by the lowest-numbered row of the frame whose footprint holds it
+//                          (paste_pixel): every frame byte has at most one reader and writer in the launch, whatever the order the
+//                          workgroups run in.  Stores are per pixel, byte by byte: nothing a neighbour owns is touched.
+//
+// The per-pixel arithmetic is csrc/sdm_align_paste_device.h.
+#include "sdm_kernels.h"
+#include "sdm_align_paste_device.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+#define PASTE_BLOCK 256
+#define PASTE_TILE_W 64
+#define PASTE_TILE_H (PASTE_BLOCK / PASTE_TILE_W)
+#define PASTE_PREPARE_BLOCK 64
+
+__global__ __launch_bounds__(PASTE_PREPARE_BLOCK) void paste_prepare_kernel(AlignFace* __restrict__ faces, const int* __restrict__ frame_of_row,
+                                                                            const PasteFrameDev* __restrict__ frames, int N, int cw, int ch,
+                                                                            int fitted, PasteRow* __restrict__ rows)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const int fi = frame_of_row[n];
+    const PasteFrameDev f = frames[fi];
+    float m[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) m[e] = faces[n].m[e];
+    PasteRow r;
+    paste_prepare_row(m, fitted ? faces[n].flags : -1, fi, f.w, f.h, cw, ch, r);
+    rows[n] = r;
+    faces[n].flags = r.flags;
+}
+
+__global__ __launch_bounds__(PASTE_BLOCK) void paste_kernel(const PasteFrameDev* __restrict__ frames, const PasteRow* __restrict__ rows,
+                                                            const int* __restrict__ list, const int* __restrict__ entry_of_row, PasteCropDev c)
+{
+    // the row, its list entry and its frame: uniform for the workgroup
+    const int n = blockIdx.x;
+    const int k = entry_of_row[n];
+    const PasteRow r = rows[n];
+    const int bw = r.x1 - r.x0, bh = r.y1 - r.y0;
+    if (bw <= 0 || bh <= 0) return;
+    const PasteFrameDev f = frames[r.frame];
+    const int tx = (bw + PASTE_TILE_W - 1) / PASTE_TILE_W, ty = (bh + PASTE_TILE_H - 1) / PASTE_TILE_H;
+    const int lx = threadIdx.x & (PASTE_TILE_W - 1), ly = threadIdx.x / PASTE_TILE_W;
+    for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
+        const int tj = (int)(t % tx), ti = (int)(t / tx);
+        const int X = r.x0 + tj * PASTE_TILE_W + lx, Y = r.y0 + ti * PASTE_TILE_H + ly;
+        if (X < r.x1 && Y < r.y1) paste_pixel(f, rows, list, k, c, X, Y);
+    }
+}
+
+}  // namespace
+
+void sdm_launch_paste_prepare(AlignFace* faces, const int* frame_of_row, const PasteFrameDev* frames, int N, int cw, int ch, bool fitted,
+                              PasteRow* rows, hipStream_t s)
+{
+    hipLaunchKernelGGL(paste_prepare_kernel, dim3((unsigned)((N + PASTE_PREPARE_BLOCK - 1) / PASTE_PREPARE_BLOCK)), dim3(PASTE_PREPARE_BLOCK), 0, s,
+                       faces, frame_of_row, frames, N, cw, ch, fitted ? 1 : 0, rows);
+}
+
+void sdm_launch_paste(const PasteFrameDev* frames, const PasteRow* rows, const int* list, const int* entry_of_row, int N,
+                      const PasteCropDev& crop, hipStream_t s)
+{
+    // workgroups per row: one per 1 024 crop pixels, 1 ... 32 (a 112 x 112 crop: 13)
+    int groups = (crop.cw * crop.ch + 1023) / 1024;
+    groups = groups < 1 ? 1 : (groups > 32 ? 32 : groups);
+    hipLaunchKernelGGL(paste_kernel, dim3((unsigned)N, (unsigned)groups), dim3(PASTE_BLOCK), 0, s, frames, rows, list, entry_of_row, crop);
+}

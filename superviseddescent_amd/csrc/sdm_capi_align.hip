@@ -3,6 +3,7 @@
 // before anything is launched; the landmark state, the images and the tracker's slots are only read.  sdm_align_set_source_frames and
 // sdm_align_crops_tensor (csrc/sdm_align_tensor.hip): a frame list used in place as the source, and the crops as a network's input tensor;
 // sdm_align_crops_tensor_filtered (csrc/sdm_align_area.hip): that tensor with a minifying row's pixels averaged over their footprint.
+// The way back, sdm_align_paste_tensor, is csrc/sdm_capi_paste.hip; it shares the checks and the fit below.
 #include "sdm_capi_internal.h"
 
 #include <cmath>
@@ -20,7 +21,7 @@ static int align_frame_bpp(int format)
 
 // what sdm_align_crops and sdm_align_crops_tensor check alike, before anything is launched: geometry, rows, indices, template, crop
 // size, and that the source covers every row's image with that image's size
-static int align_check_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h)
+int sdm_capi::align_check_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h)
 {
     if (c->L <= 0) return fail(SDM_ERR_INVALID, "geometry not set");
     if (c->N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
@@ -124,7 +125,7 @@ int sdm_capi::align_check_rows(sdm_ctx* c)
 }
 
 // the K indices and the template in, the fit of every row into a.faces (the buffers are there)
-static int align_fit_rows(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h)
+int sdm_capi::align_fit_rows(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h)
 {
     sdm_ctx::Align& a = c->align;
     std::vector<int> in((size_t)3 * K);

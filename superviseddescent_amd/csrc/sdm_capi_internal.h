@@ -7,7 +7,7 @@
 //   sdm_capi_debug.hip     device pointers, timing, debug entry points   sdm_capi_pose.hip / sdm_capi_track.hip  head pose, tracking
 //   sdm_capi_align.hip     aligned face crops                          sdm_capi_sweep.hip     regulariser sweep on one Gram product
 //   sdm_capi_frames.hip    device-resident frames as the image set     sdm_capi_upright.hip   upright chips for rolled faces
-//   sdm_capi_warp.hip      piecewise-affine warped faces
+//   sdm_capi_warp.hip      piecewise-affine warped faces               sdm_capi_paste.hip     crop tensors pasted back into frames
 #pragma once
 #include "../../include/sdm.h"
 #include "sdm_kernels.h"
@@ -281,9 +281,11 @@ struct sdm_ctx {
         DevBuf<AlignFrameDev> fr_dev;
         const uint8_t* fr_base = nullptr;
         int fr_bpp = 0;
+        // the paste (sdm_capi_paste.hip): a call's frame table, row -> frame index and row lists in one block, and the rows' records
+        DevBuf<unsigned char> paste_tab, paste_rows;
         void release()
         {
-            in.release(); faces.release(); crops.release(); owned.release(); fr_dev.release();
+            in.release(); faces.release(); crops.release(); owned.release(); fr_dev.release(); paste_tab.release(); paste_rows.release();
             base = nullptr; n = 0; C = 1; fr.clear();
         }
     } align;
@@ -395,6 +397,8 @@ int upright_roll_cs(float roll_deg, double* cs);
 // (sdm_capi_align.hip) the checks and the element stage's constants that sdm_align_crops_tensor and sdm_warp_crops_tensor share: the
 // specification, the output pointer, that the crop source covers every row's image with that image's size, the source itself and the
 // landmark subset of a template
+int align_check_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h);      // geometry, rows, indices, template, crop size
+int align_fit_rows(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h);        // the fit of every row into align.faces
 int align_check_spec(const sdm_align_tensor* spec);
 int align_check_out(const void* out_dev);
 int align_check_rows(sdm_ctx* c);

@@ -1,0 +1,159 @@
+// sdm_capi_paste.hip -- C-ABI of the paste-back of crop tensors into frames (include/sdm.h, "Pasting crops back"): the two entry points
+// check every argument before anything is launched or changed, build the frame table and the rows-of-frame lists on the host from the
+// image index they already hold, and enqueue -- fit form -- sdm_align_crops' fit, then the prepare kernel and the one paste launch
+// (csrc/sdm_align_paste.hip).  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
+// landmark state, the images, the crop source and the tracker's slots are only read; the frames' colour bytes are written in place.
+#include "sdm_capi_internal.h"
+#include "sdm_align_paste_device.h"
+
+#include <cmath>
+
+namespace {
+
+int paste_frame_bpp(int format)
+{
+    switch (format) {
+    case SDM_FRAME_GRAY: return 1;
+    case SDM_FRAME_BGR: case SDM_FRAME_RGB: return 3;
+    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return 4;
+    default: return 0;
+    }
+}
+
+// what both forms refuse of the tensor, the opacity maps and the destination frames
+int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames)
+{
+    if (!in_dev) return fail(SDM_ERR_INVALID, "no tensor");
+    if ((uintptr_t)in_dev % 16 != 0) return fail(SDM_ERR_INVALID, "the tensor must be 16-byte aligned");
+    if (!paste) return fail(SDM_ERR_INVALID, "no paste options");
+    if (paste->alpha_per_row != 0 && paste->alpha_per_row != 1) return fail(SDM_ERR_INVALID, "alpha_per_row must be 0 or 1");
+    if (!frames || n_frames < 1) return fail(SDM_ERR_INVALID, "bad frame list");
+    for (int i = 0; i < n_frames; ++i) {
+        const sdm_frame& f = frames[i];
+        if (f.format == SDM_FRAME_NV12) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": an NV12 frame cannot be pasted into");
+        const int bpp = paste_frame_bpp(f.format);
+        if (!bpp) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": unknown format");
+        if (!f.data) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": null pointer");
+        if (f.width < 1 || f.height < 1) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": width and height must be >= 1");
+        if ((long long)f.stride_bytes < (long long)f.width * bpp)
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < width * bytes per pixel");
+    }
+    return SDM_OK;
+}
+
+// behind the checks: `faces` holds N records with M (fitted: and the fit's flags).  frame_of_row: N checked indices.
+int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int cw, int ch, const sdm_align_tensor* spec, const void* in_dev,
+              const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host, int* flags_host)
+{
+    sdm_ctx::Align& a = c->align;
+    const int N = (int)frame_of_row.size();
+    // the frame table, the row -> frame index, the rows of every frame in ascending order, and every row's place among them
+    const size_t tab_bytes = (size_t)n_frames * sizeof(PasteFrameDev), bytes = tab_bytes + (size_t)3 * N * sizeof(int);
+    std::vector<unsigned char> blob(bytes);
+    PasteFrameDev* tab = (PasteFrameDev*)blob.data();
+    int* of_row = (int*)(blob.data() + tab_bytes);
+    int* list = of_row + N;
+    int* entry = list + N;
+    std::vector<int> count((size_t)n_frames + 1, 0);
+    for (int r = 0; r < N; ++r) { of_row[r] = frame_of_row[r]; ++count[(size_t)frame_of_row[r] + 1]; }
+    for (int i = 0; i < n_frames; ++i) count[(size_t)i + 1] += count[i];
+    for (int i = 0; i < n_frames; ++i) {
+        const sdm_frame& f = frames[i];
+        PasteFrameDev& d = tab[i];
+        d.p = (uint8_t*)const_cast<void*>(f.data);                 // (sdm_frame is the read-only view of the crop calls: written here)
+        d.stride = f.stride_bytes; d.w = f.width; d.h = f.height; d.format = f.format;
+        d.row_begin = count[i]; d.row_end = count[(size_t)i + 1]; d.pad = 0;
+    }
+    std::vector<int> fill(count.begin(), count.end() - 1);
+    for (int r = 0; r < N; ++r) { const int at = fill[frame_of_row[r]]++; list[at] = r; entry[r] = at; }
+    int rc;
+    if ((rc = a.paste_tab.ensure(bytes)) || (rc = a.paste_rows.ensure((size_t)N * sizeof(PasteRow)))) return rc;
+    HIP_TRY(hipMemcpyAsync(a.paste_tab.p, blob.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    const PasteFrameDev* tab_dev = (const PasteFrameDev*)a.paste_tab.p;
+    const int* of_row_dev = (const int*)(a.paste_tab.p + tab_bytes);
+    PasteRow* rows_dev = (PasteRow*)a.paste_rows.p;
+    sdm_launch_paste_prepare(a.faces.p, of_row_dev, tab_dev, N, cw, ch, fitted, rows_dev, c->stream);
+    HIP_TRY(hipGetLastError());
+    PasteCropDev crop{};
+    crop.in = in_dev; crop.alpha = paste->alpha_dev;
+    crop.cw = cw; crop.ch = ch; crop.dtype = spec->dtype; crop.channels = spec->channels;
+    crop.sn = (long long)spec->channels * cw * ch;
+    if (spec->layout == SDM_ALIGN_NCHW) { crop.sc = cw * ch; crop.sy = cw; crop.sx = 1; }
+    else { crop.sc = 1; crop.sy = cw * spec->channels; crop.sx = spec->channels; }
+    crop.an = paste->alpha_per_row ? (long long)cw * ch : 0;
+    const AlignTensorDev t = align_tensor_dev(spec);
+    for (int k = 0; k < 3; ++k) { crop.t.scale[k] = t.scale[k]; crop.t.bias[k] = t.bias[k]; }
+    crop.t.order = t.order; crop.t.wb = t.wb; crop.t.wg = t.wg; crop.t.wr = t.wr; crop.t.gray_shift = t.gray_shift;
+    sdm_launch_paste(tab_dev, rows_dev, of_row_dev + N, of_row_dev + 2 * N, N, crop, c->stream);
+    HIP_TRY(hipGetLastError());
+    // the records in one copy, one synchronise
+    std::vector<AlignFace> host;
+    if (matrices_host || flags_host) {
+        host.resize((size_t)N);
+        HIP_TRY(hipMemcpyAsync(host.data(), a.faces.p, (size_t)N * sizeof(AlignFace), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t r = 0; r < host.size(); ++r) {
+        if (matrices_host) memcpy(matrices_host + 6 * r, host[r].m, 6 * sizeof(float));
+        if (flags_host) flags_host[r] = host[r].flags;
+    }
+    return SDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdm_align_paste_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, int ch, const sdm_align_tensor* spec,
+                           const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host,
+                           int* flags_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    int rc;
+    if ((rc = align_check_call(c, lm, tmpl, K, cw, ch)) || (rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames)) ||
+        (rc = align_check_rows(c)))
+        return rc;
+    const int N = c->N;
+    std::vector<int> frame_of_row((size_t)N);
+    for (int r = 0; r < N; ++r) {
+        const int im = c->idx_identity ? r : c->img_idx_host[r];
+        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to image " + std::to_string(im) + ", beyond the frames");
+        if (frames[im].width != c->img_w_host[im] || frames[im].height != c->img_h_host[im])
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(im) + " differs in size from image " + std::to_string(im) + " of the context");
+        frame_of_row[r] = im;
+    }
+    sdm_ctx::Align& a = c->align;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure((size_t)N))) return rc;
+    if ((rc = align_fit_rows(c, lm, tmpl, K, cw, ch))) return rc;
+    return paste_run(c, true, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host);
+}
+
+int sdm_align_paste_tensor_at(sdm_ctx* c, const float* matrices_host, const int* image_index, int n_rows, int cw, int ch,
+                              const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
+                              int n_frames, int* flags_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    if (!matrices_host) return fail(SDM_ERR_INVALID, "no matrices");
+    if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
+    if (cw < 1 || cw > 1024 || ch < 1 || ch > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
+    int rc;
+    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames))) return rc;
+    std::vector<int> frame_of_row((size_t)n_rows);
+    std::vector<AlignFace> faces((size_t)n_rows);
+    for (int r = 0; r < n_rows; ++r) {
+        const int im = image_index ? image_index[r] : r;
+        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to frame " + std::to_string(im) + ", outside the list");
+        frame_of_row[r] = im;
+        AlignFace& f = faces[r];
+        memcpy(f.m, matrices_host + (size_t)6 * r, 6 * sizeof(float));
+        f.flags = 0; f.w = frames[im].width; f.h = frames[im].height; f.stride = frames[im].stride_bytes; f.off = 0;
+    }
+    sdm_ctx::Align& a = c->align;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = a.faces.ensure((size_t)n_rows))) return rc;
+    HIP_TRY(hipMemcpyAsync(a.faces.p, faces.data(), faces.size() * sizeof(AlignFace), hipMemcpyHostToDevice, c->stream));
+    return paste_run(c, false, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, nullptr, flags_host);
+}
+
+}  // extern "C"

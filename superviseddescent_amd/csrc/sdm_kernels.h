@@ -433,6 +433,18 @@ void sdm_launch_align_area(const uint8_t* base, const AlignFace* faces, const Al
                            int N, int out_w, int out_h, int dtype, int layout, int channels, const AlignTensorDev& spec,
                            const AlignAreaDev& area, int* samples, void* out, hipStream_t s);
 
+// ---- crop tensors pasted back into frames (sdm_align_paste.hip; the records are csrc/sdm_align_paste_device.h's) ----
+struct PasteFrameDev;
+struct PasteRow;
+struct PasteCropDev;
+// faces: N records holding M (fitted: and the fit's flags; otherwise PARTIAL is evaluated here); the final flags go back into them.
+// frame_of_row: N frame indices; rows: N records out
+void sdm_launch_paste_prepare(AlignFace* faces, const int* frame_of_row, const PasteFrameDev* frames, int N, int cw, int ch, bool fitted,
+                              PasteRow* rows, hipStream_t s);
+// list: the rows of every frame, ascending (PasteFrameDev::row_begin / row_end); entry_of_row: where row n stands in it
+void sdm_launch_paste(const PasteFrameDev* frames, const PasteRow* rows, const int* list, const int* entry_of_row, int N,
+                      const PasteCropDev& crop, hipStream_t s);
+
 // ---- upright-normalised detect and tracking (sdm_upright.hip) ----
 // per row: the chip -> frame matrix M and its inverse W (float32, rounded from the double rotation), the SDM_UPRIGHT_* flags and the
 // row's frame in the context's image set

@@ -819,6 +819,81 @@ class Context:
         check(self._lib.sdm_warp_crops_tensor(self._h, ctypes.byref(spec), ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
         return out, mats, flags
 
+    # -- crop tensors pasted back into frames (csrc/sdm_align_paste.hip) ------------------------------
+    def _paste_call(self, y, layout, frames, formats, mask, spec, options):
+        """What the two paste calls do alike before their call: the tensor (a contiguous uint8 / float16 / float32 device tensor,
+        N x C x H x W or N x H x W x C by ``layout``, C in {1, 3}) gives dtype, channels and the crop size of the specification (``spec``,
+        or the ``options`` of ``_lib.paste_tensor_spec``); the frames' descriptors; the opacity (``mask``: None, or an H x W or
+        N x H x W uint8 device tensor or numpy array).  torch's stream is synchronised: the library runs on its own.  Returns
+        (spec, paste, frame array, rows, width, height, what must stay alive over the call)."""
+        import torch
+        if not (isinstance(y, torch.Tensor) and y.is_cuda and y.is_contiguous() and y.dim() == 4):
+            raise ValueError("the tensor must be a contiguous 4-dimensional tensor on the device")
+        name = str(y.dtype).split(".")[-1]
+        if name not in _lib.ALIGN_DTYPES:
+            raise ValueError(f"the tensor must be uint8, float16 or float32, not {y.dtype}")
+        if not isinstance(layout, str) or layout.lower() not in _lib.ALIGN_LAYOUTS:
+            raise ValueError(f"unknown layout {layout!r}: one of {sorted(_lib.ALIGN_LAYOUTS)}")
+        n, (channels, height, width) = int(y.shape[0]), ([int(v) for v in y.shape[1:]] if layout.lower() == "nchw"
+                                                         else [int(y.shape[3]), int(y.shape[1]), int(y.shape[2])])
+        if spec is None:
+            spec = _lib.paste_tensor_spec(name, layout, channels, **options)
+        elif options:
+            raise ValueError("give either spec or the named options")
+        elif (spec.dtype, spec.layout, spec.channels) != (_lib.ALIGN_DTYPES[name], _lib.ALIGN_LAYOUTS[layout.lower()], channels):
+            raise ValueError("spec does not describe this tensor")
+        alpha = None
+        if mask is not None:
+            alpha = mask if isinstance(mask, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(mask, np.uint8)).to(y.device)
+            if not alpha.is_cuda or alpha.dtype != torch.uint8 or not alpha.is_contiguous() or \
+                    tuple(alpha.shape) not in ((height, width), (n, height, width)):
+                raise ValueError(f"mask must be a contiguous uint8 {height} x {width} or {n} x {height} x {width} array or device tensor")
+        paste = _lib.SdmAlignPaste(None if alpha is None else alpha.data_ptr(), int(alpha is not None and alpha.dim() == 3))
+        desc = _lib.frame_descriptors(frames, formats)
+        arr = (_lib.SdmFrame * len(desc))(*[_lib.SdmFrame(ctypes.c_void_p(p), w, h, st, f) for p, w, h, st, f in desc])
+        torch.cuda.current_stream(y.device).synchronize()
+        return spec, paste, arr, n, width, height, (alpha, frames)
+
+    def align_paste_tensor(self, landmark_index, template: np.ndarray, y, frames, formats=None, layout="nchw", mask=None, spec=None,
+                           **options):
+        """The inverse of ``align_crops_tensor`` for the N current rows (include/sdm.h, sdm_align_paste_tensor): ``y`` -- a network's
+        output on the crops, a device tensor whose dtype, channels and crop size are read from it -- is warped back through every row's
+        fitted similarity and blended into ``frames`` IN PLACE.  ``frames`` / ``formats``: as for ``set_frames_device``, without NV12;
+        row n goes to the frame ``set_sample_image_index`` names.  ``mask``: the crop-space opacity, None (255 inside the crop) or an
+        H x W (all rows) or N x H x W uint8 device tensor or numpy array.  ``options``: order, scale, bias, mean, std, gray_shift of
+        ``_lib.paste_tensor_spec`` (an element is decoded as e * scale + bias: ``mean`` / ``std`` as in the crop call undo it).  Returns
+        (matrices N x 2 x 3 float32 crop -> frame, flags N int32: SDM_ALIGN_* bits)."""
+        idx = np.ascontiguousarray(landmark_index, np.int32).reshape(-1)
+        t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
+        if t.shape[0] != idx.size:
+            raise ValueError("one template point (x, y) per landmark index expected")
+        spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
+        if int(getattr(self, "N", 0)) and n != self.N:          # (no rows yet: the library refuses the call)
+            raise ValueError(f"the tensor has {n} rows, the context {int(getattr(self, 'N', 0))}")
+        mats = np.empty((n, 2, 3), np.float32)
+        flags = np.empty(n, np.int32)
+        check(self._lib.sdm_align_paste_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, width, height, ctypes.byref(spec),
+                                               ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr), mats.ctypes.data,
+                                               flags.ctypes.data))
+        return mats, flags
+
+    def align_paste_tensor_at(self, matrices, y, frames, formats=None, image_index=None, layout="nchw", mask=None, spec=None, **options):
+        """``align_paste_tensor`` with explicit crop -> frame matrices (sdm_align_paste_tensor_at): ``matrices`` N x 2 x 3 as an earlier
+        crop call returned them -- the tracker may have stepped on since; no landmark state, geometry or context image is needed.
+        ``image_index``: the frame of every row (None: row i -> frame i).  Returns flags N int32: SDM_ALIGN_* bits."""
+        spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
+        m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 6)
+        if m.shape[0] != n:
+            raise ValueError(f"one matrix per row of the tensor expected: {m.shape[0]} for {n}")
+        idx = None if image_index is None else np.ascontiguousarray(image_index, np.int32).reshape(-1)
+        if idx is not None and idx.size != n:
+            raise ValueError("one image index per row expected")
+        flags = np.empty(n, np.int32)
+        check(self._lib.sdm_align_paste_tensor_at(self._h, m.ctypes.data, None if idx is None else idx.ctypes.data, n, width, height,
+                                                  ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr),
+                                                  flags.ctypes.data))
+        return flags
+
     # -- misc ------------------------------------------------------------------------------------------
     def synchronize(self):
         check(self._lib.sdm_synchronize(self._h))
@@ -1605,6 +1680,39 @@ class detection_model:
             if frames is not None:
                 c.align_set_source_frames(None)                           # (no pointer to the caller's frames stays behind)
 
+    def paste_crops_tensor(self, y, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None, margin: float = 0.2,
+                           frames=None, formats=None, layout="nchw", order="rgb", scale=None, bias=None, mean=None, std=None, gray_shift=14,
+                           mask=None, matrices=None, image_index=None):
+        """The way back of :meth:`aligned_crops_tensor`: ``y = net(x)`` on the crops -- a device tensor, N x C x H x W or N x H x W x C by
+        ``layout``; dtype, channels and crop size are read from it -- is warped back and blended into ``frames`` in place, in one launch
+        (include/sdm.h, "Pasting crops back").  ``landmark_ids``, ``template``, ``margin``, ``order``, ``gray_shift``: as in the crop call,
+        with the same defaults, so that ``paste(net(crop(...)))`` lands where it was cut.  ``frames`` / ``formats``: the destination, as
+        for ``detect_batch`` on device frames, without NV12.  ``mean`` / ``std`` (0-255 units) as in the crop call: here they mean
+        ``scale = std``, ``bias = mean``, the decoded value is ``e * scale + bias``.  ``mask``: the crop-space opacity -- None, or an H x W
+        or N x H x W uint8 device tensor or numpy array, e.g. :func:`feather_mask`.  ``matrices`` (N x 2 x 3, as a crop call returned
+        them) with ``image_index`` (None: row i -> frame i) pastes rows that are no longer current; otherwise the current rows are
+        fitted again.  Returns (matrices N x 2 x 3 crop -> frame, flags N: SDM_ALIGN_*).  No pointer to the frames stays behind."""
+        c = self.optimised_model.ctx
+        if frames is None:
+            raise ValueError("give the frames to paste into")
+        options = dict(order=order, scale=scale, bias=bias, mean=mean, std=std, gray_shift=gray_shift)
+        if matrices is not None:
+            m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 2, 3)
+            return m, c.align_paste_tensor_at(m, y, frames, formats, image_index, layout, mask, **options)
+        if image_index is not None:
+            raise ValueError("image_index goes with matrices; the current rows map through the context's sample -> image index")
+        if not getattr(c, "N", 0):
+            raise RuntimeError("run detect_batch or Tracker.step first")
+        height, width = (int(y.shape[2]), int(y.shape[3])) if str(layout).lower() == "nchw" else (int(y.shape[1]), int(y.shape[2]))
+        ids = self.landmark_ids if landmark_ids is None else [str(i) for i in landmark_ids]
+        missing = [i for i in ids if i not in self.landmark_ids]
+        if missing:
+            raise ValueError(f"landmark ids not in this model: {missing}")
+        idx = [self.landmark_ids.index(i) for i in ids]
+        if template is None:
+            template = alignment_template(self.mean, idx, width, height, margin)
+        return c.align_paste_tensor(idx, template, y, frames, formats, layout, mask, **options)
+
     def warp_mask(self) -> np.ndarray:
         """height x width bool of the last :meth:`warped_crops_tensor`'s mesh: True where a triangle covers the crop pixel."""
         return self.optimised_model.ctx.warp_labels() != _lib.SDM_WARP_NO_TRIANGLE
@@ -1628,6 +1736,19 @@ def alignment_template(mean: np.ndarray, landmark_index: Sequence[int], width: i
     tx = (px - (px.min() + px.max()) / 2) * s + (width - 1) / 2
     ty = (py - (py.min() + py.max()) / 2) * s + (height - 1) / 2
     return np.stack([tx, ty], 1).astype(np.float32)
+
+
+def feather_mask(size, border: int) -> np.ndarray:
+    """A crop-space opacity map for :meth:`detection_model.paste_crops_tensor` (height x width uint8, computed on the host): 255 in the
+    interior, a linear ramp to 0 over ``border`` pixels towards every edge -- pixel k from an edge has round(255 (k + 1) / (border + 1)).
+    ``size``: an int (square) or (width, height)."""
+    width, height = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+    if border < 0 or width < 1 or height < 1:
+        raise ValueError("size must be >= 1 and border >= 0")
+    dx = np.minimum(np.arange(width), np.arange(width)[::-1])[None, :]
+    dy = np.minimum(np.arange(height), np.arange(height)[::-1])[:, None]
+    k = np.minimum(np.minimum(dx, dy) + 1, border + 1)
+    return np.rint(255.0 * k / (border + 1)).astype(np.uint8)
 
 
 class Tracker:

@@ -9,6 +9,9 @@
 //     // a.crops[i]: stream ids[i]; a.matrices.row(i): its crop -> source map (M00 M01 M02 M10 M11 M12); a.flags[i]: SDM_ALIGN_*
 //
 // The rows of detection_model::detect_batch work the same way (the overload taking the images and the rows).
+//
+// rcr::aligned_crops_tensor writes the crops as a network's input tensor straight from frames on the device, and rcr::paste_crops_tensor is
+// its way back: a network's output on those crops, warped back through the rows' similarities and blended into the frames in place.
 #pragma once
 
 #ifndef RCR_ALIGNMENT_HPP_
@@ -250,6 +253,110 @@ inline aligned_tensor_result aligned_crops_tensor(detection_model& model, const 
                                                   const std::vector<const void*>& chroma = {})
 {
     return aligned_crops_tensor(model, frames, rows, image_index, landmark_index, tmpl, width, height, spec, out_dev, chroma, &filter);
+}
+
+/** The crop-space opacity of a paste (sdm_align_paste of include/sdm.h): device memory, height x width bytes for all rows or -- per_row --
+ *  one such map per row; nullptr: 255 everywhere inside the crop. */
+struct PasteMask {
+    const uint8_t* alpha_dev = nullptr;
+    bool per_row = false;
+};
+
+struct paste_result {
+    cv::Mat matrices;              // rows x 6 CV_32FC1: the crop -> frame map of every row (NaN for a degenerate row of the fit)
+    std::vector<int> flags;        // SDM_ALIGN_DEGENERATE / SDM_ALIGN_PARTIAL bits
+};
+
+namespace detail {
+
+inline sdm_align_tensor paste_spec(const TensorSpec& spec)
+{
+    sdm_align_tensor s{};
+    s.dtype = spec.dtype; s.layout = spec.layout; s.channels = spec.channels; s.order = spec.order; s.gray_shift = spec.gray_shift;
+    for (int k = 0; k < 3; ++k) { s.scale[k] = spec.scale[k]; s.bias[k] = spec.bias[k]; }
+    return s;
+}
+
+inline std::vector<sdm_frame> paste_frames(const std::vector<DeviceFrame>& frames)
+{
+    std::vector<sdm_frame> f;
+    for (const auto& d : frames) f.push_back(sdm_frame{d.data, d.width, d.height, d.stride_bytes, d.format});
+    return f;
+}
+
+// the n current rows of the handle `c`: the fit of aligned_crops_tensor, then the tensor at `in_dev` pasted into `frames` in place
+inline paste_result paste_current_rows(sdm_ctx* c, int n, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                       const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames, const PasteMask& mask)
+{
+    using superviseddescent::hip::check;
+    if (tmpl.rows != (int)landmark_index.size() || tmpl.cols != 2) throw std::runtime_error("paste_crops_tensor: one template point (x, y) per landmark");
+    cv::Mat t = tmpl.isContinuous() ? tmpl : tmpl.clone();
+    const std::vector<sdm_frame> f = paste_frames(frames);
+    const sdm_align_tensor s = paste_spec(spec);
+    const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
+    paste_result res;
+    res.matrices = cv::Mat(n, 6, CV_32FC1);
+    res.flags.resize((size_t)n);
+    check(sdm_align_paste_tensor(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s, in_dev, &p,
+                                 f.empty() ? nullptr : f.data(), (int)f.size(), res.matrices.ptr<float>(0), res.flags.data()),
+          "sdm_align_paste_tensor");
+    return res;
+}
+
+}  // namespace detail
+
+/** The way back of aligned_crops_tensor: `in_dev` -- a network's output on the crops of the tracker's last step, rows * channels * height *
+ *  width elements of spec.dtype in spec.layout, 16-byte aligned device memory -- is warped back through every stream's fitted similarity
+ *  and blended into `frames` IN PLACE (the frames of that step, GRAY / BGR / RGB / BGRA / RGBA; NV12 is refused), in one launch
+ *  (include/sdm.h, "Pasting crops back").  An element is decoded as e * spec.scale[c] + spec.bias[c]: scale = std, bias = mean in 0-255
+ *  units undo TensorSpec::normalise(mean, std) of the crop call. */
+inline paste_result paste_crops_tensor(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                       const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames,
+                                       const PasteMask& mask = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("paste_crops_tensor: step the tracker first");
+    return detail::paste_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask);
+}
+
+/** The same for landmark rows on device frames (as the detection_model overload of aligned_crops_tensor: a handle of its own, the frames
+ *  as its image set, the rows uploaded): row i is pasted into frames[image_index[i]] (default: frames[i]). */
+inline paste_result paste_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                       const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
+                                       int height, const TensorSpec& spec, const void* in_dev, const PasteMask& mask = {})
+{
+    using superviseddescent::hip::check;
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    sdm_ctx* c = h.get();
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::set_device_frames(h, frames);
+    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
+    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("paste_crops_tensor: rows must hold 2L coordinates");
+    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
+    return detail::paste_current_rows(c, x.rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask);
+}
+
+/** The explicit form (sdm_align_paste_tensor_at): `matrices` rows x 6 CV_32FC1 as an earlier crop call returned them -- the rows need not
+ *  be current any more; no model, no landmark state.  Row i goes to frames[image_index[i]] (default: frames[i]).  The result's matrices
+ *  are the ones given. */
+inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>& image_index, int width, int height, const TensorSpec& spec,
+                                       const void* in_dev, const std::vector<DeviceFrame>& frames, const PasteMask& mask = {})
+{
+    using superviseddescent::hip::check;
+    if (matrices.type() != CV_32FC1 || matrices.cols != 6 || matrices.rows < 1) throw std::runtime_error("paste_crops_tensor: matrices must be rows x 6 CV_32FC1");
+    if (!image_index.empty() && (int)image_index.size() != matrices.rows) throw std::runtime_error("paste_crops_tensor: one image index per row");
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    paste_result res;
+    res.matrices = matrices.isContinuous() ? matrices : matrices.clone();
+    res.flags.resize((size_t)matrices.rows);
+    const std::vector<sdm_frame> f = detail::paste_frames(frames);
+    const sdm_align_tensor s = detail::paste_spec(spec);
+    const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
+    check(sdm_align_paste_tensor_at(h.get(), res.matrices.ptr<float>(0), image_index.empty() ? nullptr : image_index.data(), matrices.rows, width,
+                                    height, &s, in_dev, &p, f.empty() ? nullptr : f.data(), (int)f.size(), res.flags.data()),
+          "sdm_align_paste_tensor_at");
+    return res;
 }
 
 }  // namespace rcr
