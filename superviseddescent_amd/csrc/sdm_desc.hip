@@ -339,7 +339,15 @@ template <int TO, int VARIANT, bool FUSED, int FB, int W = DS_WAVES>
 void launch_desc(const float* cells, const int* cut, int N, int L, float* feat, long long ldf, int has_bias, const void* planes, int NT,
                  const unsigned* rmax, const float* Rt, long long ldr, float* partial, hipStream_t stream)
 {
-    const size_t lds = FUSED ? desc_stage_bytes(desc_pk(25, desc_dim(TO, VARIANT)), FB) : 0;
+    // The 16-face instances (9 orientations) must have a compute unit to themselves.  Two of their workgroups fit one CU's LDS (52 / 65 KB
+    // each), and whenever two were resident together -- any grid of more workgroups than the chip has CUs -- the later one's product read
+    // a staged row of waves 4 ... 7 (an odd face of the tile) that did not hold what those waves had stored: one face of a batch moved by
+    // up to 1.4 pixels from run to run, 53 of 300 repeats at 72 landmarks x 70 faces, every repeat at 22 x 512
+    // (profiles/landmark_count_tests.txt).  The cells read and the instruction stream are right (the LDS stores are waited for in
+    // front of the barrier, a second barrier changes nothing), so the cause lies below this source and is not known; the 32-face
+    // instances, three to a CU, never showed it.  Asking for 40 KB more than the stage needs leaves room for one workgroup per CU:
+    // 0 of 500 repeats differ.
+    const size_t lds = FUSED ? desc_stage_bytes(desc_pk(25, desc_dim(TO, VARIANT)), FB) + (FB == 16 ? 40 * 1024 : 0) : 0;
     const unsigned grid = (unsigned)(((long long)N + FB - 1) / FB * L);
     static unsigned long long seen = 0;
     if (FUSED && sdm_first_use_on_device(seen))

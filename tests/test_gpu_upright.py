@@ -8,6 +8,7 @@ import align_ref as A
 import pose_f64 as P
 import track_ref as T
 import upright_cases as C
+from upright_cases import BOXES, IDX, ROLLS, ragged_frames
 import upright_ref as U
 from superviseddescent_amd import (Context, HoGParam, HogTransform, LinearRegressor, ModelProjection, Regulariser, SdmError,
                                    SupervisedDescentOptimiser, detection_model, ibug, synth)
@@ -79,29 +80,6 @@ def restated(dm, grays, idx, M, init, chip):
     chips = np.stack([U.chips(grays[i], m, chip) for i, m in zip(idx, M)])
     q = detect_from(dm, init, list(chips))
     return chips, q, U.back(M, q)
-
-
-def ragged_frames():
-    """five frames of different sizes on the device -- gray, a pitched odd-aligned view, gray, BGR, NV12 -- and their gray host copies
-    (the colour frame's is None: the context's conversion is read back)"""
-    import torch
-    rng = np.random.default_rng(99)
-    g0 = rng.integers(0, 256, (120, 160), dtype=np.uint8)
-    wide = rng.integers(0, 256, (131, 128), dtype=np.uint8)
-    g2 = rng.integers(0, 256, (64, 64), dtype=np.uint8)
-    bgr = rng.integers(0, 256, (48, 80, 3), dtype=np.uint8)
-    nv = rng.integers(0, 256, (75, 72), dtype=np.uint8)                # 70 x 50 luma rows of 72 bytes, 25 chroma rows behind
-    keep = [torch.from_numpy(a).cuda() for a in (g0, wide, g2, bgr, nv)]
-    frames = [keep[0], keep[1][:, 5:102], keep[2], keep[3], (keep[4].data_ptr(), 70, 50, 72, "nv12")]
-    grays = [g0, np.ascontiguousarray(wide[:, 5:102]), g2, None, np.ascontiguousarray(nv[:50, :70])]
-    return frames, grays, keep
-
-
-ROLLS = np.array([0, 0, 90, 180, -90, 17.3, -33, 45, 135, -150, 271, 360.5], np.float32)
-IDX = np.array([0, 0, 0, 1, 1, 1, 2, 3, 3, 4, 4, 2], np.int32)
-# boxes of 30 ... 70 pixels; rows 2, 5 and 8 hang over a frame edge, row 11 lies wholly outside its frame
-BOXES = np.array([[40, 30, 50, 50], [80, 40, 70, 60], [130, 80, 60, 55], [20, 40, 45, 45], [30, 60, 40, 50], [-20, 10, 50, 64],
-                  [10, 12, 40, 40], [20, 5, 36, 36], [50, 30, 44, 30], [15, 8, 30, 30], [25, 10, 33, 35], [100, -90, 40, 40]], np.int32)
 
 
 @pytest.mark.parametrize("chip", [32, 64, 97])

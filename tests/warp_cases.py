@@ -48,7 +48,7 @@ def mesh_254(w, h):
     return idx, t, np.concatenate(reps)[:254].astype(np.int32)
 
 
-def rows_for(frames, rows_to_frames, idx, template, w, h, seed, bend=0.02):
+def rows_for(frames, rows_to_frames, idx, template, w, h, seed, bend=0.02, L=L):
     """N x 2L float32 rows whose mesh landmarks are the template, sheared and bent a little (no longer a similarity; gentle enough that
     not even the mesh's slivers fold), seen through a similarity into the row's frame: scale, rotation and offset vary, and some rows
     reach over the border."""
