@@ -50,6 +50,8 @@ __host__ __device__ constexpr int hp_pair_slots(int cell, int C, bool cells, boo
 // (The ablation switches of rounds 3-6 -- HP_ABL = 1 ... 15: no folds, no read-modify-write, no image loads, conflict-free operand
 //  reads, ... -- are scripts/experiments/hog_packed_ablations.patch; scripts/r6_hog_lds_variants.sh applies it to a copy and builds
 //  the variants.  Their measurements: profiles/r04_hog_ablations.txt, profiles/r06_hog_lds.txt.)
+// (What a band fold costs by part -- no folds, no operand split, no stores, no matrix instructions, no clears -- is
+//  scripts/experiments/hog_fold_ablations.patch, measured in profiles/hog_fold_cost.txt.)
 // (The settled build switches of rounds 2-6 -- of this file, sdm_hog_fast.hip and sdm_hog_plan.hip; among them the float / double
 //  normalisation and the three- / four-product float16 fold that scripts/feature_error.py compared -- are
 //  scripts/experiments/hog_settled_switches.patch, which re-adds them to this tree.)
@@ -348,6 +350,10 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
 
     unsigned spread_sel = HF_SPREAD_SEL;
     asm volatile("" : "+v"(spread_sel));
+    // -1 in a scalar register, opaque to the optimiser: fma(half, -1, v) written with the literal is rewritten to a conversion and a
+    // subtraction; with the register it stays the one v_fma_mix_f32 of the fold's operand split
+    float neg_one = -1.0f;
+    if constexpr (CELLS) asm volatile("" : "+s"(neg_one));
     const int li = lane & 15, lq = lane >> 4;
 
     for (int t = t_first; t < npass; ++t) {
@@ -479,18 +485,49 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
                 const float* arow = colrows + (ROTB ? (int)HP_ROW_OF_BIN(pair ? (li & 7) : (li < 2 * O ? li : 2 * O - 1)) : (pair ? (li & 7) : (li < 2 * O ? li : 2 * O - 1))) * ST * 2
                                     + ((pair && (li >> 3)) ? (sl ^ 1) : sl) + 16 * lq;
                 f32x4 facc = {0.0f, 0.0f, 0.0f, 0.0f};
+                // CELLS: an operand is read AND cleared by ONE LDS instruction, an exchange with zero (ds_wrxchg_rtn_b32), instead of a
+                // read here and a bank-conflicted clear of the lane's own column below: the sixteen operands of lanes (li < 8, lq) are
+                // each entry of the folded slot exactly once (of both slots in a pair fold, where all sixteen li are rows), so the slot is
+                // all zero afterwards as after the clears, and a wave's own LDS accesses execute in order.  The clears were the largest
+                // separable part of a fold (4 % of the kernel, profiles/hog_fold_cost.txt).  Lanes li >= 8 of a one-band fold would
+                // repeat row 7, and which lane of an exchange gets the value of a shared address is not promised: they stay out, and
+                // whatever their registers hold feeds matrix rows 8 .. 15, whose results (lanes lq >= 2) nobody stores.
+                float vx[2][8];
+                if constexpr (CELLS) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) asm volatile("" : "=v"(vx[i >> 3][i & 7]));
+                    if (pair || li < 2 * O) {
+#pragma unroll
+                        for (int i = 0; i < 16; ++i)
+                            vx[i >> 3][i & 7] = __builtin_bit_cast(float, __hip_atomic_exchange((unsigned*)const_cast<float*>(&arow[64 * (i >> 3) + 2 * (i & 7)]), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT));
+                    }
+                }
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb) {
                     float v[8];
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) v[j] = arow[64 * kb + 2 * j];
+                    for (int j = 0; j < 8; ++j) v[j] = CELLS ? vx[kb][j] : arow[64 * kb + 2 * j];
                     unsigned hp_[4], lp_[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        const float h0 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v[2 * e]) & 0xffffe000u);
-                        const float h1 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v[2 * e + 1]) & 0xffffe000u);
-                        hp_[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(h0, h1));
-                        lp_[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v[2 * e] - h0, v[2 * e + 1] - h1));
+                        // first piece: v cut to float16's eleven significant bits, which is what the conversion toward zero does to a
+                        // float16-normal v -- and v is zero or normal: a non-zero column sum is a sum of non-negative terms
+                        // magnitude (>= 1 for a non-zero integer gradient) x band-slot weight (>= 1 / (2 cell)) x 8, each
+                        // >= 8 / 24 > 2^-14, and the static_assert above bounds it below 65 504.  Second piece: v minus the first,
+                        // exact in float32, by one mixed-precision multiply-add (v_fma_mix_f32) per value.  Four vector instructions
+                        // per pair of values (six with the piece cut out by a mask first), the same bits.
+                        // (The feature-row form keeps the mask: at its 80 registers the shorter split made cells 10 and 8 spill.)
+                        if constexpr (CELLS) {
+                            const auto hh = __builtin_amdgcn_cvt_pkrtz(v[2 * e], v[2 * e + 1]);
+                            hp_[e] = __builtin_bit_cast(unsigned, hh);
+                            lp_[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)hh[0], neg_one, v[2 * e]),
+                                                                                             __builtin_fmaf((float)hh[1], neg_one, v[2 * e + 1])));
+                        } else {
+                            const float h0 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v[2 * e]) & 0xffffe000u);
+                            const float h1 = __builtin_bit_cast(float, __builtin_bit_cast(unsigned, v[2 * e + 1]) & 0xffffe000u);
+                            hp_[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(h0, h1));
+                            lp_[e] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(v[2 * e] - h0, v[2 * e + 1] - h1));
+                        }
                     }
                     typedef unsigned u32x4f __attribute__((ext_vector_type(4)));
                     const f16x8 ah = __builtin_bit_cast(f16x8, (u32x4f){hp_[0], hp_[1], hp_[2], hp_[3]});
@@ -529,7 +566,8 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
             }
             }
             // every lane clears the slot(s) of its own pixel column (the LDS unit executes this wave's accesses in order)
-            if (pair) {
+            if (CELLS && F16F) { }      // (cleared by the operand exchange above)
+            else if (pair) {
 #pragma unroll
                 for (int k = 0; k < 2 * O; ++k) *(f32x2*)((float*)cbase0 + k * ST * 2) = (f32x2){0.0f, 0.0f};
             } else {
