@@ -781,8 +781,8 @@ int sdm_warp_crops_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, void* out_
  *           previous one left, whatever the launch order: a pixel is loaded once, every row whose footprint holds it is applied in
  *           registers in row order, and it is stored once.
  *   never stored to, not even with their old value: pitch padding, pixels outside every footprint, pixels whose every a is 0, alpha bytes.
- * Out of scope, and not half-built: NV12 destinations (refused), the piecewise-affine paste (the inverse of sdm_warp_crops_tensor), and
- * any antialiasing when the face in the frame is smaller than the crop -- the paste is plain bilinear, as sdm_align_crops is.
+ * Out of scope, and not half-built: NV12 destinations (refused) and any antialiasing when the face in the frame is smaller than the
+ * crop -- the paste is plain bilinear, as sdm_align_crops is.  (The inverse of sdm_warp_crops_tensor is "Pasting warped faces back".)
  * Refused with SDM_ERR_INVALID, no state changed, nothing launched: what sdm_align_crops_tensor refuses of landmark_index, template_xy,
  * K, the crop size, spec and the rows' source (fit form); in_dev NULL or not 16-byte aligned; paste NULL; alpha_per_row not 0 or 1;
  * dst_frames NULL or n_frames < 1; what sdm_set_frames_device refuses of a frame; an NV12 frame; a row whose image index is outside
@@ -803,6 +803,62 @@ int sdm_align_paste_tensor(sdm_ctx* ctx, const int* landmark_index, const float*
 int sdm_align_paste_tensor_at(sdm_ctx* ctx, const float* matrices_host /* in, n_rows x 6 */, const int* image_index /* NULL: row i -> frame i */,
                               int n_rows, int crop_width, int crop_height, const sdm_align_tensor* spec, const void* in_dev,
                               const sdm_align_paste* paste, const sdm_frame* dst_frames, int n_frames, int* flags_host);
+
+/* Pasting warped faces back: the inverse path of sdm_warp_crops_tensor.  A network's output in template space -- a transferred
+ * expression, a swapped, re-lit or de-aged texture -- is warped back under the face's own shape, triangle by triangle, and blended into
+ * the frames in place: the fit of sdm_warp_crops_tensor, one launch per (row, triangle), one launch for the pixels.  Both forms use the
+ * mesh of sdm_warp_set_mesh; the crop is its out_width x out_height.  in_dev, spec, paste and dst_frames mean exactly what they mean for
+ * sdm_align_paste_tensor (formats, alignment, pitch, 64-bit offsets, NV12 refused, scale / bias the inverse of the crop call's, the size
+ * rule of the fit form, the alpha byte never touched).  Every expression is evaluated as written: double on the float32 inputs where
+ * marked, each operation rounded on its own, nothing contracted.
+ *   points  p_k, the row's K mesh landmarks as float32: (x[idx_k], x[L + idx_k]) of the current rows (sdm_warp_paste_tensor) or row n of
+ *           points_host (sdm_warp_paste_tensor_at).  A_t per triangle is that of "Warped faces": the same code on the same points gives
+ *           the same bits in both forms.
+ *   flags   the SDM_WARP_* bits.  DEGENERATE: a mesh landmark is not finite; the row pastes nothing and no other bit is evaluated.
+ *           PARTIAL: the warp's rule against the destination frame's width and height.  FOLDED: the warp's rule.
+ *   box     x0 = floor(min_k p_k.x), x1 = ceil(max_k p_k.x) + 1, y the same, formed in double and clipped to the frame before any
+ *           conversion to int.  A pixel outside [x0, x1) x [y0, y1) is outside the row's footprint.
+ *   triangle   of frame pixel (column X, row Y).  Per triangle, in double: det E = E00 E11 - E01 E10 (the FOLDED rule's expression).
+ *           det E == 0: the triangle covers nothing.  det E < 0: b and c are exchanged, for the edge functions only.  The edge functions
+ *           are e0, e1, e2 of the label map with p_a, p_b, p_c in place of the template points and x = (double)X, y = (double)Y.  W_t is
+ *           the inverse of the float32 A_t by the formula of "Pasting crops back" (double, each of the six entries rounded once to
+ *           float32); a triangle with d == 0 or an entry of W_t that is not finite is skipped as if it were absent.  A triangle has a
+ *           box of its own: floor(min(p_a.x, p_b.x, p_c.x)) - 1 <= X < ceil(max(p_a.x, p_b.x, p_c.x)) + 2 and the same in y, in double;
+ *           it covers no pixel outside it, whatever the edge functions say.  (With exact arithmetic the box holds every pixel the edge
+ *           functions accept, with a pixel to spare.  The rounded edge functions of a needle triangle with a corner far outside the
+ *           frame -- 1e9 and beyond -- can be >= 0 many pixels past its corners; the box makes the answer one that every path of the
+ *           kernel gives alike.)  The pixel takes the lowest-numbered remaining triangle whose box holds it and with e0 >= 0, e1 >= 0
+ *           and e2 >= 0 (a comparison with a NaN is false) -- also on an edge two triangles share, where a folded shape overlaps
+ *           itself, and under a FOLDED triangle: such pixels follow the formula.
+ *   position   u = (W_t00 X + W_t01 Y) + W_t02, v likewise, in float32, then sdm_align_crops' quantisation.  The pixel is IN THE
+ *           FOOTPRINT of the row when it is in the box, has a triangle, u and v are finite with |u|, |v| <= 2^20, and
+ *           -1 <= u0 <= crop_width - 1, -1 <= v0 <= crop_height - 1.  (The position of the pixel's one triangle decides: no second
+ *           triangle is tried.)
+ *   colour  the four taps, their clamping into the crop, the decode and (... + 512) >> 10 of "Pasting crops back", unchanged.
+ *   opacity a tap reads 0 when it lies outside the crop OR ITS CROP PIXEL HAS LABEL 255; otherwise the opacity map's byte, or 255 with
+ *           alpha_dev NULL; the same weights and rounding.  The hull of the mesh therefore fades over one pixel by itself.  The warp
+ *           writes v = 0 outside the hull; the colour taps still read those elements, at the reduced opacity.  A caller who wants them
+ *           gone passes a map that fades inside the hull.
+ *   write, several rows on one frame, never stored to   those of "Pasting crops back", word for word: the blend divides by 255, a pixel
+ *           is loaded once, every row of the frame whose footprint holds it is applied in increasing row number in registers, it is
+ *           stored once and only if some opacity was not 0, stores are per byte.
+ * Out of scope, and not half-built: NV12 destinations (refused); any antialiasing when the face in the frame is smaller than its crop;
+ * a colour renormalised at the hull's border.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched: no mesh (none set, or sdm_set_model_geometry has changed L since);
+ * fit form: no current rows, and sdm_warp_crops_tensor's rules on the rows' source sizes; everything sdm_align_paste_tensor refuses of
+ * spec, in_dev, paste, dst_frames, n_frames, an NV12 frame, a row's image index or a size mismatch; _at form: points_host NULL or
+ * n_rows < 1. */
+/* the current rows.  in_dev: N * channels * out_height * out_width elements.  matrices_host (N x T x 6: the A_t bits that
+ * sdm_warp_crops_tensor returns) and flags_host (N) may be NULL; they come back behind the call's one synchronise.  Neither the landmark
+ * state, the images, the crop source nor the tracker's slots are changed. */
+int sdm_warp_paste_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste,
+                          const sdm_frame* dst_frames, int n_frames, float* matrices_host /* out, N x T x 6, may be NULL */,
+                          int* flags_host /* out, may be NULL */);
+/* explicit landmarks: the mesh is needed, but no landmark state, no geometry rows and no context images -- the network may run on frame t
+ * while the tracker has stepped to t + 1 */
+int sdm_warp_paste_tensor_at(sdm_ctx* ctx, const float* points_host /* in, n_rows x K x 2: (x, y) of the mesh's k-th landmark */,
+                             const int* image_index /* NULL: row i -> frame i */, int n_rows, const sdm_align_tensor* spec,
+                             const void* in_dev, const sdm_align_paste* paste, const sdm_frame* dst_frames, int n_frames, int* flags_host);
 
 #ifdef __cplusplus
 }

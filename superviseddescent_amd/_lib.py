@@ -40,6 +40,7 @@ EXPORTED = [
     "sdm_upright_configure", "sdm_detect_batch_upright", "sdm_upright_get", "sdm_track_configure_upright", "sdm_track_start_rolled",
     "sdm_warp_delaunay", "sdm_warp_set_mesh", "sdm_warp_get_labels", "sdm_warp_crops_tensor",
     "sdm_align_paste_tensor", "sdm_align_paste_tensor_at",
+    "sdm_warp_paste_tensor", "sdm_warp_paste_tensor_at",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -445,6 +446,10 @@ def lib() -> ctypes.CDLL:
                                        ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_int, c_void_p, c_void_p],
             "sdm_align_paste_tensor_at": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,
                                           ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_int, c_void_p],
+            "sdm_warp_paste_tensor": [c_void_p, ctypes.POINTER(SdmAlignTensor), c_void_p, ctypes.POINTER(SdmAlignPaste),
+                                      ctypes.POINTER(SdmFrame), c_int, c_void_p, c_void_p],
+            "sdm_warp_paste_tensor_at": [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,
+                                         ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_int, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

@@ -1,9 +1,10 @@
 // sdm_align_paste_device.h -- the arithmetic of the paste-back of crop tensors into frames (include/sdm.h, "Pasting crops back"): a row's
 // inverse map, flags and box (paste_prepare_row), the footprint test, the decoded taps, the integer bilinear colour and opacity
-// (paste_sample), the blend, and paste_pixel -- what one frame pixel's owner does from the ownership test to its one store.  The
-// quantisation, the weights, the gray rule and the element formula are sdm_align_tensor_device.h's.  Plain C++ behind one macro, so the
-// same text is the device code of csrc/sdm_align_paste.hip and -- compiled for the host, tests/cpp/align_paste_host.cpp -- a program
-// that runs under the host sanitizers on frames, tensors and opacity maps of exactly the bytes they own.
+// (paste_sample), the blend, the pixel's load / apply / store, and paste_pixel -- what one frame pixel's owner does from the ownership
+// test to its one store.  The quantisation, the weights, the gray rule and the element formula are sdm_align_tensor_device.h's.  Plain
+// C++ behind one macro, so the same text is the device code of csrc/sdm_align_paste.hip and -- compiled for the host,
+// tests/cpp/align_paste_host.cpp -- a program that runs under the host sanitizers on frames, tensors and opacity maps of exactly the
+// bytes they own.
 //
 // Every float operation is rounded on its own (no contraction: the pragma below under clang, -ffp-contract=off elsewhere); everything
 // else is int32 / uint32 arithmetic, every offset 64-bit.
@@ -50,6 +51,18 @@ struct PasteCropDev {
     PasteTensorDev t;
 };
 
+// W (frame -> crop) of a float32 M (crop -> frame): in double, each of the six entries rounded once to float32; returns d
+ALIGN_HD double paste_inverse(const float m[6], float w[6])
+{
+    const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5];
+    const double d = m00 * m11 - m01 * m10;
+    const double w00 = m11 / d, w01 = -m01 / d, w10 = -m10 / d, w11 = m00 / d;
+    const double w02 = -(w00 * m02 + w01 * m12), w12 = -(w10 * m02 + w11 * m12);
+    w[0] = (float)w00; w[1] = (float)w01; w[2] = (float)w02;
+    w[3] = (float)w10; w[4] = (float)w11; w[5] = (float)w12;
+    return d;
+}
+
 // M00 M01 M02 M10 M11 M12 (float32, crop -> frame) of a row in a frame of fw x fh pixels: W, the flags and the box.  flags_in: the
 // fit's flags, or -1 -- then PARTIAL is the fit's rule evaluated here, on the corner pixel centres of the crop.
 ALIGN_HD void paste_prepare_row(const float m[6], int flags_in, int frame, int fw, int fh, int cw, int ch, PasteRow& r)
@@ -69,11 +82,7 @@ ALIGN_HD void paste_prepare_row(const float m[6], int flags_in, int frame, int f
             }
     }
     const double m00 = m[0], m01 = m[1], m02 = m[2], m10 = m[3], m11 = m[4], m12 = m[5];
-    const double d = m00 * m11 - m01 * m10;
-    const double w00 = m11 / d, w01 = -m01 / d, w10 = -m10 / d, w11 = m00 / d;
-    const double w02 = -(w00 * m02 + w01 * m12), w12 = -(w10 * m02 + w11 * m12);
-    r.w[0] = (float)w00; r.w[1] = (float)w01; r.w[2] = (float)w02;
-    r.w[3] = (float)w10; r.w[4] = (float)w11; r.w[5] = (float)w12;
+    const double d = paste_inverse(m, r.w);
     bool ok = finite && !(flags & SDM_ALIGN_DEGENERATE) && d != 0.0;
     for (int e = 0; e < 6; ++e) ok = ok && isfinite(r.w[e]);
     if (!ok) {
@@ -155,8 +164,10 @@ ALIGN_HD uint32_t paste_decode(const PasteCropDev& c, long long e, int ch)
     return (uint32_t)rintf(fminf(fmaxf(f, 0.0f), 255.0f));
 }
 
-// the sampled (B, G, R) and opacity of row n's crop at the quantised position q (inside the footprint)
-ALIGN_HD void paste_sample(const PasteCropDev& c, int n, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
+// the sampled (B, G, R) and opacity of row n's crop at the quantised position q (inside the footprint).  LABELLED (the piecewise-affine
+// paste, csrc/sdm_warp_paste_device.h): a tap whose crop pixel has label 255 in `labels` (crop_height x crop_width bytes) reads opacity 0
+template <bool LABELLED>
+ALIGN_HD void paste_sample_taps(const PasteCropDev& c, int n, const AlignPos& q, const uint8_t* labels, uint32_t bgr[3], uint32_t& a)
 {
     const uint32_t wt[4] = {(uint32_t)((32 - q.fx) * (32 - q.fy)), (uint32_t)(q.fx * (32 - q.fy)), (uint32_t)((32 - q.fx) * q.fy),
                             (uint32_t)(q.fx * q.fy)};
@@ -166,7 +177,8 @@ ALIGN_HD void paste_sample(const PasteCropDev& c, int n, const AlignPos& q, uint
         const int x = q.x0 + (k & 1), y = q.y0 + (k >> 1);
         const bool in = x >= 0 && x < c.cw && y >= 0 && y < c.ch;
         const int xc = x < 0 ? 0 : (x > c.cw - 1 ? c.cw - 1 : x), yc = y < 0 ? 0 : (y > c.ch - 1 ? c.ch - 1 : y);
-        if (in) asum += wt[k] * (c.alpha ? (uint32_t)c.alpha[(long long)n * c.an + (long long)yc * c.cw + xc] : 255u);
+        if (in && (!LABELLED || labels[(long long)yc * c.cw + xc] != 255u))
+            asum += wt[k] * (c.alpha ? (uint32_t)c.alpha[(long long)n * c.an + (long long)yc * c.cw + xc] : 255u);
         const long long e = (long long)n * c.sn + (long long)yc * c.sy + (long long)xc * c.sx;
         if (c.channels == 3) {
 #pragma unroll
@@ -185,7 +197,56 @@ ALIGN_HD void paste_sample(const PasteCropDev& c, int n, const AlignPos& q, uint
     }
 }
 
+ALIGN_HD void paste_sample(const PasteCropDev& c, int n, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
+{
+    paste_sample_taps<false>(c, n, q, nullptr, bgr, a);
+}
+
 ALIGN_HD uint32_t paste_blend(uint32_t a, uint32_t q, uint32_t o) { return (a * q + (255u - a) * o + 127u) / 255u; }
+
+// One frame pixel in its owner's registers: the old colour bytes loaded once (paste_load), every row's sample blended in (paste_apply),
+// the colour bytes stored once, byte by byte, if any opacity was not 0 (paste_store).  Shared by both pastes.
+struct PastePixel {
+    uint8_t* p;
+    uint32_t o[3];
+    int nb;                     // colour bytes: 1 | 3 (the alpha byte is neither read nor written)
+    bool swap, any;
+};
+
+ALIGN_HD void paste_load(const PasteFrameDev& f, int X, int Y, PastePixel& s)
+{
+    const int bpp = f.format == SDM_FRAME_GRAY ? 1 : (f.format == SDM_FRAME_BGR || f.format == SDM_FRAME_RGB) ? 3 : 4;
+    s.nb = bpp == 1 ? 1 : 3;
+    s.p = f.p + ((long long)Y * f.stride + (long long)X * bpp);
+    s.o[0] = s.o[1] = s.o[2] = 0u;
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+        if (b < s.nb) s.o[b] = s.p[b];
+    s.swap = f.format == SDM_FRAME_RGB || f.format == SDM_FRAME_RGBA;
+    s.any = false;
+}
+
+ALIGN_HD void paste_apply(const PasteCropDev& c, const uint32_t bgr[3], uint32_t a, PastePixel& s)
+{
+    if (a == 0u) return;
+    s.any = true;
+    if (s.nb == 1) {
+        const uint32_t g = c.channels == 3 ? (bgr[0] * c.t.wb + bgr[1] * c.t.wg + bgr[2] * c.t.wr + (1u << (c.t.gray_shift - 1))) >> c.t.gray_shift
+                                           : bgr[0];
+        s.o[0] = paste_blend(a, g, s.o[0]);
+    } else {
+#pragma unroll
+        for (int b = 0; b < 3; ++b) s.o[b] = paste_blend(a, bgr[s.swap ? 2 - b : b], s.o[b]);
+    }
+}
+
+ALIGN_HD void paste_store(const PastePixel& s)
+{
+    if (!s.any) return;
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+        if (b < s.nb) s.p[b] = (uint8_t)s.o[b];
+}
 
 // Frame pixel (X, Y) as seen by entry k of its frame's row list: nothing unless the pixel is in that row's footprint and in no earlier
 // entry's -- then this is the pixel's one reader and writer: the old bytes once, every later entry of the list that holds the pixel
@@ -198,33 +259,14 @@ ALIGN_HD void paste_pixel(const PasteFrameDev& f, const PasteRow* rows, const in
         AlignPos qj;
         if (paste_footprint(rows[list[j]], c.cw, c.ch, X, Y, qj)) return;
     }
-    const int bpp = f.format == SDM_FRAME_GRAY ? 1 : (f.format == SDM_FRAME_BGR || f.format == SDM_FRAME_RGB) ? 3 : 4;
-    const int nb = bpp == 1 ? 1 : 3;                                // (the alpha byte is neither read nor written)
-    uint8_t* p = f.p + ((long long)Y * f.stride + (long long)X * bpp);
-    uint32_t o[3] = {0u, 0u, 0u};
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-        if (b < nb) o[b] = p[b];
-    const bool swap = f.format == SDM_FRAME_RGB || f.format == SDM_FRAME_RGBA;
-    bool any = false;
+    PastePixel s;
+    paste_load(f, X, Y, s);
     for (int j = k; j < f.row_end; ++j) {
         const int n = list[j];
         if (j > k && !paste_footprint(rows[n], c.cw, c.ch, X, Y, q)) continue;
         uint32_t bgr[3], a;
         paste_sample(c, n, q, bgr, a);
-        if (a == 0u) continue;
-        any = true;
-        if (nb == 1) {
-            const uint32_t g = c.channels == 3 ? (bgr[0] * c.t.wb + bgr[1] * c.t.wg + bgr[2] * c.t.wr + (1u << (c.t.gray_shift - 1))) >> c.t.gray_shift
-                                               : bgr[0];
-            o[0] = paste_blend(a, g, o[0]);
-        } else {
-#pragma unroll
-            for (int b = 0; b < 3; ++b) o[b] = paste_blend(a, bgr[swap ? 2 - b : b], o[b]);
-        }
+        paste_apply(c, bgr, a, s);
     }
-    if (!any) return;
-#pragma unroll
-    for (int b = 0; b < 3; ++b)
-        if (b < nb) p[b] = (uint8_t)o[b];
+    paste_store(s);
 }

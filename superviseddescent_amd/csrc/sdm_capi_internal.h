@@ -334,8 +334,13 @@ struct sdm_ctx {
         DevBuf<unsigned char> tri;         // T WarpTri records (csrc/sdm_warp_device.h)
         DevBuf<int> lm;                    // K
         DevBuf<unsigned char> rows;        // N WarpFace records, then N x T x 6 floats
-        void drop() { K = T = L = out_w = out_h = 0; labels_host.clear(); }
-        void release() { drop(); labels.release(); tri.release(); lm.release(); rows.release(); }
+        // the piecewise-affine paste (sdm_capi_paste.hip): the landmark indices on the host, the uploaded points of the _at form in the
+        // landmark state's layout, and a call's N WarpPasteRow records with the N x T WarpPasteTri records behind them
+        std::vector<int> lm_host;
+        DevBuf<float> points;
+        DevBuf<unsigned char> paste;
+        void drop() { K = T = L = out_w = out_h = 0; labels_host.clear(); lm_host.clear(); }
+        void release() { drop(); labels.release(); tri.release(); lm.release(); rows.release(); points.release(); paste.release(); }
     } warp;
     // host copies of the image sizes and of the sample -> image index (the checks of an external crop source)
     std::vector<int> img_w_host, img_h_host, img_idx_host;

@@ -1,10 +1,13 @@
-// sdm_capi_paste.hip -- C-ABI of the paste-back of crop tensors into frames (include/sdm.h, "Pasting crops back"): the two entry points
-// check every argument before anything is launched or changed, build the frame table and the rows-of-frame lists on the host from the
+// sdm_capi_paste.hip -- C-ABI of the paste-back of crop tensors into frames (include/sdm.h, "Pasting crops back" and "Pasting warped
+// faces back"): the entry points check every argument before anything is launched or changed, build the frame table and the rows-of-frame lists on the host from the
 // image index they already hold, and enqueue -- fit form -- sdm_align_crops' fit, then the prepare kernel and the one paste launch
-// (csrc/sdm_align_paste.hip).  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
+// (csrc/sdm_align_paste.hip); the piecewise-affine forms enqueue warp_fit_kernel, their prepare kernel and their paste launch
+// (csrc/sdm_warp_paste.hip) on the mesh of sdm_warp_set_mesh.  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
 // landmark state, the images, the crop source and the tracker's slots are only read; the frames' colour bytes are written in place.
 #include "sdm_capi_internal.h"
 #include "sdm_align_paste_device.h"
+#include "sdm_warp.h"
+#include "sdm_warp_paste.h"
 
 #include <cmath>
 
@@ -41,15 +44,23 @@ int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm
     return SDM_OK;
 }
 
-// behind the checks: `faces` holds N records with M (fitted: and the fit's flags).  frame_of_row: N checked indices.
-int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int cw, int ch, const sdm_align_tensor* spec, const void* in_dev,
-              const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host, int* flags_host)
+// the device tables of a call in align.paste_tab: the frame table, the row -> frame index, the rows of every frame in ascending order,
+// and every row's place among them (enqueued; nothing waits: `blob`, the host side of the copy, lives until the call's synchronise)
+struct PasteTables {
+    const PasteFrameDev* frames;
+    const int* of_row;
+    const int* list;
+    const int* entry;
+    std::vector<unsigned char> blob;
+};
+
+int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_frame* frames, int n_frames, PasteTables& out)
 {
     sdm_ctx::Align& a = c->align;
     const int N = (int)frame_of_row.size();
-    // the frame table, the row -> frame index, the rows of every frame in ascending order, and every row's place among them
     const size_t tab_bytes = (size_t)n_frames * sizeof(PasteFrameDev), bytes = tab_bytes + (size_t)3 * N * sizeof(int);
-    std::vector<unsigned char> blob(bytes);
+    std::vector<unsigned char>& blob = out.blob;
+    blob.assign(bytes, 0);
     PasteFrameDev* tab = (PasteFrameDev*)blob.data();
     int* of_row = (int*)(blob.data() + tab_bytes);
     int* list = of_row + N;
@@ -67,13 +78,18 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
     std::vector<int> fill(count.begin(), count.end() - 1);
     for (int r = 0; r < N; ++r) { const int at = fill[frame_of_row[r]]++; list[at] = r; entry[r] = at; }
     int rc;
-    if ((rc = a.paste_tab.ensure(bytes)) || (rc = a.paste_rows.ensure((size_t)N * sizeof(PasteRow)))) return rc;
+    if ((rc = a.paste_tab.ensure(bytes))) return rc;
     HIP_TRY(hipMemcpyAsync(a.paste_tab.p, blob.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    const PasteFrameDev* tab_dev = (const PasteFrameDev*)a.paste_tab.p;
-    const int* of_row_dev = (const int*)(a.paste_tab.p + tab_bytes);
-    PasteRow* rows_dev = (PasteRow*)a.paste_rows.p;
-    sdm_launch_paste_prepare(a.faces.p, of_row_dev, tab_dev, N, cw, ch, fitted, rows_dev, c->stream);
-    HIP_TRY(hipGetLastError());
+    out.frames = (const PasteFrameDev*)a.paste_tab.p;
+    out.of_row = (const int*)(a.paste_tab.p + tab_bytes);
+    out.list = out.of_row + N;
+    out.entry = out.of_row + 2 * N;
+    return SDM_OK;
+}
+
+// the tensor and the opacity maps of a call as the pixel code reads them
+PasteCropDev paste_crop_dev(const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, int cw, int ch)
+{
     PasteCropDev crop{};
     crop.in = in_dev; crop.alpha = paste->alpha_dev;
     crop.cw = cw; crop.ch = ch; crop.dtype = spec->dtype; crop.channels = spec->channels;
@@ -84,6 +100,24 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
     const AlignTensorDev t = align_tensor_dev(spec);
     for (int k = 0; k < 3; ++k) { crop.t.scale[k] = t.scale[k]; crop.t.bias[k] = t.bias[k]; }
     crop.t.order = t.order; crop.t.wb = t.wb; crop.t.wg = t.wg; crop.t.wr = t.wr; crop.t.gray_shift = t.gray_shift;
+    return crop;
+}
+
+// behind the checks: `faces` holds N records with M (fitted: and the fit's flags).  frame_of_row: N checked indices.
+int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int cw, int ch, const sdm_align_tensor* spec, const void* in_dev,
+              const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host, int* flags_host)
+{
+    sdm_ctx::Align& a = c->align;
+    const int N = (int)frame_of_row.size();
+    int rc;
+    PasteTables tab;
+    if ((rc = a.paste_rows.ensure((size_t)N * sizeof(PasteRow))) || (rc = paste_tables(c, frame_of_row, frames, n_frames, tab))) return rc;
+    const PasteFrameDev* tab_dev = tab.frames;
+    const int* of_row_dev = tab.of_row;
+    PasteRow* rows_dev = (PasteRow*)a.paste_rows.p;
+    sdm_launch_paste_prepare(a.faces.p, of_row_dev, tab_dev, N, cw, ch, fitted, rows_dev, c->stream);
+    HIP_TRY(hipGetLastError());
+    const PasteCropDev crop = paste_crop_dev(spec, in_dev, paste, cw, ch);
     sdm_launch_paste(tab_dev, rows_dev, of_row_dev + N, of_row_dev + 2 * N, N, crop, c->stream);
     HIP_TRY(hipGetLastError());
     // the records in one copy, one synchronise
@@ -100,9 +134,110 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
     return SDM_OK;
 }
 
+// The piecewise-affine paste behind its checks.  x: N x 2L on the device (the landmark state, or the uploaded points in its layout);
+// src, img_idx: what warp_fit_kernel takes for its own record (the prepare kernel takes FOLDED from it and evaluates PARTIAL against the destination frames).
+int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const int* img_idx, const std::vector<int>& frame_of_row,
+                   const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames,
+                   float* matrices_host, int* flags_host)
+{
+    sdm_ctx::Warp& w = c->warp;
+    const int N = (int)frame_of_row.size(), T = w.T;
+    int rc;
+    const size_t rec = (size_t)N * sizeof(WarpFace), mat = (size_t)N * T * 6 * sizeof(float);
+    const size_t rows_bytes = (size_t)N * sizeof(WarpPasteRow), tris_bytes = (size_t)N * T * sizeof(WarpPasteTri);
+    PasteTables tab;
+    if ((rc = w.rows.ensure(rec + mat)) || (rc = w.paste.ensure(rows_bytes + tris_bytes)) ||
+        (rc = paste_tables(c, frame_of_row, frames, n_frames, tab)))
+        return rc;
+    WarpFace* faces = (WarpFace*)w.rows.p;
+    float* matrices = (float*)(w.rows.p + rec);
+    WarpPasteRow* rows_dev = (WarpPasteRow*)w.paste.p;
+    WarpPasteTri* tris_dev = (WarpPasteTri*)(w.paste.p + rows_bytes);
+    sdm_launch_warp_fit(x, N, w.L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, src, img_idx, faces, matrices, c->stream);
+    HIP_TRY(hipGetLastError());
+    sdm_launch_warp_paste_prepare(x, N, w.L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, faces, matrices, tab.of_row, tab.frames, rows_dev,
+                                  tris_dev, c->stream);
+    HIP_TRY(hipGetLastError());
+    sdm_launch_warp_paste(tab.frames, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p,
+                          paste_crop_dev(spec, in_dev, paste, w.out_w, w.out_h), c->stream);
+    HIP_TRY(hipGetLastError());
+    // the matrices and the rows' records, one synchronise
+    std::vector<WarpPasteRow> host;
+    if (matrices_host) HIP_TRY(hipMemcpyAsync(matrices_host, matrices, mat, hipMemcpyDeviceToHost, c->stream));
+    if (flags_host) {
+        host.resize((size_t)N);
+        HIP_TRY(hipMemcpyAsync(host.data(), rows_dev, rows_bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t r = 0; r < host.size(); ++r) flags_host[r] = host[r].flags;
+    return SDM_OK;
+}
+
+int warp_paste_check_mesh(sdm_ctx* c)
+{
+    if (c->L <= 0) return fail(SDM_ERR_INVALID, "geometry not set");
+    if (c->warp.T < 1 || c->warp.L != c->L) return fail(SDM_ERR_INVALID, "no mesh (sdm_warp_set_mesh first)");
+    return SDM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int sdm_warp_paste_tensor(sdm_ctx* c, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
+                          int n_frames, float* matrices_host, int* flags_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    int rc;
+    if ((rc = warp_paste_check_mesh(c))) return rc;
+    const int N = c->N;
+    if (N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
+    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames)) || (rc = align_check_rows(c))) return rc;
+    std::vector<int> frame_of_row((size_t)N);
+    for (int r = 0; r < N; ++r) {
+        const int im = c->idx_identity ? r : c->img_idx_host[r];
+        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to image " + std::to_string(im) + ", beyond the frames");
+        if (frames[im].width != c->img_w_host[im] || frames[im].height != c->img_h_host[im])
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(im) + " differs in size from image " + std::to_string(im) + " of the context");
+        frame_of_row[r] = im;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    return warp_paste_run(c, c->x[c->cur].p, align_source_dev(c), c->idx_identity ? nullptr : c->img_idx.p, frame_of_row, spec, in_dev, paste,
+                          frames, n_frames, matrices_host, flags_host);
+}
+
+int sdm_warp_paste_tensor_at(sdm_ctx* c, const float* points_host, const int* image_index, int n_rows, const sdm_align_tensor* spec,
+                             const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, int* flags_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    int rc;
+    if ((rc = warp_paste_check_mesh(c))) return rc;
+    if (!points_host) return fail(SDM_ERR_INVALID, "no points");
+    if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
+    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames))) return rc;
+    sdm_ctx::Warp& w = c->warp;
+    const int L = w.L, K = w.K;
+    std::vector<int> frame_of_row((size_t)n_rows);
+    // the points in the landmark state's layout (row: L x then L y), the mesh's landmarks at their indices, 0 elsewhere: the fit and the
+    // prepare kernel read them as they read the state
+    std::vector<float> x((size_t)n_rows * 2 * L, 0.0f);
+    for (int r = 0; r < n_rows; ++r) {
+        const int im = image_index ? image_index[r] : r;
+        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to frame " + std::to_string(im) + ", outside the list");
+        frame_of_row[r] = im;
+        for (int k = 0; k < K; ++k) {
+            x[(size_t)r * 2 * L + w.lm_host[k]] = points_host[((size_t)r * K + k) * 2];
+            x[(size_t)r * 2 * L + L + w.lm_host[k]] = points_host[((size_t)r * K + k) * 2 + 1];
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = w.points.ensure(x.size()))) return rc;
+    HIP_TRY(hipMemcpyAsync(w.points.p, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    // warp_fit_kernel's own record wants an image per row: a stack of one 1 x 1 image (of its flags only FOLDED is read)
+    AlignSourceDev src{};
+    src.width = src.height = src.stride = 1;
+    return warp_paste_run(c, w.points.p, src, nullptr, frame_of_row, spec, in_dev, paste, frames, n_frames, nullptr, flags_host);
+}
 
 int sdm_align_paste_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, int ch, const sdm_align_tensor* spec,
                            const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host,

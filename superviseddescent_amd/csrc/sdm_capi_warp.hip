@@ -193,6 +193,7 @@ int sdm_warp_set_mesh(sdm_ctx* c, const int* lm, const float* tmpl, int K, const
     if (e != hipSuccess) { w.drop(); return fail(SDM_ERR_HIP, std::string("sdm_warp_set_mesh: ") + hipGetErrorString(e)); }
     w.K = K; w.T = T; w.L = L; w.out_w = out_w; w.out_h = out_h;
     w.labels_host.swap(labels);
+    w.lm_host.assign(lm, lm + K);
     return SDM_OK;
 }
 

@@ -1,0 +1,158 @@
+// sdm_warp_paste.hip -- warped face tensors pasted back into frames on gfx950 (include/sdm.h, "Pasting warped faces back"), behind
+// warp_fit_kernel of csrc/sdm_warp.hip.
+//
+//   warp_paste_prepare_kernel   one wave per row, one lane per triangle (T > 64: in turns), as warp_fit_kernel: the lanes first look at
+//                          the mesh's K landmarks -- DEGENERATE, PARTIAL against the destination frame, the extremes, reduced across the
+//                          wave into the row's box --, then every lane turns its triangle's A_t into one WarpPasteTri record in device
+//                          memory: W_t, the corners in edge-function order, the triangle's box, the "covers nothing" bit.  FOLDED is the
+//                          bit warp_fit_kernel left in the row's record; lane 0 writes the row's record: nothing is atomic, nothing
+//                          depends on an execution order.
+//   warp_paste_kernel      the rigid paste's grid: (row, G workgroups); a workgroup strides over the 64 x 4 pixel tiles of its row's
+//                          box, a wave covers 64 consecutive pixels of one frame row.  The row's T records are staged in LDS once per
+//                          workgroup (68 bytes each: 17 272 bytes at T = 254).  Per tile a wave culls: lane l tests the boxes of
+//                          triangles l, l + 64, ... against the wave's strip of pixels, four ballots give the candidate set in scalar
+//                          registers, and every lane walks the set bits in ascending order up to the first triangle that holds its
+//                          pixel -- by warp_paste_inside, which tests the pixel against the triangle's box itself, so the strip cull
+//                          only leaves out triangles that the pixel's own test refuses, and this walk and the ownership path's
+//                          (warp_paste_footprint) decide every pixel alike.  The ownership
+//                          test against earlier rows of the frame and the application of later rows read those rows' records from
+//                          device memory, the row box first (warp_paste_owned).  One owner per pixel, no atomics, one pass.
+//
+// The per-pixel arithmetic is csrc/sdm_warp_paste_device.h.
+#include "sdm_warp.h"
+#include "sdm_warp_paste.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+#define WPASTE_BLOCK 256
+#define WPASTE_TILE_W 64
+#define WPASTE_TILE_H (WPASTE_BLOCK / WPASTE_TILE_W)
+#define WPASTE_PREPARE_BLOCK 256      // four rows per workgroup
+#define WPASTE_WORDS ((SDM_WARP_MAX_TRIANGLES + 63) / 64)
+#define WPASTE_REC_INTS ((int)(sizeof(WarpPasteTri) / sizeof(int)))
+
+__device__ __forceinline__ float wave_min(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
+    return v;
+}
+
+__device__ __forceinline__ float wave_max(float v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+
+__global__ __launch_bounds__(WPASTE_PREPARE_BLOCK) void warp_paste_prepare_kernel(const float* __restrict__ x, int N, int L,
+                                                                                  const int* __restrict__ lm, int K,
+                                                                                  const WarpTri* __restrict__ tri, int T,
+                                                                                  const WarpFace* __restrict__ faces,
+                                                                                  const float* __restrict__ matrices,
+                                                                                  const int* __restrict__ frame_of_row,
+                                                                                  const PasteFrameDev* __restrict__ frames,
+                                                                                  WarpPasteRow* __restrict__ rows, WarpPasteTri* __restrict__ tris)
+{
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * (WPASTE_PREPARE_BLOCK / 64) + (threadIdx.x >> 6);
+    if (r >= N) return;                                             // (the whole wave)
+    const float* xr = x + (long long)r * 2 * L;
+    const int fi = frame_of_row[r];
+    const int fw = frames[fi].w, fh = frames[fi].h;
+    WarpPasteScan s;
+    warp_paste_scan_init(s);
+    for (int k = lane; k < K; k += 64) warp_paste_scan_point(xr[lm[k]], xr[L + lm[k]], fw, fh, s);
+    s.bad = __ballot(s.bad) != 0;
+    s.outside = __ballot(s.outside) != 0;
+    // (a NaN among the landmarks: s.bad, and the extremes are not read)
+    s.xlo = wave_min(s.xlo); s.xhi = wave_max(s.xhi); s.ylo = wave_min(s.ylo); s.yhi = wave_max(s.yhi);
+    // FOLDED is the fit's own answer (warp_fit_triangle, ORed over the row by warp_fit_kernel); its PARTIAL is the source's, not read
+    WarpPasteRow row;
+    warp_paste_row(s, (faces[r].flags & SDM_WARP_FOLDED) != 0, fi, fw, fh, row);
+    const float* mrow = matrices + (long long)r * T * 6;
+    WarpPasteTri* trow = tris + (long long)r * T;
+    for (int t = lane; t < T; t += 64) {
+        const WarpTri tr = tri[t];
+        const float pa[2] = {xr[tr.ia], xr[L + tr.ia]}, pb[2] = {xr[tr.ib], xr[L + tr.ib]}, pc[2] = {xr[tr.ic], xr[L + tr.ic]};
+        float m[6];
+#pragma unroll
+        for (int e = 0; e < 6; ++e) m[e] = mrow[6 * t + e];
+        WarpPasteTri rec;
+        warp_paste_triangle(m, pa, pb, pc, row.x0, row.y0, row.x1, row.y1, rec);
+        trow[t] = rec;
+    }
+    if (lane == 0) rows[r] = row;
+}
+
+__global__ __launch_bounds__(WPASTE_BLOCK) void warp_paste_kernel(const PasteFrameDev* __restrict__ frames, const WarpPasteRow* __restrict__ rows,
+                                                                  const WarpPasteTri* __restrict__ tris, int T, const int* __restrict__ list,
+                                                                  const int* __restrict__ entry_of_row, const uint8_t* __restrict__ labels,
+                                                                  PasteCropDev c)
+{
+    __shared__ WarpPasteTri lds[SDM_WARP_MAX_TRIANGLES];
+    // the row, its list entry and its frame: uniform for the workgroup
+    const int n = blockIdx.x;
+    const int k = entry_of_row[n];
+    const WarpPasteRow r = rows[n];
+    const int bw = r.x1 - r.x0, bh = r.y1 - r.y0;
+    if (bw <= 0 || bh <= 0) return;
+    const PasteFrameDev f = frames[r.frame];
+    {
+        const int* src = (const int*)(tris + (long long)n * T);
+        int* dst = (int*)lds;
+        for (int e = threadIdx.x; e < T * WPASTE_REC_INTS; e += WPASTE_BLOCK) dst[e] = src[e];
+    }
+    __syncthreads();
+    const int tx = (bw + WPASTE_TILE_W - 1) / WPASTE_TILE_W, ty = (bh + WPASTE_TILE_H - 1) / WPASTE_TILE_H;
+    const int lx = threadIdx.x & (WPASTE_TILE_W - 1), ly = threadIdx.x / WPASTE_TILE_W;
+    for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
+        const int tj = (int)(t % tx), ti = (int)(t / tx);
+        const int X0 = r.x0 + tj * WPASTE_TILE_W, Y = r.y0 + ti * WPASTE_TILE_H + ly;
+        if (Y >= r.y1) continue;                                    // (the whole wave)
+        const int X = X0 + lx, X1 = X0 + WPASTE_TILE_W < r.x1 ? X0 + WPASTE_TILE_W : r.x1;
+        // the wave's candidates: triangles whose box meets its strip of pixels
+        unsigned long long cand[WPASTE_WORDS];
+#pragma unroll
+        for (int w = 0; w < WPASTE_WORDS; ++w) {
+            const int tt = w * 64 + lx;
+            cand[w] = __ballot(tt < T && warp_paste_hits(lds[tt < T ? tt : 0], X0, Y, X1, Y + 1));
+        }
+        int mine = -1;
+        bool open = X < r.x1;                                       // still looking
+#pragma unroll
+        for (int w = 0; w < WPASTE_WORDS; ++w) {
+            unsigned long long m = cand[w];
+            while (m != 0ull && __ballot(open) != 0ull) {
+                const int tt = w * 64 + __builtin_ctzll(m);
+                m &= m - 1ull;
+                if (open && warp_paste_inside(lds[tt], X, Y)) { mine = tt; open = false; }
+            }
+        }
+        AlignPos q;
+        if (mine >= 0 && warp_paste_position(lds[mine], c.cw, c.ch, X, Y, q)) warp_paste_owned(f, rows, tris, T, list, k, c, labels, X, Y, q);
+    }
+}
+
+}  // namespace
+
+void sdm_launch_warp_paste_prepare(const float* x, int N, int L, const int* lm, int K, const WarpTri* tri, int T, const WarpFace* faces,
+                                   const float* matrices, const int* frame_of_row, const PasteFrameDev* frames, WarpPasteRow* rows,
+                                   WarpPasteTri* tris, hipStream_t s)
+{
+    const int per = WPASTE_PREPARE_BLOCK / 64;
+    hipLaunchKernelGGL(warp_paste_prepare_kernel, dim3((unsigned)((N + per - 1) / per)), dim3(WPASTE_PREPARE_BLOCK), 0, s, x, N, L, lm, K, tri, T,
+                       faces, matrices, frame_of_row, frames, rows, tris);
+}
+
+void sdm_launch_warp_paste(const PasteFrameDev* frames, const WarpPasteRow* rows, const WarpPasteTri* tris, int T, const int* list,
+                           const int* entry_of_row, int N, const uint8_t* labels, const PasteCropDev& crop, hipStream_t s)
+{
+    // workgroups per row: the rigid paste's rule, one per 1 024 crop pixels, 1 ... 32
+    int groups = (crop.cw * crop.ch + 1023) / 1024;
+    groups = groups < 1 ? 1 : (groups > 32 ? 32 : groups);
+    hipLaunchKernelGGL(warp_paste_kernel, dim3((unsigned)N, (unsigned)groups), dim3(WPASTE_BLOCK), 0, s, frames, rows, tris, T, list, entry_of_row,
+                       labels, crop);
+}

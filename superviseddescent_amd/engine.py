@@ -894,6 +894,46 @@ class Context:
                                                   flags.ctypes.data))
         return flags
 
+    # -- warped face tensors pasted back into frames (csrc/sdm_warp_paste.hip) -------------------------
+    def _warp_paste_size(self, width, height):
+        T, w, h = getattr(self, "warp_mesh", (0, 0, 0))
+        if T and (w, h) != (width, height):
+            raise ValueError(f"the tensor's crop is {width} x {height}, the mesh's {w} x {h}")
+        return T
+
+    def warp_paste_tensor(self, y, frames, formats=None, layout="nchw", mask=None, spec=None, **options):
+        """The inverse of ``warp_crops_tensor`` for the N current rows (include/sdm.h, sdm_warp_paste_tensor): ``y`` -- a network's output
+        in template space, a device tensor of the mesh's crop size -- is warped back under every row's own shape, triangle by triangle,
+        and blended into ``frames`` IN PLACE.  ``frames``, ``formats``, ``layout``, ``mask``, ``spec`` / ``options``: as for
+        ``align_paste_tensor``.  Returns (matrices N x T x 2 x 3 float32 crop -> frame, as ``warp_crops_tensor`` returns them, flags N
+        int32: SDM_WARP_* bits)."""
+        spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
+        T = self._warp_paste_size(width, height)
+        if int(getattr(self, "N", 0)) and n != self.N:          # (no rows yet: the library refuses the call)
+            raise ValueError(f"the tensor has {n} rows, the context {int(getattr(self, 'N', 0))}")
+        mats = np.empty((n, T, 2, 3), np.float32)
+        flags = np.empty(n, np.int32)
+        check(self._lib.sdm_warp_paste_tensor(self._h, ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr),
+                                              mats.ctypes.data, flags.ctypes.data))
+        return mats, flags
+
+    def warp_paste_tensor_at(self, points, y, frames, formats=None, image_index=None, layout="nchw", mask=None, spec=None, **options):
+        """``warp_paste_tensor`` with explicit landmarks (sdm_warp_paste_tensor_at): ``points`` N x K x 2 float32, (x, y) of the mesh's
+        k-th landmark in its row's frame -- the tracker may have stepped on since; the mesh is needed, but no landmark state and no
+        context image.  ``image_index``: the frame of every row (None: row i -> frame i).  Returns flags N int32: SDM_WARP_* bits."""
+        spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
+        self._warp_paste_size(width, height)
+        p = np.ascontiguousarray(points, np.float32)
+        if p.ndim != 3 or p.shape[0] != n or p.shape[2] != 2:
+            raise ValueError(f"points must be N x K x 2 with one row per row of the tensor ({n}), not {p.shape}")
+        idx = None if image_index is None else np.ascontiguousarray(image_index, np.int32).reshape(-1)
+        if idx is not None and idx.size != n:
+            raise ValueError("one image index per row expected")
+        flags = np.empty(n, np.int32)
+        check(self._lib.sdm_warp_paste_tensor_at(self._h, p.ctypes.data, None if idx is None else idx.ctypes.data, n, ctypes.byref(spec),
+                                                 ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr), flags.ctypes.data))
+        return flags
+
     # -- misc ------------------------------------------------------------------------------------------
     def synchronize(self):
         check(self._lib.sdm_synchronize(self._h))
@@ -1673,6 +1713,7 @@ class detection_model:
         if triangles is None:
             triangles = _lib.delaunay(template)
         c.warp_set_mesh(idx, template, triangles, width, height)
+        self._warp_index = idx
         c.align_set_source_frames(frames, formats, chroma)
         try:
             return c.warp_crops_tensor(spec=spec, out=out)
@@ -1713,6 +1754,64 @@ class detection_model:
             template = alignment_template(self.mean, idx, width, height, margin)
         return c.align_paste_tensor(idx, template, y, frames, formats, layout, mask, **options)
 
+    def _warp_mesh_of(self, width, height, landmark_ids, template, triangles, margin):
+        ids = self.landmark_ids if landmark_ids is None else [str(i) for i in landmark_ids]
+        missing = [i for i in ids if i not in self.landmark_ids]
+        if missing:
+            raise ValueError(f"landmark ids not in this model: {missing}")
+        idx = [self.landmark_ids.index(i) for i in ids]
+        if template is None:
+            template = alignment_template(self.mean, idx, width, height, margin)
+        if triangles is None:
+            triangles = _lib.delaunay(template)
+        return idx, template, triangles
+
+    def paste_warped_tensor(self, y, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
+                            triangles: Optional[np.ndarray] = None, margin: float = 0.1, frames=None, formats=None, layout="nchw",
+                            order="rgb", scale=None, bias=None, mean=None, std=None, gray_shift=14, mask=None, points=None,
+                            image_index=None):
+        """The way back of :meth:`warped_crops_tensor`: ``y = net(x)`` on the warped faces -- a texture in template space, a device tensor
+        whose dtype, channels and crop size are read from it -- is warped back under every face's own shape and blended into ``frames``
+        in place (include/sdm.h, "Pasting warped faces back").  ``landmark_ids``, ``template``, ``triangles``, ``margin``, ``order``,
+        ``gray_shift``: as in the warp call, with the same defaults, so that ``paste_warped(net(warped_crops(...)))`` lands where it was
+        cut.  ``frames``, ``formats``, ``mean`` / ``std``, ``mask``: as for :meth:`paste_crops_tensor`; a tap outside the mesh's hull has
+        opacity 0 whatever the mask says (:func:`feather_warp_mask` fades inside it).  ``points`` (N x K x 2, :meth:`warp_points` of
+        an earlier moment) with ``image_index`` (None: row i -> frame i) pastes rows that are no longer current; otherwise the current
+        rows are fitted again.  Returns (matrices N x T x 2 x 3 crop -> frame or None with ``points``, flags N: SDM_WARP_* bits).  No
+        pointer to the frames stays behind."""
+        c = self.optimised_model.ctx
+        if frames is None:
+            raise ValueError("give the frames to paste into")
+        if not hasattr(y, "shape") or len(y.shape) != 4:
+            raise ValueError("the tensor must be a contiguous 4-dimensional tensor on the device")
+        height, width = (int(y.shape[2]), int(y.shape[3])) if str(layout).lower() == "nchw" else (int(y.shape[1]), int(y.shape[2]))
+        if points is None:
+            if image_index is not None:
+                raise ValueError("image_index goes with points; the current rows map through the context's sample -> image index")
+            if not getattr(c, "N", 0):
+                raise RuntimeError("run detect_batch or Tracker.step first")
+        idx, template, triangles = self._warp_mesh_of(width, height, landmark_ids, template, triangles, margin)
+        c.warp_set_mesh(idx, template, triangles, width, height)
+        self._warp_index = idx
+        options = dict(order=order, scale=scale, bias=bias, mean=mean, std=std, gray_shift=gray_shift)
+        if points is not None:
+            return None, c.warp_paste_tensor_at(points, y, frames, formats, image_index, layout, mask, **options)
+        return c.warp_paste_tensor(y, frames, formats, layout, mask, **options)
+
+    def warp_points(self) -> np.ndarray:
+        """N x K x 2 float32: (x, y) of the mesh's K landmarks of the current rows, in the order of the last
+        :meth:`warped_crops_tensor` / :meth:`paste_warped_tensor` mesh -- what ``points=`` of :meth:`paste_warped_tensor` takes later."""
+        c = self.optimised_model.ctx
+        idx = getattr(self, "_warp_index", None)
+        if idx is None:
+            raise RuntimeError("run warped_crops_tensor or paste_warped_tensor first")
+        if not getattr(c, "N", 0):
+            raise RuntimeError("run detect_batch or Tracker.step first")
+        x = np.asarray(c.get_x(), np.float32)
+        L = x.shape[1] // 2
+        idx = np.asarray(idx, np.int64)
+        return np.ascontiguousarray(np.stack([x[:, idx], x[:, L + idx]], -1))
+
     def warp_mask(self) -> np.ndarray:
         """height x width bool of the last :meth:`warped_crops_tensor`'s mesh: True where a triangle covers the crop pixel."""
         return self.optimised_model.ctx.warp_labels() != _lib.SDM_WARP_NO_TRIANGLE
@@ -1749,6 +1848,32 @@ def feather_mask(size, border: int) -> np.ndarray:
     dy = np.minimum(np.arange(height), np.arange(height)[::-1])[:, None]
     k = np.minimum(np.minimum(dx, dy) + 1, border + 1)
     return np.rint(255.0 * k / (border + 1)).astype(np.uint8)
+
+
+def feather_warp_mask(mask, radius: int) -> np.ndarray:
+    """A crop-space opacity map for :meth:`detection_model.paste_warped_tensor` (height x width uint8, computed on the host) from a bool
+    height x width map such as :meth:`detection_model.warp_mask`: 0 on unlabelled pixels, rising linearly to 255 over ``radius`` pixels of
+    city-block distance -- a pixel at distance d from the nearest unlabelled or out-of-crop pixel has
+    round(255 min(d, radius + 1) / (radius + 1)); ``radius`` = 0 gives 255 where the mask is set."""
+    m = np.asarray(mask)
+    if m.ndim != 2 or m.dtype != np.bool_:
+        raise ValueError("mask must be a bool height x width map")
+    if radius < 0:
+        raise ValueError("radius must be >= 0")
+    h, w = m.shape
+    # city-block distance to the nearest False pixel, the crop's outside counting as False: two sweeps
+    big = h + w + 2
+    d = np.where(np.pad(m, 1), big, 0).astype(np.int64)
+    for i in range(1, h + 2):
+        d[i] = np.minimum(d[i], d[i - 1] + 1)
+    for i in range(h, -1, -1):
+        d[i] = np.minimum(d[i], d[i + 1] + 1)
+    for j in range(1, w + 2):
+        d[:, j] = np.minimum(d[:, j], d[:, j - 1] + 1)
+    for j in range(w, -1, -1):
+        d[:, j] = np.minimum(d[:, j], d[:, j + 1] + 1)
+    k = np.minimum(d[1:-1, 1:-1], radius + 1)
+    return np.rint(255.0 * k / (radius + 1)).astype(np.uint8)
 
 
 class Tracker:

@@ -10,6 +10,10 @@
 //     // out_dev: rows x 3 x 112 x 112 float16; w.matrices.row(i): stream ids[i]'s T crop -> source maps; w.flags[i]: SDM_WARP_*
 //
 // The rows of detection_model::detect_batch work the same way (the overload taking the frames and the rows).
+//
+// rcr::paste_warped_tensor is the way back: a network's output in template space blended into the frames under every face's own shape.
+//
+//     auto p = rcr::paste_warped_tensor(tr, mesh, paste_spec, net_out_dev, device_frames);       // p.flags[i]: SDM_WARP_*
 #pragma once
 
 #ifndef RCR_WARP_HPP_
@@ -131,6 +135,97 @@ inline warped_tensor_result warped_crops_tensor(detection_model& model, const st
     else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
     check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
     return detail::warp_tensor_current_rows(c, x.rows, mesh, frames, chroma, spec, out_dev);
+}
+
+struct warp_paste_result {
+    cv::Mat matrices;              // rows x (6 T) CV_32FC1: the crop -> frame maps, as warped_crops_tensor returns them (empty: the form with points)
+    std::vector<int> flags;        // SDM_WARP_DEGENERATE / SDM_WARP_PARTIAL / SDM_WARP_FOLDED bits
+};
+
+namespace detail {
+
+inline void warp_paste_set_mesh(sdm_ctx* c, const WarpMesh& mesh)
+{
+    if (mesh.tmpl.rows != (int)mesh.landmark_index.size() || mesh.tmpl.cols != 2 || mesh.tmpl.type() != CV_32FC1)
+        throw std::runtime_error("paste_warped_tensor: one template point (x, y) per landmark");
+    if (mesh.triangles.size() % 3 != 0) throw std::runtime_error("paste_warped_tensor: three positions per triangle");
+    cv::Mat t = mesh.tmpl.isContinuous() ? mesh.tmpl : mesh.tmpl.clone();
+    superviseddescent::hip::check(sdm_warp_set_mesh(c, mesh.landmark_index.data(), t.ptr<float>(0), (int)mesh.landmark_index.size(),
+                                                    mesh.triangles.data(), mesh.n_triangles(), mesh.width, mesh.height), "sdm_warp_set_mesh");
+}
+
+// the n current rows of the handle `c`: the fit of warped_crops_tensor, then the tensor at `in_dev` pasted into `frames` in place
+inline warp_paste_result warp_paste_current_rows(sdm_ctx* c, int n, const WarpMesh& mesh, const TensorSpec& spec, const void* in_dev,
+                                                 const std::vector<DeviceFrame>& frames, const PasteMask& mask)
+{
+    warp_paste_set_mesh(c, mesh);
+    const std::vector<sdm_frame> f = paste_frames(frames);
+    const sdm_align_tensor s = paste_spec(spec);
+    const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
+    warp_paste_result res;
+    res.matrices = cv::Mat(n, 6 * mesh.n_triangles(), CV_32FC1);
+    res.flags.resize((size_t)n);
+    superviseddescent::hip::check(sdm_warp_paste_tensor(c, &s, in_dev, &p, f.empty() ? nullptr : f.data(), (int)f.size(),
+                                                        res.matrices.ptr<float>(0), res.flags.data()), "sdm_warp_paste_tensor");
+    return res;
+}
+
+}  // namespace detail
+
+/** The way back of warped_crops_tensor: `in_dev` -- a network's output in template space on the streams of the tracker's last step,
+ *  rows * channels * height * width elements of spec.dtype in spec.layout, 16-byte aligned device memory -- is warped back under every
+ *  face's own shape, triangle by triangle, and blended into `frames` IN PLACE (the frames of that step, GRAY / BGR / RGB / BGRA / RGBA;
+ *  NV12 is refused) (include/sdm.h, "Pasting warped faces back").  spec and mask: as for paste_crops_tensor; a tap outside the mesh's
+ *  hull has opacity 0 whatever the mask says. */
+inline warp_paste_result paste_warped_tensor(tracker& tr, const WarpMesh& mesh, const TensorSpec& spec, const void* in_dev,
+                                             const std::vector<DeviceFrame>& frames, const PasteMask& mask = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("paste_warped_tensor: step the tracker first");
+    return detail::warp_paste_current_rows(tr.context(), tr.rows().rows, mesh, spec, in_dev, frames, mask);
+}
+
+/** The same for landmark rows on device frames (as the detection_model overload of warped_crops_tensor: a handle of its own, the frames
+ *  as its image set, the rows uploaded): row i is pasted into frames[image_index[i]] (default: frames[i]). */
+inline warp_paste_result paste_warped_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                             const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec,
+                                             const void* in_dev, const PasteMask& mask = {})
+{
+    using superviseddescent::hip::check;
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    sdm_ctx* c = h.get();
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::set_device_frames(h, frames);
+    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
+    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("paste_warped_tensor: rows must hold 2L coordinates");
+    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
+    return detail::warp_paste_current_rows(c, x.rows, mesh, spec, in_dev, frames, mask);
+}
+
+/** The explicit form (sdm_warp_paste_tensor_at): `points` rows x 2K CV_32FC1 -- per row x, y of the mesh's first landmark, then of its
+ *  second, ... -- as they were when the tensor was cut; the rows need not be current any more.  The model gives the landmark count the
+ *  mesh's indices refer to; no landmark state and no image is needed.  Row i goes to frames[image_index[i]] (default: frames[i]). */
+inline warp_paste_result paste_warped_tensor(detection_model& model, cv::Mat points, const std::vector<int>& image_index, const WarpMesh& mesh,
+                                             const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames,
+                                             const PasteMask& mask = {})
+{
+    using superviseddescent::hip::check;
+    if (points.type() != CV_32FC1 || points.cols != 2 * (int)mesh.landmark_index.size() || points.rows < 1)
+        throw std::runtime_error("paste_warped_tensor: points must be rows x 2K CV_32FC1");
+    if (!image_index.empty() && (int)image_index.size() != points.rows) throw std::runtime_error("paste_warped_tensor: one image index per row");
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::warp_paste_set_mesh(h.get(), mesh);
+    cv::Mat pts = points.isContinuous() ? points : points.clone();
+    const std::vector<sdm_frame> f = detail::paste_frames(frames);
+    const sdm_align_tensor s = detail::paste_spec(spec);
+    const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
+    warp_paste_result res;
+    res.flags.resize((size_t)points.rows);
+    check(sdm_warp_paste_tensor_at(h.get(), pts.ptr<float>(0), image_index.empty() ? nullptr : image_index.data(), points.rows, &s, in_dev, &p,
+                                   f.empty() ? nullptr : f.data(), (int)f.size(), res.flags.data()), "sdm_warp_paste_tensor_at");
+    return res;
 }
 
 }  // namespace rcr

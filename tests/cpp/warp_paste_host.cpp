@@ -1,0 +1,123 @@
+// Host build of the arithmetic of sdm_warp_paste_tensor (superviseddescent_amd/csrc/sdm_warp_paste_device.h on top of
+// sdm_warp_device.h and sdm_align_paste_device.h), run by tests/test_warp_paste_host.py under -fsanitize=address,undefined: the frame,
+// the tensor, the label map and the opacity maps of a case each live in a heap block of exactly the bytes they own (a frame: up to the
+// last pixel of the last row), so a load or store that leaves them is reported.  A case is ONE frame with its rows; they are pasted with
+// the kernels' per-row, per-triangle and per-pixel functions in plain loops: per row the scan of its landmarks, every triangle's fit
+// (warp_fit_triangle) and record, then for every row every pixel of its box through warp_paste_footprint and warp_paste_owned -- once
+// in DESCENDING and once in ascending row order, since the result must not depend on it.  The kernel's own wave-wide strip cull, its
+// ballots and its LDS staging are not here: only the GPU tests run them.  No device, no HIP.
+//   usage: warp_paste_host <cases.bin> <out.bin>
+//   cases.bin   int32 n, then per case: int32 format, w, h, stride, cw, ch, dtype, layout, channels, order, gray_shift, n_rows,
+//               alpha_mode (0: none, 1: one map, 2: one per row), K, T; float32 scale[3], bias[3]; T x 3 int32 triangle positions;
+//               T x 7 float64 (G00 G01 G10 G11 qa.x qa.y D); n_rows x K x 2 float32 points; int32 bytes + the label map;
+//               int32 bytes + the tensor; int32 bytes + the opacity maps; int32 bytes + the frame
+//   out.bin     per case: n_rows int32 flags, n_rows x T x 6 float32 A_t, n_rows x T x 6 float32 W_t, n_rows x T int32 covers,
+//               n_rows x 4 int32 box, the frame's bytes after the rows were pasted in descending order, and after ascending order
+#include "../../superviseddescent_amd/csrc/sdm_warp_paste_device.h"
+
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <memory>
+#include <vector>
+
+template <class T>
+static T get(std::ifstream& f)
+{
+    T v;
+    f.read((char*)&v, sizeof(T));
+    if (!f) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
+    return v;
+}
+
+static std::unique_ptr<uint8_t[]> block(std::ifstream& f, int& bytes)
+{
+    bytes = get<int>(f);
+    std::unique_ptr<uint8_t[]> p(new uint8_t[bytes > 0 ? bytes : 1]);
+    f.read((char*)p.get(), bytes);
+    if (!f) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
+    return p;
+}
+
+int main(int argc, char** argv)
+{
+    if (argc < 3) { std::fprintf(stderr, "usage: warp_paste_host <cases.bin> <out.bin>\n"); return 2; }
+    std::ifstream in(argv[1], std::ios::binary);
+    std::ofstream out(argv[2], std::ios::binary);
+    const int n = get<int>(in);
+    for (int k = 0; k < n; ++k) {
+        PasteFrameDev f{};
+        f.format = get<int>(in); f.w = get<int>(in); f.h = get<int>(in); f.stride = get<int>(in);
+        PasteCropDev c{};
+        c.cw = get<int>(in); c.ch = get<int>(in); c.dtype = get<int>(in);
+        const int layout = get<int>(in);
+        c.channels = get<int>(in); c.t.order = get<int>(in); c.t.gray_shift = get<int>(in);
+        const int rows_n = get<int>(in), alpha_mode = get<int>(in), K = get<int>(in), T = get<int>(in);
+        for (int e = 0; e < 3; ++e) c.t.scale[e] = get<float>(in);
+        for (int e = 0; e < 3; ++e) c.t.bias[e] = get<float>(in);
+        if (c.t.gray_shift == 14) { c.t.wb = 1868; c.t.wg = 9617; c.t.wr = 4899; }
+        else { c.t.wb = 3735; c.t.wg = 19235; c.t.wr = 9798; }
+        std::vector<WarpTri> tri((size_t)T);
+        for (WarpTri& t : tri) { t.ia = get<int>(in); t.ib = get<int>(in); t.ic = get<int>(in); t.pad = 0; }
+        for (WarpTri& t : tri) {
+            for (int e = 0; e < 4; ++e) t.g[e] = get<double>(in);
+            t.qa[0] = get<double>(in); t.qa[1] = get<double>(in); t.D = get<double>(in);
+        }
+        std::vector<float> pts((size_t)rows_n * K * 2);
+        for (float& v : pts) v = get<float>(in);
+        int lb, tb, ab, fb;
+        const std::unique_ptr<uint8_t[]> labels = block(in, lb), tensor = block(in, tb), alpha = block(in, ab), frame = block(in, fb);
+        c.in = tensor.get(); c.alpha = alpha_mode ? alpha.get() : nullptr;
+        c.an = alpha_mode == 2 ? (long long)c.cw * c.ch : 0;
+        c.sn = (long long)c.channels * c.cw * c.ch;
+        if (layout == SDM_ALIGN_NCHW) { c.sc = c.cw * c.ch; c.sy = c.cw; c.sx = 1; }
+        else { c.sc = 1; c.sy = c.cw * c.channels; c.sx = c.channels; }
+        f.p = frame.get(); f.row_begin = 0; f.row_end = rows_n;
+        std::vector<WarpPasteRow> rows((size_t)rows_n);
+        std::vector<WarpPasteTri> recs((size_t)rows_n * T);
+        std::vector<float> mats((size_t)rows_n * T * 6);
+        std::vector<int> list((size_t)rows_n);
+        for (int r = 0; r < rows_n; ++r) {
+            list[r] = r;
+            const float* p = &pts[(size_t)r * K * 2];
+            WarpPasteScan s;
+            warp_paste_scan_init(s);
+            for (int j = 0; j < K; ++j) warp_paste_scan_point(p[2 * j], p[2 * j + 1], f.w, f.h, s);
+            warp_paste_row(s, false, 0, f.w, f.h, rows[r]);
+            bool folded = false;
+            for (int t = 0; t < T; ++t) {
+                const float* pa = p + 2 * tri[t].ia; const float* pb = p + 2 * tri[t].ib; const float* pc = p + 2 * tri[t].ic;
+                float* m = &mats[((size_t)r * T + t) * 6];
+                if (s.bad) for (int e = 0; e < 6; ++e) m[e] = __builtin_nanf("");
+                else folded = warp_fit_triangle(tri[t], pa, pb, pc, m) || folded;
+                warp_paste_triangle(m, pa, pb, pc, rows[r].x0, rows[r].y0, rows[r].x1, rows[r].y1, recs[(size_t)r * T + t]);
+            }
+            if (!s.bad && folded) rows[r].flags |= SDM_WARP_FOLDED;
+        }
+        // both launch orders, each on the frame as the case gives it
+        std::unique_ptr<uint8_t[]> other(new uint8_t[fb > 0 ? fb : 1]);
+        std::memcpy(other.get(), frame.get(), (size_t)fb);
+        for (int pass = 0; pass < 2; ++pass) {
+            f.p = pass ? other.get() : frame.get();
+            for (int i = 0; i < rows_n; ++i) {
+                const int r = pass ? i : rows_n - 1 - i;
+                const WarpPasteRow& b = rows[r];
+                for (int Y = b.y0; Y < b.y1; ++Y)
+                    for (int X = b.x0; X < b.x1; ++X) {
+                        AlignPos q;
+                        if (warp_paste_footprint(b, &recs[(size_t)r * T], T, c.cw, c.ch, X, Y, q))
+                            warp_paste_owned(f, rows.data(), recs.data(), T, list.data(), r, c, labels.get(), X, Y, q);
+                    }
+            }
+        }
+        for (int r = 0; r < rows_n; ++r) out.write((const char*)&rows[r].flags, sizeof(int));
+        out.write((const char*)mats.data(), (std::streamsize)(mats.size() * sizeof(float)));
+        for (const WarpPasteTri& t : recs) out.write((const char*)t.w, 6 * sizeof(float));
+        for (const WarpPasteTri& t : recs) out.write((const char*)&t.covers, sizeof(int));
+        for (int r = 0; r < rows_n; ++r) out.write((const char*)&rows[r].x0, 4 * sizeof(int));
+        out.write((const char*)frame.get(), fb);
+        out.write((const char*)other.get(), fb);
+    }
+    std::printf("%d cases\n", n);
+    return 0;
+}
