@@ -3,23 +3,18 @@
 //
 //   paste_prepare_kernel   one lane per row: the inverse map W (double, rounded once to float32), the flags and the footprint's box in
 //                          the row's frame, written as one PasteRow record; the final flags go back into the fit's record
-//   paste_kernel           grid (row list entry, PASTE_GROUPS workgroups): the workgroups of an entry stride over the 64 x 4 pixel tiles
-//                          of its row's box -- a wave covers 64 consecutive pixels of one frame row --, so the box never reaches the
-//                          host.  A lane's pixel is pasted by the lowest-numbered row of the frame whose footprint holds it
-//                          (paste_pixel): every frame byte has at most one reader and writer in the launch, whatever the order the
-//                          workgroups run in.  Stores are per pixel, byte by byte: nothing a neighbour owns is touched.
+//   paste_kernel           the tile walk of csrc/sdm_paste.h over the row's box.  A lane's pixel is pasted by the lowest-numbered row
+//                          of the frame whose footprint holds it (paste_pixel, paste_owned): every frame byte has at most one reader
+//                          and writer in the launch, whatever the order the workgroups run in.  Stores are per pixel, byte by byte:
+//                          nothing a neighbour owns is touched.
 //
-// The per-pixel arithmetic is csrc/sdm_align_paste_device.h.
-#include "sdm_kernels.h"
-#include "sdm_align_paste_device.h"
+// The per-pixel arithmetic is csrc/sdm_align_paste_device.h on top of csrc/sdm_paste_device.h.
+#include "sdm_paste.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define PASTE_BLOCK 256
-#define PASTE_TILE_W 64
-#define PASTE_TILE_H (PASTE_BLOCK / PASTE_TILE_W)
 #define PASTE_PREPARE_BLOCK 64
 
 __global__ __launch_bounds__(PASTE_PREPARE_BLOCK) void paste_prepare_kernel(AlignFace* __restrict__ faces, const int* __restrict__ frame_of_row,
@@ -49,11 +44,10 @@ __global__ __launch_bounds__(PASTE_BLOCK) void paste_kernel(const PasteFrameDev*
     const int bw = r.x1 - r.x0, bh = r.y1 - r.y0;
     if (bw <= 0 || bh <= 0) return;
     const PasteFrameDev f = frames[r.frame];
-    const int tx = (bw + PASTE_TILE_W - 1) / PASTE_TILE_W, ty = (bh + PASTE_TILE_H - 1) / PASTE_TILE_H;
+    const int tx = paste_tiles_x(bw), ty = paste_tiles_y(bh);
     const int lx = threadIdx.x & (PASTE_TILE_W - 1), ly = threadIdx.x / PASTE_TILE_W;
     for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
-        const int tj = (int)(t % tx), ti = (int)(t / tx);
-        const int X = r.x0 + tj * PASTE_TILE_W + lx, Y = r.y0 + ti * PASTE_TILE_H + ly;
+        const int X = r.x0 + paste_tile_x(t, tx) + lx, Y = r.y0 + paste_tile_y(t, tx) + ly;
         if (X < r.x1 && Y < r.y1) paste_pixel(f, rows, list, k, c, X, Y);
     }
 }
@@ -70,8 +64,6 @@ void sdm_launch_paste_prepare(AlignFace* faces, const int* frame_of_row, const P
 void sdm_launch_paste(const PasteFrameDev* frames, const PasteRow* rows, const int* list, const int* entry_of_row, int N,
                       const PasteCropDev& crop, hipStream_t s)
 {
-    // workgroups per row: one per 1 024 crop pixels, 1 ... 32 (a 112 x 112 crop: 13)
-    int groups = (crop.cw * crop.ch + 1023) / 1024;
-    groups = groups < 1 ? 1 : (groups > 32 ? 32 : groups);
-    hipLaunchKernelGGL(paste_kernel, dim3((unsigned)N, (unsigned)groups), dim3(PASTE_BLOCK), 0, s, frames, rows, list, entry_of_row, crop);
+    hipLaunchKernelGGL(paste_kernel, dim3((unsigned)N, (unsigned)paste_groups(crop)), dim3(PASTE_BLOCK), 0, s, frames, rows, list, entry_of_row,
+                       crop);
 }

@@ -38,6 +38,13 @@ struct AlignRow {
 
 struct AlignPos { int x0, fx, y0, fy; };
 
+// what the element stage and the pastes' decode need: per TENSOR channel scale and bias, the channel order, the colour -> gray weights
+struct AlignTensorDev {
+    float scale[3], bias[3];
+    int order;                  // SDM_ALIGN_ORDER_*
+    int wb, wg, wr, gray_shift;
+};
+
 // 1/32-pixel position of (sx, sy); false: refused by the 2^20 rule (also NaN: a degenerate row's M)
 ALIGN_HD bool align_quantise(float sx, float sy, AlignPos& q)
 {

@@ -9,16 +9,6 @@
 #include <cmath>
 #include <limits.h>
 
-static int align_frame_bpp(int format)
-{
-    switch (format) {
-    case SDM_FRAME_GRAY: case SDM_FRAME_NV12: return 1;
-    case SDM_FRAME_BGR: case SDM_FRAME_RGB: return 3;
-    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return 4;
-    default: return 0;
-    }
-}
-
 // what sdm_align_crops and sdm_align_crops_tensor check alike, before anything is launched: geometry, rows, indices, template, crop
 // size, and that the source covers every row's image with that image's size
 int sdm_capi::align_check_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h)
@@ -237,16 +227,12 @@ int sdm_align_set_source_frames(sdm_ctx* c, const sdm_frame* frames, const void*
     if (!frames || n == 0) { a.base = nullptr; a.n = 0; a.C = 1; a.fr.clear(); return SDM_OK; }     // the context's images
     // ---- every argument is checked before anything is allocated or copied ----
     std::vector<AlignFrameDev> tab((size_t)n);
-    int bpp_all = -1;
+    int bpp_all = -1, rc;
     const uint8_t* lowest = nullptr;
     for (int i = 0; i < n; ++i) {
         const sdm_frame& f = frames[i];
-        const int bpp = align_frame_bpp(f.format);
-        if (!bpp) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": unknown format");
-        if (!f.data) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": null pointer");
-        if (f.width < 1 || f.height < 1) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": width and height must be >= 1");
-        if ((long long)f.stride_bytes < (long long)f.width * bpp)
-            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < width * bytes per pixel");
+        if ((rc = check_frame(i, f, true))) return rc;
+        const int bpp = frame_bpp(f.format);
         AlignFrameDev& d = tab[i];
         d.p0 = (const uint8_t*)f.data; d.p1 = nullptr; d.stride = f.stride_bytes; d.cstride = 0; d.format = f.format; d.pad = 0;
         if (f.format == SDM_FRAME_NV12) {
@@ -261,8 +247,7 @@ int sdm_align_set_source_frames(sdm_ctx* c, const sdm_frame* frames, const void*
         if (!lowest || d.p0 < lowest) lowest = d.p0;
     }
     HIP_TRY(hipSetDevice(c->device));
-    int rc = a.fr_dev.ensure((size_t)n);
-    if (rc) return rc;
+    if ((rc = a.fr_dev.ensure((size_t)n))) return rc;
     HIP_TRY(hipMemcpyAsync(a.fr_dev.p, tab.data(), (size_t)n * sizeof(AlignFrameDev), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     a.base = nullptr; a.n = 0; a.C = bpp_all > 0 ? bpp_all : 1;                // (a frame list replaces a stack)

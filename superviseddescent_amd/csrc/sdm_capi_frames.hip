@@ -4,7 +4,7 @@
 
 #include <limits.h>
 
-static int frame_bpp(int format)
+int sdm_capi::frame_bpp(int format)
 {
     switch (format) {
     case SDM_FRAME_GRAY: case SDM_FRAME_NV12: return 1;
@@ -12,6 +12,18 @@ static int frame_bpp(int format)
     case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return 4;
     default: return 0;
     }
+}
+
+int sdm_capi::check_frame(int i, const sdm_frame& f, bool allow_nv12)
+{
+    const std::string at = "frame " + std::to_string(i) + ": ";
+    if (!allow_nv12 && f.format == SDM_FRAME_NV12) return fail(SDM_ERR_INVALID, at + "an NV12 frame cannot be pasted into");
+    const int bpp = frame_bpp(f.format);
+    if (!bpp) return fail(SDM_ERR_INVALID, at + "unknown format");
+    if (!f.data) return fail(SDM_ERR_INVALID, at + "null pointer");
+    if (f.width < 1 || f.height < 1) return fail(SDM_ERR_INVALID, at + "width and height must be >= 1");
+    if ((long long)f.stride_bytes < (long long)f.width * bpp) return fail(SDM_ERR_INVALID, at + "stride_bytes < width * bytes per pixel");
+    return SDM_OK;
 }
 
 extern "C" {
@@ -23,14 +35,11 @@ int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_s
     // ---- every argument is checked before anything is allocated, copied or launched ----
     std::vector<FrameConvDev> conv;
     long long owned = 0, blocks = 0;
+    int rc;
     for (int i = 0; i < n; ++i) {
         const sdm_frame& f = frames[i];
+        if ((rc = check_frame(i, f, true))) return rc;
         const int bpp = frame_bpp(f.format);
-        if (!bpp) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": unknown format");
-        if (!f.data) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": null pointer");
-        if (f.width < 1 || f.height < 1) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": width and height must be >= 1");
-        if ((long long)f.stride_bytes < (long long)f.width * bpp)
-            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < width * bytes per pixel");
         if (bpp == 1) continue;
         FrameConvDev d{};
         d.src = (const uint8_t*)f.data; d.dst_off = owned; d.w = f.width; d.h = f.height; d.pitch = f.stride_bytes;
@@ -45,7 +54,6 @@ int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_s
         conv.push_back(d);
     }
     HIP_TRY(hipSetDevice(c->device));
-    int rc;
     if (!conv.empty() && ((rc = c->frames.gray.ensure((size_t)owned)) || (rc = c->frames.desc.ensure(conv.size())))) return rc;
     if ((rc = c->img_off.ensure(n)) || (rc = c->img_w.ensure(n)) || (rc = c->img_h.ensure(n)) || (rc = c->img_stride.ensure(n)))
         return rc;

@@ -399,6 +399,10 @@ int upright_check(sdm_ctx* c, int n);
 int upright_ensure(sdm_ctx* c, int n);
 int upright_run(sdm_ctx* c, int n);
 int upright_roll_cs(float roll_deg, double* cs);
+// (sdm_capi_frames.hip) bytes per pixel of a frame's plane 0 (NV12: luma; 0: unknown format), and what every entry point that takes
+// frames refuses of frame i: format, null pointer, width / height, stride -- with allow_nv12 false (the pastes) an NV12 frame first
+int frame_bpp(int format);
+int check_frame(int i, const sdm_frame& frame, bool allow_nv12);
 // (sdm_capi_align.hip) the checks and the element stage's constants that sdm_align_crops_tensor and sdm_warp_crops_tensor share: the
 // specification, the output pointer, that the crop source covers every row's image with that image's size, the source itself and the
 // landmark subset of a template

@@ -5,23 +5,11 @@
 // (csrc/sdm_warp_paste.hip) on the mesh of sdm_warp_set_mesh.  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
 // landmark state, the images, the crop source and the tracker's slots are only read; the frames' colour bytes are written in place.
 #include "sdm_capi_internal.h"
-#include "sdm_align_paste_device.h"
-#include "sdm_warp.h"
-#include "sdm_warp_paste.h"
+#include "sdm_paste.h"
 
 #include <cmath>
 
 namespace {
-
-int paste_frame_bpp(int format)
-{
-    switch (format) {
-    case SDM_FRAME_GRAY: return 1;
-    case SDM_FRAME_BGR: case SDM_FRAME_RGB: return 3;
-    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return 4;
-    default: return 0;
-    }
-}
 
 // what both forms refuse of the tensor, the opacity maps and the destination frames
 int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames)
@@ -31,15 +19,34 @@ int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm
     if (!paste) return fail(SDM_ERR_INVALID, "no paste options");
     if (paste->alpha_per_row != 0 && paste->alpha_per_row != 1) return fail(SDM_ERR_INVALID, "alpha_per_row must be 0 or 1");
     if (!frames || n_frames < 1) return fail(SDM_ERR_INVALID, "bad frame list");
-    for (int i = 0; i < n_frames; ++i) {
-        const sdm_frame& f = frames[i];
-        if (f.format == SDM_FRAME_NV12) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": an NV12 frame cannot be pasted into");
-        const int bpp = paste_frame_bpp(f.format);
-        if (!bpp) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": unknown format");
-        if (!f.data) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": null pointer");
-        if (f.width < 1 || f.height < 1) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": width and height must be >= 1");
-        if ((long long)f.stride_bytes < (long long)f.width * bpp)
-            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < width * bytes per pixel");
+    int rc;
+    for (int i = 0; i < n_frames; ++i)
+        if ((rc = check_frame(i, frames[i], false))) return rc;
+    return SDM_OK;
+}
+
+// the fit forms' row -> frame map: every current row's image, which must be among the frames and of its frame's size
+int paste_frames_of_rows(const sdm_ctx* c, const sdm_frame* frames, int n_frames, std::vector<int>& frame_of_row)
+{
+    frame_of_row.resize((size_t)c->N);
+    for (int r = 0; r < c->N; ++r) {
+        const int im = c->idx_identity ? r : c->img_idx_host[r];
+        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to image " + std::to_string(im) + ", beyond the frames");
+        if (frames[im].width != c->img_w_host[im] || frames[im].height != c->img_h_host[im])
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(im) + " differs in size from image " + std::to_string(im) + " of the context");
+        frame_of_row[r] = im;
+    }
+    return SDM_OK;
+}
+
+// the _at forms' row -> frame map: image_index (null: row r pastes into frame r), every entry among the frames
+int paste_frames_of_index(const int* image_index, int n_rows, int n_frames, std::vector<int>& frame_of_row)
+{
+    frame_of_row.resize((size_t)n_rows);
+    for (int r = 0; r < n_rows; ++r) {
+        const int im = image_index ? image_index[r] : r;
+        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to frame " + std::to_string(im) + ", outside the list");
+        frame_of_row[r] = im;
     }
     return SDM_OK;
 }
@@ -82,8 +89,7 @@ int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_fra
     HIP_TRY(hipMemcpyAsync(a.paste_tab.p, blob.data(), bytes, hipMemcpyHostToDevice, c->stream));
     out.frames = (const PasteFrameDev*)a.paste_tab.p;
     out.of_row = (const int*)(a.paste_tab.p + tab_bytes);
-    out.list = out.of_row + N;
-    out.entry = out.of_row + 2 * N;
+    out.list = out.of_row + N; out.entry = out.of_row + 2 * N;
     return SDM_OK;
 }
 
@@ -97,9 +103,7 @@ PasteCropDev paste_crop_dev(const sdm_align_tensor* spec, const void* in_dev, co
     if (spec->layout == SDM_ALIGN_NCHW) { crop.sc = cw * ch; crop.sy = cw; crop.sx = 1; }
     else { crop.sc = 1; crop.sy = cw * spec->channels; crop.sx = spec->channels; }
     crop.an = paste->alpha_per_row ? (long long)cw * ch : 0;
-    const AlignTensorDev t = align_tensor_dev(spec);
-    for (int k = 0; k < 3; ++k) { crop.t.scale[k] = t.scale[k]; crop.t.bias[k] = t.bias[k]; }
-    crop.t.order = t.order; crop.t.wb = t.wb; crop.t.wg = t.wg; crop.t.wr = t.wr; crop.t.gray_shift = t.gray_shift;
+    crop.t = align_tensor_dev(spec);
     return crop;
 }
 
@@ -112,13 +116,10 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
     int rc;
     PasteTables tab;
     if ((rc = a.paste_rows.ensure((size_t)N * sizeof(PasteRow))) || (rc = paste_tables(c, frame_of_row, frames, n_frames, tab))) return rc;
-    const PasteFrameDev* tab_dev = tab.frames;
-    const int* of_row_dev = tab.of_row;
     PasteRow* rows_dev = (PasteRow*)a.paste_rows.p;
-    sdm_launch_paste_prepare(a.faces.p, of_row_dev, tab_dev, N, cw, ch, fitted, rows_dev, c->stream);
+    sdm_launch_paste_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, rows_dev, c->stream);
     HIP_TRY(hipGetLastError());
-    const PasteCropDev crop = paste_crop_dev(spec, in_dev, paste, cw, ch);
-    sdm_launch_paste(tab_dev, rows_dev, of_row_dev + N, of_row_dev + 2 * N, N, crop, c->stream);
+    sdm_launch_paste(tab.frames, rows_dev, tab.list, tab.entry, N, paste_crop_dev(spec, in_dev, paste, cw, ch), c->stream);
     HIP_TRY(hipGetLastError());
     // the records in one copy, one synchronise
     std::vector<AlignFace> host;
@@ -190,17 +191,10 @@ int sdm_warp_paste_tensor(sdm_ctx* c, const sdm_align_tensor* spec, const void* 
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     int rc;
     if ((rc = warp_paste_check_mesh(c))) return rc;
-    const int N = c->N;
-    if (N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
+    if (c->N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
     if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames)) || (rc = align_check_rows(c))) return rc;
-    std::vector<int> frame_of_row((size_t)N);
-    for (int r = 0; r < N; ++r) {
-        const int im = c->idx_identity ? r : c->img_idx_host[r];
-        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to image " + std::to_string(im) + ", beyond the frames");
-        if (frames[im].width != c->img_w_host[im] || frames[im].height != c->img_h_host[im])
-            return fail(SDM_ERR_INVALID, "frame " + std::to_string(im) + " differs in size from image " + std::to_string(im) + " of the context");
-        frame_of_row[r] = im;
-    }
+    std::vector<int> frame_of_row;
+    if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     return warp_paste_run(c, c->x[c->cur].p, align_source_dev(c), c->idx_identity ? nullptr : c->img_idx.p, frame_of_row, spec, in_dev, paste,
                           frames, n_frames, matrices_host, flags_host);
@@ -215,21 +209,18 @@ int sdm_warp_paste_tensor_at(sdm_ctx* c, const float* points_host, const int* im
     if (!points_host) return fail(SDM_ERR_INVALID, "no points");
     if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
     if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames))) return rc;
+    std::vector<int> frame_of_row;
+    if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;
     sdm_ctx::Warp& w = c->warp;
     const int L = w.L, K = w.K;
-    std::vector<int> frame_of_row((size_t)n_rows);
     // the points in the landmark state's layout (row: L x then L y), the mesh's landmarks at their indices, 0 elsewhere: the fit and the
     // prepare kernel read them as they read the state
     std::vector<float> x((size_t)n_rows * 2 * L, 0.0f);
-    for (int r = 0; r < n_rows; ++r) {
-        const int im = image_index ? image_index[r] : r;
-        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to frame " + std::to_string(im) + ", outside the list");
-        frame_of_row[r] = im;
+    for (int r = 0; r < n_rows; ++r)
         for (int k = 0; k < K; ++k) {
             x[(size_t)r * 2 * L + w.lm_host[k]] = points_host[((size_t)r * K + k) * 2];
             x[(size_t)r * 2 * L + L + w.lm_host[k]] = points_host[((size_t)r * K + k) * 2 + 1];
         }
-    }
     HIP_TRY(hipSetDevice(c->device));
     if ((rc = w.points.ensure(x.size()))) return rc;
     HIP_TRY(hipMemcpyAsync(w.points.p, x.data(), x.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -248,18 +239,11 @@ int sdm_align_paste_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, 
     if ((rc = align_check_call(c, lm, tmpl, K, cw, ch)) || (rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames)) ||
         (rc = align_check_rows(c)))
         return rc;
-    const int N = c->N;
-    std::vector<int> frame_of_row((size_t)N);
-    for (int r = 0; r < N; ++r) {
-        const int im = c->idx_identity ? r : c->img_idx_host[r];
-        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to image " + std::to_string(im) + ", beyond the frames");
-        if (frames[im].width != c->img_w_host[im] || frames[im].height != c->img_h_host[im])
-            return fail(SDM_ERR_INVALID, "frame " + std::to_string(im) + " differs in size from image " + std::to_string(im) + " of the context");
-        frame_of_row[r] = im;
-    }
+    std::vector<int> frame_of_row;
+    if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
     sdm_ctx::Align& a = c->align;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure((size_t)N))) return rc;
+    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure((size_t)c->N))) return rc;
     if ((rc = align_fit_rows(c, lm, tmpl, K, cw, ch))) return rc;
     return paste_run(c, true, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host);
 }
@@ -274,15 +258,14 @@ int sdm_align_paste_tensor_at(sdm_ctx* c, const float* matrices_host, const int*
     if (cw < 1 || cw > 1024 || ch < 1 || ch > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
     int rc;
     if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames))) return rc;
-    std::vector<int> frame_of_row((size_t)n_rows);
+    std::vector<int> frame_of_row;
+    if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;
     std::vector<AlignFace> faces((size_t)n_rows);
     for (int r = 0; r < n_rows; ++r) {
-        const int im = image_index ? image_index[r] : r;
-        if (im < 0 || im >= n_frames) return fail(SDM_ERR_INVALID, "row " + std::to_string(r) + " maps to frame " + std::to_string(im) + ", outside the list");
-        frame_of_row[r] = im;
+        const sdm_frame& fr = frames[frame_of_row[r]];
         AlignFace& f = faces[r];
         memcpy(f.m, matrices_host + (size_t)6 * r, 6 * sizeof(float));
-        f.flags = 0; f.w = frames[im].width; f.h = frames[im].height; f.stride = frames[im].stride_bytes; f.off = 0;
+        f.flags = 0; f.w = fr.width; f.h = fr.height; f.stride = fr.stride_bytes; f.off = 0;
     }
     sdm_ctx::Align& a = c->align;
     HIP_TRY(hipSetDevice(c->device));

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <stdint.h>
+#include "sdm_align_tensor_device.h"
 
 #define SDM_SCALE_TAB 128
 #define SDM_MAX_ORIENT 16  // max undirected orientations (num_bins) a level may ask for
@@ -407,12 +408,6 @@ struct AlignFrameDev {
     const uint8_t* p1;
     int stride, cstride, format, pad;
 };
-// what the element stage needs: per OUTPUT channel scale and bias, the channel order and the colour -> gray weights
-struct AlignTensorDev {
-    float scale[3], bias[3];
-    int order;                 // SDM_ALIGN_ORDER_*
-    int wb, wg, wr, gray_shift;
-};
 // faces: the fit's records (M, flags, size; offset and stride against `base` unless `frames` is given).  frames: the frame table, or
 // null -- then every row's image is `src_format` (GRAY, BGR or BGRA) at base + faces[n].off.  img_idx: row -> frame (null: identity).
 // out: N * channels * out_h * out_w elements of `dtype` in `layout` (SDM_ALIGN_*), 16-byte aligned.
@@ -432,18 +427,6 @@ struct AlignAreaDev {
 void sdm_launch_align_area(const uint8_t* base, const AlignFace* faces, const AlignFrameDev* frames, const int* img_idx, int src_format,
                            int N, int out_w, int out_h, int dtype, int layout, int channels, const AlignTensorDev& spec,
                            const AlignAreaDev& area, int* samples, void* out, hipStream_t s);
-
-// ---- crop tensors pasted back into frames (sdm_align_paste.hip; the records are csrc/sdm_align_paste_device.h's) ----
-struct PasteFrameDev;
-struct PasteRow;
-struct PasteCropDev;
-// faces: N records holding M (fitted: and the fit's flags; otherwise PARTIAL is evaluated here); the final flags go back into them.
-// frame_of_row: N frame indices; rows: N records out
-void sdm_launch_paste_prepare(AlignFace* faces, const int* frame_of_row, const PasteFrameDev* frames, int N, int cw, int ch, bool fitted,
-                              PasteRow* rows, hipStream_t s);
-// list: the rows of every frame, ascending (PasteFrameDev::row_begin / row_end); entry_of_row: where row n stands in it
-void sdm_launch_paste(const PasteFrameDev* frames, const PasteRow* rows, const int* list, const int* entry_of_row, int N,
-                      const PasteCropDev& crop, hipStream_t s);
 
 // ---- upright-normalised detect and tracking (sdm_upright.hip) ----
 // per row: the chip -> frame matrix M and its inverse W (float32, rounded from the double rotation), the SDM_UPRIGHT_* flags and the

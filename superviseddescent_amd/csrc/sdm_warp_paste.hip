@@ -7,8 +7,7 @@
 //                          memory: W_t, the corners in edge-function order, the triangle's box, the "covers nothing" bit.  FOLDED is the
 //                          bit warp_fit_kernel left in the row's record; lane 0 writes the row's record: nothing is atomic, nothing
 //                          depends on an execution order.
-//   warp_paste_kernel      the rigid paste's grid: (row, G workgroups); a workgroup strides over the 64 x 4 pixel tiles of its row's
-//                          box, a wave covers 64 consecutive pixels of one frame row.  The row's T records are staged in LDS once per
+//   warp_paste_kernel      the tile walk of csrc/sdm_paste.h over the row's box.  The row's T records are staged in LDS once per
 //                          workgroup (68 bytes each: 17 272 bytes at T = 254).  Per tile a wave culls: lane l tests the boxes of
 //                          triangles l, l + 64, ... against the wave's strip of pixels, four ballots give the candidate set in scalar
 //                          registers, and every lane walks the set bits in ascending order up to the first triangle that holds its
@@ -16,19 +15,15 @@
 //                          only leaves out triangles that the pixel's own test refuses, and this walk and the ownership path's
 //                          (warp_paste_footprint) decide every pixel alike.  The ownership
 //                          test against earlier rows of the frame and the application of later rows read those rows' records from
-//                          device memory, the row box first (warp_paste_owned).  One owner per pixel, no atomics, one pass.
+//                          device memory, the row box first (paste_owned).  One owner per pixel, no atomics, one pass.
 //
-// The per-pixel arithmetic is csrc/sdm_warp_paste_device.h.
-#include "sdm_warp.h"
-#include "sdm_warp_paste.h"
+// The per-pixel arithmetic is csrc/sdm_warp_paste_device.h on top of csrc/sdm_paste_device.h.
+#include "sdm_paste.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-#define WPASTE_BLOCK 256
-#define WPASTE_TILE_W 64
-#define WPASTE_TILE_H (WPASTE_BLOCK / WPASTE_TILE_W)
 #define WPASTE_PREPARE_BLOCK 256      // four rows per workgroup
 #define WPASTE_WORDS ((SDM_WARP_MAX_TRIANGLES + 63) / 64)
 #define WPASTE_REC_INTS ((int)(sizeof(WarpPasteTri) / sizeof(int)))
@@ -87,7 +82,7 @@ __global__ __launch_bounds__(WPASTE_PREPARE_BLOCK) void warp_paste_prepare_kerne
     if (lane == 0) rows[r] = row;
 }
 
-__global__ __launch_bounds__(WPASTE_BLOCK) void warp_paste_kernel(const PasteFrameDev* __restrict__ frames, const WarpPasteRow* __restrict__ rows,
+__global__ __launch_bounds__(PASTE_BLOCK) void warp_paste_kernel(const PasteFrameDev* __restrict__ frames, const WarpPasteRow* __restrict__ rows,
                                                                   const WarpPasteTri* __restrict__ tris, int T, const int* __restrict__ list,
                                                                   const int* __restrict__ entry_of_row, const uint8_t* __restrict__ labels,
                                                                   PasteCropDev c)
@@ -103,16 +98,15 @@ __global__ __launch_bounds__(WPASTE_BLOCK) void warp_paste_kernel(const PasteFra
     {
         const int* src = (const int*)(tris + (long long)n * T);
         int* dst = (int*)lds;
-        for (int e = threadIdx.x; e < T * WPASTE_REC_INTS; e += WPASTE_BLOCK) dst[e] = src[e];
+        for (int e = threadIdx.x; e < T * WPASTE_REC_INTS; e += PASTE_BLOCK) dst[e] = src[e];
     }
     __syncthreads();
-    const int tx = (bw + WPASTE_TILE_W - 1) / WPASTE_TILE_W, ty = (bh + WPASTE_TILE_H - 1) / WPASTE_TILE_H;
-    const int lx = threadIdx.x & (WPASTE_TILE_W - 1), ly = threadIdx.x / WPASTE_TILE_W;
+    const int tx = paste_tiles_x(bw), ty = paste_tiles_y(bh);
+    const int lx = threadIdx.x & (PASTE_TILE_W - 1), ly = threadIdx.x / PASTE_TILE_W;
     for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
-        const int tj = (int)(t % tx), ti = (int)(t / tx);
-        const int X0 = r.x0 + tj * WPASTE_TILE_W, Y = r.y0 + ti * WPASTE_TILE_H + ly;
+        const int X0 = r.x0 + paste_tile_x(t, tx), Y = r.y0 + paste_tile_y(t, tx) + ly;
         if (Y >= r.y1) continue;                                    // (the whole wave)
-        const int X = X0 + lx, X1 = X0 + WPASTE_TILE_W < r.x1 ? X0 + WPASTE_TILE_W : r.x1;
+        const int X = X0 + lx, X1 = X0 + PASTE_TILE_W < r.x1 ? X0 + PASTE_TILE_W : r.x1;
         // the wave's candidates: triangles whose box meets its strip of pixels
         unsigned long long cand[WPASTE_WORDS];
 #pragma unroll
@@ -132,7 +126,7 @@ __global__ __launch_bounds__(WPASTE_BLOCK) void warp_paste_kernel(const PasteFra
             }
         }
         AlignPos q;
-        if (mine >= 0 && warp_paste_position(lds[mine], c.cw, c.ch, X, Y, q)) warp_paste_owned(f, rows, tris, T, list, k, c, labels, X, Y, q);
+        if (mine >= 0 && paste_position(lds[mine].w, c.cw, c.ch, X, Y, q)) paste_owned(f, PasteMesh{rows, tris, T, labels}, list, k, c, X, Y, q);
     }
 }
 
@@ -150,9 +144,6 @@ void sdm_launch_warp_paste_prepare(const float* x, int N, int L, const int* lm, 
 void sdm_launch_warp_paste(const PasteFrameDev* frames, const WarpPasteRow* rows, const WarpPasteTri* tris, int T, const int* list,
                            const int* entry_of_row, int N, const uint8_t* labels, const PasteCropDev& crop, hipStream_t s)
 {
-    // workgroups per row: the rigid paste's rule, one per 1 024 crop pixels, 1 ... 32
-    int groups = (crop.cw * crop.ch + 1023) / 1024;
-    groups = groups < 1 ? 1 : (groups > 32 ? 32 : groups);
-    hipLaunchKernelGGL(warp_paste_kernel, dim3((unsigned)N, (unsigned)groups), dim3(WPASTE_BLOCK), 0, s, frames, rows, tris, T, list, entry_of_row,
-                       labels, crop);
+    hipLaunchKernelGGL(warp_paste_kernel, dim3((unsigned)N, (unsigned)paste_groups(crop)), dim3(PASTE_BLOCK), 0, s, frames, rows, tris, T, list,
+                       entry_of_row, labels, crop);
 }

@@ -1,14 +1,14 @@
 // sdm_warp_paste_device.h -- the arithmetic of the piecewise-affine paste (include/sdm.h, "Pasting warped faces back"): a row's flags
 // and box from its mesh landmarks, a triangle's record -- the inverse W_t of its float32 A_t, its corners in edge-function order, its
-// box --, the triangle of a frame pixel, its position, and warp_paste_owned: what one frame pixel's owner does from the ownership
-// test to its one store.  The fit is warp_fit_triangle (sdm_warp_device.h); the inverse, the taps, the decode, the blend and the pixel's
-// load / apply / store are sdm_align_paste_device.h's; the quantisation is sdm_align_tensor_device.h's.  Plain C++ behind ALIGN_HD, so
+// box --, the triangle of a frame pixel, and the paste's shape for the ownership rule (PasteMesh).  The fit is warp_fit_triangle
+// (sdm_warp_device.h); the inverse, the position, the taps, the decode, the blend, the pixel's load / apply / store and the ownership
+// rule (paste_owned) are sdm_paste_device.h's; the quantisation is sdm_align_tensor_device.h's.  Plain C++ behind ALIGN_HD, so
 // the same text is the device code of csrc/sdm_warp_paste.hip and -- compiled for the host, tests/cpp/warp_paste_host.cpp -- a program
 // that runs under the host sanitizers.
 //
 // Every floating-point operation is rounded on its own (no contraction: the pragma below under clang, -ffp-contract=off elsewhere).
 #pragma once
-#include "sdm_align_paste_device.h"
+#include "sdm_paste_device.h"
 #include "sdm_warp_device.h"
 
 #if defined(__clang__)
@@ -126,16 +126,6 @@ ALIGN_HD bool warp_paste_inside(const WarpPasteTri& t, int X, int Y)
     return e2 >= 0.0;
 }
 
-// the pixel's position in the crop through its triangle: accepted by the 2^20 rule and with at least one tap in the crop
-ALIGN_HD bool warp_paste_position(const WarpPasteTri& t, int cw, int ch, int X, int Y, AlignPos& q)
-{
-    const float fx = (float)X, fy = (float)Y;
-    const float u = (t.w[0] * fx + t.w[1] * fy) + t.w[2];
-    const float v = (t.w[3] * fx + t.w[4] * fy) + t.w[5];
-    if (!align_quantise(u, v, q)) return false;
-    return q.x0 >= -1 && q.x0 <= cw - 1 && q.y0 >= -1 && q.y0 <= ch - 1;
-}
-
 // frame pixel (X, Y) in the footprint of row r with the T records tris: inside the row's box, the lowest-numbered covering triangle that
 // holds it, and that triangle's position accepted
 ALIGN_HD bool warp_paste_footprint(const WarpPasteRow& r, const WarpPasteTri* tris, int T, int cw, int ch, int X, int Y, AlignPos& q)
@@ -144,31 +134,32 @@ ALIGN_HD bool warp_paste_footprint(const WarpPasteRow& r, const WarpPasteTri* tr
     for (int t = 0; t < T; ++t) {
         const WarpPasteTri& tr = tris[t];
         if (!warp_paste_inside(tr, X, Y)) continue;
-        return warp_paste_position(tr, cw, ch, X, Y, q);
+        return paste_position(tr.w, cw, ch, X, Y, q);
     }
     return false;
 }
 
-// Frame pixel (X, Y), which lies in the footprint of entry k of its frame's row list at position q: nothing if an earlier entry's
-// footprint holds it too -- else this is the pixel's one reader and writer: the old bytes once, entry k and every later entry that
-// holds the pixel applied in order, the colour bytes stored once if any opacity was not 0.  rows: all rows' records; tris: all rows'
-// triangle records, T per row; list: the row lists; labels: the mesh's label map (crop_height x crop_width).
+// the piecewise-affine paste's shape for paste_owned: all rows' records, their triangle records (T per row), the mesh's label map
+struct PasteMesh {
+    const WarpPasteRow* rows;
+    const WarpPasteTri* tris;
+    int T;
+    const uint8_t* labels;
+};
+
+ALIGN_HD bool paste_holds(const PasteMesh& p, int n, const PasteCropDev& c, int X, int Y, AlignPos& q)
+{
+    return warp_paste_footprint(p.rows[n], p.tris + (long long)n * p.T, p.T, c.cw, c.ch, X, Y, q);
+}
+
+ALIGN_HD void paste_taps(const PasteMesh& p, const PasteCropDev& c, int n, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
+{
+    paste_sample_taps<true>(c, n, q, p.labels, bgr, a);
+}
+
+// paste_owned for the mesh from its parts, as the host program calls it
 ALIGN_HD void warp_paste_owned(const PasteFrameDev& f, const WarpPasteRow* rows, const WarpPasteTri* tris, int T, const int* list, int k,
                                const PasteCropDev& c, const uint8_t* labels, int X, int Y, AlignPos q)
 {
-    for (int j = f.row_begin; j < k; ++j) {
-        AlignPos qj;
-        const int n = list[j];
-        if (warp_paste_footprint(rows[n], tris + (long long)n * T, T, c.cw, c.ch, X, Y, qj)) return;
-    }
-    PastePixel s;
-    paste_load(f, X, Y, s);
-    for (int j = k; j < f.row_end; ++j) {
-        const int n = list[j];
-        if (j > k && !warp_paste_footprint(rows[n], tris + (long long)n * T, T, c.cw, c.ch, X, Y, q)) continue;
-        uint32_t bgr[3], a;
-        paste_sample_taps<true>(c, n, q, labels, bgr, a);
-        paste_apply(c, bgr, a, s);
-    }
-    paste_store(s);
+    paste_owned(f, PasteMesh{rows, tris, T, labels}, list, k, c, X, Y, q);
 }

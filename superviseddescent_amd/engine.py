@@ -854,6 +854,16 @@ class Context:
         torch.cuda.current_stream(y.device).synchronize()
         return spec, paste, arr, n, width, height, (alpha, frames)
 
+    def _paste_rows(self, n):                                   # the fit forms: the tensor's rows are the context's current rows
+        if int(getattr(self, "N", 0)) and n != self.N:          # (no rows yet: the library refuses the call)
+            raise ValueError(f"the tensor has {n} rows, the context {int(getattr(self, 'N', 0))}")
+
+    def _paste_image_index(self, image_index, n):               # the ``_at`` forms: None, or one int32 per row
+        idx = None if image_index is None else np.ascontiguousarray(image_index, np.int32).reshape(-1)
+        if idx is not None and idx.size != n:
+            raise ValueError("one image index per row expected")
+        return idx
+
     def align_paste_tensor(self, landmark_index, template: np.ndarray, y, frames, formats=None, layout="nchw", mask=None, spec=None,
                            **options):
         """The inverse of ``align_crops_tensor`` for the N current rows (include/sdm.h, sdm_align_paste_tensor): ``y`` -- a network's
@@ -868,8 +878,7 @@ class Context:
         if t.shape[0] != idx.size:
             raise ValueError("one template point (x, y) per landmark index expected")
         spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
-        if int(getattr(self, "N", 0)) and n != self.N:          # (no rows yet: the library refuses the call)
-            raise ValueError(f"the tensor has {n} rows, the context {int(getattr(self, 'N', 0))}")
+        self._paste_rows(n)
         mats = np.empty((n, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
         check(self._lib.sdm_align_paste_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, width, height, ctypes.byref(spec),
@@ -885,9 +894,7 @@ class Context:
         m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 6)
         if m.shape[0] != n:
             raise ValueError(f"one matrix per row of the tensor expected: {m.shape[0]} for {n}")
-        idx = None if image_index is None else np.ascontiguousarray(image_index, np.int32).reshape(-1)
-        if idx is not None and idx.size != n:
-            raise ValueError("one image index per row expected")
+        idx = self._paste_image_index(image_index, n)
         flags = np.empty(n, np.int32)
         check(self._lib.sdm_align_paste_tensor_at(self._h, m.ctypes.data, None if idx is None else idx.ctypes.data, n, width, height,
                                                   ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr),
@@ -909,8 +916,7 @@ class Context:
         int32: SDM_WARP_* bits)."""
         spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
         T = self._warp_paste_size(width, height)
-        if int(getattr(self, "N", 0)) and n != self.N:          # (no rows yet: the library refuses the call)
-            raise ValueError(f"the tensor has {n} rows, the context {int(getattr(self, 'N', 0))}")
+        self._paste_rows(n)
         mats = np.empty((n, T, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
         check(self._lib.sdm_warp_paste_tensor(self._h, ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr),
@@ -926,9 +932,7 @@ class Context:
         p = np.ascontiguousarray(points, np.float32)
         if p.ndim != 3 or p.shape[0] != n or p.shape[2] != 2:
             raise ValueError(f"points must be N x K x 2 with one row per row of the tensor ({n}), not {p.shape}")
-        idx = None if image_index is None else np.ascontiguousarray(image_index, np.int32).reshape(-1)
-        if idx is not None and idx.size != n:
-            raise ValueError("one image index per row expected")
+        idx = self._paste_image_index(image_index, n)
         flags = np.empty(n, np.int32)
         check(self._lib.sdm_warp_paste_tensor_at(self._h, p.ctypes.data, None if idx is None else idx.ctypes.data, n, ctypes.byref(spec),
                                                  ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr), flags.ctypes.data))
