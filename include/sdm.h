@@ -781,8 +781,9 @@ int sdm_warp_crops_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, void* out_
  *           previous one left, whatever the launch order: a pixel is loaded once, every row whose footprint holds it is applied in
  *           registers in row order, and it is stored once.
  *   never stored to, not even with their old value: pitch padding, pixels outside every footprint, pixels whose every a is 0, alpha bytes.
- * Out of scope, and not half-built: NV12 destinations (refused) and any antialiasing when the face in the frame is smaller than the
- * crop -- the paste is plain bilinear, as sdm_align_crops is.  (The inverse of sdm_warp_crops_tensor is "Pasting warped faces back".)
+ * Out of scope, and not half-built: NV12 destinations (refused).  These two calls are plain bilinear, as sdm_align_crops is; the
+ * antialiasing for a face that is smaller in the frame than in the crop is the filtered form, "Pasting crops back, filtered" below.
+ * (The inverse of sdm_warp_crops_tensor is "Pasting warped faces back".)
  * Refused with SDM_ERR_INVALID, no state changed, nothing launched: what sdm_align_crops_tensor refuses of landmark_index, template_xy,
  * K, the crop size, spec and the rows' source (fit form); in_dev NULL or not 16-byte aligned; paste NULL; alpha_per_row not 0 or 1;
  * dst_frames NULL or n_frames < 1; what sdm_set_frames_device refuses of a frame; an NV12 frame; a row whose image index is outside
@@ -803,6 +804,52 @@ int sdm_align_paste_tensor(sdm_ctx* ctx, const int* landmark_index, const float*
 int sdm_align_paste_tensor_at(sdm_ctx* ctx, const float* matrices_host /* in, n_rows x 6 */, const int* image_index /* NULL: row i -> frame i */,
                               int n_rows, int crop_width, int crop_height, const sdm_align_tensor* spec, const void* in_dev,
                               const sdm_align_paste* paste, const sdm_frame* dst_frames, int n_frames, int* flags_host);
+
+/* Pasting crops back, filtered: sdm_align_paste_tensor and sdm_align_paste_tensor_at with area-averaged sampling where the crop outsizes
+ * the face.  A network that runs at 256 or 512 pixels on a face 60 to 200 pixels wide in the frame puts 9 to 64 tensor elements under
+ * every frame pixel, of which four bilinear taps see a fraction: fine texture aliases and shimmers from frame to frame.  Here every frame
+ * pixel of such a row takes the average of S x S bilinear sub-samples spread over its footprint in the crop, S chosen per row from W, in
+ * the integer arithmetic of the paste; the average is taken BEFORE the blend, of colour and opacity alike.  One launch for all rows
+ * behind the prepare stage.  Every rule of "Pasting crops back" that is not restated here holds word for word: M, W, the flags, the
+ * decode, the clamped colour taps, opacity 0 outside the crop, the / 255 blend, per-byte stores, the alpha byte never touched, the rows
+ * of one frame applied in increasing row number.  NV12 destinations stay refused; the piecewise-affine paste (sdm_warp_paste_tensor*)
+ * stays plain bilinear.  Every float operation is rounded on its own, nothing is contracted.
+ *   S of row n   s2 = W00 W00 + W10 W10 in float32 on the float32 W, each operation rounded: the mirror image of
+ *           sdm_align_crops_tensor_filtered, which takes it from M.  S = 1 for mode BILINEAR, for s2 < min_scale * min_scale (float32),
+ *           for a non-finite s2 and for a DEGENERATE row; otherwise the smallest integer in [1, max_samples] with (float)(S S) >= s2, and
+ *           max_samples when there is none.  samples_host[n] = S.
+ *   sub-samples of frame pixel (X, Y), S > 1   for u, v in 0 ... S - 1: fX = (float)X + o[u], fY = (float)Y + o[v], with
+ *           o[u] = (float)(2u + 1 - S) / (float)(2S) as in sdm_align_crops_tensor_filtered; the position is (W00 fX + W01 fY) + W02 and
+ *           (W10 fX + W11 fY) + W12, quantised as in "Pasting crops back" (2^20 rule, 1/32 pixel).  Per sub-sample the UNROUNDED sums:
+ *           per channel w00 p00 + w10 p10 + w01 p01 + w11 p11 with the taps clamped into the crop, and the same weights on the opacity,
+ *           where a tap outside the crop reads 0 and, with alpha_dev NULL, a tap inside reads 255.
+ *   pixel   q_c = (sum over the S S sub-samples + 512 S S) / (1024 S S) per channel, a the same from the opacity sums: unsigned integer
+ *           divisions; the sums stay below 2^26 + 2^17.  Channel order, the gray weights and the blend apply to the averaged q and a
+ *           exactly as they do at S = 1.
+ *   not touched by a row   a pixel of which any sub-sample is refused by the 2^20 rule; a pixel with a == 0: no byte is written.
+ *   result and footprint   the RESULT is the formula above evaluated over the whole frame, row after row.  The kernel's working
+ *           footprint of a row with S > 1 is one predicate, used alike for "an earlier row owns this pixel" and "this row is applied
+ *           here": the pixel lies in the row's box -- the box of the unfiltered paste one frame pixel wider on each side, |o| < 1/2; an empty box stays empty --
+ *           and the float32 position (u, v) of its CENTRE (the expression of "Pasting crops back") satisfies
+ *           -1 - du <= u <= crop_width + du and -1 - dv <= v <= crop_height + dv, with du = (|W00| + |W01|) / 2 + 2^-20 mag_u + 9/32,
+ *           mag_u = |W00| (width + 1) + |W01| (height + 1) + |W02| (double, rounded once to float32), dv and mag_v the same on the
+ *           second row of W.  With mag_u or mag_v >= 2^20, or du or dv >= 2^15, the box alone decides.  The predicate holds every pixel
+ *           for which the formula gives a != 0; pixels it holds beyond those get a == 0 and are not written.
+ *   S = 1   such a row gives the bits of the unfiltered call, through its footprint and its code.  Rows of different S on one frame
+ *           overlap and are applied in row order.  With mode BILINEAR the call writes exactly the bytes of the unfiltered one.
+ * Refused in addition to what the unfiltered calls refuse (SDM_ERR_INVALID, no state changed, nothing launched): filter NULL, an unknown
+ * mode, max_samples outside [1, 16], min_scale not finite or below 1.  samples_host (one int per row) may be NULL; S comes back in the
+ * same copy as the flags. */
+int sdm_align_paste_tensor_filtered(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int crop_width,
+                                    int crop_height, const sdm_align_tensor* spec, const sdm_align_filter* filter, const void* in_dev,
+                                    const sdm_align_paste* paste, const sdm_frame* dst_frames, int n_frames,
+                                    float* matrices_host /* out, N x 6, may be NULL */, int* flags_host /* out, may be NULL */,
+                                    int* samples_host /* out, may be NULL */);
+int sdm_align_paste_tensor_at_filtered(sdm_ctx* ctx, const float* matrices_host /* in, n_rows x 6 */,
+                                       const int* image_index /* NULL: row i -> frame i */, int n_rows, int crop_width, int crop_height,
+                                       const sdm_align_tensor* spec, const sdm_align_filter* filter, const void* in_dev,
+                                       const sdm_align_paste* paste, const sdm_frame* dst_frames, int n_frames, int* flags_host,
+                                       int* samples_host);
 
 /* Pasting warped faces back: the inverse path of sdm_warp_crops_tensor.  A network's output in template space -- a transferred
  * expression, a swapped, re-lit or de-aged texture -- is warped back under the face's own shape, triangle by triangle, and blended into

@@ -41,6 +41,7 @@ EXPORTED = [
     "sdm_warp_delaunay", "sdm_warp_set_mesh", "sdm_warp_get_labels", "sdm_warp_crops_tensor",
     "sdm_align_paste_tensor", "sdm_align_paste_tensor_at",
     "sdm_warp_paste_tensor", "sdm_warp_paste_tensor_at",
+    "sdm_align_paste_tensor_filtered", "sdm_align_paste_tensor_at_filtered",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -450,6 +451,12 @@ def lib() -> ctypes.CDLL:
                                       ctypes.POINTER(SdmFrame), c_int, c_void_p, c_void_p],
             "sdm_warp_paste_tensor_at": [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,
                                          ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_int, c_void_p],
+            "sdm_align_paste_tensor_filtered": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor),
+                                                ctypes.POINTER(SdmAlignFilter), c_void_p, ctypes.POINTER(SdmAlignPaste),
+                                                ctypes.POINTER(SdmFrame), c_int, c_void_p, c_void_p, c_void_p],
+            "sdm_align_paste_tensor_at_filtered": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor),
+                                                   ctypes.POINTER(SdmAlignFilter), c_void_p, ctypes.POINTER(SdmAlignPaste),
+                                                   ctypes.POINTER(SdmFrame), c_int, c_void_p, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

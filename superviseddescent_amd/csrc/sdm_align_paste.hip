@@ -8,7 +8,12 @@
 //                          and writer in the launch, whatever the order the workgroups run in.  Stores are per pixel, byte by byte:
 //                          nothing a neighbour owns is touched.
 //
-// The per-pixel arithmetic is csrc/sdm_align_paste_device.h on top of csrc/sdm_paste_device.h.
+//   paste_area_prepare_kernel, paste_area_kernel   the filtered calls' pair: the prepare stage also leaves S and the working footprint
+//                          of every row (PasteAreaRow); the paste is the same tile walk and the same ownership rule on the shape
+//                          PasteRigidArea.  S is uniform for a workgroup (one row) and, in the owner loop, per list entry: every
+//                          sub-sample loop has a wave-uniform trip count.  Rows with S = 1 take paste_kernel's per-pixel code.
+//
+// The per-pixel arithmetic is csrc/sdm_align_paste_device.h and csrc/sdm_align_paste_area_device.h on top of csrc/sdm_paste_device.h.
 #include "sdm_paste.h"
 
 #pragma clang fp contract(off)
@@ -52,6 +57,45 @@ __global__ __launch_bounds__(PASTE_BLOCK) void paste_kernel(const PasteFrameDev*
     }
 }
 
+__global__ __launch_bounds__(PASTE_PREPARE_BLOCK) void paste_area_prepare_kernel(AlignFace* __restrict__ faces, const int* __restrict__ frame_of_row,
+                                                                                 const PasteFrameDev* __restrict__ frames, int N, int cw, int ch,
+                                                                                 int fitted, AlignAreaDev area, PasteRow* __restrict__ rows,
+                                                                                 PasteAreaRow* __restrict__ area_rows, int* __restrict__ samples)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= N) return;
+    const int fi = frame_of_row[n];
+    const PasteFrameDev f = frames[fi];
+    float m[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) m[e] = faces[n].m[e];
+    PasteRow r;
+    PasteAreaRow ar;
+    paste_area_prepare_row(m, fitted ? faces[n].flags : -1, fi, f.w, f.h, cw, ch, area.mode, area.max_samples, area.min2, r, ar);
+    rows[n] = r;
+    area_rows[n] = ar;
+    samples[n] = ar.S;
+    faces[n].flags = r.flags;
+}
+
+__global__ __launch_bounds__(PASTE_BLOCK) void paste_area_kernel(const PasteFrameDev* __restrict__ frames, const PasteRow* __restrict__ rows,
+                                                                 const PasteAreaRow* __restrict__ area_rows, const int* __restrict__ list,
+                                                                 const int* __restrict__ entry_of_row, PasteCropDev c)
+{
+    const int n = blockIdx.x;
+    const int k = entry_of_row[n];
+    const PasteRow r = rows[n];
+    const int bw = r.x1 - r.x0, bh = r.y1 - r.y0;
+    if (bw <= 0 || bh <= 0) return;
+    const PasteFrameDev f = frames[r.frame];
+    const int tx = paste_tiles_x(bw), ty = paste_tiles_y(bh);
+    const int lx = threadIdx.x & (PASTE_TILE_W - 1), ly = threadIdx.x / PASTE_TILE_W;
+    for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
+        const int X = r.x0 + paste_tile_x(t, tx) + lx, Y = r.y0 + paste_tile_y(t, tx) + ly;
+        if (X < r.x1 && Y < r.y1) paste_area_pixel(f, rows, area_rows, list, k, c, X, Y);
+    }
+}
+
 }  // namespace
 
 void sdm_launch_paste_prepare(AlignFace* faces, const int* frame_of_row, const PasteFrameDev* frames, int N, int cw, int ch, bool fitted,
@@ -66,4 +110,18 @@ void sdm_launch_paste(const PasteFrameDev* frames, const PasteRow* rows, const i
 {
     hipLaunchKernelGGL(paste_kernel, dim3((unsigned)N, (unsigned)paste_groups(crop)), dim3(PASTE_BLOCK), 0, s, frames, rows, list, entry_of_row,
                        crop);
+}
+
+void sdm_launch_paste_area_prepare(AlignFace* faces, const int* frame_of_row, const PasteFrameDev* frames, int N, int cw, int ch, bool fitted,
+                                   const AlignAreaDev& area, PasteRow* rows, PasteAreaRow* area_rows, int* samples, hipStream_t s)
+{
+    hipLaunchKernelGGL(paste_area_prepare_kernel, dim3((unsigned)((N + PASTE_PREPARE_BLOCK - 1) / PASTE_PREPARE_BLOCK)), dim3(PASTE_PREPARE_BLOCK),
+                       0, s, faces, frame_of_row, frames, N, cw, ch, fitted ? 1 : 0, area, rows, area_rows, samples);
+}
+
+void sdm_launch_paste_area(const PasteFrameDev* frames, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
+                           const int* entry_of_row, int N, const PasteCropDev& crop, hipStream_t s)
+{
+    hipLaunchKernelGGL(paste_area_kernel, dim3((unsigned)N, (unsigned)paste_groups(crop)), dim3(PASTE_BLOCK), 0, s, frames, rows, area_rows, list,
+                       entry_of_row, crop);
 }

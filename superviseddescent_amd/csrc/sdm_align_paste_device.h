@@ -88,7 +88,7 @@ ALIGN_HD bool paste_holds(const PasteRigid& p, int n, const PasteCropDev& c, int
     return paste_footprint(p.rows[n], c.cw, c.ch, X, Y, q);
 }
 
-ALIGN_HD void paste_taps(const PasteRigid&, const PasteCropDev& c, int n, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
+ALIGN_HD void paste_taps(const PasteRigid&, const PasteCropDev& c, int n, int, int, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
 {
     paste_sample_taps<false>(c, n, q, nullptr, bgr, a);
 }

@@ -128,6 +128,15 @@ int sdm_capi::align_fit_rows(sdm_ctx* c, const int* lm, const float* tmpl, int K
     return SDM_OK;
 }
 
+int sdm_capi::align_check_filter(const sdm_align_filter* filter)
+{
+    if (!filter) return fail(SDM_ERR_INVALID, "no filter");
+    if (filter->mode != SDM_ALIGN_FILTER_BILINEAR && filter->mode != SDM_ALIGN_FILTER_AREA) return fail(SDM_ERR_INVALID, "unknown filter mode");
+    if (filter->max_samples < 1 || filter->max_samples > 16) return fail(SDM_ERR_INVALID, "max_samples must be in [1, 16]");
+    if (!std::isfinite(filter->min_scale) || filter->min_scale < 1.0f) return fail(SDM_ERR_INVALID, "min_scale must be finite and >= 1");
+    return SDM_OK;
+}
+
 // the records -- and, behind them in the same buffer, the rows' S when `samples_host` is given -- in one copy, one synchronise
 static int align_fetch_rows(sdm_ctx* c, float* matrices_host, int* flags_host, int* samples_host = nullptr)
 {
@@ -160,12 +169,7 @@ static int align_tensor_call(sdm_ctx* c, const int* lm, const float* tmpl, int K
     int rc;
     if ((rc = align_check_call(c, lm, tmpl, K, out_w, out_h))) return rc;
     if ((rc = align_check_spec(spec))) return rc;
-    if (filtered) {
-        if (!filter) return fail(SDM_ERR_INVALID, "no filter");
-        if (filter->mode != SDM_ALIGN_FILTER_BILINEAR && filter->mode != SDM_ALIGN_FILTER_AREA) return fail(SDM_ERR_INVALID, "unknown filter mode");
-        if (filter->max_samples < 1 || filter->max_samples > 16) return fail(SDM_ERR_INVALID, "max_samples must be in [1, 16]");
-        if (!std::isfinite(filter->min_scale) || filter->min_scale < 1.0f) return fail(SDM_ERR_INVALID, "min_scale must be finite and >= 1");
-    }
+    if (filtered && (rc = align_check_filter(filter))) return rc;
     if ((rc = align_check_out(out_dev))) return rc;
     if ((rc = align_check_rows(c))) return rc;
     const int N = c->N;

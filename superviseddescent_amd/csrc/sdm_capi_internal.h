@@ -409,6 +409,7 @@ int check_frame(int i, const sdm_frame& frame, bool allow_nv12);
 int align_check_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h);      // geometry, rows, indices, template, crop size
 int align_fit_rows(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h);        // the fit of every row into align.faces
 int align_check_spec(const sdm_align_tensor* spec);
+int align_check_filter(const sdm_align_filter* filter);                                                    // mode, max_samples, min_scale
 int align_check_out(const void* out_dev);
 int align_check_rows(sdm_ctx* c);
 AlignTensorDev align_tensor_dev(const sdm_align_tensor* spec);

@@ -1,7 +1,7 @@
 // sdm_capi_paste.hip -- C-ABI of the paste-back of crop tensors into frames (include/sdm.h, "Pasting crops back" and "Pasting warped
 // faces back"): the entry points check every argument before anything is launched or changed, build the frame table and the rows-of-frame lists on the host from the
 // image index they already hold, and enqueue -- fit form -- sdm_align_crops' fit, then the prepare kernel and the one paste launch
-// (csrc/sdm_align_paste.hip); the piecewise-affine forms enqueue warp_fit_kernel, their prepare kernel and their paste launch
+// (csrc/sdm_align_paste.hip), the filtered forms that file's area-capable pair; the piecewise-affine forms enqueue warp_fit_kernel, their prepare kernel and their paste launch
 // (csrc/sdm_warp_paste.hip) on the mesh of sdm_warp_set_mesh.  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
 // landmark state, the images, the crop source and the tracker's slots are only read; the frames' colour bytes are written in place.
 #include "sdm_capi_internal.h"
@@ -107,31 +107,58 @@ PasteCropDev paste_crop_dev(const sdm_align_tensor* spec, const void* in_dev, co
     return crop;
 }
 
-// behind the checks: `faces` holds N records with M (fitted: and the fit's flags).  frame_of_row: N checked indices.
+// the N records of align.faces, with room for N ints -- the rows' S -- behind them when the call is filtered
+size_t paste_face_records(int N, bool filtered)
+{
+    return (size_t)N + (filtered ? ((size_t)N * sizeof(int) + sizeof(AlignFace) - 1) / sizeof(AlignFace) : 0);
+}
+
+// behind the checks: `faces` holds N records with M (fitted: and the fit's flags).  frame_of_row: N checked indices.  filter: null --
+// the unfiltered calls --, or the checked filter of the filtered ones: their prepare stage and their kernel, S behind the records
 int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int cw, int ch, const sdm_align_tensor* spec, const void* in_dev,
-              const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host, int* flags_host)
+              const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host, int* flags_host,
+              const sdm_align_filter* filter, int* samples_host)
 {
     sdm_ctx::Align& a = c->align;
     const int N = (int)frame_of_row.size();
     int rc;
     PasteTables tab;
-    if ((rc = a.paste_rows.ensure((size_t)N * sizeof(PasteRow))) || (rc = paste_tables(c, frame_of_row, frames, n_frames, tab))) return rc;
+    const size_t rows_bytes = (size_t)N * sizeof(PasteRow);
+    if ((rc = a.paste_rows.ensure(rows_bytes + (filter ? (size_t)N * sizeof(PasteAreaRow) : 0))) ||
+        (rc = paste_tables(c, frame_of_row, frames, n_frames, tab)))
+        return rc;
     PasteRow* rows_dev = (PasteRow*)a.paste_rows.p;
-    sdm_launch_paste_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, rows_dev, c->stream);
+    const PasteCropDev crop = paste_crop_dev(spec, in_dev, paste, cw, ch);
+    if (!filter) {
+        sdm_launch_paste_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, rows_dev, c->stream);
+        HIP_TRY(hipGetLastError());
+        sdm_launch_paste(tab.frames, rows_dev, tab.list, tab.entry, N, crop, c->stream);
+    } else {
+        AlignAreaDev area{};
+        area.mode = filter->mode; area.max_samples = filter->max_samples;
+        area.min2 = filter->min_scale * filter->min_scale;                          // (float32, rounded once; may be inf: then every S is 1)
+        PasteAreaRow* area_dev = (PasteAreaRow*)(a.paste_rows.p + rows_bytes);
+        sdm_launch_paste_area_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, area, rows_dev, area_dev, (int*)(a.faces.p + N),
+                                      c->stream);
+        HIP_TRY(hipGetLastError());
+        sdm_launch_paste_area(tab.frames, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);
+    }
     HIP_TRY(hipGetLastError());
-    sdm_launch_paste(tab.frames, rows_dev, tab.list, tab.entry, N, paste_crop_dev(spec, in_dev, paste, cw, ch), c->stream);
-    HIP_TRY(hipGetLastError());
-    // the records in one copy, one synchronise
-    std::vector<AlignFace> host;
-    if (matrices_host || flags_host) {
-        host.resize((size_t)N);
-        HIP_TRY(hipMemcpyAsync(host.data(), a.faces.p, (size_t)N * sizeof(AlignFace), hipMemcpyDeviceToHost, c->stream));
+    // the records -- and the rows' S behind them -- in one copy, one synchronise
+    const size_t rec = (size_t)N * sizeof(AlignFace), bytes = rec + (samples_host ? (size_t)N * sizeof(int) : 0);
+    std::vector<unsigned char> host;
+    if (matrices_host || flags_host || samples_host) {
+        host.resize(bytes);
+        HIP_TRY(hipMemcpyAsync(host.data(), a.faces.p, bytes, hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t r = 0; r < host.size(); ++r) {
-        if (matrices_host) memcpy(matrices_host + 6 * r, host[r].m, 6 * sizeof(float));
-        if (flags_host) flags_host[r] = host[r].flags;
+    if (host.empty()) return SDM_OK;
+    const AlignFace* faces = (const AlignFace*)host.data();
+    for (int r = 0; r < N; ++r) {
+        if (matrices_host) memcpy(matrices_host + (size_t)6 * r, faces[r].m, 6 * sizeof(float));
+        if (flags_host) flags_host[r] = faces[r].flags;
     }
+    if (samples_host) memcpy(samples_host, host.data() + rec, (size_t)N * sizeof(int));
     return SDM_OK;
 }
 
@@ -172,6 +199,55 @@ int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const 
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (size_t r = 0; r < host.size(); ++r) flags_host[r] = host[r].flags;
     return SDM_OK;
+}
+
+// sdm_align_paste_tensor (filtered false) and sdm_align_paste_tensor_filtered: the same checks, the same fit, then the paste
+int paste_fit_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, int ch, const sdm_align_tensor* spec,
+                   const sdm_align_filter* filter, bool filtered, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
+                   int n_frames, float* matrices_host, int* flags_host, int* samples_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    int rc;
+    if ((rc = align_check_call(c, lm, tmpl, K, cw, ch)) || (rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
+        (rc = paste_check_args(in_dev, paste, frames, n_frames)) || (rc = align_check_rows(c)))
+        return rc;
+    std::vector<int> frame_of_row;
+    if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
+    sdm_ctx::Align& a = c->align;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(paste_face_records(c->N, filtered)))) return rc;
+    if ((rc = align_fit_rows(c, lm, tmpl, K, cw, ch))) return rc;
+    return paste_run(c, true, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host, filtered ? filter : nullptr,
+                     samples_host);
+}
+
+// sdm_align_paste_tensor_at (filtered false) and sdm_align_paste_tensor_at_filtered
+int paste_at_call(sdm_ctx* c, const float* matrices_host, const int* image_index, int n_rows, int cw, int ch, const sdm_align_tensor* spec,
+                  const sdm_align_filter* filter, bool filtered, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
+                  int n_frames, int* flags_host, int* samples_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    if (!matrices_host) return fail(SDM_ERR_INVALID, "no matrices");
+    if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
+    if (cw < 1 || cw > 1024 || ch < 1 || ch > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
+    int rc;
+    if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) || (rc = paste_check_args(in_dev, paste, frames, n_frames)))
+        return rc;
+    std::vector<int> frame_of_row;
+    if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;
+    std::vector<AlignFace> faces((size_t)n_rows);
+    for (int r = 0; r < n_rows; ++r) {
+        const sdm_frame& fr = frames[frame_of_row[r]];
+        AlignFace& f = faces[r];
+        memcpy(f.m, matrices_host + (size_t)6 * r, 6 * sizeof(float));
+        f.flags = 0; f.w = fr.width; f.h = fr.height; f.stride = fr.stride_bytes; f.off = 0;
+    }
+    sdm_ctx::Align& a = c->align;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = a.faces.ensure(paste_face_records(n_rows, filtered)))) return rc;
+    HIP_TRY(hipMemcpyAsync(a.faces.p, faces.data(), faces.size() * sizeof(AlignFace), hipMemcpyHostToDevice, c->stream));
+    return paste_run(c, false, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, nullptr, flags_host, filtered ? filter : nullptr,
+                     samples_host);
 }
 
 int warp_paste_check_mesh(sdm_ctx* c)
@@ -234,44 +310,29 @@ int sdm_align_paste_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, 
                            const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host,
                            int* flags_host)
 {
-    if (!c) return fail(SDM_ERR_INVALID, "null context");
-    int rc;
-    if ((rc = align_check_call(c, lm, tmpl, K, cw, ch)) || (rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames)) ||
-        (rc = align_check_rows(c)))
-        return rc;
-    std::vector<int> frame_of_row;
-    if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
-    sdm_ctx::Align& a = c->align;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure((size_t)c->N))) return rc;
-    if ((rc = align_fit_rows(c, lm, tmpl, K, cw, ch))) return rc;
-    return paste_run(c, true, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host);
+    return paste_fit_call(c, lm, tmpl, K, cw, ch, spec, nullptr, false, in_dev, paste, frames, n_frames, matrices_host, flags_host, nullptr);
 }
 
 int sdm_align_paste_tensor_at(sdm_ctx* c, const float* matrices_host, const int* image_index, int n_rows, int cw, int ch,
                               const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
                               int n_frames, int* flags_host)
 {
-    if (!c) return fail(SDM_ERR_INVALID, "null context");
-    if (!matrices_host) return fail(SDM_ERR_INVALID, "no matrices");
-    if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
-    if (cw < 1 || cw > 1024 || ch < 1 || ch > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
-    int rc;
-    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames))) return rc;
-    std::vector<int> frame_of_row;
-    if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;
-    std::vector<AlignFace> faces((size_t)n_rows);
-    for (int r = 0; r < n_rows; ++r) {
-        const sdm_frame& fr = frames[frame_of_row[r]];
-        AlignFace& f = faces[r];
-        memcpy(f.m, matrices_host + (size_t)6 * r, 6 * sizeof(float));
-        f.flags = 0; f.w = fr.width; f.h = fr.height; f.stride = fr.stride_bytes; f.off = 0;
-    }
-    sdm_ctx::Align& a = c->align;
-    HIP_TRY(hipSetDevice(c->device));
-    if ((rc = a.faces.ensure((size_t)n_rows))) return rc;
-    HIP_TRY(hipMemcpyAsync(a.faces.p, faces.data(), faces.size() * sizeof(AlignFace), hipMemcpyHostToDevice, c->stream));
-    return paste_run(c, false, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, nullptr, flags_host);
+    return paste_at_call(c, matrices_host, image_index, n_rows, cw, ch, spec, nullptr, false, in_dev, paste, frames, n_frames, flags_host, nullptr);
+}
+
+int sdm_align_paste_tensor_filtered(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, int ch, const sdm_align_tensor* spec,
+                                    const sdm_align_filter* filter, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
+                                    int n_frames, float* matrices_host, int* flags_host, int* samples_host)
+{
+    return paste_fit_call(c, lm, tmpl, K, cw, ch, spec, filter, true, in_dev, paste, frames, n_frames, matrices_host, flags_host, samples_host);
+}
+
+int sdm_align_paste_tensor_at_filtered(sdm_ctx* c, const float* matrices_host, const int* image_index, int n_rows, int cw, int ch,
+                                       const sdm_align_tensor* spec, const sdm_align_filter* filter, const void* in_dev,
+                                       const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, int* flags_host, int* samples_host)
+{
+    return paste_at_call(c, matrices_host, image_index, n_rows, cw, ch, spec, filter, true, in_dev, paste, frames, n_frames, flags_host,
+                         samples_host);
 }
 
 }  // extern "C"

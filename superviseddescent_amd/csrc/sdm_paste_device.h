@@ -1,7 +1,8 @@
 // sdm_paste_device.h -- what the two pastes of tensors back into frames share (include/sdm.h, "Pasting crops back" and "Pasting warped
 // faces back"): the frame and crop records, the inverse map, a frame pixel's position in the crop (paste_position), the decoded taps,
 // the integer bilinear colour and opacity, the blend, the pixel's load / apply / store, and paste_owned -- the one text of the ownership
-// rule, which a paste calls with its shape (PasteRigid of csrc/sdm_align_paste_device.h, PasteMesh of csrc/sdm_warp_paste_device.h).
+// rule, which a paste calls with its shape (PasteRigid of csrc/sdm_align_paste_device.h, PasteRigidArea of
+// csrc/sdm_align_paste_area_device.h, PasteMesh of csrc/sdm_warp_paste_device.h).
 // Plain C++ behind ALIGN_HD: the device code of both kernels and, compiled for the host, of the two programs of tests/cpp that run it
 // under the host sanitizers on frames, tensors and opacity maps of exactly the bytes they own.
 //
@@ -176,7 +177,8 @@ ALIGN_HD void paste_store(const PastePixel& s)
 // The ownership rule.  Frame pixel (X, Y) lies in the footprint of entry k of its frame's row list at position q: nothing if an earlier
 // entry's footprint holds it too -- else this is the pixel's one reader and writer: the old bytes once, entry k and every later entry
 // that holds the pixel applied in order, the colour bytes stored once if any opacity was not 0.  list: the row lists.  Shape: the paste's
-// rows, with paste_holds(shape, n, crop, X, Y, q) -- row n's footprint holds the pixel, at q -- and paste_taps(shape, crop, n, q, bgr, a)
+// rows, with paste_holds(shape, n, crop, X, Y, q) -- row n's footprint holds the pixel, at q -- and paste_taps(shape, crop, n, X, Y, q,
+// bgr, a): row n's colour and opacity for the pixel (a == 0: the row leaves it alone)
 template <class Shape>
 ALIGN_HD void paste_owned(const PasteFrameDev& f, const Shape& shape, const int* list, int k, const PasteCropDev& c, int X, int Y, AlignPos q)
 {
@@ -190,7 +192,7 @@ ALIGN_HD void paste_owned(const PasteFrameDev& f, const Shape& shape, const int*
         const int n = list[j];
         if (j > k && !paste_holds(shape, n, c, X, Y, q)) continue;
         uint32_t bgr[3], a;
-        paste_taps(shape, c, n, q, bgr, a);
+        paste_taps(shape, c, n, X, Y, q, bgr, a);
         paste_apply(c, bgr, a, s);
     }
     paste_store(s);

@@ -152,7 +152,7 @@ ALIGN_HD bool paste_holds(const PasteMesh& p, int n, const PasteCropDev& c, int 
     return warp_paste_footprint(p.rows[n], p.tris + (long long)n * p.T, p.T, c.cw, c.ch, X, Y, q);
 }
 
-ALIGN_HD void paste_taps(const PasteMesh& p, const PasteCropDev& c, int n, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
+ALIGN_HD void paste_taps(const PasteMesh& p, const PasteCropDev& c, int n, int, int, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
 {
     paste_sample_taps<true>(c, n, q, p.labels, bgr, a);
 }

@@ -864,15 +864,29 @@ class Context:
             raise ValueError("one image index per row expected")
         return idx
 
+    @staticmethod
+    def _paste_filter(filter, max_samples, min_scale):
+        """None, or the ``SdmAlignFilter`` of a paste call's ``filter`` ("area" | "bilinear" with ``max_samples`` / ``min_scale``, or
+        an ``SdmAlignFilter`` as it is)"""
+        if filter is None or isinstance(filter, _lib.SdmAlignFilter):
+            return filter
+        if isinstance(filter, str):
+            return _lib.align_filter(filter, max_samples, min_scale)
+        raise ValueError('filter must be None, "area", "bilinear" or an SdmAlignFilter')
+
     def align_paste_tensor(self, landmark_index, template: np.ndarray, y, frames, formats=None, layout="nchw", mask=None, spec=None,
-                           **options):
+                           filter=None, max_samples=16, min_scale=1.0, **options):
         """The inverse of ``align_crops_tensor`` for the N current rows (include/sdm.h, sdm_align_paste_tensor): ``y`` -- a network's
         output on the crops, a device tensor whose dtype, channels and crop size are read from it -- is warped back through every row's
         fitted similarity and blended into ``frames`` IN PLACE.  ``frames`` / ``formats``: as for ``set_frames_device``, without NV12;
         row n goes to the frame ``set_sample_image_index`` names.  ``mask``: the crop-space opacity, None (255 inside the crop) or an
         H x W (all rows) or N x H x W uint8 device tensor or numpy array.  ``options``: order, scale, bias, mean, std, gray_shift of
         ``_lib.paste_tensor_spec`` (an element is decoded as e * scale + bias: ``mean`` / ``std`` as in the crop call undo it).  Returns
-        (matrices N x 2 x 3 float32 crop -> frame, flags N int32: SDM_ALIGN_* bits)."""
+        (matrices N x 2 x 3 float32 crop -> frame, flags N int32: SDM_ALIGN_* bits).  ``filter``: None (plain bilinear), or "area" /
+        "bilinear" with ``max_samples`` and ``min_scale`` (``_lib.align_filter``) or an ``SdmAlignFilter`` for
+        sdm_align_paste_tensor_filtered -- a row whose crop outsizes its face averages S x S sub-samples per frame pixel -- which
+        returns (matrices, flags, samples N int32: S of every row)."""
+        filter = self._paste_filter(filter, max_samples, min_scale)
         idx = np.ascontiguousarray(landmark_index, np.int32).reshape(-1)
         t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
         if t.shape[0] != idx.size:
@@ -881,25 +895,40 @@ class Context:
         self._paste_rows(n)
         mats = np.empty((n, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
-        check(self._lib.sdm_align_paste_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, width, height, ctypes.byref(spec),
-                                               ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr), mats.ctypes.data,
-                                               flags.ctypes.data))
-        return mats, flags
+        if filter is None:
+            check(self._lib.sdm_align_paste_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, width, height, ctypes.byref(spec),
+                                                   ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr), mats.ctypes.data,
+                                                   flags.ctypes.data))
+            return mats, flags
+        samples = np.empty(n, np.int32)
+        check(self._lib.sdm_align_paste_tensor_filtered(self._h, idx.ctypes.data, t.ctypes.data, idx.size, width, height, ctypes.byref(spec),
+                                                        ctypes.byref(filter), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr,
+                                                        len(arr), mats.ctypes.data, flags.ctypes.data, samples.ctypes.data))
+        return mats, flags, samples
 
-    def align_paste_tensor_at(self, matrices, y, frames, formats=None, image_index=None, layout="nchw", mask=None, spec=None, **options):
+    def align_paste_tensor_at(self, matrices, y, frames, formats=None, image_index=None, layout="nchw", mask=None, spec=None, filter=None,
+                              max_samples=16, min_scale=1.0, **options):
         """``align_paste_tensor`` with explicit crop -> frame matrices (sdm_align_paste_tensor_at): ``matrices`` N x 2 x 3 as an earlier
         crop call returned them -- the tracker may have stepped on since; no landmark state, geometry or context image is needed.
-        ``image_index``: the frame of every row (None: row i -> frame i).  Returns flags N int32: SDM_ALIGN_* bits."""
+        ``image_index``: the frame of every row (None: row i -> frame i).  Returns flags N int32: SDM_ALIGN_* bits; with a ``filter``
+        (as for ``align_paste_tensor``: sdm_align_paste_tensor_at_filtered) it returns (flags, samples N int32: S of every row)."""
+        filter = self._paste_filter(filter, max_samples, min_scale)
         spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
         m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 6)
         if m.shape[0] != n:
             raise ValueError(f"one matrix per row of the tensor expected: {m.shape[0]} for {n}")
         idx = self._paste_image_index(image_index, n)
         flags = np.empty(n, np.int32)
-        check(self._lib.sdm_align_paste_tensor_at(self._h, m.ctypes.data, None if idx is None else idx.ctypes.data, n, width, height,
-                                                  ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr),
-                                                  flags.ctypes.data))
-        return flags
+        if filter is None:
+            check(self._lib.sdm_align_paste_tensor_at(self._h, m.ctypes.data, None if idx is None else idx.ctypes.data, n, width, height,
+                                                      ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr),
+                                                      flags.ctypes.data))
+            return flags
+        samples = np.empty(n, np.int32)
+        check(self._lib.sdm_align_paste_tensor_at_filtered(self._h, m.ctypes.data, None if idx is None else idx.ctypes.data, n, width, height,
+                                                           ctypes.byref(spec), ctypes.byref(filter), ctypes.c_void_p(y.data_ptr()),
+                                                           ctypes.byref(paste), arr, len(arr), flags.ctypes.data, samples.ctypes.data))
+        return flags, samples
 
     # -- warped face tensors pasted back into frames (csrc/sdm_warp_paste.hip) -------------------------
     def _warp_paste_size(self, width, height):
@@ -1727,7 +1756,7 @@ class detection_model:
 
     def paste_crops_tensor(self, y, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None, margin: float = 0.2,
                            frames=None, formats=None, layout="nchw", order="rgb", scale=None, bias=None, mean=None, std=None, gray_shift=14,
-                           mask=None, matrices=None, image_index=None):
+                           mask=None, matrices=None, image_index=None, filter=None, max_samples=16, min_scale=1.0):
         """The way back of :meth:`aligned_crops_tensor`: ``y = net(x)`` on the crops -- a device tensor, N x C x H x W or N x H x W x C by
         ``layout``; dtype, channels and crop size are read from it -- is warped back and blended into ``frames`` in place, in one launch
         (include/sdm.h, "Pasting crops back").  ``landmark_ids``, ``template``, ``margin``, ``order``, ``gray_shift``: as in the crop call,
@@ -1736,14 +1765,20 @@ class detection_model:
         ``scale = std``, ``bias = mean``, the decoded value is ``e * scale + bias``.  ``mask``: the crop-space opacity -- None, or an H x W
         or N x H x W uint8 device tensor or numpy array, e.g. :func:`feather_mask`.  ``matrices`` (N x 2 x 3, as a crop call returned
         them) with ``image_index`` (None: row i -> frame i) pastes rows that are no longer current; otherwise the current rows are
-        fitted again.  Returns (matrices N x 2 x 3 crop -> frame, flags N: SDM_ALIGN_*).  No pointer to the frames stays behind."""
+        fitted again.  Returns (matrices N x 2 x 3 crop -> frame, flags N: SDM_ALIGN_*).  No pointer to the frames stays behind.
+        ``filter``: None (plain bilinear) | "area" | "bilinear" | an ``SdmAlignFilter``, with ``max_samples`` and ``min_scale`` as in
+        :func:`align_filter`: where the crop is larger than the face in the frame -- a 256- or 512-pixel network on a face 100 pixels
+        wide -- every frame pixel averages S x S sub-samples of the crop (include/sdm.h, "Pasting crops back, filtered"), and the
+        call returns (matrices, flags, S), as :meth:`aligned_crops_tensor` appends S."""
         c = self.optimised_model.ctx
         if frames is None:
             raise ValueError("give the frames to paste into")
-        options = dict(order=order, scale=scale, bias=bias, mean=mean, std=std, gray_shift=gray_shift)
+        options = dict(order=order, scale=scale, bias=bias, mean=mean, std=std, gray_shift=gray_shift, filter=filter, max_samples=max_samples,
+                       min_scale=min_scale)
         if matrices is not None:
             m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 2, 3)
-            return m, c.align_paste_tensor_at(m, y, frames, formats, image_index, layout, mask, **options)
+            got = c.align_paste_tensor_at(m, y, frames, formats, image_index, layout, mask, **options)
+            return (m, got) if filter is None else (m,) + tuple(got)
         if image_index is not None:
             raise ValueError("image_index goes with matrices; the current rows map through the context's sample -> image index")
         if not getattr(c, "N", 0):

@@ -265,6 +265,7 @@ struct PasteMask {
 struct paste_result {
     cv::Mat matrices;              // rows x 6 CV_32FC1: the crop -> frame map of every row (NaN for a degenerate row of the fit)
     std::vector<int> flags;        // SDM_ALIGN_DEGENERATE / SDM_ALIGN_PARTIAL bits
+    std::vector<int> samples;      // the overloads taking an AlignFilter: S of every row; empty otherwise
 };
 
 namespace detail {
@@ -284,9 +285,11 @@ inline std::vector<sdm_frame> paste_frames(const std::vector<DeviceFrame>& frame
     return f;
 }
 
-// the n current rows of the handle `c`: the fit of aligned_crops_tensor, then the tensor at `in_dev` pasted into `frames` in place
+// the n current rows of the handle `c`: the fit of aligned_crops_tensor, then the tensor at `in_dev` pasted into `frames` in place;
+// `filter`: nullptr, or the sampling of sdm_align_paste_tensor_filtered
 inline paste_result paste_current_rows(sdm_ctx* c, int n, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
-                                       const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames, const PasteMask& mask)
+                                       const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames, const PasteMask& mask,
+                                       const AlignFilter* filter = nullptr)
 {
     using superviseddescent::hip::check;
     if (tmpl.rows != (int)landmark_index.size() || tmpl.cols != 2) throw std::runtime_error("paste_crops_tensor: one template point (x, y) per landmark");
@@ -297,6 +300,15 @@ inline paste_result paste_current_rows(sdm_ctx* c, int n, const std::vector<int>
     paste_result res;
     res.matrices = cv::Mat(n, 6, CV_32FC1);
     res.flags.resize((size_t)n);
+    if (filter) {
+        const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
+        res.samples.resize((size_t)n);
+        check(sdm_align_paste_tensor_filtered(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s, &fl,
+                                              in_dev, &p, f.empty() ? nullptr : f.data(), (int)f.size(), res.matrices.ptr<float>(0),
+                                              res.flags.data(), res.samples.data()),
+              "sdm_align_paste_tensor_filtered");
+        return res;
+    }
     check(sdm_align_paste_tensor(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s, in_dev, &p,
                                  f.empty() ? nullptr : f.data(), (int)f.size(), res.matrices.ptr<float>(0), res.flags.data()),
           "sdm_align_paste_tensor");
@@ -318,11 +330,22 @@ inline paste_result paste_crops_tensor(tracker& tr, const std::vector<int>& land
     return detail::paste_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask);
 }
 
+/** The same with the sampling of `filter` (sdm_align_paste_tensor_filtered): where the crop is larger than the face in the frame, every
+ *  frame pixel averages S x S sub-samples of the crop; the result's `samples` holds S of every stream. */
+inline paste_result paste_crops_tensor(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                       const TensorSpec& spec, const AlignFilter& filter, const void* in_dev,
+                                       const std::vector<DeviceFrame>& frames, const PasteMask& mask = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("paste_crops_tensor: step the tracker first");
+    return detail::paste_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask, &filter);
+}
+
 /** The same for landmark rows on device frames (as the detection_model overload of aligned_crops_tensor: a handle of its own, the frames
  *  as its image set, the rows uploaded): row i is pasted into frames[image_index[i]] (default: frames[i]). */
 inline paste_result paste_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
                                        const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
-                                       int height, const TensorSpec& spec, const void* in_dev, const PasteMask& mask = {})
+                                       int height, const TensorSpec& spec, const void* in_dev, const PasteMask& mask = {},
+                                       const AlignFilter* filter = nullptr)
 {
     using superviseddescent::hip::check;
     superviseddescent::hip::Handle h(superviseddescent::hip::device());
@@ -334,14 +357,24 @@ inline paste_result paste_crops_tensor(detection_model& model, const std::vector
     if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
     else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
     check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
-    return detail::paste_current_rows(c, x.rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask);
+    return detail::paste_current_rows(c, x.rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask, filter);
+}
+
+/** The same with the sampling of `filter` (the result's `samples`: S of every row). */
+inline paste_result paste_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                       const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
+                                       int height, const TensorSpec& spec, const AlignFilter& filter, const void* in_dev,
+                                       const PasteMask& mask = {})
+{
+    return paste_crops_tensor(model, frames, rows, image_index, landmark_index, tmpl, width, height, spec, in_dev, mask, &filter);
 }
 
 /** The explicit form (sdm_align_paste_tensor_at): `matrices` rows x 6 CV_32FC1 as an earlier crop call returned them -- the rows need not
  *  be current any more; no model, no landmark state.  Row i goes to frames[image_index[i]] (default: frames[i]).  The result's matrices
  *  are the ones given. */
 inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>& image_index, int width, int height, const TensorSpec& spec,
-                                       const void* in_dev, const std::vector<DeviceFrame>& frames, const PasteMask& mask = {})
+                                       const void* in_dev, const std::vector<DeviceFrame>& frames, const PasteMask& mask = {},
+                                       const AlignFilter* filter = nullptr)
 {
     using superviseddescent::hip::check;
     if (matrices.type() != CV_32FC1 || matrices.cols != 6 || matrices.rows < 1) throw std::runtime_error("paste_crops_tensor: matrices must be rows x 6 CV_32FC1");
@@ -353,10 +386,27 @@ inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>&
     const std::vector<sdm_frame> f = detail::paste_frames(frames);
     const sdm_align_tensor s = detail::paste_spec(spec);
     const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
+    if (filter) {
+        const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
+        res.samples.resize((size_t)matrices.rows);
+        check(sdm_align_paste_tensor_at_filtered(h.get(), res.matrices.ptr<float>(0), image_index.empty() ? nullptr : image_index.data(),
+                                                 matrices.rows, width, height, &s, &fl, in_dev, &p, f.empty() ? nullptr : f.data(), (int)f.size(),
+                                                 res.flags.data(), res.samples.data()),
+              "sdm_align_paste_tensor_at_filtered");
+        return res;
+    }
     check(sdm_align_paste_tensor_at(h.get(), res.matrices.ptr<float>(0), image_index.empty() ? nullptr : image_index.data(), matrices.rows, width,
                                     height, &s, in_dev, &p, f.empty() ? nullptr : f.data(), (int)f.size(), res.flags.data()),
           "sdm_align_paste_tensor_at");
     return res;
+}
+
+/** The explicit form with the sampling of `filter` (sdm_align_paste_tensor_at_filtered; the result's `samples`: S of every row). */
+inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>& image_index, int width, int height, const TensorSpec& spec,
+                                       const AlignFilter& filter, const void* in_dev, const std::vector<DeviceFrame>& frames,
+                                       const PasteMask& mask = {})
+{
+    return paste_crops_tensor(matrices, image_index, width, height, spec, in_dev, frames, mask, &filter);
 }
 
 }  // namespace rcr
