@@ -781,7 +781,8 @@ int sdm_warp_crops_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, void* out_
  *           previous one left, whatever the launch order: a pixel is loaded once, every row whose footprint holds it is applied in
  *           registers in row order, and it is stored once.
  *   never stored to, not even with their old value: pitch padding, pixels outside every footprint, pixels whose every a is 0, alpha bytes.
- * Out of scope, and not half-built: NV12 destinations (refused).  These two calls are plain bilinear, as sdm_align_crops is; the
+ * NV12 destinations are refused here and taken by sdm_align_paste_tensor_nv12 / _at_nv12 ("Pasting crops back into NV12 frames"
+ * below).  These two calls are plain bilinear, as sdm_align_crops is; the
  * antialiasing for a face that is smaller in the frame than in the crop is the filtered form, "Pasting crops back, filtered" below.
  * (The inverse of sdm_warp_crops_tensor is "Pasting warped faces back".)
  * Refused with SDM_ERR_INVALID, no state changed, nothing launched: what sdm_align_crops_tensor refuses of landmark_index, template_xy,
@@ -812,7 +813,8 @@ int sdm_align_paste_tensor_at(sdm_ctx* ctx, const float* matrices_host /* in, n_
  * the integer arithmetic of the paste; the average is taken BEFORE the blend, of colour and opacity alike.  One launch for all rows
  * behind the prepare stage.  Every rule of "Pasting crops back" that is not restated here holds word for word: M, W, the flags, the
  * decode, the clamped colour taps, opacity 0 outside the crop, the / 255 blend, per-byte stores, the alpha byte never touched, the rows
- * of one frame applied in increasing row number.  NV12 destinations stay refused; the piecewise-affine paste (sdm_warp_paste_tensor*)
+ * of one frame applied in increasing row number.  NV12 destinations are refused here too (they go through sdm_align_paste_tensor_nv12
+ * with this filter, "Pasting crops back into NV12 frames" below); the piecewise-affine paste (sdm_warp_paste_tensor*)
  * stays plain bilinear.  Every float operation is rounded on its own, nothing is contracted.
  *   S of row n   s2 = W00 W00 + W10 W10 in float32 on the float32 W, each operation rounded: the mirror image of
  *           sdm_align_crops_tensor_filtered, which takes it from M.  S = 1 for mode BILINEAR, for s2 < min_scale * min_scale (float32),
@@ -850,6 +852,54 @@ int sdm_align_paste_tensor_at_filtered(sdm_ctx* ctx, const float* matrices_host 
                                        const sdm_align_tensor* spec, const sdm_align_filter* filter, const void* in_dev,
                                        const sdm_align_paste* paste, const sdm_frame* dst_frames, int n_frames, int* flags_host,
                                        int* samples_host);
+
+/* Pasting crops back into NV12 frames: sdm_align_paste_tensor[_filtered] and sdm_align_paste_tensor_at[_filtered] for a list of
+ * destinations that may hold NV12 frames -- what a hardware decoder delivers and a hardware encoder takes, and what
+ * sdm_align_crops_tensor reads in place.  Luma and 4:2:0 chroma are blended where they lie; no plane is converted, nothing outside the
+ * faces is re-quantised.  One launch for all rows behind the prepare stage.  Every rule of "Pasting crops back" and "Pasting crops back,
+ * filtered" that is not restated here holds word for word.  filter NULL: plain bilinear, S = 1 for every row.
+ *   destination   sdm_frame with format SDM_FRAME_NV12: data is the Y plane, height rows of stride_bytes, written in place.  The UV plane
+ *           is dst_chroma[i]; with a NULL entry, or dst_chroma == NULL, it is (uint8_t*)data + (size_t)height * stride_bytes, as in
+ *           sdm_align_set_source_frames.  It has (height + 1) / 2 rows of stride_bytes and (width + 1) / 2 (U, V) byte pairs per row.
+ *           Any pointer alignment; every offset is 64-bit.  The other five formats are accepted in the same list -- a BGR camera and a
+ *           decoder surface in one step -- and get exactly the bytes of the calls above, through their per-pixel code; their
+ *           dst_chroma entry is ignored.
+ *   per luma pixel   (q_B, q_G, q_R) and a are exactly those of the unfiltered paste, or of the filtered paste averaged over S x S
+ *           sub-samples: the footprint, the 2^20 rule, S per row and the working footprint are the same.
+ *   luma    3-channel tensor: Yq = (269484 q_R + 528482 q_G + 102760 q_B + (16 << 20) + (1 << 19)) >> 20.  1-channel tensor: Yq = q, no
+ *           conversion (the mirror of the crop call, which hands out Y as it is for channels == 1), and the UV plane is neither read nor
+ *           written.  Y' = (a Yq + (255 - a) Y + 127) / 255; a == 0: the byte is not written.
+ *   chroma  3-channel tensor.  Sample (cx, cy) belongs to the pixels X in {2 cx, 2 cx + 1}, Y in {2 cy, 2 cy + 1} that lie inside the
+ *           frame; cnt in {4, 2, 1} counts them.  For row n: A = sum of a_i over those pixels, a pixel outside the row's footprint having
+ *           a_i = 0.  A == 0: the row leaves the sample alone.  Otherwise per B, G and R: m = (sum of a_i q_i + A / 2) / A, an unsigned
+ *           division -- an opacity-weighted mean, so that a half-covered block takes the colour of its covered pixels.  In int32 with an
+ *           arithmetic shift, clamped to [0, 255]:
+ *               Uq = (460324 m_B - 305135 m_G - 155188 m_R + (128 << 20) + (1 << 19)) >> 20
+ *               Vq = (460324 m_R - 385875 m_G -  74448 m_B + (128 << 20) + (1 << 19)) >> 20
+ *           a_c = (A + cnt / 2) / cnt.  a_c == 0: neither byte is written.  Otherwise U and V are blended with a_c by the / 255 formula.
+ *           The Q20 constants are BT.601 limited range (0.257, 0.504, 0.098; 0.439, 0.291, 0.148; 0.368, 0.071), the counterpart of the
+ *           crop call's decode constants; the numbers above are the definition.
+ *   several rows on one frame   the result is that of pasting the rows one after another in increasing row number, each reading the luma
+ *           and the chroma the previous one left.  On an NV12 frame the unit of ownership is the 2 x 2 block: it is loaded once (up to
+ *           four Y bytes, one UV pair) by the lowest-numbered row of the frame whose footprint holds one of its pixels, every row from
+ *           that one on is applied in registers in row order, and every changed byte is stored once.
+ *   never stored to, not even with their old value: pitch padding of either plane; luma pixels whose every a is 0, even in a block whose
+ *           chroma is written; chroma samples whose every a_c is 0; the UV plane for a 1-channel tensor.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched: everything the filtered calls refuse, except that an NV12 frame and a
+ * NULL filter are accepted; an NV12 frame with stride_bytes < 2 * ((width + 1) / 2).  The fit form's size rule holds against the context
+ * image (an NV12 frame set through sdm_set_frames_device is its own luma).  samples_host may be NULL.  The piecewise-affine paste
+ * (sdm_warp_paste_tensor*) has no NV12 form yet. */
+int sdm_align_paste_tensor_nv12(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int crop_width, int crop_height,
+                                const sdm_align_tensor* spec, const sdm_align_filter* filter /* NULL: plain bilinear */, const void* in_dev,
+                                const sdm_align_paste* paste, const sdm_frame* dst_frames,
+                                void* const* dst_chroma /* n_frames UV planes; NULL, or a NULL entry: behind the Y plane */, int n_frames,
+                                float* matrices_host /* out, N x 6, may be NULL */, int* flags_host /* out, may be NULL */,
+                                int* samples_host /* out, may be NULL */);
+int sdm_align_paste_tensor_at_nv12(sdm_ctx* ctx, const float* matrices_host /* in, n_rows x 6 */,
+                                   const int* image_index /* NULL: row i -> frame i */, int n_rows, int crop_width, int crop_height,
+                                   const sdm_align_tensor* spec, const sdm_align_filter* filter /* NULL: plain bilinear */,
+                                   const void* in_dev, const sdm_align_paste* paste, const sdm_frame* dst_frames, void* const* dst_chroma,
+                                   int n_frames, int* flags_host, int* samples_host);
 
 /* Pasting warped faces back: the inverse path of sdm_warp_crops_tensor.  A network's output in template space -- a transferred
  * expression, a swapped, re-lit or de-aged texture -- is warped back under the face's own shape, triangle by triangle, and blended into
@@ -889,7 +939,8 @@ int sdm_align_paste_tensor_at_filtered(sdm_ctx* ctx, const float* matrices_host 
  *   write, several rows on one frame, never stored to   those of "Pasting crops back", word for word: the blend divides by 255, a pixel
  *           is loaded once, every row of the frame whose footprint holds it is applied in increasing row number in registers, it is
  *           stored once and only if some opacity was not 0, stores are per byte.
- * Out of scope, and not half-built: NV12 destinations (refused); any antialiasing when the face in the frame is smaller than its crop;
+ * Out of scope, and not half-built: NV12 destinations (refused -- the rigid paste has them, "Pasting crops back into NV12 frames";
+ * the block ownership written there is what this paste would adopt: the remaining gap); any antialiasing when the face in the frame is smaller than its crop;
  * a colour renormalised at the hull's border.
  * Refused with SDM_ERR_INVALID, no state changed, nothing launched: no mesh (none set, or sdm_set_model_geometry has changed L since);
  * fit form: no current rows, and sdm_warp_crops_tensor's rules on the rows' source sizes; everything sdm_align_paste_tensor refuses of

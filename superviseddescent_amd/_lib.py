@@ -42,6 +42,7 @@ EXPORTED = [
     "sdm_align_paste_tensor", "sdm_align_paste_tensor_at",
     "sdm_warp_paste_tensor", "sdm_warp_paste_tensor_at",
     "sdm_align_paste_tensor_filtered", "sdm_align_paste_tensor_at_filtered",
+    "sdm_align_paste_tensor_nv12", "sdm_align_paste_tensor_at_nv12",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -457,6 +458,12 @@ def lib() -> ctypes.CDLL:
             "sdm_align_paste_tensor_at_filtered": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor),
                                                    ctypes.POINTER(SdmAlignFilter), c_void_p, ctypes.POINTER(SdmAlignPaste),
                                                    ctypes.POINTER(SdmFrame), c_int, c_void_p, c_void_p],
+            "sdm_align_paste_tensor_nv12": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor),
+                                            ctypes.POINTER(SdmAlignFilter), c_void_p, ctypes.POINTER(SdmAlignPaste),
+                                            ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+            "sdm_align_paste_tensor_at_nv12": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor),
+                                               ctypes.POINTER(SdmAlignFilter), c_void_p, ctypes.POINTER(SdmAlignPaste),
+                                               ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

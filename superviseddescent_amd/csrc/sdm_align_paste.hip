@@ -13,6 +13,15 @@
 //                          PasteRigidArea.  S is uniform for a workgroup (one row) and, in the owner loop, per list entry: every
 //                          sub-sample loop has a wave-uniform trip count.  Rows with S = 1 take paste_kernel's per-pixel code.
 //
+//   paste_nv12_kernel<AREA>   the calls that take NV12 destinations (include/sdm.h, "Pasting crops back into NV12 frames"), plain bilinear
+//                          (AREA false: behind paste_prepare_kernel) and filtered (AREA true: behind paste_area_prepare_kernel), one text.
+//                          The frame's format is uniform for a workgroup.  On an NV12 frame the tile walk runs over the 2 x 2 blocks
+//                          of the row's box widened to even coordinates -- a wave covers 64 blocks of one block row -- and a block is
+//                          pasted by the lowest-numbered row of the frame whose footprint holds one of its pixels (paste_owned_block):
+//                          every byte of both planes has at most one reader and writer in the launch.  The UV planes come as an array
+//                          of their own beside the frame table, which the three kernels above read as they did.  On any other frame
+//                          it is the pixel walk of paste_kernel / paste_area_kernel through paste_pixel / paste_area_pixel.
+//
 // The per-pixel arithmetic is csrc/sdm_align_paste_device.h and csrc/sdm_align_paste_area_device.h on top of csrc/sdm_paste_device.h.
 #include "sdm_paste.h"
 
@@ -96,6 +105,41 @@ __global__ __launch_bounds__(PASTE_BLOCK) void paste_area_kernel(const PasteFram
     }
 }
 
+template <bool AREA>
+__global__ __launch_bounds__(PASTE_BLOCK) void paste_nv12_kernel(const PasteFrameDev* __restrict__ frames, uint8_t* const* __restrict__ chroma,
+                                                                 const PasteRow* __restrict__ rows, const PasteAreaRow* __restrict__ area_rows,
+                                                                 const int* __restrict__ list, const int* __restrict__ entry_of_row, PasteCropDev c)
+{
+    const int n = blockIdx.x;
+    const int k = entry_of_row[n];
+    const PasteRow r = rows[n];
+    if (r.x1 - r.x0 <= 0 || r.y1 - r.y0 <= 0) return;
+    const PasteFrameDev f = frames[r.frame];
+    const int lx = threadIdx.x & (PASTE_TILE_W - 1), ly = threadIdx.x / PASTE_TILE_W;
+    if (f.format != SDM_FRAME_NV12) {
+        const int tx = paste_tiles_x(r.x1 - r.x0), ty = paste_tiles_y(r.y1 - r.y0);
+        for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
+            const int X = r.x0 + paste_tile_x(t, tx) + lx, Y = r.y0 + paste_tile_y(t, tx) + ly;
+            if (X < r.x1 && Y < r.y1) {
+                if (AREA) paste_area_pixel(f, rows, area_rows, list, k, c, X, Y);
+                else paste_pixel(f, rows, list, k, c, X, Y);
+            }
+        }
+        return;
+    }
+    // the blocks of the box widened to even coordinates: [bx0, bx1) x [by0, by1)
+    uint8_t* const uv = chroma[r.frame];
+    const int bx0 = r.x0 >> 1, by0 = r.y0 >> 1, bx1 = (r.x1 + 1) >> 1, by1 = (r.y1 + 1) >> 1;
+    const int tx = paste_tiles_x(bx1 - bx0), ty = paste_tiles_y(by1 - by0);
+    for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
+        const int BX = bx0 + paste_tile_x(t, tx) + lx, BY = by0 + paste_tile_y(t, tx) + ly;
+        if (BX < bx1 && BY < by1) {
+            if (AREA) paste_owned_block(f, uv, PasteRigidArea{rows, area_rows}, list, k, c, BX, BY);
+            else paste_owned_block(f, uv, PasteRigid{rows}, list, k, c, BX, BY);
+        }
+    }
+}
+
 }  // namespace
 
 void sdm_launch_paste_prepare(AlignFace* faces, const int* frame_of_row, const PasteFrameDev* frames, int N, int cw, int ch, bool fitted,
@@ -124,4 +168,14 @@ void sdm_launch_paste_area(const PasteFrameDev* frames, const PasteRow* rows, co
 {
     hipLaunchKernelGGL(paste_area_kernel, dim3((unsigned)N, (unsigned)paste_groups(crop)), dim3(PASTE_BLOCK), 0, s, frames, rows, area_rows, list,
                        entry_of_row, crop);
+}
+
+void sdm_launch_paste_nv12(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows,
+                           const int* list, const int* entry_of_row, int N, const PasteCropDev& crop, hipStream_t s)
+{
+    const dim3 grid((unsigned)N, (unsigned)paste_groups(crop));
+    if (area_rows)
+        hipLaunchKernelGGL(paste_nv12_kernel<true>, grid, dim3(PASTE_BLOCK), 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
+    else
+        hipLaunchKernelGGL(paste_nv12_kernel<false>, grid, dim3(PASTE_BLOCK), 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
 }

@@ -1,7 +1,8 @@
 // sdm_capi_paste.hip -- C-ABI of the paste-back of crop tensors into frames (include/sdm.h, "Pasting crops back" and "Pasting warped
 // faces back"): the entry points check every argument before anything is launched or changed, build the frame table and the rows-of-frame lists on the host from the
 // image index they already hold, and enqueue -- fit form -- sdm_align_crops' fit, then the prepare kernel and the one paste launch
-// (csrc/sdm_align_paste.hip), the filtered forms that file's area-capable pair; the piecewise-affine forms enqueue warp_fit_kernel, their prepare kernel and their paste launch
+// (csrc/sdm_align_paste.hip), the filtered forms that file's area-capable pair, the NV12 forms either prepare kernel and paste_nv12_kernel
+// with the frames' UV planes as a device array of their own; the piecewise-affine forms enqueue warp_fit_kernel, their prepare kernel and their paste launch
 // (csrc/sdm_warp_paste.hip) on the mesh of sdm_warp_set_mesh.  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
 // landmark state, the images, the crop source and the tracker's slots are only read; the frames' colour bytes are written in place.
 #include "sdm_capi_internal.h"
@@ -12,7 +13,7 @@
 namespace {
 
 // what both forms refuse of the tensor, the opacity maps and the destination frames
-int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames)
+int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, bool nv12 = false)
 {
     if (!in_dev) return fail(SDM_ERR_INVALID, "no tensor");
     if ((uintptr_t)in_dev % 16 != 0) return fail(SDM_ERR_INVALID, "the tensor must be 16-byte aligned");
@@ -21,7 +22,10 @@ int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm
     if (!frames || n_frames < 1) return fail(SDM_ERR_INVALID, "bad frame list");
     int rc;
     for (int i = 0; i < n_frames; ++i)
-        if ((rc = check_frame(i, frames[i], false))) return rc;
+        if ((rc = check_frame(i, frames[i], nv12))) return rc;
+    for (int i = 0; i < n_frames; ++i)                               // (the UV plane's row: (width + 1) / 2 byte pairs)
+        if (frames[i].format == SDM_FRAME_NV12 && (long long)frames[i].stride_bytes < 2LL * ((frames[i].width + 1) / 2))
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < 2 * ((width + 1) / 2) of an NV12 frame");
     return SDM_OK;
 }
 
@@ -52,20 +56,24 @@ int paste_frames_of_index(const int* image_index, int n_rows, int n_frames, std:
 }
 
 // the device tables of a call in align.paste_tab: the frame table, the row -> frame index, the rows of every frame in ascending order,
-// and every row's place among them (enqueued; nothing waits: `blob`, the host side of the copy, lives until the call's synchronise)
+// and every row's place among them (enqueued; nothing waits: `blob`, the host side of the copy, lives until the call's synchronise);
+// for the NV12 calls the frames' UV planes behind them, 8-byte aligned -- an array of its own: the frame table is what it was
 struct PasteTables {
     const PasteFrameDev* frames;
+    uint8_t* const* chroma;
     const int* of_row;
     const int* list;
     const int* entry;
     std::vector<unsigned char> blob;
 };
 
-int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_frame* frames, int n_frames, PasteTables& out)
+int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_frame* frames, int n_frames, PasteTables& out, bool nv12 = false,
+                 void* const* dst_chroma = nullptr)
 {
     sdm_ctx::Align& a = c->align;
     const int N = (int)frame_of_row.size();
-    const size_t tab_bytes = (size_t)n_frames * sizeof(PasteFrameDev), bytes = tab_bytes + (size_t)3 * N * sizeof(int);
+    const size_t tab_bytes = (size_t)n_frames * sizeof(PasteFrameDev), uv_at = (tab_bytes + (size_t)3 * N * sizeof(int) + 7) / 8 * 8;
+    const size_t bytes = nv12 ? uv_at + (size_t)n_frames * sizeof(uint8_t*) : tab_bytes + (size_t)3 * N * sizeof(int);
     std::vector<unsigned char>& blob = out.blob;
     blob.assign(bytes, 0);
     PasteFrameDev* tab = (PasteFrameDev*)blob.data();
@@ -82,6 +90,15 @@ int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_fra
         d.stride = f.stride_bytes; d.w = f.width; d.h = f.height; d.format = f.format;
         d.row_begin = count[i]; d.row_end = count[(size_t)i + 1]; d.pad = 0;
     }
+    if (nv12) {
+        uint8_t** uv = (uint8_t**)(blob.data() + uv_at);
+        for (int i = 0; i < n_frames; ++i) {
+            const sdm_frame& f = frames[i];
+            uv[i] = f.format != SDM_FRAME_NV12 ? nullptr
+                    : dst_chroma && dst_chroma[i] ? (uint8_t*)dst_chroma[i]
+                                                  : (uint8_t*)const_cast<void*>(f.data) + (size_t)f.height * (size_t)f.stride_bytes;
+        }
+    }
     std::vector<int> fill(count.begin(), count.end() - 1);
     for (int r = 0; r < N; ++r) { const int at = fill[frame_of_row[r]]++; list[at] = r; entry[r] = at; }
     int rc;
@@ -90,6 +107,7 @@ int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_fra
     out.frames = (const PasteFrameDev*)a.paste_tab.p;
     out.of_row = (const int*)(a.paste_tab.p + tab_bytes);
     out.list = out.of_row + N; out.entry = out.of_row + 2 * N;
+    out.chroma = nv12 ? (uint8_t* const*)(a.paste_tab.p + uv_at) : nullptr;
     return SDM_OK;
 }
 
@@ -114,10 +132,12 @@ size_t paste_face_records(int N, bool filtered)
 }
 
 // behind the checks: `faces` holds N records with M (fitted: and the fit's flags).  frame_of_row: N checked indices.  filter: null --
-// the unfiltered calls --, or the checked filter of the filtered ones: their prepare stage and their kernel, S behind the records
+// the unfiltered calls --, or the checked filter of the filtered ones: their prepare stage and their kernel, S behind the records.
+// nv12: the calls that take NV12 destinations -- the same prepare stages, then paste_nv12_kernel with the UV planes (dst_chroma: the
+// caller's, or null); without a filter their S is 1 for every row
 int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int cw, int ch, const sdm_align_tensor* spec, const void* in_dev,
               const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host, int* flags_host,
-              const sdm_align_filter* filter, int* samples_host)
+              const sdm_align_filter* filter, int* samples_host, bool nv12 = false, void* const* dst_chroma = nullptr)
 {
     sdm_ctx::Align& a = c->align;
     const int N = (int)frame_of_row.size();
@@ -125,14 +145,15 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
     PasteTables tab;
     const size_t rows_bytes = (size_t)N * sizeof(PasteRow);
     if ((rc = a.paste_rows.ensure(rows_bytes + (filter ? (size_t)N * sizeof(PasteAreaRow) : 0))) ||
-        (rc = paste_tables(c, frame_of_row, frames, n_frames, tab)))
+        (rc = paste_tables(c, frame_of_row, frames, n_frames, tab, nv12, dst_chroma)))
         return rc;
     PasteRow* rows_dev = (PasteRow*)a.paste_rows.p;
     const PasteCropDev crop = paste_crop_dev(spec, in_dev, paste, cw, ch);
     if (!filter) {
         sdm_launch_paste_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, rows_dev, c->stream);
         HIP_TRY(hipGetLastError());
-        sdm_launch_paste(tab.frames, rows_dev, tab.list, tab.entry, N, crop, c->stream);
+        if (nv12) sdm_launch_paste_nv12(tab.frames, tab.chroma, rows_dev, nullptr, tab.list, tab.entry, N, crop, c->stream);
+        else sdm_launch_paste(tab.frames, rows_dev, tab.list, tab.entry, N, crop, c->stream);
     } else {
         AlignAreaDev area{};
         area.mode = filter->mode; area.max_samples = filter->max_samples;
@@ -141,9 +162,14 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
         sdm_launch_paste_area_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, area, rows_dev, area_dev, (int*)(a.faces.p + N),
                                       c->stream);
         HIP_TRY(hipGetLastError());
-        sdm_launch_paste_area(tab.frames, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);
+        if (nv12) sdm_launch_paste_nv12(tab.frames, tab.chroma, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);
+        else sdm_launch_paste_area(tab.frames, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);
     }
     HIP_TRY(hipGetLastError());
+    if (samples_host && !filter) {                                                      // (an NV12 call without a filter: plain bilinear)
+        for (int r = 0; r < N; ++r) samples_host[r] = 1;
+        samples_host = nullptr;
+    }
     // the records -- and the rows' S behind them -- in one copy, one synchronise
     const size_t rec = (size_t)N * sizeof(AlignFace), bytes = rec + (samples_host ? (size_t)N * sizeof(int) : 0);
     std::vector<unsigned char> host;
@@ -204,12 +230,12 @@ int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const 
 // sdm_align_paste_tensor (filtered false) and sdm_align_paste_tensor_filtered: the same checks, the same fit, then the paste
 int paste_fit_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, int ch, const sdm_align_tensor* spec,
                    const sdm_align_filter* filter, bool filtered, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
-                   int n_frames, float* matrices_host, int* flags_host, int* samples_host)
+                   int n_frames, float* matrices_host, int* flags_host, int* samples_host, bool nv12 = false, void* const* dst_chroma = nullptr)
 {
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     int rc;
     if ((rc = align_check_call(c, lm, tmpl, K, cw, ch)) || (rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
-        (rc = paste_check_args(in_dev, paste, frames, n_frames)) || (rc = align_check_rows(c)))
+        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)) || (rc = align_check_rows(c)))
         return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
@@ -218,20 +244,21 @@ int paste_fit_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, 
     if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(paste_face_records(c->N, filtered)))) return rc;
     if ((rc = align_fit_rows(c, lm, tmpl, K, cw, ch))) return rc;
     return paste_run(c, true, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host, filtered ? filter : nullptr,
-                     samples_host);
+                     samples_host, nv12, dst_chroma);
 }
 
 // sdm_align_paste_tensor_at (filtered false) and sdm_align_paste_tensor_at_filtered
 int paste_at_call(sdm_ctx* c, const float* matrices_host, const int* image_index, int n_rows, int cw, int ch, const sdm_align_tensor* spec,
                   const sdm_align_filter* filter, bool filtered, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
-                  int n_frames, int* flags_host, int* samples_host)
+                  int n_frames, int* flags_host, int* samples_host, bool nv12 = false, void* const* dst_chroma = nullptr)
 {
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     if (!matrices_host) return fail(SDM_ERR_INVALID, "no matrices");
     if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
     if (cw < 1 || cw > 1024 || ch < 1 || ch > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
     int rc;
-    if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) || (rc = paste_check_args(in_dev, paste, frames, n_frames)))
+    if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
+        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)))
         return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;
@@ -247,7 +274,7 @@ int paste_at_call(sdm_ctx* c, const float* matrices_host, const int* image_index
     if ((rc = a.faces.ensure(paste_face_records(n_rows, filtered)))) return rc;
     HIP_TRY(hipMemcpyAsync(a.faces.p, faces.data(), faces.size() * sizeof(AlignFace), hipMemcpyHostToDevice, c->stream));
     return paste_run(c, false, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, nullptr, flags_host, filtered ? filter : nullptr,
-                     samples_host);
+                     samples_host, nv12, dst_chroma);
 }
 
 int warp_paste_check_mesh(sdm_ctx* c)
@@ -333,6 +360,24 @@ int sdm_align_paste_tensor_at_filtered(sdm_ctx* c, const float* matrices_host, c
 {
     return paste_at_call(c, matrices_host, image_index, n_rows, cw, ch, spec, filter, true, in_dev, paste, frames, n_frames, flags_host,
                          samples_host);
+}
+
+// the calls that take NV12 destinations: filter NULL is plain bilinear
+int sdm_align_paste_tensor_nv12(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, int ch, const sdm_align_tensor* spec,
+                                const sdm_align_filter* filter, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
+                                void* const* dst_chroma, int n_frames, float* matrices_host, int* flags_host, int* samples_host)
+{
+    return paste_fit_call(c, lm, tmpl, K, cw, ch, spec, filter, filter != nullptr, in_dev, paste, frames, n_frames, matrices_host, flags_host,
+                          samples_host, true, dst_chroma);
+}
+
+int sdm_align_paste_tensor_at_nv12(sdm_ctx* c, const float* matrices_host, const int* image_index, int n_rows, int cw, int ch,
+                                   const sdm_align_tensor* spec, const sdm_align_filter* filter, const void* in_dev,
+                                   const sdm_align_paste* paste, const sdm_frame* frames, void* const* dst_chroma, int n_frames,
+                                   int* flags_host, int* samples_host)
+{
+    return paste_at_call(c, matrices_host, image_index, n_rows, cw, ch, spec, filter, filter != nullptr, in_dev, paste, frames, n_frames,
+                         flags_host, samples_host, true, dst_chroma);
 }
 
 }  // extern "C"

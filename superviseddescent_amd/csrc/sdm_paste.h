@@ -1,5 +1,5 @@
 // sdm_paste.h -- what the two paste kernels (csrc/sdm_align_paste.hip, csrc/sdm_warp_paste.hip) and their C-ABI (csrc/sdm_capi_paste.hip)
-// share: the device headers' records, the six launches, and a paste kernel's tile walk -- grid (row, paste_groups workgroups); the
+// share: the device headers' records, the seven launches, and a paste kernel's tile walk -- grid (row, paste_groups workgroups); the
 // workgroups of a row stride over the 64 x 4 pixel tiles of its box, a wave covers 64 pixels of one frame row: the box never reaches the host.
 #pragma once
 #include "sdm_warp.h"
@@ -36,6 +36,10 @@ void sdm_launch_paste_area_prepare(AlignFace* faces, const int* frame_of_row, co
                                    const AlignAreaDev& area, PasteRow* rows, PasteAreaRow* area_rows, int* samples, hipStream_t s);
 void sdm_launch_paste_area(const PasteFrameDev* frames, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
                            const int* entry_of_row, int N, const PasteCropDev& crop, hipStream_t s);
+// the calls with NV12 destinations, behind either prepare stage.  chroma: one UV plane per frame (read for NV12 frames only);
+// area_rows: null -- plain bilinear --, or the filtered prepare stage's records
+void sdm_launch_paste_nv12(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows,
+                           const int* list, const int* entry_of_row, int N, const PasteCropDev& crop, hipStream_t s);
 // x: N x 2L; lm: the mesh's K landmark indices; tri: T triangles; faces, matrices: the N records (their FOLDED bit is read) and the
 // N x T x 6 floats of sdm_launch_warp_fit; frame_of_row: N checked indices into frames.  rows: N records; tris: N x T records
 void sdm_launch_warp_paste_prepare(const float* x, int N, int L, const int* lm, int K, const WarpTri* tri, int T, const WarpFace* faces,

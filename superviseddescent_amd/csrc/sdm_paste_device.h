@@ -2,8 +2,9 @@
 // faces back"): the frame and crop records, the inverse map, a frame pixel's position in the crop (paste_position), the decoded taps,
 // the integer bilinear colour and opacity, the blend, the pixel's load / apply / store, and paste_owned -- the one text of the ownership
 // rule, which a paste calls with its shape (PasteRigid of csrc/sdm_align_paste_device.h, PasteRigidArea of
-// csrc/sdm_align_paste_area_device.h, PasteMesh of csrc/sdm_warp_paste_device.h).
-// Plain C++ behind ALIGN_HD: the device code of both kernels and, compiled for the host, of the two programs of tests/cpp that run it
+// csrc/sdm_align_paste_area_device.h, PasteMesh of csrc/sdm_warp_paste_device.h) -- and, for NV12 destinations ("Pasting crops back
+// into NV12 frames"), its sibling paste_owned_block with the 2 x 2 block's load / luma / chroma / store.
+// Plain C++ behind ALIGN_HD: the device code of both kernels and, compiled for the host, of the programs of tests/cpp that run it
 // under the host sanitizers on frames, tensors and opacity maps of exactly the bytes they own.
 //
 // Every float operation is rounded on its own (no contraction: the pragma below under clang, -ffp-contract=off elsewhere); everything
@@ -196,4 +197,138 @@ ALIGN_HD void paste_owned(const PasteFrameDev& f, const Shape& shape, const int*
         paste_apply(c, bgr, a, s);
     }
     paste_store(s);
+}
+
+// NV12 destinations (include/sdm.h, "Pasting crops back into NV12 frames").  The unit is the 2 x 2 block of luma pixels that share one
+// (U, V) pair: block (BX, BY) holds the pixels X in {2 BX, 2 BX + 1}, Y in {2 BY, 2 BY + 1} that lie inside the frame, pixel i at
+// (2 BX + (i & 1), 2 BY + (i >> 1)).  BT.601 limited range in Q20, the counterpart of align_nv12_to_bgr.
+ALIGN_HD uint32_t paste_nv12_luma(const uint32_t bgr[3])
+{
+    return (269484u * bgr[2] + 528482u * bgr[1] + 102760u * bgr[0] + (16u << 20) + (1u << 19)) >> 20;
+}
+
+ALIGN_HD void paste_nv12_chroma(const uint32_t m[3], uint32_t& u, uint32_t& v)
+{
+    const int b = (int)m[0], g = (int)m[1], r = (int)m[2];
+    const int uq = (460324 * b - 305135 * g - 155188 * r + (128 << 20) + (1 << 19)) >> 20;
+    const int vq = (460324 * r - 385875 * g - 74448 * b + (128 << 20) + (1 << 19)) >> 20;
+    u = (uint32_t)(uq < 0 ? 0 : (uq > 255 ? 255 : uq));
+    v = (uint32_t)(vq < 0 ? 0 : (vq > 255 ? 255 : vq));
+}
+
+// One block in its owner's registers: the up-to-four luma bytes (packed, pixel i at bits 8 i) and the UV pair loaded once
+// (paste_block_load), every row applied (paste_block_luma per pixel, paste_block_chroma per row), the changed bytes stored once
+struct PasteBlock {
+    uint8_t* y;                 // the luma byte of pixel 0
+    uint8_t* uv;                // the (U, V) pair; null: a 1-channel tensor, the UV plane is neither read nor written
+    long long stride;
+    uint32_t luma, u, v;
+    int in;                     // bit i: pixel i lies inside the frame
+    int wrote;                  // bit i: a row's opacity was not 0 on pixel i; bit 4: some a_c was not 0
+    uint32_t cnt;               // the pixels inside the frame: 4 | 2 | 1
+};
+
+ALIGN_HD void paste_block_load(const PasteFrameDev& f, uint8_t* chroma, const PasteCropDev& c, int BX, int BY, PasteBlock& s)
+{
+    const int X = 2 * BX, Y = 2 * BY;
+    s.stride = f.stride;
+    s.y = f.p + ((long long)Y * f.stride + X);
+    s.in = 1 | (X + 1 < f.w ? 2 : 0) | (Y + 1 < f.h ? 4 : 0) | (X + 1 < f.w && Y + 1 < f.h ? 8 : 0);
+    s.cnt = (X + 1 < f.w ? 2u : 1u) * (Y + 1 < f.h ? 2u : 1u);
+    s.luma = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (s.in >> i & 1) s.luma |= (uint32_t)s.y[(long long)(i >> 1) * s.stride + (i & 1)] << (8 * i);
+    s.uv = c.channels == 3 ? chroma + ((long long)BY * f.stride + 2 * (long long)BX) : nullptr;
+    s.u = s.v = 0u;
+    if (s.uv) { s.u = s.uv[0]; s.v = s.uv[1]; }
+    s.wrote = 0;
+}
+
+// a row's colour and opacity (a != 0) on pixel i: the luma blend; the opacity-weighted colour sums of the row's chroma rule
+ALIGN_HD void paste_block_luma(const PasteCropDev& c, const uint32_t bgr[3], uint32_t a, int i, PasteBlock& s, uint32_t sum[3], uint32_t& A)
+{
+    const uint32_t yq = c.channels == 3 ? paste_nv12_luma(bgr) : bgr[0];
+    const uint32_t o = s.luma >> (8 * i) & 255u;
+    s.luma = (s.luma & ~(255u << (8 * i))) | paste_blend(a, yq, o) << (8 * i);
+    s.wrote |= 1 << i;
+    A += a;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) sum[t] += a * bgr[t];
+}
+
+// a row's chroma: the opacity-weighted mean colour of the block's pixels, converted, blended with the mean opacity over cnt
+ALIGN_HD void paste_block_chroma(const uint32_t sum[3], uint32_t A, PasteBlock& s)
+{
+    if (!s.uv || A == 0u) return;
+    const uint32_t m[3] = {(sum[0] + A / 2u) / A, (sum[1] + A / 2u) / A, (sum[2] + A / 2u) / A};
+    const uint32_t ac = (A + s.cnt / 2u) / s.cnt;
+    if (ac == 0u) return;
+    uint32_t uq, vq;
+    paste_nv12_chroma(m, uq, vq);
+    s.u = paste_blend(ac, uq, s.u);
+    s.v = paste_blend(ac, vq, s.v);
+    s.wrote |= 16;
+}
+
+ALIGN_HD void paste_block_store(const PasteBlock& s)
+{
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (s.wrote >> i & 1) s.y[(long long)(i >> 1) * s.stride + (i & 1)] = (uint8_t)(s.luma >> (8 * i));
+    if (s.wrote & 16) { s.uv[0] = (uint8_t)s.u; s.uv[1] = (uint8_t)s.v; }
+}
+
+// the pixels of block (BX, BY) that row n's footprint holds, as bits
+template <class Shape>
+ALIGN_HD int paste_block_holds(const PasteFrameDev& f, const Shape& shape, int n, const PasteCropDev& c, int BX, int BY)
+{
+    int held = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int X = 2 * BX + (i & 1), Y = 2 * BY + (i >> 1);
+        AlignPos q;
+        if (X < f.w && Y < f.h && paste_holds(shape, n, c, X, Y, q)) held |= 1 << i;
+    }
+    return held;
+}
+
+// The ownership rule on an NV12 frame: paste_owned with the block as its unit.  Block (BX, BY) as entry k of its frame's row list sees
+// it: nothing unless entry k's footprint holds one of its pixels and no earlier entry's does -- else this is the one reader and writer of
+// the block's luma bytes and of its UV pair: loaded once, entry k and every later entry applied in order (per pixel the taps and the luma
+// blend, then the row's chroma), stored once.  chroma: the frame's UV plane.  The pixel loop is kept rolled: one pixel's taps are live
+// at a time, the block's state is five registers.
+// paste_owned_block_state: the rule up to the store -- false: not this entry's block; true: s is the block as it is to be stored (what the
+// host program of tests/cpp reads the written bytes from).
+template <class Shape>
+ALIGN_HD bool paste_owned_block_state(const PasteFrameDev& f, uint8_t* chroma, const Shape& shape, const int* list, int k, const PasteCropDev& c,
+                                      int BX, int BY, PasteBlock& s)
+{
+    if (!paste_block_holds(f, shape, list[k], c, BX, BY)) return false;
+    for (int j = f.row_begin; j < k; ++j)
+        if (paste_block_holds(f, shape, list[j], c, BX, BY)) return false;
+    paste_block_load(f, chroma, c, BX, BY, s);
+    for (int j = k; j < f.row_end; ++j) {
+        const int n = list[j];
+        uint32_t sum[3] = {0u, 0u, 0u}, A = 0u;
+#pragma unroll 1
+        for (int i = 0; i < 4; ++i) {
+            const int X = 2 * BX + (i & 1), Y = 2 * BY + (i >> 1);
+            AlignPos q;
+            if (!(s.in >> i & 1) || !paste_holds(shape, n, c, X, Y, q)) continue;
+            uint32_t bgr[3], a;
+            paste_taps(shape, c, n, X, Y, q, bgr, a);
+            if (a != 0u) paste_block_luma(c, bgr, a, i, s, sum, A);
+        }
+        paste_block_chroma(sum, A, s);
+    }
+    return true;
+}
+
+template <class Shape>
+ALIGN_HD void paste_owned_block(const PasteFrameDev& f, uint8_t* chroma, const Shape& shape, const int* list, int k, const PasteCropDev& c,
+                                int BX, int BY)
+{
+    PasteBlock s;
+    if (paste_owned_block_state(f, chroma, shape, list, k, c, BX, BY, s)) paste_block_store(s);
 }

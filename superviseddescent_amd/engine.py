@@ -874,18 +874,32 @@ class Context:
             return _lib.align_filter(filter, max_samples, min_scale)
         raise ValueError('filter must be None, "area", "bilinear" or an SdmAlignFilter')
 
+    @staticmethod
+    def _paste_chroma(chroma, arr, keep):
+        """The NV12 calls' UV planes: None unless a destination is NV12 or ``chroma`` is given -- then (the c_void_p array or None,
+        what must stay alive).  ``chroma``: one entry per frame as ``align_set_source_frames`` takes it -- a device pointer, a uint8
+        tensor or None (directly behind the Y plane)."""
+        if chroma is None:
+            return (None, keep) if any(f.format == _lib.SDM_FRAME_NV12 for f in arr) else None
+        if len(chroma) != len(arr):
+            raise ValueError("one chroma entry (or None) per frame expected")
+        uv = (ctypes.c_void_p * len(arr))(*[None if u is None else int(u.data_ptr()) if _lib._is_tensor(u) else int(u) for u in chroma])
+        return uv, (keep, chroma)
+
     def align_paste_tensor(self, landmark_index, template: np.ndarray, y, frames, formats=None, layout="nchw", mask=None, spec=None,
-                           filter=None, max_samples=16, min_scale=1.0, **options):
+                           filter=None, max_samples=16, min_scale=1.0, chroma=None, **options):
         """The inverse of ``align_crops_tensor`` for the N current rows (include/sdm.h, sdm_align_paste_tensor): ``y`` -- a network's
         output on the crops, a device tensor whose dtype, channels and crop size are read from it -- is warped back through every row's
-        fitted similarity and blended into ``frames`` IN PLACE.  ``frames`` / ``formats``: as for ``set_frames_device``, without NV12;
+        fitted similarity and blended into ``frames`` IN PLACE.  ``frames`` / ``formats``: as for ``set_frames_device``;
         row n goes to the frame ``set_sample_image_index`` names.  ``mask``: the crop-space opacity, None (255 inside the crop) or an
         H x W (all rows) or N x H x W uint8 device tensor or numpy array.  ``options``: order, scale, bias, mean, std, gray_shift of
         ``_lib.paste_tensor_spec`` (an element is decoded as e * scale + bias: ``mean`` / ``std`` as in the crop call undo it).  Returns
         (matrices N x 2 x 3 float32 crop -> frame, flags N int32: SDM_ALIGN_* bits).  ``filter``: None (plain bilinear), or "area" /
         "bilinear" with ``max_samples`` and ``min_scale`` (``_lib.align_filter``) or an ``SdmAlignFilter`` for
         sdm_align_paste_tensor_filtered -- a row whose crop outsizes its face averages S x S sub-samples per frame pixel -- which
-        returns (matrices, flags, samples N int32: S of every row)."""
+        returns (matrices, flags, samples N int32: S of every row).  With an "nv12" destination among ``frames``, or ``chroma`` given
+        (per frame the UV plane's device pointer, a uint8 tensor or None, as for ``align_set_source_frames``), the call is
+        sdm_align_paste_tensor_nv12: luma and 4:2:0 chroma blended in place; the return values are the same."""
         filter = self._paste_filter(filter, max_samples, min_scale)
         idx = np.ascontiguousarray(landmark_index, np.int32).reshape(-1)
         t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
@@ -895,6 +909,14 @@ class Context:
         self._paste_rows(n)
         mats = np.empty((n, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
+        nv12 = self._paste_chroma(chroma, arr, keep)
+        if nv12 is not None:
+            samples = np.empty(n, np.int32)
+            check(self._lib.sdm_align_paste_tensor_nv12(self._h, idx.ctypes.data, t.ctypes.data, idx.size, width, height, ctypes.byref(spec),
+                                                        None if filter is None else ctypes.byref(filter), ctypes.c_void_p(y.data_ptr()),
+                                                        ctypes.byref(paste), arr, nv12[0], len(arr), mats.ctypes.data, flags.ctypes.data,
+                                                        samples.ctypes.data))
+            return (mats, flags) if filter is None else (mats, flags, samples)
         if filter is None:
             check(self._lib.sdm_align_paste_tensor(self._h, idx.ctypes.data, t.ctypes.data, idx.size, width, height, ctypes.byref(spec),
                                                    ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr), mats.ctypes.data,
@@ -907,11 +929,12 @@ class Context:
         return mats, flags, samples
 
     def align_paste_tensor_at(self, matrices, y, frames, formats=None, image_index=None, layout="nchw", mask=None, spec=None, filter=None,
-                              max_samples=16, min_scale=1.0, **options):
+                              max_samples=16, min_scale=1.0, chroma=None, **options):
         """``align_paste_tensor`` with explicit crop -> frame matrices (sdm_align_paste_tensor_at): ``matrices`` N x 2 x 3 as an earlier
         crop call returned them -- the tracker may have stepped on since; no landmark state, geometry or context image is needed.
         ``image_index``: the frame of every row (None: row i -> frame i).  Returns flags N int32: SDM_ALIGN_* bits; with a ``filter``
-        (as for ``align_paste_tensor``: sdm_align_paste_tensor_at_filtered) it returns (flags, samples N int32: S of every row)."""
+        (as for ``align_paste_tensor``: sdm_align_paste_tensor_at_filtered) it returns (flags, samples N int32: S of every row).  "nv12"
+        destinations and ``chroma``: as for ``align_paste_tensor`` (sdm_align_paste_tensor_at_nv12)."""
         filter = self._paste_filter(filter, max_samples, min_scale)
         spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
         m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 6)
@@ -919,6 +942,14 @@ class Context:
             raise ValueError(f"one matrix per row of the tensor expected: {m.shape[0]} for {n}")
         idx = self._paste_image_index(image_index, n)
         flags = np.empty(n, np.int32)
+        nv12 = self._paste_chroma(chroma, arr, keep)
+        if nv12 is not None:
+            samples = np.empty(n, np.int32)
+            check(self._lib.sdm_align_paste_tensor_at_nv12(self._h, m.ctypes.data, None if idx is None else idx.ctypes.data, n, width, height,
+                                                           ctypes.byref(spec), None if filter is None else ctypes.byref(filter),
+                                                           ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, nv12[0], len(arr),
+                                                           flags.ctypes.data, samples.ctypes.data))
+            return flags if filter is None else (flags, samples)
         if filter is None:
             check(self._lib.sdm_align_paste_tensor_at(self._h, m.ctypes.data, None if idx is None else idx.ctypes.data, n, width, height,
                                                       ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, len(arr),
@@ -1756,12 +1787,14 @@ class detection_model:
 
     def paste_crops_tensor(self, y, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None, margin: float = 0.2,
                            frames=None, formats=None, layout="nchw", order="rgb", scale=None, bias=None, mean=None, std=None, gray_shift=14,
-                           mask=None, matrices=None, image_index=None, filter=None, max_samples=16, min_scale=1.0):
+                           mask=None, matrices=None, image_index=None, filter=None, max_samples=16, min_scale=1.0, chroma=None):
         """The way back of :meth:`aligned_crops_tensor`: ``y = net(x)`` on the crops -- a device tensor, N x C x H x W or N x H x W x C by
         ``layout``; dtype, channels and crop size are read from it -- is warped back and blended into ``frames`` in place, in one launch
         (include/sdm.h, "Pasting crops back").  ``landmark_ids``, ``template``, ``margin``, ``order``, ``gray_shift``: as in the crop call,
         with the same defaults, so that ``paste(net(crop(...)))`` lands where it was cut.  ``frames`` / ``formats``: the destination, as
-        for ``detect_batch`` on device frames, without NV12.  ``mean`` / ``std`` (0-255 units) as in the crop call: here they mean
+        for ``detect_batch`` on device frames; an "nv12" frame -- ``(y_ptr, width, height, stride, "nv12")``, with ``chroma`` per frame the
+        UV plane's pointer, a uint8 tensor or None (directly behind the Y plane) as in the crop call -- has its luma and 4:2:0 chroma
+        blended in place (include/sdm.h, "Pasting crops back into NV12 frames").  ``mean`` / ``std`` (0-255 units) as in the crop call: here they mean
         ``scale = std``, ``bias = mean``, the decoded value is ``e * scale + bias``.  ``mask``: the crop-space opacity -- None, or an H x W
         or N x H x W uint8 device tensor or numpy array, e.g. :func:`feather_mask`.  ``matrices`` (N x 2 x 3, as a crop call returned
         them) with ``image_index`` (None: row i -> frame i) pastes rows that are no longer current; otherwise the current rows are
@@ -1775,6 +1808,8 @@ class detection_model:
             raise ValueError("give the frames to paste into")
         options = dict(order=order, scale=scale, bias=bias, mean=mean, std=std, gray_shift=gray_shift, filter=filter, max_samples=max_samples,
                        min_scale=min_scale)
+        if chroma is not None:
+            options["chroma"] = chroma
         if matrices is not None:
             m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 2, 3)
             got = c.align_paste_tensor_at(m, y, frames, formats, image_index, layout, mask, **options)

@@ -285,11 +285,19 @@ inline std::vector<sdm_frame> paste_frames(const std::vector<DeviceFrame>& frame
     return f;
 }
 
+// the UV planes of an NV12 paste as the C call takes them: one entry per frame, or none at all
+inline void* const* paste_chroma(const std::vector<void*>& chroma, size_t n_frames)
+{
+    if (!chroma.empty() && chroma.size() != n_frames) throw std::runtime_error("paste_crops_tensor: one chroma entry (or nullptr) per frame");
+    return chroma.empty() ? nullptr : chroma.data();
+}
+
 // the n current rows of the handle `c`: the fit of aligned_crops_tensor, then the tensor at `in_dev` pasted into `frames` in place;
-// `filter`: nullptr, or the sampling of sdm_align_paste_tensor_filtered
+// `filter`: nullptr, or the sampling of sdm_align_paste_tensor_filtered; `chroma`: nullptr, or -- the overloads for NV12 destinations,
+// sdm_align_paste_tensor_nv12 -- the frames' UV planes (empty: every one directly behind its Y plane)
 inline paste_result paste_current_rows(sdm_ctx* c, int n, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
                                        const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames, const PasteMask& mask,
-                                       const AlignFilter* filter = nullptr)
+                                       const AlignFilter* filter = nullptr, const std::vector<void*>* chroma = nullptr)
 {
     using superviseddescent::hip::check;
     if (tmpl.rows != (int)landmark_index.size() || tmpl.cols != 2) throw std::runtime_error("paste_crops_tensor: one template point (x, y) per landmark");
@@ -300,6 +308,15 @@ inline paste_result paste_current_rows(sdm_ctx* c, int n, const std::vector<int>
     paste_result res;
     res.matrices = cv::Mat(n, 6, CV_32FC1);
     res.flags.resize((size_t)n);
+    if (chroma) {
+        const sdm_align_filter fl = filter ? sdm_align_filter{filter->mode, filter->max_samples, filter->min_scale} : sdm_align_filter{};
+        if (filter) res.samples.resize((size_t)n);
+        check(sdm_align_paste_tensor_nv12(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s,
+                                          filter ? &fl : nullptr, in_dev, &p, f.empty() ? nullptr : f.data(), paste_chroma(*chroma, f.size()),
+                                          (int)f.size(), res.matrices.ptr<float>(0), res.flags.data(), filter ? res.samples.data() : nullptr),
+              "sdm_align_paste_tensor_nv12");
+        return res;
+    }
     if (filter) {
         const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
         res.samples.resize((size_t)n);
@@ -319,7 +336,7 @@ inline paste_result paste_current_rows(sdm_ctx* c, int n, const std::vector<int>
 
 /** The way back of aligned_crops_tensor: `in_dev` -- a network's output on the crops of the tracker's last step, rows * channels * height *
  *  width elements of spec.dtype in spec.layout, 16-byte aligned device memory -- is warped back through every stream's fitted similarity
- *  and blended into `frames` IN PLACE (the frames of that step, GRAY / BGR / RGB / BGRA / RGBA; NV12 is refused), in one launch
+ *  and blended into `frames` IN PLACE (the frames of that step, GRAY / BGR / RGB / BGRA / RGBA; NV12: the overloads with `chroma`), in one launch
  *  (include/sdm.h, "Pasting crops back").  An element is decoded as e * spec.scale[c] + spec.bias[c]: scale = std, bias = mean in 0-255
  *  units undo TensorSpec::normalise(mean, std) of the crop call. */
 inline paste_result paste_crops_tensor(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
@@ -340,12 +357,35 @@ inline paste_result paste_crops_tensor(tracker& tr, const std::vector<int>& land
     return detail::paste_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask, &filter);
 }
 
+/** NV12 destinations (include/sdm.h, "Pasting crops back into NV12 frames"): `frames` may hold SDM_FRAME_NV12 entries -- the decoder
+ *  surfaces the tracker stepped on -- beside the other five formats; luma and 4:2:0 chroma are blended in place.  `chroma`: per frame the
+ *  UV plane's device pointer, or nullptr / an empty vector for "directly behind the Y plane" (as for aligned_crops_tensor). */
+inline paste_result paste_crops_tensor(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                       const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames,
+                                       const std::vector<void*>& chroma, const PasteMask& mask = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("paste_crops_tensor: step the tracker first");
+    return detail::paste_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask, nullptr,
+                                      &chroma);
+}
+
+/** NV12 destinations with the sampling of `filter`. */
+inline paste_result paste_crops_tensor(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                       const TensorSpec& spec, const AlignFilter& filter, const void* in_dev,
+                                       const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma, const PasteMask& mask = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("paste_crops_tensor: step the tracker first");
+    return detail::paste_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask, &filter,
+                                      &chroma);
+}
+
 /** The same for landmark rows on device frames (as the detection_model overload of aligned_crops_tensor: a handle of its own, the frames
- *  as its image set, the rows uploaded): row i is pasted into frames[image_index[i]] (default: frames[i]). */
+ *  as its image set, the rows uploaded): row i is pasted into frames[image_index[i]] (default: frames[i]).  `chroma`: nullptr, or the
+ *  frames' UV planes -- then NV12 frames are accepted (the overloads below). */
 inline paste_result paste_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
                                        const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
                                        int height, const TensorSpec& spec, const void* in_dev, const PasteMask& mask = {},
-                                       const AlignFilter* filter = nullptr)
+                                       const AlignFilter* filter = nullptr, const std::vector<void*>* chroma = nullptr)
 {
     using superviseddescent::hip::check;
     superviseddescent::hip::Handle h(superviseddescent::hip::device());
@@ -357,7 +397,24 @@ inline paste_result paste_crops_tensor(detection_model& model, const std::vector
     if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
     else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
     check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
-    return detail::paste_current_rows(c, x.rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask, filter);
+    return detail::paste_current_rows(c, x.rows, landmark_index, tmpl, width, height, spec, in_dev, frames, mask, filter, chroma);
+}
+
+/** NV12 destinations for landmark rows: `chroma` as in the tracker overload; `filter`: nullptr (plain bilinear) or the sampling. */
+inline paste_result paste_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma,
+                                       cv::Mat rows, const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl,
+                                       int width, int height, const TensorSpec& spec, const void* in_dev, const PasteMask& mask = {},
+                                       const AlignFilter* filter = nullptr)
+{
+    return paste_crops_tensor(model, frames, rows, image_index, landmark_index, tmpl, width, height, spec, in_dev, mask, filter, &chroma);
+}
+
+inline paste_result paste_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma,
+                                       cv::Mat rows, const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl,
+                                       int width, int height, const TensorSpec& spec, const AlignFilter& filter, const void* in_dev,
+                                       const PasteMask& mask = {})
+{
+    return paste_crops_tensor(model, frames, rows, image_index, landmark_index, tmpl, width, height, spec, in_dev, mask, &filter, &chroma);
 }
 
 /** The same with the sampling of `filter` (the result's `samples`: S of every row). */
@@ -374,7 +431,7 @@ inline paste_result paste_crops_tensor(detection_model& model, const std::vector
  *  are the ones given. */
 inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>& image_index, int width, int height, const TensorSpec& spec,
                                        const void* in_dev, const std::vector<DeviceFrame>& frames, const PasteMask& mask = {},
-                                       const AlignFilter* filter = nullptr)
+                                       const AlignFilter* filter = nullptr, const std::vector<void*>* chroma = nullptr)
 {
     using superviseddescent::hip::check;
     if (matrices.type() != CV_32FC1 || matrices.cols != 6 || matrices.rows < 1) throw std::runtime_error("paste_crops_tensor: matrices must be rows x 6 CV_32FC1");
@@ -386,6 +443,16 @@ inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>&
     const std::vector<sdm_frame> f = detail::paste_frames(frames);
     const sdm_align_tensor s = detail::paste_spec(spec);
     const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
+    if (chroma) {
+        const sdm_align_filter fl = filter ? sdm_align_filter{filter->mode, filter->max_samples, filter->min_scale} : sdm_align_filter{};
+        if (filter) res.samples.resize((size_t)matrices.rows);
+        check(sdm_align_paste_tensor_at_nv12(h.get(), res.matrices.ptr<float>(0), image_index.empty() ? nullptr : image_index.data(),
+                                             matrices.rows, width, height, &s, filter ? &fl : nullptr, in_dev, &p,
+                                             f.empty() ? nullptr : f.data(), detail::paste_chroma(*chroma, f.size()), (int)f.size(),
+                                             res.flags.data(), filter ? res.samples.data() : nullptr),
+              "sdm_align_paste_tensor_at_nv12");
+        return res;
+    }
     if (filter) {
         const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
         res.samples.resize((size_t)matrices.rows);
@@ -407,6 +474,21 @@ inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>&
                                        const PasteMask& mask = {})
 {
     return paste_crops_tensor(matrices, image_index, width, height, spec, in_dev, frames, mask, &filter);
+}
+
+/** The explicit form for NV12 destinations (sdm_align_paste_tensor_at_nv12): `chroma` as in the tracker overload. */
+inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>& image_index, int width, int height, const TensorSpec& spec,
+                                       const void* in_dev, const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma,
+                                       const PasteMask& mask = {})
+{
+    return paste_crops_tensor(matrices, image_index, width, height, spec, in_dev, frames, mask, nullptr, &chroma);
+}
+
+inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>& image_index, int width, int height, const TensorSpec& spec,
+                                       const AlignFilter& filter, const void* in_dev, const std::vector<DeviceFrame>& frames,
+                                       const std::vector<void*>& chroma, const PasteMask& mask = {})
+{
+    return paste_crops_tensor(matrices, image_index, width, height, spec, in_dev, frames, mask, &filter, &chroma);
 }
 
 }  // namespace rcr
