@@ -675,8 +675,17 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
                 // (specialised instance: yy and with it the band are constants after unrolling; prev_by folds away)
                 const int cby = CELL > 0 ? packed_band_of(yy, CELL) : __builtin_bit_cast(int, rt[2]);
                 if (cby != prev_by) {
-                    if (prev_by >= 0) fold_band(prev_by);
-                    prev_by = cby;
+                    // Detect instances: band C - 2 is not folded where band C - 1's rows begin but together with it, in the closing pair
+                    // fold behind the loop -- four fold events per pass, not five.  The rows of band C - 1 leave its slot as it is: their
+                    // weight for that slot is the one of cell row C, which does not exist and is zero in the row table (fill_row_tab), and
+                    // fma(0, g, q) is q for a finite g and a column sum q, which is never -0.  (The pair fold was written for this; the row
+                    // loop folded band C - 2 at the boundary all the same, so the closing call only ever saw band C - 1 alone:
+                    // profiles/hog_fold_overlap.txt.)
+                    if (CELLS && F16F && cby == C - 1 && prev_by == C - 2) { }
+                    else {
+                        if (prev_by >= 0) fold_band(prev_by);
+                        prev_by = cby;
+                    }
                 }
                 if constexpr (ROTB) {
                     // the octant code straight from the three sign bits (shifts and shift-ors instead of three compares and three selects)
