@@ -45,6 +45,15 @@ struct AlignTensorDev {
     int wb, wg, wr, gray_shift;
 };
 
+// gray_shift and its weight set: sdm_upload_images_bgr_u8's two, 14 (OpenCV 2.4 ... 3.x) or 15 (later releases).  Host code: the C-ABI
+// fills the record with it, and so do the host programs of tests/cpp.
+static inline void align_gray_weights(int gray_shift, AlignTensorDev& t)
+{
+    t.gray_shift = gray_shift;
+    if (gray_shift == 14) { t.wb = 1868; t.wg = 9617; t.wr = 4899; }
+    else { t.wb = 3735; t.wg = 19235; t.wr = 9798; }
+}
+
 // 1/32-pixel position of (sx, sy); false: refused by the 2^20 rule (also NaN: a degenerate row's M)
 ALIGN_HD bool align_quantise(float sx, float sy, AlignPos& q)
 {

@@ -66,9 +66,8 @@ AlignTensorDev sdm_capi::align_tensor_dev(const sdm_align_tensor* spec)
 {
     AlignTensorDev t{};
     for (int k = 0; k < 3; ++k) { t.scale[k] = spec->scale[k]; t.bias[k] = spec->bias[k]; }
-    t.order = spec->order; t.gray_shift = spec->gray_shift;
-    if (spec->gray_shift == 14) { t.wb = 1868; t.wg = 9617; t.wr = 4899; }        // sdm_upload_images_bgr_u8's two weight sets
-    else { t.wb = 3735; t.wg = 19235; t.wr = 9798; }
+    t.order = spec->order;
+    align_gray_weights(spec->gray_shift, t);
     return t;
 }
 
@@ -137,10 +136,23 @@ int sdm_capi::align_check_filter(const sdm_align_filter* filter)
     return SDM_OK;
 }
 
-// the records -- and, behind them in the same buffer, the rows' S when `samples_host` is given -- in one copy, one synchronise
-static int align_fetch_rows(sdm_ctx* c, float* matrices_host, int* flags_host, int* samples_host = nullptr)
+AlignAreaDev sdm_capi::align_area_dev(const sdm_align_filter* filter)
 {
-    const size_t rec = (size_t)c->N * sizeof(AlignFace), bytes = rec + (samples_host ? (size_t)c->N * sizeof(int) : 0);
+    AlignAreaDev area{};
+    area.mode = filter->mode; area.max_samples = filter->max_samples;
+    area.min2 = filter->min_scale * filter->min_scale;                              // (float32, rounded once; may be inf: then every S is 1)
+    return area;
+}
+
+size_t sdm_capi::align_face_records(int N, bool with_samples)
+{
+    return (size_t)N + (with_samples ? ((size_t)N * sizeof(int) + sizeof(AlignFace) - 1) / sizeof(AlignFace) : 0);
+}
+
+// the records -- and, behind them in the same buffer, the rows' S when `samples_host` is given -- in one copy, one synchronise
+int sdm_capi::align_fetch_rows(sdm_ctx* c, int N, float* matrices_host, int* flags_host, int* samples_host)
+{
+    const size_t rec = (size_t)N * sizeof(AlignFace), bytes = rec + (samples_host ? (size_t)N * sizeof(int) : 0);
     std::vector<unsigned char> host;
     if (matrices_host || flags_host || samples_host) {
         host.resize(bytes);
@@ -149,16 +161,13 @@ static int align_fetch_rows(sdm_ctx* c, float* matrices_host, int* flags_host, i
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (host.empty()) return SDM_OK;
     const AlignFace* faces = (const AlignFace*)host.data();
-    for (int r = 0; r < c->N; ++r) {
+    for (int r = 0; r < N; ++r) {
         if (matrices_host) memcpy(matrices_host + (size_t)6 * r, faces[r].m, 6 * sizeof(float));
         if (flags_host) flags_host[r] = faces[r].flags;
     }
-    if (samples_host) memcpy(samples_host, host.data() + rec, (size_t)c->N * sizeof(int));
+    if (samples_host) memcpy(samples_host, host.data() + rec, (size_t)N * sizeof(int));
     return SDM_OK;
 }
-
-// records of N rows with room for N ints behind them
-static size_t align_records_with_samples(int N) { return (size_t)N + ((size_t)N * sizeof(int) + sizeof(AlignFace) - 1) / sizeof(AlignFace); }
 
 // sdm_align_crops_tensor (filter null) and sdm_align_crops_tensor_filtered: the same checks, the same fit, one launch behind it
 static int align_tensor_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h, const sdm_align_tensor* spec,
@@ -175,7 +184,7 @@ static int align_tensor_call(sdm_ctx* c, const int* lm, const float* tmpl, int K
     const int N = c->N;
     sdm_ctx::Align& a = c->align;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(filtered ? align_records_with_samples(N) : (size_t)N))) return rc;
+    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(align_face_records(N, filtered)))) return rc;
     if ((rc = align_fit_rows(c, lm, tmpl, K, out_w, out_h))) return rc;
     const AlignTensorDev t = align_tensor_dev(spec);
     const AlignTapSource src = align_tap_source(c);
@@ -184,15 +193,12 @@ static int align_tensor_call(sdm_ctx* c, const int* lm, const float* tmpl, int K
         sdm_launch_align_tensor(src.base, a.faces.p, src.frames, img_idx, src.stack_format, N, out_w, out_h, spec->dtype, spec->layout,
                                 spec->channels, t, out_dev, c->stream);
         HIP_TRY(hipGetLastError());
-        return align_fetch_rows(c, matrices_host, flags_host);
+        return align_fetch_rows(c, N, matrices_host, flags_host, nullptr);
     }
-    AlignAreaDev area{};
-    area.mode = filter->mode; area.max_samples = filter->max_samples;
-    area.min2 = filter->min_scale * filter->min_scale;                              // (float32, rounded once; may be inf: then every S is 1)
     sdm_launch_align_area(src.base, a.faces.p, src.frames, img_idx, src.stack_format, N, out_w, out_h, spec->dtype, spec->layout,
-                          spec->channels, t, area, (int*)(a.faces.p + N), out_dev, c->stream);
+                          spec->channels, t, align_area_dev(filter), (int*)(a.faces.p + N), out_dev, c->stream);
     HIP_TRY(hipGetLastError());
-    return align_fetch_rows(c, matrices_host, flags_host, samples_host);
+    return align_fetch_rows(c, N, matrices_host, flags_host, samples_host);
 }
 
 extern "C" {
@@ -291,7 +297,7 @@ int sdm_align_crops(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out
     sdm_launch_align_warp(img, a.faces.p, N, out_w, out_h, C, dst, c->stream);
     HIP_TRY(hipGetLastError());
     if (!out_on_device) HIP_TRY(hipMemcpyAsync(out, a.crops.p, crop_bytes, hipMemcpyDeviceToHost, c->stream));
-    return align_fetch_rows(c, matrices_host, flags_host);
+    return align_fetch_rows(c, N, matrices_host, flags_host, nullptr);
 }
 
 int sdm_align_crops_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out_w, int out_h, const sdm_align_tensor* spec,

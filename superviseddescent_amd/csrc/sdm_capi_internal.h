@@ -417,6 +417,13 @@ AlignTensorDev align_tensor_dev(const sdm_align_tensor* spec);
 AlignSourceDev align_source_dev(const sdm_ctx* c);
 struct AlignTapSource { const uint8_t* base; const AlignFrameDev* frames; int stack_format; };     // (frames null: stack_format at base + off)
 AlignTapSource align_tap_source(const sdm_ctx* c);
+// what the filtered crop and paste calls share behind their checks: the checked filter as the kernels read it; the records of
+// align.faces that hold N rows -- with room for N ints, the rows' S, behind them when with_samples --; and, behind a call's launches,
+// the N records -- and S behind them when samples_host is given -- in one copy, one synchronise, scattered to the caller's arrays
+// (each may be null)
+AlignAreaDev align_area_dev(const sdm_align_filter* filter);
+size_t align_face_records(int N, bool with_samples);
+int align_fetch_rows(sdm_ctx* c, int N, float* matrices_host, int* flags_host, int* samples_host);
 // K in [Kmin, L], K distinct landmark indices in [0, L), a finite template of K points
 int check_landmark_subset(const sdm_ctx* c, const int* lm, const float* tmpl, int K, int Kmin);
 int ensure_sample_buffers(sdm_ctx* c, int N);

@@ -117,18 +117,9 @@ PasteCropDev paste_crop_dev(const sdm_align_tensor* spec, const void* in_dev, co
     PasteCropDev crop{};
     crop.in = in_dev; crop.alpha = paste->alpha_dev;
     crop.cw = cw; crop.ch = ch; crop.dtype = spec->dtype; crop.channels = spec->channels;
-    crop.sn = (long long)spec->channels * cw * ch;
-    if (spec->layout == SDM_ALIGN_NCHW) { crop.sc = cw * ch; crop.sy = cw; crop.sx = 1; }
-    else { crop.sc = 1; crop.sy = cw * spec->channels; crop.sx = spec->channels; }
-    crop.an = paste->alpha_per_row ? (long long)cw * ch : 0;
+    paste_crop_layout(crop, spec->layout, paste->alpha_per_row != 0);
     crop.t = align_tensor_dev(spec);
     return crop;
-}
-
-// the N records of align.faces, with room for N ints -- the rows' S -- behind them when the call is filtered
-size_t paste_face_records(int N, bool filtered)
-{
-    return (size_t)N + (filtered ? ((size_t)N * sizeof(int) + sizeof(AlignFace) - 1) / sizeof(AlignFace) : 0);
 }
 
 // behind the checks: `faces` holds N records with M (fitted: and the fit's flags).  frame_of_row: N checked indices.  filter: null --
@@ -155,12 +146,9 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
         if (nv12) sdm_launch_paste_nv12(tab.frames, tab.chroma, rows_dev, nullptr, tab.list, tab.entry, N, crop, c->stream);
         else sdm_launch_paste(tab.frames, rows_dev, tab.list, tab.entry, N, crop, c->stream);
     } else {
-        AlignAreaDev area{};
-        area.mode = filter->mode; area.max_samples = filter->max_samples;
-        area.min2 = filter->min_scale * filter->min_scale;                          // (float32, rounded once; may be inf: then every S is 1)
         PasteAreaRow* area_dev = (PasteAreaRow*)(a.paste_rows.p + rows_bytes);
-        sdm_launch_paste_area_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, area, rows_dev, area_dev, (int*)(a.faces.p + N),
-                                      c->stream);
+        sdm_launch_paste_area_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, align_area_dev(filter), rows_dev, area_dev,
+                                      (int*)(a.faces.p + N), c->stream);
         HIP_TRY(hipGetLastError());
         if (nv12) sdm_launch_paste_nv12(tab.frames, tab.chroma, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);
         else sdm_launch_paste_area(tab.frames, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);
@@ -170,22 +158,7 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
         for (int r = 0; r < N; ++r) samples_host[r] = 1;
         samples_host = nullptr;
     }
-    // the records -- and the rows' S behind them -- in one copy, one synchronise
-    const size_t rec = (size_t)N * sizeof(AlignFace), bytes = rec + (samples_host ? (size_t)N * sizeof(int) : 0);
-    std::vector<unsigned char> host;
-    if (matrices_host || flags_host || samples_host) {
-        host.resize(bytes);
-        HIP_TRY(hipMemcpyAsync(host.data(), a.faces.p, bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (host.empty()) return SDM_OK;
-    const AlignFace* faces = (const AlignFace*)host.data();
-    for (int r = 0; r < N; ++r) {
-        if (matrices_host) memcpy(matrices_host + (size_t)6 * r, faces[r].m, 6 * sizeof(float));
-        if (flags_host) flags_host[r] = faces[r].flags;
-    }
-    if (samples_host) memcpy(samples_host, host.data() + rec, (size_t)N * sizeof(int));
-    return SDM_OK;
+    return align_fetch_rows(c, N, matrices_host, flags_host, samples_host);
 }
 
 // The piecewise-affine paste behind its checks.  x: N x 2L on the device (the landmark state, or the uploaded points in its layout);
@@ -241,7 +214,7 @@ int paste_fit_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, 
     if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
     sdm_ctx::Align& a = c->align;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(paste_face_records(c->N, filtered)))) return rc;
+    if ((rc = a.in.ensure((size_t)3 * K)) || (rc = a.faces.ensure(align_face_records(c->N, filtered)))) return rc;
     if ((rc = align_fit_rows(c, lm, tmpl, K, cw, ch))) return rc;
     return paste_run(c, true, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host, filtered ? filter : nullptr,
                      samples_host, nv12, dst_chroma);
@@ -271,7 +244,7 @@ int paste_at_call(sdm_ctx* c, const float* matrices_host, const int* image_index
     }
     sdm_ctx::Align& a = c->align;
     HIP_TRY(hipSetDevice(c->device));
-    if ((rc = a.faces.ensure(paste_face_records(n_rows, filtered)))) return rc;
+    if ((rc = a.faces.ensure(align_face_records(n_rows, filtered)))) return rc;
     HIP_TRY(hipMemcpyAsync(a.faces.p, faces.data(), faces.size() * sizeof(AlignFace), hipMemcpyHostToDevice, c->stream));
     return paste_run(c, false, frame_of_row, cw, ch, spec, in_dev, paste, frames, n_frames, nullptr, flags_host, filtered ? filter : nullptr,
                      samples_host, nv12, dst_chroma);

@@ -37,6 +37,16 @@ struct PasteCropDev {
     AlignTensorDev t;           // the decode and gray constants
 };
 
+// sn, sc, sy, sx and an of a tensor of cw x ch x channels in `layout` (SDM_ALIGN_NCHW | SDM_ALIGN_NHWC), one opacity map per row or one
+// for all.  Host code: the C-ABI fills the record with it, and so do the host programs of tests/cpp.
+static inline void paste_crop_layout(PasteCropDev& c, int layout, bool alpha_per_row)
+{
+    c.sn = (long long)c.channels * c.cw * c.ch;
+    if (layout == SDM_ALIGN_NCHW) { c.sc = c.cw * c.ch; c.sy = c.cw; c.sx = 1; }
+    else { c.sc = 1; c.sy = c.cw * c.channels; c.sx = c.channels; }
+    c.an = alpha_per_row ? (long long)c.cw * c.ch : 0;
+}
+
 // W (frame -> crop) of a float32 M (crop -> frame): in double, each of the six entries rounded once to float32; returns d
 ALIGN_HD double paste_inverse(const float m[6], float w[6])
 {

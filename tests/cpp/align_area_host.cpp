@@ -10,19 +10,9 @@
 // exits 1 when the 32-bit and the 64-bit offset paths disagree, or the reciprocal division is not the division
 #include "../../superviseddescent_amd/csrc/sdm_align_area_device.h"
 
-#include <cstdio>
-#include <fstream>
-#include <memory>
-#include <vector>
+#include "host_case.hpp"
 
-template <class T>
-static T get(std::ifstream& f)
-{
-    T v;
-    f.read((char*)&v, sizeof(T));
-    if (!f) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
-    return v;
-}
+#include <vector>
 
 template <bool WIDE>
 static void segment(const AlignRow& r, int i, int j0, int npx, int S, uint32_t px[4][3])
@@ -43,6 +33,9 @@ int main(int argc, char** argv)
     std::ifstream in(argv[1], std::ios::binary);
     std::ofstream out(argv[2], std::ios::binary);
     const int n = get<int>(in);
+    AlignTensorDev w14{}, w15{};
+    align_gray_weights(14, w14);
+    align_gray_weights(15, w15);
     bool same = true;
     for (int k = 0; k < n; ++k) {
         AlignRow r;
@@ -54,12 +47,8 @@ int main(int argc, char** argv)
         for (int e = 0; e < 3; ++e) bias[e] = get<float>(in);
         const int mode = get<int>(in), max_samples = get<int>(in);
         const float min_scale = get<float>(in);
-        const int b0 = get<int>(in);
-        std::unique_ptr<uint8_t[]> p0(new uint8_t[b0]);
-        in.read((char*)p0.get(), b0);
-        const int b1 = get<int>(in);
-        std::unique_ptr<uint8_t[]> p1(new uint8_t[b1 > 0 ? b1 : 1]);
-        in.read((char*)p1.get(), b1);
+        int b0, b1;
+        const std::unique_ptr<uint8_t[]> p0 = block(in, b0), p1 = block(in, b1);
         r.p0 = p0.get(); r.p1 = b1 > 0 ? p1.get() : nullptr;
         const int S = align_area_samples(r.m, 0, mode, max_samples, min_scale * min_scale);
         AlignRow luma = r;                                   // one output channel: an NV12 row is its Y plane
@@ -82,8 +71,8 @@ int main(int argc, char** argv)
                         bgr[at * 3 + c] = (uint8_t)px[q][c];
                         planes[(size_t)c * oh * ow + at] = align_element(align_channel<3>(px[q], c, weigh, SDM_ALIGN_ORDER_RGB, 0, 0, 0, 14), scale[c], bias[c]);
                     }
-                    g14[at] = (uint8_t)align_channel<1>(one[q], 0, weigh, 0, 1868, 9617, 4899, 14);
-                    g15[at] = (uint8_t)align_channel<1>(one[q], 0, weigh, 0, 3735, 19235, 9798, 15);
+                    g14[at] = (uint8_t)align_channel<1>(one[q], 0, weigh, 0, w14.wb, w14.wg, w14.wr, w14.gray_shift);
+                    g15[at] = (uint8_t)align_channel<1>(one[q], 0, weigh, 0, w15.wb, w15.wg, w15.wr, w15.gray_shift);
                 }
             }
         out.write((const char*)&S, sizeof(int));

@@ -9,22 +9,9 @@
 // writes track_gray.u8, track_mats.f32, track_flags.i32, track_colour.u8, detect_rows.f32, detect_gray.u8, detect_mats.f32
 #include "rcr/alignment.hpp"
 
-#include <cstdio>
-#include <fstream>
+#include "gpu_driver.hpp"
 
 using cv::Mat;
-
-template <class T>
-static std::vector<T> read_all(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    const size_t n = (size_t)f.tellg();
-    f.seekg(0);
-    std::vector<T> v(n / sizeof(T));
-    f.read((char*)v.data(), (std::streamsize)n);
-    return v;
-}
 
 static void write_crops(const std::string& path, const rcr::aligned_crops_result& r)
 {
@@ -32,17 +19,9 @@ static void write_crops(const std::string& path, const rcr::aligned_crops_result
     for (const auto& m : r.crops) f.write((const char*)m.ptr<uint8_t>(0), (std::streamsize)(m.rows * m.step()));
 }
 
-static void write_mat(const std::string& path, const Mat& m)
-{
-    std::ofstream f(path, std::ios::binary);
-    for (int r = 0; r < m.rows; ++r) f.write((const char*)m.ptr<float>(r), (std::streamsize)m.cols * 4);
-}
-
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: align_gpu <dir>\n"); return 2; }
-    const std::string dir = argv[1];
-    try {
+    return driver_main(argc, argv, "align_gpu", [](const std::string& dir) {
         std::ifstream meta(dir + "/meta.txt");
         int S, T, H, W, K;
         meta >> S >> T >> H >> W >> K;
@@ -76,7 +55,7 @@ int main(int argc, char** argv)
         if ((int)gray.crops.size() != S || col.crops[0].channels() != 3) throw std::runtime_error("unexpected crop shapes");
         write_crops(dir + "/track_gray.u8", gray);
         write_mat(dir + "/track_mats.f32", gray.matrices);
-        std::ofstream(dir + "/track_flags.i32", std::ios::binary).write((const char*)gray.flags.data(), (std::streamsize)S * 4);
+        write_bytes(dir + "/track_flags.i32", gray.flags.data(), (size_t)S * 4);
         write_crops(dir + "/track_colour.u8", col);
 
         const std::vector<Mat> f0 = frame(0);
@@ -88,9 +67,6 @@ int main(int argc, char** argv)
         int partial = 0;
         for (int f : gray.flags) partial += (f & SDM_ALIGN_PARTIAL) != 0;
         std::printf("streams %d, crops 112 x 112 gray + colour, partial %d\n", S, partial);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

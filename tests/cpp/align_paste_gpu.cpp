@@ -11,54 +11,13 @@
 // writes fit.u8 and at.u8 (the frames' bytes after each paste), mats.f32, flags.i32, flags_at.i32
 #include "rcr/alignment.hpp"
 
-#include <cstdio>
-#include <dlfcn.h>
-#include <fstream>
-
-// the runtime calls the driver needs, taken from the HIP runtime that libsdm_hip.so has already brought into the process
-struct Hip {
-    int (*malloc_)(void**, size_t) = nullptr;
-    int (*free_)(void*) = nullptr;
-    int (*memcpy_)(void*, const void*, size_t, int) = nullptr;
-    Hip()
-    {
-        malloc_ = (int (*)(void**, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
-        free_ = (int (*)(void*))dlsym(RTLD_DEFAULT, "hipFree");
-        memcpy_ = (int (*)(void*, const void*, size_t, int))dlsym(RTLD_DEFAULT, "hipMemcpy");
-        if (!malloc_ || !free_ || !memcpy_) throw std::runtime_error("the HIP runtime is not loaded");
-    }
-};
-
-template <class T>
-static std::vector<T> read_all(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    const size_t n = (size_t)f.tellg();
-    f.seekg(0);
-    std::vector<T> v(n / sizeof(T));
-    f.read((char*)v.data(), (std::streamsize)n);
-    return v;
-}
-
-static void write_bytes(const std::string& path, const void* p, size_t n)
-{
-    std::ofstream f(path, std::ios::binary);
-    f.write((const char*)p, (std::streamsize)n);
-}
+#include "gpu_driver.hpp"
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: align_paste_gpu <dir>\n"); return 2; }
-    const std::string dir = argv[1];
-    try {
-        std::ifstream meta(dir + "/meta.txt");
-        int S, cw, ch, K;
-        meta >> S >> cw >> ch >> K;
-        std::vector<int> lm(K);
-        for (int& v : lm) meta >> v;
-        std::vector<int> fmt(S), W(S), H(S), stride(S), bytes(S);
-        for (int s = 0; s < S; ++s) meta >> fmt[s] >> W[s] >> H[s] >> stride[s] >> bytes[s];
+    return driver_main(argc, argv, "align_paste_gpu", [](const std::string& dir) {
+        const Scenario sc(dir + "/meta.txt");
+        const int S = sc.S, cw = sc.w, ch = sc.h, K = (int)sc.lm.size();
         rcr::detection_model model = rcr::load_detection_model(dir + "/model.bin");
         auto pixels = read_all<uint8_t>(dir + "/frames.u8");
         auto rows = read_all<float>(dir + "/rows.f32");
@@ -68,18 +27,9 @@ int main(int argc, char** argv)
         const int L = (int)model.get_landmark_ids().size();
         if ((int)rows.size() != S * 2 * L || (int)tm.size() != 2 * K || tensor.size() != (size_t)S * 3 * cw * ch * 2 || alpha.size() != (size_t)S * cw * ch)
             throw std::runtime_error("scenario size mismatch");
-        superviseddescent::hip::Handle first(superviseddescent::hip::device());     // (the device is up from here on)
-        Hip hip;
-        std::vector<void*> allocations;
-        auto upload = [&](const void* src, size_t n, size_t shift) {
-            void* d = nullptr;
-            if (hip.malloc_(&d, n + shift) != 0) throw std::runtime_error("hipMalloc failed");
-            allocations.push_back(d);
-            if (hip.memcpy_((uint8_t*)d + shift, src, n, 1 /* host to device */) != 0) throw std::runtime_error("hipMemcpy failed");
-            return (uint8_t*)d + shift;
-        };
-        const uint8_t* in_dev = upload(tensor.data(), tensor.size(), 0);
-        const rcr::PasteMask mask{upload(alpha.data(), alpha.size(), 0), true};
+        DeviceMemory mem;
+        const uint8_t* in_dev = mem.upload(tensor.data(), tensor.size());
+        const rcr::PasteMask mask{mem.upload(alpha.data(), alpha.size()), true};
         cv::Mat x(S, 2 * L, CV_32FC1), tmpl(K, 2, CV_32FC1);
         std::memcpy(x.ptr<float>(0), rows.data(), rows.size() * 4);
         std::memcpy(tmpl.ptr<float>(0), tm.data(), tm.size() * 4);
@@ -91,28 +41,24 @@ int main(int argc, char** argv)
             std::vector<rcr::DeviceFrame> frames;
             size_t at = 0;
             for (int s = 0; s < S; ++s) {
-                uint8_t* p = upload(pixels.data() + at, (size_t)bytes[s], (size_t)(s % 4));     // misalignment 0 ... 3
-                at += (size_t)bytes[s];
-                frames.push_back(rcr::DeviceFrame{p, W[s], H[s], stride[s], fmt[s]});
+                uint8_t* p = mem.upload(pixels.data() + at, (size_t)sc.bytes[s], (size_t)(s % 4));     // misalignment 0 ... 3
+                at += (size_t)sc.bytes[s];
+                frames.push_back(rcr::DeviceFrame{p, sc.W[s], sc.H[s], sc.stride[s], sc.fmt[s]});
             }
             rcr::paste_result res;
-            if (pass == 0) res = fit = rcr::paste_crops_tensor(model, frames, x, {}, lm, tmpl, cw, ch, spec, in_dev, mask);
+            if (pass == 0) res = fit = rcr::paste_crops_tensor(model, frames, x, {}, sc.lm, tmpl, cw, ch, spec, in_dev, mask);
             else res = rcr::paste_crops_tensor(fit.matrices, {}, cw, ch, spec, in_dev, frames, mask);
             std::vector<uint8_t> host(pixels.size());
             at = 0;
             for (int s = 0; s < S; ++s) {
-                if (hip.memcpy_(host.data() + at, frames[s].data, (size_t)bytes[s], 2 /* device to host */) != 0) throw std::runtime_error("hipMemcpy failed");
-                at += (size_t)bytes[s];
+                mem.download(host.data() + at, frames[s].data, (size_t)sc.bytes[s]);
+                at += (size_t)sc.bytes[s];
             }
             write_bytes(dir + (pass == 0 ? "/fit.u8" : "/at.u8"), host.data(), host.size());
             write_bytes(dir + (pass == 0 ? "/flags.i32" : "/flags_at.i32"), res.flags.data(), (size_t)S * 4);
         }
         write_bytes(dir + "/mats.f32", fit.matrices.ptr<float>(0), (size_t)S * 6 * 4);
-        for (void* d : allocations) hip.free_(d);
         std::printf("%d rows of %d x %d pasted twice\n", S, cw, ch);
         return 0;
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
+    });
 }

@@ -8,45 +8,9 @@
 // writes detect_mat.f32, detect_dev.f32, track_mat.f32, track_dev.f32 (the rows after frame T - 1) and exits 1 when they differ
 #include "rcr/tracker.hpp"
 
-#include <cstdio>
-#include <cstring>
-#include <dlfcn.h>
-#include <fstream>
+#include "gpu_driver.hpp"
 
 using cv::Mat;
-
-// the three runtime calls the driver needs, taken from the HIP runtime that libsdm_hip.so has already brought into the process
-// (built with g++, no HIP headers)
-struct Hip {
-    int (*malloc_)(void**, size_t) = nullptr;
-    int (*free_)(void*) = nullptr;
-    int (*memcpy2d)(void*, size_t, const void*, size_t, size_t, size_t, int) = nullptr;
-    Hip()
-    {
-        malloc_ = (int (*)(void**, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
-        free_ = (int (*)(void*))dlsym(RTLD_DEFAULT, "hipFree");
-        memcpy2d = (int (*)(void*, size_t, const void*, size_t, size_t, size_t, int))dlsym(RTLD_DEFAULT, "hipMemcpy2D");
-        if (!malloc_ || !free_ || !memcpy2d) throw std::runtime_error("the HIP runtime is not loaded");
-    }
-};
-
-template <class T>
-static std::vector<T> read_all(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    const size_t n = (size_t)f.tellg();
-    f.seekg(0);
-    std::vector<T> v(n / sizeof(T));
-    f.read((char*)v.data(), (std::streamsize)n);
-    return v;
-}
-
-static void write_mat(const std::string& path, const Mat& m)
-{
-    std::ofstream f(path, std::ios::binary);
-    for (int r = 0; r < m.rows; ++r) f.write((const char*)m.ptr<float>(r), (std::streamsize)m.cols * 4);
-}
 
 static bool same_bits(const Mat& a, const Mat& b)
 {
@@ -58,9 +22,7 @@ static bool same_bits(const Mat& a, const Mat& b)
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: frames_gpu <dir>\n"); return 2; }
-    const std::string dir = argv[1];
-    try {
+    return driver_main(argc, argv, "frames_gpu", [](const std::string& dir) {
         std::ifstream meta(dir + "/meta.txt");
         int S, T;
         meta >> S >> T;
@@ -76,25 +38,21 @@ int main(int argc, char** argv)
         std::vector<int> ids(S);
         for (int s = 0; s < S; ++s) ids[s] = s;
 
-        rcr::tracker tr_mat(model, S), tr_dev(model, S);      // (the device is up from here on: each tracker owns a handle)
-        Hip hip;
+        DeviceMemory mem;
+        rcr::tracker tr_mat(model, S), tr_dev(model, S);
         // every frame on the host as cv::Mat views, and on the device with a pitch of its own (row + 5 + s bytes: odd row starts)
         std::vector<std::vector<Mat>> mats(T);
         std::vector<std::vector<rcr::DeviceFrame>> devs(T);
-        std::vector<void*> allocations;
         size_t at = 0;
         for (int t = 0; t < T; ++t)
             for (int s = 0; s < S; ++s) {
                 uint8_t* p = pixels.data() + at;
                 at += (size_t)H[s] * W[s] * 3;
                 mats[t].push_back(Mat(H[s], W[s], CV_8UC3, p));
-                const size_t pitch = (size_t)W[s] * 3 + 5 + s;
-                void* d = nullptr;
-                if (hip.malloc_(&d, pitch * H[s]) != 0) throw std::runtime_error("hipMalloc failed");
-                allocations.push_back(d);
-                if (hip.memcpy2d(d, pitch, p, (size_t)W[s] * 3, (size_t)W[s] * 3, (size_t)H[s], 1 /* host to device */) != 0)
-                    throw std::runtime_error("hipMemcpy2D failed");
-                devs[t].push_back(rcr::DeviceFrame{d, W[s], H[s], (int)pitch, SDM_FRAME_BGR});
+                const size_t row = (size_t)W[s] * 3, pitch = row + 5 + s;
+                std::vector<uint8_t> pitched(pitch * H[s], 0);
+                for (int y = 0; y < H[s]; ++y) std::memcpy(pitched.data() + y * pitch, p + y * row, row);
+                devs[t].push_back(rcr::DeviceFrame{mem.upload(pitched.data(), pitched.size()), W[s], H[s], (int)pitch, SDM_FRAME_BGR});
             }
 
         const Mat rows_mat = model.detect_batch(mats[0], b0);
@@ -112,11 +70,7 @@ int main(int argc, char** argv)
         }
         write_mat(dir + "/track_mat.f32", tr_mat.rows());
         write_mat(dir + "/track_dev.f32", tr_dev.rows());
-        for (void* d : allocations) hip.free_(d);
         std::printf("streams %d, frames %d: DeviceFrame overloads %s the cv::Mat overloads\n", S, T, ok ? "equal" : "DIFFER from");
         return ok ? 0 : 1;
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
+    });
 }

@@ -7,8 +7,8 @@
 //   usage: landmark_detection_gpu <dir>
 #include "rcr/model.hpp"
 
-#include <cstdio>
-#include <fstream>
+#include "gpu_driver.hpp"
+
 #include <iostream>
 
 using cv::Mat;
@@ -16,28 +16,9 @@ using std::vector;
 using namespace superviseddescent;
 using HogTransform = rcr::FixedHogTransform;      // landmark_detection.cpp:158
 
-template <class T>
-static std::vector<T> read_all(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    const size_t n = (size_t)f.tellg();
-    f.seekg(0);
-    std::vector<T> v(n / sizeof(T));
-    f.read((char*)v.data(), (std::streamsize)n);
-    return v;
-}
-static void write_mat(const std::string& path, const Mat& m)
-{
-    std::ofstream f(path, std::ios::binary);
-    for (int r = 0; r < m.rows; ++r) f.write((const char*)m.ptr<float>(r), (std::streamsize)m.cols * 4);
-}
-
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: landmark_detection_gpu <dir>\n"); return 2; }
-    const std::string dir = argv[1];
-    try {
+    return driver_main(argc, argv, "landmark_detection_gpu", [](const std::string& dir) {
         int n_img, H, W, L;
         std::ifstream(dir + "/meta.txt") >> n_img >> H >> W >> L;
         auto img_bytes = read_all<uint8_t>(dir + "/images.u8");
@@ -93,8 +74,5 @@ int main(int argc, char** argv)
         write_mat(dir + "/cpp_feat_row2.f32", hog(x0.row(2), 0, 2));
         std::cout << "done" << std::endl;
         return 0;
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "landmark_detection_gpu: %s\n", e.what());
-        return 1;
-    }
+    });
 }

@@ -6,37 +6,18 @@
 //   usage: rcr_gpu <dir>
 #include "rcr/model.hpp"
 
+#include "gpu_driver.hpp"
+
 #include <cmath>
-#include <cstdio>
-#include <fstream>
 #include <iostream>
 #include <sstream>
 
 using cv::Mat;
 using namespace superviseddescent;
 
-template <class T>
-static std::vector<T> read_all(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    const size_t n = (size_t)f.tellg();
-    f.seekg(0);
-    std::vector<T> v(n / sizeof(T));
-    f.read((char*)v.data(), (std::streamsize)n);
-    return v;
-}
-static void write_mat(const std::string& path, const Mat& m)
-{
-    std::ofstream f(path, std::ios::binary);
-    for (int r = 0; r < m.rows; ++r) f.write((const char*)m.ptr<float>(r), (std::streamsize)m.cols * 4);
-}
-
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: rcr_gpu <dir>\n"); return 2; }
-    const std::string dir = argv[1];
-    try {
+    return driver_main(argc, argv, "rcr_gpu", [](const std::string& dir) {
         // meta: n_images H W N L n_levels, then per level: variant cells cell bins rel, then ids..., right eye ids, left eye ids
         std::ifstream meta(dir + "/meta.txt");
         int n_img, H, W, N, L, n_levels, n_test;
@@ -176,9 +157,6 @@ int main(int argc, char** argv)
             if (!(q.rank == 1 && q.full_rank == 2)) throw std::runtime_error("ColPivHouseholderQRSolver: rank of a singular system");
         }
         std::printf("rcr_gpu ok\n");
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "rcr_gpu failed: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

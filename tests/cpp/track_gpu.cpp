@@ -9,28 +9,13 @@
 // writes <dir>/cpp_landmarks.f32 (T x S x 2L, the rows of every step) and <dir>/cpp_lost.i32 (T x S masks)
 #include "rcr/tracker.hpp"
 
-#include <cstdio>
-#include <fstream>
+#include "gpu_driver.hpp"
 
 using cv::Mat;
 
-template <class T>
-static std::vector<T> read_all(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    const size_t n = (size_t)f.tellg();
-    f.seekg(0);
-    std::vector<T> v(n / sizeof(T));
-    f.read((char*)v.data(), (std::streamsize)n);
-    return v;
-}
-
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: track_gpu <dir>\n"); return 2; }
-    const std::string dir = argv[1];
-    try {
+    return driver_main(argc, argv, "track_gpu", [](const std::string& dir) {
         std::ifstream meta(dir + "/meta.txt");
         int S, T, H, W, capacity;
         meta >> S >> T >> H >> W >> capacity;
@@ -66,9 +51,6 @@ int main(int argc, char** argv)
         int tracked = 0;
         for (int s = 0; s < S; ++s) tracked += got.second[s] == rcr::tracker::tracked;
         std::printf("frames %d streams %d restarts %d tracked at the end %d\n", T, S, restarts, tracked);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

@@ -9,35 +9,13 @@
 // writes cpp_detect.f32 (n x 2L), cpp_mats.f32 (n x 6), cpp_flags.i32 (n), cpp_track.f32 (T x n x 2L), cpp_lost.i32 (T x n)
 #include "rcr/tracker.hpp"
 
-#include <cstdio>
-#include <fstream>
+#include "gpu_driver.hpp"
 
 using cv::Mat;
 
-template <class T>
-static std::vector<T> read_all(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    const size_t n = (size_t)f.tellg();
-    f.seekg(0);
-    std::vector<T> v(n / sizeof(T));
-    f.read((char*)v.data(), (std::streamsize)n);
-    return v;
-}
-
-template <class T>
-static void write_all(const std::string& path, const T* p, size_t count)
-{
-    std::ofstream f(path, std::ios::binary);
-    f.write((const char*)p, (std::streamsize)(count * sizeof(T)));
-}
-
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: upright_gpu <dir>\n"); return 2; }
-    const std::string dir = argv[1];
-    try {
+    return driver_main(argc, argv, "upright_gpu", [](const std::string& dir) {
         std::ifstream meta(dir + "/meta.txt");
         int n, T, chip, guard;
         meta >> n >> T >> chip >> guard;
@@ -61,9 +39,9 @@ int main(int argc, char** argv)
 
         Mat x = model.detect_batch_upright(images_of(0), rects, rolls, chip, guard);
         if (x.rows != n || !x.isContinuous()) throw std::runtime_error("detect_batch_upright returned the wrong rows");
-        write_all(dir + "/cpp_detect.f32", x.ptr<float>(0), (size_t)x.rows * x.cols);
-        write_all(dir + "/cpp_mats.f32", model.upright_matrices().ptr<float>(0), (size_t)n * 6);
-        write_all(dir + "/cpp_flags.i32", model.upright_flags().data(), (size_t)n);
+        write_bytes(dir + "/cpp_detect.f32", x.ptr<float>(0), (size_t)x.rows * x.cols * 4);
+        write_bytes(dir + "/cpp_mats.f32", model.upright_matrices().ptr<float>(0), (size_t)n * 6 * 4);
+        write_bytes(dir + "/cpp_flags.i32", model.upright_flags().data(), (size_t)n * 4);
 
         rcr::tracker tr(model, n);
         tr.upright(chip, guard);
@@ -83,9 +61,6 @@ int main(int argc, char** argv)
             if (!again.empty()) tr.start(again, again_boxes, again_rolls);
         }
         std::printf("upright detect of %d rows, %d upright tracker steps, %d restarts\n", n, T, lost);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

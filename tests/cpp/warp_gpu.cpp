@@ -9,83 +9,35 @@
 // writes f16.bin, u8.bin, mats.f32, flags.i32, labels.u8, tmpl.f32, tri.i32
 #include "rcr/warp.hpp"
 
-#include <cstdio>
-#include <dlfcn.h>
-#include <fstream>
-
-// the runtime calls the driver needs, taken from the HIP runtime that libsdm_hip.so has already brought into the process
-struct Hip {
-    int (*malloc_)(void**, size_t) = nullptr;
-    int (*free_)(void*) = nullptr;
-    int (*memcpy_)(void*, const void*, size_t, int) = nullptr;
-    Hip()
-    {
-        malloc_ = (int (*)(void**, size_t))dlsym(RTLD_DEFAULT, "hipMalloc");
-        free_ = (int (*)(void*))dlsym(RTLD_DEFAULT, "hipFree");
-        memcpy_ = (int (*)(void*, const void*, size_t, int))dlsym(RTLD_DEFAULT, "hipMemcpy");
-        if (!malloc_ || !free_ || !memcpy_) throw std::runtime_error("the HIP runtime is not loaded");
-    }
-};
-
-template <class T>
-static std::vector<T> read_all(const std::string& path)
-{
-    std::ifstream f(path, std::ios::binary | std::ios::ate);
-    if (!f) throw std::runtime_error("cannot open " + path);
-    const size_t n = (size_t)f.tellg();
-    f.seekg(0);
-    std::vector<T> v(n / sizeof(T));
-    f.read((char*)v.data(), (std::streamsize)n);
-    return v;
-}
-
-static void write_bytes(const std::string& path, const void* p, size_t n)
-{
-    std::ofstream f(path, std::ios::binary);
-    f.write((const char*)p, (std::streamsize)n);
-}
+#include "gpu_driver.hpp"
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: warp_gpu <dir>\n"); return 2; }
-    const std::string dir = argv[1];
-    try {
-        std::ifstream meta(dir + "/meta.txt");
-        int S, ow, oh, K;
-        meta >> S >> ow >> oh >> K;
-        std::vector<int> lm(K);
-        for (int& v : lm) meta >> v;
-        std::vector<int> fmt(S), W(S), H(S), stride(S), bytes(S), uv(S);
-        for (int s = 0; s < S; ++s) meta >> fmt[s] >> W[s] >> H[s] >> stride[s] >> bytes[s] >> uv[s];
+    return driver_main(argc, argv, "warp_gpu", [](const std::string& dir) {
+        const Scenario sc(dir + "/meta.txt", 1);                                    // tail: uv_offset
+        const int S = sc.S, ow = sc.w, oh = sc.h, K = (int)sc.lm.size();
         rcr::detection_model model = rcr::load_detection_model(dir + "/model.bin");
         auto pixels = read_all<uint8_t>(dir + "/frames.u8");
         auto rows = read_all<float>(dir + "/rows.f32");
         const int L = (int)model.get_landmark_ids().size();
         if ((int)rows.size() != S * 2 * L) throw std::runtime_error("scenario size mismatch");
-        superviseddescent::hip::Handle first(superviseddescent::hip::device());     // (the device is up from here on)
-        Hip hip;
+        DeviceMemory mem;
         std::vector<rcr::DeviceFrame> frames;
         std::vector<const void*> chroma;
-        std::vector<void*> allocations;
         size_t at = 0;
         for (int s = 0; s < S; ++s) {
-            void* d = nullptr;
-            if (hip.malloc_(&d, (size_t)bytes[s] + 3) != 0) throw std::runtime_error("hipMalloc failed");
-            allocations.push_back(d);
-            uint8_t* p = (uint8_t*)d + s % 4;                                       // source misalignment 0 ... 3
-            if (hip.memcpy_(p, pixels.data() + at, (size_t)bytes[s], 1 /* host to device */) != 0) throw std::runtime_error("hipMemcpy failed");
-            at += (size_t)bytes[s];
-            frames.push_back(rcr::DeviceFrame{p, W[s], H[s], stride[s], fmt[s]});
-            chroma.push_back(uv[s] >= 0 ? p + uv[s] : nullptr);
+            uint8_t* p = mem.upload(pixels.data() + at, (size_t)sc.bytes[s], (size_t)(s % 4));      // source misalignment 0 ... 3
+            at += (size_t)sc.bytes[s];
+            frames.push_back(rcr::DeviceFrame{p, sc.W[s], sc.H[s], sc.stride[s], sc.fmt[s]});
+            const int uv = sc.tail[s][0];
+            chroma.push_back(uv >= 0 ? p + uv : nullptr);
         }
         cv::Mat x(S, 2 * L, CV_32FC1);
         std::memcpy(x.ptr<float>(0), rows.data(), rows.size() * 4);
         const size_t n = (size_t)S * 3 * ow * oh;
-        void* out = nullptr;
-        if (hip.malloc_(&out, n * 2) != 0) throw std::runtime_error("hipMalloc failed");
-        allocations.push_back(out);
+        void* out = mem.alloc(n * 2);
 
-        const rcr::WarpMesh mesh = rcr::WarpMesh::of_mean(model.get_mean(), lm, ow, oh);
+        const rcr::WarpMesh mesh = rcr::WarpMesh::of_mean(model.get_mean(), sc.lm, ow, oh);
         const int T = mesh.n_triangles();
         write_bytes(dir + "/tmpl.f32", mesh.tmpl.ptr<float>(0), (size_t)K * 2 * 4);
         write_bytes(dir + "/tri.i32", mesh.triangles.data(), (size_t)T * 3 * 4);
@@ -94,7 +46,7 @@ int main(int argc, char** argv)
         f16.normalise(mean, sd);
         auto a = rcr::warped_crops_tensor(model, frames, x, {}, mesh, f16, out, chroma);
         std::vector<uint8_t> host(n * 2);
-        if (hip.memcpy_(host.data(), out, n * 2, 2 /* device to host */) != 0) throw std::runtime_error("hipMemcpy failed");
+        mem.download(host.data(), out, n * 2);
         write_bytes(dir + "/f16.bin", host.data(), n * 2);
         write_bytes(dir + "/mats.f32", a.matrices.ptr<float>(0), (size_t)S * T * 6 * 4);
         write_bytes(dir + "/flags.i32", a.flags.data(), (size_t)S * 4);
@@ -103,13 +55,9 @@ int main(int argc, char** argv)
         rcr::TensorSpec u8;
         u8.dtype = SDM_ALIGN_U8; u8.layout = SDM_ALIGN_NHWC; u8.order = SDM_ALIGN_ORDER_BGR;
         rcr::warped_crops_tensor(model, frames, x, {}, mesh, u8, out, chroma);
-        if (hip.memcpy_(host.data(), out, n, 2) != 0) throw std::runtime_error("hipMemcpy failed");
+        mem.download(host.data(), out, n);
         write_bytes(dir + "/u8.bin", host.data(), n);
-        for (void* d : allocations) hip.free_(d);
         std::printf("%d rows, %d triangles, %d x %d crops written\n", S, T, ow, oh);
         return 0;
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "error: %s\n", e.what());
-        return 1;
-    }
+    });
 }

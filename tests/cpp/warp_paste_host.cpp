@@ -15,29 +15,10 @@
 //               n_rows x 4 int32 box, the frame's bytes after the rows were pasted in descending order, and after ascending order
 #include "../../superviseddescent_amd/csrc/sdm_warp_paste_device.h"
 
-#include <cstdio>
+#include "host_case.hpp"
+
 #include <cstring>
-#include <fstream>
-#include <memory>
 #include <vector>
-
-template <class T>
-static T get(std::ifstream& f)
-{
-    T v;
-    f.read((char*)&v, sizeof(T));
-    if (!f) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
-    return v;
-}
-
-static std::unique_ptr<uint8_t[]> block(std::ifstream& f, int& bytes)
-{
-    bytes = get<int>(f);
-    std::unique_ptr<uint8_t[]> p(new uint8_t[bytes > 0 ? bytes : 1]);
-    f.read((char*)p.get(), bytes);
-    if (!f) { std::fprintf(stderr, "short case file\n"); std::exit(2); }
-    return p;
-}
 
 int main(int argc, char** argv)
 {
@@ -51,12 +32,11 @@ int main(int argc, char** argv)
         PasteCropDev c{};
         c.cw = get<int>(in); c.ch = get<int>(in); c.dtype = get<int>(in);
         const int layout = get<int>(in);
-        c.channels = get<int>(in); c.t.order = get<int>(in); c.t.gray_shift = get<int>(in);
+        c.channels = get<int>(in); c.t.order = get<int>(in);
+        align_gray_weights(get<int>(in), c.t);
         const int rows_n = get<int>(in), alpha_mode = get<int>(in), K = get<int>(in), T = get<int>(in);
         for (int e = 0; e < 3; ++e) c.t.scale[e] = get<float>(in);
         for (int e = 0; e < 3; ++e) c.t.bias[e] = get<float>(in);
-        if (c.t.gray_shift == 14) { c.t.wb = 1868; c.t.wg = 9617; c.t.wr = 4899; }
-        else { c.t.wb = 3735; c.t.wg = 19235; c.t.wr = 9798; }
         std::vector<WarpTri> tri((size_t)T);
         for (WarpTri& t : tri) { t.ia = get<int>(in); t.ib = get<int>(in); t.ic = get<int>(in); t.pad = 0; }
         for (WarpTri& t : tri) {
@@ -68,10 +48,7 @@ int main(int argc, char** argv)
         int lb, tb, ab, fb;
         const std::unique_ptr<uint8_t[]> labels = block(in, lb), tensor = block(in, tb), alpha = block(in, ab), frame = block(in, fb);
         c.in = tensor.get(); c.alpha = alpha_mode ? alpha.get() : nullptr;
-        c.an = alpha_mode == 2 ? (long long)c.cw * c.ch : 0;
-        c.sn = (long long)c.channels * c.cw * c.ch;
-        if (layout == SDM_ALIGN_NCHW) { c.sc = c.cw * c.ch; c.sy = c.cw; c.sx = 1; }
-        else { c.sc = 1; c.sy = c.cw * c.channels; c.sx = c.channels; }
+        paste_crop_layout(c, layout, alpha_mode == 2);
         f.p = frame.get(); f.row_begin = 0; f.row_end = rows_n;
         std::vector<WarpPasteRow> rows((size_t)rows_n);
         std::vector<WarpPasteTri> recs((size_t)rows_n * T);

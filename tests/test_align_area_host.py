@@ -1,11 +1,9 @@
 """sdm_align_crops_tensor_filtered without a device: the S rule, the offset tables, what area sampling does to 1-pixel stripes and how
 close it comes to the box integral of the bilinear surface, and the kernel's per-pixel code compiled for the host
-(tests/cpp/align_area_host.cpp, -fsanitize=address,undefined, planes of exactly the frames' bytes) against the numpy restatement
-(tests/align_area_ref.py) on the device tests' frame sets."""
+(tests/cpp/align_area_host.cpp, address and undefined-behaviour sanitizers, planes of exactly the frames' bytes) against the numpy
+restatement (tests/align_area_ref.py) on the device tests' frame sets."""
 import ctypes
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,9 +13,9 @@ import align_area_ref as R
 import align_ref as A
 import align_tensor_cases as K
 import align_tensor_ref as T
+import cpp_build as B
 from superviseddescent_amd import _lib, align_filter
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 
 
@@ -136,10 +134,7 @@ def test_host_build_of_the_pixel_code_under_sanitizers(tmp_path):
     """the device functions, compiled for the host with their own main, on planes of exactly the frames' bytes.  The host program also
     runs every segment through the 64-bit offset path (WIDE) and compares: no frame set of the device tests has a plane beyond INT_MAX
     bytes, so this is where that path is covered."""
-    exe = str(tmp_path / "align_area_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan",
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "align_area_host.cpp"), "-o", exe])
+    exe = B.host_program("align_area_host", tmp_path)
     scale, bias = np.array([1 / 58.395, 1 / 57.12, 1 / 57.375], f32), np.array([-2.1179, -2.0357, -1.8044], f32)
     cases, blob, seen = [], [b""], set()
     for specs, seed in ((K.RAGGED, 11), (K.NV12, 12)):
@@ -161,10 +156,7 @@ def test_host_build_of_the_pixel_code_under_sanitizers(tmp_path):
     assert seen >= {(fmt, S) for fmt in range(6) for S in (1, 2, 3, 4, 5, 16)}          # every format at every S
     blob[0] = struct.pack("<i", len(cases))
     (tmp_path / "cases.bin").write_bytes(b"".join(blob))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, env=env, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
+    B.run(exe, [tmp_path / "cases.bin", tmp_path / "out.bin"], 300, sanitized=True)
     got = np.fromfile(str(tmp_path / "out.bin"), np.uint8)
     at = 0
     for frame, M, w, h, S in cases:

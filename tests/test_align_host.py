@@ -3,11 +3,11 @@ rcr/alignment.hpp, the default template, and the host restatement (tests/align_r
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 
 import align_ref as A
+import cpp_build as B
 from superviseddescent_amd import _lib, alignment_template, ibug
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,8 +32,7 @@ def test_alignment_header_compiles(tmp_path):
                    '    cv::Mat t = rcr::alignment_template(mean, {0, 1}, 112, 96);\n'
                    '    return t.rows == 2 ? 0 : 1;\n'
                    '}\n')
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+    B.gpu_driver("t", tmp_path, src=src, opt=(), link=False)
 
 
 def test_alignment_header_refuses_source_types_it_cannot_hold(tmp_path, built):
@@ -49,13 +48,8 @@ def test_alignment_header_refuses_source_types_it_cannot_hold(tmp_path, built):
                    '    catch (const std::runtime_error& e) { std::printf("%s\\n", e.what()); return 0; }\n'
                    '    return 1;\n'
                    '}\n')
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    exe = str(tmp_path / "t")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"), str(src), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib])
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0 and "CV_8UC1 or CV_8UC3" in out.stdout, out.stdout + out.stderr
+    out = B.run(B.gpu_driver("t", tmp_path, src=src, opt=()), [], 60)
+    assert "CV_8UC1 or CV_8UC3" in out.stdout, out.stdout + out.stderr
 
 
 def test_default_template():

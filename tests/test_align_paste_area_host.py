@@ -1,13 +1,11 @@
 """sdm_align_paste_tensor_filtered without a device: the kernel's per-pixel code and its prepare stage compiled for the host
-(tests/cpp/align_paste_area_host.cpp, -fsanitize=address,undefined, every frame, tensor and opacity map in a heap block of exactly its
-bytes) against the numpy restatement (tests/paste_area_ref.py), bit for bit on every byte the frame owns; that the working footprint and
-the box hold every pixel the formula touches; a known answer that needs neither implementation; the aliasing the filter is for; the
-choice of S; the Python argument handling."""
+(tests/cpp/align_paste_area_host.cpp, address and undefined-behaviour sanitizers, every frame, tensor and opacity map in a heap block of
+exactly its bytes) against the numpy restatement (tests/paste_area_ref.py), bit for bit on every byte the frame owns; that the working
+footprint and the box hold every pixel the formula touches; a known answer that needs neither implementation; the aliasing the filter
+is for; the choice of S; the Python argument handling."""
 import ctypes
 import inspect
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,13 +13,13 @@ import pytest
 import align_ref as A
 import align_area_ref as R
 import align_tensor_ref as T
+import cpp_build as B
 import paste_area_cases as D
 import paste_area_ref as Q
 import paste_cases as C
 import paste_ref as P
 from superviseddescent_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 SPEC = ("layout", "channels", "order", "gray_shift")
 
@@ -82,10 +80,7 @@ def restate(c):
 def ran(tmp_path_factory):
     """the host program built under the sanitizers and run ONCE, as a child process, on every case: [(case, its output)]"""
     tmp = tmp_path_factory.mktemp("paste_area")
-    exe = str(tmp / "align_paste_area_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "align_paste_area_host.cpp"), "-o", exe])
+    exe = B.host_program("align_paste_area_host", tmp)
     cases = D.host_cases() + extra_cases()
     blob = [struct.pack("<i", len(cases))]
     for c in cases:
@@ -98,10 +93,7 @@ def ran(tmp_path_factory):
                     + struct.pack("<i", c["x"].nbytes) + c["x"].tobytes() + struct.pack("<i", len(a)) + a
                     + struct.pack("<i", c["frame"].size) + c["frame"].tobytes())
     (tmp / "cases.bin").write_bytes(b"".join(blob))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(tmp / "cases.bin"), str(tmp / "out.bin")], capture_output=True, text=True, env=env, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
+    B.run(exe, [tmp / "cases.bin", tmp / "out.bin"], 300, sanitized=True)
     got = np.fromfile(str(tmp / "out.bin"), np.uint8)
     at, out = 0, []
     for c in cases:

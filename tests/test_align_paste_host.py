@@ -1,11 +1,9 @@
 """sdm_align_paste_tensor without a device: the kernel's per-pixel code and its prepare stage compiled for the host
-(tests/cpp/align_paste_host.cpp, -fsanitize=address,undefined, every frame, tensor and opacity map in a heap block of exactly its bytes)
-against the numpy restatement (tests/paste_ref.py), bit for bit on every byte the frame owns; the restatement's own blend identities;
-the Python argument handling."""
+(tests/cpp/align_paste_host.cpp, address and undefined-behaviour sanitizers, every frame, tensor and opacity map in a heap block of
+exactly its bytes) against the numpy restatement (tests/paste_ref.py), bit for bit on every byte the frame owns; the restatement's own
+blend identities; the Python argument handling."""
 import itertools
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,11 +11,11 @@ import pytest
 import align_ref as A
 import align_tensor_cases as K
 import align_tensor_ref as T
+import cpp_build as B
 import paste_cases as C
 import paste_ref as P
 from superviseddescent_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 COMBOS = list(itertools.product(("uint8", "float16", "float32"), ("nhwc", "nchw"), (1, 3), ("bgr", "rgb")))
 
@@ -79,10 +77,7 @@ def host_cases():
 
 
 def test_host_build_of_the_pixel_code_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "align_paste_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan",
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "align_paste_host.cpp"), "-o", exe])
+    exe = B.host_program("align_paste_host", tmp_path)
     cases = host_cases()
     blob = [struct.pack("<i", len(cases))]
     for c in cases:
@@ -95,10 +90,7 @@ def test_host_build_of_the_pixel_code_under_sanitizers(tmp_path):
                     + struct.pack("<i", c["x"].nbytes) + c["x"].tobytes() + struct.pack("<i", len(a)) + a
                     + struct.pack("<i", c["frame"].size) + c["frame"].tobytes())
     (tmp_path / "cases.bin").write_bytes(b"".join(blob))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, env=env, timeout=120)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
+    B.run(exe, [tmp_path / "cases.bin", tmp_path / "out.bin"], 120, sanitized=True)
     got = np.fromfile(str(tmp_path / "out.bin"), np.uint8)
     at, seen, touched, formats = 0, 0, 0, set()
     for k, c in enumerate(cases):

@@ -1,19 +1,18 @@
 """sdm_align_paste_tensor_nv12 without a device: the block ownership rule and the luma / chroma arithmetic compiled for the host
-(tests/cpp/align_paste_nv12_host.cpp, -fsanitize=address,undefined, every plane, tensor and opacity map in a heap block of exactly its
-bytes, every (row, block) in a shuffled order) against the numpy restatement (tests/paste_nv12_ref.py), bit for bit in both planes, pitch
-padding included; which bytes are stored; the restatement against the two it is built on and against a block worked by hand; the round
-trip's deviation; the Python argument handling."""
+(tests/cpp/align_paste_nv12_host.cpp, address and undefined-behaviour sanitizers, every plane, tensor and opacity map in a heap block of
+exactly its bytes, every (row, block) in a shuffled order) against the numpy restatement (tests/paste_nv12_ref.py), bit for bit in both
+planes, pitch padding included; which bytes are stored; the restatement against the two it is built on and against a block worked by
+hand; the round trip's deviation; the Python argument handling."""
 import ctypes
 import inspect
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_ref as A
 import align_tensor_ref as T
+import cpp_build as B
 import paste_area_ref as Q
 import paste_cases as C
 import paste_nv12_cases as V
@@ -21,7 +20,6 @@ import paste_nv12_ref as N
 import paste_ref as P
 from superviseddescent_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 
 
@@ -66,10 +64,7 @@ def restate(c):
 def ran(tmp_path_factory):
     """the host program built under the sanitizers and run ONCE, as a child process, on every case: [(case, its output)]"""
     tmp = tmp_path_factory.mktemp("paste_nv12")
-    exe = str(tmp / "align_paste_nv12_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "align_paste_nv12_host.cpp"), "-o", exe])
+    exe = B.host_program("align_paste_nv12_host", tmp)
     cases = host_cases()
     blob = [struct.pack("<i", len(cases))]
     for c in cases:
@@ -83,10 +78,7 @@ def ran(tmp_path_factory):
                     + struct.pack("<i", c["x"].nbytes) + c["x"].tobytes() + struct.pack("<i", len(a)) + a
                     + struct.pack("<i", c["Y"].size) + c["Y"].tobytes() + struct.pack("<i", c["UV"].size) + c["UV"].tobytes())
     (tmp / "cases.bin").write_bytes(b"".join(blob))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(tmp / "cases.bin"), str(tmp / "out.bin")], capture_output=True, text=True, env=env, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
+    B.run(exe, [tmp / "cases.bin", tmp / "out.bin"], 300, sanitized=True)
     got = np.fromfile(str(tmp / "out.bin"), np.uint8)
     at, out = 0, []
     for c in cases:

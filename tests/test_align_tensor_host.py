@@ -1,18 +1,17 @@
 """sdm_align_crops_tensor without a device: the restated NV12 conversion over all 256^3 inputs, the element formula against float64,
 the Python argument handling on fake tensors, and the kernel's per-pixel code compiled for the host (tests/cpp/align_tensor_host.cpp,
--fsanitize=address,undefined, planes of exactly the frames' bytes) against the numpy restatement on the device tests' frame sets."""
-import os
+address and undefined-behaviour sanitizers, planes of exactly the frames' bytes) against the numpy restatement on the device tests'
+frame sets."""
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_tensor_cases as K
 import align_tensor_ref as T
+import cpp_build as B
 from superviseddescent_amd import _lib, align_tensor_spec
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 
 
@@ -116,10 +115,7 @@ def test_out_tensor_is_checked():
 
 def test_host_build_of_the_pixel_code_under_sanitizers(tmp_path):
     """the device functions, compiled for the host with their own main, on planes of exactly the frames' bytes"""
-    exe = str(tmp_path / "align_tensor_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan",
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "align_tensor_host.cpp"), "-o", exe])
+    exe = B.host_program("align_tensor_host", tmp_path)
     scale, bias = np.array([1 / 58.395, 1 / 57.12, 1 / 57.375], f32), np.array([-2.1179, -2.0357, -1.8044], f32)
     cases, blob = [], [b""]
     for specs, seed in ((K.RAGGED, 11), (K.NV12, 12)):
@@ -135,10 +131,7 @@ def test_host_build_of_the_pixel_code_under_sanitizers(tmp_path):
                 cases.append((K.host_frame(buf, f), M, w, h))
     blob[0] = struct.pack("<i", len(cases))
     (tmp_path / "cases.bin").write_bytes(b"".join(blob))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, env=env, timeout=120)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
+    B.run(exe, [tmp_path / "cases.bin", tmp_path / "out.bin"], 120, sanitized=True)
     got = np.fromfile(str(tmp_path / "out.bin"), np.uint8)
     at = 0
     for frame, M, w, h in cases:

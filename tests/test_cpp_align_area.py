@@ -1,7 +1,6 @@
 """The rcr::aligned_crops_tensor overload with an rcr::AlignFilter (tests/cpp/align_area_gpu.cpp): landmark rows of several scales on two
 ragged BGR DeviceFrames and one NV12 frame give the bytes and the S of the Python layer -- the same kernels behind the same C-ABI."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,31 +9,26 @@ import align_area_cases as C
 import align_area_ref as AR
 import align_tensor_cases as K
 import align_tensor_ref as T
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_build as B
 
 
 @pytest.mark.gpu
 def test_cpp_area_crops_match_python(built, tmp_path):
     import torch
-    from superviseddescent_amd import Context, HoGParam, _lib, ibug, model_io
+    from superviseddescent_amd import Context, HoGParam, _lib, ibug
     ids = ibug.RCR22_IDS
     L = len(ids)
     mean = ibug.select_mean(ids)
     params = [HoGParam(1, 5, 6, 4, 0.6)]
+    d = str(tmp_path)
     rng = np.random.default_rng(4321)
-    R = [rng.normal(0, 3e-3, (L * p.patch_dim + 1, 2 * L)).astype(np.float32) for p in params]
+    B.write_model(d, L, params, mean, ids, seed=rng)                     # (the similarities below draw on behind the regressors)
     buf, frames = K.place([(37, 29, T.BGR), (64, 48, T.BGR), (7, 5, T.NV12)], 13)
     lm = [3, 6, 9, 12, 15]
     w, h = 7, 7
     tmpl = (np.array([[0.2, 0.2], [0.8, 0.25], [0.5, 0.5], [0.3, 0.8], [0.75, 0.7]]) * (w - 1, h - 1)).astype(np.float32)
     sims = [C.similarity(f, w, h, s, rng) for f, s in zip(frames, (1.7, 4.5, 2.6))]
     x = K.landmark_rows(sims, tmpl, lm, L)
-    d = str(tmp_path)
-    model_io.save_detection_model(model_io.DetectionModelFile(
-        [model_io.RegressorRecord(r, 1, 1.5, False) for r in R], mean, ids,
-        [(p.vlhog_variant, p.num_cells, p.cell_size, p.num_bins, p.relative_patch_size) for p in params],
-        ibug.RIGHT_EYE_IDS, ibug.LEFT_EYE_IDS), os.path.join(d, "model.bin"))
     sizes = []
     with open(os.path.join(d, "frames.u8"), "wb") as f:
         for fr in frames:
@@ -46,22 +40,14 @@ def test_cpp_area_crops_match_python(built, tmp_path):
     with open(os.path.join(d, "meta.txt"), "w") as f:
         f.write(f"3 {w} {h} {len(lm)} " + " ".join(map(str, lm)) + "\n")
         f.write("".join(f"{fr['fmt']} {fr['w']} {fr['h']} {fr['stride']} {n}\n" for fr, n in zip(frames, sizes)))
-    exe = str(tmp_path / "align_area_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "align_area_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread", "-ldl"])
-    out = subprocess.run([exe, d], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    B.run(B.gpu_driver("align_area_gpu", tmp_path), [d], 300)
     # the Python layer on the same bytes
     c = Context(0)
     try:
         re_, le_ = ibug.eye_indices(ids)
         c.set_model_geometry(L, re_, le_, params)
         dev = torch.from_numpy(buf).cuda()
-        lst = [(dev.data_ptr() + fr["off"], fr["w"], fr["h"], fr["stride"], K.NAMES[fr["fmt"]]) for fr in frames]
+        lst = B.device_frames(dev, frames)
         c.set_frames_device(lst)
         c.set_sample_image_index(None)
         c.set_x(x)

@@ -3,30 +3,26 @@ tests/cpp/align_paste_nv12_gpu.cpp): landmark rows on NV12 DeviceFrames -- the U
 BGR one give, through the fit and through explicit matrices, filtered and plain, the bytes and the S of the Python layer on the same
 rows, tensor, opacity maps and frames -- the same kernel behind the same C-ABI --, and those are the restatement's."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_tensor_cases as K
 import align_tensor_ref as T
+import cpp_build as B
 import paste_area_cases as D
 import paste_area_ref as Q
 import paste_cases as C
 import paste_nv12_cases as V
 import paste_nv12_ref as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
 
 @pytest.mark.gpu
 def test_cpp_nv12_paste_matches_python(built, tmp_path):
     import torch
-    from superviseddescent_amd import Context, HoGParam, ibug, model_io
+    from superviseddescent_amd import Context, HoGParam, ibug
     from test_gpu_align_tensor import IDS as ids, L, LM, MEAN as mean, template
     params = [HoGParam(1, 5, 6, 4, 0.6)]
-    rng = np.random.default_rng(4321)
-    regs = [rng.normal(0, 3e-3, (L * p.patch_dim + 1, 2 * L)).astype(np.float32) for p in params]
     buf, frames = V.place([V.FRAMES[0], V.FRAMES[1], V.FRAMES[7], V.FRAMES[6]], 17)
     w, h, S = 16, 16, 4
     tmpl = template(w, h)
@@ -35,10 +31,7 @@ def test_cpp_nv12_paste_matches_python(built, tmp_path):
     y = C.tensor(S, w, h, "float16", "nchw", 3, 19)
     alpha = C.alpha_maps(S, w, h, 20, zero_band=True)
     d = str(tmp_path)
-    model_io.save_detection_model(model_io.DetectionModelFile(
-        [model_io.RegressorRecord(r, 1, 1.5, False) for r in regs], mean, ids,
-        [(p.vlhog_variant, p.num_cells, p.cell_size, p.num_bins, p.relative_patch_size) for p in params],
-        ibug.RIGHT_EYE_IDS, ibug.LEFT_EYE_IDS), os.path.join(d, "model.bin"))
+    B.write_model(d, L, params, mean, ids)
     meta = [f"{S} {w} {h} {len(LM)} " + " ".join(map(str, LM)) + "\n"]
 
     def planes_of(b):
@@ -62,15 +55,7 @@ def test_cpp_nv12_paste_matches_python(built, tmp_path):
     alpha.tofile(os.path.join(d, "alpha.u8"))
     with open(os.path.join(d, "meta.txt"), "w") as f:
         f.write("".join(meta))
-    exe = str(tmp_path / "align_paste_nv12_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "align_paste_nv12_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread", "-ldl"])
-    out = subprocess.run([exe, d], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    B.run(B.gpu_driver("align_paste_nv12_gpu", tmp_path), [d], 300)
     rd = lambda name, dt: np.fromfile(os.path.join(d, name), dt)
     c = Context(0)
     try:
@@ -79,9 +64,7 @@ def test_cpp_nv12_paste_matches_python(built, tmp_path):
 
         def fresh():
             dev = torch.from_numpy(full).cuda()
-            lst = [(dev.data_ptr() + fr["off"], fr["w"], fr["h"], fr["stride"], K.NAMES[fr["fmt"]]) for fr in frames]
-            chroma = [dev.data_ptr() + fr["uv_off"] if fr["fmt"] == T.NV12 and fr["separate"] else None for fr in frames]
-            return dev, lst, chroma
+            return dev, B.device_frames(dev, frames), B.device_chroma(dev, frames, only_separate=True)
         dev, lst, chroma = fresh()
         c.set_frames_device(lst)
         c.set_sample_image_index(None)

@@ -2,22 +2,22 @@
 tracker::step on BGR frames that are already on the device -- ragged sizes, odd pitches -- against the cv::Mat overloads on the same
 pixels, and against the Python layer: the same kernels, so the same bytes."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_build as B
 
 
 @pytest.mark.gpu
 def test_cpp_device_frames_match_the_mat_overloads(built, tmp_path):
-    from superviseddescent_amd import HoGParam, LinearRegressor, SupervisedDescentOptimiser, detection_model, ibug, model_io, synth
+    from superviseddescent_amd import HoGParam, LinearRegressor, SupervisedDescentOptimiser, detection_model, ibug, synth
     ids = ibug.RCR22_IDS
     mean = ibug.select_mean(ids)
     params = [HoGParam(1, 5, 6, 4, 0.6), HoGParam(1, 5, 4, 4, 0.4)]
+    d = str(tmp_path)
     rng = np.random.default_rng(1234)
-    R = [rng.normal(0, 3e-3, (len(ids) * p.patch_dim + 1, 2 * len(ids))).astype(np.float32) for p in params]
+    R = B.write_model(d, len(ids), params, mean, ids, seed=rng)              # (the colour channels below draw on behind the regressors)
     frames, _, boxes = synth.make_tracks(3, 2, seed=57)                      # frames x streams x H x W
     cut = ((slice(0, 230), slice(0, 256)), (slice(0, 256), slice(0, 241)), (slice(0, 199), slice(0, 233)))      # three sizes
     colour = []
@@ -29,11 +29,6 @@ def test_cpp_device_frames_match_the_mat_overloads(built, tmp_path):
             c[..., 1] = g
             row.append(c)
         colour.append(row)
-    d = str(tmp_path)
-    model_io.save_detection_model(model_io.DetectionModelFile(
-        [model_io.RegressorRecord(r, 1, 1.5, False) for r in R], mean, ids,
-        [(p.vlhog_variant, p.num_cells, p.cell_size, p.num_bins, p.relative_patch_size) for p in params],
-        ibug.RIGHT_EYE_IDS, ibug.LEFT_EYE_IDS), os.path.join(d, "model.bin"))
     with open(os.path.join(d, "frames.u8"), "wb") as f:
         for row in colour:
             for c in row:
@@ -41,15 +36,7 @@ def test_cpp_device_frames_match_the_mat_overloads(built, tmp_path):
     boxes[0].astype(np.int32).tofile(os.path.join(d, "boxes.i32"))
     with open(os.path.join(d, "meta.txt"), "w") as f:
         f.write("3 2\n" + "".join(f"{c.shape[0]} {c.shape[1]}\n" for c in colour[0]))
-    exe = str(tmp_path / "frames_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "frames_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread", "-ldl"])
-    out = subprocess.run([exe, d], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    B.run(B.gpu_driver("frames_gpu", tmp_path), [d], 300)
 
     def rd(name):
         return np.fromfile(os.path.join(d, name), np.float32).reshape(3, 2 * len(ids))

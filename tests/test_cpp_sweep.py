@@ -2,12 +2,11 @@
 superviseddescent::RegulariserSweep, trained with train(..., callback, holdout), against the Python layer on the same scenario --
 the same kernels, so the same bytes."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_build as B
 
 
 @pytest.mark.gpu
@@ -29,15 +28,7 @@ def test_cpp_sweep_scenario_matches_python_layer(built, tmp_path):
             f.write(" ".join(str(v) for v in p) + "\n")
         f.write(" ".join(ids) + "\n" + " ".join(ibug.RIGHT_EYE_IDS) + "\n" + " ".join(ibug.LEFT_EYE_IDS) + "\n")
         f.write(f"1 1 {len(candidates)} " + " ".join(repr(c) for c in candidates) + "\n")
-    exe = str(tmp_path / "sweep_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "sweep_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread"])
-    out = subprocess.run([exe, d], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    B.run(B.gpu_driver("sweep_gpu", tmp_path), [d], 300)
 
     def rd(name):
         return np.fromfile(os.path.join(d, name), np.float32).reshape(-1, 2 * len(ids))

@@ -1,33 +1,28 @@
 """rcr::detection_model::detect_batch_upright and rcr::tracker's upright mode (tests/cpp/upright_gpu.cpp): rolled boxes on three frames
 of different sizes give the bits of the Python layer -- the same kernels behind the same C-ABI."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import cpp_build as B
 
 
 @pytest.mark.gpu
 def test_cpp_upright_matches_python(built, tmp_path):
-    from superviseddescent_amd import HoGParam, LinearRegressor, SupervisedDescentOptimiser, detection_model, ibug, model_io
+    from superviseddescent_amd import HoGParam, LinearRegressor, SupervisedDescentOptimiser, detection_model, ibug
     ids = ibug.RCR22_IDS
     L = len(ids)
     mean = ibug.select_mean(ids)
     params = [HoGParam(1, 5, 6, 4, 0.6)]
+    d = str(tmp_path)
     rng = np.random.default_rng(4321)
-    R = [rng.normal(0, 3e-3, (L * p.patch_dim + 1, 2 * L)).astype(np.float32) for p in params]
+    R = B.write_model(d, L, params, mean, ids, seed=rng)                 # (the frames below draw on behind the regressors)
     sizes = [(160, 120), (97, 131), (64, 64)]                            # (width, height)
     T, chip, guard = 4, 97, 12
     frames = [[rng.integers(0, 256, (h, w), dtype=np.uint8) for w, h in sizes] for _ in range(T)]
     boxes = np.array([[40, 30, 50, 50], [-20, 40, 60, 64], [10, 12, 40, 40]], np.int32)
     rolls = np.array([17.3, -90.0, 135.0], np.float32)
-    d = str(tmp_path)
-    model_io.save_detection_model(model_io.DetectionModelFile(
-        [model_io.RegressorRecord(r, 1, 1.5, False) for r in R], mean, ids,
-        [(p.vlhog_variant, p.num_cells, p.cell_size, p.num_bins, p.relative_patch_size) for p in params],
-        ibug.RIGHT_EYE_IDS, ibug.LEFT_EYE_IDS), os.path.join(d, "model.bin"))
     with open(os.path.join(d, "frames.u8"), "wb") as f:
         for fs in frames:
             for im in fs:
@@ -36,15 +31,7 @@ def test_cpp_upright_matches_python(built, tmp_path):
     rolls.tofile(os.path.join(d, "rolls.f32"))
     with open(os.path.join(d, "meta.txt"), "w") as f:
         f.write(f"3 {T} {chip} {guard}\n" + "".join(f"{w} {h}\n" for w, h in sizes))
-    exe = str(tmp_path / "upright_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "upright_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread", "-ldl"])
-    out = subprocess.run([exe, d], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    B.run(B.gpu_driver("upright_gpu", tmp_path), [d], 300)
     # the Python layer on the same bytes
     regs = [LinearRegressor() for _ in params]
     for r, x in zip(regs, R):

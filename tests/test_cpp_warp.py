@@ -2,36 +2,29 @@
 NV12 DeviceFrames of the device tests give the bytes of the Python layer on the same rows and frames -- the same kernels behind the
 same C-ABI --, and rcr::WarpMesh::of_mean is the Python layer's default mesh."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_tensor_cases as K
 import align_tensor_ref as T
+import cpp_build as B
 import warp_cases as W
 import warp_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.gpu
 def test_cpp_warped_crops_match_python(built, tmp_path):
     import torch
-    from superviseddescent_amd import Context, HoGParam, ibug, model_io
+    from superviseddescent_amd import Context, HoGParam, ibug
     ids, L, mean = W.IDS, W.L, W.MEAN
     params = [HoGParam(1, 5, 6, 4, 0.6)]
-    rng = np.random.default_rng(4321)
-    regs = [rng.normal(0, 3e-3, (L * p.patch_dim + 1, 2 * L)).astype(np.float32) for p in params]
     buf, frames = W.place()
     w, h = W.CROPS[1]
     idx, tmpl, tri = W.mesh_rcr22(w, h)
     x = W.rows_for(frames, range(4), idx, tmpl, w, h, 21)
     d = str(tmp_path)
-    model_io.save_detection_model(model_io.DetectionModelFile(
-        [model_io.RegressorRecord(r, 1, 1.5, False) for r in regs], mean, ids,
-        [(p.vlhog_variant, p.num_cells, p.cell_size, p.num_bins, p.relative_patch_size) for p in params],
-        ibug.RIGHT_EYE_IDS, ibug.LEFT_EYE_IDS), os.path.join(d, "model.bin"))
+    B.write_model(d, L, params, mean, ids)
     meta = [f"4 {w} {h} {len(idx)} " + " ".join(map(str, idx)) + "\n"]
     with open(os.path.join(d, "frames.u8"), "wb") as f:
         for fr in frames:
@@ -41,15 +34,7 @@ def test_cpp_warped_crops_match_python(built, tmp_path):
     x.tofile(os.path.join(d, "rows.f32"))
     with open(os.path.join(d, "meta.txt"), "w") as f:
         f.write("".join(meta))
-    exe = str(tmp_path / "warp_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "warp_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread", "-ldl"])
-    out = subprocess.run([exe, d], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    B.run(B.gpu_driver("warp_gpu", tmp_path), [d], 300)
     rd = lambda name, dt: np.fromfile(os.path.join(d, name), dt)
     # the C++ layer's default mesh is the Python layer's
     assert rd("tmpl.f32", np.uint32).tobytes() == tmpl.tobytes() and np.array_equal(rd("tri.i32", np.int32).reshape(-1, 3), tri)
@@ -58,8 +43,7 @@ def test_cpp_warped_crops_match_python(built, tmp_path):
         re_, le_ = ibug.eye_indices(ids)
         c.set_model_geometry(L, re_, le_, params)
         dev = torch.from_numpy(buf).cuda()
-        lst = [(dev.data_ptr() + fr["off"], fr["w"], fr["h"], fr["stride"], K.NAMES[fr["fmt"]]) for fr in frames]
-        chroma = [dev.data_ptr() + fr["uv_off"] if fr["fmt"] == T.NV12 else None for fr in frames]
+        lst, chroma = B.device_frames(dev, frames), B.device_chroma(dev, frames)
         c.set_frames_device(lst)
         c.set_sample_image_index(None)
         c.set_x(x)

@@ -3,17 +3,16 @@ the host restatement (tests/align_ref.py) applied to the device's own matrix, th
 similarities, borders, degenerate rows, row independence, the tracker hand-off, the device output path, argument limits, the C++
 layer, and the agreement of crops of rotated faces."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_ref as A
+import cpp_build as B
 from superviseddescent_amd import (Context, HoGParam, HogTransform, LinearRegressor, Regulariser, SdmError, SupervisedDescentOptimiser,
-                                   alignment_template, detection_model, ibug, model_io, synth)
+                                   alignment_template, detection_model, ibug, synth)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = ibug.RCR22_IDS
 L = len(IDS)
 RE, LE = ibug.eye_indices(IDS)
@@ -337,25 +336,14 @@ def test_cpp_alignment_matches_python(model, tmp_path):
     colour = np.random.default_rng(5).integers(0, 256, (S, H, W, 3), dtype=np.uint8)
     colour[..., 0] = frames[1]
     d = str(tmp_path)
-    model_io.save_detection_model(model_io.DetectionModelFile(
-        [model_io.RegressorRecord(r.x, 1, 1.5, False) for r in model.optimised_model.regressors], MEAN, IDS,
-        [(p.vlhog_variant, p.num_cells, p.cell_size, p.num_bins, p.relative_patch_size) for p in model.hog_params],
-        ibug.RIGHT_EYE_IDS, ibug.LEFT_EYE_IDS), os.path.join(d, "model.bin"))
+    B.write_model(d, L, model.hog_params, MEAN, IDS, regressors=[r.x for r in model.optimised_model.regressors])
     frames.tofile(os.path.join(d, "frames.u8"))
     colour.tofile(os.path.join(d, "colour.u8"))
     boxes.astype(np.int32).tofile(os.path.join(d, "boxes.i32"))
     LMl = [int(v) for v in LM]
     with open(os.path.join(d, "meta.txt"), "w") as f:
         f.write(f"{S} {n_frames} {H} {W} {len(LMl)} " + " ".join(map(str, LMl)) + "\n")
-    exe = str(tmp_path / "align_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "align_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread"])
-    out = subprocess.run([exe, d], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    B.run(B.gpu_driver("align_gpu", tmp_path), [d], 300)
     # the same through Python: the tracker after two frames (gray and colour), and detect_batch's rows on frame 0
     tmpl = alignment_template(MEAN, LM, 112, 112, 0.2)
     names = [IDS[i] for i in LM]

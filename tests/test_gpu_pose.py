@@ -2,18 +2,15 @@
 examples/pose_estimation.cpp against the float64 restatement of its formulas (tests/pose_f64.py), its bit-level contracts
 (fused vs level by level, batch independence, reproducible training), the detect -> pose hand-off and the C++ port of the
 example's main."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import cpp_build as B
 import pose_f64 as P
 from superviseddescent_amd import (Context, HoGParam, HogTransform, LinearRegressor, ModelProjection, Regulariser, SdmError,
                                    SupervisedDescentOptimiser, detection_model, ibug, synth)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MN = Regulariser.RegularisationType.MatrixNorm
 # device float32 projection vs float64, max |error| per row / max |u, v| of the row (the host evaluation measures 1.5e-6)
 FEAT_TOL = 6e-6
@@ -231,15 +228,8 @@ def test_invalid_sizes_and_singular_system(ctx):
 
 
 def test_cpp_port_of_the_example(built, tmp_path):
-    exe = str(tmp_path / "pose_estimation_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "pose_estimation_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread"])
     samples = str(tmp_path / "x_tr.txt")
-    out = subprocess.run([exe, samples], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stdout + out.stderr
+    out = B.run(B.gpu_driver("pose_estimation_gpu", tmp_path), [samples], 300)
     lines = out.stdout.strip().splitlines()
     residuals = [float(v) for v in lines[1:4]]
     assert residuals[2] < residuals[0] < 1e-3
@@ -248,5 +238,4 @@ def test_cpp_port_of_the_example(built, tmp_path):
     x0 = np.tile(P.EXAMPLE_X0, (len(x_tr), 1))
     Rs, _ = P.train(x_tr, x0, ModelProjection(homogeneous(P.EXAMPLE_POINTS))(x_tr))
     ref = P.test(P.EXAMPLE_X0, P.example_templates(), Rs)[0]
-    print(out.stdout)
     assert np.abs(np.array(pred) - ref[:3]).max() < PREDICT_TOL_DEG

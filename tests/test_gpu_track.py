@@ -2,18 +2,17 @@
 the detect batch it must equal bit for bit, the realign and lost rules against their host restatement (tests/track_ref.py), stream
 independence, argument limits, accuracy on synthetic video, the track -> pose hand-off and the C++ layer's rcr::tracker."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import cpp_build as B
 import pose_f64 as P
 import track_ref as T
 from superviseddescent_amd import (Context, HoGParam, HogTransform, LinearRegressor, ModelProjection, Regulariser, SdmError,
-                                   SupervisedDescentOptimiser, detection_model, ibug, model_io, synth)
+                                   SupervisedDescentOptimiser, detection_model, ibug, synth)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = ibug.RCR22_IDS
 L = len(IDS)
 RE, LE = ibug.eye_indices(IDS)
@@ -320,23 +319,12 @@ def test_cpp_tracker_matches_python(model, tmp_path):
     frames[6, 2] = 128                                                  # a blank frame for stream 2: it may be lost and restarted
     n_frames, S, H, W = frames.shape
     d = str(tmp_path)
-    model_io.save_detection_model(model_io.DetectionModelFile(
-        [model_io.RegressorRecord(r.x, 1, 1.5, False) for r in model.optimised_model.regressors], MEAN, IDS,
-        [(p.vlhog_variant, p.num_cells, p.cell_size, p.num_bins, p.relative_patch_size) for p in model.hog_params],
-        ibug.RIGHT_EYE_IDS, ibug.LEFT_EYE_IDS), os.path.join(d, "model.bin"))
+    B.write_model(d, L, model.hog_params, MEAN, IDS, regressors=[r.x for r in model.optimised_model.regressors])
     frames.tofile(os.path.join(d, "frames.u8"))
     boxes.astype(np.int32).tofile(os.path.join(d, "boxes.i32"))
     with open(os.path.join(d, "meta.txt"), "w") as f:
         f.write(f"{S} {n_frames} {H} {W} {S}\n")
-    exe = str(tmp_path / "track_gpu")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"),
-                           os.path.join(ROOT, "tests", "cpp", "track_gpu.cpp"), "-o", exe, "-L" + lib, "-lsdm_hip",
-                           "-Wl,-rpath," + lib, "-lpthread"])
-    out = subprocess.run([exe, d], capture_output=True, text=True, timeout=300)
-    print(out.stdout)
-    assert out.returncode == 0, out.stdout + out.stderr
+    B.run(B.gpu_driver("track_gpu", tmp_path), [d], 300)
     # the same loop through the Python Tracker
     tr = model.tracker(S)
     ids = np.arange(S)

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import cpp_build as B
 import pose_f64 as P
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -73,12 +74,7 @@ def test_normalised_coordinates_do_not_depend_on_screen_or_clip_planes():
 @pytest.fixture(scope="module")
 def pose_host_bin(built, tmp_path_factory):
     """tests/cpp/pose_host.cpp built with g++ and the flags of tests/cpp/Makefile into a temp dir."""
-    out = str(tmp_path_factory.mktemp("pose_cpp") / "pose_host")
-    lib = os.path.join(ROOT, "superviseddescent_amd", "lib")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-Wno-unused-function", "-I" + os.path.join(ROOT, "include"),
-                           "-I" + os.path.join(ROOT, "superviseddescent_amd", "include"), os.path.join(ROOT, "tests", "cpp", "pose_host.cpp"),
-                           "-o", out, "-L" + lib, "-lsdm_hip", "-Wl,-rpath," + lib, "-lpthread"])
-    return out
+    return B.gpu_driver("pose_host", tmp_path_factory.mktemp("pose_cpp"))
 
 
 def run_cpp_host(binary, tmp_path, x, points=P.EXAMPLE_POINTS, cam=(1800.0, 1000.0, 1000.0, 1.0, 5000.0)):

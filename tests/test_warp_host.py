@@ -1,20 +1,19 @@
 """The piecewise-affine face warp without a device (include/sdm.h, "Warped faces"): sdm_warp_delaunay, the properties of the label map as
 tests/warp_ref.py restates it, and the per-triangle and per-pixel code of csrc/sdm_warp_device.h compiled for the host
-(tests/cpp/warp_host.cpp, -fsanitize=address,undefined, planes of exactly the frames' bytes) against that restatement, bit for bit."""
-import os
+(tests/cpp/warp_host.cpp, address and undefined-behaviour sanitizers, planes of exactly the frames' bytes) against that restatement, bit
+for bit."""
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import align_tensor_cases as K
 import align_tensor_ref as T
+import cpp_build as B
 import warp_cases as W
 import warp_ref as R
 from superviseddescent_amd import _lib, delaunay, ibug
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 
 
@@ -164,10 +163,7 @@ def border_matrices(f, w, h, T_):
 
 
 def test_host_build_of_the_warp_code_under_sanitizers(built, tmp_path):
-    exe = str(tmp_path / "warp_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan",
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "warp_host.cpp"), "-o", exe])
+    exe = B.host_program("warp_host", tmp_path)
     scale, bias = np.array([1 / 58.395, 1 / 57.12, 1 / 57.375], f32), np.array([-2.1179, -2.0357, -1.8044], f32)
     # ---- the fit of a triangle: the rows of the device test, one folded and one flat triangle among them
     w, h = W.CROPS[0]
@@ -209,10 +205,7 @@ def test_host_build_of_the_warp_code_under_sanitizers(built, tmp_path):
     assert seen == set(range(6))
     blob[0] = struct.pack("<i", len(cases))
     (tmp_path / "cases.bin").write_bytes(b"".join(fits) + b"".join(blob))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, env=env, timeout=300)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
+    B.run(exe, [tmp_path / "cases.bin", tmp_path / "out.bin"], 300, sanitized=True)
     got = np.fromfile(str(tmp_path / "out.bin"), np.uint8)
     nf = want_m.shape[0] * want_m.shape[1]
     rec = got[:nf * 28].reshape(nf, 28)

@@ -1,13 +1,11 @@
 """sdm_warp_paste_tensor without a device: properties of the numpy restatement alone (tests/warp_paste_ref.py) against exact rational
 geometry; feather_warp_mask; and the kernels' per-row, per-triangle and per-pixel code compiled for the host
-(tests/cpp/warp_paste_host.cpp, -fsanitize=address,undefined, every frame, tensor, label map and opacity map in a heap block of exactly
-its bytes, run as a child process) against the restatement, bit for bit: the flags, every A_t and W_t, the row boxes and every byte
-the frame owns, with the rows pasted in descending and in ascending order.  The host program walks pixels in plain loops; the kernel's
-wave-wide cull and its LDS staging run only in tests/test_gpu_warp_paste.py."""
+(tests/cpp/warp_paste_host.cpp, address and undefined-behaviour sanitizers, every frame, tensor, label map and opacity map in a heap
+block of exactly its bytes, run as a child process) against the restatement, bit for bit: the flags, every A_t and W_t, the row boxes
+and every byte the frame owns, with the rows pasted in descending and in ascending order.  The host program walks pixels in plain
+loops; the kernel's wave-wide cull and its LDS staging run only in tests/test_gpu_warp_paste.py."""
 import itertools
-import os
 import struct
-import subprocess
 from fractions import Fraction
 
 import numpy as np
@@ -15,13 +13,13 @@ import pytest
 
 import align_tensor_cases as K
 import align_tensor_ref as T
+import cpp_build as B
 import paste_cases as C
 import warp_cases as WC
 import warp_paste_ref as WP
 import warp_ref as R
 from superviseddescent_amd import _lib, feather_warp_mask
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 COMBOS = list(itertools.product(("uint8", "float16", "float32"), ("nhwc", "nchw"), (1, 3), ("bgr", "rgb")))
 MESHES = (WC.mesh_rcr22, WC.mesh_single, WC.mesh_254)
@@ -215,10 +213,7 @@ def needle_cases(buf, frames, k0):
 
 
 def test_host_build_of_the_pixel_code_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "warp_paste_host")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan",
-                           "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "warp_paste_host.cpp"), "-o", exe])
+    exe = B.host_program("warp_paste_host", tmp_path)
     cases = host_cases()
     blob = [struct.pack("<i", len(cases))]
     for c in cases:
@@ -234,10 +229,7 @@ def test_host_build_of_the_pixel_code_under_sanitizers(tmp_path):
                     + struct.pack("<i", c["x"].nbytes) + c["x"].tobytes() + struct.pack("<i", len(a)) + a
                     + struct.pack("<i", c["frame"].size) + c["frame"].tobytes())
     (tmp_path / "cases.bin").write_bytes(b"".join(blob))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    run = subprocess.run([exe, str(tmp_path / "cases.bin"), str(tmp_path / "out.bin")], capture_output=True, text=True, env=env, timeout=120)
-    print(run.stdout)
-    assert run.returncode == 0, run.stdout + run.stderr
+    B.run(exe, [tmp_path / "cases.bin", tmp_path / "out.bin"], 120, sanitized=True)
     got = np.fromfile(str(tmp_path / "out.bin"), np.uint8)
     at, seen, touched, boxed, formats = 0, 0, 0, 0, set()
     for k, c in enumerate(cases):
