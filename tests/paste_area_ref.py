@@ -28,18 +28,20 @@ def samples(M, mode=AREA, max_samples=16, min_scale=1.0):
     return R.samples_of_s2(s2_of(M), mode, max_samples, min_scale, degenerate)
 
 
-def paste_row(pix, fmt, M, x, alpha=None, S=1, layout="nchw", channels=3, order="rgb", scale=(1, 1, 1), bias=(0, 0, 0), gray_shift=14):
+def paste_row(pix, fmt, M, x, alpha=None, S=1, layout="nchw", channels=3, order="rgb", scale=(1, 1, 1), bias=(0, 0, 0), gray_shift=14,
+              origin=(0, 0)):
+    """origin = (X0, Y0): pix is the window of the frame that starts at frame pixel (X0, Y0), as for paste_ref.paste_row"""
     spec = dict(layout=layout, channels=channels, order=order, scale=scale, bias=bias, gray_shift=gray_shift)
     if S == 1:
-        return P.paste_row(pix, fmt, M, x, alpha, **spec)[1]
+        return P.paste_row(pix, fmt, M, x, alpha, origin=origin, **spec)[1]
     H, Wd = pix.shape[:2]
     W, degenerate = P.inverse(M)
     assert not degenerate
     p = P.decode(P.as_hwc(x, layout, channels), scale, bias)                   # ch x cw x C
     ch, cw = p.shape[:2]
     o = R.offsets(S)
-    fX = (np.arange(Wd, dtype=f32)[None, :, None, None] + o[None, None, None, :]).astype(f32)
-    fY = (np.arange(H, dtype=f32)[:, None, None, None] + o[None, None, :, None]).astype(f32)
+    fX = (np.arange(origin[0], origin[0] + Wd, dtype=f32)[None, :, None, None] + o[None, None, None, :]).astype(f32)
+    fY = (np.arange(origin[1], origin[1] + H, dtype=f32)[:, None, None, None] + o[None, None, :, None]).astype(f32)
     with np.errstate(all="ignore"):
         u = (((W[0] * fX).astype(f32) + (W[1] * fY).astype(f32)).astype(f32) + W[2]).astype(f32)
         v = (((W[3] * fX).astype(f32) + (W[4] * fY).astype(f32)).astype(f32) + W[5]).astype(f32)

@@ -19,7 +19,7 @@ import paste_ref as P
 f32 = np.float32
 
 
-def sample(M, x, alpha, S, H, Wd, layout="nchw", channels=3, order="rgb", scale=(1, 1, 1), bias=(0, 0, 0), gray_shift=14):
+def sample(M, x, alpha, S, H, Wd, layout="nchw", channels=3, order="rgb", scale=(1, 1, 1), bias=(0, 0, 0), gray_shift=14, origin=(0, 0)):
     """The colour and the opacity of one non-degenerate row at every frame pixel: at S = 1 the formula of "Pasting crops back" (one
     sub-sample with offset 0: the same float32 expression), else the S x S average of "Pasting crops back, filtered"."""
     W, degenerate = P.inverse(M)
@@ -27,8 +27,8 @@ def sample(M, x, alpha, S, H, Wd, layout="nchw", channels=3, order="rgb", scale=
     p = P.decode(P.as_hwc(x, layout, channels), scale, bias)                   # ch x cw x C
     ch, cw = p.shape[:2]
     o = R.offsets(S) if S > 1 else np.zeros(1, f32)
-    fX = (np.arange(Wd, dtype=f32)[None, :, None, None] + o[None, None, None, :]).astype(f32)
-    fY = (np.arange(H, dtype=f32)[:, None, None, None] + o[None, None, :, None]).astype(f32)
+    fX = (np.arange(origin[0], origin[0] + Wd, dtype=f32)[None, :, None, None] + o[None, None, None, :]).astype(f32)
+    fY = (np.arange(origin[1], origin[1] + H, dtype=f32)[:, None, None, None] + o[None, None, :, None]).astype(f32)
     with np.errstate(all="ignore"):
         u = (((W[0] * fX).astype(f32) + (W[1] * fY).astype(f32)).astype(f32) + W[2]).astype(f32)
         v = (((W[3] * fX).astype(f32) + (W[4] * fY).astype(f32)).astype(f32) + W[5]).astype(f32)
@@ -76,12 +76,15 @@ def blocks(v):
     return pad.reshape((pad.shape[0] // 2, 2, pad.shape[1] // 2, 2) + v.shape[2:]).sum((1, 3))
 
 
-def paste_row(Y, UV, M, x, alpha=None, S=1, channels=3, **spec):
-    """returns the row's opacity a (H x W); a degenerate row pastes nothing"""
+def paste_row(Y, UV, M, x, alpha=None, S=1, channels=3, origin=(0, 0), **spec):
+    """returns the row's opacity a (H x W); a degenerate row pastes nothing.  origin = (X0, Y0), both EVEN: Y and UV are the windows of
+    the planes that start at luma pixel (X0, Y0) and chroma sample (X0 / 2, Y0 / 2); a window of odd width or height must end at the
+    frame's own odd edge (a pixel beyond the window counts as outside the frame)"""
     H, Wd = Y.shape
+    assert origin[0] % 2 == 0 and origin[1] % 2 == 0
     if P.inverse(M)[1]:
         return np.zeros((H, Wd), np.int64)
-    q, a = sample(M, x, alpha, S, H, Wd, channels=channels, **spec)
+    q, a = sample(M, x, alpha, S, H, Wd, channels=channels, origin=origin, **spec)
     yq = luma_of(q) if channels == 3 else q[..., 0]
     old = Y.astype(np.int64)
     Y[...] = np.where(a > 0, blend(a, yq, old), old).astype(np.uint8)

@@ -5,7 +5,8 @@ the WHOLE frame, one row after the other.
   inverse(M)                              (W 6 float32, degenerate) of a float32 crop -> frame matrix
   flags_at(M, cw, ch, W, H)               the flags of sdm_align_paste_tensor_at
   decode(x, dtype-independent, scale, bias)   tensor elements (... x C) -> 0 ... 255
-  paste_row(pix, fmt, M, x, alpha, ...)   one row into pix (H x W x bpp uint8, in place); returns (footprint mask, opacity)
+  paste_row(pix, fmt, M, x, alpha, ...)   one row into pix (H x W x bpp uint8, in place); returns (footprint mask, opacity);
+                                          origin=(X0, Y0): pix is a window of the frame that starts at frame pixel (X0, Y0)
   paste(pix, fmt, rows, ...)              rows = [(M, x, alpha), ...] in row order
 """
 import numpy as np
@@ -52,7 +53,10 @@ def decode(x, scale, bias):
     return np.where(np.isnan(f), 0, p).astype(np.int64)
 
 
-def paste_row(pix, fmt, M, x, alpha=None, layout="nchw", channels=3, order="rgb", scale=(1, 1, 1), bias=(0, 0, 0), gray_shift=14):
+def paste_row(pix, fmt, M, x, alpha=None, layout="nchw", channels=3, order="rgb", scale=(1, 1, 1), bias=(0, 0, 0), gray_shift=14,
+              origin=(0, 0)):
+    """origin = (X0, Y0): pix is the window of the frame whose first pixel is frame pixel (X0, Y0); the positions are those of the TRUE
+    frame coordinates, and everything returned has the window's shape"""
     H, Wd = pix.shape[:2]
     W, degenerate = inverse(M)
     none = np.zeros((H, Wd), bool)
@@ -60,8 +64,8 @@ def paste_row(pix, fmt, M, x, alpha=None, layout="nchw", channels=3, order="rgb"
         return none, np.zeros((H, Wd), np.int64)
     p = decode(as_hwc(x, layout, channels), scale, bias)                   # ch x cw x C
     ch, cw = p.shape[:2]
-    X = np.arange(Wd, dtype=f32)[None, :]
-    Y = np.arange(H, dtype=f32)[:, None]
+    X = np.arange(origin[0], origin[0] + Wd, dtype=f32)[None, :]
+    Y = np.arange(origin[1], origin[1] + H, dtype=f32)[:, None]
     with np.errstate(all="ignore"):
         u = ((W[0] * X + W[1] * Y).astype(f32) + W[2]).astype(f32)
         v = ((W[3] * X + W[4] * Y).astype(f32) + W[5]).astype(f32)

@@ -75,15 +75,15 @@ def det_e(p, triangles):
         return e0[:, 0] * e1[:, 1] - e1[:, 0] * e0[:, 1]
 
 
-def covers(p, t, tri, det, W, H, tri_box=True):
+def covers(p, t, tri, det, W, H, tri_box=True, origin=(0, 0)):
     """H x W bool: the pixel lies in the triangle's box -- floor(min) - 1 <= x < ceil(max) + 2 over its three corners, the same in y,
     in float64 -- and the three edge functions of triangle t (b and c exchanged where det E < 0) are >= 0 at the pixel centre"""
     d = np.asarray(p, f32).astype(f64)
     a, b, c = tri[t]
     if det[t] < 0:
         b, c = c, b
-    x = np.arange(W, dtype=f64)[None, :]
-    y = np.arange(H, dtype=f64)[:, None]
+    x = np.arange(origin[0], origin[0] + W, dtype=f64)[None, :]
+    y = np.arange(origin[1], origin[1] + H, dtype=f64)[:, None]
     cx, cy = d[[a, b, c], 0], d[[a, b, c], 1]
     ok = ((x >= np.floor(cx.min()) - 1.0) & (x < (np.ceil(cx.max()) + 1.0) + 1.0)
           & (y >= np.floor(cy.min()) - 1.0) & (y < (np.ceil(cy.max()) + 1.0) + 1.0))
@@ -94,7 +94,9 @@ def covers(p, t, tri, det, W, H, tri_box=True):
     return ok
 
 
-def triangle_map(p, triangles, mats, W, H, use_box=True, tri_box=True):
+def triangle_map(p, triangles, mats, W, H, use_box=True, tri_box=True, origin=(0, 0)):
+    """origin = (X0, Y0): the map of the W x H window of the frame that starts at frame pixel (X0, Y0); the window lies inside the frame,
+    so the row's box clipped to the window's far corner and cut at its origin is the box clipped to the frame, seen from the window"""
     tri = np.asarray(triangles, np.int64).reshape(-1, 3)
     out = np.full((H, W), -1, np.int64)
     if not np.isfinite(np.asarray(p, f32)).all():
@@ -104,26 +106,28 @@ def triangle_map(p, triangles, mats, W, H, use_box=True, tri_box=True):
     for t in range(tri.shape[0] - 1, -1, -1):                 # (descending: the lowest number is written last)
         if det[t] == 0 or skipped[t]:
             continue
-        out[covers(p, t, tri, det, W, H, tri_box)] = t
+        out[covers(p, t, tri, det, W, H, tri_box, origin)] = t
     if use_box:
-        x0, y0, x1, y1 = box(p, W, H)
+        X0, Y0 = origin
+        x0, y0, x1, y1 = box(p, X0 + W, Y0 + H)
         inside = np.zeros((H, W), bool)
-        inside[y0:y1, x0:x1] = True
+        inside[max(y0 - Y0, 0):max(y1 - Y0, 0), max(x0 - X0, 0):max(x1 - X0, 0)] = True
         out[~inside] = -1
     return out
 
 
 def paste_row(pix, fmt, p, triangles, mats, lab, x, alpha=None, layout="nchw", channels=3, order="rgb", scale=(1, 1, 1), bias=(0, 0, 0),
-              gray_shift=14):
+              gray_shift=14, origin=(0, 0)):
+    """origin = (X0, Y0): pix is the window of the frame that starts at frame pixel (X0, Y0), as for paste_ref.paste_row"""
     H, Wd = pix.shape[:2]
-    tmap = triangle_map(p, triangles, mats, Wd, H)
+    tmap = triangle_map(p, triangles, mats, Wd, H, origin=origin)
     Wt, _ = inverses(mats)
     px = P.decode(P.as_hwc(x, layout, channels), scale, bias)              # ch x cw x C
     ch, cw = px.shape[:2]
     has = tmap >= 0
     w = Wt[np.where(has, tmap, 0)]                                         # H x W x 6 float32
-    X = np.broadcast_to(np.arange(Wd, dtype=f32)[None, :], (H, Wd))
-    Y = np.broadcast_to(np.arange(H, dtype=f32)[:, None], (H, Wd))
+    X = np.broadcast_to(np.arange(origin[0], origin[0] + Wd, dtype=f32)[None, :], (H, Wd))
+    Y = np.broadcast_to(np.arange(origin[1], origin[1] + H, dtype=f32)[:, None], (H, Wd))
     with np.errstate(all="ignore"):
         u = ((w[..., 0] * X + w[..., 1] * Y).astype(f32) + w[..., 2]).astype(f32)
         v = ((w[..., 3] * X + w[..., 4] * Y).astype(f32) + w[..., 5]).astype(f32)
