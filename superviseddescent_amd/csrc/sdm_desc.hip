@@ -63,8 +63,13 @@ __device__ inline int desc_f16_exponent(unsigned maxbits)      // (= apply_f16_e
     return (int)((maxbits >> 23) & 0xff) - 127;
 }
 
+// k-parts of the fused product (waves per column tile) and waves side by side on column tiles, from the staged K (PK = desc_pk)
+__host__ __device__ constexpr int desc_kparts(int PK) { return desc_kp(PK) / 32 <= 14 ? 2 : 4; }
+__host__ __device__ constexpr int desc_nw(int PK, int W) { return W / desc_kparts(PK); }
+
 // One wave = two patches (lane >> 5), one lane = one cell (lane & 31 < C*C).  FB samples x one landmark per workgroup.
-template <int TO, int TC, int VARIANT, bool FUSED, int FB, int W = DS_WAVES>      // W waves per workgroup
+// ONE (fused form): at most one column tile per wave (NT <= NW), see the product phase.
+template <int TO, int TC, int VARIANT, bool FUSED, int FB, int W = DS_WAVES, bool ONE = false>      // W waves per workgroup
 __global__ void __launch_bounds__(W * 64, (TO > 4 && !FUSED) ? 2 : ((TO <= 4 && FUSED) ? DS_MINW : 4))      // (the 31 / 36 features per cell of 9 orientations need > 128 registers in the store form)
 desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N, int L,
             float* __restrict__ feat, long long ldf, int has_bias,
@@ -90,6 +95,7 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
     const int iA = (lb + ym * C + xm) * 4, iB = (lb + ym * C + x) * 4, iC = (lb + ym * C + xp) * 4;
     const int iD = (lb + y * C + xm) * 4, iF = (lb + y * C + xp) * 4;
     const int iG = (lb + yp * C + xm) * 4, iH = (lb + yp * C + x) * 4, iI = (lb + yp * C + xp) * 4;
+    const unsigned ipk0 = iA | iB << 8 | iC << 16 | iD << 24, ipk1 = iF | iG << 8 | iH << 16 | iI << 24;      // (fused form, below)
     const bool is_cut = cut[l] != 0;
 
     if (FUSED) {      // the rows' padding (and the spare bytes behind the last row) is read by the last k-step: zero it once
@@ -113,30 +119,46 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
     constexpr int NIT = FB / (2 * W);
     auto face_of = [&](int it) { const int fr = tile * FB + it * (2 * W) + wave * 2 + half; return fr < N ? fr : N - 1; };      // (a partial last tile repeats the last sample; never stored)
     // cells[sample][landmark][part][cell][2O]: this lane's cell = 2O consecutive floats
-    auto load_cells = [&](int it, float* h) {
+    // A patch cut by a pass boundary has a second part, the second pass's partial folds (same sum as the in-kernel "+=").  The store
+    // form adds it here, as it arrives.  The fused form (DEFER) keeps it in registers of its own, h2, and adds it where the iteration
+    // takes the patch over: added here, the sum needs the loaded values at once, and the prefetch below was waited for in front of the
+    // arithmetic it should have run under.
+    constexpr bool DEFER = FUSED;
+    auto load_cells = [&](int it, float* h, float* h2) {
         const float* hp = cells + ((((long long)face_of(it) * L + l) * 2) * CC + cc) * (2 * O);
 #pragma unroll
         for (int j = 0; j + 4 <= 2 * O; j += 4) { const f32x4u v = *(const f32x4u*)(hp + j); h[j] = v[0]; h[j + 1] = v[1]; h[j + 2] = v[2]; h[j + 3] = v[3]; }
         if ((2 * O) % 4) { const f32x2u v = *(const f32x2u*)(hp + (2 * O) / 4 * 4); h[(2 * O) / 4 * 4] = v[0]; h[(2 * O) / 4 * 4 + 1] = v[1]; }
-        if (is_cut) {       // a patch cut by a pass boundary: the second pass's partial folds (same sum as the in-kernel "+=")
+        if (is_cut) {
             const float* hq = hp + (size_t)CC * 2 * O;
+            if (DEFER) {
 #pragma unroll
-            for (int j = 0; j + 4 <= 2 * O; j += 4) { const f32x4u v = *(const f32x4u*)(hq + j); h[j] += v[0]; h[j + 1] += v[1]; h[j + 2] += v[2]; h[j + 3] += v[3]; }
-            if ((2 * O) % 4) { const f32x2u v = *(const f32x2u*)(hq + (2 * O) / 4 * 4); h[(2 * O) / 4 * 4] += v[0]; h[(2 * O) / 4 * 4 + 1] += v[1]; }
+                for (int j = 0; j + 4 <= 2 * O; j += 4) { const f32x4u v = *(const f32x4u*)(hq + j); h2[j] = v[0]; h2[j + 1] = v[1]; h2[j + 2] = v[2]; h2[j + 3] = v[3]; }
+                if ((2 * O) % 4) { const f32x2u v = *(const f32x2u*)(hq + (2 * O) / 4 * 4); h2[(2 * O) / 4 * 4] = v[0]; h2[(2 * O) / 4 * 4 + 1] = v[1]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j + 4 <= 2 * O; j += 4) { const f32x4u v = *(const f32x4u*)(hq + j); h[j] += v[0]; h[j + 1] += v[1]; h[j + 2] += v[2]; h[j + 3] += v[3]; }
+                if ((2 * O) % 4) { const f32x2u v = *(const f32x2u*)(hq + (2 * O) / 4 * 4); h[(2 * O) / 4 * 4] += v[0]; h[(2 * O) / 4 * 4 + 1] += v[1]; }
+            }
         }
     };
     static_assert((2 * TO) % 2 == 0, "");
-    float hn[2 * O];
-    load_cells(0, hn);
+    float hn[2 * O], hn2[DEFER ? 2 * O : 1] = {};
+    load_cells(0, hn, hn2);
 #pragma unroll 1
     for (int it = 0; it < NIT; ++it) {
         const int m = it * (2 * W) + wave * 2 + half;             // sample of the tile
         const int face_real = tile * FB + m;
         const int face = face_real < N ? face_real : N - 1;
         float h[2 * O];
+        if (DEFER && is_cut) {
 #pragma unroll
-        for (int j = 0; j < 2 * O; ++j) h[j] = hn[j];
-        if (it + 1 < NIT) load_cells(it + 1, hn);                        // the next patch's cells are in flight during this one's arithmetic
+            for (int j = 0; j < 2 * O; ++j) h[j] = hn[j] + hn2[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2 * O; ++j) h[j] = hn[j];
+        }
+        if (it + 1 < NIT) load_cells(it + 1, hn, hn2);                   // the next patch's cells are in flight during this one's arithmetic
         if (DS_ABL == 2 && FUSED) {
             if (active) { float t = 0.0f; for (int j = 0; j < 2 * O; ++j) t += h[j]; stage_hi[(size_t)m * KS + cc * DP] = (unsigned short)(t == 12345.0f); }
             continue;
@@ -149,10 +171,17 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
             n += hs * hs;
         }
         const int nb = __builtin_bit_cast(int, n);
-        const float nA = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(iA, nb)), nB = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(iB, nb));
-        const float nC = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(iC, nb)), nD = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(iD, nb));
-        const float nF = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(iF, nb)), nG = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(iG, nb));
-        const float nH = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(iH, nb)), nI = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(iI, nb));
+        int jA = iA, jB = iB, jC = iC, jD = iD, jF = iF, jG = iG, jH = iH, jI = iI;
+        if (DEFER) {      // the eight lane addresses (< 256 each) wait in two registers, not eight; unpacked per patch, which the asm keeps in the loop
+            unsigned p0 = ipk0, p1 = ipk1;
+            asm volatile("" : "+v"(p0), "+v"(p1));
+            jA = p0 & 0xff; jB = (p0 >> 8) & 0xff; jC = (p0 >> 16) & 0xff; jD = p0 >> 24;
+            jF = p1 & 0xff; jG = (p1 >> 8) & 0xff; jH = (p1 >> 16) & 0xff; jI = p1 >> 24;
+        }
+        const float nA = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(jA, nb)), nB = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(jB, nb));
+        const float nC = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(jC, nb)), nD = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(jD, nb));
+        const float nF = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(jF, nb)), nG = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(jG, nb));
+        const float nH = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(jH, nb)), nI = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(jI, nb));
         // block factors of the four blocks this cell belongs to (hog.c:930-981; hog_finish_direct's fac[] with the same operand order)
         const f32x2 F12 = {__builtin_amdgcn_rsqf(nA + nB + nD + n + 1e-4f) * SC, __builtin_amdgcn_rsqf(nB + nC + n + nF + 1e-4f) * SC};
         const f32x2 F34 = {__builtin_amdgcn_rsqf(nD + n + nG + nH + 1e-4f) * SC, __builtin_amdgcn_rsqf(n + nF + nH + nI + 1e-4f) * SC};
@@ -211,19 +240,46 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
     }
     if (!FUSED) return;
     if (DS_ABL == 1) { if (threadIdx.x == 0 && stage_hi[5] == 0x1234) partial[0] = 1.0f; return; }
+    // vmcnt(0).  No load is in flight here -- the last iteration prefetches nothing -- but the compiler's count cannot know that, and
+    // without this it waits below for the prefetch registers wherever it reuses one of them: in front of loads that are in flight by then.
+    if (NIT > 1) __builtin_amdgcn_s_waitcnt(0x0f70);
 
-    __syncthreads();
     // ---- [FB x P] x [P x 2L] ------------------------------------------------------------------------------------------------------
-    // Wave w multiplies k-part w % KPARTS of the column tiles w / KPARTS, + 8 / KPARTS, ...: a part is <= 7 k-steps, so ALL of its
-    // regressor fragments are requested before the first product (one L2 round trip per task; with the fragments fetched one k-step
-    // ahead every k-step waited ~600 cycles for ~100 cycles of matrix work).  Parts > 0 hand their tile to part 0 through LDS.
-    constexpr int KPARTS = KSTEPS <= 14 ? 2 : 4, NW = W / KPARTS;
+    // Wave w multiplies k-part w % KPARTS of the column tiles w / KPARTS, + 8 / KPARTS, ...: one (tile, k-part) is a task of <= 8 k-steps,
+    // two 16-byte fragment loads per k-step.  Parts > 0 hand their tile to part 0 through LDS.
+    //   * ONE (NT <= NW, at most one task per wave): ALL of the task's fragments, the last, conditional k-step's pair included, are
+    //     requested in one batch, and in front of the first barrier -- the descriptor's registers are dead there, so the L2 round trip
+    //     runs while the wave waits for the others -- then the products follow with counted waits, vmcnt(13), (12), ... (0).  The source
+    //     order alone does not give that: the compiler moves each k-step's two loads down to the products that use them (two loads, a
+    //     wait, the products: 6 or 7 L2 round trips in a row per task).  What holds the order: the barrier between loads and products,
+    //     the scheduling barrier in front of the products, and the use of the last pair behind the products (an empty asm), without
+    //     which that pair is sunk into the `j < nks` branch.  The fragments are 2 * KMAX * 4 = 56 / 64 registers; with one tile's
+    //     accumulators the 4-orientation instances take 76, six waves per SIMD, no scratch.
+    //   * the general form (NT > NW, reached with fuse_wide only): the same loop, compiled one k-step at a time as described; with
+    //     MAXT tiles' accumulators live, holding the batch by a scheduling barrier spills.
+    // scripts/isa_desc_fetch.py prints the compiled order of every fused instance; measurements: profiles/desc_fetch.txt.
+    constexpr int KPARTS = desc_kparts(PK), NW = desc_nw(PK, W);
     constexpr int KBASE = KSTEPS / KPARTS, KREM = KSTEPS % KPARTS, KMAX = KBASE + (KREM ? 1 : 0);
-    constexpr int MAXT = (9 + NW - 1) / NW;                         // column tiles per wave at 2L <= 144
-    const int li = lane & 15, lq = lane >> 4;
+    constexpr int MAXT = ONE ? 1 : (9 + NW - 1) / NW;               // column tiles per wave at 2L <= 144
+    // (the thread index is taken afresh: what the product phase derives from it is then computed here and holds no registers in the
+    // descriptor loop, which has none to spare with the deferred second part)
+    unsigned tx = threadIdx.x;
+    if (DEFER) asm volatile("" : "+v"(tx));
+    const int lane_p = tx & 63, wave_p = tx >> 6;      // (= lane, wave)
+    const int li = lane_p & 15, lq = lane_p >> 4;
     const int Mp = NT * 16;
-    const int kp = wave % KPARTS, ntl = wave / KPARTS;
+    const int kp = wave_p % KPARTS, ntl = wave_p / KPARTS;
     const int ks0 = kp * KBASE + (kp < KREM ? kp : KREM), nks = KBASE + (kp < KREM ? 1 : 0);
+    u32x4 bq1[ONE ? KMAX : 1][2];
+    auto fetch_task = [&]() {      // ONE: the wave's task, planes[l][k-step][column tile][piece][lane] as below
+        if constexpr (ONE) if (ntl < NT) {
+            const unsigned b0 = ((((unsigned)l * KSTEPS + ks0) * NT + ntl) * 2) * 64 + lane_p, bstep = (unsigned)NT * 2 * 64;
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) { bq1[j][0] = planes[b0 + j * bstep]; bq1[j][1] = planes[b0 + j * bstep + 64]; }
+        }
+    };
+    if (ONE) fetch_task();
+    __syncthreads();
     f32x4 acc[MAXT][MT];
     // what the epilogue of the k-part-0 waves needs from memory -- the column's scale and, for landmark 0, the bias row of the regressor --
     // is requested here, in front of the products, instead of behind the last barrier (one more memory round trip at the end of every workgroup)
@@ -238,6 +294,32 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
             if (has_bias && l == 0) biasv[ti] = Rt[(long long)(16 * nt + li) * ldr + (long long)L * P];
         }
     }
+    if (ONE) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) acc[0][mt] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
+        if (ntl < NT) {
+            __builtin_amdgcn_sched_barrier(0);                      // nothing of the products moves up among the loads
+            const unsigned a0 = (unsigned)li * KS + 32 * ks0 + 8 * lq;
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j) {
+                if (j < nks) {
+                    const f16x8 vbh = __builtin_bit_cast(f16x8, bq1[j][0]), vbl = __builtin_bit_cast(f16x8, bq1[j][1]);
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt) {
+                        const unsigned ao = a0 + 16 * mt * KS + 32 * j;
+                        const f16x8 ah = *(const f16x8*)(stage_hi + ao);
+                        const f16x8 al = *(const f16x8*)(stage_lo + ao);
+                        acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, vbh, acc[0][mt], 0, 0, 0);
+                        acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, vbl, acc[0][mt], 0, 0, 0);
+                        acc[0][mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, vbh, acc[0][mt], 0, 0, 0);
+                    }
+                }
+            }
+            // a use on every path: the last pair's loads stay with the batch (a short part fetches the step behind its last one --
+            // the next part's first, or the planes' padding -- and does not multiply it)
+            if (KREM) asm volatile("" :: "v"(bq1[KMAX - 1][0]), "v"(bq1[KMAX - 1][1]));
+        }
+    } else {
 #pragma unroll
     for (int ti = 0; ti < MAXT; ++ti) {
         const int nt = ntl + ti * NW;
@@ -246,7 +328,7 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
         if (nt >= NT) continue;
         // planes[l][k-step][column tile][piece][lane]: the lane's 8 consecutive k of column 16 nt + li (32-bit index arithmetic:
         // the planes of 72 landmarks x 29 k-steps x 9 tiles are 2.4 M fragments)
-        const unsigned b0 = ((((unsigned)l * KSTEPS + ks0) * NT + nt) * 2) * 64 + lane, bstep = (unsigned)NT * 2 * 64;
+        const unsigned b0 = ((((unsigned)l * KSTEPS + ks0) * NT + nt) * 2) * 64 + lane_p, bstep = (unsigned)NT * 2 * 64;
         u32x4 bq[KMAX][2];
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {      // (a short part also fetches the step behind its last one -- the next part's first, or the planes' padding; not multiplied)
@@ -269,7 +351,8 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
             }
         }
     }
-    __syncthreads();                                                 // every wave is done with the staged descriptors: the space becomes the hand-over buffer
+    }
+    __syncthreads();                                                // every wave is done with the staged descriptors: the space becomes the hand-over buffer
     float* red = (float*)smem;                                      // [KPARTS - 1][NT][MT][4][64]
     if (kp > 0) {
 #pragma unroll
@@ -279,7 +362,7 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) red[((((size_t)(kp - 1) * NT + nt) * MT + mt) * 4 + e) * 64 + lane] = acc[ti][mt][e];
+                for (int e = 0; e < 4; ++e) red[((((size_t)(kp - 1) * NT + nt) * MT + mt) * 4 + e) * 64 + lane_p] = acc[ti][mt][e];
         }
     }
     __syncthreads();
@@ -298,7 +381,7 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
                 for (int e = 0; e < 4; ++e) {
                     float v = acc[ti][mt][e];
 #pragma unroll
-                    for (int q = 1; q < KPARTS; ++q) v += red[((((size_t)(q - 1) * NT + nt) * MT + mt) * 4 + e) * 64 + lane];      // (fixed order: k-parts 0, 1, ...)
+                    for (int q = 1; q < KPARTS; ++q) v += red[((((size_t)(q - 1) * NT + nt) * MT + mt) * 4 + e) * 64 + lane_p];      // (fixed order: k-parts 0, 1, ...)
                     const int face = tile * FB + 16 * mt + 4 * lq + e;      // C/D layout of the 16 x 16 tile: col = lane & 15, row = 4 (lane >> 4) + e
                     if (face < N) partial[((long long)l * N + face) * Mp + col] = v * unscale + bias;
                 }
@@ -335,7 +418,7 @@ __global__ void __launch_bounds__(256) desc_planes_kernel(const float* __restric
     planes[frag * 128 + 64 + lane] = p2;
 }
 
-template <int TO, int VARIANT, bool FUSED, int FB, int W = DS_WAVES>
+template <int TO, int VARIANT, bool FUSED, int FB, int W = DS_WAVES, bool ONE = false>
 void launch_desc(const float* cells, const int* cut, int N, int L, float* feat, long long ldf, int has_bias, const void* planes, int NT,
                  const unsigned* rmax, const float* Rt, long long ldr, float* partial, hipStream_t stream)
 {
@@ -351,8 +434,8 @@ void launch_desc(const float* cells, const int* cut, int N, int L, float* feat, 
     const unsigned grid = (unsigned)(((long long)N + FB - 1) / FB * L);
     static unsigned long long seen = 0;
     if (FUSED && sdm_first_use_on_device(seen))
-        SDM_SET_ATTR((const void*)desc_kernel<TO, 5, VARIANT, FUSED, FB, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((desc_kernel<TO, 5, VARIANT, FUSED, FB, W>), dim3(grid), dim3(W * 64), lds, stream, cells, cut, N, L, feat, ldf,
+        SDM_SET_ATTR((const void*)desc_kernel<TO, 5, VARIANT, FUSED, FB, W, ONE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL((desc_kernel<TO, 5, VARIANT, FUSED, FB, W, ONE>), dim3(grid), dim3(W * 64), lds, stream, cells, cut, N, L, feat, ldf,
                        has_bias, (const u32x4*)planes, NT, rmax, Rt, ldr, partial);
 }
 
@@ -395,7 +478,11 @@ void sdm_launch_desc_apply(const HogLevelDev& lv, const float* cells, const int*
 {
     if (N <= 0) return;
     const int hb = lv.fixed_h == 0 ? 1 : 0, NT = (M + 15) / 16;
-#define DA(O, V, FB) launch_desc<O, V, true, FB>(cells, cut, N, L, nullptr, 0, hb, planes, NT, rmax, Rt, ldr, partial, stream)
+    // at most one column tile per wave (NT <= NW: 2L <= 64 at 4 orientations, 2L <= 32 at 9): the instance that fetches a task in one batch
+#define DA(O, V, FB) do { \
+        if (NT <= desc_nw(desc_pk(25, desc_dim(O, V)), DS_WAVES)) launch_desc<O, V, true, FB, DS_WAVES, true>(cells, cut, N, L, nullptr, 0, hb, planes, NT, rmax, Rt, ldr, partial, stream); \
+        else launch_desc<O, V, true, FB>(cells, cut, N, L, nullptr, 0, hb, planes, NT, rmax, Rt, ldr, partial, stream); \
+    } while (0)
     if (lv.O == 4) { if (lv.variant == 1) DA(4, 1, 32); else DA(4, 0, 32); }
     else { if (lv.variant == 1) DA(9, 1, 16); else DA(9, 0, 16); }
 #undef DA
