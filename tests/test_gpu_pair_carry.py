@@ -4,59 +4,28 @@ every pixel row takes its lower source row from the previous row's upper one (a 
 lower source row is the one after the previous row's upper one).  Which half-widths qualify, the per-row "take the spare" masks
 and the per-pair spare rows are decided per (level, h) on the device from cv::resize's vertical taps.
 
-CPU part: the structure restated from test_gpu_row_carry.py's resize_taps (which reproduce the oracle's cv::resize bit for bit):
+CPU part: the structure restated in tests/hog_taps_ref.py from its resize_taps (which reproduce the oracle's cv::resize bit for bit):
 for S = 55 the half-widths 27 .. 41 are pair eligible and no others (27, 2h = S - 1, has shift rows only), from 28 on they have
 2h - 56 orphans, skip no source row and never hold two orphans in an aligned pair of pixel rows, in either pair phase; what the definition gives for S = 50 / 40 / 30.
 
 GPU part.  (1) The table the library built on the device (sdm_debug_hog_pair_taps), all 128 half-widths of the four shipped
 levels, equals the CPU expectation, and the table of sdm_debug_hog_taps is what it was.  (2) A half-width sweep at level 0 on NOISE
 images (one wrong source row changes cells), once with stride = width and once with stride > width: patch indices are the oracle's,
-feature rows are inside the standing bounds of the packed mode against the oracle (tests/test_gpu_parity.py::check_features), and
-the default is BIT IDENTICAL to option hog_two_load on the feature rows read through the raw cells, on the landmark update of
+feature rows are inside the standing bounds of the packed mode against the oracle (pixel_kernel_cases.PACKED_MAX_ABS, PACKED_REL_L2),
+and the default is BIT IDENTICAL to option hog_two_load on the feature rows read through the raw cells, on the landmark update of
 sdm_detect_level and on a four-level detect_batch of 192 faces."""
 import os
 
 import numpy as np
 import pytest
 
+from hog_taps_ref import eligible_range, expected_table, one_load_eligible, pair_expected, source_rows
 from oracle import sdm_oracle as orc
-from superviseddescent_amd._lib import SDM_HOG_COLUMNS
-from test_gpu_row_carry import (IDS, L, LE, O_SHIPPED, RE, SHIPPED, SIZES, _bits, _faces, _scaled_rows, expected_table,
-                                one_load_eligible, resize_taps)
-
-EXTRA_H = (27, 28, 41, 42, 43)          # either side of both ends of the eligible range of level 0
+from pixel_kernel_cases import (EXTRA_H, L22, LE22, O_SHIPPED, PACKED_MAX_ABS, PACKED_REL_L2, RE22, SHIPPED, SIZES, bits, noise, options,
+                                pair_sweep_rows, smooth_faces)  # noqa: F401
 
 
-# ---------------------------------------------------------------------------------------------- the definition, restated
-def source_rows(S, h):
-    """The two source rows of every resized row as the device's table holds them (columns 2 and 3 of sdm_debug_hog_taps)."""
-    if h == 0:                                   # the empty patch is given a 1-pixel source
-        return np.zeros(S, np.int64), np.zeros(S, np.int64)
-    taps = resize_taps(S, h)
-    if taps is None:                             # exact 2x: rows 2d, 2d + 1
-        return 2 * np.arange(S), 2 * np.arange(S) + 1
-    return taps[3], taps[4]
-
-
-def pair_expected(S, h):
-    """(eligible, take-the-spare mask [S], spare source row per pair [(S - 1) // 2] or -1, orphan rows) by the definition: every row
-    d >= 1 a shift or an orphan row, at most one orphan per pair (2p + 1, 2p + 2), a last row without a partner a shift row."""
-    r0, r1 = source_rows(S, h)
-    shift, orphan = np.zeros(S, bool), np.zeros(S, bool)
-    shift[1:] = r0[1:] == r1[:-1]
-    orphan[1:] = r0[1:] == r1[:-1] + 1
-    npairs = (S - 1) // 2
-    first, second = orphan[1:2 * npairs:2], orphan[2:2 * npairs + 1:2]
-    ok = bool((shift | orphan)[1:].all()) and not bool((first & second).any()) and bool(shift[2 * npairs + 1:].all())
-    eligible = h >= 1 and 2 * h != 2 * S and ok
-    spare = np.where(first, r0[1:2 * npairs:2], np.where(second, r0[2:2 * npairs + 1:2], -1))
-    return eligible, np.where(orphan, -1, 0), spare, int(orphan.sum())
-
-
-def eligible_range(S):
-    return [h for h in range(128) if pair_expected(S, h)[0]]
-
-
+# ---------------------------------------------------------------------------------------------- CPU: the definition (tests/hog_taps_ref.py)
 def test_pair_structure_at_level_0(built):
     S = 55
     for h in range(1, 128):
@@ -117,9 +86,8 @@ def test_pair_eligibility_of_the_other_levels(built):
 
 # ---------------------------------------------------------------------------------------------- GPU
 @pytest.mark.gpu
-def test_the_librarys_pair_table(gpu_ctx):
-    gpu_ctx.set_hog_mode(SDM_HOG_COLUMNS)
-    gpu_ctx.set_model_geometry(L, RE, LE, SHIPPED)
+def test_the_librarys_pair_table(gpu_ctx, options):
+    gpu_ctx.set_model_geometry(L22, RE22, LE22, SHIPPED)
     for level, S in enumerate(SIZES):
         table, info = gpu_ctx.debug_hog_pair_taps(level)
         taps, tinfo = gpu_ctx.debug_hog_taps(level)
@@ -149,45 +117,17 @@ def test_the_librarys_pair_table(gpu_ctx):
             assert eligible == list(range(27, 42))
 
 
-def _noise_images(n=24, seed=77):
-    return np.random.default_rng(seed).integers(0, 256, (n, 256, 256)).astype(np.uint8)
-
-
-def _sweep_rows(x0):
-    """test_gpu_row_carry's rows of level 0 (h = 1 .. 55, rows hanging off each border and wholly outside), then the half-widths either
-    side of both ends of the eligible range once more on another face, inside the image and hanging off each border."""
-    x, hs = _scaled_rows(x0, 0)
-    rel = float(np.float32(SHIPPED[0].relative_patch_size))
-    rows, more = [x], []
-    for h in EXTRA_H:
-        for s, (dx, dy) in enumerate(((0.0, 0.0), (3.0, -5.0), (-126.0, 0.0), (126.0, 0.0), (0.0, -126.0), (0.0, 126.0), (-125.0, 127.0))):
-            f = (11 * h + s) % x0.shape[0]
-            xs, ys = x0[f, :L].astype(np.float64), x0[f, L:].astype(np.float64)
-            k = (2.0 * h / rel) / orc.get_ied(x0[f], RE, LE)
-            rows.append(np.concatenate([128.0 + dx + (xs - xs.mean()) * k, 128.0 + dy + (ys - ys.mean()) * k]).astype(np.float32)[None])
-            more.append(h)
-    return np.concatenate(rows), np.concatenate([hs, np.array(more)])
-
-
 @pytest.fixture(scope="module")
 def sweep():
     """The sweep and its oracle, computed once for both strides."""
-    images = _noise_images()
-    _, x0 = _faces()
-    x, hs = _sweep_rows(x0)
+    images = noise(24, seed=77)
+    _, x0 = smooth_faces()
+    x, hs = pair_sweep_rows(x0)
     idx = (np.arange(x.shape[0]) % images.shape[0]).astype(np.int32)
-    want, widx = orc.hog_features_batch(images, idx, x, RE, LE, O_SHIPPED[0], n_threads=min(os.cpu_count() or 1, 16), want_idx=True)
+    want, widx = orc.hog_features_batch(images, idx, x, RE22, LE22, O_SHIPPED[0], n_threads=min(os.cpu_count() or 1, 16), want_idx=True)
     assert np.array_equal(widx[:, 0], hs)                                  # the sweep is the one intended
     assert set(range(1, 56)) <= set(hs.tolist()) and set(EXTRA_H) <= set(hs.tolist())
     return dict(images=images, x0=x0, x=x, hs=hs, idx=idx, want=want, widx=widx)
-
-
-@pytest.fixture
-def options(gpu_ctx):
-    yield gpu_ctx.set_option
-    gpu_ctx.set_option("hog_two_load", 0)
-    gpu_ctx.set_option("hog_split_store", 0)
-    gpu_ctx.set_sample_image_index(None)
 
 
 @pytest.mark.gpu
@@ -196,12 +136,11 @@ def test_half_width_sweep_on_noise(gpu_ctx, options, sweep, pitch):
     import torch
     images, x, hs, idx, want, widx = (sweep[k] for k in ("images", "x", "hs", "idx", "want", "widx"))
     n = x.shape[0]
-    gpu_ctx.set_hog_mode(SDM_HOG_COLUMNS)
-    gpu_ctx.set_model_geometry(L, RE, LE, SHIPPED)
+    gpu_ctx.set_model_geometry(L22, RE22, LE22, SHIPPED)
     if pitch == 256:
         gpu_ctx.upload_images(images)
     else:                                                     # the same images as views into wider rows of other noise
-        big = torch.from_numpy(np.random.default_rng(78).integers(0, 256, (images.shape[0], 256, pitch)).astype(np.uint8)).cuda()
+        big = torch.from_numpy(noise(images.shape[0], seed=78, w=pitch)).cuda()
         big[:, :, :256] = torch.from_numpy(images).cuda()
         gpu_ctx.set_frames_device([big[i, :, :256] for i in range(images.shape[0])])
     table, info = gpu_ctx.debug_hog_pair_taps(0)
@@ -212,7 +151,7 @@ def test_half_width_sweep_on_noise(gpu_ctx, options, sweep, pitch):
     assert (masks[:, 1::2] != 0).any() and (masks[:, 2::2] != 0).any()          # orphans in both positions of a pair
     got, upd, final = {}, {}, {}
     rng = np.random.default_rng(5)
-    Rs = [(rng.standard_normal((gpu_ctx.feature_dim(lv), 2 * L)) * 1e-3).astype(np.float32) for lv in range(4)]
+    Rs = [(rng.standard_normal((gpu_ctx.feature_dim(lv), 2 * L22)) * 1e-3).astype(np.float32) for lv in range(4)]
     for lv in range(4):
         gpu_ctx.set_regressor(lv, Rs[lv])
     x192 = sweep["x0"][:192]
@@ -239,7 +178,7 @@ def test_half_width_sweep_on_noise(gpu_ctx, options, sweep, pitch):
     rel = float(np.linalg.norm((got[False] - want).astype(np.float64)) / np.linalg.norm(want.astype(np.float64)))
     print("pitch %d: %d rows (%d on the pair loop), features against the oracle max abs %.3g rel L2 %.3g" % (pitch, n, n_pair, diff, rel))
     assert n_pair > 0                                         # the pair loop is taken
-    assert np.array_equal(_bits(got[False]), _bits(got[True]))
-    assert np.array_equal(_bits(upd[False]), _bits(upd[True]))
-    assert np.isfinite(final[False]).all() and np.array_equal(_bits(final[False]), _bits(final[True]))
-    assert diff <= 1e-6 and rel <= 5e-7          # tests/test_gpu_parity.py::check_features, packed mode
+    assert np.array_equal(bits(got[False]), bits(got[True]))
+    assert np.array_equal(bits(upd[False]), bits(upd[True]))
+    assert np.isfinite(final[False]).all() and np.array_equal(bits(final[False]), bits(final[True]))
+    assert diff <= PACKED_MAX_ABS and rel <= PACKED_REL_L2

@@ -3,15 +3,15 @@ requests what depends on (level, pass, lane) only -- its lane_tab entry, the fol
 rows -- before the geometry's arithmetic, takes the pass's words from ONE 16-byte load and picks its segment's by selects, and clears
 its column rows with stores at constant offsets.  Checked against the CPU oracle at the shapes where a set-up can go wrong: the
 integer decisions (sdm_get_patch_indices) are the oracle's, the feature rows read through the raw cells (hog_split_store) are inside
-the standing bounds of the packed mode (tests/test_gpu_parity.py::check_features), and a four-level detect with random regressors
-is, bit for bit, the same four levels stepped one at a time.
+the standing bounds of the packed mode (pixel_kernel_cases.check_cells), and a four-level detect with random regressors is, bit for
+bit, the same four levels stepped one at a time.
 
-Shapes: 1, 3 and 7 faces on 256 x 256 noise images and one ragged set of frames with differing sizes and strides; L = 5, 22, 32
+Shapes: 1, 3 and 7 faces on 256 x 256 noise images and two ragged sets of frames with differing sizes and strides; L = 5, 22, 32
 and 33 (2L = 64 and 66: either side of the fused detect's limit); all four shipped levels; eye counts (1, 1), (2, 2), (3, 3), (4, 4)
 and (1, 4): the reciprocal and the division branch of the eye centres.  The face counts make a workgroup's four waves straddle two
-faces and leave the last workgroup partial (asserted from the plans).  Rows: landmarks on x.5 (cvRound ties), negative coordinates,
-patches off every border, small and large faces.  L = 1 has one landmark for both eyes, so its inter-eye distance is zero: with it
-and with a tiny face SDM_ERR_EMPTY_PATCH must still be reported.
+faces and leave the last workgroup partial (asserted from the plans, tests/test_gpu_fold_overlap.py).  Rows: landmarks on x.5 (cvRound
+ties), negative coordinates, patches off every border, small and large faces.  L = 1 has one landmark for both eyes, so its inter-eye
+distance is zero: with it and with a tiny face SDM_ERR_EMPTY_PATCH must still be reported.
 
 Half-width sweep: eyes on a horizontal line, the left one at x = 0 so that the float difference IS the right eye's x, chosen so
 that rel * IED / 2 lands on k + 1/2, within a few float steps of it either side, and 2^-10 either side of it, for several k at each
@@ -23,162 +23,73 @@ import numpy as np
 import pytest
 
 from oracle import sdm_oracle as orc
-from superviseddescent_amd import HoGParam, SdmError, ibug
-from superviseddescent_amd._lib import SDM_HOG_COLUMNS
-from superviseddescent_amd.engine import hog_plan
-
-SHIPPED = [HoGParam(*p) for p in ibug.SHIPPED_HOG_PARAMS]
-RELS = [float(np.float32(p.relative_patch_size)) for p in SHIPPED]
-SIZES = [p.num_cells * p.cell_size for p in SHIPPED]
-
-# (L, right-eye indices, left-eye indices)
-CASES = {
-    "L5-eyes1+4": (5, [0], [1, 2, 3, 4]),
-    "L5-eyes2+2": (5, [0, 1], [3, 4]),
-    "L22-eyes3+3": (22, [2, 5, 7], [10, 11, 20]),
-    "L22-eyes1+1": (22, [21], [0]),
-    "L32-eyes4+4": (32, [0, 1, 2, 3], [28, 29, 30, 31]),
-    "L33-eyes2+2": (33, [32, 4], [0, 16]),
-}
+from pixel_kernel_cases import (EYE_CASES, L22, LE22, RE22, RELS, SHIPPED, SIZES, cells_features, check_cells,
+                                detect_equals_stepped_levels, edge_rows, face, noise, options, oracle_indices, oracle_per_row,
+                                tie_sweep_rows)  # noqa: F401
+from superviseddescent_amd import SdmError
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _noise(n, seed, h=256, w=256):
-    return np.random.default_rng(seed).integers(0, 256, (n, h, w)).astype(np.uint8)
-
-
-def _rows(L, re, le, seed):
-    """Seven rows of 2L landmarks: eye centres 20 .. 150 px apart on a tilted line, the rest scattered; then, row by row, the edge
-    cases of the docstring."""
-    rng = np.random.default_rng(seed)
-    rows = []
-    for kind in range(7):
-        ied = (66.0, 58.0, 47.0, 83.0, 20.0, 150.0, 71.0)[kind]
-        ang = rng.uniform(-0.5, 0.5)
-        cx, cy = ((128, 128), (128, 128), (20, 15), (236, 240), (128, 128), (128, 128), (250, 8))[kind]
-        xs = cx + rng.uniform(-70, 70, L)
-        ys = cy + rng.uniform(-70, 70, L)
-        for idx, sign in ((re, +1.0), (le, -1.0)):
-            for i in idx:
-                xs[i] = cx + sign * 0.5 * ied * np.cos(ang) + rng.uniform(-3, 3)
-                ys[i] = cy + sign * 0.5 * ied * np.sin(ang) + rng.uniform(-3, 3)
-        if kind == 1:                                        # cvRound ties: every coordinate on x.5 (even and odd integer parts)
-            xs, ys = np.floor(xs) + 0.5, np.floor(ys) + 0.5
-        if kind == 2:                                        # negative coordinates, patches off the left and the top border
-            xs[: (L + 1) // 2] -= 60.0
-            ys[L // 2:] -= 45.0
-            xs[0] = -0.5
-        if kind == 3:                                        # off the right and the bottom border, one patch wholly outside
-            xs[L - 1], ys[L - 1] = 700.0, 650.0
-        rows.append(np.concatenate([xs, ys]).astype(np.float32))
-    return np.stack(rows)
-
-
-def _oracle_indices(x, L, re, le, rel):
-    out = np.zeros((x.shape[0], 1 + 2 * L), np.int32)
-    for n in range(x.shape[0]):
-        v = float(np.float32(rel)) * orc.get_ied(x[n], re, le) / 2.0
-        out[n, 0] = int(np.floor(v + 0.5))                   # C's round() of a value >= 0
-        out[n, 1:] = [orc.cv_round(c) for c in x[n]]
-    return out
-
-
-O_SHIPPED = [orc.HoGParam(*p) for p in ibug.SHIPPED_HOG_PARAMS]
-
-
-@pytest.fixture
-def restore(gpu_ctx):
-    yield
-    gpu_ctx.set_option("hog_split_store", 0)
-    gpu_ctx.set_sample_image_index(None)
-
-
-def _check_against_the_oracle(gpu_ctx, x, L, re, le, oracle_images, what):
-    """Feature rows of the four levels through the raw cells and the patch indices of each against the oracle (`oracle_images`: one
+def _check_against_the_oracle(gpu_ctx, x, L, re, le, row_images, what, stepped=True):
+    """Feature rows of the four levels through the raw cells and the patch indices of each against the oracle (`row_images`: one
     image per row of x), then a four-level detect against the same levels stepped one at a time."""
-    rng = np.random.default_rng(6)
     gpu_ctx.set_option("hog_split_store", 1)
     for lv in range(4):
-        gpu_ctx.set_x(x)
-        got = gpu_ctx.hog_features(lv, fetch=True)
-        idx = gpu_ctx.patch_indices()
-        assert np.array_equal(idx, _oracle_indices(x, L, re, le, RELS[lv])), (what, lv)
-        want = np.concatenate([orc.hog_features_batch(im[None], None, x[i:i + 1], re, le, O_SHIPPED[lv]) for i, im in enumerate(oracle_images)])
-        diff = float(np.abs(got - want).max())
-        rel = float(np.linalg.norm((got - want).astype(np.float64)) / np.linalg.norm(want.astype(np.float64)))
-        print("%s level %d: %d rows, h %d .. %d, features against the oracle max abs %.3g rel L2 %.3g"
-              % (what, lv, x.shape[0], idx[:, 0].min(), idx[:, 0].max(), diff, rel))
-        assert diff <= 1e-6 and rel <= 5e-7, (what, lv)          # tests/test_gpu_parity.py::check_features, packed mode
-    gpu_ctx.set_option("hog_split_store", 0)
-    for lv in range(4):
-        gpu_ctx.set_regressor(lv, (rng.standard_normal((gpu_ctx.feature_dim(lv), 2 * L)) * 1e-3).astype(np.float32))
-    gpu_ctx.set_x(x)
-    final = gpu_ctx.detect_batch()
-    gpu_ctx.set_x(x)
-    for lv in range(4):
-        gpu_ctx.detect_level(lv)
-    assert np.isfinite(final).all() and np.array_equal(_bits(final), _bits(gpu_ctx.get_x())), what
-
-
-def test_face_counts_straddle_and_leave_a_partial_workgroup(built):
-    """1, 3 and 7 faces against the plans' units per face: somewhere a workgroup of four waves holds units of two faces, and somewhere
-    the last workgroup is partial."""
-    straddle = partial = 0
-    for L, _, _ in CASES.values():
-        for p in SHIPPED:
-            plan = hog_plan(p.num_cells, p.cell_size, p.num_bins, L)
-            gpf = plan["n_main"] * plan["P"] + plan["Pt"]
-            for n in (3, 7):
-                straddle += gpf % 4 != 0
-                partial += (n * gpf) % 4 != 0
-            partial += gpf % 4 != 0                           # one face
-    assert straddle >= 8 and partial >= 8
+        got, idx = cells_features(gpu_ctx, x, lv)
+        want, widx = oracle_per_row(row_images, x, re, le, lv)
+        assert np.array_equal(widx, oracle_indices(x, L, re, le, RELS[lv])), (what, lv)
+        check_cells(got, idx, want, widx, "%s, level %d" % (what, lv))
+    if stepped:
+        detect_equals_stepped_levels(gpu_ctx, x, L, seed=6)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("case", sorted(CASES))
-def test_set_up_against_the_oracle(gpu_ctx, restore, case):
-    L, re, le = CASES[case]
-    gpu_ctx.set_hog_mode(SDM_HOG_COLUMNS)
+@pytest.mark.parametrize("case", sorted(EYE_CASES))
+def test_set_up_against_the_oracle(gpu_ctx, options, case):
+    L, re, le = EYE_CASES[case]
     gpu_ctx.set_model_geometry(L, re, le, SHIPPED)
-    rows = _rows(L, re, le, seed=1000 + L + len(re) * 7 + len(le))
+    rows = edge_rows(L, re, le, seed=1000 + L + len(re) * 7 + len(le))
     for n, pick in ((1, slice(1, 2)), (3, slice(2, 5)), (7, slice(0, 7))):
-        images = _noise(n, seed=40 + n)
+        images = noise(n, seed=40 + n)
         gpu_ctx.upload_images(images)
         gpu_ctx.set_sample_image_index(None)
         _check_against_the_oracle(gpu_ctx, rows[pick], L, re, le, images, "%s, %d faces" % (case, n))
 
 
 @pytest.mark.gpu
-def test_ragged_frames_with_differing_strides(gpu_ctx, restore):
+@pytest.mark.parametrize("frames", ["four-by-half-width", "seven-edge-rows"])
+def test_ragged_frames_with_differing_strides(gpu_ctx, options, frames):
+    """Frames of differing sizes and pitches, the samples in another order than the frames: the image borders stay per patch."""
     import torch
-    L, re, le = CASES["L22-eyes3+3"]
-    gpu_ctx.set_hog_mode(SDM_HOG_COLUMNS)
+    if frames == "four-by-half-width":       # RCR-22's eyes, one face per frame placed by its half-width
+        L, re, le = L22, RE22, LE22
+        sizes = [(256, 256, 256), (200, 240, 320), (256, 130, 384), (131, 133, 192)]      # h, w, pitch
+        order, seed = np.array([3, 1, 0, 2], np.int32), 591
+        x = np.stack([face(L, re, le, h0, c, seed=600 + i, spread=40.0)
+                      for i, (h0, c) in enumerate(((24, (60, 70)), (31, (130, 90)), (40, (128, 128)), (27, (70, 120))))])
+    else:                                    # three landmarks per eye, the edge rows at half size, and the stepped detect
+        L, re, le = EYE_CASES["L22-eyes3+3"]
+        sizes = [(256, 256, 256), (200, 240, 320), (256, 130, 384), (97, 256, 257), (256, 256, 512), (255, 201, 300), (131, 133, 192)]
+        order, seed = np.array([3, 1, 6, 0, 2, 5, 4], np.int32), 78
+        x = edge_rows(L, re, le, seed=77)
+        x[:, :L] *= np.float32(0.5)                          # (the smallest frame is 131 x 133)
+        x[:, L:] *= np.float32(0.5)
     gpu_ctx.set_model_geometry(L, re, le, SHIPPED)
-    x = _rows(L, re, le, seed=77)
-    x[:, :L] *= np.float32(0.5)                              # (the smallest frame is 131 x 133)
-    x[:, L:] *= np.float32(0.5)
-    sizes = [(256, 256, 256), (200, 240, 320), (256, 130, 384), (97, 256, 257), (256, 256, 512), (255, 201, 300), (131, 133, 192)]   # h, w, pitch
-    rng = np.random.default_rng(78)
+    rng = np.random.default_rng(seed)
     host = [rng.integers(0, 256, (h, pitch)).astype(np.uint8) for h, _, pitch in sizes]
     keep = [torch.from_numpy(a).cuda() for a in host]
     gpu_ctx.set_frames_device([t[:, :w] for t, (_, w, _) in zip(keep, sizes)])
-    order = np.array([3, 1, 6, 0, 2, 5, 4], np.int32)
     gpu_ctx.set_sample_image_index(order)
-    _check_against_the_oracle(gpu_ctx, x, L, re, le, [np.ascontiguousarray(host[i][:, :sizes[i][1]]) for i in order], "ragged")
-    gpu_ctx.upload_images(_noise(1, seed=1))                 # (the frames go out of scope)
+    _check_against_the_oracle(gpu_ctx, x, L, re, le, [host[i][:, :sizes[i][1]] for i in order], "ragged, " + frames,
+                              stepped=frames == "seven-edge-rows")
+    gpu_ctx.upload_images(noise(1, seed=1))                  # (the frames go out of scope)
 
 
 @pytest.mark.gpu
-def test_empty_patch_is_still_reported(gpu_ctx, restore):
-    gpu_ctx.set_hog_mode(SDM_HOG_COLUMNS)
-    gpu_ctx.upload_images(_noise(3, seed=9))
-    gpu_ctx.set_sample_image_index(None)
+def test_empty_patch_is_still_reported(gpu_ctx, options):
+    gpu_ctx.upload_images(noise(3, seed=9))
 
-    def codes(x):
+    def codes(x, detect=True):
+        """The status of the four levels' feature rows through the raw cells, then of a four-level detect."""
         out = []
         gpu_ctx.set_option("hog_split_store", 1)
         for lv in range(4):
@@ -189,12 +100,13 @@ def test_empty_patch_is_still_reported(gpu_ctx, restore):
             except SdmError as e:
                 out.append(e.code)
         gpu_ctx.set_option("hog_split_store", 0)
-        gpu_ctx.set_x(x)
-        try:
-            gpu_ctx.detect_batch()
-            out.append(0)
-        except SdmError as e:
-            out.append(e.code)
+        if detect:
+            gpu_ctx.set_x(x)
+            try:
+                gpu_ctx.detect_batch()
+                out.append(0)
+            except SdmError as e:
+                out.append(e.code)
         return out
 
     # one landmark: both eye centres are that landmark, the inter-eye distance is 0
@@ -203,46 +115,34 @@ def test_empty_patch_is_still_reported(gpu_ctx, restore):
         gpu_ctx.set_regressor(lv, np.zeros((gpu_ctx.feature_dim(lv), 2), np.float32))
     assert codes(np.array([[100.25, 90.5], [3.0, 250.0], [128.0, 128.0]], np.float32)) == [-4] * 5
     # a face of two pixels between two good ones: rel * IED / 2 < 1 / 2 at every level
-    L, re, le = CASES["L22-eyes3+3"]
+    L, re, le = EYE_CASES["L22-eyes3+3"]
     gpu_ctx.set_model_geometry(L, re, le, SHIPPED)
     for lv in range(4):
         gpu_ctx.set_regressor(lv, np.zeros((gpu_ctx.feature_dim(lv), 2 * L), np.float32))
-    x = _rows(L, re, le, seed=5)[:3]
+    x = edge_rows(L, re, le, seed=5)[:3]
     x[1] = (128.0 + (x[1] - 128.0) * np.float32(0.01)).astype(np.float32)
     assert all(float(np.float32(r)) * orc.get_ied(x[1], re, le) / 2.0 < 0.49 for r in RELS)
     assert codes(x) == [-4] * 5
     # and the same context goes on working
-    assert codes(_rows(L, re, le, seed=5)[:3]) == [0] * 5
-
-
-def _sweep_rows(rel, ks):
-    """Rows of L = 5 landmarks, right eye = landmark 0 at (d, 128), left eye = landmark 1 at (0, 128): the float difference of the
-    eye centres is d itself.  d runs over the float32 neighbours of the values that put t = rel / 2 * d on each target."""
-    f32 = np.float32
-    half = f32(f32(rel) * f32(0.5))
-    rows, ds = [], []
-    for k in ks:
-        for target in (k + 0.5, k + 0.5 - 2.0 ** -10, k + 0.5 + 2.0 ** -10):
-            d0 = f32(target / float(half))
-            b0 = int(np.array(d0, f32).view(np.int32))
-            for step in range(-3, 4):
-                ds.append(np.array(b0 + step, np.int32).view(f32))
-    ds = np.array(ds, f32)
-    for d in ds:
-        xs = np.array([d, 0.0, 100.0, 128.25, 160.5], f32)
-        ys = np.array([128.0, 128.0, 90.0, 128.5, 170.0], f32)
-        rows.append(np.concatenate([xs, ys]))
-    t = (half * ds).astype(f32)
-    return np.stack(rows).astype(f32), ds, t
+    assert codes(edge_rows(L, re, le, seed=5)[:3]) == [0] * 5
+    # the same with RCR-22's eyes and faces of half-widths 30, 36 and 41, the feature rows alone
+    gpu_ctx.set_model_geometry(L22, RE22, LE22, SHIPPED)
+    gpu_ctx.upload_images(noise(3, seed=611))
+    good = np.stack([face(L22, RE22, LE22, h0, (128, 128), seed=620 + i) for i, h0 in enumerate((30, 36, 41))])
+    bad = good.copy()
+    bad[1] = (128.0 + (bad[1] - 128.0) * np.float32(0.01)).astype(np.float32)
+    assert all(r * orc.get_ied(bad[1], RE22, LE22) / 2.0 < 0.49 for r in RELS)
+    assert codes(bad, detect=False) == [-4] * 4
+    assert codes(good, detect=False) == [0] * 4
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("level", [0, 1, 2, 3])
-def test_half_width_sweep_around_the_ties(gpu_ctx, restore, level):
+def test_half_width_sweep_around_the_ties(gpu_ctx, options, level):
     L, re, le = 5, [0], [1]
     rel, S = RELS[level], SIZES[level]
     ks = sorted({0, 1, 3, S // 2 - 1, S // 2, S // 2 + 1, S, 100, 126, 127})
-    x, ds, t = _sweep_rows(rel, ks)
+    x, ds, t = tie_sweep_rows(rel, ks)
     # the sweep is the one intended: t on a tie, within a float step of it on either side, and on both sides of the guard's edges
     frac = t - np.floor(t)
     assert (frac == 0.5).sum() >= len(ks) // 2 and (t[frac == 0.5] < 128).all()
@@ -254,15 +154,12 @@ def test_half_width_sweep_around_the_ties(gpu_ctx, restore, level):
     assert want_h.min() == 0 and want_h.max() == 128
     keep = want_h >= 1                                       # (h = 0 is the empty patch: reported, see test_empty_patch_is_still_reported)
     x, want_h = x[keep], want_h[keep]
-    gpu_ctx.set_hog_mode(SDM_HOG_COLUMNS)
     gpu_ctx.set_model_geometry(L, re, le, SHIPPED)
-    gpu_ctx.upload_images(_noise(4, seed=31))
+    gpu_ctx.upload_images(noise(4, seed=31))
     gpu_ctx.set_sample_image_index((np.arange(x.shape[0]) % 4).astype(np.int32))
 
-    gpu_ctx.set_option("hog_split_store", 1)
-    gpu_ctx.set_x(x)
-    f = gpu_ctx.hog_features(level, fetch=True)
-    idx = gpu_ctx.patch_indices()
+    options("hog_split_store", 1)
+    f, idx = cells_features(gpu_ctx, x, level)
     print("level %d: %d rows, h %d .. %d" % (level, x.shape[0], want_h.min(), want_h.max()))
     assert np.isfinite(f).all() and np.array_equal(idx[:, 0], want_h)
     assert np.array_equal(idx[:, 1:], [[orc.cv_round(c) for c in r] for r in x])

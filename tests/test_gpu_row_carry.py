@@ -2,16 +2,16 @@
 pixel row loads and filters only the UPPER of its two source rows and takes the lower one from what the previous pixel row holds.
 Which half-widths h qualify is decided per (level, h) from cv::resize's vertical taps when the geometry is set.
 
-CPU part: the taps restated here reproduce the oracle's cv::resize bit for bit (so they ARE the oracle's taps), and from them every
-h with 2h <= S of the shipped levels is one-load eligible; the exact-2x reduction never is.
+CPU part: the taps restated in tests/hog_taps_ref.py reproduce the oracle's cv::resize bit for bit (so they ARE the oracle's taps),
+and from them every h with 2h <= S of the shipped levels is one-load eligible; the exact-2x reduction never is.
 
 GPU part.  (1) The table the library built on the device (read back with sdm_debug_hog_taps), all 128 half-widths of the four
 shipped levels: its taps are the restated ones, its eligibility flag is one_load_eligible() and its carry masks are the expected
 ones; the cells launch of levels 1-3 is an instance that holds the one-load loop.  (2) Landmark rows scaled so that h takes every
 integer from 1 to S (2h = 2S) at each shipped level, with patches hanging off every image border and wholly outside the image,
 in SDM_HOG_COLUMNS mode with the raw-cells launch asserted to be the one in use.  Patch indices are the oracle's.  The float results
-of the packed kernel were never the oracle's bits (the separable column sums of its mode: tests/test_gpu_parity.py::check_features
-bounds them at 1e-6 absolute, 5e-7 relative L2), so they are held to that standing bound against the oracle and to BIT IDENTITY
+of the packed kernel were never the oracle's bits (the separable column sums of its mode), so they are held to the packed mode's
+standing bound against the oracle (pixel_kernel_cases.PACKED_MAX_ABS, PACKED_REL_L2) and to BIT IDENTITY
 between the one-load and the two-load loop (option hog_two_load) -- feature rows from the raw cells, the landmark update of
 sdm_detect_level, and the landmarks bench.py dumps for its own batch.  That bit comparison is the test of the new loop's arithmetic.
 The resized ROI bytes of the debug read-back are compared with the oracle as well, but sdm_debug_patch runs a kernel of its own:
@@ -23,58 +23,15 @@ import sys
 import numpy as np
 import pytest
 
+from hog_taps_ref import expected_table, one_load_eligible, resize_taps, resize_with_taps
 from oracle import sdm_oracle as orc
-from superviseddescent_amd import HoGParam, ibug, synth
-from superviseddescent_amd._lib import SDM_HOG_COLUMNS
+from pixel_kernel_cases import (L22, LE22, O_SHIPPED, PACKED_MAX_ABS, PACKED_REL_L2, RE22, SHIPPED, SIZES, bits, options, scaled_rows,
+                                smooth_faces)  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-IDS = ibug.RCR22_IDS
-RE, LE = ibug.eye_indices(IDS)
-L = len(IDS)
-SHIPPED = [HoGParam(*p) for p in ibug.SHIPPED_HOG_PARAMS]
-O_SHIPPED = [orc.HoGParam(*p) for p in ibug.SHIPPED_HOG_PARAMS]
-SIZES = [p.num_cells * p.cell_size for p in SHIPPED]          # S = 55, 50, 40, 30
 
 
-# ---------------------------------------------------------------------------------------------- cv::resize's taps, restated
-def resize_taps(S, h):
-    """Per destination coordinate d of the 2h -> S bilinear 8-bit resize: unclamped source index, the two 11-bit weights, and the
-    two source ROWS of the vertical pass (clipped to the patch).  None for the exact-2x reduction (box average, no taps)."""
-    sw = 2 * h
-    if sw == 2 * S:
-        return None
-    scale = 1.0 / (float(S) / float(sw))
-    d = np.arange(S, dtype=np.float64)
-    f = ((d + 0.5) * scale - 0.5).astype(np.float32)
-    s0 = np.floor(f).astype(np.int64)
-    f = (f - s0.astype(np.float32)).astype(np.float32)
-    c0 = np.clip(np.rint((np.float32(1.0) - f) * np.float32(2048.0)), -32768, 32767).astype(np.int64)
-    c1 = np.clip(np.rint(f * np.float32(2048.0)), -32768, 32767).astype(np.int64)
-    return s0, c0, c1, np.clip(s0, 0, sw - 1), np.clip(s0 + 1, 0, sw - 1)
-
-
-def resize_with_taps(src, S, taps):
-    """orc_resize_u8_linear's arithmetic with the taps above: horizontal taps clamped in the table, vertical rows clipped."""
-    sw = src.shape[1]
-    s0, c0, c1, r0, r1 = taps
-    sx, a0, a1 = s0.copy(), c0.copy(), c1.copy()
-    lo, hi = sx < 0, sx >= sw - 1
-    sx[lo], a0[lo], a1[lo] = 0, 2048, 0
-    sx[hi], a0[hi], a1[hi] = sw - 1, 2048, 0
-    sx1 = np.minimum(sx + 1, sw - 1)
-    H = src.astype(np.int64)[:, sx] * a0 + src.astype(np.int64)[:, sx1] * a1          # [source row][dx]
-    out = (((c0[:, None] * (H[r0] >> 4)) >> 16) + ((c1[:, None] * (H[r1] >> 4)) >> 16) + 2) >> 2
-    return out.astype(np.uint8)
-
-
-def one_load_eligible(S, h):
-    taps = resize_taps(S, h)
-    if taps is None:
-        return False
-    _, _, _, r0, r1 = taps
-    return bool(np.all((r0[1:] == r0[:-1]) | (r0[1:] == r1[:-1])))
-
-
+# ---------------------------------------------------------------------------------------------- CPU: the restated taps (tests/hog_taps_ref.py)
 @pytest.mark.parametrize("S", SIZES)
 def test_restated_taps_are_the_oracles(built, S):
     rng = np.random.default_rng(S)
@@ -104,62 +61,9 @@ def test_enlarged_patches_are_one_load_eligible(built, S):
 
 
 # ---------------------------------------------------------------------------------------------- GPU
-def _faces(n=192):
-    images, boxes, gt = synth.make_faces(n, seed=2024)
-    _, x0, _ = synth.make_samples(boxes, gt, IDS, n_perturb=0, seed=2025)
-    return images, x0
-
-
-def _scaled_rows(x0, level):
-    """One row per half-width h = 1 .. S of the level (the landmarks of a face scaled about their centroid so that
-    round(rel * ied / 2) = h), then rows hanging off each image border and one wholly outside, at half-widths around 2h = S."""
-    rel, S = float(np.float32(SHIPPED[level].relative_patch_size)), SIZES[level]
-
-    def row(s, h, dx=0.0, dy=0.0):
-        xs, ys = x0[s, :L].astype(np.float64), x0[s, L:].astype(np.float64)
-        k = (2.0 * h / rel) / orc.get_ied(x0[s], RE, LE)
-        cx, cy = xs.mean(), ys.mean()
-        return np.concatenate([128.0 + dx + (xs - cx) * k, 128.0 + dy + (ys - cy) * k]).astype(np.float32)
-
-    rows, hs = [], []
-    for h in range(1, S + 1):
-        rows.append(row(h % x0.shape[0], h)); hs.append(h)
-    for h in sorted({1, 3, (S - 1) // 2, S // 2, (S + 1) // 2, S // 2 + 1, S - 1, S}):
-        for dx, dy in ((-126.0, 0.0), (126.0, 0.0), (0.0, -126.0), (0.0, 126.0), (-125.0, 127.0), (-700.0, -700.0)):
-            rows.append(row((7 * h) % x0.shape[0], h, dx, dy)); hs.append(h)
-    return np.stack(rows), np.array(hs)
-
-
-def expected_table(S, h):
-    """Columns 2..7 of the library's table for one half-width: sy0, sy1, b0 << 12, b1 << 12, carry mask, eligible (rows d < S)."""
-    if h == 0:                                   # the empty patch is given a 1-pixel source; never eligible
-        scale = 1.0 / (float(S) / 1.0)
-        f = ((np.arange(S) + 0.5) * scale - 0.5).astype(np.float32)
-        s0 = np.floor(f).astype(np.int64)
-        f = (f - s0.astype(np.float32)).astype(np.float32)
-        c0 = np.rint((np.float32(1.0) - f) * np.float32(2048.0)).astype(np.int64)
-        c1 = np.rint(f * np.float32(2048.0)).astype(np.int64)
-        r0, r1 = np.clip(s0, 0, 0), np.clip(s0 + 1, 0, 0)
-        return s0, c0, c1, r0, r1, np.zeros(S, np.int64), 0
-    taps = resize_taps(S, h)
-    if taps is None:                             # exact 2x: rows 2d, 2d + 1 with weights 1024; the index and horizontal weights as computed
-        sw = 2 * h
-        f = ((np.arange(S) + 0.5) * 2.0 - 0.5).astype(np.float32)
-        s0 = np.floor(f).astype(np.int64)
-        f = (f - s0.astype(np.float32)).astype(np.float32)
-        c0 = np.rint((np.float32(1.0) - f) * np.float32(2048.0)).astype(np.int64)
-        c1 = np.rint(f * np.float32(2048.0)).astype(np.int64)
-        return s0, c0, c1, 2 * np.arange(S), 2 * np.arange(S) + 1, None, 0
-    s0, c0, c1, r0, r1 = taps
-    mask = np.zeros(S, np.int64)
-    mask[1:] = np.where(r0[1:] == r1[:-1], -1, 0)
-    return s0, c0, c1, r0, r1, mask, int(one_load_eligible(S, h))
-
-
 @pytest.mark.gpu
-def test_the_librarys_table_is_the_oracles_eligibility(gpu_ctx):
-    gpu_ctx.set_hog_mode(SDM_HOG_COLUMNS)
-    gpu_ctx.set_model_geometry(L, RE, LE, SHIPPED)
+def test_the_librarys_table_is_the_oracles_eligibility(gpu_ctx, options):
+    gpu_ctx.set_model_geometry(L22, RE22, LE22, SHIPPED)
     for level, S in enumerate(SIZES):
         table, info = gpu_ctx.debug_hog_taps(level)
         assert info["cells_launch"] and not info["two_load_option"]
@@ -189,28 +93,16 @@ def test_the_librarys_table_is_the_oracles_eligibility(gpu_ctx):
         print("level %d S %d: one-load eligible half-widths 1..%d" % (level, S, eligible[-1]))
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-@pytest.fixture
-def two_load_switch(gpu_ctx):
-    yield lambda on: gpu_ctx.set_option("hog_two_load", 1 if on else 0)
-    gpu_ctx.set_option("hog_two_load", 0)
-    gpu_ctx.set_option("hog_split_store", 0)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("level", [0, 1, 2, 3])
-def test_half_width_sweep(gpu_ctx, two_load_switch, level):
-    images, x0 = _faces()
-    x, hs = _scaled_rows(x0, level)
+def test_half_width_sweep(gpu_ctx, options, level):
+    images, x0 = smooth_faces()
+    x, hs = scaled_rows(x0, level)
     n = x.shape[0]
     idx = (np.arange(n) % images.shape[0]).astype(np.int32)
     S = SIZES[level]
     assert {S // 2, (S + 1) // 2, S // 2 + 1} <= set(hs.tolist())          # 2h = S - 1 / S / S + 1, whichever are even
-    gpu_ctx.set_hog_mode(SDM_HOG_COLUMNS)
-    gpu_ctx.set_model_geometry(L, RE, LE, SHIPPED)
+    gpu_ctx.set_model_geometry(L22, RE22, LE22, SHIPPED)
     gpu_ctx.upload_images(images)
     gpu_ctx.set_sample_image_index(idx)
     table, info = gpu_ctx.debug_hog_taps(level)
@@ -218,36 +110,34 @@ def test_half_width_sweep(gpu_ctx, two_load_switch, level):
     assert info["one_load_instance"] == (level >= 1)
     n_one_load = int(sum(int(table[h, 0, 7]) for h in hs)) if info["one_load_instance"] else 0
     assert (n_one_load > 0) == (level >= 1)
-    want, widx = orc.hog_features_batch(images, idx, x, RE, LE, O_SHIPPED[level], n_threads=os.cpu_count() or 1, want_idx=True)
+    want, widx = orc.hog_features_batch(images, idx, x, RE22, LE22, O_SHIPPED[level], n_threads=os.cpu_count() or 1, want_idx=True)
     assert np.array_equal(widx[:, 0], hs)                                  # the sweep is the one intended
-    try:
-        gpu_ctx.set_option("hog_split_store", 1)          # feature rows through the raw cells of the CELLS pixel kernel
-        got = {}
-        for two in (False, True):
-            two_load_switch(two)
-            assert gpu_ctx.debug_hog_taps(level)[1]["two_load_option"] == two
-            gpu_ctx.set_x(x)
-            got[two] = gpu_ctx.hog_features(level, fetch=True)
-            assert np.array_equal(gpu_ctx.patch_indices(), widx)
-        # the landmark update of the detect path (cells -> descriptor x regressor), both loops
-        rng = np.random.default_rng(5)
-        R = (rng.standard_normal((gpu_ctx.feature_dim(level), 2 * L)) * 1e-3).astype(np.float32)
-        gpu_ctx.set_regressor(level, R)
-        upd = {}
-        for two in (False, True):
-            two_load_switch(two)
-            gpu_ctx.set_x(x)
-            gpu_ctx.detect_level(level)
-            upd[two] = gpu_ctx.get_x()
-    finally:
-        gpu_ctx.set_option("hog_split_store", 0)
-        two_load_switch(False)
+    options("hog_split_store", 1)                             # feature rows through the raw cells of the CELLS pixel kernel
+    got = {}
+    for two in (False, True):
+        options("hog_two_load", int(two))
+        assert gpu_ctx.debug_hog_taps(level)[1]["two_load_option"] == two
+        gpu_ctx.set_x(x)
+        got[two] = gpu_ctx.hog_features(level, fetch=True)
+        assert np.array_equal(gpu_ctx.patch_indices(), widx)
+    # the landmark update of the detect path (cells -> descriptor x regressor), both loops
+    rng = np.random.default_rng(5)
+    R = (rng.standard_normal((gpu_ctx.feature_dim(level), 2 * L22)) * 1e-3).astype(np.float32)
+    gpu_ctx.set_regressor(level, R)
+    upd = {}
+    for two in (False, True):
+        options("hog_two_load", int(two))
+        gpu_ctx.set_x(x)
+        gpu_ctx.detect_level(level)
+        upd[two] = gpu_ctx.get_x()
+    options("hog_split_store", 0)
+    options("hog_two_load", 0)
     diff = np.abs(got[False] - want).max()
     rel = float(np.linalg.norm((got[False] - want).astype(np.float64)) / np.linalg.norm(want.astype(np.float64)))
     print("level %d: %d rows (%d on the one-load loop), features against the oracle max abs %.3g rel L2 %.3g" % (level, n, n_one_load, diff, rel))
-    assert np.array_equal(_bits(got[False]), _bits(got[True]))
-    assert np.array_equal(_bits(upd[False]), _bits(upd[True]))
-    assert diff <= 1e-6 and rel <= 5e-7          # tests/test_gpu_parity.py::check_features, packed mode
+    assert np.array_equal(bits(got[False]), bits(got[True]))
+    assert np.array_equal(bits(upd[False]), bits(upd[True]))
+    assert diff <= PACKED_MAX_ABS and rel <= PACKED_REL_L2
     # resized ROI bytes through the debug read-back (a kernel of its own, see above): around 2h = S, a border row and the row outside the image
     gpu_ctx.set_x(x)
     picks = [S // 2 - 1, S // 2, S // 2 + 1, S - 1, n - 6, n - 1]
@@ -255,7 +145,7 @@ def test_half_width_sweep(gpu_ctx, two_load_switch, level):
         h = int(hs[s])
         for lm in (0, 13):
             rsz, _, _, _ = gpu_ctx.debug_patch(level, s, lm, SHIPPED[level])
-            cx, cy = orc.cv_round(x[s, lm]), orc.cv_round(x[s, lm + L])
+            cx, cy = orc.cv_round(x[s, lm]), orc.cv_round(x[s, lm + L22])
             roi = np.zeros((2 * h, 2 * h), np.uint8)
             ys, xs = np.mgrid[cy - h:cy + h, cx - h:cx + h]
             ok = (ys >= 0) & (ys < 256) & (xs >= 0) & (xs < 256)
@@ -274,5 +164,5 @@ def test_both_loops_on_the_bench_batch(built, tmp_path):
                            env=dict(os.environ, SDM_HOG_TWO_LOAD=two))
         assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
         out[two] = np.load(d / "landmarks.npy")
-    assert out["0"].shape == (1024, 2 * L) and np.isfinite(out["0"]).all()
+    assert out["0"].shape == (1024, 2 * L22) and np.isfinite(out["0"]).all()
     assert out["0"].tobytes() == out["1"].tobytes()
