@@ -383,6 +383,12 @@ int sdm_debug_hog_plan(int num_cells, int cell_size, int num_bins, int num_landm
 /* cut[num_landmarks]: 1 where the landmark's patch is cut by a pass boundary of that plan (its raw cell histograms arrive in two
  * parts, csrc/sdm_hog_packed.hip CELLS form); host only.  Returns SDM_ERR_INVALID when the geometry has no packed instance. */
 int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_landmarks, int* cut);
+/* Tests: the band-slot weights {slot 0, slot 1} of the resized-ROI rows d < num_cells * cell_size (hog.c:697-704; zero for the cell
+ * rows -1 and num_cells, swapped on odd bands; rows from num_cells * cell_size on are zero) as the one definition of them gives them
+ * (csrc/sdm_kernels.h: packed_row_const) -- for the cell sizes with specialised pixel-kernel instances the values the COMPILER
+ * evaluated, which are the constants the detect instances multiply by; host only.  SDM_ERR_INVALID unless
+ * 1 <= num_cells * cell_size <= 64. */
+int sdm_debug_hog_band_weights(int cell_size, int num_cells, float out[64][2]);
 /* Tests: the level's table of cv::resize taps as the device built it at sdm_set_model_geometry (csrc/sdm_hog_packed.hip,
  * taps_table_kernel): table[128 half-widths][64 coordinates][8] ints = {s0, c0 | c1 << 16, sy0, sy1, b0 << 12, b1 << 12, carry mask of
  * the row, half-width is one-load eligible}.  info3 = {the level's HOG launch of detect is the raw-cells launch as the context stands

@@ -141,6 +141,18 @@ int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_l
     return SDM_OK;
 }
 
+int sdm_debug_hog_band_weights(int cell_size, int num_cells, float out[64][2])
+{
+    if (!out || cell_size < 1 || num_cells < 1 || (long long)num_cells * cell_size > 64) return fail(SDM_ERR_INVALID, "bad arguments");
+    const HogRowConst* compiled = sdm_hog_compiled_row_consts(cell_size, num_cells);
+    memset(out, 0, 64 * 2 * sizeof(float));
+    for (int d = 0; d < num_cells * cell_size; ++d) {
+        const HogRowConst rc = compiled ? compiled[d] : packed_row_const(d, cell_size, num_cells);
+        out[d][0] = rc.ws0; out[d][1] = rc.ws1;
+    }
+    return SDM_OK;
+}
+
 int sdm_debug_hog_taps(sdm_ctx* c, int level, int* table, int* info3)
 {
     if (!c || level < 0 || level >= (int)c->levels.size() || !table || !info3) return fail(SDM_ERR_INVALID, "bad arguments");

@@ -4,18 +4,15 @@
 namespace sdm_capi {
 
 // the kernels' per-coordinate arithmetic (hog.c:697-704), IEEE on the host: {weight of band slot 0, of band slot 1, cell index, upper weight}
+// (packed_row_const, sdm_kernels.h: the one definition, which the detect instances of the pixel kernel evaluate at compile time)
 void fill_row_tab(HogLevelDev& lv)
 {
     for (int d = 0; d < 64 && d < lv.S; ++d) {
-        const float hx = (float)((d + 0.5) / (double)lv.cell - 0.5);
-        int b = (int)hx;
-        if (!(hx >= 0.0f || (float)b == hx)) b -= 1;                        // vl_floor_f
-        const float w2 = hx - (float)b, w1 = (float)(1.0 - w2);
-        const float wlo = b >= 0 ? w1 : 0.0f, whi = b + 1 <= lv.C - 1 ? w2 : 0.0f;   // the cell rows -1 and C do not exist
-        lv.row_tab[d][0] = (b & 1) ? whi : wlo;                              // band b lives in slot b & 1
-        lv.row_tab[d][1] = (b & 1) ? wlo : whi;
-        memcpy(&lv.row_tab[d][2], &b, sizeof(int));
-        lv.row_tab[d][3] = w2;
+        const HogRowConst rc = packed_row_const(d, lv.cell, lv.C);
+        lv.row_tab[d][0] = rc.ws0;
+        lv.row_tab[d][1] = rc.ws1;
+        memcpy(&lv.row_tab[d][2], &rc.band, sizeof(int));
+        lv.row_tab[d][3] = rc.w2;
     }
 }
 

@@ -86,16 +86,77 @@ __host__ __device__ inline size_t packed_lds_bytes(int C, int O, int S, int hist
 {
     return al16(HP_ROWS_BYTES(O)) + packed_rowtab_bytes(S, spec) + al16((size_t)pair_slots * 4) + hist_slots * al16(HP_HIST_BYTES(O, C * C));
 }
-// specialised instances: the band-slot weights {ws0, ws1} of every pixel row (level constants, hog.c:697-704) in ONE table per
-// workgroup behind the waves' regions, read per row with a broadcast 8-byte LDS read straight into the register pair the
-// packed multiply-add takes (scalar loads of them cannot stay in SGPRs over an unrolled ROI: the compiler spilled them to
-// vector lanes and paid two v_readlane per row)
-// (rows 0 and S - 1 have no gradient: the table holds rows 1 .. S - 2 -- at S = 50 the 16 bytes that let eight workgroups share a CU's LDS)
+// specialised instances of the feature-row form: the band-slot weights {ws0, ws1} of every pixel row (level constants,
+// hog.c:697-704) in ONE table per workgroup behind the waves' regions, read per row with a broadcast 8-byte LDS read straight
+// into the register pair the packed multiply-add takes (scalar loads of them cannot stay in SGPRs over an unrolled ROI: the
+// compiler spilled them to vector lanes and paid two v_readlane per row)
+// (rows 0 and S - 1 have no gradient: the table holds rows 1 .. S - 2)
+// The detect instances (raw cells, 4 orientations) have no such table: the pairs are compile-time constants (packed_row_const,
+// sdm_kernels.h) that the row loop takes from scalar registers -- HpBandPairs below.
+__host__ __device__ constexpr bool hp_const_weights(int O, int cell, bool cells, bool raw) { return cells && raw && O == 4 && cell > 0; }
 __host__ __device__ inline size_t packed_wstab_bytes(int S) { return al16((size_t)(S - 2) * 8); }
-__host__ __device__ inline size_t packed_wg_lds_bytes(int C, int O, int S, int hist_slots, bool spec, int pair_slots = 0)
+__host__ __device__ inline size_t packed_wg_lds_bytes(int C, int O, int S, int hist_slots, bool spec, int pair_slots = 0, bool wstab = true)
 {
-    return packed_lds_bytes(C, O, S, hist_slots, spec, pair_slots) * HP_WAVES + (spec ? packed_wstab_bytes(S) : 0);
+    return packed_lds_bytes(C, O, S, hist_slots, spec, pair_slots) * HP_WAVES + (spec && wstab ? packed_wstab_bytes(S) : 0);
 }
+
+// The band-slot weights of a detect instance, sorted out at compile time.  Rows 1 .. S - 2 multiply by the pair {ws0, ws1} of
+// packed_row_const (x 8 where the folds are float16: the column sums carry that factor, exactly).
+//  * A row with two non-zero weights takes its pair from a PAIR of scalar registers, the operand of the packed multiply-add.  Two
+//    rows whose pairs hold the same two bit patterns -- in either slot order: a row of an even band and the matching row of an odd
+//    one -- share the registers; `swap` says that the row wants them the other way round, which the instruction's operand
+//    selectors do.
+//  * A row with ONE non-zero weight -- the half cells at either end, whose other cell row (-1 or C) does not exist, and the centre
+//    row of an odd cell -- changes one column sum only: fma(0, g, q) is q for a finite g and a column sum q, which is never -0.  It
+//    takes a plain multiply-add on that slot, with ONE scalar register: an element of a pair where the bits are the same, else a
+//    register of its own.
+// What this is for: the hardware admits a workgroup of four waves by its scalar registers too, in steps of sixteen -- eight per CU up
+// to 80, seven up to 96 -- and the compiler's occupancy figure does not know (profiles/hog_row_weights.txt).  Only cell 8 divides
+// exactly; at the other cell sizes the fraction of hx is rounded at the magnitude of hx, so the same position in another band is
+// often another bit pattern: 14 / 12 / 4 / 9 pairs and 4 / 1 / 0 / 1 single registers at cells 11 / 10 / 8 / 6 (every row a pair: 23 / 19 / 7 /
+// 12 pairs, which cost cells 11 and 10 a workgroup per CU and with it the whole gain).
+template <int CELL, int C, bool X8>
+struct HpBandPairs {
+    static constexpr int S = C * CELL;
+    int n = 0, n1 = 0;
+    float a[S] = {}, b[S] = {};      // pair k as the registers hold it
+    float one[S] = {};               // single register k
+    int idx[S] = {};                 // row d -> its pair; a row of one weight: the pair it borrows from, or -1 - (its single register)
+    bool swap[S] = {};               // row d takes {b, a}; a row of one weight that borrows: element b
+    int slot[S] = {};                // row d has one weight, for this slot; -1: two
+    constexpr HpBandPairs()
+    {
+        float w[S][2] = {};
+        for (int d = 1; d < S - 1; ++d) {
+            const HogRowConst rc = packed_row_const(d, CELL, C);
+            w[d][0] = rc.ws0 * (X8 ? 8.0f : 1.0f); w[d][1] = rc.ws1 * (X8 ? 8.0f : 1.0f);
+            slot[d] = w[d][1] == 0.0f ? 0 : (w[d][0] == 0.0f ? 1 : -1);
+        }
+        for (int d = 1; d < S - 1; ++d) {      // (weights are never NaN and never -0: == compares the bits)
+            if (slot[d] >= 0) continue;
+            int k = 0;
+            bool sw = false;
+            for (; k < n; ++k) {
+                if (a[k] == w[d][0] && b[k] == w[d][1]) break;
+                if (a[k] == w[d][1] && b[k] == w[d][0]) { sw = true; break; }
+            }
+            if (k == n) { a[n] = w[d][0]; b[n] = w[d][1]; ++n; }
+            idx[d] = k; swap[d] = sw;
+        }
+        for (int d = 1; d < S - 1; ++d) {
+            if (slot[d] < 0) continue;
+            const float v = w[d][slot[d]];
+            int k = 0;
+            for (; k < n; ++k)
+                if (a[k] == v || b[k] == v) break;
+            if (k < n) { idx[d] = k; swap[d] = a[k] != v; continue; }
+            for (k = 0; k < n1; ++k)
+                if (one[k] == v) break;
+            if (k == n1) one[n1++] = v;
+            idx[d] = -1 - k;
+        }
+    }
+};
 
 // arithmetic type of the packed kernel's normalisation (hog.c:930-1052 computes the block factors and the clamped products in
 // double and stores floats).  In float -- v_rsq_f32 for 1 / sqrt, f32 products -- the features differ from the oracle exactly as
@@ -242,7 +303,8 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     i32x4* rowtab = (i32x4*)(lds + al16(HP_ROWS_BYTES(O)));                          // [S (+ 2)] {row offset 0, row offset 1, weight 0 << 12, weight 1 << 12}
     int* sptab = (int*)(lds + al16(HP_ROWS_BYTES(O)) + packed_rowtab_bytes(S, SPEC));      // [NPAIR] byte offset of the pair's spare source row (PAIR)
     float* hist = (float*)(lds + al16(HP_ROWS_BYTES(O)) + packed_rowtab_bytes(S, SPEC) + al16((size_t)NPAIR * 4));   // [nslots][2O][CC]
-    f32x2* wstab = (f32x2*)(smem + (size_t)HP_WAVES * packed_lds_bytes(C, O, S, nslots, SPEC, NPAIR));      // [S - 2] per workgroup (SPEC): rows 1 .. S - 2
+    constexpr bool WCONST = hp_const_weights(TO, CELL, CELLS, RAW);      // the band-slot weights are constants in scalar registers: no table
+    f32x2* wstab = (f32x2*)(smem + (size_t)HP_WAVES * packed_lds_bytes(C, O, S, nslots, SPEC, NPAIR));      // [S - 2] per workgroup (SPEC && !WCONST): rows 1 .. S - 2
     constexpr int HSTR = (2 * O * CC * 4 + 15) / 16 * 4;      // floats per histogram slot (16-byte multiple)
     unsigned char* scratch = lds;      // the finish scratch overlays the column rows, which are all zero between two passes
     auto hist_slot = [&](int patch_slot) { return nslots == 2 ? (patch_slot & 1) : patch_slot % 3; };
@@ -265,7 +327,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         for (int i = 0; i < 4; ++i)
             wq1[i] = F16F ? ((const f32x4*)(plan.wb16 + ((size_t)pt1 * 64 + lane) * 32))[i] : ((const f32x4*)(plan.wb + ((size_t)pt1 * 64 + lane) * 16))[i];
         pinfo1 = *(const i32x4*)(plan.pass_info + pt1 * 4);      // wave-uniform, 16 bytes
-        if (CELL > 0) wsrow = (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]};
+        if (CELL > 0 && !WCONST) wsrow = (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]};
     }
 
     // ---- group geometry (wave-uniform; adaptive_vlhog.hpp:123) ----------------------------------------------------------
@@ -339,7 +401,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     // 4 orientations, specialised instances: band folds on the 16-bit matrix cores (column sums x 8 and weights x 2^10 as two float16
     // pieces each, all four piece products)
     static_assert(!F16F || CELL * 361 * 8 < 65504, "float16 folds: a band slot's column sum (<= cell x 255 sqrt 2) x 8 must stay a float16 number");      // (column sums carry a factor 8: exact, undone with the weights' 2^10 after the fold)
-    if (SPEC && lane >= 1 && lane < S - 1) wstab[lane - 1] = (CELLS ? wsrow : (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]}) * (F16F ? 8.0f : 1.0f);
+    if (SPEC && !WCONST && lane >= 1 && lane < S - 1) wstab[lane - 1] = (CELLS ? wsrow : (f32x2){lv.row_tab[lane][0], lv.row_tab[lane][1]}) * (F16F ? 8.0f : 1.0f);
     if (!SPEC && S + 2 > 64 && lane < S + 2 - 64) {
         i32x4 last;
 #pragma unroll
@@ -354,6 +416,34 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
     // subtraction; with the register it stays the one v_fma_mix_f32 of the fold's operand split
     float neg_one = -1.0f;
     if constexpr (CELLS) asm volatile("" : "+s"(neg_one));
+    // the band-slot weight pairs of the instance, each pinned in a pair of scalar registers for the whole pass (opaque to the
+    // optimiser, as neg_one: a constant the compiler can see through it is free to re-materialise where it is used, two scalar moves
+    // of a literal per pixel row), and the single registers of the rows with one weight
+    constexpr HpBandPairs<WCONST ? CELL : 1, TC, F16F> BP{};
+    f32x2 wpair[BP.n > 0 ? BP.n : 1];
+    float wone[BP.n1 > 0 ? BP.n1 : 1];
+    if constexpr (WCONST) {
+#pragma unroll
+        for (int k = 0; k < BP.n; ++k) {
+            wpair[k] = (f32x2){BP.a[k], BP.b[k]};
+            asm volatile("" : "+s"(wpair[k]));
+        }
+#pragma unroll
+        for (int k = 0; k < BP.n1; ++k) {
+            wone[k] = BP.one[k];
+            asm volatile("" : "+s"(wone[k]));
+        }
+    }
+    // the column sums of a lane with the magnitude g of pixel row yy added: {q.x + ws0 g, q.y + ws1 g} (yy = 0: no row is pending, q)
+    auto add_row = [&](const int yy, const float g, const f32x2 q) __attribute__((always_inline)) -> f32x2 {
+        if (yy <= 0) return q;
+        if (BP.slot[yy] < 0) {
+            const f32x2 p = wpair[BP.idx[yy]];
+            return __builtin_elementwise_fma(BP.swap[yy] ? (f32x2){p.y, p.x} : p, (f32x2){g, g}, q);
+        }
+        const float w = BP.idx[yy] < 0 ? wone[-1 - BP.idx[yy]] : (BP.swap[yy] ? wpair[BP.idx[yy]].y : wpair[BP.idx[yy]].x);
+        return BP.slot[yy] == 0 ? (f32x2){__builtin_fmaf(w, g, q.x), q.y} : (f32x2){q.x, __builtin_fmaf(w, g, q.y)};
+    };
     const int li = lane & 15, lq = lane >> 4;
 
     for (int t = t_first; t < npass; ++t) {
@@ -460,6 +550,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         lds_f32x2* pend_p = (lds_f32x2*)(size_t)cadr0;
         f32x2 pend_v = {0.0f, 0.0f};
         float pend_g = 0.0f;
+        int pend_yy = 0;      // WCONST: the pending row (a constant after unrolling) in the place of its weights
         int prev_by = -1;
         // fold band b (slot b & 1): hist[patch of n][bin][b][cell of n] += sum_x col[bin][x] W[x][n], clear the slot
         // `pair` (CELLS, 4 orientations; round 4): bands b and b + 1 in ONE set of products -- the 8 bin rows of band b's slot are the
@@ -646,9 +737,19 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
             const float r0 = vertical(H0, H1, y, LOOP != 0);
             if (grad) {
                 const int yy = y - 1;                      // gradient of row y - 1 (hog.c:616-672)
-                const float gx = from_right(rm1) - from_left(rm1);
-                const float gy = r0 - rm2;
-                const float g2 = gx * gx + gy * gy;
+                float gx, gy, g2;
+                if constexpr (WCONST) {
+                    // the two differences and the two squares written as the packed operations they compile to: left to the compiler,
+                    // the cell-11 instance with the weights in registers had them unpacked in one of its loops (51 vector instructions)
+                    typedef float g_v2 __attribute__((ext_vector_type(2)));
+                    const g_v2 gv = (g_v2){from_right(rm1), r0} - (g_v2){from_left(rm1), rm2};
+                    const g_v2 gq = gv * gv;
+                    gx = gv.x; gy = gv.y; g2 = gq.x + gq.y;
+                } else {      // (the feature-row form spills with the packed form: 12 bytes of scratch at cells 11 / 10 / 8)
+                    gx = from_right(rm1) - from_left(rm1);
+                    gy = r0 - rm2;
+                    g2 = gx * gx + gy * gy;
+                }
                 const float gm = RAW ? __builtin_amdgcn_sqrtf(g2) : sqrt_int_up(g2);
                 bool b0 = false, b1 = false, b2 = false;
                 int bin_any = 0;
@@ -666,10 +767,11 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
                 } else if constexpr (TO == 4) bin_sector4_bits(gx, gy, lv, b0, b1, b2);
                 else bin_sector<TO>(gx, gy, lv, TO, bin_any);      // (a zero gradient lands in bin 0 with magnitude 0)
                 // column sums by fused multiply-add: one v_pk_fma_f32 instead of a multiply and an add per pixel
-                *pend_p = __builtin_elementwise_fma(pend_v, (f32x2){pend_g, pend_g}, qv);
+                *pend_p = WCONST ? add_row(pend_yy, pend_g, qv) : __builtin_elementwise_fma(pend_v, (f32x2){pend_g, pend_g}, qv);
                 const float* rt = lv.row_tab[yy];
                 f32x2 wsv;
-                if (SPEC) wsv = wstab[yy - 1];
+                if (WCONST) wsv = (f32x2){0.0f, 0.0f};      // (add_row takes the row's weights from the registers)
+                else if (SPEC) wsv = wstab[yy - 1];
                 else wsv = (f32x2){rt[0], rt[1]};
                 const float ws0 = wsv.x, ws1 = wsv.y;
                 // (specialised instance: yy and with it the band are constants after unrolling; prev_by folds away)
@@ -696,7 +798,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
                     pend_p = (lds_f32x2*)(size_t)((b0 ? cadr1 : cadr0) + ((b1 ? 2u * bin_stride : 0u) + (b2 ? 4u * bin_stride : 0u)));
                 else
                     pend_p = (lds_f32x2*)(size_t)(cadr0 + (unsigned)bin_any * bin_stride);
-                pend_v = (f32x2){ws0, ws1}; pend_g = gm;
+                pend_v = (f32x2){ws0, ws1}; pend_g = gm; pend_yy = yy;
             }
             rm2 = rm1; rm1 = r0;
         };
@@ -742,7 +844,7 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
                 for (int yrow = 2; yrow < SC; ++yrow) row_step(yrow & 1, yrow, true, pair_load);
             } else two_load_rows();
         } else two_load_rows();
-        *pend_p = __builtin_elementwise_fma(pend_v, (f32x2){pend_g, pend_g}, *pend_p);
+        *pend_p = WCONST ? add_row(pend_yy, pend_g, *pend_p) : __builtin_elementwise_fma(pend_v, (f32x2){pend_g, pend_g}, *pend_p);
         if (CELLS && TO == 4 && prev_by >= 0 && prev_by + 1 <= C - 1) fold_band(prev_by, true);
         else {
             if (prev_by >= 0) fold_band(prev_by);
@@ -839,7 +941,7 @@ static void launch_hog_packed(const ImageSetDev& imgs, const int* img_idx, const
     const unsigned grid = (unsigned)((total + HP_WAVES - 1) / HP_WAVES);
 #define HP_LAUNCH_O(TO, CELL, RAW)                                                                                              \
     hipLaunchKernelGGL((hog_packed_kernel<TO, 5, CELL, RAW, CELLS>), dim3(grid), dim3(HP_WAVES * 64),                              \
-                       packed_wg_lds_bytes(5, TO, lv.S, CELLS ? 0 : plan.hist_slots, CELL > 0, hp_pair_slots(CELL, 5, CELLS, RAW)), stream, imgs, img_idx, x, N, L,  \
+                       packed_wg_lds_bytes(5, TO, lv.S, CELLS ? 0 : plan.hist_slots, CELL > 0, hp_pair_slots(CELL, 5, CELLS, RAW), !hp_const_weights(TO, CELL, CELLS, RAW)), stream, imgs, img_idx, x, N, L,  \
                        eyes, lv, plan, feat, ldf, idx_out, status)
 #define HP_LAUNCH(CELL, RAW) HP_LAUNCH_O(4, CELL, RAW)
     if (lv.O == 9) {      // "31-bin" HOG (9 orientations, hog.c:212-215): 18 bin rows = two matrix-core row tiles per band fold

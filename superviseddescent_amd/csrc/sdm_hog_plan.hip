@@ -51,7 +51,25 @@ int plan_pack(int S, int npatch, std::vector<std::vector<PlanLane>>& passes)
     if (pw <= pc) { passes.swap(whole); return pw; }
     return pc;
 }
+template <int CELL, int C>
+const HogRowConst* compiled_rows()
+{
+    static constexpr HogRowConstTable<CELL, C> table{};      // constant-evaluated: what the kernel instances of this cell size hold
+    return table.r;
+}
 }  // namespace
+
+const HogRowConst* sdm_hog_compiled_row_consts(int cell, int C)
+{
+    if (C != 5) return nullptr;
+    switch (cell) {      // the cell sizes with specialised instances (sdm_hog_packed.hip: launch_hog_packed)
+    case 11: return compiled_rows<11, 5>();
+    case 10: return compiled_rows<10, 5>();
+    case 8: return compiled_rows<8, 5>();
+    case 6: return compiled_rows<6, 5>();
+    default: return nullptr;
+    }
+}
 
 bool sdm_hog_plan_build(const HogLevelDev& lv, int L, HogPlanHost& out)
 {
@@ -61,6 +79,13 @@ bool sdm_hog_plan_build(const HogLevelDev& lv, int L, HogPlanHost& out)
     for (int d = 0; d < S; ++d) {      // the specialised instances compute the band of a row in integers: must equal the table
         int b; memcpy(&b, &lv.row_tab[d][2], sizeof(int));
         if (b != packed_band_of(d, lv.cell)) return false;
+    }
+    // ... and the detect instances take the band-slot weights from packed_row_const AS THE COMPILER evaluated it: must be the
+    // table's bits, which the host computed at run time (a level that differs gets no packed plan, as with the band above)
+    const HogRowConst* compiled = sdm_hog_compiled_row_consts(lv.cell, lv.C);
+    for (int d = 0; d < S; ++d) {
+        const HogRowConst rc = compiled ? compiled[d] : packed_row_const(d, lv.cell, lv.C);
+        if (memcmp(&rc.ws0, &lv.row_tab[d][0], sizeof(float)) || memcmp(&rc.ws1, &lv.row_tab[d][1], sizeof(float))) return false;
     }
     std::vector<std::vector<PlanLane>> tmp;
     // group size: fewest passes per sample, among equals the smaller group (measured and dropped: among equally dense group

@@ -116,6 +116,29 @@ __host__ __device__ constexpr int packed_band_of(int d, int cell)
 {
     return (2 * d + 1 - cell >= 0) ? (2 * d + 1 - cell) / (2 * cell) : -1;      // (d >= 0, cell >= 1: the only negative value is -1)
 }
+// The per-row constants of resized-ROI row d (hog.c:697-704) for (cell, C): {weight of band slot 0, weight of band slot 1, cell
+// row floor(hx), upper weight hx - floor(hx)} -- THE definition: fill_row_tab fills HogLevelDev::row_tab from it on the host, and the
+// detect instances of the pixel kernel (sdm_hog_packed.hip) take the first two from it at compile time, so that no table of them is
+// built or read on the device.  IEEE float and double operations only, evaluated alike by the host and by the compiler;
+// sdm_hog_plan_build compares the two, bit for bit, before a specialised instance is chosen.
+struct HogRowConst { float ws0, ws1; int band; float w2; };
+__host__ __device__ constexpr HogRowConst packed_row_const(int d, int cell, int C)
+{
+    const float hx = (float)((d + 0.5) / (double)cell - 0.5);
+    int b = (int)hx;
+    if (!(hx >= 0.0f || (float)b == hx)) b -= 1;                        // vl_floor_f
+    const float w2 = hx - (float)b, w1 = (float)(1.0 - w2);
+    const float wlo = b >= 0 ? w1 : 0.0f, whi = b + 1 <= C - 1 ? w2 : 0.0f;   // the cell rows -1 and C do not exist
+    return (b & 1) ? HogRowConst{whi, wlo, b, w2} : HogRowConst{wlo, whi, b, w2};      // band b lives in slot b & 1
+}
+// all rows of one (cell, C), for constant evaluation
+template <int CELL, int C>
+struct HogRowConstTable {
+    HogRowConst r[C * CELL] = {};
+    constexpr HogRowConstTable() { for (int d = 0; d < C * CELL; ++d) r[d] = packed_row_const(d, CELL, C); }
+};
+// rows 0 .. C * cell - 1 as the COMPILER evaluated them, for the cell sizes with specialised instances; null for any other (cell, C)
+const HogRowConst* sdm_hog_compiled_row_consts(int cell, int C);
 #ifdef __cplusplus
 #include <vector>
 struct HogPlanHost {

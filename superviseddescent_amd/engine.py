@@ -1113,6 +1113,14 @@ def hog_plan(num_cells: int, cell_size: int, num_bins: int, num_landmarks: int, 
             "lane_tab": lane_tab[:n], "wb": wb[:n], "pass_info": pass_info[:n], "cut": cut}
 
 
+def hog_band_weights(cell_size: int, num_cells: int):
+    """The band-slot weights {slot 0, slot 1} of the resized-ROI rows of a level geometry, [num_cells * cell_size][2] float32, as the
+    pixel kernel's detect instances hold them (host only; include/sdm.h: sdm_debug_hog_band_weights)."""
+    out = np.zeros((64, 2), np.float32)
+    check(_lib.lib().sdm_debug_hog_band_weights(cell_size, num_cells, _fp(out)))
+    return out[:num_cells * cell_size]
+
+
 # --------------------------------------------------------------------------------------------------
 # Reference-shaped operator surface
 # --------------------------------------------------------------------------------------------------
