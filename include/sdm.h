@@ -894,7 +894,7 @@ int sdm_align_paste_tensor_at_filtered(sdm_ctx* ctx, const float* matrices_host 
  * Refused with SDM_ERR_INVALID, no state changed, nothing launched: everything the filtered calls refuse, except that an NV12 frame and a
  * NULL filter are accepted; an NV12 frame with stride_bytes < 2 * ((width + 1) / 2).  The fit form's size rule holds against the context
  * image (an NV12 frame set through sdm_set_frames_device is its own luma).  samples_host may be NULL.  The piecewise-affine paste
- * (sdm_warp_paste_tensor*) has no NV12 form yet. */
+ * has its NV12 form in sdm_warp_paste_tensor_nv12 / _at_nv12 ("Pasting warped faces back into NV12 frames"). */
 int sdm_align_paste_tensor_nv12(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int crop_width, int crop_height,
                                 const sdm_align_tensor* spec, const sdm_align_filter* filter /* NULL: plain bilinear */, const void* in_dev,
                                 const sdm_align_paste* paste, const sdm_frame* dst_frames,
@@ -945,8 +945,9 @@ int sdm_align_paste_tensor_at_nv12(sdm_ctx* ctx, const float* matrices_host /* i
  *   write, several rows on one frame, never stored to   those of "Pasting crops back", word for word: the blend divides by 255, a pixel
  *           is loaded once, every row of the frame whose footprint holds it is applied in increasing row number in registers, it is
  *           stored once and only if some opacity was not 0, stores are per byte.
- * Out of scope, and not half-built: NV12 destinations (refused -- the rigid paste has them, "Pasting crops back into NV12 frames";
- * the block ownership written there is what this paste would adopt: the remaining gap); any antialiasing when the face in the frame is smaller than its crop;
+ * NV12 destinations are refused here and taken by sdm_warp_paste_tensor_nv12 / _at_nv12 ("Pasting warped faces back into NV12
+ * frames" below, with the block ownership of "Pasting crops back into NV12 frames").
+ * Out of scope, and not half-built: any antialiasing when the face in the frame is smaller than its crop;
  * a colour renormalised at the hull's border.
  * Refused with SDM_ERR_INVALID, no state changed, nothing launched: no mesh (none set, or sdm_set_model_geometry has changed L since);
  * fit form: no current rows, and sdm_warp_crops_tensor's rules on the rows' source sizes; everything sdm_align_paste_tensor refuses of
@@ -963,6 +964,30 @@ int sdm_warp_paste_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, const void
 int sdm_warp_paste_tensor_at(sdm_ctx* ctx, const float* points_host /* in, n_rows x K x 2: (x, y) of the mesh's k-th landmark */,
                              const int* image_index /* NULL: row i -> frame i */, int n_rows, const sdm_align_tensor* spec,
                              const void* in_dev, const sdm_align_paste* paste, const sdm_frame* dst_frames, int n_frames, int* flags_host);
+
+/* Pasting warped faces back into NV12 frames: sdm_warp_paste_tensor and sdm_warp_paste_tensor_at for a list of destinations that may
+ * hold NV12 frames, which closes decode -> warp -> network -> paste -> encode for the piecewise-affine path without a whole-frame
+ * conversion.  The section is a composition of two others and restates nothing else.
+ *   per luma pixel   everything is that of "Pasting warped faces back", word for word: the points and the flags (PARTIAL against the
+ *           destination's luma width and height), the row's box and the triangle's box, the lowest-numbered triangle and the one
+ *           position that decides, the footprint, the four taps, and the opacity that reads 0 outside the crop or on label 255.
+ *   destination, luma, chroma, several rows on one frame, never stored to   those of "Pasting crops back into NV12 frames", word for
+ *           word, with "the row's footprint" being the mesh footprint: dst_chroma, the 1-channel rule, the opacity-weighted mean over
+ *           the block, cnt and a_c, the rows in increasing row number, the 2 x 2 block as the unit of ownership, per-byte stores.
+ *   a consequence   a pixel of a block that lies outside the hull or outside the row's box has a_i = 0.  It still counts in cnt: a
+ *           block that the hull's edge crosses gets the colour of its covered pixels at an opacity reduced by the uncovered ones.
+ *   mixed lists   the other five formats are accepted in the same list and get exactly the bytes of sdm_warp_paste_tensor[_at];
+ *           their dst_chroma entry is ignored.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched: everything sdm_warp_paste_tensor[_at] refuse, except an NV12
+ * frame; an NV12 frame with stride_bytes < 2 * ((width + 1) / 2). */
+int sdm_warp_paste_tensor_nv12(sdm_ctx* ctx, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste,
+                               const sdm_frame* dst_frames,
+                               void* const* dst_chroma /* n_frames UV planes; NULL, or a NULL entry: behind the Y plane */, int n_frames,
+                               float* matrices_host /* out, N x T x 6, may be NULL */, int* flags_host /* out, may be NULL */);
+int sdm_warp_paste_tensor_at_nv12(sdm_ctx* ctx, const float* points_host /* in, n_rows x K x 2 */,
+                                  const int* image_index /* NULL: row i -> frame i */, int n_rows, const sdm_align_tensor* spec,
+                                  const void* in_dev, const sdm_align_paste* paste, const sdm_frame* dst_frames, void* const* dst_chroma,
+                                  int n_frames, int* flags_host);
 
 #ifdef __cplusplus
 }

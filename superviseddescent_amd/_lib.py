@@ -43,6 +43,7 @@ EXPORTED = [
     "sdm_warp_paste_tensor", "sdm_warp_paste_tensor_at",
     "sdm_align_paste_tensor_filtered", "sdm_align_paste_tensor_at_filtered",
     "sdm_align_paste_tensor_nv12", "sdm_align_paste_tensor_at_nv12",
+    "sdm_warp_paste_tensor_nv12", "sdm_warp_paste_tensor_at_nv12",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -465,6 +466,10 @@ def lib() -> ctypes.CDLL:
             "sdm_align_paste_tensor_at_nv12": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor),
                                                ctypes.POINTER(SdmAlignFilter), c_void_p, ctypes.POINTER(SdmAlignPaste),
                                                ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p, c_void_p],
+            "sdm_warp_paste_tensor_nv12": [c_void_p, ctypes.POINTER(SdmAlignTensor), c_void_p, ctypes.POINTER(SdmAlignPaste),
+                                           ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p, c_void_p],
+            "sdm_warp_paste_tensor_at_nv12": [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,
+                                              ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

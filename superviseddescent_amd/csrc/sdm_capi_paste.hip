@@ -3,7 +3,8 @@
 // image index they already hold, and enqueue -- fit form -- sdm_align_crops' fit, then the prepare kernel and the one paste launch
 // (csrc/sdm_align_paste.hip), the filtered forms that file's area-capable pair, the NV12 forms either prepare kernel and paste_nv12_kernel
 // with the frames' UV planes as a device array of their own; the piecewise-affine forms enqueue warp_fit_kernel, their prepare kernel and their paste launch
-// (csrc/sdm_warp_paste.hip) on the mesh of sdm_warp_set_mesh.  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
+// (csrc/sdm_warp_paste.hip) on the mesh of sdm_warp_set_mesh, their NV12 forms warp_paste_nv12_kernel with the same array of UV
+// planes.  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
 // landmark state, the images, the crop source and the tracker's slots are only read; the frames' colour bytes are written in place.
 #include "sdm_capi_internal.h"
 #include "sdm_paste.h"
@@ -163,9 +164,10 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
 
 // The piecewise-affine paste behind its checks.  x: N x 2L on the device (the landmark state, or the uploaded points in its layout);
 // src, img_idx: what warp_fit_kernel takes for its own record (the prepare kernel takes FOLDED from it and evaluates PARTIAL against the destination frames).
+// nv12: the calls that take NV12 destinations -- the same two kernels, then warp_paste_nv12_kernel with the UV planes (dst_chroma: the caller's, or null)
 int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const int* img_idx, const std::vector<int>& frame_of_row,
                    const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames,
-                   float* matrices_host, int* flags_host)
+                   float* matrices_host, int* flags_host, bool nv12, void* const* dst_chroma)
 {
     sdm_ctx::Warp& w = c->warp;
     const int N = (int)frame_of_row.size(), T = w.T;
@@ -174,7 +176,7 @@ int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const 
     const size_t rows_bytes = (size_t)N * sizeof(WarpPasteRow), tris_bytes = (size_t)N * T * sizeof(WarpPasteTri);
     PasteTables tab;
     if ((rc = w.rows.ensure(rec + mat)) || (rc = w.paste.ensure(rows_bytes + tris_bytes)) ||
-        (rc = paste_tables(c, frame_of_row, frames, n_frames, tab)))
+        (rc = paste_tables(c, frame_of_row, frames, n_frames, tab, nv12, dst_chroma)))
         return rc;
     WarpFace* faces = (WarpFace*)w.rows.p;
     float* matrices = (float*)(w.rows.p + rec);
@@ -185,8 +187,9 @@ int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const 
     sdm_launch_warp_paste_prepare(x, N, w.L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, faces, matrices, tab.of_row, tab.frames, rows_dev,
                                   tris_dev, c->stream);
     HIP_TRY(hipGetLastError());
-    sdm_launch_warp_paste(tab.frames, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p,
-                          paste_crop_dev(spec, in_dev, paste, w.out_w, w.out_h), c->stream);
+    const PasteCropDev crop = paste_crop_dev(spec, in_dev, paste, w.out_w, w.out_h);
+    if (nv12) sdm_launch_warp_paste_nv12(tab.frames, tab.chroma, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
+    else sdm_launch_warp_paste(tab.frames, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
     HIP_TRY(hipGetLastError());
     // the matrices and the rows' records, one synchronise
     std::vector<WarpPasteRow> host;
@@ -257,34 +260,32 @@ int warp_paste_check_mesh(sdm_ctx* c)
     return SDM_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int sdm_warp_paste_tensor(sdm_ctx* c, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
-                          int n_frames, float* matrices_host, int* flags_host)
+// sdm_warp_paste_tensor and sdm_warp_paste_tensor_nv12: the same checks in the same order
+int warp_paste_fit_call(sdm_ctx* c, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
+                        int n_frames, float* matrices_host, int* flags_host, bool nv12, void* const* dst_chroma)
 {
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     int rc;
     if ((rc = warp_paste_check_mesh(c))) return rc;
     if (c->N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
-    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames)) || (rc = align_check_rows(c))) return rc;
+    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)) || (rc = align_check_rows(c))) return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     return warp_paste_run(c, c->x[c->cur].p, align_source_dev(c), c->idx_identity ? nullptr : c->img_idx.p, frame_of_row, spec, in_dev, paste,
-                          frames, n_frames, matrices_host, flags_host);
+                          frames, n_frames, matrices_host, flags_host, nv12, dst_chroma);
 }
 
-int sdm_warp_paste_tensor_at(sdm_ctx* c, const float* points_host, const int* image_index, int n_rows, const sdm_align_tensor* spec,
-                             const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, int* flags_host)
+// sdm_warp_paste_tensor_at and sdm_warp_paste_tensor_at_nv12
+int warp_paste_at_call(sdm_ctx* c, const float* points_host, const int* image_index, int n_rows, const sdm_align_tensor* spec, const void* in_dev,
+                       const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, int* flags_host, bool nv12, void* const* dst_chroma)
 {
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     int rc;
     if ((rc = warp_paste_check_mesh(c))) return rc;
     if (!points_host) return fail(SDM_ERR_INVALID, "no points");
     if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
-    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames))) return rc;
+    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12))) return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;
     sdm_ctx::Warp& w = c->warp;
@@ -303,7 +304,37 @@ int sdm_warp_paste_tensor_at(sdm_ctx* c, const float* points_host, const int* im
     // warp_fit_kernel's own record wants an image per row: a stack of one 1 x 1 image (of its flags only FOLDED is read)
     AlignSourceDev src{};
     src.width = src.height = src.stride = 1;
-    return warp_paste_run(c, w.points.p, src, nullptr, frame_of_row, spec, in_dev, paste, frames, n_frames, nullptr, flags_host);
+    return warp_paste_run(c, w.points.p, src, nullptr, frame_of_row, spec, in_dev, paste, frames, n_frames, nullptr, flags_host, nv12, dst_chroma);
+}
+
+}  // namespace
+
+extern "C" {
+
+int sdm_warp_paste_tensor(sdm_ctx* c, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
+                          int n_frames, float* matrices_host, int* flags_host)
+{
+    return warp_paste_fit_call(c, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host, false, nullptr);
+}
+
+int sdm_warp_paste_tensor_at(sdm_ctx* c, const float* points_host, const int* image_index, int n_rows, const sdm_align_tensor* spec,
+                             const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, int* flags_host)
+{
+    return warp_paste_at_call(c, points_host, image_index, n_rows, spec, in_dev, paste, frames, n_frames, flags_host, false, nullptr);
+}
+
+// the calls that take NV12 destinations
+int sdm_warp_paste_tensor_nv12(sdm_ctx* c, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste,
+                               const sdm_frame* frames, void* const* dst_chroma, int n_frames, float* matrices_host, int* flags_host)
+{
+    return warp_paste_fit_call(c, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host, true, dst_chroma);
+}
+
+int sdm_warp_paste_tensor_at_nv12(sdm_ctx* c, const float* points_host, const int* image_index, int n_rows, const sdm_align_tensor* spec,
+                                  const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, void* const* dst_chroma,
+                                  int n_frames, int* flags_host)
+{
+    return warp_paste_at_call(c, points_host, image_index, n_rows, spec, in_dev, paste, frames, n_frames, flags_host, true, dst_chroma);
 }
 
 int sdm_align_paste_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, int ch, const sdm_align_tensor* spec,

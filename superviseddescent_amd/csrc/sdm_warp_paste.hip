@@ -16,6 +16,16 @@
 //                          (warp_paste_footprint) decide every pixel alike.  The ownership
 //                          test against earlier rows of the frame and the application of later rows read those rows' records from
 //                          device memory, the row box first (paste_owned).  One owner per pixel, no atomics, one pass.
+//   warp_paste_nv12_kernel   the calls that take NV12 destinations (include/sdm.h, "Pasting warped faces back into NV12 frames"), behind
+//                          the same two kernels.  The frame's format is uniform for a workgroup: any other frame takes
+//                          warp_paste_kernel's per-pixel body, so that a mixed list costs one launch.  On an NV12 frame the tile walk
+//                          runs over the 2 x 2 blocks of the row's box widened to even coordinates; a wave covers 64 blocks of one block
+//                          row, a strip of 128 x 2 luma pixels.  The cull is taken once per wave against that strip; every lane then
+//                          walks the candidates in ascending order and tests the up-to-four pixels of its block that are still looking
+//                          (those inside the row's box), until no lane has one: the four winners, 255 for none, pack into one
+//                          register.  The block rule is paste_owned_block on the shape PasteMeshOwn, which answers for the owner's row
+//                          from the winners and the staged records and for every other row through warp_paste_footprint: every byte
+//                          of both planes has at most one reader and writer in the launch.
 //
 // The per-pixel arithmetic is csrc/sdm_warp_paste_device.h on top of csrc/sdm_paste_device.h.
 #include "sdm_paste.h"
@@ -130,6 +140,102 @@ __global__ __launch_bounds__(PASTE_BLOCK) void warp_paste_kernel(const PasteFram
     }
 }
 
+// The calls that take NV12 destinations.  The non-NV12 branch is warp_paste_kernel's body, text for text: a copy, to be kept in step
+// by hand.  Sharing it through a __forceinline__ function was tried three ways (the staged records as a pointer, as an array
+// reference, the parameters without __restrict__) and each moved warp_paste_kernel's instructions (scripts/isa_kernel_identity.py:
+// 2 826 lines of text became 2 868, 2 868 and 2 873), which that kernel's record does not allow.  On an NV12 frame a lane owns block (BX, BY) of the row's box widened to even coordinates; a wave's
+// 64 blocks are a strip of 128 x 2 luma pixels.  The strip cull tests the triangles' boxes against that strip as it is: every
+// triangle's box lies inside the row's box, so a triangle left out is one whose own box test refuses every pixel of the strip.
+__global__ __launch_bounds__(PASTE_BLOCK) void warp_paste_nv12_kernel(const PasteFrameDev* __restrict__ frames, uint8_t* const* __restrict__ chroma,
+                                                                       const WarpPasteRow* __restrict__ rows, const WarpPasteTri* __restrict__ tris,
+                                                                       int T, const int* __restrict__ list, const int* __restrict__ entry_of_row,
+                                                                       const uint8_t* __restrict__ labels, PasteCropDev c)
+{
+    __shared__ WarpPasteTri lds[SDM_WARP_MAX_TRIANGLES];
+    const int n = blockIdx.x;
+    const int k = entry_of_row[n];
+    const WarpPasteRow r = rows[n];
+    const int bw = r.x1 - r.x0, bh = r.y1 - r.y0;
+    if (bw <= 0 || bh <= 0) return;
+    const PasteFrameDev f = frames[r.frame];
+    {
+        const int* src = (const int*)(tris + (long long)n * T);
+        int* dst = (int*)lds;
+        for (int e = threadIdx.x; e < T * WPASTE_REC_INTS; e += PASTE_BLOCK) dst[e] = src[e];
+    }
+    __syncthreads();
+    const int lx = threadIdx.x & (PASTE_TILE_W - 1), ly = threadIdx.x / PASTE_TILE_W;
+    if (f.format != SDM_FRAME_NV12) {
+        const int tx = paste_tiles_x(bw), ty = paste_tiles_y(bh);
+        for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
+            const int X0 = r.x0 + paste_tile_x(t, tx), Y = r.y0 + paste_tile_y(t, tx) + ly;
+            if (Y >= r.y1) continue;                                    // (the whole wave)
+            const int X = X0 + lx, X1 = X0 + PASTE_TILE_W < r.x1 ? X0 + PASTE_TILE_W : r.x1;
+            unsigned long long cand[WPASTE_WORDS];
+#pragma unroll
+            for (int w = 0; w < WPASTE_WORDS; ++w) {
+                const int tt = w * 64 + lx;
+                cand[w] = __ballot(tt < T && warp_paste_hits(lds[tt < T ? tt : 0], X0, Y, X1, Y + 1));
+            }
+            int mine = -1;
+            bool open = X < r.x1;
+#pragma unroll
+            for (int w = 0; w < WPASTE_WORDS; ++w) {
+                unsigned long long m = cand[w];
+                while (m != 0ull && __ballot(open) != 0ull) {
+                    const int tt = w * 64 + __builtin_ctzll(m);
+                    m &= m - 1ull;
+                    if (open && warp_paste_inside(lds[tt], X, Y)) { mine = tt; open = false; }
+                }
+            }
+            AlignPos q;
+            if (mine >= 0 && paste_position(lds[mine].w, c.cw, c.ch, X, Y, q)) paste_owned(f, PasteMesh{rows, tris, T, labels}, list, k, c, X, Y, q);
+        }
+        return;
+    }
+    // the blocks of the box widened to even coordinates: [bx0, bx1) x [by0, by1)
+    uint8_t* const uv = chroma[r.frame];
+    const int bx0 = r.x0 >> 1, by0 = r.y0 >> 1, bx1 = (r.x1 + 1) >> 1, by1 = (r.y1 + 1) >> 1;
+    const int tx = paste_tiles_x(bx1 - bx0), ty = paste_tiles_y(by1 - by0);
+    for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
+        const int B0 = bx0 + paste_tile_x(t, tx), BY = by0 + paste_tile_y(t, tx) + ly;
+        if (BY >= by1) continue;                                        // (the whole wave)
+        const int BX = B0 + lx;
+        // the wave's candidates: triangles whose box meets its strip of 128 x 2 pixels
+        unsigned long long cand[WPASTE_WORDS];
+#pragma unroll
+        for (int w = 0; w < WPASTE_WORDS; ++w) {
+            const int tt = w * 64 + lx;
+            cand[w] = __ballot(tt < T && warp_paste_hits(lds[tt < T ? tt : 0], 2 * B0, 2 * BY, 2 * B0 + 2 * PASTE_TILE_W, 2 * BY + 2));
+        }
+        // the block's pixels inside the row's box (hence inside the frame) are still looking, bit i for pixel i
+        int open = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int X = 2 * BX + (i & 1), Y = 2 * BY + (i >> 1);
+            if (X >= r.x0 && X < r.x1 && Y >= r.y0 && Y < r.y1) open |= 1 << i;
+        }
+        uint32_t winners = 0xffffffffu;
+#pragma unroll
+        for (int w = 0; w < WPASTE_WORDS; ++w) {
+            unsigned long long m = cand[w];
+            while (m != 0ull && __ballot(open != 0) != 0ull) {
+                const int tt = w * 64 + __builtin_ctzll(m);
+                m &= m - 1ull;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if ((open >> i & 1) && warp_paste_inside(lds[tt], 2 * BX + (i & 1), 2 * BY + (i >> 1))) {
+                        winners = (winners & ~(255u << (8 * i))) | (uint32_t)tt << (8 * i);
+                        open &= ~(1 << i);
+                    }
+            }
+        }
+        // (a lane whose block the row does not hold -- beyond bx1 too: nothing was open -- leaves before any ownership test)
+        if (winners != 0xffffffffu)
+            paste_owned_block(f, uv, PasteMeshOwn{PasteMesh{rows, tris, T, labels}, n, winners, lds}, list, k, c, BX, BY);
+    }
+}
+
 }  // namespace
 
 void sdm_launch_warp_paste_prepare(const float* x, int N, int L, const int* lm, int K, const WarpTri* tri, int T, const WarpFace* faces,
@@ -146,4 +252,11 @@ void sdm_launch_warp_paste(const PasteFrameDev* frames, const WarpPasteRow* rows
 {
     hipLaunchKernelGGL(warp_paste_kernel, dim3((unsigned)N, (unsigned)paste_groups(crop)), dim3(PASTE_BLOCK), 0, s, frames, rows, tris, T, list,
                        entry_of_row, labels, crop);
+}
+
+void sdm_launch_warp_paste_nv12(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris, int T,
+                                const int* list, const int* entry_of_row, int N, const uint8_t* labels, const PasteCropDev& crop, hipStream_t s)
+{
+    hipLaunchKernelGGL(warp_paste_nv12_kernel, dim3((unsigned)N, (unsigned)paste_groups(crop)), dim3(PASTE_BLOCK), 0, s, frames, chroma, rows, tris,
+                       T, list, entry_of_row, labels, crop);
 }

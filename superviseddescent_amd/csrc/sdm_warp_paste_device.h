@@ -1,6 +1,7 @@
 // sdm_warp_paste_device.h -- the arithmetic of the piecewise-affine paste (include/sdm.h, "Pasting warped faces back"): a row's flags
 // and box from its mesh landmarks, a triangle's record -- the inverse W_t of its float32 A_t, its corners in edge-function order, its
-// box --, the triangle of a frame pixel, and the paste's shape for the ownership rule (PasteMesh).  The fit is warp_fit_triangle
+// box --, the triangle of a frame pixel, and the paste's shapes for the ownership rule (PasteMesh; PasteMeshOwn for the owner of an
+// NV12 block, whose own triangle search is done before the block rule runs).  The fit is warp_fit_triangle
 // (sdm_warp_device.h); the inverse, the position, the taps, the decode, the blend, the pixel's load / apply / store and the ownership
 // rule (paste_owned) are sdm_paste_device.h's; the quantisation is sdm_align_tensor_device.h's.  Plain C++ behind ALIGN_HD, so
 // the same text is the device code of csrc/sdm_warp_paste.hip and -- compiled for the host, tests/cpp/warp_paste_host.cpp -- a program
@@ -155,6 +156,46 @@ ALIGN_HD bool paste_holds(const PasteMesh& p, int n, const PasteCropDev& c, int 
 ALIGN_HD void paste_taps(const PasteMesh& p, const PasteCropDev& c, int n, int, int, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
 {
     paste_sample_taps<true>(c, n, q, p.labels, bgr, a);
+}
+
+// The mesh as the owner of an NV12 block sees it (paste_owned_block of sdm_paste_device.h; include/sdm.h, "Pasting warped faces back
+// into NV12 frames"): the owner's own triangle search has been done before the block rule runs -- on the device by a walk over the
+// row's records staged in LDS, on the host by a plain loop -- and its four answers come packed, pixel i of the block ((X & 1) | (Y & 1)
+// << 1) at bits 8 i, 255: no triangle, or the pixel lies outside the row's box.  Every other row answers through warp_paste_footprint.
+// own_tris: the owner's T records (its staged copy).  A winner is the lowest-numbered triangle that warp_paste_inside accepts, so that
+// this shape and PasteMesh decide every pixel alike: that one triangle's position, and no second triangle tried.
+struct PasteMeshOwn {
+    PasteMesh mesh;
+    int own;                    // the owner's row number
+    uint32_t winners;
+    const WarpPasteTri* own_tris;
+};
+
+#define WPASTE_NO_WINNER 255u
+
+ALIGN_HD bool paste_holds(const PasteMeshOwn& p, int n, const PasteCropDev& c, int X, int Y, AlignPos& q)
+{
+    if (n != p.own) return paste_holds(p.mesh, n, c, X, Y, q);
+    const uint32_t t = p.winners >> (8 * ((X & 1) | (Y & 1) << 1)) & 255u;
+    return t != WPASTE_NO_WINNER && paste_position(p.own_tris[t].w, c.cw, c.ch, X, Y, q);
+}
+
+ALIGN_HD void paste_taps(const PasteMeshOwn& p, const PasteCropDev& c, int n, int X, int Y, const AlignPos& q, uint32_t bgr[3], uint32_t& a)
+{
+    paste_taps(p.mesh, c, n, X, Y, q, bgr, a);
+}
+
+// the owner's search for the pixels of block (BX, BY) that lie in its box r, triangle after triangle: what the device's LDS walk leaves
+ALIGN_HD uint32_t warp_paste_block_winners(const WarpPasteRow& r, const WarpPasteTri* own_tris, int T, int BX, int BY)
+{
+    uint32_t winners = 0xffffffffu;
+    for (int i = 0; i < 4; ++i) {
+        const int X = 2 * BX + (i & 1), Y = 2 * BY + (i >> 1);
+        if (X < r.x0 || X >= r.x1 || Y < r.y0 || Y >= r.y1) continue;
+        for (int t = 0; t < T; ++t)
+            if (warp_paste_inside(own_tris[t], X, Y)) { winners = (winners & ~(255u << (8 * i))) | (uint32_t)t << (8 * i); break; }
+    }
+    return winners;
 }
 
 // paste_owned for the mesh from its parts, as the host program calls it

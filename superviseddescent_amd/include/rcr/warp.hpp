@@ -14,6 +14,7 @@
 // rcr::paste_warped_tensor is the way back: a network's output in template space blended into the frames under every face's own shape.
 //
 //     auto p = rcr::paste_warped_tensor(tr, mesh, paste_spec, net_out_dev, device_frames);       // p.flags[i]: SDM_WARP_*
+//     auto q = rcr::paste_warped_tensor(tr, mesh, paste_spec, net_out_dev, nv12_frames, std::vector<void*>());   // NV12, UV behind Y
 #pragma once
 
 #ifndef RCR_WARP_HPP_
@@ -154,9 +155,12 @@ inline void warp_paste_set_mesh(sdm_ctx* c, const WarpMesh& mesh)
                                                     mesh.triangles.data(), mesh.n_triangles(), mesh.width, mesh.height), "sdm_warp_set_mesh");
 }
 
-// the n current rows of the handle `c`: the fit of warped_crops_tensor, then the tensor at `in_dev` pasted into `frames` in place
+// the n current rows of the handle `c`: the fit of warped_crops_tensor, then the tensor at `in_dev` pasted into `frames` in place;
+// `chroma`: nullptr, or -- the overloads for NV12 destinations, sdm_warp_paste_tensor_nv12 -- the frames' UV planes (empty: every one
+// directly behind its Y plane)
 inline warp_paste_result warp_paste_current_rows(sdm_ctx* c, int n, const WarpMesh& mesh, const TensorSpec& spec, const void* in_dev,
-                                                 const std::vector<DeviceFrame>& frames, const PasteMask& mask)
+                                                 const std::vector<DeviceFrame>& frames, const PasteMask& mask,
+                                                 const std::vector<void*>* chroma = nullptr)
 {
     warp_paste_set_mesh(c, mesh);
     const std::vector<sdm_frame> f = paste_frames(frames);
@@ -165,8 +169,61 @@ inline warp_paste_result warp_paste_current_rows(sdm_ctx* c, int n, const WarpMe
     warp_paste_result res;
     res.matrices = cv::Mat(n, 6 * mesh.n_triangles(), CV_32FC1);
     res.flags.resize((size_t)n);
+    if (chroma) {
+        superviseddescent::hip::check(sdm_warp_paste_tensor_nv12(c, &s, in_dev, &p, f.empty() ? nullptr : f.data(), paste_chroma(*chroma, f.size()),
+                                                                 (int)f.size(), res.matrices.ptr<float>(0), res.flags.data()),
+                                      "sdm_warp_paste_tensor_nv12");
+        return res;
+    }
     superviseddescent::hip::check(sdm_warp_paste_tensor(c, &s, in_dev, &p, f.empty() ? nullptr : f.data(), (int)f.size(),
                                                         res.matrices.ptr<float>(0), res.flags.data()), "sdm_warp_paste_tensor");
+    return res;
+}
+
+// landmark rows on device frames: a handle of its own, the frames as its image set, the rows uploaded.  chroma: as above
+inline warp_paste_result warp_paste_rows(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                         const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec, const void* in_dev,
+                                         const PasteMask& mask, const std::vector<void*>* chroma)
+{
+    using superviseddescent::hip::check;
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    sdm_ctx* c = h.get();
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::set_device_frames(h, frames);
+    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
+    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("paste_warped_tensor: rows must hold 2L coordinates");
+    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
+    return detail::warp_paste_current_rows(c, x.rows, mesh, spec, in_dev, frames, mask, chroma);
+}
+
+// explicit points: sdm_warp_paste_tensor_at, or with chroma sdm_warp_paste_tensor_at_nv12
+inline warp_paste_result warp_paste_points(detection_model& model, cv::Mat points, const std::vector<int>& image_index, const WarpMesh& mesh,
+                                           const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames,
+                                           const PasteMask& mask, const std::vector<void*>* chroma)
+{
+    using superviseddescent::hip::check;
+    if (points.type() != CV_32FC1 || points.cols != 2 * (int)mesh.landmark_index.size() || points.rows < 1)
+        throw std::runtime_error("paste_warped_tensor: points must be rows x 2K CV_32FC1");
+    if (!image_index.empty() && (int)image_index.size() != points.rows) throw std::runtime_error("paste_warped_tensor: one image index per row");
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::warp_paste_set_mesh(h.get(), mesh);
+    cv::Mat pts = points.isContinuous() ? points : points.clone();
+    const std::vector<sdm_frame> f = detail::paste_frames(frames);
+    const sdm_align_tensor s = detail::paste_spec(spec);
+    const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
+    warp_paste_result res;
+    res.flags.resize((size_t)points.rows);
+    const int* index = image_index.empty() ? nullptr : image_index.data();
+    if (chroma)
+        check(sdm_warp_paste_tensor_at_nv12(h.get(), pts.ptr<float>(0), index, points.rows, &s, in_dev, &p, f.empty() ? nullptr : f.data(),
+                                            detail::paste_chroma(*chroma, f.size()), (int)f.size(), res.flags.data()),
+              "sdm_warp_paste_tensor_at_nv12");
+    else
+        check(sdm_warp_paste_tensor_at(h.get(), pts.ptr<float>(0), index, points.rows, &s, in_dev, &p, f.empty() ? nullptr : f.data(),
+                                       (int)f.size(), res.flags.data()), "sdm_warp_paste_tensor_at");
     return res;
 }
 
@@ -190,17 +247,7 @@ inline warp_paste_result paste_warped_tensor(detection_model& model, const std::
                                              const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec,
                                              const void* in_dev, const PasteMask& mask = {})
 {
-    using superviseddescent::hip::check;
-    superviseddescent::hip::Handle h(superviseddescent::hip::device());
-    sdm_ctx* c = h.get();
-    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
-    detail::set_device_frames(h, frames);
-    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
-    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("paste_warped_tensor: rows must hold 2L coordinates");
-    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
-    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
-    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
-    return detail::warp_paste_current_rows(c, x.rows, mesh, spec, in_dev, frames, mask);
+    return detail::warp_paste_rows(model, frames, rows, image_index, mesh, spec, in_dev, mask, nullptr);
 }
 
 /** The explicit form (sdm_warp_paste_tensor_at): `points` rows x 2K CV_32FC1 -- per row x, y of the mesh's first landmark, then of its
@@ -210,22 +257,33 @@ inline warp_paste_result paste_warped_tensor(detection_model& model, cv::Mat poi
                                              const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames,
                                              const PasteMask& mask = {})
 {
-    using superviseddescent::hip::check;
-    if (points.type() != CV_32FC1 || points.cols != 2 * (int)mesh.landmark_index.size() || points.rows < 1)
-        throw std::runtime_error("paste_warped_tensor: points must be rows x 2K CV_32FC1");
-    if (!image_index.empty() && (int)image_index.size() != points.rows) throw std::runtime_error("paste_warped_tensor: one image index per row");
-    superviseddescent::hip::Handle h(superviseddescent::hip::device());
-    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
-    detail::warp_paste_set_mesh(h.get(), mesh);
-    cv::Mat pts = points.isContinuous() ? points : points.clone();
-    const std::vector<sdm_frame> f = detail::paste_frames(frames);
-    const sdm_align_tensor s = detail::paste_spec(spec);
-    const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
-    warp_paste_result res;
-    res.flags.resize((size_t)points.rows);
-    check(sdm_warp_paste_tensor_at(h.get(), pts.ptr<float>(0), image_index.empty() ? nullptr : image_index.data(), points.rows, &s, in_dev, &p,
-                                   f.empty() ? nullptr : f.data(), (int)f.size(), res.flags.data()), "sdm_warp_paste_tensor_at");
-    return res;
+    return detail::warp_paste_points(model, points, image_index, mesh, spec, in_dev, frames, mask, nullptr);
+}
+
+/** The three forms for destinations that may hold NV12 frames (include/sdm.h, "Pasting warped faces back into NV12 frames"): luma and
+ *  4:2:0 chroma are blended in place, the other formats get the bytes of the forms above.  `chroma`: per frame the UV plane of an NV12
+ *  frame (nullptr: directly behind its Y plane); an empty vector: every UV plane lies behind its Y plane.  `chroma` stands where the
+ *  forms above have their defaulted mask, so a bare `{}` in that place names neither a mask nor a chroma vector: the call is
+ *  ambiguous (as for the paste_crops_tensor overloads of rcr/alignment.hpp).  Write `rcr::PasteMask{}` or `std::vector<void*>{}`. */
+inline warp_paste_result paste_warped_tensor(tracker& tr, const WarpMesh& mesh, const TensorSpec& spec, const void* in_dev,
+                                             const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma, const PasteMask& mask = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("paste_warped_tensor: step the tracker first");
+    return detail::warp_paste_current_rows(tr.context(), tr.rows().rows, mesh, spec, in_dev, frames, mask, &chroma);
+}
+
+inline warp_paste_result paste_warped_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma,
+                                             cv::Mat rows, const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec,
+                                             const void* in_dev, const PasteMask& mask = {})
+{
+    return detail::warp_paste_rows(model, frames, rows, image_index, mesh, spec, in_dev, mask, &chroma);
+}
+
+inline warp_paste_result paste_warped_tensor(detection_model& model, cv::Mat points, const std::vector<int>& image_index, const WarpMesh& mesh,
+                                             const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames,
+                                             const std::vector<void*>& chroma, const PasteMask& mask = {})
+{
+    return detail::warp_paste_points(model, points, image_index, mesh, spec, in_dev, frames, mask, &chroma);
 }
 
 }  // namespace rcr
