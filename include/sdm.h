@@ -711,8 +711,8 @@ int sdm_align_crops_tensor_filtered(sdm_ctx* ctx, const int* landmark_index, con
  *   pixel    (column j, row i) with label t: sx = (A_t00 j + A_t01 i) + A_t02, sy = (A_t10 j + A_t11 i) + A_t12 in float32, every operation
  *            rounded; from that position on it is items 1 to 5 of sdm_align_crops_tensor, unchanged: the 1/32-pixel quantisation, the taps,
  *            the weights, (... + 512) >> 10, the 2^20 rule, the source formats, the channel rules, the element, the layout.  A pixel with
- *            label 255 takes the elements of v = 0 (bias[c] for the float dtypes) and reads no source byte.  Sampling is plain bilinear:
- *            the area filter of sdm_align_crops_tensor_filtered does not apply here.
+ *            label 255 takes the elements of v = 0 (bias[c] for the float dtypes) and reads no source byte.  Sampling is plain bilinear
+ *            here; sdm_warp_crops_tensor_filtered below is this call with the area filter, per triangle and per axis.
  *   flags    per row:
  *            SDM_WARP_DEGENERATE  one of the mesh's K landmarks is not finite: every element is that of v = 0, every matrix of the row is
  *                                 six NaNs, and no other bit is evaluated.
@@ -745,6 +745,40 @@ int sdm_warp_get_labels(sdm_ctx* ctx, uint8_t* labels_host);
  * matrices_host (N x T x 6) and flags_host (N) may be NULL; they come back in one copy, behind one synchronise.  Neither the landmark
  * state, the images, the crop source nor the tracker's slots are changed. */
 int sdm_warp_crops_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, void* out_dev, float* matrices_host, int* flags_host);
+
+/* Warped faces, filtered: sdm_warp_crops_tensor with area-averaged sampling where a triangle's map minifies.  Every triangle has its own
+ * affine map: a turned head minifies the near cheek while the far cheek magnifies, and the maps shear, so the sub-sample count is chosen
+ * per TRIANGLE and per AXIS.  Every pixel of triangle t is the average of Sx x Sy bilinear sub-samples spread over its footprint, in the
+ * integer arithmetic of the crop path, in the same two launches; the filter is sdm_align_crops_tensor_filtered's sdm_align_filter.
+ *   1. unchanged from sdm_warp_crops_tensor: the mesh and the label map, G, A_t and its rounding to float32, the flags, the source rules,
+ *      the channel, element and layout rules and every refusal.  Refused in addition what sdm_align_crops_tensor_filtered refuses of
+ *      filter: NULL, an unknown mode, max_samples outside [1, 16], min_scale not finite or below 1.  Every refusal returns SDM_ERR_INVALID,
+ *      changes no state and launches nothing.
+ *   2. (Sx, Sy) of row n, triangle t   from the float32 A_t, in float32, each operation rounded, nothing contracted:
+ *      cx2 = A00 A00 + A10 A10 (the source step per crop column, squared), cy2 = A01 A01 + A11 A11 (per crop row).  Sx is item 2 of
+ *      sdm_align_crops_tensor_filtered applied to cx2, Sy the same rule applied to cy2: 1 for mode BILINEAR, for a DEGENERATE row, for a
+ *      value that is not finite or below min_scale * min_scale (float32); otherwise the smallest integer in [1, max_samples] with
+ *      (float)(S S) >= value, and max_samples when there is none.  For a similarity Sx = Sy = the rigid call's S.  A FOLDED triangle
+ *      follows the formula like any other.  samples_host[(n T + t) 2] = Sx, [(n T + t) 2 + 1] = Sy.
+ *   3. sub-samples of pixel (j, i) with label t   all go through the pixel's own A_t, also those whose crop position lies past the
+ *      triangle's edge or in unlabelled territory.  For u in 0 ... Sx - 1 and v in 0 ... Sy - 1: fj = (float)j + o_Sx[u],
+ *      fi = (float)i + o_Sy[v] with o_S[u] = (float)(2u + 1 - S) / (float)(2S), correctly rounded (the rigid call's offsets); then
+ *      sx = (A00 fj + A01 fi) + A02 and sy likewise.
+ *   4. value   items 4 to 7 of sdm_align_crops_tensor_filtered with S S replaced by n = Sx Sy <= 256: the sub-samples are un-rounded tap
+ *      sums q, v = (sum of q + 512 n) / (1024 n), an unsigned integer division, the sum below 2^26 + 2^17; a pixel with any sub-sample
+ *      refused by the 2^20 rule is 0; NV12 averages Y, U and V over the same sub-samples and converts once (channels == 1: the averaged Y,
+ *      the UV plane is not read); the gray weights apply to the averaged (B, G, R).
+ *   5. a pixel with label 255 takes the elements of v = 0 and reads no source byte, as in sdm_warp_crops_tensor.
+ *   6. bit identity   a pixel whose triangle has Sx = Sy = 1 takes exactly the bits sdm_warp_crops_tensor gives it; mode BILINEAR gives
+ *      the unfiltered tensor for any rows.
+ * Two consequences, both chosen for simplicity and determinism: the MAP is continuous across an edge two triangles share, the sample
+ * count is not -- two neighbouring triangles may average over different grids --; and A_t extrapolates up to half a crop pixel past its
+ * triangle for the sub-samples of the triangle's border pixels.
+ * samples_host (N x T x 2) may be NULL; it comes back with the matrices and flags in the same single copy and synchronise.  The paste
+ * direction (sdm_warp_paste_tensor*) has no such filter. */
+int sdm_warp_crops_tensor_filtered(sdm_ctx* ctx, const sdm_align_tensor* spec, const sdm_align_filter* filter, void* out_dev,
+                                   float* matrices_host /* N x T x 6 */, int* flags_host /* N */,
+                                   int* samples_host /* N x T x 2: (Sx, Sy) of every triangle; may be NULL */);
 
 /* Pasting crops back: the inverse path of sdm_align_crops_tensor.  A network's output y = net(x) on the crops x -- a restored, swapped,
  * re-lit, blurred or pixelated face -- is warped back through the row's similarity and blended into the frames where they lie on the

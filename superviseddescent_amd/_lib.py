@@ -39,6 +39,7 @@ EXPORTED = [
     "sdm_set_frames_device", "sdm_debug_download_image",
     "sdm_upright_configure", "sdm_detect_batch_upright", "sdm_upright_get", "sdm_track_configure_upright", "sdm_track_start_rolled",
     "sdm_warp_delaunay", "sdm_warp_set_mesh", "sdm_warp_get_labels", "sdm_warp_crops_tensor",
+    "sdm_warp_crops_tensor_filtered",
     "sdm_align_paste_tensor", "sdm_align_paste_tensor_at",
     "sdm_warp_paste_tensor", "sdm_warp_paste_tensor_at",
     "sdm_align_paste_tensor_filtered", "sdm_align_paste_tensor_at_filtered",
@@ -446,6 +447,8 @@ def lib() -> ctypes.CDLL:
             "sdm_warp_set_mesh": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int],
             "sdm_warp_get_labels": [c_void_p, c_void_p],
             "sdm_warp_crops_tensor": [c_void_p, ctypes.POINTER(SdmAlignTensor), c_void_p, c_void_p, c_void_p],
+            "sdm_warp_crops_tensor_filtered": [c_void_p, ctypes.POINTER(SdmAlignTensor), ctypes.POINTER(SdmAlignFilter), c_void_p, c_void_p,
+                                               c_void_p, c_void_p],
             "sdm_align_paste_tensor": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,
                                        ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_int, c_void_p, c_void_p],
             "sdm_align_paste_tensor_at": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,

@@ -333,7 +333,7 @@ struct sdm_ctx {
         DevBuf<uint8_t> labels;
         DevBuf<unsigned char> tri;         // T WarpTri records (csrc/sdm_warp_device.h)
         DevBuf<int> lm;                    // K
-        DevBuf<unsigned char> rows;        // N WarpFace records, then N x T x 6 floats
+        DevBuf<unsigned char> rows;        // N WarpFace records, then N x T x 6 floats, then (filtered call) N x T x 2 ints
         // the piecewise-affine paste (sdm_capi_paste.hip): the landmark indices on the host, the uploaded points of the _at form in the
         // landmark state's layout, and a call's N WarpPasteRow records with the N x T WarpPasteTri records behind them
         std::vector<int> lm_host;

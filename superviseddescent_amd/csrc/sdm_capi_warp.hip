@@ -1,7 +1,7 @@
 // sdm_capi_warp.hip -- C-ABI of the piecewise-affine warped faces (include/sdm.h, "Warped faces"): the host side of the mesh -- the
 // Delaunay triangulation of a template, the label map and the triangles' constants, all in double with nothing contracted
-// (-ffp-contract=off, csrc/Makefile) -- kept in sdm_ctx::warp, and the call that fits every row's triangles and warps its image
-// (csrc/sdm_warp.hip).  Every argument is checked before anything is launched or changed; the landmark state, the images, the crop
+// (-ffp-contract=off, csrc/Makefile) -- kept in sdm_ctx::warp, and the two calls that fit every row's triangles and warp its image:
+// plain bilinear (csrc/sdm_warp.hip) and area-averaged per triangle and axis ("Warped faces, filtered", csrc/sdm_warp_area.hip).  Every argument is checked before anything is launched or changed; the landmark state, the images, the crop
 // source and the tracker's slots are only read.
 #include "sdm_capi_internal.h"
 #include "sdm_warp.h"
@@ -109,6 +109,53 @@ int delaunay(const std::vector<P2>& p, std::vector<int>& tris)
     return SDM_OK;
 }
 
+// sdm_warp_crops_tensor (filter null) and sdm_warp_crops_tensor_filtered: the same checks, the same fit, one launch behind it.  The
+// device buffer holds the records, the matrices and -- filtered -- the triangles' (Sx, Sy) behind them, so one copy brings all home.
+int warp_tensor_call(sdm_ctx* c, const sdm_align_tensor* spec, const sdm_align_filter* filter, bool filtered, void* out_dev,
+                     float* matrices_host, int* flags_host, int* samples_host)
+{
+    if (!c) return fail(SDM_ERR_INVALID, "null context");
+    if (c->L <= 0) return fail(SDM_ERR_INVALID, "geometry not set");
+    sdm_ctx::Warp& w = c->warp;
+    if (w.T < 1 || w.L != c->L) return fail(SDM_ERR_INVALID, "no mesh (sdm_warp_set_mesh first)");
+    const int N = c->N, L = c->L, T = w.T;
+    if (N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
+    int rc;
+    if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) || (rc = align_check_out(out_dev)) ||
+        (rc = align_check_rows(c)))
+        return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t rec = (size_t)N * sizeof(WarpFace), mat = (size_t)N * T * 6 * sizeof(float), smp = (size_t)N * T * 2 * sizeof(int);
+    if ((rc = w.rows.ensure(rec + mat + (filtered ? smp : 0)))) return rc;
+    WarpFace* faces = (WarpFace*)w.rows.p;
+    float* matrices = (float*)(w.rows.p + rec);
+    const int* img_idx = c->idx_identity ? nullptr : c->img_idx.p;
+    sdm_launch_warp_fit(c->x[c->cur].p, N, L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, align_source_dev(c), img_idx, faces, matrices,
+                        c->stream);
+    HIP_TRY(hipGetLastError());
+    const AlignTapSource src = align_tap_source(c);
+    if (filtered)
+        sdm_launch_warp_area(src.base, faces, matrices, T, w.labels.p, src.frames, img_idx, src.stack_format, N, w.out_w, w.out_h,
+                             spec->dtype, spec->layout, spec->channels, align_tensor_dev(spec), align_area_dev(filter),
+                             (int*)(w.rows.p + rec + mat), out_dev, c->stream);
+    else
+        sdm_launch_warp_tensor(src.base, faces, matrices, T, w.labels.p, src.frames, img_idx, src.stack_format,
+                               N, w.out_w, w.out_h, spec->dtype, spec->layout, spec->channels, align_tensor_dev(spec), out_dev, c->stream);
+    HIP_TRY(hipGetLastError());
+    // the records, the matrices and the samples in one copy, one synchronise
+    std::vector<unsigned char> host;
+    if (matrices_host || flags_host || samples_host) {
+        host.resize(samples_host ? rec + mat + smp : matrices_host ? rec + mat : rec);
+        HIP_TRY(hipMemcpyAsync(host.data(), w.rows.p, host.size(), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (flags_host)
+        for (int r = 0; r < N; ++r) flags_host[r] = ((const WarpFace*)host.data())[r].flags;
+    if (matrices_host) memcpy(matrices_host, host.data() + rec, mat);
+    if (samples_host) memcpy(samples_host, host.data() + rec + mat, smp);
+    return SDM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -209,38 +256,13 @@ int sdm_warp_get_labels(sdm_ctx* c, uint8_t* labels_host)
 
 int sdm_warp_crops_tensor(sdm_ctx* c, const sdm_align_tensor* spec, void* out_dev, float* matrices_host, int* flags_host)
 {
-    if (!c) return fail(SDM_ERR_INVALID, "null context");
-    if (c->L <= 0) return fail(SDM_ERR_INVALID, "geometry not set");
-    sdm_ctx::Warp& w = c->warp;
-    if (w.T < 1 || w.L != c->L) return fail(SDM_ERR_INVALID, "no mesh (sdm_warp_set_mesh first)");
-    const int N = c->N, L = c->L, T = w.T;
-    if (N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
-    int rc;
-    if ((rc = align_check_spec(spec)) || (rc = align_check_out(out_dev)) || (rc = align_check_rows(c))) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t rec = (size_t)N * sizeof(WarpFace), bytes = rec + (size_t)N * T * 6 * sizeof(float);
-    if ((rc = w.rows.ensure(bytes))) return rc;
-    WarpFace* faces = (WarpFace*)w.rows.p;
-    float* matrices = (float*)(w.rows.p + rec);
-    const int* img_idx = c->idx_identity ? nullptr : c->img_idx.p;
-    sdm_launch_warp_fit(c->x[c->cur].p, N, L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, align_source_dev(c), img_idx, faces, matrices,
-                        c->stream);
-    HIP_TRY(hipGetLastError());
-    const AlignTapSource src = align_tap_source(c);
-    sdm_launch_warp_tensor(src.base, faces, matrices, T, w.labels.p, src.frames, img_idx, src.stack_format,
-                           N, w.out_w, w.out_h, spec->dtype, spec->layout, spec->channels, align_tensor_dev(spec), out_dev, c->stream);
-    HIP_TRY(hipGetLastError());
-    // the records and the matrices in one copy, one synchronise
-    std::vector<unsigned char> host;
-    if (matrices_host || flags_host) {
-        host.resize(matrices_host ? bytes : rec);
-        HIP_TRY(hipMemcpyAsync(host.data(), w.rows.p, host.size(), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (flags_host)
-        for (int r = 0; r < N; ++r) flags_host[r] = ((const WarpFace*)host.data())[r].flags;
-    if (matrices_host) memcpy(matrices_host, host.data() + rec, (size_t)N * T * 6 * sizeof(float));
-    return SDM_OK;
+    return warp_tensor_call(c, spec, nullptr, false, out_dev, matrices_host, flags_host, nullptr);
+}
+
+int sdm_warp_crops_tensor_filtered(sdm_ctx* c, const sdm_align_tensor* spec, const sdm_align_filter* filter, void* out_dev,
+                                   float* matrices_host, int* flags_host, int* samples_host)
+{
+    return warp_tensor_call(c, spec, filter, true, out_dev, matrices_host, flags_host, samples_host);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // sdm_warp.h -- what csrc/sdm_warp.hip (kernels) and csrc/sdm_capi_warp.hip (C-ABI) of the piecewise-affine face warp share
-// (include/sdm.h, "Warped faces"): the per-row record and the two launches.
+// (include/sdm.h, "Warped faces"): the per-row record and the launches.
 #pragma once
 #include "sdm_kernels.h"
 #include "sdm_warp_device.h"
@@ -21,3 +21,8 @@ void sdm_launch_warp_fit(const float* x, int N, int L, const int* lm, int K, con
 void sdm_launch_warp_tensor(const uint8_t* base, const WarpFace* faces, const float* matrices, int T, const uint8_t* labels,
                             const AlignFrameDev* frames, const int* img_idx, int src_format, int N, int out_w, int out_h, int dtype,
                             int layout, int channels, const AlignTensorDev& spec, void* out, hipStream_t s);
+// the same with area-averaged sampling (csrc/sdm_warp_area.hip).  samples: N x T x 2 ints (Sx, Sy), 8-byte aligned, written by the launch
+void sdm_launch_warp_area(const uint8_t* base, const WarpFace* faces, const float* matrices, int T, const uint8_t* labels,
+                          const AlignFrameDev* frames, const int* img_idx, int src_format, int N, int out_w, int out_h, int dtype,
+                          int layout, int channels, const AlignTensorDev& spec, const AlignAreaDev& area, int* samples, void* out,
+                          hipStream_t s);

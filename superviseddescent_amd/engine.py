@@ -807,17 +807,30 @@ class Context:
         check(self._lib.sdm_warp_get_labels(self._h, out.ctypes.data))
         return out
 
-    def warp_crops_tensor(self, spec=None, out=None, **options):
+    def warp_crops_tensor(self, spec=None, out=None, filter=None, **options):
         """The N current rows warped piecewise-affinely onto the mesh's template, as a network's input tensor (include/sdm.h,
         sdm_warp_crops_tensor), from the source ``align_crops_tensor`` reads.  ``spec`` / ``options`` / ``out``: as for
         ``align_crops_tensor``.  Returns (tensor N x C x H x W or N x H x W x C, matrices N x T x 2 x 3 float32 crop -> source, one per
-        triangle, flags N int32: SDM_WARP_* bits)."""
+        triangle, flags N int32: SDM_WARP_* bits).  ``filter``: None (plain bilinear), or "area" / "bilinear" / an
+        ``_lib.SdmAlignFilter`` (``_lib.align_filter``) for sdm_warp_crops_tensor_filtered -- every pixel of a triangle whose map
+        minifies averages Sx x Sy sub-samples -- which returns (tensor, matrices, flags, samples N x T x 2 int32: (Sx, Sy) of every
+        triangle)."""
+        if isinstance(filter, str):
+            filter = _lib.align_filter(filter)
+        elif filter is not None and not isinstance(filter, _lib.SdmAlignFilter):
+            raise ValueError('filter must be None, "area", "bilinear" or an SdmAlignFilter')
         T, width, height = getattr(self, "warp_mesh", (0, 0, 0))
         spec, out, n = self._crop_tensor_out(spec, options, width, height, out)
         mats = np.empty((n, T, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
-        check(self._lib.sdm_warp_crops_tensor(self._h, ctypes.byref(spec), ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
-        return out, mats, flags
+        if filter is None:
+            check(self._lib.sdm_warp_crops_tensor(self._h, ctypes.byref(spec), ctypes.c_void_p(out.data_ptr()), mats.ctypes.data,
+                                                  flags.ctypes.data))
+            return out, mats, flags
+        samples = np.empty((n, T, 2), np.int32)
+        check(self._lib.sdm_warp_crops_tensor_filtered(self._h, ctypes.byref(spec), ctypes.byref(filter), ctypes.c_void_p(out.data_ptr()),
+                                                       mats.ctypes.data, flags.ctypes.data, samples.ctypes.data))
+        return out, mats, flags, samples
 
     # -- crop tensors pasted back into frames (csrc/sdm_align_paste.hip) ------------------------------
     def _paste_call(self, y, layout, frames, formats, mask, spec, options):
@@ -1775,7 +1788,7 @@ class detection_model:
     def warped_crops_tensor(self, size, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
                             triangles: Optional[np.ndarray] = None, margin: float = 0.1, frames=None, formats=None, chroma=None,
                             dtype="float16", layout="nchw", channels=3, order="rgb", scale=None, bias=None, mean=None, std=None,
-                            gray_shift=14, out=None):
+                            gray_shift=14, out=None, filter=None, max_samples=16, min_scale=1.0):
         """The faces of the current rows warped piecewise-affinely onto a template shape -- every landmark lands on its template point:
         the shape-normalised texture -- as a network's input tensor, in two launches from the frames where they lie on the device
         (include/sdm.h, "Warped faces").  ``size``, ``landmark_ids``, ``frames``, ``formats``, ``chroma``, the tensor options and ``out``: as
@@ -1783,10 +1796,15 @@ class detection_model:
         :func:`alignment_template` of the mean with ``margin``).  ``triangles``: T x 3 positions 0 .. K - 1, T <= 254 (default: the
         Delaunay triangulation of the template; a list of one's own may e.g. leave the mouth's interior out).  Pixels that no triangle
         covers are 0 before scale and bias; :meth:`warp_mask` tells them apart.  Returns (tensor, matrices N x T x 2 x 3 crop -> source,
-        flags N: SDM_WARP_* bits).  No pointer to the frames stays behind."""
+        flags N: SDM_WARP_* bits).  No pointer to the frames stays behind.
+        ``filter``: None (plain bilinear) | "area" | "bilinear" | an ``SdmAlignFilter``, with ``max_samples`` and ``min_scale`` as in
+        :func:`align_filter`: with a filter, every pixel of a triangle that is larger in the frame than in the crop is averaged over its
+        footprint, the sub-sample counts chosen per triangle and per axis (include/sdm.h, "Warped faces, filtered"), and the return
+        value is (tensor, matrices, flags, samples N x T x 2: (Sx, Sy) of every triangle)."""
         c = self.optimised_model.ctx
         if not getattr(c, "N", 0):
             raise RuntimeError("run detect_batch or Tracker.step first")
+        filter = c._paste_filter(filter, max_samples, min_scale)
         spec = _lib.align_tensor_spec(dtype, layout, channels, order, scale, bias, mean, std, gray_shift)
         width, height = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
         ids = self.landmark_ids if landmark_ids is None else [str(i) for i in landmark_ids]
@@ -1802,7 +1820,7 @@ class detection_model:
         self._warp_index = idx
         c.align_set_source_frames(frames, formats, chroma)
         try:
-            return c.warp_crops_tensor(spec=spec, out=out)
+            return c.warp_crops_tensor(spec=spec, out=out, filter=filter)
         finally:
             if frames is not None:
                 c.align_set_source_frames(None)                           # (no pointer to the caller's frames stays behind)

@@ -11,6 +11,10 @@
 //
 // The rows of detection_model::detect_batch work the same way (the overload taking the frames and the rows).
 //
+// With an rcr::AlignFilter behind the spec the texture is area-averaged where a triangle minifies (w.samples: Sx, Sy of every triangle):
+//
+//     auto w = rcr::warped_crops_tensor(tr, mesh, rcr::TensorSpec(), rcr::AlignFilter(), out_dev, device_frames);
+//
 // rcr::paste_warped_tensor is the way back: a network's output in template space blended into the frames under every face's own shape.
 //
 //     auto p = rcr::paste_warped_tensor(tr, mesh, paste_spec, net_out_dev, device_frames);       // p.flags[i]: SDM_WARP_*
@@ -71,14 +75,16 @@ struct warped_tensor_result {
     cv::Mat matrices;              // rows x (6 T) CV_32FC1: per row the T crop -> source maps M00 M01 M02 M10 M11 M12 (NaN for a degenerate row)
     std::vector<int> flags;        // SDM_WARP_DEGENERATE / SDM_WARP_PARTIAL / SDM_WARP_FOLDED bits
     cv::Mat labels;                // height x width CV_8UC1: the triangle of every crop pixel, SDM_WARP_NO_TRIANGLE = none
+    std::vector<int> samples;      // the overloads taking an AlignFilter: rows x T x 2, (Sx, Sy) of every triangle; empty otherwise
 };
 
 namespace detail {
 
 // the n current rows of the handle `c` warped onto the mesh's template, as a tensor in device memory, from `frames` in place or -- no
-// frames -- from the handle's own images
+// frames -- from the handle's own images; `filter`: nullptr, or the sampling of sdm_warp_crops_tensor_filtered
 inline warped_tensor_result warp_tensor_current_rows(sdm_ctx* c, int n, const WarpMesh& mesh, const std::vector<DeviceFrame>& frames,
-                                                     const std::vector<const void*>& chroma, const TensorSpec& spec, void* out_dev)
+                                                     const std::vector<const void*>& chroma, const TensorSpec& spec, void* out_dev,
+                                                     const AlignFilter* filter = nullptr)
 {
     using superviseddescent::hip::check;
     if (mesh.tmpl.rows != (int)mesh.landmark_index.size() || mesh.tmpl.cols != 2 || mesh.tmpl.type() != CV_32FC1)
@@ -98,12 +104,37 @@ inline warped_tensor_result warp_tensor_current_rows(sdm_ctx* c, int n, const Wa
     warped_tensor_result res;
     res.matrices = cv::Mat(n, 6 * mesh.n_triangles(), CV_32FC1);
     res.flags.resize((size_t)n);
-    const int rc = sdm_warp_crops_tensor(c, &s, out_dev, res.matrices.ptr<float>(0), res.flags.data());
+    int rc;
+    if (filter) {
+        const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
+        res.samples.resize((size_t)n * mesh.n_triangles() * 2);
+        rc = sdm_warp_crops_tensor_filtered(c, &s, &fl, out_dev, res.matrices.ptr<float>(0), res.flags.data(), res.samples.data());
+    } else {
+        rc = sdm_warp_crops_tensor(c, &s, out_dev, res.matrices.ptr<float>(0), res.flags.data());
+    }
     if (!frames.empty()) sdm_align_set_source_frames(c, nullptr, nullptr, 0);     // (no pointer to the caller's frames stays behind)
-    check(rc, "sdm_warp_crops_tensor");
+    check(rc, filter ? "sdm_warp_crops_tensor_filtered" : "sdm_warp_crops_tensor");
     res.labels = cv::Mat(mesh.height, mesh.width, CV_8UC1);
     check(sdm_warp_get_labels(c, res.labels.ptr<uint8_t>(0)), "sdm_warp_get_labels");
     return res;
+}
+
+// landmark rows on device frames: a handle of its own, the frames as its image set, the rows uploaded
+inline warped_tensor_result warp_tensor_rows(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                             const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec, void* out_dev,
+                                             const std::vector<const void*>& chroma, const AlignFilter* filter)
+{
+    using superviseddescent::hip::check;
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    sdm_ctx* c = h.get();
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::set_device_frames(h, frames);
+    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
+    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("warped_crops_tensor: rows must hold 2L coordinates");
+    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
+    return detail::warp_tensor_current_rows(c, x.rows, mesh, frames, chroma, spec, out_dev, filter);
 }
 
 }  // namespace detail
@@ -125,17 +156,24 @@ inline warped_tensor_result warped_crops_tensor(detection_model& model, const st
                                                 const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec, void* out_dev,
                                                 const std::vector<const void*>& chroma = {})
 {
-    using superviseddescent::hip::check;
-    superviseddescent::hip::Handle h(superviseddescent::hip::device());
-    sdm_ctx* c = h.get();
-    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
-    detail::set_device_frames(h, frames);
-    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
-    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("warped_crops_tensor: rows must hold 2L coordinates");
-    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
-    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
-    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
-    return detail::warp_tensor_current_rows(c, x.rows, mesh, frames, chroma, spec, out_dev);
+    return detail::warp_tensor_rows(model, frames, rows, image_index, mesh, spec, out_dev, chroma, nullptr);
+}
+
+/** The two forms with area-averaged sampling (include/sdm.h, "Warped faces, filtered"; rcr::AlignFilter of rcr/alignment.hpp): every pixel
+ *  of a triangle whose map minifies is the average of Sx x Sy bilinear sub-samples of its footprint, the counts chosen per triangle and
+ *  per axis; triangles at (1, 1) get the bits of the forms above.  The result's `samples` holds rows x T x 2 counts. */
+inline warped_tensor_result warped_crops_tensor(tracker& tr, const WarpMesh& mesh, const TensorSpec& spec, const AlignFilter& filter, void* out_dev,
+                                                const std::vector<DeviceFrame>& frames = {}, const std::vector<const void*>& chroma = {})
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("warped_crops_tensor: step the tracker first");
+    return detail::warp_tensor_current_rows(tr.context(), tr.rows().rows, mesh, frames, chroma, spec, out_dev, &filter);
+}
+
+inline warped_tensor_result warped_crops_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                                const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec,
+                                                const AlignFilter& filter, void* out_dev, const std::vector<const void*>& chroma = {})
+{
+    return detail::warp_tensor_rows(model, frames, rows, image_index, mesh, spec, out_dev, chroma, &filter);
 }
 
 struct warp_paste_result {
