@@ -383,6 +383,10 @@ int sdm_debug_hog_plan(int num_cells, int cell_size, int num_bins, int num_landm
 /* cut[num_landmarks]: 1 where the landmark's patch is cut by a pass boundary of that plan (its raw cell histograms arrive in two
  * parts, csrc/sdm_hog_packed.hip CELLS form); host only.  Returns SDM_ERR_INVALID when the geometry has no packed instance. */
 int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_landmarks, int* cut);
+/* columns3[num_landmarks][3] = {cut, jA, jB}: part 0 of the landmark's raw cells holds the cell columns 0 .. jA, part 1 (cut patches)
+ * the columns jB .. num_cells - 1; no other (part, column) is written or read, its fold weights are all zero (csrc/sdm_kernels.h:
+ * HogPlanHost::cut).  Uncut: {0, num_cells - 1, num_cells}.  Host only; SDM_ERR_INVALID when the geometry has no packed instance. */
+int sdm_debug_hog_plan_columns(int num_cells, int cell_size, int num_bins, int num_landmarks, int* columns3);
 /* Tests: the band-slot weights {slot 0, slot 1} of the resized-ROI rows d < num_cells * cell_size (hog.c:697-704; zero for the cell
  * rows -1 and num_cells, swapped on odd bands; rows from num_cells * cell_size on are zero) as the one definition of them gives them
  * (csrc/sdm_kernels.h: packed_row_const) -- for the cell sizes with specialised pixel-kernel instances the values the COMPILER

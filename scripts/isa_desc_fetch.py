@@ -9,7 +9,7 @@ A .hip file (default: superviseddescent_amd/csrc/sdm_desc.hip) is compiled with
 (include path: the default source's directory; further arguments go to the compiler), a .s file is read as it is.  Per fused instance:
 
   * registers, scratch and the compiler's occupancy figure;
-  * the descriptor part (everything in front of the first s_barrier), one line per basic block: L = a global load, w(n) = s_waitcnt
+  * the descriptor part (everything in front of the first s_barrier), one line per basic block: L = a global or buffer load, w(n) = s_waitcnt
     vmcnt(n), p = the eight ds_bpermute of the cell norms (the middle of a patch's arithmetic), s = the stores of the staged
     descriptor (its end), `-> label` = the block's branch.  The prefetch of the next patch is the L run in the block of the loop's
     head; a w between it and the s of the same pass is a wait in front of arithmetic that does not need the data yet;
@@ -87,7 +87,7 @@ def tokens(lines):
         if s.startswith("."):
             continue
         op = s.split()[0]
-        if op.startswith("global_load"):
+        if op.startswith(("global_load", "buffer_load")):
             out.append(("L", op))
         elif op == "s_waitcnt":
             m = re.search(r"vmcnt\((\d+)\)", s)

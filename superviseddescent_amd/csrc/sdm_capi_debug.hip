@@ -137,7 +137,24 @@ int sdm_debug_hog_plan_cut(int num_cells, int cell_size, int num_bins, int num_l
     fill_row_tab(lv);
     HogPlanHost hp;
     if (!sdm_hog_plan_build(lv, num_landmarks, hp)) return fail(SDM_ERR_INVALID, "no packed instance for this geometry");
-    memcpy(cut, hp.cut.data(), (size_t)num_landmarks * sizeof(int));
+    for (int l = 0; l < num_landmarks; ++l) cut[l] = hp.cut[(size_t)l] & 1;
+    return SDM_OK;
+}
+
+// the cell columns the two parts of every landmark's raw cells hold (HogPlanHost::cut): columns3[l] = {cut flag, jA, jB}
+int sdm_debug_hog_plan_columns(int num_cells, int cell_size, int num_bins, int num_landmarks, int* columns3)
+{
+    if (!columns3 || num_landmarks <= 0) return fail(SDM_ERR_INVALID, "bad arguments");
+    HogLevelDev lv;
+    memset(&lv, 0, sizeof(lv));
+    lv.variant = SDM_VARIANT_UOCTTI; lv.C = num_cells; lv.cell = cell_size; lv.O = num_bins; lv.S = num_cells * cell_size;
+    fill_row_tab(lv);
+    HogPlanHost hp;
+    if (!sdm_hog_plan_build(lv, num_landmarks, hp)) return fail(SDM_ERR_INVALID, "no packed instance for this geometry");
+    for (int l = 0; l < num_landmarks; ++l) {
+        const int w = hp.cut[(size_t)l];
+        columns3[3 * l] = w & 1; columns3[3 * l + 1] = (w >> 8) & 0xff; columns3[3 * l + 2] = (w >> 16) & 0xff;
+    }
     return SDM_OK;
 }
 

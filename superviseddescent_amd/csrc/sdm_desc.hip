@@ -1,7 +1,7 @@
 // sdm_desc.hip -- from raw cell histograms to descriptors, and (detect) straight on to the regressor update, for gfx950.
 //
 // Second half of the HOG transform of the default (column-sum) mode, split off the pixel kernel in round 4:
-//   hog_packed_kernel<..., CELLS> (sdm_hog_packed.hip) leaves cells[sample][landmark][part][C*C][2O] in HBM (vl_hog_put_image,
+//   hog_packed_kernel<..., CELLS> (sdm_hog_packed.hip) leaves cells[sample][landmark][part][cell column][cell row][2O] in HBM (vl_hog_put_image,
 //   include/rcr/hog.c:595-728); this file is vl_hog_extract (hog.c:857-1062) + the Matlab cell order of
 //   rcr::HogTransform::operator() (include/rcr/adaptive_vlhog.hpp:166-175), and in detect also
 //   LinearRegressor::predict (include/superviseddescent/regressors.hpp:377-381) for the landmark's rows of the regressor.
@@ -88,15 +88,22 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
     const int half = lane >> 5, cell = lane & 31;
     const bool active = cell < CC;
     const int cc = active ? cell : CC - 1;
-    const int y = cc / C, x = cc - y * C, ct = x * C + y;                    // Matlab order, adaptive_vlhog.hpp:166-175
+    // The lanes take the cells COLUMN by column, the order of the cells in memory (cells[..][part][cell column][cell row][2O]):
+    // neighbouring lanes load neighbouring 2O floats.  ct: the cell in Matlab order (adaptive_vlhog.hpp:166-175), which is that order;
+    // ci: the cell row by row, the order of the staged operand and of the regressor planes (desc_planes_kernel).
+    const int x = cc / C, y = cc - x * C, ct = x * C + y, ci = y * C + x;
     // lanes of the clamped 3 x 3 neighbourhood (hog.c:930-981: a block factor sums the norms of 2 x 2 cells, clamped at the border)
     const int xm = x > 0 ? x - 1 : 0, xp = x < C - 1 ? x + 1 : C - 1, ym = y > 0 ? y - 1 : 0, yp = y < C - 1 ? y + 1 : C - 1;
     const int lb = half * 32;
-    const int iA = (lb + ym * C + xm) * 4, iB = (lb + ym * C + x) * 4, iC = (lb + ym * C + xp) * 4;
-    const int iD = (lb + y * C + xm) * 4, iF = (lb + y * C + xp) * 4;
-    const int iG = (lb + yp * C + xm) * 4, iH = (lb + yp * C + x) * 4, iI = (lb + yp * C + xp) * 4;
+    const int iA = (lb + xm * C + ym) * 4, iB = (lb + x * C + ym) * 4, iC = (lb + xp * C + ym) * 4;
+    const int iD = (lb + xm * C + y) * 4, iF = (lb + xp * C + y) * 4;
+    const int iG = (lb + xm * C + yp) * 4, iH = (lb + x * C + yp) * 4, iI = (lb + xp * C + yp) * 4;
     const unsigned ipk0 = iA | iB << 8 | iC << 16 | iD << 24, ipk1 = iF | iG << 8 | iH << 16 | iI << 24;      // (fused form, below)
-    const bool is_cut = cut[l] != 0;
+    // the landmark's plan word (HogPlanHost::cut): cut flag | jA << 8 | jB << 16.  Part 0 holds this lane's cell column iff x <= jA,
+    // part 1 iff the patch is cut and x >= jB; what a part does not hold was never written (its fold weights are all zero)
+    const int cutw = cut[l];
+    const bool is_cut = (cutw & 1) != 0;
+    const bool ld0 = x <= ((cutw >> 8) & 0xff), ld1 = x >= ((cutw >> 16) & 0xff);
 
     if (FUSED) {      // the rows' padding (and the spare bytes behind the last row) is read by the last k-step: zero it once
         constexpr int PADW = KS - PK;
@@ -114,33 +121,43 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
     constexpr float SC = (FUSED ? 4096.0f : 1.0f) * (VARIANT == 1 ? 0.5f : 1.0f);
     constexpr float CLAMP = 0.2f * SC;
     typedef float f32x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x4u __attribute__((ext_vector_type(4), aligned(8)));
-    typedef float f32x2u __attribute__((ext_vector_type(2), aligned(8)));
     constexpr int NIT = FB / (2 * W);
     auto face_of = [&](int it) { const int fr = tile * FB + it * (2 * W) + wave * 2 + half; return fr < N ? fr : N - 1; };      // (a partial last tile repeats the last sample; never stored)
-    // cells[sample][landmark][part][cell][2O]: this lane's cell = 2O consecutive floats
     // A patch cut by a pass boundary has a second part, the second pass's partial folds (same sum as the in-kernel "+=").  The store
     // form adds it here, as it arrives.  The fused form (DEFER) keeps it in registers of its own, h2, and adds it where the iteration
     // takes the patch over: added here, the sum needs the loaded values at once, and the prefetch below was waited for in front of the
     // arithmetic it should have run under.
     constexpr bool DEFER = FUSED;
-    auto load_cells = [&](int it, float* h, float* h2) {
-        const float* hp = cells + ((((long long)face_of(it) * L + l) * 2) * CC + cc) * (2 * O);
+    // cells[sample][landmark][part][cell column][cell row][2O]: the lane's cell is ct.  The loads are buffer loads on the workgroup's
+    // own faces (the tile's real ones: nothing outside them can be addressed), and a lane whose cell column a part does not hold gives
+    // an offset outside the buffer's range: the range check returns +0.0f for it and fetches nothing -- the value the pixel kernel
+    // used to store there and this kernel to read back.  So the sums below have the operands they always had: p + (+0) where one part
+    // holds the column, p + q in that order where both do.
+    constexpr int PARTB = CC * 2 * O * 4;                                     // bytes of a part
+    const int faceb = L * 2 * PARTB;                                          // ... of a face
+    const int nf = N - tile * FB < FB ? N - tile * FB : FB;                   // real faces of the tile (>= 1)
+    const __amdgpu_buffer_rsrc_t crs = __builtin_amdgcn_make_buffer_rsrc((void*)(cells + (long long)tile * FB * L * 2 * CC * 2 * O), 0, nf * faceb, 0x00020000);
+    const int cellb = (l * 2 * CC + ct) * (2 * O * 4);
+    constexpr int NOWHERE = (int)0x80000000;
+    const int off0 = ld0 ? cellb : NOWHERE, off1 = ld1 ? cellb + PARTB : NOWHERE;
+    auto load_part = [&](int off, float* h, const bool add) {
 #pragma unroll
-        for (int j = 0; j + 4 <= 2 * O; j += 4) { const f32x4u v = *(const f32x4u*)(hp + j); h[j] = v[0]; h[j + 1] = v[1]; h[j + 2] = v[2]; h[j + 3] = v[3]; }
-        if ((2 * O) % 4) { const f32x2u v = *(const f32x2u*)(hp + (2 * O) / 4 * 4); h[(2 * O) / 4 * 4] = v[0]; h[(2 * O) / 4 * 4 + 1] = v[1]; }
-        if (is_cut) {
-            const float* hq = hp + (size_t)CC * 2 * O;
-            if (DEFER) {
-#pragma unroll
-                for (int j = 0; j + 4 <= 2 * O; j += 4) { const f32x4u v = *(const f32x4u*)(hq + j); h2[j] = v[0]; h2[j + 1] = v[1]; h2[j + 2] = v[2]; h2[j + 3] = v[3]; }
-                if ((2 * O) % 4) { const f32x2u v = *(const f32x2u*)(hq + (2 * O) / 4 * 4); h2[(2 * O) / 4 * 4] = v[0]; h2[(2 * O) / 4 * 4 + 1] = v[1]; }
-            } else {
-#pragma unroll
-                for (int j = 0; j + 4 <= 2 * O; j += 4) { const f32x4u v = *(const f32x4u*)(hq + j); h[j] += v[0]; h[j + 1] += v[1]; h[j + 2] += v[2]; h[j + 3] += v[3]; }
-                if ((2 * O) % 4) { const f32x2u v = *(const f32x2u*)(hq + (2 * O) / 4 * 4); h[(2 * O) / 4 * 4] += v[0]; h[(2 * O) / 4 * 4 + 1] += v[1]; }
-            }
+        for (int j = 0; j + 4 <= 2 * O; j += 4) {
+            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(crs, off + 4 * j, 0, 0));
+            if (add) { h[j] += v[0]; h[j + 1] += v[1]; h[j + 2] += v[2]; h[j + 3] += v[3]; }
+            else { h[j] = v[0]; h[j + 1] = v[1]; h[j + 2] = v[2]; h[j + 3] = v[3]; }
         }
+        if ((2 * O) % 4) {
+            constexpr int j = (2 * O) / 4 * 4;
+            const f32x2 v = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(crs, off + 4 * j, 0, 0));
+            if (add) { h[j] += v[0]; h[j + 1] += v[1]; }
+            else { h[j] = v[0]; h[j + 1] = v[1]; }
+        }
+    };
+    auto load_cells = [&](int it, float* h, float* h2) {
+        const int fo = (face_of(it) - tile * FB) * faceb;      // (NOWHERE + fo stays out of range: fo < 2^31)
+        load_part(fo + off0, h, false);
+        if (is_cut) load_part(fo + off1, DEFER ? h2 : h, !DEFER);
     };
     static_assert((2 * TO) % 2 == 0, "");
     float hn[2 * O], hn2[DEFER ? 2 * O : 1] = {};
@@ -160,7 +177,7 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
         }
         if (it + 1 < NIT) load_cells(it + 1, hn, hn2);                   // the next patch's cells are in flight during this one's arithmetic
         if (DS_ABL == 2 && FUSED) {
-            if (active) { float t = 0.0f; for (int j = 0; j < 2 * O; ++j) t += h[j]; stage_hi[(size_t)m * KS + cc * DP] = (unsigned short)(t == 12345.0f); }
+            if (active) { float t = 0.0f; for (int j = 0; j < 2 * O; ++j) t += h[j]; stage_hi[(size_t)m * KS + ci * DP] = (unsigned short)(t == 12345.0f); }
             continue;
         }
         // cell norm (hog.c:875-890)
@@ -220,8 +237,8 @@ desc_kernel(const float* __restrict__ cells, const int* __restrict__ cut, int N,
         } else if (active) {
             // v 2^12 = h1 + h2: h1 = the leading 11 bits (exact in float16), h2 = float16(v 2^12 - h1)   (apply_split8); two features
             // per conversion, eight per 16-byte store, the cell's DP features contiguous in the staged row
-            u32x4* sh = (u32x4*)(stage_hi + (size_t)m * KS + cc * DP);
-            u32x4* sl = (u32x4*)(stage_lo + (size_t)m * KS + cc * DP);
+            u32x4* sh = (u32x4*)(stage_hi + (size_t)m * KS + ci * DP);
+            u32x4* sl = (u32x4*)(stage_lo + (size_t)m * KS + ci * DP);
 #pragma unroll
             for (int q = 0; q < DP / 8; ++q) {
                 u32x4 vh, vl;

@@ -248,7 +248,7 @@ __device__ void hog_finish_direct(const float* hist, unsigned char* scratch, flo
 // (the round-2 form of the loop).  RAW: the gradient magnitude is v_sqrt_f32 as the hardware returns it (chosen per level at
 // sdm_set_model_geometry, only if the exhaustive check found it exact or one ulp low on all 511^2 gradients).
 // CELLS: the launch stops at the raw cell histograms (round 4): every band fold stores its cells straight to HBM,
-// cells[sample][landmark][part][C*C][2O] (a lane stores its four bins of one cell with one 16-byte store; part 0: the pass that sees the patch's first column, part 1: the second pass of a
+// cells[sample][landmark][part][cell column][cell row][2O] (a lane stores its four bins of one cell with one 16-byte store; part 0: the pass that sees the patch's first column, part 1: the second pass of a
 // patch cut by a pass boundary -- the consumer adds the two), there are no histogram slots in LDS and no normalisation phase in
 // this kernel: sdm_desc.hip normalises (hog.c:857-1062) with a lane per cell and either writes the feature rows or multiplies
 // the descriptors by the regressor while they are still on the chip.  `feat` is then the cells buffer, `ldf` unused.
@@ -492,16 +492,19 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
         const i32x4 pinfo = CELLS ? pinfo1 : *(const i32x4*)(plan.pass_info + pt * 4);
         const int sg = li < C ? 0 : (li < 2 * C ? 1 : (li < 3 * C ? 2 : 3));
         const int seg_slot = sg == 0 ? pinfo.x : (sg == 1 ? pinfo.y : (sg == 2 ? pinfo.z : -1));
-        const bool recv = seg_slot >= 0;                                   // (rows 16 mt + 4 lq + e >= 2O are skipped at the store)
+        // (rows 16 mt + 4 lq + e >= 2O are skipped at the store)
+        // CELLS: ... and the cell columns of a cut patch that this pass's weights leave at exact zero are not stored at all (bit 24 of
+        // the lane's plan word, known here, once per pass: sdm_hog_plan.hip, plan_cut_columns; sdm_desc.hip does not load them)
+        const bool recv = seg_slot >= 0 && (!CELLS || ((desc >> 24) & 1u));
         const int done = pinfo.w;
         const int nkp = (done >> 16) & 0xff;          // k-step pairs (8 lanes each) that hold columns in this pass
         // the first pass that touches a patch STORES its cells, a later one (the patch was cut) adds to them: the histogram
         // slots need no clearing, and the uncut patches no read-modify-write
         const bool first_seen = sg < 3 && ((done >> (24 + sg)) & 1);
         float* hrecv;
-        if (CELLS)      // HBM: cells[sample][landmark][part][cell][bin]; part 1 = the second pass of a cut patch.  A lane holds four
-                        // consecutive bins of one cell: one 16-byte store per fold
-            hrecv = feat + ((((long long)s * L + lm0 + (seg_slot >= 0 ? seg_slot : 0)) * 2 + (first_seen ? 0 : 1)) * CC + (li - sg * C)) * (2 * O) + 4 * lq;
+        if (CELLS)      // HBM: cells[sample][landmark][part][cell column][cell row][bin]; part 1 = the second pass of a cut patch.  A lane
+                        // holds four consecutive bins of one cell: one 16-byte store per fold (band b = cell row b of the lane's column)
+            hrecv = feat + ((((long long)s * L + lm0 + (seg_slot >= 0 ? seg_slot : 0)) * 2 + (first_seen ? 0 : 1)) * CC + (li - sg * C) * C) * (2 * O) + 4 * lq;
         else
             hrecv = hist + (seg_slot >= 0 ? hist_slot(seg_slot) : 0) * HSTR + (4 * lq) * CC + (li - sg * C);
 
@@ -670,12 +673,12 @@ hog_packed_kernel(ImageSetDev imgs, const int* __restrict__ img_idx, const float
                 if (recv) {
                     typedef float f32x4u __attribute__((ext_vector_type(4), aligned(8)));
                     if (pair) {      // rows 4 lq .. 4 lq + 3: bins 4 (lq & 1) .. of band b + (lq >> 1)
-                        float* hf = hrecv + ((b + (lq >> 1)) * C) * (2 * O) - 4 * lq + 4 * (lq & 1);
+                        float* hf = hrecv + (b + (lq >> 1)) * (2 * O) - 4 * lq + 4 * (lq & 1);
                         *(f32x4u*)hf = fa0[0] + fa1[0];
                     } else {
 #pragma unroll
                         for (int mt = 0; mt < MT; ++mt) {
-                            float* hf = hrecv + b * C * (2 * O) + 16 * mt;
+                            float* hf = hrecv + b * (2 * O) + 16 * mt;
                             const int left = 2 * O - (16 * mt + 4 * lq);      // bins from this lane's first one to the last
                             if (left >= 4) *(f32x4u*)hf = fa0[mt] + fa1[mt];
                             else if (left >= 2) *(f32x2*)hf = (f32x2){fa0[mt][0] + fa1[mt][0], fa0[mt][1] + fa1[mt][1]};

@@ -51,6 +51,65 @@ int plan_pack(int S, int npatch, std::vector<std::vector<PlanLane>>& passes)
     if (pw <= pc) { passes.swap(whole); return pw; }
     return pc;
 }
+// Which cell columns of a cut patch each of its two passes has to move (HogPlanDev: cut word, lane_tab bit 24), read from the
+// finished fold tables themselves -- wb and wb16, what the kernels multiply by -- not from the packing: a pixel column feeds its two
+// nearest cell columns only, so the pass left of a cut folds exact +0 into the cell columns right of the overlap and the pass
+// right of it into those left of it.  jA = the last cell column with a non-zero weight in the pass that holds the patch's
+// column 0 (part 0), jB = the first one with a non-zero weight in the other pass (part 1); an uncut patch keeps all C columns.
+// A (pass, matrix column) is dropped only where every weight of it, in both tables, is zero (halo lanes have none); false if a
+// column of a cut patch would be left without an owner.
+bool plan_cut_columns(int C, HogPlanHost& out)
+{
+    const int NP = out.P + out.Pt, L = (int)out.cut.size();
+    auto nonzero = [&](int pt, int n) {
+        for (int l = n; l < 64; l += 16) {
+            for (int ks = 0; ks < 16; ++ks)
+                if (out.wb[((size_t)pt * 64 + l) * 16 + ks] != 0.0f) return true;
+            for (int k = 0; k < 32; ++k)
+                if (out.wb16[((size_t)pt * 64 + l) * 32 + k] & 0x7fffu) return true;
+        }
+        return false;
+    };
+    auto first_landmark = [&](int pt, int slot) { return pt < out.P ? slot : out.n_main * out.G + slot; };
+    std::vector<int> jA((size_t)L, -1), jB((size_t)L, C);
+    for (int pt = 0; pt < NP; ++pt) {
+        const int first_bits = (out.pass_info[(size_t)pt * 4 + 3] >> 24) & 7;
+        for (int sg = 0; sg < SDM_PLAN_MAX_SEG; ++sg) {
+            const int slot = out.pass_info[(size_t)pt * 4 + sg];
+            if (slot < 0) continue;
+            int lo = C, hi = -1;
+            for (int j = 0; j < C; ++j)
+                if (nonzero(pt, sg * C + j)) { if (lo == C) lo = j; hi = j; }
+            const int reps = pt < out.P ? out.n_main : 1;      // the passes of the main groups stand for every main group
+            for (int g = 0; g < reps; ++g) {
+                const int lm = first_landmark(pt, slot) + g * out.G;
+                if ((first_bits >> sg) & 1) jA[lm] = hi; else jB[lm] = lo;
+            }
+        }
+    }
+    for (int l = 0; l < L; ++l) {
+        const bool cut = out.cut[l] != 0;
+        if (!cut) { jA[l] = C - 1; jB[l] = C; }
+        else if (jA[l] < 0 || jB[l] > C - 1 || jA[l] + 1 < jB[l]) return false;
+        out.cut[l] = (cut ? 1 : 0) | (jA[l] << 8) | (jB[l] << 16);
+    }
+    for (int pt = 0; pt < NP; ++pt) {
+        const int first_bits = (out.pass_info[(size_t)pt * 4 + 3] >> 24) & 7;
+        unsigned stores = 0;
+        for (int sg = 0; sg < SDM_PLAN_MAX_SEG; ++sg) {
+            const int slot = out.pass_info[(size_t)pt * 4 + sg];
+            if (slot < 0) continue;
+            const int w = out.cut[first_landmark(pt, slot)];
+            for (int j = 0; j < C; ++j) {
+                const bool keep = !(w & 1) || (((first_bits >> sg) & 1) ? j <= ((w >> 8) & 0xff) : j >= ((w >> 16) & 0xff));
+                if (!keep && nonzero(pt, sg * C + j)) return false;
+                if (keep) stores |= 1u << (sg * C + j);
+            }
+        }
+        for (int x = 0; x < 64; ++x) out.lane_tab[(size_t)pt * 64 + x] |= ((stores >> (x & 15)) & 1u) << 24;
+    }
+    return true;
+}
 template <int CELL, int C>
 const HogRowConst* compiled_rows()
 {
@@ -168,5 +227,5 @@ bool sdm_hog_plan_build(const HogLevelDev& lv, int L, HogPlanHost& out)
                     out.wb16[(((size_t)pt * 64 + l) * 2 + kb) * 16 + 8 + j] = b2;
                 }
     }
-    return true;
+    return plan_cut_columns(lv.C, out);
 }

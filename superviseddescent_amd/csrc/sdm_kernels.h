@@ -91,7 +91,8 @@ void sdm_launch_hog_fast(const ImageSetDev& imgs, const int* img_idx, const floa
 // Gt = L - n_main * G patches, 0 = none).  One wave walks a group in P (Pt) passes; in a pass every lane owns one pixel
 // column of one patch of the group, so a 50-column ROI no longer leaves 14 lanes idle: five of them share four passes.
 // A patch cut by a pass boundary repeats one column on either side of the cut (the gradient's left / right neighbour).
-//   lane_tab[pass][lane]  patch slot in the group | column << 8 | contributes << 16 | lane in use << 17 | segment << 20
+//   lane_tab[pass][lane]  patch slot in the group | column << 8 | contributes << 16 | lane in use << 17 | segment << 20 |
+//                         (matrix column n = lane & 15 of this pass stores its cells: CELLS form, see `cut`) << 24
 //   wb[pass][lane][16]    the fold weights W[x][n] (hog.c:697-704; n = segment * C + cell column) in the order the
 //                         matrix-core B operand wants them: entry ks of lane l is W[4 ks + (l >> 4)][l & 15]
 //   pass_info[pass][4]    patch slot of segment 0, 1, 2 (-1 = none); first completed patch slot | count << 8 | k-step pairs in
@@ -147,7 +148,10 @@ struct HogPlanHost {
     std::vector<float> wb;
     std::vector<unsigned short> wb16;
     std::vector<int> pass_info;
-    std::vector<int> cut;      // [L] 1: the landmark's patch is cut by a pass boundary (its raw cells arrive in two parts)
+    std::vector<int> cut;      // [L] bit 0: the landmark's patch is cut by a pass boundary (its raw cells arrive in two parts) | jA << 8 |
+                               // jB << 16: part 0 holds the cell columns 0 .. jA, part 1 (cut patches) the columns jB .. C - 1; the columns
+                               // in jB .. jA are the sum of both.  Uncut: jA = C - 1, jB = C.  Every other (part, column) would hold the
+                               // exact zeros of all-zero fold weights: the pixel kernel does not store it, sdm_desc.hip does not load it
 };
 // false when the level has no packed instance (then sdm_launch_hog_fast runs it)
 bool sdm_hog_plan_build(const HogLevelDev& lv, int L, HogPlanHost& out);
@@ -156,8 +160,10 @@ void sdm_launch_hog_packed(const ImageSetDev& imgs, const int* img_idx, const fl
                            const EyeIdxDev& eyes, const HogLevelDev& lv, const HogPlanDev& plan, float* feat, long long ldf,
                            int* idx_out, int* status, hipStream_t stream);
 
-// The packed launch stopping at the raw cell histograms (round 4): cells[N][L][2 parts][C*C][2O] f32 (a cell's 2O bins are consecutive: what the producer's band folds store and sdm_desc.hip's lane per cell loads); part 1 is written only
-// for landmarks with plan cut[l] = 1 (patch cut by a pass boundary); sdm_desc.hip turns them into descriptors.
+// The packed launch stopping at the raw cell histograms (round 4): cells[N][L][2 parts][C cell columns][C cell rows][2O] f32 (a cell's 2O bins are consecutive: what the producer's band folds store and sdm_desc.hip's lane per cell loads;
+// a cell COLUMN is C * 2O consecutive floats, so the columns a part of a cut patch does not hold -- the tail of part 0, the head of part 1: HogPlanHost::cut -- are whole
+// runs of memory that are neither written nor read); part 1 is written only
+// for landmarks with plan cut[l] & 1 (patch cut by a pass boundary); sdm_desc.hip turns them into descriptors.
 void sdm_launch_hog_cells(const ImageSetDev& imgs, const int* img_idx, const float* x, int N, int L,
                           const EyeIdxDev& eyes, const HogLevelDev& lv, const HogPlanDev& plan, float* cells,
                           int* idx_out, int* status, hipStream_t stream);

@@ -1136,8 +1136,10 @@ def hog_plan(num_cells: int, cell_size: int, num_bins: int, num_landmarks: int, 
     n = int(info[1] + info[4])
     cut = np.zeros(num_landmarks, np.int32)
     check(L.sdm_debug_hog_plan_cut(num_cells, cell_size, num_bins, num_landmarks, _ip(cut)))
+    cols = np.zeros((num_landmarks, 3), np.int32)      # {cut, jA, jB}: the cell columns part 0 (0 .. jA) and part 1 (jB ..) hold
+    check(L.sdm_debug_hog_plan_columns(num_cells, cell_size, num_bins, num_landmarks, _ip(cols)))
     return {"G": int(info[0]), "P": int(info[1]), "n_main": int(info[2]), "Gt": int(info[3]), "Pt": int(info[4]),
-            "lane_tab": lane_tab[:n], "wb": wb[:n], "pass_info": pass_info[:n], "cut": cut}
+            "lane_tab": lane_tab[:n], "wb": wb[:n], "pass_info": pass_info[:n], "cut": cut, "columns": cols}
 
 
 def hog_band_weights(cell_size: int, num_cells: int):
