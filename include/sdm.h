@@ -779,7 +779,7 @@ int sdm_warp_crops_tensor(sdm_ctx* ctx, const sdm_align_tensor* spec, void* out_
  * count is not -- two neighbouring triangles may average over different grids --; and A_t extrapolates up to half a crop pixel past its
  * triangle for the sub-samples of the triangle's border pixels.
  * samples_host (N x T x 2) may be NULL; it comes back with the matrices and flags in the same single copy and synchronise.  The paste
- * direction (sdm_warp_paste_tensor*) has no such filter. */
+ * direction has the same filter, on W_t: sdm_warp_paste_tensor_filtered ("Pasting warped faces back, filtered"). */
 int sdm_warp_crops_tensor_filtered(sdm_ctx* ctx, const sdm_align_tensor* spec, const sdm_align_filter* filter, void* out_dev,
                                    float* matrices_host /* N x T x 6 */, int* flags_host /* N */,
                                    int* samples_host /* N x T x 2: (Sx, Sy) of every triangle; may be NULL */);
@@ -858,8 +858,8 @@ int sdm_align_paste_tensor_at(sdm_ctx* ctx, const float* matrices_host /* in, n_
  * behind the prepare stage.  Every rule of "Pasting crops back" that is not restated here holds word for word: M, W, the flags, the
  * decode, the clamped colour taps, opacity 0 outside the crop, the / 255 blend, per-byte stores, the alpha byte never touched, the rows
  * of one frame applied in increasing row number.  NV12 destinations are refused here too (they go through sdm_align_paste_tensor_nv12
- * with this filter, "Pasting crops back into NV12 frames" below); the piecewise-affine paste (sdm_warp_paste_tensor*)
- * stays plain bilinear.  Every float operation is rounded on its own, nothing is contracted.
+ * with this filter, "Pasting crops back into NV12 frames" below); the piecewise-affine paste has its own filtered form, per triangle
+ * and per axis ("Pasting warped faces back, filtered").  Every float operation is rounded on its own, nothing is contracted.
  *   S of row n   s2 = W00 W00 + W10 W10 in float32 on the float32 W, each operation rounded: the mirror image of
  *           sdm_align_crops_tensor_filtered, which takes it from M.  S = 1 for mode BILINEAR, for s2 < min_scale * min_scale (float32),
  *           for a non-finite s2 and for a DEGENERATE row; otherwise the smallest integer in [1, max_samples] with (float)(S S) >= s2, and
@@ -985,8 +985,8 @@ int sdm_align_paste_tensor_at_nv12(sdm_ctx* ctx, const float* matrices_host /* i
  *           stored once and only if some opacity was not 0, stores are per byte.
  * NV12 destinations are refused here and taken by sdm_warp_paste_tensor_nv12 / _at_nv12 ("Pasting warped faces back into NV12
  * frames" below, with the block ownership of "Pasting crops back into NV12 frames").
- * Out of scope, and not half-built: any antialiasing when the face in the frame is smaller than its crop;
- * a colour renormalised at the hull's border.
+ * These calls are plain bilinear; the antialiasing for a face that is smaller in the frame than its crop is the filtered form,
+ * "Pasting warped faces back, filtered" below.  Out of scope, and not half-built: a colour renormalised at the hull's border.
  * Refused with SDM_ERR_INVALID, no state changed, nothing launched: no mesh (none set, or sdm_set_model_geometry has changed L since);
  * fit form: no current rows, and sdm_warp_crops_tensor's rules on the rows' source sizes; everything sdm_align_paste_tensor refuses of
  * spec, in_dev, paste, dst_frames, n_frames, an NV12 frame, a row's image index or a size mismatch; _at form: points_host NULL or
@@ -1026,6 +1026,53 @@ int sdm_warp_paste_tensor_at_nv12(sdm_ctx* ctx, const float* points_host /* in, 
                                   const int* image_index /* NULL: row i -> frame i */, int n_rows, const sdm_align_tensor* spec,
                                   const void* in_dev, const sdm_align_paste* paste, const sdm_frame* dst_frames, void* const* dst_chroma,
                                   int n_frames, int* flags_host);
+
+/* Pasting warped faces back, filtered: sdm_warp_paste_tensor[_at][_nv12] with area-averaged sampling where a triangle's inverse map
+ * minifies.  The networks behind this path run at 256 or 512 pixels in template space and go back onto faces 60 to 200 pixels wide; on a
+ * turned head the far cheek's triangles take 8 or more tensor elements per frame pixel along one axis while the near cheek's take 2, so
+ * the sub-sample count is chosen per TRIANGLE and per AXIS, as "Warped faces, filtered" does on the way in.  One launch for the pixels
+ * behind the fit, the prepare stage and a small stage for the counts; the destination list may mix GRAY, BGR, RGB, BGRA, RGBA and NV12
+ * frames, dst_chroma as in the _nv12 calls.  Every rule of "Pasting warped faces back" and "Pasting warped faces back into NV12 frames"
+ * that is not restated here holds word for word.  Every float operation is rounded on its own, nothing is contracted.
+ *   1. unchanged   the points, A_t, W_t (the inverse of the float32 A_t) and the flags; the row's box and each triangle's box; the
+ *      lowest-numbered triangle whose box and edge functions hold the pixel CENTRE; the position of the centre through that one
+ *      triangle; and the FOOTPRINT, which is exactly the unfiltered one: the centre lies in the row's box, has a triangle, and its
+ *      position is accepted.  The row's box is not widened and there is no second, working footprint: the filter changes what a row
+ *      contributes to a pixel it holds, never which pixels it holds.  The ownership rule -- one reader and writer per pixel, per 2 x 2
+ *      block on NV12, rows applied in increasing row number -- is the existing one on the existing predicate.
+ *   2. (Sx, Sy) of row n, triangle t   from the float32 W_t, in float32, each operation rounded: cx2 = W00 W00 + W10 W10 (the crop step
+ *      per frame column, squared), cy2 = W01 W01 + W11 W11 (per frame row).  Sx is the rule of sdm_align_crops_tensor_filtered's S on
+ *      cx2, Sy the same rule on cy2: 1 for mode BILINEAR, for a DEGENERATE row, for a triangle that is skipped or covers nothing
+ *      (det E == 0, d == 0, an entry of W_t not finite, or a row whose box is empty), for a value that is not finite or below
+ *      min_scale * min_scale (float32); otherwise the smallest integer in [1, max_samples] with (float)(S S) >= value, and max_samples
+ *      when there is none.  samples_host[(n T + t) 2] = Sx, [(n T + t) 2 + 1] = Sy.  For a row whose points are a similarity of the
+ *      template, Sx = Sy = the S of the rigid filtered paste.
+ *   3. sub-samples of frame pixel (X, Y) whose triangle is t   for u in 0 ... Sx - 1 and v in 0 ... Sy - 1: fX = (float)X + o_Sx[u],
+ *      fY = (float)Y + o_Sy[v] with the offsets of sdm_align_crops_tensor_filtered.  All go through the pixel's own W_t, also those
+ *      whose frame position lies past the triangle's edge: (W00 fX + W01 fY) + W02, v likewise; each is quantised as in "Pasting crops
+ *      back" (the 2^20 rule, 1/32 pixel) and gives the UNROUNDED weighted sums per channel (taps clamped into the crop) and of the
+ *      opacity, where a tap reads 0 outside the crop OR ON A CROP PIXEL WITH LABEL 255, otherwise the map's byte, or 255 without a map.
+ *   4. pixel   with n = Sx Sy <= 256: q_c = (sum + 512 n) / (1024 n) per channel, a the same on the opacity sums, unsigned integer
+ *      divisions; the sums stay below 2^26 + 2^17.  Channel order, the gray weights, the / 255 blend, the NV12 luma and chroma formulas
+ *      and the block's opacity-weighted mean apply to the averaged q and a exactly as they do at n = 1.  A pixel of which any
+ *      sub-sample is refused by the 2^20 rule gets a = 0 from that row.
+ *   5. bit identity   a pixel whose triangle has Sx = Sy = 1 takes exactly the bytes of the unfiltered call; mode BILINEAR writes
+ *      exactly the bytes of sdm_warp_paste_tensor[_at] on lists without NV12 frames and of sdm_warp_paste_tensor[_at]_nv12 on lists
+ *      with them.
+ *   6. consequences   the MAP is continuous across an edge two triangles share, the sample count is not; W_t extrapolates up to half a
+ *      frame pixel past its triangle; the hull's border is now antialiased from the inside -- a border pixel's sub-samples that land
+ *      on label 255 count with opacity 0 --; a frame pixel whose centre lies outside the hull is still never touched.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched: everything the _nv12 forms of the warped paste refuse; filter NULL,
+ * an unknown mode, max_samples outside [1, 16], min_scale not finite or below 1.  samples_host (N x T x 2) may be NULL; it comes back
+ * in the same copy as the flags.  Out of scope: widening the footprint beyond pixels whose centre lies in the hull. */
+int sdm_warp_paste_tensor_filtered(sdm_ctx* ctx, const sdm_align_tensor* spec, const sdm_align_filter* filter, const void* in_dev,
+                                   const sdm_align_paste* paste, const sdm_frame* dst_frames, void* const* dst_chroma, int n_frames,
+                                   float* matrices_host /* N x T x 6, may be NULL */, int* flags_host /* may be NULL */,
+                                   int* samples_host /* N x T x 2, may be NULL */);
+int sdm_warp_paste_tensor_at_filtered(sdm_ctx* ctx, const float* points_host, const int* image_index, int n_rows,
+                                      const sdm_align_tensor* spec, const sdm_align_filter* filter, const void* in_dev,
+                                      const sdm_align_paste* paste, const sdm_frame* dst_frames, void* const* dst_chroma, int n_frames,
+                                      int* flags_host, int* samples_host);
 
 #ifdef __cplusplus
 }

@@ -45,6 +45,7 @@ EXPORTED = [
     "sdm_align_paste_tensor_filtered", "sdm_align_paste_tensor_at_filtered",
     "sdm_align_paste_tensor_nv12", "sdm_align_paste_tensor_at_nv12",
     "sdm_warp_paste_tensor_nv12", "sdm_warp_paste_tensor_at_nv12",
+    "sdm_warp_paste_tensor_filtered", "sdm_warp_paste_tensor_at_filtered",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -474,6 +475,12 @@ def lib() -> ctypes.CDLL:
                                            ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p, c_void_p],
             "sdm_warp_paste_tensor_at_nv12": [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(SdmAlignTensor), c_void_p,
                                               ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p],
+            "sdm_warp_paste_tensor_filtered": [c_void_p, ctypes.POINTER(SdmAlignTensor), ctypes.POINTER(SdmAlignFilter), c_void_p,
+                                               ctypes.POINTER(SdmAlignPaste), ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p, c_void_p,
+                                               c_void_p],
+            "sdm_warp_paste_tensor_at_filtered": [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(SdmAlignTensor),
+                                                  ctypes.POINTER(SdmAlignFilter), c_void_p, ctypes.POINTER(SdmAlignPaste),
+                                                  ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p, c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

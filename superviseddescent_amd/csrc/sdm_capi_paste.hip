@@ -4,8 +4,9 @@
 // (csrc/sdm_align_paste.hip), the filtered forms that file's area-capable pair, the NV12 forms either prepare kernel and paste_nv12_kernel
 // with the frames' UV planes as a device array of their own; the piecewise-affine forms enqueue warp_fit_kernel, their prepare kernel and their paste launch
 // (csrc/sdm_warp_paste.hip) on the mesh of sdm_warp_set_mesh, their NV12 forms warp_paste_nv12_kernel with the same array of UV
-// planes.  Nothing waits between them; the one synchronise of a call brings the matrices and flags back.  The
-// landmark state, the images, the crop source and the tracker's slots are only read; the frames' colour bytes are written in place.
+// planes, their filtered forms the counts stage and warp_paste_area_kernel (csrc/sdm_warp_paste_area.hip).  Nothing waits between
+// them; the one synchronise of a call brings the matrices and flags back.  The landmark state, the images, the crop source and the
+// tracker's slots are only read; the frames' colour bytes are written in place.
 #include "sdm_capi_internal.h"
 #include "sdm_paste.h"
 
@@ -164,42 +165,56 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
 
 // The piecewise-affine paste behind its checks.  x: N x 2L on the device (the landmark state, or the uploaded points in its layout);
 // src, img_idx: what warp_fit_kernel takes for its own record (the prepare kernel takes FOLDED from it and evaluates PARTIAL against the destination frames).
-// nv12: the calls that take NV12 destinations -- the same two kernels, then warp_paste_nv12_kernel with the UV planes (dst_chroma: the caller's, or null)
+// nv12: the calls that take NV12 destinations -- the same two kernels, then warp_paste_nv12_kernel with the UV planes (dst_chroma: the caller's, or null).
+// filter: null -- the unfiltered calls --, or the checked filter of the filtered ones (nv12 is true for them): the counts stage behind the
+// prepare kernel, then warp_paste_area_kernel (csrc/sdm_warp_paste_area.hip); the N x T x 2 counts stand directly behind the rows' records,
+// so that they come back in the flags' copy, and the packed counts behind the triangle records
 int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const int* img_idx, const std::vector<int>& frame_of_row,
                    const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames,
-                   float* matrices_host, int* flags_host, bool nv12, void* const* dst_chroma)
+                   float* matrices_host, int* flags_host, bool nv12, void* const* dst_chroma, const sdm_align_filter* filter = nullptr,
+                   int* samples_host = nullptr)
 {
     sdm_ctx::Warp& w = c->warp;
     const int N = (int)frame_of_row.size(), T = w.T;
     int rc;
     const size_t rec = (size_t)N * sizeof(WarpFace), mat = (size_t)N * T * 6 * sizeof(float);
     const size_t rows_bytes = (size_t)N * sizeof(WarpPasteRow), tris_bytes = (size_t)N * T * sizeof(WarpPasteTri);
+    const size_t samples_bytes = filter ? (size_t)N * T * 2 * sizeof(int) : 0, counts_bytes = filter ? (size_t)N * T * sizeof(uint16_t) : 0;
     PasteTables tab;
-    if ((rc = w.rows.ensure(rec + mat)) || (rc = w.paste.ensure(rows_bytes + tris_bytes)) ||
+    if ((rc = w.rows.ensure(rec + mat)) || (rc = w.paste.ensure(rows_bytes + samples_bytes + tris_bytes + counts_bytes)) ||
         (rc = paste_tables(c, frame_of_row, frames, n_frames, tab, nv12, dst_chroma)))
         return rc;
     WarpFace* faces = (WarpFace*)w.rows.p;
     float* matrices = (float*)(w.rows.p + rec);
     WarpPasteRow* rows_dev = (WarpPasteRow*)w.paste.p;
-    WarpPasteTri* tris_dev = (WarpPasteTri*)(w.paste.p + rows_bytes);
+    int* samples_dev = (int*)(w.paste.p + rows_bytes);
+    WarpPasteTri* tris_dev = (WarpPasteTri*)(w.paste.p + rows_bytes + samples_bytes);
+    uint16_t* counts_dev = (uint16_t*)(w.paste.p + rows_bytes + samples_bytes + tris_bytes);
     sdm_launch_warp_fit(x, N, w.L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, src, img_idx, faces, matrices, c->stream);
     HIP_TRY(hipGetLastError());
     sdm_launch_warp_paste_prepare(x, N, w.L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, faces, matrices, tab.of_row, tab.frames, rows_dev,
                                   tris_dev, c->stream);
     HIP_TRY(hipGetLastError());
     const PasteCropDev crop = paste_crop_dev(spec, in_dev, paste, w.out_w, w.out_h);
-    if (nv12) sdm_launch_warp_paste_nv12(tab.frames, tab.chroma, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
+    if (filter) {
+        sdm_launch_warp_paste_area_counts(rows_dev, tris_dev, N, T, align_area_dev(filter), counts_dev, samples_dev, c->stream);
+        HIP_TRY(hipGetLastError());
+        sdm_launch_warp_paste_area(tab.frames, tab.chroma, rows_dev, tris_dev, counts_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
+    } else if (nv12) sdm_launch_warp_paste_nv12(tab.frames, tab.chroma, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
     else sdm_launch_warp_paste(tab.frames, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
     HIP_TRY(hipGetLastError());
-    // the matrices and the rows' records, one synchronise
-    std::vector<WarpPasteRow> host;
+    // the matrices and the rows' records (a filtered call: with the counts behind them, in the same copy), one synchronise
+    if (!filter) samples_host = nullptr;
+    std::vector<unsigned char> host;
     if (matrices_host) HIP_TRY(hipMemcpyAsync(matrices_host, matrices, mat, hipMemcpyDeviceToHost, c->stream));
-    if (flags_host) {
-        host.resize((size_t)N);
-        HIP_TRY(hipMemcpyAsync(host.data(), rows_dev, rows_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (flags_host || samples_host) {
+        host.resize(rows_bytes + (samples_host ? samples_bytes : 0));
+        HIP_TRY(hipMemcpyAsync(host.data(), rows_dev, host.size(), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (size_t r = 0; r < host.size(); ++r) flags_host[r] = host[r].flags;
+    if (flags_host)
+        for (int r = 0; r < N; ++r) flags_host[r] = ((const WarpPasteRow*)host.data())[r].flags;
+    if (samples_host) memcpy(samples_host, host.data() + rows_bytes, samples_bytes);
     return SDM_OK;
 }
 
@@ -262,30 +277,36 @@ int warp_paste_check_mesh(sdm_ctx* c)
 
 // sdm_warp_paste_tensor and sdm_warp_paste_tensor_nv12: the same checks in the same order
 int warp_paste_fit_call(sdm_ctx* c, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames,
-                        int n_frames, float* matrices_host, int* flags_host, bool nv12, void* const* dst_chroma)
+                        int n_frames, float* matrices_host, int* flags_host, bool nv12, void* const* dst_chroma, bool filtered = false,
+                        const sdm_align_filter* filter = nullptr, int* samples_host = nullptr)
 {
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     int rc;
     if ((rc = warp_paste_check_mesh(c))) return rc;
     if (c->N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
-    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)) || (rc = align_check_rows(c))) return rc;
+    if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
+        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)) || (rc = align_check_rows(c)))
+        return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
     HIP_TRY(hipSetDevice(c->device));
     return warp_paste_run(c, c->x[c->cur].p, align_source_dev(c), c->idx_identity ? nullptr : c->img_idx.p, frame_of_row, spec, in_dev, paste,
-                          frames, n_frames, matrices_host, flags_host, nv12, dst_chroma);
+                          frames, n_frames, matrices_host, flags_host, nv12, dst_chroma, filtered ? filter : nullptr, samples_host);
 }
 
 // sdm_warp_paste_tensor_at and sdm_warp_paste_tensor_at_nv12
 int warp_paste_at_call(sdm_ctx* c, const float* points_host, const int* image_index, int n_rows, const sdm_align_tensor* spec, const void* in_dev,
-                       const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, int* flags_host, bool nv12, void* const* dst_chroma)
+                       const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, int* flags_host, bool nv12, void* const* dst_chroma,
+                       bool filtered = false, const sdm_align_filter* filter = nullptr, int* samples_host = nullptr)
 {
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     int rc;
     if ((rc = warp_paste_check_mesh(c))) return rc;
     if (!points_host) return fail(SDM_ERR_INVALID, "no points");
     if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
-    if ((rc = align_check_spec(spec)) || (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12))) return rc;
+    if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
+        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)))
+        return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;
     sdm_ctx::Warp& w = c->warp;
@@ -304,7 +325,8 @@ int warp_paste_at_call(sdm_ctx* c, const float* points_host, const int* image_in
     // warp_fit_kernel's own record wants an image per row: a stack of one 1 x 1 image (of its flags only FOLDED is read)
     AlignSourceDev src{};
     src.width = src.height = src.stride = 1;
-    return warp_paste_run(c, w.points.p, src, nullptr, frame_of_row, spec, in_dev, paste, frames, n_frames, nullptr, flags_host, nv12, dst_chroma);
+    return warp_paste_run(c, w.points.p, src, nullptr, frame_of_row, spec, in_dev, paste, frames, n_frames, nullptr, flags_host, nv12, dst_chroma,
+                          filtered ? filter : nullptr, samples_host);
 }
 
 }  // namespace
@@ -335,6 +357,22 @@ int sdm_warp_paste_tensor_at_nv12(sdm_ctx* c, const float* points_host, const in
                                   int n_frames, int* flags_host)
 {
     return warp_paste_at_call(c, points_host, image_index, n_rows, spec, in_dev, paste, frames, n_frames, flags_host, true, dst_chroma);
+}
+
+// the filtered calls: a list that may mix NV12 and the per-pixel formats
+int sdm_warp_paste_tensor_filtered(sdm_ctx* c, const sdm_align_tensor* spec, const sdm_align_filter* filter, const void* in_dev,
+                                   const sdm_align_paste* paste, const sdm_frame* frames, void* const* dst_chroma, int n_frames,
+                                   float* matrices_host, int* flags_host, int* samples_host)
+{
+    return warp_paste_fit_call(c, spec, in_dev, paste, frames, n_frames, matrices_host, flags_host, true, dst_chroma, true, filter, samples_host);
+}
+
+int sdm_warp_paste_tensor_at_filtered(sdm_ctx* c, const float* points_host, const int* image_index, int n_rows, const sdm_align_tensor* spec,
+                                      const sdm_align_filter* filter, const void* in_dev, const sdm_align_paste* paste,
+                                      const sdm_frame* frames, void* const* dst_chroma, int n_frames, int* flags_host, int* samples_host)
+{
+    return warp_paste_at_call(c, points_host, image_index, n_rows, spec, in_dev, paste, frames, n_frames, flags_host, true, dst_chroma, true, filter,
+                              samples_host);
 }
 
 int sdm_align_paste_tensor(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, int ch, const sdm_align_tensor* spec,

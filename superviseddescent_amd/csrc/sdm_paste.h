@@ -1,5 +1,5 @@
 // sdm_paste.h -- what the two paste kernels (csrc/sdm_align_paste.hip, csrc/sdm_warp_paste.hip) and their C-ABI (csrc/sdm_capi_paste.hip)
-// share: the device headers' records, the eight launches, and a paste kernel's tile walk -- grid (row, paste_groups workgroups); the
+// share: the device headers' records, the launches, and a paste kernel's tile walk -- grid (row, paste_groups workgroups); the
 // workgroups of a row stride over the 64 x 4 pixel tiles of its box, a wave covers 64 pixels of one frame row: the box never reaches the host.
 #pragma once
 #include "sdm_warp.h"
@@ -51,3 +51,11 @@ void sdm_launch_warp_paste(const PasteFrameDev* frames, const WarpPasteRow* rows
 // the piecewise-affine calls with NV12 destinations, behind the same prepare stage.  chroma: as for sdm_launch_paste_nv12
 void sdm_launch_warp_paste_nv12(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris, int T,
                                 const int* list, const int* entry_of_row, int N, const uint8_t* labels, const PasteCropDev& crop, hipStream_t s);
+// the filtered piecewise-affine calls (csrc/sdm_warp_paste_area.hip), behind sdm_launch_warp_paste_prepare.  counts: N x T packed (Sx, Sy)
+// out (csrc/sdm_warp_paste_area_device.h); samples: N x T x 2 ints out, for the host
+void sdm_launch_warp_paste_area_counts(const WarpPasteRow* rows, const WarpPasteTri* tris, int N, int T, const AlignAreaDev& area,
+                                       uint16_t* counts, int* samples, hipStream_t s);
+// one launch for a list that may mix NV12 and the per-pixel formats.  chroma: as for sdm_launch_paste_nv12
+void sdm_launch_warp_paste_area(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris,
+                                const uint16_t* counts, int T, const int* list, const int* entry_of_row, int N, const uint8_t* labels,
+                                const PasteCropDev& crop, hipStream_t s);

@@ -981,18 +981,35 @@ class Context:
             raise ValueError(f"the tensor's crop is {width} x {height}, the mesh's {w} x {h}")
         return T
 
-    def warp_paste_tensor(self, y, frames, formats=None, layout="nchw", mask=None, spec=None, chroma=None, **options):
+    def _warp_paste_chroma(self, chroma, arr, keep):
+        """the filtered calls take a mixed list: their UV planes, all None (behind the Y plane, read for NV12 frames only) by default"""
+        return self._paste_chroma(chroma, arr, keep) or (None, keep)
+
+    def warp_paste_tensor(self, y, frames, formats=None, layout="nchw", mask=None, spec=None, chroma=None, filter=None, max_samples=16,
+                          min_scale=1.0, **options):
         """The inverse of ``warp_crops_tensor`` for the N current rows (include/sdm.h, sdm_warp_paste_tensor): ``y`` -- a network's output
         in template space, a device tensor of the mesh's crop size -- is warped back under every row's own shape, triangle by triangle,
         and blended into ``frames`` IN PLACE.  ``frames``, ``formats``, ``layout``, ``mask``, ``spec`` / ``options``: as for
         ``align_paste_tensor``.  Returns (matrices N x T x 2 x 3 float32 crop -> frame, as ``warp_crops_tensor`` returns them, flags N
         int32: SDM_WARP_* bits).  With an "nv12" destination among ``frames``, or ``chroma`` given (as for ``align_paste_tensor``), the
-        call is sdm_warp_paste_tensor_nv12: luma and 4:2:0 chroma blended in place; the return values are the same."""
+        call is sdm_warp_paste_tensor_nv12: luma and 4:2:0 chroma blended in place; the return values are the same.  ``filter``: None
+        (plain bilinear), or "area" / "bilinear" with ``max_samples`` and ``min_scale`` (``_lib.align_filter``) or an ``SdmAlignFilter``
+        for sdm_warp_paste_tensor_filtered -- a frame pixel whose triangle's inverse map minifies averages Sx x Sy sub-samples, the
+        destinations may mix NV12 and the other formats -- which returns (matrices, flags, samples N x T x 2 int32: (Sx, Sy) of every
+        triangle)."""
+        filter = self._paste_filter(filter, max_samples, min_scale)
         spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
         T = self._warp_paste_size(width, height)
         self._paste_rows(n)
         mats = np.empty((n, T, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
+        if filter is not None:
+            uv, keep = self._warp_paste_chroma(chroma, arr, keep)
+            samples = np.empty((n, T, 2), np.int32)
+            check(self._lib.sdm_warp_paste_tensor_filtered(self._h, ctypes.byref(spec), ctypes.byref(filter), ctypes.c_void_p(y.data_ptr()),
+                                                           ctypes.byref(paste), arr, uv, len(arr), mats.ctypes.data, flags.ctypes.data,
+                                                           samples.ctypes.data))
+            return mats, flags, samples
         nv12 = self._paste_chroma(chroma, arr, keep)
         if nv12 is not None:
             check(self._lib.sdm_warp_paste_tensor_nv12(self._h, ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr,
@@ -1003,18 +1020,27 @@ class Context:
         return mats, flags
 
     def warp_paste_tensor_at(self, points, y, frames, formats=None, image_index=None, layout="nchw", mask=None, spec=None, chroma=None,
-                             **options):
+                             filter=None, max_samples=16, min_scale=1.0, **options):
         """``warp_paste_tensor`` with explicit landmarks (sdm_warp_paste_tensor_at): ``points`` N x K x 2 float32, (x, y) of the mesh's
         k-th landmark in its row's frame -- the tracker may have stepped on since; the mesh is needed, but no landmark state and no
         context image.  ``image_index``: the frame of every row (None: row i -> frame i).  Returns flags N int32: SDM_WARP_* bits.
-        "nv12" destinations and ``chroma``: as for ``warp_paste_tensor`` (sdm_warp_paste_tensor_at_nv12)."""
+        "nv12" destinations and ``chroma``: as for ``warp_paste_tensor`` (sdm_warp_paste_tensor_at_nv12).  With a ``filter`` (as for
+        ``warp_paste_tensor``: sdm_warp_paste_tensor_at_filtered) it returns (flags, samples N x T x 2 int32)."""
+        filter = self._paste_filter(filter, max_samples, min_scale)
         spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
-        self._warp_paste_size(width, height)
+        T = self._warp_paste_size(width, height)
         p = np.ascontiguousarray(points, np.float32)
         if p.ndim != 3 or p.shape[0] != n or p.shape[2] != 2:
             raise ValueError(f"points must be N x K x 2 with one row per row of the tensor ({n}), not {p.shape}")
         idx = self._paste_image_index(image_index, n)
         flags = np.empty(n, np.int32)
+        if filter is not None:
+            uv, keep = self._warp_paste_chroma(chroma, arr, keep)
+            samples = np.empty((n, T, 2), np.int32)
+            check(self._lib.sdm_warp_paste_tensor_at_filtered(self._h, p.ctypes.data, None if idx is None else idx.ctypes.data, n,
+                                                              ctypes.byref(spec), ctypes.byref(filter), ctypes.c_void_p(y.data_ptr()),
+                                                              ctypes.byref(paste), arr, uv, len(arr), flags.ctypes.data, samples.ctypes.data))
+            return flags, samples
         nv12 = self._paste_chroma(chroma, arr, keep)
         if nv12 is not None:
             check(self._lib.sdm_warp_paste_tensor_at_nv12(self._h, p.ctypes.data, None if idx is None else idx.ctypes.data, n, ctypes.byref(spec),
@@ -1885,7 +1911,7 @@ class detection_model:
     def paste_warped_tensor(self, y, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
                             triangles: Optional[np.ndarray] = None, margin: float = 0.1, frames=None, formats=None, layout="nchw",
                             order="rgb", scale=None, bias=None, mean=None, std=None, gray_shift=14, mask=None, points=None,
-                            image_index=None, chroma=None):
+                            image_index=None, chroma=None, filter=None, max_samples=16, min_scale=1.0):
         """The way back of :meth:`warped_crops_tensor`: ``y = net(x)`` on the warped faces -- a texture in template space, a device tensor
         whose dtype, channels and crop size are read from it -- is warped back under every face's own shape and blended into ``frames``
         in place (include/sdm.h, "Pasting warped faces back").  ``landmark_ids``, ``template``, ``triangles``, ``margin``, ``order``,
@@ -1895,7 +1921,11 @@ class detection_model:
         an earlier moment) with ``image_index`` (None: row i -> frame i) pastes rows that are no longer current; otherwise the current
         rows are fitted again.  Returns (matrices N x T x 2 x 3 crop -> frame or None with ``points``, flags N: SDM_WARP_* bits).  No
         pointer to the frames stays behind.  An "nv12" frame, with ``chroma`` as for :meth:`paste_crops_tensor`, has its luma and 4:2:0
-        chroma blended in place (include/sdm.h, "Pasting warped faces back into NV12 frames")."""
+        chroma blended in place (include/sdm.h, "Pasting warped faces back into NV12 frames").  ``filter``: None (plain bilinear) |
+        "area" | "bilinear" | an ``SdmAlignFilter``, with ``max_samples`` and ``min_scale`` as in :func:`align_filter`: where a
+        triangle of the face is smaller in the frame than in the crop, every frame pixel averages Sx x Sy sub-samples of the crop,
+        chosen per triangle and per axis (include/sdm.h, "Pasting warped faces back, filtered"), and the call returns (matrices or
+        None, flags, samples N x T x 2)."""
         c = self.optimised_model.ctx
         if frames is None:
             raise ValueError("give the frames to paste into")
@@ -1913,8 +1943,11 @@ class detection_model:
         options = dict(order=order, scale=scale, bias=bias, mean=mean, std=std, gray_shift=gray_shift)
         if chroma is not None:
             options["chroma"] = chroma
+        if filter is not None:
+            options.update(filter=filter, max_samples=max_samples, min_scale=min_scale)
         if points is not None:
-            return None, c.warp_paste_tensor_at(points, y, frames, formats, image_index, layout, mask, **options)
+            got = c.warp_paste_tensor_at(points, y, frames, formats, image_index, layout, mask, **options)
+            return (None, got) if filter is None else (None,) + tuple(got)
         return c.warp_paste_tensor(y, frames, formats, layout, mask, **options)
 
     def warp_points(self) -> np.ndarray:

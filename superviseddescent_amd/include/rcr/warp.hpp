@@ -19,6 +19,8 @@
 //
 //     auto p = rcr::paste_warped_tensor(tr, mesh, paste_spec, net_out_dev, device_frames);       // p.flags[i]: SDM_WARP_*
 //     auto q = rcr::paste_warped_tensor(tr, mesh, paste_spec, net_out_dev, nv12_frames, std::vector<void*>());   // NV12, UV behind Y
+//     std::vector<int> samples;                                                                  // rows x T x 2: (Sx, Sy) of every triangle
+//     auto a = rcr::paste_warped_tensor(tr, mesh, paste_spec, rcr::AlignFilter(), net_out_dev, frames, {}, rcr::PasteMask{}, &samples);
 #pragma once
 
 #ifndef RCR_WARP_HPP_
@@ -195,10 +197,12 @@ inline void warp_paste_set_mesh(sdm_ctx* c, const WarpMesh& mesh)
 
 // the n current rows of the handle `c`: the fit of warped_crops_tensor, then the tensor at `in_dev` pasted into `frames` in place;
 // `chroma`: nullptr, or -- the overloads for NV12 destinations, sdm_warp_paste_tensor_nv12 -- the frames' UV planes (empty: every one
-// directly behind its Y plane)
+// directly behind its Y plane); `filter`: nullptr, or -- the overloads taking an AlignFilter, sdm_warp_paste_tensor_filtered -- the
+// sampling, with `samples` (may be nullptr) taking rows x T x 2 counts
 inline warp_paste_result warp_paste_current_rows(sdm_ctx* c, int n, const WarpMesh& mesh, const TensorSpec& spec, const void* in_dev,
                                                  const std::vector<DeviceFrame>& frames, const PasteMask& mask,
-                                                 const std::vector<void*>* chroma = nullptr)
+                                                 const std::vector<void*>* chroma = nullptr, const AlignFilter* filter = nullptr,
+                                                 std::vector<int>* samples = nullptr)
 {
     warp_paste_set_mesh(c, mesh);
     const std::vector<sdm_frame> f = paste_frames(frames);
@@ -207,6 +211,16 @@ inline warp_paste_result warp_paste_current_rows(sdm_ctx* c, int n, const WarpMe
     warp_paste_result res;
     res.matrices = cv::Mat(n, 6 * mesh.n_triangles(), CV_32FC1);
     res.flags.resize((size_t)n);
+    if (filter) {
+        const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
+        if (samples) samples->assign((size_t)n * mesh.n_triangles() * 2, 0);
+        superviseddescent::hip::check(sdm_warp_paste_tensor_filtered(c, &s, &fl, in_dev, &p, f.empty() ? nullptr : f.data(),
+                                                                     chroma ? paste_chroma(*chroma, f.size()) : nullptr, (int)f.size(),
+                                                                     res.matrices.ptr<float>(0), res.flags.data(),
+                                                                     samples ? samples->data() : nullptr),
+                                      "sdm_warp_paste_tensor_filtered");
+        return res;
+    }
     if (chroma) {
         superviseddescent::hip::check(sdm_warp_paste_tensor_nv12(c, &s, in_dev, &p, f.empty() ? nullptr : f.data(), paste_chroma(*chroma, f.size()),
                                                                  (int)f.size(), res.matrices.ptr<float>(0), res.flags.data()),
@@ -221,7 +235,8 @@ inline warp_paste_result warp_paste_current_rows(sdm_ctx* c, int n, const WarpMe
 // landmark rows on device frames: a handle of its own, the frames as its image set, the rows uploaded.  chroma: as above
 inline warp_paste_result warp_paste_rows(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
                                          const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec, const void* in_dev,
-                                         const PasteMask& mask, const std::vector<void*>* chroma)
+                                         const PasteMask& mask, const std::vector<void*>* chroma, const AlignFilter* filter = nullptr,
+                                         std::vector<int>* samples = nullptr)
 {
     using superviseddescent::hip::check;
     superviseddescent::hip::Handle h(superviseddescent::hip::device());
@@ -233,13 +248,14 @@ inline warp_paste_result warp_paste_rows(detection_model& model, const std::vect
     if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
     else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
     check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
-    return detail::warp_paste_current_rows(c, x.rows, mesh, spec, in_dev, frames, mask, chroma);
+    return detail::warp_paste_current_rows(c, x.rows, mesh, spec, in_dev, frames, mask, chroma, filter, samples);
 }
 
 // explicit points: sdm_warp_paste_tensor_at, or with chroma sdm_warp_paste_tensor_at_nv12
 inline warp_paste_result warp_paste_points(detection_model& model, cv::Mat points, const std::vector<int>& image_index, const WarpMesh& mesh,
                                            const TensorSpec& spec, const void* in_dev, const std::vector<DeviceFrame>& frames,
-                                           const PasteMask& mask, const std::vector<void*>* chroma)
+                                           const PasteMask& mask, const std::vector<void*>* chroma, const AlignFilter* filter = nullptr,
+                                           std::vector<int>* samples = nullptr)
 {
     using superviseddescent::hip::check;
     if (points.type() != CV_32FC1 || points.cols != 2 * (int)mesh.landmark_index.size() || points.rows < 1)
@@ -255,7 +271,14 @@ inline warp_paste_result warp_paste_points(detection_model& model, cv::Mat point
     warp_paste_result res;
     res.flags.resize((size_t)points.rows);
     const int* index = image_index.empty() ? nullptr : image_index.data();
-    if (chroma)
+    if (filter) {
+        const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
+        if (samples) samples->assign((size_t)points.rows * mesh.n_triangles() * 2, 0);
+        check(sdm_warp_paste_tensor_at_filtered(h.get(), pts.ptr<float>(0), index, points.rows, &s, &fl, in_dev, &p, f.empty() ? nullptr : f.data(),
+                                                chroma ? detail::paste_chroma(*chroma, f.size()) : nullptr, (int)f.size(), res.flags.data(),
+                                                samples ? samples->data() : nullptr),
+              "sdm_warp_paste_tensor_at_filtered");
+    } else if (chroma)
         check(sdm_warp_paste_tensor_at_nv12(h.get(), pts.ptr<float>(0), index, points.rows, &s, in_dev, &p, f.empty() ? nullptr : f.data(),
                                             detail::paste_chroma(*chroma, f.size()), (int)f.size(), res.flags.data()),
               "sdm_warp_paste_tensor_at_nv12");
@@ -322,6 +345,34 @@ inline warp_paste_result paste_warped_tensor(detection_model& model, cv::Mat poi
                                              const std::vector<void*>& chroma, const PasteMask& mask = {})
 {
     return detail::warp_paste_points(model, points, image_index, mesh, spec, in_dev, frames, mask, &chroma);
+}
+
+/** The three forms with area-averaged sampling (include/sdm.h, "Pasting warped faces back, filtered"; rcr::AlignFilter of
+ *  rcr/alignment.hpp): a frame pixel whose triangle is smaller in the frame than in the crop averages Sx x Sy sub-samples, chosen per
+ *  triangle and per axis.  The destinations may mix NV12 and the other formats; `chroma` as above (empty: every UV plane behind its Y
+ *  plane).  `samples`, when given, takes rows x T x 2 ints: (Sx, Sy) of every triangle. */
+inline warp_paste_result paste_warped_tensor(tracker& tr, const WarpMesh& mesh, const TensorSpec& spec, const AlignFilter& filter, const void* in_dev,
+                                             const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma = {},
+                                             const PasteMask& mask = {}, std::vector<int>* samples = nullptr)
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("paste_warped_tensor: step the tracker first");
+    return detail::warp_paste_current_rows(tr.context(), tr.rows().rows, mesh, spec, in_dev, frames, mask, &chroma, &filter, samples);
+}
+
+inline warp_paste_result paste_warped_tensor(detection_model& model, const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma,
+                                             cv::Mat rows, const std::vector<int>& image_index, const WarpMesh& mesh, const TensorSpec& spec,
+                                             const AlignFilter& filter, const void* in_dev, const PasteMask& mask = {},
+                                             std::vector<int>* samples = nullptr)
+{
+    return detail::warp_paste_rows(model, frames, rows, image_index, mesh, spec, in_dev, mask, &chroma, &filter, samples);
+}
+
+inline warp_paste_result paste_warped_tensor(detection_model& model, cv::Mat points, const std::vector<int>& image_index, const WarpMesh& mesh,
+                                             const TensorSpec& spec, const AlignFilter& filter, const void* in_dev,
+                                             const std::vector<DeviceFrame>& frames, const std::vector<void*>& chroma = {},
+                                             const PasteMask& mask = {}, std::vector<int>* samples = nullptr)
+{
+    return detail::warp_paste_points(model, points, image_index, mesh, spec, in_dev, frames, mask, &chroma, &filter, samples);
 }
 
 }  // namespace rcr
