@@ -1,4 +1,4 @@
-"""Time of the filtered paste (detection_model.paste_crops_tensor(filter="area"), csrc/sdm_align_paste.hip: paste_area_kernel) beside the
+"""Time of the filtered paste (detection_model.paste_crops_tensor(filter="area"), csrc/sdm_align_paste.hip: paste_kernel_t<false, true>) beside the
 unfiltered paste of the same rows in the same session, where the crop outsizes the face: 256 rows of C x C float16 NCHW RGB with
 mean / std and a feathered opacity map, C = 256 and 512, BGR frames of 1920 x 1080 resident on the device and written in place, the crop
 64 to 200 frame pixels wide (crop -> frame scale 64 / C ... 200 / C, +-20 degrees, wholly inside the frame: S spans 2 to 8), with

@@ -1,6 +1,6 @@
-"""Time of the paste into NV12 frames (Context.align_paste_tensor_at on "nv12" destinations, csrc/sdm_align_paste.hip: paste_nv12_kernel)
+"""Time of the paste into NV12 frames (Context.align_paste_tensor_at on "nv12" destinations, csrc/sdm_align_paste.hip: paste_kernel_t<true, AREA>)
 beside the paste of the same rows into BGR frames of the same size through the existing calls (sdm_align_paste_tensor_at and
-sdm_align_paste_tensor_at_filtered: paste_kernel and paste_area_kernel, the yardstick) in the same session.  Rows of C x C float16 NCHW
+sdm_align_paste_tensor_at_filtered: paste_kernel_t<false, AREA>, the yardstick) in the same session.  Rows of C x C float16 NCHW
 RGB with mean / std and a feathered opacity map, frames of 1920 x 1080 resident on the device and written in place, +-20 degrees, wholly
 inside the frame:
   bilinear   C = 112, the crop 100 to 600 frame pixels wide (the configuration of scripts/align_paste_timing.py)

@@ -1,5 +1,5 @@
-"""Time of the filtered piecewise-affine paste (Context.warp_paste_tensor(filter=...), csrc/sdm_warp_paste_area.hip:
-warp_paste_area_kernel behind the counts stage) beside the unfiltered call on the same frames and rows, in the same process: DESIGN
+"""Time of the filtered piecewise-affine paste (Context.warp_paste_tensor(filter=...), csrc/sdm_warp_paste.hip:
+warp_paste_kernel_t<true, true> behind the counts stage) beside the unfiltered call on the same frames and rows, in the same process: DESIGN
 4.18's shapes -- 256 rows of 256 x 256 float16 NCHW RGB with mean / std, the RCR-22 Delaunay mesh, frames of 1920 x 1080 resident on the
 device and written in place, one face per frame or 16 faces per frame (the faces overlap where they fall on each other), the face's crop
 60, 120 or 250 frame pixels wide (+-20 degrees, wholly inside the frame): a 256-pixel network's output going back onto a small, a medium

@@ -1,5 +1,5 @@
 """Time of the piecewise-affine paste into NV12 frames (Context.warp_paste_tensor on "nv12" destinations, csrc/sdm_warp_paste.hip:
-warp_paste_nv12_kernel) beside the unchanged warp_paste_kernel on BGR frames of the same size and rows, in the same process: the faces
+warp_paste_kernel_t<true, false>) beside the unchanged warp_paste_kernel_t<false, false> on BGR frames of the same size and rows, in the same process: the faces
 and settings of scripts/warp_paste_timing.py -- 256 and 4 096 rows of 112 x 112 float16 NCHW RGB with mean / std, the RCR-22 Delaunay
 mesh, frames of 1920 x 1080 resident on the device and written in place, the face's crop 100 to 600 frame pixels wide (+-20 degrees,
 wholly inside the frame), one face per frame or 16 faces per frame (the faces overlap where they fall on each other).  The BGR frames are

@@ -1,10 +1,10 @@
 // sdm_capi_paste.hip -- C-ABI of the paste-back of crop tensors into frames (include/sdm.h, "Pasting crops back" and "Pasting warped
 // faces back"): the entry points check every argument before anything is launched or changed, build the frame table and the rows-of-frame lists on the host from the
 // image index they already hold, and enqueue -- fit form -- sdm_align_crops' fit, then the prepare kernel and the one paste launch
-// (csrc/sdm_align_paste.hip), the filtered forms that file's area-capable pair, the NV12 forms either prepare kernel and paste_nv12_kernel
+// (csrc/sdm_align_paste.hip: paste_kernel_t<NV12, AREA>), the filtered forms behind that file's filtered prepare kernel, the NV12 forms
 // with the frames' UV planes as a device array of their own; the piecewise-affine forms enqueue warp_fit_kernel, their prepare kernel and their paste launch
-// (csrc/sdm_warp_paste.hip) on the mesh of sdm_warp_set_mesh, their NV12 forms warp_paste_nv12_kernel with the same array of UV
-// planes, their filtered forms the counts stage and warp_paste_area_kernel (csrc/sdm_warp_paste_area.hip).  Nothing waits between
+// (csrc/sdm_warp_paste.hip: warp_paste_kernel_t<NV12, AREA>) on the mesh of sdm_warp_set_mesh, their NV12 forms with the same array of UV
+// planes, their filtered forms the counts stage ahead of it.  Nothing waits between
 // them; the one synchronise of a call brings the matrices and flags back.  The landmark state, the images, the crop source and the
 // tracker's slots are only read; the frames' colour bytes are written in place.
 #include "sdm_capi_internal.h"
@@ -126,8 +126,8 @@ PasteCropDev paste_crop_dev(const sdm_align_tensor* spec, const void* in_dev, co
 
 // behind the checks: `faces` holds N records with M (fitted: and the fit's flags).  frame_of_row: N checked indices.  filter: null --
 // the unfiltered calls --, or the checked filter of the filtered ones: their prepare stage and their kernel, S behind the records.
-// nv12: the calls that take NV12 destinations -- the same prepare stages, then paste_nv12_kernel with the UV planes (dst_chroma: the
-// caller's, or null); without a filter their S is 1 for every row
+// nv12: the calls that take NV12 destinations -- the same prepare stages, then paste_kernel_t<true, ...> with the UV planes (dst_chroma:
+// the caller's, or null); without a filter their S is 1 for every row
 int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int cw, int ch, const sdm_align_tensor* spec, const void* in_dev,
               const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, float* matrices_host, int* flags_host,
               const sdm_align_filter* filter, int* samples_host, bool nv12 = false, void* const* dst_chroma = nullptr)
@@ -142,19 +142,14 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
         return rc;
     PasteRow* rows_dev = (PasteRow*)a.paste_rows.p;
     const PasteCropDev crop = paste_crop_dev(spec, in_dev, paste, cw, ch);
-    if (!filter) {
+    PasteAreaRow* area_dev = filter ? (PasteAreaRow*)(a.paste_rows.p + rows_bytes) : nullptr;
+    if (!filter)
         sdm_launch_paste_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, rows_dev, c->stream);
-        HIP_TRY(hipGetLastError());
-        if (nv12) sdm_launch_paste_nv12(tab.frames, tab.chroma, rows_dev, nullptr, tab.list, tab.entry, N, crop, c->stream);
-        else sdm_launch_paste(tab.frames, rows_dev, tab.list, tab.entry, N, crop, c->stream);
-    } else {
-        PasteAreaRow* area_dev = (PasteAreaRow*)(a.paste_rows.p + rows_bytes);
+    else
         sdm_launch_paste_area_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, align_area_dev(filter), rows_dev, area_dev,
                                       (int*)(a.faces.p + N), c->stream);
-        HIP_TRY(hipGetLastError());
-        if (nv12) sdm_launch_paste_nv12(tab.frames, tab.chroma, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);
-        else sdm_launch_paste_area(tab.frames, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);
-    }
+    HIP_TRY(hipGetLastError());
+    sdm_launch_paste(tab.frames, tab.chroma, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);   // (tab.chroma: null unless nv12)
     HIP_TRY(hipGetLastError());
     if (samples_host && !filter) {                                                      // (an NV12 call without a filter: plain bilinear)
         for (int r = 0; r < N; ++r) samples_host[r] = 1;
@@ -165,9 +160,9 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
 
 // The piecewise-affine paste behind its checks.  x: N x 2L on the device (the landmark state, or the uploaded points in its layout);
 // src, img_idx: what warp_fit_kernel takes for its own record (the prepare kernel takes FOLDED from it and evaluates PARTIAL against the destination frames).
-// nv12: the calls that take NV12 destinations -- the same two kernels, then warp_paste_nv12_kernel with the UV planes (dst_chroma: the caller's, or null).
+// nv12: the calls that take NV12 destinations -- the same two kernels, then warp_paste_kernel_t<true, false> with the UV planes (dst_chroma: the caller's, or null).
 // filter: null -- the unfiltered calls --, or the checked filter of the filtered ones (nv12 is true for them): the counts stage behind the
-// prepare kernel, then warp_paste_area_kernel (csrc/sdm_warp_paste_area.hip); the N x T x 2 counts stand directly behind the rows' records,
+// prepare kernel, then warp_paste_kernel_t<true, true>; the N x T x 2 counts stand directly behind the rows' records,
 // so that they come back in the flags' copy, and the packed counts behind the triangle records
 int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const int* img_idx, const std::vector<int>& frame_of_row,
                    const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames,
@@ -189,7 +184,7 @@ int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const 
     WarpPasteRow* rows_dev = (WarpPasteRow*)w.paste.p;
     int* samples_dev = (int*)(w.paste.p + rows_bytes);
     WarpPasteTri* tris_dev = (WarpPasteTri*)(w.paste.p + rows_bytes + samples_bytes);
-    uint16_t* counts_dev = (uint16_t*)(w.paste.p + rows_bytes + samples_bytes + tris_bytes);
+    uint16_t* counts_dev = filter ? (uint16_t*)(w.paste.p + rows_bytes + samples_bytes + tris_bytes) : nullptr;
     sdm_launch_warp_fit(x, N, w.L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, src, img_idx, faces, matrices, c->stream);
     HIP_TRY(hipGetLastError());
     sdm_launch_warp_paste_prepare(x, N, w.L, w.lm.p, w.K, (const WarpTri*)w.tri.p, T, faces, matrices, tab.of_row, tab.frames, rows_dev,
@@ -199,9 +194,8 @@ int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const 
     if (filter) {
         sdm_launch_warp_paste_area_counts(rows_dev, tris_dev, N, T, align_area_dev(filter), counts_dev, samples_dev, c->stream);
         HIP_TRY(hipGetLastError());
-        sdm_launch_warp_paste_area(tab.frames, tab.chroma, rows_dev, tris_dev, counts_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
-    } else if (nv12) sdm_launch_warp_paste_nv12(tab.frames, tab.chroma, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
-    else sdm_launch_warp_paste(tab.frames, rows_dev, tris_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);
+    }
+    sdm_launch_warp_paste(tab.frames, tab.chroma, rows_dev, tris_dev, counts_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);   // (tab.chroma: null unless nv12)
     HIP_TRY(hipGetLastError());
     // the matrices and the rows' records (a filtered call: with the counts behind them, in the same copy), one synchronise
     if (!filter) samples_host = nullptr;

@@ -5,7 +5,7 @@
 // rule: PasteMeshArea, and PasteMeshAreaOwn for an owner whose records and counts are staged and whose triangle search is already done.
 // The footprint is the unfiltered one (warp_paste_footprint's predicate); the offsets and the exact average are
 // csrc/sdm_align_area_device.h's, the blend and the ownership rule csrc/sdm_paste_device.h's.  Plain C++ behind ALIGN_HD: the device code
-// of csrc/sdm_warp_paste_area.hip and, compiled for the host, tests/cpp/warp_paste_area_host.cpp.  No float contraction.
+// of csrc/sdm_warp_paste.hip and, compiled for the host, tests/cpp/warp_paste_area_host.cpp.  No float contraction.
 #pragma once
 #include "sdm_warp_paste_device.h"
 #include "sdm_warp_area_device.h"

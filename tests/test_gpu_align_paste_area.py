@@ -1,4 +1,4 @@
-"""The filtered paste on the device (csrc/sdm_align_paste.hip: paste_area_kernel; include/sdm.h "Pasting crops back, filtered";
+"""The filtered paste on the device (csrc/sdm_align_paste.hip: paste_kernel_t<false, true>; include/sdm.h "Pasting crops back, filtered";
 detection_model.paste_crops_tensor(filter="area")).  Every comparison is bit for bit against the host restatement
 (tests/paste_area_ref.py) and on the WHOLE destination buffer: the frames, their pitch padding and the 16 guard bytes around each
 (tests/paste_cases.py)."""

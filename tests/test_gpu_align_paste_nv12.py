@@ -1,4 +1,4 @@
-"""Crop tensors pasted back into NV12 frames on the device (csrc/sdm_align_paste.hip: paste_nv12_kernel; include/sdm.h "Pasting crops
+"""Crop tensors pasted back into NV12 frames on the device (csrc/sdm_align_paste.hip: paste_kernel_t<true, AREA>; include/sdm.h "Pasting crops
 back into NV12 frames"; detection_model.paste_crops_tensor on "nv12" frames).  Every comparison is bit for bit against the host
 restatement (tests/paste_nv12_ref.py) and on the WHOLE destination buffer: both planes of every frame, their pitch padding and the 16
 guard bytes around each plane (tests/paste_nv12_cases.py)."""

@@ -1,4 +1,4 @@
-"""The filtered piecewise-affine paste on the device (csrc/sdm_warp_paste_area.hip: warp_paste_area_kernel; include/sdm.h "Pasting warped
+"""The filtered piecewise-affine paste on the device (csrc/sdm_warp_paste.hip: warp_paste_kernel_t<true, true>; include/sdm.h "Pasting warped
 faces back, filtered"; Context.warp_paste_tensor[_at](filter=...), detection_model.paste_warped_tensor(filter=...)).  Every comparison is
 bit for bit against the host restatement (tests/warp_paste_area_ref.py) and on the WHOLE destination buffer: every frame and plane, their
 pitch padding and the 16 guard bytes around each (tests/warp_paste_area_cases.py); the geometry case on a window around every row inside

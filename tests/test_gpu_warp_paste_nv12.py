@@ -1,4 +1,4 @@
-"""Warped face tensors pasted back into NV12 frames on the device (csrc/sdm_warp_paste.hip: warp_paste_nv12_kernel; include/sdm.h
+"""Warped face tensors pasted back into NV12 frames on the device (csrc/sdm_warp_paste.hip: warp_paste_kernel_t<true, false>; include/sdm.h
 "Pasting warped faces back into NV12 frames"; detection_model.paste_warped_tensor on "nv12" frames).  Every comparison is bit for bit
 against the host restatement (tests/warp_paste_nv12_ref.py) and on the WHOLE destination buffer: both planes of every frame, their
 pitch padding and the 16 guard bytes around each plane (tests/warp_paste_nv12_cases.py); the two geometry cases on a window around
