@@ -560,6 +560,54 @@ int sdm_track_configure_upright(sdm_ctx* ctx, int enable);
 /* sdm_track_start with a roll per stream (degrees; the rule of sdm_detect_batch_upright).  Needs upright mode. */
 int sdm_track_start_rolled(sdm_ctx* ctx, const int* ids, const int* boxes, const float* roll_deg, int n);
 
+/* Tracking, filtered: a temporal filter on the tracker's output.  A regression cascade's answer jitters by a fraction of a pixel from
+ * frame to frame, on a face that does not move too; crops, warps and pastes fitted to the rows carry that jitter on.  The filter is
+ * the One-Euro filter (Casiez, Roussel, Vogel 2012): a first-order low-pass whose cut-off rises with the filtered speed -- steady
+ * when the face is still, no lag when the head moves --, the speed measured in units of the face's own size, so that one parameter
+ * set serves a 60-pixel and a 600-pixel face.  It filters what a step RETURNS, in one launch behind the commit: the slots' landmark
+ * rows stay raw, so the next step's initialisation, the lost rule and sdm_track_get are bit-identical to a tracker without it.
+ * After sdm_track_step_filtered the current rows x are the FILTERED rows in ids order: sdm_get_x, sdm_align_crops*, sdm_warp_*,
+ * the pastes without _at and sdm_pose_templates_from_landmarks work on them.  sdm_upright_get's matrices and flags are those of
+ * the raw step.
+ *   parameters   min_cutoff > 0 (Hz), beta >= 0 (Hz per face size per second), d_cutoff > 0 (Hz)
+ *   state        per slot three rows of 2L floats -- r the previous raw row, d the filtered derivative, f the previous filtered row --
+ *                and one int, primed.  sdm_track_configure_filter allocates it, all slots un-primed; sdm_track_start and
+ *                sdm_track_start_rolled un-prime the slots they name.
+ *   arithmetic   float32, every operation rounded as written, nothing contracted.  Row i of a step with raw result x (frame
+ *                coordinates), lost mask m and dt = dt_seconds[i]:
+ *                  alpha(fc)  = 1.0f / (1.0f + (1.0f / (6.2831855f * fc)) / dt)
+ *                  m != 0     : out = x; primed = 0                        (a lost row passes through, its state is dropped)
+ *                  !primed    : r = x; d = 0; f = x; out = x; primed = 1   (first filtered step since start / restart / configure)
+ *                  otherwise  : s  = fmaxf(max x - min x, max y - min y) of the row    (min / max are exact in any order)
+ *                               w  = s > 0 ? beta / s : 0
+ *                               ad = alpha(d_cutoff)
+ *                               per coordinate j:
+ *                                 v  = (x[j] - r[j]) / dt
+ *                                 dn = (ad * v) + ((1.0f - ad) * d[j]);       dn not finite: dn = 0
+ *                                 a  = alpha(min_cutoff + w * fabsf(dn))
+ *                                 fn = (a * x[j]) + ((1.0f - a) * f[j]);      fn not finite: fn = x[j]
+ *                                 r[j] = x[j]; d[j] = dn; f[j] = fn; out[j] = fn
+ *   dt           seconds since the stream's last FILTERED step, in [1e-4, 1e4]: the bounds keep v finite for any pixel coordinate.
+ *                sdm_track_step never touches the filter's state, whether a filter is configured or not.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched, the slot table, the filter state and the current rows keep their
+ * bits: everything sdm_track_step refuses; no filter configured (or OFF) for the step and the get; an unknown mode; min_cutoff or
+ * d_cutoff not finite or not > 0; beta not finite or < 0; dt_seconds NULL; a dt outside [1e-4, 1e4] or not finite. */
+enum {
+    SDM_TRACK_FILTER_OFF = 0,
+    SDM_TRACK_FILTER_ONE_EURO = 1       /* the arithmetic above */
+};
+/* Needs sdm_track_configure; allocates the state for its capacity, all slots un-primed.  mode OFF frees the state (the parameters
+ * are not looked at).  A later sdm_track_configure switches the filter off. */
+int sdm_track_configure_filter(sdm_ctx* ctx, int mode, float min_cutoff_hz, float beta, float d_cutoff_hz);
+/* sdm_track_step, in plain and in upright mode, plus the filter launch: the same copies (the n step times travel with the ids), one
+ * synchronise, SDM_ERR_EMPTY_PATCH reported the same way.  landmarks_host receives the raw rows, filtered_host the filtered rows
+ * (n x 2L each); landmarks_host, lost_host and filtered_host may be NULL. */
+int sdm_track_step_filtered(sdm_ctx* ctx, const int* ids, int n, const float* dt_seconds, float* landmarks_host, int* lost_host,
+                            float* filtered_host);
+/* The slots' filtered rows f and derivative rows d (n x 2L each) and primed flags (n); an un-primed slot gives zeros and 0.  Each
+ * output may be NULL.  Neither the state nor the current rows x are touched. */
+int sdm_track_get_filtered(sdm_ctx* ctx, const int* ids, int n, float* filtered_host, float* derivative_host, int* primed_host);
+
 /* Aligned face crops of the current rows (after sdm_detect_batch, sdm_track_step or sdm_set_x): for every row n of x (N x 2L, what
  * sdm_get_x returns) an out_width x out_height x C u8 crop in which the face stands in a canonical position -- the input of
  * recognition, expression or attribute networks -- without the landmarks or the frames leaving the device.

@@ -38,6 +38,7 @@ EXPORTED = [
     "sdm_train_level_sweep", "sdm_sweep_get_regressor",
     "sdm_set_frames_device", "sdm_debug_download_image",
     "sdm_upright_configure", "sdm_detect_batch_upright", "sdm_upright_get", "sdm_track_configure_upright", "sdm_track_start_rolled",
+    "sdm_track_configure_filter", "sdm_track_step_filtered", "sdm_track_get_filtered",
     "sdm_warp_delaunay", "sdm_warp_set_mesh", "sdm_warp_get_labels", "sdm_warp_crops_tensor",
     "sdm_warp_crops_tensor_filtered",
     "sdm_align_paste_tensor", "sdm_align_paste_tensor_at",
@@ -52,6 +53,9 @@ EXPORTED = [
 SDM_TRACK_FREE, SDM_TRACK_STARTED, SDM_TRACK_TRACKED, SDM_TRACK_LOST = 0, 1, 2, 3
 SDM_TRACK_INIT_PREVIOUS, SDM_TRACK_INIT_REALIGN = 0, 1
 SDM_TRACK_LOST_NONFINITE, SDM_TRACK_LOST_SMALL, SDM_TRACK_LOST_OUTSIDE, SDM_TRACK_LOST_SCALE = 1, 2, 4, 8
+
+# the tracker's temporal landmark filter (include/sdm.h, "Tracking, filtered")
+SDM_TRACK_FILTER_OFF, SDM_TRACK_FILTER_ONE_EURO = 0, 1
 
 # upright-normalised detect and tracking (include/sdm.h, "Rolled faces")
 SDM_UPRIGHT_PARTIAL, SDM_UPRIGHT_NEAR_EDGE = 1, 2
@@ -445,6 +449,9 @@ def lib() -> ctypes.CDLL:
             "sdm_upright_get": [c_void_p, c_void_p, c_void_p, c_void_p],
             "sdm_track_configure_upright": [c_void_p, c_int],
             "sdm_track_start_rolled": [c_void_p, c_void_p, c_void_p, c_void_p, c_int],
+            "sdm_track_configure_filter": [c_void_p, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float],
+            "sdm_track_step_filtered": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+            "sdm_track_get_filtered": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
             "sdm_warp_delaunay": [c_void_p, c_int, c_void_p, c_int, c_int_p],
             "sdm_warp_set_mesh": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int],
             "sdm_warp_get_labels": [c_void_p, c_void_p],

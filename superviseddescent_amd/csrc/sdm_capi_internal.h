@@ -257,9 +257,18 @@ struct sdm_ctx {
         unsigned stamp = 0;
         int* pin = nullptr;                // pinned staging of the ids / boxes in and the masks out
         size_t pin_cap = 0;                // ints
+        // the temporal landmark filter (sdm_track_configure_filter, csrc/sdm_track_filter.hip): per slot the previous raw row, the
+        // filtered derivative and the previous filtered row, and whether they hold anything
+        int filter = 0;                    // SDM_TRACK_FILTER_*
+        float min_cutoff = 0.f, beta = 0.f, d_cutoff = 0.f;
+        DevBuf<float> filter_state;        // 3 x S x 2L: r, d, f
+        DevBuf<int> primed;                // S
+        DevBuf<float> filter_out;          // scratch of sdm_track_get_filtered: 2 x n x 2L + n ints
+        void filter_off() { filter = 0; filter_state.release(); primed.release(); filter_out.release(); }
         void release()
         {
             mean.release(); x.release(); box.release(); status.release(); init.release(); ids.release(); masks.release(); cs.release();
+            filter_off();
             upright = false;
             if (pin) { hipError_t e = hipHostFree(pin); (void)e; }
             pin = nullptr; pin_cap = 0; S = 0;

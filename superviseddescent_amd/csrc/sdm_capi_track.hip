@@ -63,6 +63,7 @@ int sdm_track_configure(sdm_ctx* c, int capacity, const float* mean, int init_mo
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipStreamSynchronize(c->stream));
     sdm_ctx::Track& t = c->track;
+    t.filter_off();                                // (the filter's state belongs to the slots that go: sdm_track_configure_filter again)
     int rc;
     if ((rc = t.mean.ensure(M)) || (rc = t.x.ensure((size_t)capacity * M)) || (rc = t.box.ensure((size_t)capacity * 4)) ||
         (rc = t.status.ensure((size_t)capacity)))
@@ -109,6 +110,7 @@ static int track_start_common(sdm_ctx* c, const int* ids, const int* boxes, cons
     memcpy(t.pin + cs_ints + n, boxes, (size_t)4 * n * sizeof(int));
     HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (cs_ints + (size_t)5 * n) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     sdm_launch_track_start(t.ids.p + cs_ints, t.ids.p + cs_ints + n, n, t.box.p, t.status.p, c->stream);
+    if (t.filter) sdm_launch_track_filter_unprime(t.ids.p + cs_ints, n, t.primed.p, c->stream);
     if (slots_cs) sdm_launch_upright_slot_cs(t.ids.p + cs_ints, roll_deg ? (const double*)t.ids.p : nullptr, n, t.cs.p, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));      // (the pinned staging is reused by the next call)
@@ -133,11 +135,14 @@ int sdm_track_stop(sdm_ctx* c, const int* ids, int n)
     return SDM_OK;
 }
 
-int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int* lost_host)
+// sdm_track_step (dt null) and sdm_track_step_filtered: the same checks, copies and launches; with dt the filter launch behind the
+// commit, the raw rows copied out before it and the filtered rows after it
+static int track_step_common(sdm_ctx* c, const int* ids, int n, const float* dt, float* landmarks_host, int* lost_host, float* filtered_host)
 {
     int rc = track_ready(c);
     if (rc) return rc;
     sdm_ctx::Track& t = c->track;
+    if (dt && t.filter == SDM_TRACK_FILTER_OFF) return fail(SDM_ERR_INVALID, "no filter configured (sdm_track_configure_filter)");
     if (c->levels.empty()) return fail(SDM_ERR_INVALID, "geometry not set");
     for (size_t l = 0; l < c->levels.size(); ++l)
         if (!c->have_R[l]) return fail(SDM_ERR_INVALID, "no regressor set for level " + std::to_string(l));
@@ -147,6 +152,8 @@ int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int
         if (st == SDM_TRACK_FREE) return fail(SDM_ERR_INVALID, "stream " + std::to_string(ids[i]) + " is not started");
         if (st == SDM_TRACK_LOST) return fail(SDM_ERR_INVALID, "stream " + std::to_string(ids[i]) + " is lost: start it again from a face box");
     }
+    for (int i = 0; dt && i < n; ++i)
+        if (!(dt[i] >= 1e-4f && dt[i] <= 1e4f)) return fail(SDM_ERR_INVALID, "a step time outside [1e-4, 1e4] seconds");
     if (c->tmpl_N > 0) return fail(SDM_ERR_INVALID, "templates are set: the tracker runs the cascade without (sdm_set_templates(NULL))");
     if (t.upright) {
         if (t.cs.cap < (size_t)2 * t.S) return fail(SDM_ERR_INVALID, "the tracker was configured again: call sdm_track_configure_upright again");
@@ -160,15 +167,18 @@ int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int
         return fail(SDM_ERR_INVALID, "sample->image index refers to an image beyond the current image set");
     HIP_TRY(hipSetDevice(c->device));
     const int M = c->M;
-    if ((rc = ensure_sample_buffers(c, n)) || (rc = t.init.ensure((size_t)n * M)) || (rc = t.ids.ensure((size_t)n)) ||
-        (rc = t.masks.ensure((size_t)n + 1)) || (rc = ensure_pinned(t, (size_t)2 * n + 1)))
+    // staging: the ids and, for a filtered step, the step times behind them go to the device in one copy; the masks come back
+    const size_t in_ints = dt ? (size_t)2 * n : (size_t)n;
+    if ((rc = ensure_sample_buffers(c, n)) || (rc = t.init.ensure((size_t)n * M)) || (rc = t.ids.ensure(in_ints)) ||
+        (rc = t.masks.ensure((size_t)n + 1)) || (rc = ensure_pinned(t, in_ints + n + 1)))
         return rc;
     if (t.upright && (rc = upright_ensure(c, n))) return rc;
     // the rows become the current x, as after sdm_set_x + sdm_detect_batch
     if (n != c->N) { c->have_targets = false; c->feat_level = -1; c->have_patch_idx = false; }
     c->N = n; c->cur = 0;
     memcpy(t.pin, ids, (size_t)n * sizeof(int));
-    HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    if (dt) memcpy(t.pin + n, dt, (size_t)n * sizeof(float));
+    HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, in_ints * sizeof(int), hipMemcpyHostToDevice, c->stream));
     if (t.upright) {
         // upright mode: the rows' chips and their init in chip coordinates, the cascade on the chips, the result back in the frame
         UprightSetupDev a{};
@@ -191,10 +201,19 @@ int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int
     sdm_launch_track_commit(t.ids.p, n, c->L, c->x[c->cur].p, t.init.p, c->idx_identity ? nullptr : c->img_idx.p, c->img_w.p, c->img_h.p,
                             c->eyes, t.min_size, t.max_scale, t.x.p, t.status.p, t.masks.p, c->status.p, c->stream);
     HIP_TRY(hipGetLastError());
-    int* masks = t.pin + n;
+    int* masks = t.pin + in_ints;
     HIP_TRY(hipMemcpyAsync(masks, t.masks.p, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (landmarks_host)
         HIP_TRY(hipMemcpyAsync(landmarks_host, c->x[c->cur].p, (size_t)n * M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (dt) {
+        // the current rows become the filtered rows; the slots' landmark rows stay raw
+        const size_t SM = (size_t)t.S * M;
+        sdm_launch_track_filter(t.ids.p, n, c->L, t.masks.p, (const float*)(t.ids.p + n), t.min_cutoff, t.beta, t.d_cutoff, c->x[c->cur].p,
+                                t.filter_state.p, t.filter_state.p + SM, t.filter_state.p + 2 * SM, t.primed.p, c->stream);
+        HIP_TRY(hipGetLastError());
+        if (filtered_host)
+            HIP_TRY(hipMemcpyAsync(filtered_host, c->x[c->cur].p, (size_t)n * M * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int i = 0; i < n; ++i) t.host_status[ids[i]] = masks[i] ? SDM_TRACK_LOST : SDM_TRACK_TRACKED;
     if (lost_host) memcpy(lost_host, masks, (size_t)n * sizeof(int));
@@ -205,6 +224,66 @@ int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int
             return fail(SDM_ERR_EMPTY_PATCH, "patch_width_half <= 0 for at least one row (inter-eye distance too small)");
         return fail(SDM_ERR_HIP, "a kernel reported status " + std::to_string(st));
     }
+    return SDM_OK;
+}
+
+int sdm_track_step(sdm_ctx* c, const int* ids, int n, float* landmarks_host, int* lost_host)
+{
+    return track_step_common(c, ids, n, nullptr, landmarks_host, lost_host, nullptr);
+}
+
+int sdm_track_configure_filter(sdm_ctx* c, int mode, float min_cutoff_hz, float beta, float d_cutoff_hz)
+{
+    int rc = track_ready(c);
+    if (rc) return rc;
+    sdm_ctx::Track& t = c->track;
+    if (mode != SDM_TRACK_FILTER_OFF && mode != SDM_TRACK_FILTER_ONE_EURO) return fail(SDM_ERR_INVALID, "unknown filter mode");
+    if (mode == SDM_TRACK_FILTER_ONE_EURO) {
+        if (!std::isfinite(min_cutoff_hz) || !(min_cutoff_hz > 0.f)) return fail(SDM_ERR_INVALID, "min_cutoff must be finite and > 0");
+        if (!std::isfinite(beta) || !(beta >= 0.f)) return fail(SDM_ERR_INVALID, "beta must be finite and >= 0");
+        if (!std::isfinite(d_cutoff_hz) || !(d_cutoff_hz > 0.f)) return fail(SDM_ERR_INVALID, "d_cutoff must be finite and > 0");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (mode == SDM_TRACK_FILTER_OFF) { t.filter_off(); return SDM_OK; }
+    const size_t SM = (size_t)t.S * 2 * t.L;
+    if ((rc = t.filter_state.ensure(3 * SM)) || (rc = t.primed.ensure((size_t)t.S))) { t.filter_off(); return rc; }
+    HIP_TRY(hipMemsetAsync(t.filter_state.p, 0, 3 * SM * sizeof(float), c->stream));
+    HIP_TRY(hipMemsetAsync(t.primed.p, 0, (size_t)t.S * sizeof(int), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    t.filter = mode; t.min_cutoff = min_cutoff_hz; t.beta = beta; t.d_cutoff = d_cutoff_hz;
+    return SDM_OK;
+}
+
+int sdm_track_step_filtered(sdm_ctx* c, const int* ids, int n, const float* dt_seconds, float* landmarks_host, int* lost_host,
+                            float* filtered_host)
+{
+    if (!dt_seconds) return fail(SDM_ERR_INVALID, "no step times");
+    return track_step_common(c, ids, n, dt_seconds, landmarks_host, lost_host, filtered_host);
+}
+
+int sdm_track_get_filtered(sdm_ctx* c, const int* ids, int n, float* filtered_host, float* derivative_host, int* primed_host)
+{
+    int rc = track_ready(c);
+    if (rc) return rc;
+    sdm_ctx::Track& t = c->track;
+    if (t.filter == SDM_TRACK_FILTER_OFF) return fail(SDM_ERR_INVALID, "no filter configured (sdm_track_configure_filter)");
+    if ((rc = check_ids(c, ids, n))) return rc;
+    if (!filtered_host && !derivative_host && !primed_host) return SDM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t nM = (size_t)n * c->M, SM = (size_t)t.S * c->M;
+    if ((rc = t.filter_out.ensure(2 * nM + n)) || (rc = t.ids.ensure((size_t)n)) || (rc = ensure_pinned(t, (size_t)n))) return rc;
+    memcpy(t.pin, ids, (size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    float* out_f = t.filter_out.p;
+    float* out_d = out_f + nM;
+    int* out_p = (int*)(out_d + nM);
+    sdm_launch_track_filter_get(t.ids.p, n, c->L, t.filter_state.p + SM, t.filter_state.p + 2 * SM, t.primed.p, out_f, out_d, out_p, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (filtered_host) HIP_TRY(hipMemcpyAsync(filtered_host, out_f, nM * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (derivative_host) HIP_TRY(hipMemcpyAsync(derivative_host, out_d, nM * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (primed_host) HIP_TRY(hipMemcpyAsync(primed_host, out_p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return SDM_OK;
 }
 

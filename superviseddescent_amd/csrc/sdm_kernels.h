@@ -409,6 +409,14 @@ void sdm_launch_track_gather(const int* ids, int n, int L, int mode, const int* 
 void sdm_launch_track_commit(const int* ids, int n, int L, const float* x, const float* init, const int* img_idx, const int* img_w,
                              const int* img_h, const EyeIdxDev& eyes, float min_size, float max_scale_change, float* slot_x,
                              int* slot_status, int* masks, const int* status_word, hipStream_t s);
+// the temporal landmark filter (sdm_track_filter.hip), behind the commit: row i of x (n x 2L, raw in, filtered out) through the
+// One-Euro state of slot ids[i] -- state_r, state_d, state_f S x 2L, primed S; masks: the commit's; dt: n step times in seconds
+void sdm_launch_track_filter(const int* ids, int n, int L, const int* masks, const float* dt, float min_cutoff, float beta, float d_cutoff,
+                             float* x, float* state_r, float* state_d, float* state_f, int* primed, hipStream_t s);
+void sdm_launch_track_filter_unprime(const int* ids, int n, int* primed, hipStream_t s);
+// out_f, out_d: n x 2L, zeros where a slot is not primed; out_primed: n
+void sdm_launch_track_filter_get(const int* ids, int n, int L, const float* state_d, const float* state_f, const int* primed, float* out_f,
+                                 float* out_d, int* out_primed, hipStream_t s);
 
 // ---- aligned face crops (sdm_align.hip) ----
 // per row: the crop -> source matrix (float32, rounded from the double fit), the SDM_ALIGN_* flags and the row's image

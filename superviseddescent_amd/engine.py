@@ -602,6 +602,44 @@ class Context:
         check(self._lib.sdm_track_get(self._h, i.ctypes.data, i.size, out.ctypes.data, st.ctypes.data))
         return out, st
 
+    # -- the tracker's temporal landmark filter (csrc/sdm_track_filter.hip) --------------------------
+    def track_configure_filter(self, min_cutoff: Optional[float] = None, beta: float = 0.0, d_cutoff: float = 1.0):
+        """The One-Euro filter on the tracker's output (include/sdm.h, "Tracking, filtered"): ``min_cutoff`` > 0 Hz, ``beta`` >= 0 Hz
+        per face size per second, ``d_cutoff`` > 0 Hz; every slot un-primed.  ``min_cutoff`` None: the filter off."""
+        if min_cutoff is None:
+            check(self._lib.sdm_track_configure_filter(self._h, _lib.SDM_TRACK_FILTER_OFF, 0.0, 0.0, 0.0))
+        else:
+            check(self._lib.sdm_track_configure_filter(self._h, _lib.SDM_TRACK_FILTER_ONE_EURO, float(min_cutoff), float(beta),
+                                                       float(d_cutoff)))
+
+    def track_step_filtered(self, ids, dt, fetch: bool = True):
+        """``track_step`` with the filter behind it; ``dt``: seconds since the streams' last filtered step, one value or one per
+        row.  Returns (filtered rows n x 2L or None, lost masks n, raw rows n x 2L or None); the FILTERED rows are the current x
+        afterwards."""
+        i = self._ids(ids)
+        d = np.ascontiguousarray(np.broadcast_to(np.asarray(dt, np.float32).reshape(-1), (i.size,)), np.float32)
+        raw = np.empty((i.size, 2 * self.L), np.float32) if fetch else None
+        out = np.empty((i.size, 2 * self.L), np.float32) if fetch else None
+        lost = np.empty(i.size, np.int32)
+        rc = self._lib.sdm_track_step_filtered(self._h, i.ctypes.data, i.size, d.ctypes.data, raw.ctypes.data if fetch else None,
+                                               lost.ctypes.data, out.ctypes.data if fetch else None)
+        if rc in (_lib.SDM_OK, _lib.SDM_ERR_EMPTY_PATCH):      # (the step was committed)
+            self.N = i.size
+            if getattr(self, "track_upright", False):
+                self.upright_N = i.size
+        check(rc)
+        return out, lost, raw
+
+    def track_get_filtered(self, ids):
+        """(filtered rows n x 2L, derivative rows n x 2L, primed flags n) of the streams ``ids``; zeros where a stream's filter holds
+        nothing yet."""
+        i = self._ids(ids)
+        f = np.empty((i.size, 2 * self.L), np.float32)
+        d = np.empty((i.size, 2 * self.L), np.float32)
+        p = np.empty(i.size, np.int32)
+        check(self._lib.sdm_track_get_filtered(self._h, i.ctypes.data, i.size, f.ctypes.data, d.ctypes.data, p.ctypes.data))
+        return f, d, p
+
     # -- upright-normalised detect and tracking (csrc/sdm_upright.hip) ------------------------------
     def upright_configure(self, chip: int, guard: int):
         """The size of the upright chips (32 ... 1024 pixels) and the NEAR_EDGE guard band (0 ... chip / 2 - 1 pixels)."""
@@ -1738,7 +1776,7 @@ class detection_model:
         return c.pose_get_x()
 
     def tracker(self, capacity: int, init: str = "realign", min_size: float = 8.0, max_scale_change: float = 1.5,
-                chip: Optional[int] = None, guard: Optional[int] = None) -> "Tracker":
+                chip: Optional[int] = None, guard: Optional[int] = None, smooth=None) -> "Tracker":
         """Multi-stream tracking on the optimiser's context: ``capacity`` stream slots whose landmarks stay on the device from
         frame to frame (see :class:`Tracker`).  ``init``: how a tracked stream's next frame starts -- "previous" (its landmarks,
         the reference's ``detect(image, initialisation)``) or "realign" (the mean shape in their enclosing box).  A stream is
@@ -1746,8 +1784,11 @@ class detection_model:
         image, or its inter-eye distance changes by more than the factor ``max_scale_change`` in one step (0: no such rule).
         ``init="upright"`` follows rolled faces: every step cuts each stream's face upright as a ``chip`` x ``chip`` image (the roll
         from the stream's own previous eye line), realigns in the chip, runs the cascade there and maps the result back; ``chip``
-        (required) and ``guard`` (default ``chip // 8``) as for ``detect_batch(roll=...)``."""
-        return Tracker(self, capacity, init, min_size, max_scale_change, chip, guard)
+        (required) and ``guard`` (default ``chip // 8``) as for ``detect_batch(roll=...)``.
+        ``smooth=(min_cutoff, beta)`` or ``(min_cutoff, beta, d_cutoff)``: a One-Euro filter on what ``step(..., dt=...)`` returns
+        and leaves as the current rows -- ``min_cutoff`` (Hz) sets how steady a still face is, ``beta`` how fast the filter lets go
+        when the face moves (in face sizes per second), ``d_cutoff`` defaults to 1 Hz.  Tracking itself is not changed by it."""
+        return Tracker(self, capacity, init, min_size, max_scale_change, chip, guard, smooth)
 
     def aligned_crops(self, size, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
                       margin: float = 0.2, source=None, out=None):
@@ -2038,7 +2079,8 @@ class Tracker:
     _MODES = {"previous": _lib.SDM_TRACK_INIT_PREVIOUS, "realign": _lib.SDM_TRACK_INIT_REALIGN}
 
     def __init__(self, model: detection_model, capacity: int, init: str = "realign", min_size: float = 8.0,
-                 max_scale_change: float = 1.5, chip: Optional[int] = None, guard: Optional[int] = None):
+                 max_scale_change: float = 1.5, chip: Optional[int] = None, guard: Optional[int] = None, smooth=None):
+        self.smooth = self._smooth(smooth)
         if init not in self._MODES and init != "upright":
             raise ValueError('init must be "previous", "realign" or "upright"')
         if init == "upright" and chip is None:
@@ -2052,6 +2094,24 @@ class Tracker:
             self.ctx.upright_configure(int(chip), int(chip) // 8 if guard is None else int(guard))
         if init == "upright" or getattr(self.ctx, "track_upright", False):      # (off again for a plain tracker on the same context)
             self.ctx.track_configure_upright(init == "upright")
+        if self.smooth is not None:
+            self.ctx.track_configure_filter(*self.smooth)
+
+    @staticmethod
+    def _smooth(smooth):
+        """(min_cutoff, beta[, d_cutoff = 1.0]) as three floats, or None"""
+        if smooth is None:
+            return None
+        try:
+            v = tuple(float(a) for a in smooth)
+        except TypeError:
+            raise ValueError("smooth is (min_cutoff, beta) or (min_cutoff, beta, d_cutoff)") from None
+        if len(v) not in (2, 3):
+            raise ValueError("smooth is (min_cutoff, beta) or (min_cutoff, beta, d_cutoff)")
+        v = v if len(v) == 3 else v + (1.0,)
+        if not (np.isfinite(v).all() and v[0] > 0 and v[1] >= 0 and v[2] > 0):
+            raise ValueError("smooth needs min_cutoff > 0, beta >= 0 and d_cutoff > 0")
+        return v
 
     @property
     def ctx(self) -> Context:
@@ -2076,13 +2136,22 @@ class Tracker:
     def stop(self, ids):
         self.ctx.track_stop(ids)
 
-    def step(self, ids, frames=None, image_index=None, fetch: bool = True, formats=None, gray_shift: int = 14):
+    def step(self, ids, frames=None, image_index=None, fetch: bool = True, formats=None, gray_shift: int = 14, dt=None):
         """One frame for the streams ``ids``: row i belongs to stream ids[i] and reads frame ``image_index[i]`` (default i).
         ``frames``: host images (a list or an n x H x W stack, uploaded), a uint8 n x H x W tensor on the device (used in place),
         any other device input of ``Context.set_frames_device`` -- a list of gray or colour tensors of different sizes, pitched
         views, a stacked n x H x W x C tensor, (ptr, w, h, stride, format) tuples; ``formats`` and ``gray_shift`` go with it --
         or None (the images already set on the context).  Returns (landmarks n x 2L -- None unless ``fetch`` --, lost masks n:
-        0 = tracked, else the SDM_TRACK_LOST_* bits)."""
+        0 = tracked, else the SDM_TRACK_LOST_* bits).
+        ``dt`` (a tracker with ``smooth`` only; seconds since the streams' last step with ``dt``, one value or one per row): the
+        step's rows go through the filter, and the return is (filtered n x 2L, lost masks n, raw n x 2L) -- the two row entries None
+        unless ``fetch``.  The filtered rows are the context's current rows: crops, warps, pastes and poses follow them."""
+        if dt is not None:
+            if self.smooth is None:
+                raise ValueError("dt needs a tracker with smooth=(min_cutoff, beta)")
+            dt = np.asarray(dt, np.float32).reshape(-1)
+            if dt.size not in (1, np.atleast_1d(np.asarray(ids)).size):
+                raise ValueError("dt is one value or one per stream id")
         c = self.ctx
         self._bind()
         if frames is not None:
@@ -2100,8 +2169,15 @@ class Tracker:
             self.model.optimised_model._bound = None                        # (the context's images are no longer a bound projection's)
         c.set_templates(None)
         c.set_sample_image_index(image_index)
-        return c.track_step(ids, fetch)
+        return c.track_step(ids, fetch) if dt is None else c.track_step_filtered(ids, dt, fetch)
 
     def get(self, ids):
         """(landmarks n x 2L, status n: SDM_TRACK_FREE / STARTED / TRACKED / LOST) of the streams ``ids``."""
         return self.ctx.track_get(ids)
+
+    def get_filtered(self, ids):
+        """(filtered rows n x 2L, their derivative in pixels per second n x 2L, primed flags n) of the streams ``ids``; a stream
+        whose filter holds nothing yet -- not stepped with ``dt`` since its start -- gives zeros."""
+        if self.smooth is None:
+            raise ValueError("get_filtered needs a tracker with smooth=(min_cutoff, beta)")
+        return self.ctx.track_get_filtered(ids)

@@ -11,6 +11,10 @@
 // Rolled faces (phone video, ceiling cameras, tilted heads): tr.upright(288) makes every step cut each stream's face upright as a
 // 288 x 288 chip -- the roll from the stream's own previous eye line --, run the cascade there and map the result back
 // (include/sdm.h, "Rolled faces"); tr.start(ids, boxes, rolls) starts streams whose faces are rolled in their boxes.
+//
+// Faces in video: tr.smooth(1.0f, 5.0f) puts a One-Euro filter behind the tracker (include/sdm.h, "Tracking, filtered"), and
+// tr.step(ids, frames, dt) returns the filtered landmarks and leaves them as the context's current rows -- crops, warps, pastes and
+// poses follow them; raw_rows() holds what the cascade gave.  Tracking itself is not changed by the filter.
 #pragma once
 
 #ifndef RCR_TRACKER_HPP_
@@ -19,6 +23,7 @@
 #include "rcr/model.hpp"
 
 #include <stdexcept>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -79,6 +84,19 @@ public:
         superviseddescent::hip::check(sdm_track_start_rolled(handle.get(), ids.data(), b.data(), rolls.data(), (int)ids.size()), "sdm_track_start_rolled");
     }
 
+    /** A One-Euro filter on what step(..., dt) returns: min_cutoff > 0 Hz (how steady a still face is), beta >= 0 Hz per face size
+     *  per second (how fast the filter lets go when the face moves), d_cutoff > 0 Hz.  Every stream's filter starts empty. */
+    void smooth(float min_cutoff, float beta, float d_cutoff = 1.0f)
+    {
+        superviseddescent::hip::check(sdm_track_configure_filter(handle.get(), SDM_TRACK_FILTER_ONE_EURO, min_cutoff, beta, d_cutoff),
+                                      "sdm_track_configure_filter");
+    }
+    /** The filter off again. */
+    void smooth_off()
+    {
+        superviseddescent::hip::check(sdm_track_configure_filter(handle.get(), SDM_TRACK_FILTER_OFF, 0.f, 0.f, 0.f), "sdm_track_configure_filter");
+    }
+
     void stop(const std::vector<int>& ids)
     {
         superviseddescent::hip::check(sdm_track_stop(handle.get(), ids.data(), (int)ids.size()), "sdm_track_stop");
@@ -103,6 +121,49 @@ public:
         return step_on_current_images(ids, image_index);
     }
 
+    /** The same through the filter of smooth(): dt = seconds since the streams' last step with dt, one value (a float or double) for
+     *  all rows or a std::vector<float> with one per row.  Returns the FILTERED landmarks, which are the context's current rows
+     *  afterwards; rows() holds them as n x 2L, raw_rows() the cascade's own result, lost() the masks.
+     *  (Templates, so that a braced third argument still means image_index.) */
+    template <class Dt, typename std::enable_if<std::is_floating_point<Dt>::value, int>::type = 0>
+    std::vector<LandmarkCollection<cv::Vec2f>> step(const std::vector<int>& ids, const std::vector<cv::Mat>& frames, Dt dt,
+                                                    const std::vector<int>& image_index = {})
+    {
+        return step(ids, frames, std::vector<float>(ids.size(), (float)dt), image_index);
+    }
+    template <class Dt, typename std::enable_if<std::is_floating_point<Dt>::value, int>::type = 0>
+    std::vector<LandmarkCollection<cv::Vec2f>> step(const std::vector<int>& ids, const std::vector<DeviceFrame>& frames, Dt dt,
+                                                    const std::vector<int>& image_index = {})
+    {
+        return step(ids, frames, std::vector<float>(ids.size(), (float)dt), image_index);
+    }
+    template <class Dt, typename std::enable_if<std::is_same<Dt, std::vector<float>>::value, int>::type = 0>
+    std::vector<LandmarkCollection<cv::Vec2f>> step(const std::vector<int>& ids, const std::vector<cv::Mat>& frames, const Dt& dt,
+                                                    const std::vector<int>& image_index = {})
+    {
+        detail::upload_images(handle, frames);
+        return step_on_current_images(ids, image_index, &dt);
+    }
+    template <class Dt, typename std::enable_if<std::is_same<Dt, std::vector<float>>::value, int>::type = 0>
+    std::vector<LandmarkCollection<cv::Vec2f>> step(const std::vector<int>& ids, const std::vector<DeviceFrame>& frames, const Dt& dt,
+                                                    const std::vector<int>& image_index = {})
+    {
+        detail::set_device_frames(handle, frames);
+        return step_on_current_images(ids, image_index, &dt);
+    }
+
+    /** The streams' filtered landmarks, their derivative rows (pixels per second, n x 2L) and primed flags; a stream whose filter
+     *  holds nothing yet gives zeros. */
+    std::pair<std::vector<LandmarkCollection<cv::Vec2f>>, std::vector<int>> get_filtered(const std::vector<int>& ids, cv::Mat* derivative = nullptr)
+    {
+        cv::Mat rows((int)ids.size(), 2 * num_landmarks(), CV_32FC1), d((int)ids.size(), 2 * num_landmarks(), CV_32FC1);
+        std::vector<int> primed(ids.size());
+        superviseddescent::hip::check(sdm_track_get_filtered(handle.get(), ids.data(), (int)ids.size(), rows.ptr<float>(0), d.ptr<float>(0),
+                                                             primed.data()), "sdm_track_get_filtered");
+        if (derivative) *derivative = d;
+        return {collections(rows), primed};
+    }
+
     /** The streams' landmarks (a started stream: its aligned mean) and statuses. */
     std::pair<std::vector<LandmarkCollection<cv::Vec2f>>, std::vector<int>> get(const std::vector<int>& ids)
     {
@@ -114,10 +175,13 @@ public:
 
     const std::vector<int>& lost() const { return last_lost; }
     const cv::Mat& rows() const { return last_rows; }
+    /** The cascade's own rows of the last step (the same as rows() after a step without dt). */
+    const cv::Mat& raw_rows() const { return last_raw; }
     sdm_ctx* context() const { return handle.get(); }
 
 private:
-    std::vector<LandmarkCollection<cv::Vec2f>> step_on_current_images(const std::vector<int>& ids, const std::vector<int>& image_index)
+    std::vector<LandmarkCollection<cv::Vec2f>> step_on_current_images(const std::vector<int>& ids, const std::vector<int>& image_index,
+                                                                      const std::vector<float>* dt = nullptr)
     {
         using superviseddescent::hip::check;
         sdm_ctx* c = handle.get();
@@ -127,7 +191,16 @@ private:
         else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
         cv::Mat rows(n, 2 * num_landmarks(), CV_32FC1);
         std::vector<int> masks(ids.size());
-        check(sdm_track_step(c, ids.data(), n, rows.ptr<float>(0), masks.data()), "sdm_track_step");
+        if (dt) {
+            if (dt->size() != ids.size()) throw std::runtime_error("tracker::step: one dt per stream id expected");
+            cv::Mat raw(n, 2 * num_landmarks(), CV_32FC1);
+            check(sdm_track_step_filtered(c, ids.data(), n, dt->data(), raw.ptr<float>(0), masks.data(), rows.ptr<float>(0)),
+                  "sdm_track_step_filtered");
+            last_raw = raw;
+        } else {
+            check(sdm_track_step(c, ids.data(), n, rows.ptr<float>(0), masks.data()), "sdm_track_step");
+            last_raw = rows;
+        }
         last_rows = rows;
         last_lost = masks;
         return collections(rows);
@@ -143,7 +216,7 @@ private:
 
     detection_model& model;
     superviseddescent::hip::Handle handle;
-    cv::Mat last_rows;
+    cv::Mat last_rows, last_raw;
     std::vector<int> last_lost;
 };
 
