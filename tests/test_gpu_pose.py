@@ -7,6 +7,7 @@ import pytest
 
 import cpp_build as B
 import pose_f64 as P
+from pose_cases import homogeneous, poses as random_poses, rel_err
 from superviseddescent_amd import (Context, HoGParam, HogTransform, LinearRegressor, ModelProjection, Regulariser, SdmError,
                                    SupervisedDescentOptimiser, detection_model, ibug, synth)
 
@@ -16,22 +17,6 @@ MN = Regulariser.RegularisationType.MatrixNorm
 FEAT_TOL = 6e-6
 # the example end to end: predicted angles of the device cascade vs the float64 cascade trained on the same samples, degrees
 PREDICT_TOL_DEG = 5e-3
-
-
-def homogeneous(points):
-    return np.concatenate([np.asarray(points, np.float32).T, np.ones((1, len(points)), np.float32)])
-
-
-def random_poses(n, seed, limit=30.0):
-    rng = np.random.default_rng(seed)
-    x = np.zeros((n, 6), np.float32)
-    x[:, :3] = rng.uniform(-limit, limit, (n, 3))
-    x[:, 5] = -2000.0
-    return x
-
-
-def rel_err(y, ref):
-    return np.abs(np.asarray(y, np.float64) - ref).max(1) / np.abs(ref).max(1)
 
 
 @pytest.fixture(scope="module")
