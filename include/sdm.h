@@ -166,8 +166,35 @@ int sdm_set_images_device(sdm_ctx* ctx, const uint8_t* dev_base, int n_images, i
 #define SDM_FRAME_RGBA 4
 #define SDM_FRAME_NV12 5   /* data = the Y plane (height rows of stride_bytes), used in place;
                               the chroma plane behind it is never read; Y is taken as it is    */
+#define SDM_FRAME_BGR_PLANAR 16   /* three planes of 1 byte per pixel, B G R: "Planar colour frames" below */
+#define SDM_FRAME_RGB_PLANAR 17   /* three planes, R G B                                                    */
 typedef struct sdm_frame { const void* data; int width, height, stride_bytes, format; } sdm_frame;
 int sdm_set_frames_device(sdm_ctx* ctx, const sdm_frame* frames, int n_frames, int gray_shift);
+/* Planar colour frames -- 3 x H x W uint8, the layout of torch's decoders, colour transforms and image networks -- as a source and
+ * as a destination of every call that takes an sdm_frame.  Nothing is repacked: the image set, the crops, the warps and the pastes
+ * address the three planes where they lie.
+ *   planes    data is plane 0: height rows of stride_bytes, one byte per pixel, stride_bytes >= width.  Plane c (c = 0, 1, 2) is at
+ *       (const uint8_t*)data + c * D with D, the plane distance, a signed 64-bit number of bytes.  The order of the planes is
+ *       B, G, R for SDM_FRAME_BGR_PLANAR and R, G, B for SDM_FRAME_RGB_PLANAR.
+ *   D         (int64_t)height * stride_bytes by default -- a contiguous 3 x H x W block, the rule NV12 has for its UV plane.  An entry
+ *       point with a `chroma` / `dst_chroma` / `planes` array takes the address of plane 1, the SECOND PLANE, as entry i of it: D is
+ *       that address minus data, of any sign (a reversed channel view has a negative D); a NULL entry, or a NULL array, is the default.
+ *       D == 0 is refused.  So a region x[:, 100:580, 200:840], a frame of an N x 3 x H x W batch and a channel-sliced buffer are all
+ *       frames as they are.  Entry points without such an array -- sdm_set_frames_device, sdm_align_paste_tensor[_at][_filtered],
+ *       sdm_warp_paste_tensor[_at] -- take planar frames with the default D; the _nv12 forms of the pastes (filter == NULL allowed, any
+ *       mix of formats) are the general forms for planar destinations.
+ *   values    a planar pixel is the interleaved pixel of the same three bytes: the image set's gray bytes, the crop and warp tensors
+ *       (channels == 1: the gray weights applied to the warped (B, G, R)) and the pasted bytes are bit-identical to those of the
+ *       SDM_FRAME_BGR / SDM_FRAME_RGB frame that holds the same pixels.  Inside a plane the offsets are those of a one-byte format
+ *       (32-bit while height * stride_bytes <= INT_MAX); D is applied to the pointer in 64 bits first.
+ *   pastes    one byte of each plane is loaded, blended and stored per owned pixel; the ownership rule, the row order and "never stored
+ *       to" hold word for word -- the bytes between the planes and the pitch padding are neither read nor written.  Reading planes
+ *       that overlap is harmless; pasting into them is undefined, as pasting into aliasing frames is.
+ *   refused   (SDM_ERR_INVALID, no state changed, nothing launched) what is refused of a one-byte-per-pixel frame; D == 0; and
+ *       sdm_align_crops, the interleaved u8 form, on a frame list that holds a planar frame (as for NV12: use sdm_align_crops_tensor).
+ * sdm_set_frames_device_planes is sdm_set_frames_device with the second planes: planes is NULL or n_frames pointers, entries of frames
+ * that are not planar are ignored. */
+int sdm_set_frames_device_planes(sdm_ctx* ctx, const sdm_frame* frames, const void* const* planes, int n_frames, int gray_shift);
 /* `training_index` of HogTransform::operator() (adaptive_vlhog.hpp:109): sample -> image.
  * idx == NULL means sample i uses image i. */
 int sdm_set_sample_image_index(sdm_ctx* ctx, const int* idx, int n_samples);
@@ -651,8 +678,9 @@ int sdm_align_crops(sdm_ctx* ctx, const int* landmark_index, const float* templa
  * N x C x H x W (or N x H x W x C) elements of u8, float16 or float32, channel order, mean and std applied.
  *
  * sdm_align_set_source_frames: a frame list as the crop source, used IN PLACE (nothing copied, nothing converted; the memory must stay
- * valid while crops are made from it).  frames: as for sdm_set_frames_device, all six formats.  chroma: NULL, or n_frames pointers;
- * entry i is the interleaved UV plane of an NV12 frame i (ignored for other formats); a NULL entry, or chroma == NULL, means
+ * valid while crops are made from it).  frames: as for sdm_set_frames_device, every format.  chroma: NULL, or n_frames pointers;
+ * entry i is the SECOND PLANE of frame i -- the interleaved UV plane of an NV12 frame, plane 1 of a planar colour frame ("Planar colour
+ * frames": its plane distance is that address minus data) --, ignored for other formats; a NULL entry, or chroma == NULL, means
  * (const uint8_t*)data + (size_t)height * stride_bytes.  The UV plane has (height + 1) / 2 rows of stride_bytes.
  * n_frames == 0 / frames == NULL: back to the context's images.  Replaces an sdm_align_set_source stack and is replaced by one.
  * Refused (SDM_ERR_INVALID, no state changed): what sdm_set_frames_device refuses of a frame (n_frames < 0, a NULL data pointer, width or
@@ -984,7 +1012,7 @@ int sdm_align_paste_tensor_at_filtered(sdm_ctx* ctx, const float* matrices_host 
 int sdm_align_paste_tensor_nv12(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int crop_width, int crop_height,
                                 const sdm_align_tensor* spec, const sdm_align_filter* filter /* NULL: plain bilinear */, const void* in_dev,
                                 const sdm_align_paste* paste, const sdm_frame* dst_frames,
-                                void* const* dst_chroma /* n_frames UV planes; NULL, or a NULL entry: behind the Y plane */, int n_frames,
+                                void* const* dst_chroma /* n_frames second planes (NV12: UV, planar: plane 1); NULL, or a NULL entry: behind the first plane */, int n_frames,
                                 float* matrices_host /* out, N x 6, may be NULL */, int* flags_host /* out, may be NULL */,
                                 int* samples_host /* out, may be NULL */);
 int sdm_align_paste_tensor_at_nv12(sdm_ctx* ctx, const float* matrices_host /* in, n_rows x 6 */,
@@ -1068,7 +1096,7 @@ int sdm_warp_paste_tensor_at(sdm_ctx* ctx, const float* points_host /* in, n_row
  * frame; an NV12 frame with stride_bytes < 2 * ((width + 1) / 2). */
 int sdm_warp_paste_tensor_nv12(sdm_ctx* ctx, const sdm_align_tensor* spec, const void* in_dev, const sdm_align_paste* paste,
                                const sdm_frame* dst_frames,
-                               void* const* dst_chroma /* n_frames UV planes; NULL, or a NULL entry: behind the Y plane */, int n_frames,
+                               void* const* dst_chroma /* n_frames second planes (NV12: UV, planar: plane 1); NULL, or a NULL entry: behind the first plane */, int n_frames,
                                float* matrices_host /* out, N x T x 6, may be NULL */, int* flags_host /* out, may be NULL */);
 int sdm_warp_paste_tensor_at_nv12(sdm_ctx* ctx, const float* points_host /* in, n_rows x K x 2 */,
                                   const int* image_index /* NULL: row i -> frame i */, int n_rows, const sdm_align_tensor* spec,

@@ -36,7 +36,7 @@ EXPORTED = [
     "sdm_track_configure", "sdm_track_start", "sdm_track_stop", "sdm_track_step", "sdm_track_get",
     "sdm_align_set_source", "sdm_align_crops", "sdm_align_set_source_frames", "sdm_align_crops_tensor", "sdm_align_crops_tensor_filtered",
     "sdm_train_level_sweep", "sdm_sweep_get_regressor",
-    "sdm_set_frames_device", "sdm_debug_download_image",
+    "sdm_set_frames_device", "sdm_set_frames_device_planes", "sdm_debug_download_image",
     "sdm_upright_configure", "sdm_detect_batch_upright", "sdm_upright_get", "sdm_track_configure_upright", "sdm_track_start_rolled",
     "sdm_track_configure_filter", "sdm_track_step_filtered", "sdm_track_get_filtered",
     "sdm_warp_delaunay", "sdm_warp_set_mesh", "sdm_warp_get_labels", "sdm_warp_crops_tensor",
@@ -82,6 +82,11 @@ SDM_WARP_NO_TRIANGLE = 255
 SDM_FRAME_GRAY, SDM_FRAME_BGR, SDM_FRAME_RGB, SDM_FRAME_BGRA, SDM_FRAME_RGBA, SDM_FRAME_NV12 = range(6)
 FRAME_FORMATS = {"gray": SDM_FRAME_GRAY, "bgr": SDM_FRAME_BGR, "rgb": SDM_FRAME_RGB, "bgra": SDM_FRAME_BGRA, "rgba": SDM_FRAME_RGBA,
                  "nv12": SDM_FRAME_NV12}
+# planar colour, 3 x H x W (include/sdm.h, "Planar colour frames"): three planes of one byte per pixel, B G R or R G B
+SDM_FRAME_BGR_PLANAR, SDM_FRAME_RGB_PLANAR = 16, 17
+FRAME_FORMATS.update({"bgr_planar": SDM_FRAME_BGR_PLANAR, "rgb_planar": SDM_FRAME_RGB_PLANAR})
+_FRAME_PLANAR = (SDM_FRAME_BGR_PLANAR, SDM_FRAME_RGB_PLANAR)
+# (bytes per pixel of plane 0; a planar frame is not among the 1-byte frames an H x W tensor can be)
 _FRAME_CHANNELS = {SDM_FRAME_GRAY: 1, SDM_FRAME_NV12: 1, SDM_FRAME_BGR: 3, SDM_FRAME_RGB: 3, SDM_FRAME_BGRA: 4, SDM_FRAME_RGBA: 4}
 
 
@@ -212,6 +217,27 @@ def _is_tensor(obj) -> bool:
     return hasattr(obj, "data_ptr") and hasattr(obj, "stride") and hasattr(obj, "shape")
 
 
+def _is_planar_name(fmt) -> bool:
+    return fmt is not None and _frame_format(fmt) in _FRAME_PLANAR
+
+
+def _planar_tensor_frame(ptr: int, shape, stride, fmt):
+    """One 3 x H x W view named planar -> ((ptr, w, h, stride_bytes, format), the second plane's address or None for the default
+    plane distance height * stride_bytes).  Only stride(2) == 1 is asked for: the row and the channel stride are free, of any sign."""
+    if len(shape) != 3 or shape[0] != 3:
+        raise ValueError(f"a {fmt!r} frame is 3 x H x W")
+    _, h, w = shape
+    ch, row, px = stride
+    if h < 1 or w < 1:
+        raise ValueError("empty frame")
+    if w > 1 and px != 1:
+        raise ValueError("a planar frame must be dense within a row: stride(2) == 1")
+    if h > 1 and row < w:
+        raise ValueError("the row stride is smaller than a row")
+    st = int(row) if h > 1 else int(w)
+    return (int(ptr), int(w), int(h), st, _frame_format(fmt)), (None if ch == h * st else int(ptr) + int(ch))
+
+
 def _tensor_frame(ptr: int, shape, stride, fmt):
     """One H x W or H x W x C view (sizes and strides in elements = bytes) -> (ptr, w, h, stride_bytes, format)."""
     if len(shape) == 2:
@@ -241,20 +267,46 @@ def _tensor_frame(ptr: int, shape, stride, fmt):
 
 
 def frame_descriptors(frames, formats=None):
-    """The ``sdm_frame`` list of ``frames`` as (ptr, width, height, stride_bytes, format) tuples.  Pure host code on duck-typed
-    objects (``data_ptr()``, ``shape``, ``stride()``, ``dtype``): no device, no torch needed.
+    """``frame_planes(frames, formats)[0]``: the ``sdm_frame`` list alone, as (ptr, width, height, stride_bytes, format) tuples.  A
+    planar tensor's 5-tuple does not carry its plane distance; the calls that take ``frames=`` use ``frame_planes``."""
+    return frame_planes(frames, formats)[0]
+
+
+def _one_planar_name(formats):
+    """The planar name that makes ONE bare 3 x H x W tensor one frame -- given as a name or as a list of that one name -- or None."""
+    if isinstance(formats, (list, tuple)) and len(formats) == 1:
+        formats = formats[0]
+    return formats if isinstance(formats, (str, int)) and _is_planar_name(formats) else None
+
+
+def frame_planes(frames, formats=None, chroma=None):
+    """(descriptors, planes): the ``sdm_frame`` list of ``frames`` as (ptr, width, height, stride_bytes, format) tuples and, per frame,
+    the address of its SECOND PLANE or None (the default: directly behind plane 0) -- what the library's ``chroma`` / ``dst_chroma`` /
+    ``planes`` arrays take.  Pure host code on duck-typed objects (``data_ptr()``, ``shape``, ``stride()``, ``dtype``): no device, no
+    torch needed.
     ``frames``: a list whose members are uint8 tensors -- H x W (gray), H x W x 3 ("bgr", the default, or "rgb"), H x W x 4 ("bgra",
     the default, or "rgba") -- or ready (ptr, w, h, stride, format) tuples (NV12 luma, foreign allocators), which pass through
     unchanged but for a format given by name; or ONE stacked tensor n x H x W [x C].  A tensor only needs stride(-1) == 1 and a pixel
     stride of C: the row stride is free, so views into larger frames work.  ``formats``: None, one name for all tensors, or one per
-    frame (None entries = the default)."""
+    frame (None entries = the default).
+    A 3 x H x W uint8 tensor is a planar colour frame ONLY when ``formats`` names it "bgr_planar" or "rgb_planar": it needs
+    stride(2) == 1, the row stride and the channel stride are free (regions x[:, 100:580, 200:840], frames of an n x 3 x H x W batch,
+    channel-reversed views with a negative stride), and its second plane is data_ptr() + stride(0) -- None when that is the default
+    height * stride_bytes.  One stacked n x 3 x H x W tensor with a planar name splits along dimension 0; one bare 3 x H x W tensor
+    with a planar name (or a list of that one name) is one frame.  ``chroma``: None or one entry per frame -- a device pointer, a
+    uint8 tensor or None --, the second plane of a (ptr, w, h, stride, "nv12" | "bgr_planar" | "rgb_planar") tuple; an entry given for
+    a planar tensor replaces the one computed from its strides.  Without a planar name everything is as ``frame_descriptors`` always
+    was, refusals included."""
     if _is_tensor(frames):
         shape, stride = tuple(int(v) for v in frames.shape), tuple(int(v) for v in frames.stride())
         if len(shape) not in (3, 4):
-            raise ValueError("a stacked tensor is n x H x W or n x H x W x C")
+            raise ValueError("a stacked tensor is n x H x W, n x H x W x C or -- named planar -- n x 3 x H x W")
         _check_u8(frames)
         base = int(frames.data_ptr())
-        items = [("t", base + i * stride[0], shape[1:], stride[1:]) for i in range(shape[0])]
+        if len(shape) == 3 and _one_planar_name(formats) is not None:
+            items = [("t", base, shape, stride)]                 # (one 3 x H x W frame named planar, not a stack of three)
+        else:
+            items = [("t", base + i * stride[0], shape[1:], stride[1:]) for i in range(shape[0])]
     else:
         items = []
         for f in frames:
@@ -271,14 +323,32 @@ def frame_descriptors(frames, formats=None):
         formats = [formats] * len(items)
     if len(formats) != len(items):
         raise ValueError("one format per frame expected")
-    out = []
+    if chroma is not None and len(chroma) != len(items):
+        raise ValueError("one chroma entry (or None) per frame expected")
+    # (a second plane is stored only where there is one, at the index of the descriptor being appended)
+    out, planes = [], [None] * len(items)
+    planar = {fmt for fmt in set(formats) if _is_planar_name(fmt)}
     for it, fmt in zip(items, formats):
         if it[0] == "d":
             ptr, w, h, st, code = it[1]
             out.append((int(ptr), int(w), int(h), int(st), _frame_format(code)))
+        elif planar and fmt in planar:
+            d, planes[len(out)] = _planar_tensor_frame(it[1], it[2], it[3], fmt)
+            out.append(d)
         else:
             out.append(_tensor_frame(it[1], it[2], it[3], fmt))
-    return out
+    if chroma is not None:
+        for i, u in enumerate(chroma):
+            if u is not None:
+                planes[i] = int(u.data_ptr()) if _is_tensor(u) else int(u)
+    return out, planes
+
+
+def planes_array(planes):
+    """The c_void_p array of ``frame_planes``' second planes, or None when every entry is the default."""
+    if planes.count(None) == len(planes):
+        return None
+    return (ctypes.c_void_p * len(planes))(*planes)
 
 
 def _check_u8(t):
@@ -443,6 +513,7 @@ def lib() -> ctypes.CDLL:
                                       c_void_p, c_void_p, c_int_p],
             "sdm_sweep_get_regressor": [c_void_p, c_int, c_float_p],
             "sdm_set_frames_device": [c_void_p, ctypes.POINTER(SdmFrame), c_int, c_int],
+            "sdm_set_frames_device_planes": [c_void_p, ctypes.POINTER(SdmFrame), c_void_p, c_int, c_int],
             "sdm_debug_download_image": [c_void_p, c_int, c_void_p],
             "sdm_upright_configure": [c_void_p, c_int, c_int],
             "sdm_detect_batch_upright": [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p],

@@ -67,6 +67,7 @@ ALIGN_HD void align_area_add(const uint8_t* p, int w, int h, int stride, const A
 #define ALIGN_AREA_BGR  1      // 3 bytes per pixel
 #define ALIGN_AREA_BGRA 2      // 4 bytes per pixel, the fourth never read
 #define ALIGN_AREA_NV12 3
+#define ALIGN_AREA_PLANAR 4    // three planes of 1 byte per pixel, r.pd apart
 
 // the sums over the S x S sub-samples of up to 4 consecutive crop pixels (row i, columns j0 ... j0 + npx - 1): acc[k] is (g, -, -),
 // (byte 0, 1, 2) or (Y, U, V); ok[k] turns false when one of pixel k's sub-samples is refused by the 2^20 rule
@@ -96,6 +97,10 @@ ALIGN_HD void align_area_sums(const AlignRow& r, int i, int j0, int npx, int S, 
                     align_area_add<3, 3, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
                 } else if constexpr (KIND == ALIGN_AREA_BGRA) {
                     align_area_add<4, 3, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
+                } else if constexpr (KIND == ALIGN_AREA_PLANAR) {
+                    align_area_add<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
+                    align_area_add<1, 1, WIDE, 0u>(r.p0 + r.pd, r.w, r.h, r.stride, q, acc[k] + 1);
+                    align_area_add<1, 1, WIDE, 0u>(r.p0 + r.pd + r.pd, r.w, r.h, r.stride, q, acc[k] + 2);
                 } else {
                     align_area_add<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
                     AlignPos qc;
@@ -121,6 +126,7 @@ ALIGN_HD void align_area_segment(const AlignRow& r, int i, int j0, int npx, int 
     case SDM_FRAME_GRAY: align_area_sums<ALIGN_AREA_GRAY, WIDE>(r, i, j0, npx, S, acc, ok); break;
     case SDM_FRAME_BGR: case SDM_FRAME_RGB: align_area_sums<ALIGN_AREA_BGR, WIDE>(r, i, j0, npx, S, acc, ok); break;
     case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: align_area_sums<ALIGN_AREA_BGRA, WIDE>(r, i, j0, npx, S, acc, ok); break;
+    case SDM_FRAME_BGR_PLANAR: case SDM_FRAME_RGB_PLANAR: align_area_sums<ALIGN_AREA_PLANAR, WIDE>(r, i, j0, npx, S, acc, ok); break;
     default: align_area_sums<ALIGN_AREA_NV12, WIDE>(r, i, j0, npx, S, acc, ok); break;
     }
     const uint32_t n = (uint32_t)(S * S), rcp = align_area_reciprocal(n);
@@ -135,7 +141,7 @@ ALIGN_HD void align_area_segment(const AlignRow& r, int i, int j0, int npx, int 
 #pragma unroll
             for (int c = 0; c < 3; ++c) a[c] = align_area_average(acc[k][c], n, rcp);
             if (r.format == SDM_FRAME_NV12) align_nv12_to_bgr(a[0], a[1], a[2], px[k]);
-            else if (r.format == SDM_FRAME_RGB || r.format == SDM_FRAME_RGBA) { px[k][0] = a[2]; px[k][1] = a[1]; px[k][2] = a[0]; }
+            else if (align_red_first(r.format)) { px[k][0] = a[2]; px[k][1] = a[1]; px[k][2] = a[0]; }
             else { px[k][0] = a[0]; px[k][1] = a[1]; px[k][2] = a[2]; }
         }
     }

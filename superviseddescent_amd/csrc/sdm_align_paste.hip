@@ -66,8 +66,9 @@ __global__ __launch_bounds__(PASTE_PREPARE_BLOCK) void paste_area_prepare_kernel
     faces[n].flags = r.flags;
 }
 
-// (area_rows is a parameter of <true, false> too, null there)
-template <bool NV12, bool AREA>
+// (area_rows is a parameter of <true, false> too, null there).  PLANAR: the frame list holds a planar colour frame -- only then is the
+// planar case of paste_load / paste_store in the kernel's code, so the lists of the other formats run the text they always ran
+template <bool NV12, bool AREA, bool PLANAR>
 __global__ __launch_bounds__(PASTE_BLOCK) void paste_kernel_t(const PasteFrameDev* __restrict__ frames, PasteOpt<NV12, uint8_t* const* __restrict__> chroma,
                                                               const PasteRow* __restrict__ rows,
                                                               PasteOpt<NV12 || AREA, const PasteAreaRow* __restrict__> area_rows,
@@ -93,8 +94,8 @@ __global__ __launch_bounds__(PASTE_BLOCK) void paste_kernel_t(const PasteFrameDe
         for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
             const int X = r.x0 + paste_tile_x(t, tx) + lx, Y = r.y0 + paste_tile_y(t, tx) + ly;
             if (X < r.x1 && Y < r.y1) {
-                if constexpr (AREA) paste_area_pixel(f, rows, area_rows, list, k, c, X, Y);
-                else paste_pixel(f, rows, list, k, c, X, Y);
+                if constexpr (AREA) paste_area_pixel<PLANAR>(f, rows, area_rows, list, k, c, X, Y);
+                else paste_pixel<PLANAR>(f, rows, list, k, c, X, Y);
             }
         }
         return;
@@ -130,16 +131,24 @@ void sdm_launch_paste_area_prepare(AlignFace* faces, const int* frame_of_row, co
                        0, s, faces, frame_of_row, frames, N, cw, ch, fitted ? 1 : 0, area, rows, area_rows, samples);
 }
 
-void sdm_launch_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
-                      const int* entry_of_row, int N, const PasteCropDev& crop, hipStream_t s)
+template <bool PLANAR>
+static void launch_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
+                         const int* entry_of_row, int N, const PasteCropDev& crop, hipStream_t s)
 {
     const dim3 grid((unsigned)N, (unsigned)paste_groups(crop)), block(PASTE_BLOCK);
     if (chroma && area_rows)
-        hipLaunchKernelGGL((paste_kernel_t<true, true>), grid, block, 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
+        hipLaunchKernelGGL((paste_kernel_t<true, true, PLANAR>), grid, block, 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
     else if (chroma)
-        hipLaunchKernelGGL((paste_kernel_t<true, false>), grid, block, 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
+        hipLaunchKernelGGL((paste_kernel_t<true, false, PLANAR>), grid, block, 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
     else if (area_rows)
-        hipLaunchKernelGGL((paste_kernel_t<false, true>), grid, block, 0, s, frames, PasteNone{}, rows, area_rows, list, entry_of_row, crop);
+        hipLaunchKernelGGL((paste_kernel_t<false, true, PLANAR>), grid, block, 0, s, frames, PasteNone{}, rows, area_rows, list, entry_of_row, crop);
     else
-        hipLaunchKernelGGL((paste_kernel_t<false, false>), grid, block, 0, s, frames, PasteNone{}, rows, PasteNone{}, list, entry_of_row, crop);
+        hipLaunchKernelGGL((paste_kernel_t<false, false, PLANAR>), grid, block, 0, s, frames, PasteNone{}, rows, PasteNone{}, list, entry_of_row, crop);
+}
+
+void sdm_launch_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
+                      const int* entry_of_row, int N, const PasteCropDev& crop, bool planar, hipStream_t s)
+{
+    if (planar) launch_paste<true>(frames, chroma, rows, area_rows, list, entry_of_row, N, crop, s);
+    else launch_paste<false>(frames, chroma, rows, area_rows, list, entry_of_row, N, crop, s);
 }

@@ -133,10 +133,11 @@ ALIGN_HD void paste_taps(const PasteRigidArea& p, const PasteCropDev& c, int n, 
 }
 
 // paste_pixel of the filtered paste
+template <bool PLANAR = true>
 ALIGN_HD void paste_area_pixel(const PasteFrameDev& f, const PasteRow* rows, const PasteAreaRow* area, const int* list, int k,
                                const PasteCropDev& c, int X, int Y)
 {
     AlignPos q;
     const int n = list[k];
-    if (paste_area_holds(rows[n], area[n], c.cw, c.ch, X, Y, q)) paste_owned(f, PasteRigidArea{rows, area}, list, k, c, X, Y, q);
+    if (paste_area_holds(rows[n], area[n], c.cw, c.ch, X, Y, q)) paste_owned<PLANAR>(f, PasteRigidArea{rows, area}, list, k, c, X, Y, q);
 }

@@ -94,8 +94,9 @@ ALIGN_HD void paste_taps(const PasteRigid&, const PasteCropDev& c, int n, int, i
 }
 
 // Frame pixel (X, Y) as seen by entry k of its frame's row list: in that row's footprint, the ownership rule (paste_owned); else nothing
+template <bool PLANAR = true>
 ALIGN_HD void paste_pixel(const PasteFrameDev& f, const PasteRow* rows, const int* list, int k, const PasteCropDev& c, int X, int Y)
 {
     AlignPos q;
-    if (paste_footprint(rows[list[k]], c.cw, c.ch, X, Y, q)) paste_owned(f, PasteRigid{rows}, list, k, c, X, Y, q);
+    if (paste_footprint(rows[list[k]], c.cw, c.ch, X, Y, q)) paste_owned<PLANAR>(f, PasteRigid{rows}, list, k, c, X, Y, q);
 }

@@ -34,7 +34,12 @@ struct AlignRow {
     int format;                 // SDM_FRAME_*
     const uint8_t* p0;          // plane 0 (gray, Y or interleaved pixels)
     const uint8_t* p1;          // NV12: the interleaved UV plane
+    long long pd;               // planar colour: bytes from plane c to plane c + 1, of any sign
 };
+
+// SDM_FRAME_BGR_PLANAR | SDM_FRAME_RGB_PLANAR: three planes of one byte per pixel, plane c at p0 + c * pd
+ALIGN_HD bool align_planar(int format) { return format == SDM_FRAME_BGR_PLANAR || format == SDM_FRAME_RGB_PLANAR; }
+ALIGN_HD bool align_red_first(int format) { return format == SDM_FRAME_RGB || format == SDM_FRAME_RGBA || format == SDM_FRAME_RGB_PLANAR; }
 
 struct AlignPos { int x0, fx, y0, fy; };
 
@@ -178,6 +183,19 @@ ALIGN_HD void align_fetch_segment(const AlignRow& r, const float sx[4], const fl
         for (int k = 0; k < 4; ++k)
             if (ok[k]) align_bilinear<4, 3, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q[k], px[k]);
         break;
+    case SDM_FRAME_BGR_PLANAR: case SDM_FRAME_RGB_PLANAR: {
+        // the plane distance goes on the pointer in 64 bits; the offsets inside each plane are a one-byte format's
+        const uint8_t* const pl1 = r.p0 + r.pd;
+        const uint8_t* const pl2 = pl1 + r.pd;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ok[k]) {
+                align_bilinear<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q[k], px[k]);
+                align_bilinear<1, 1, WIDE, 0u>(pl1, r.w, r.h, r.stride, q[k], px[k] + 1);
+                align_bilinear<1, 1, WIDE, 0u>(pl2, r.w, r.h, r.stride, q[k], px[k] + 2);
+            }
+        break;
+    }
     default: {   // SDM_FRAME_NV12
         const int cw = (r.w + 1) >> 1, ch = (r.h + 1) >> 1;
 #pragma unroll
@@ -193,7 +211,7 @@ ALIGN_HD void align_fetch_segment(const AlignRow& r, const float sx[4], const fl
         break;
     }
     }
-    if (r.format == SDM_FRAME_RGB || r.format == SDM_FRAME_RGBA) {          // byte 0 is R: (B, G, R) by byte position
+    if (align_red_first(r.format)) {                                        // byte 0 / plane 0 is R: (B, G, R) by byte position
 #pragma unroll
         for (int k = 0; k < 4; ++k) { const uint32_t t = px[k][0]; px[k][0] = px[k][2]; px[k][2] = t; }
     }
@@ -218,7 +236,8 @@ ALIGN_HD void align_segment(const AlignRow& r, int i, int j0, int npx, uint32_t 
     align_fetch_segment<WIDE>(r, sx, sy, on, px);
 }
 
-// output channel c of CH from a warped (B, G, R); weigh: the source is BGR / RGB / BGRA / RGBA (a gray or luma-only value passes)
+// output channel c of CH from a warped (B, G, R); weigh: the source is BGR / RGB / BGRA / RGBA or planar colour (a gray or luma-only
+// value passes)
 template <int CH>
 ALIGN_HD uint32_t align_channel(const uint32_t bgr[3], int c, bool weigh, int order, int wb, int wg, int wr, int shift)
 {

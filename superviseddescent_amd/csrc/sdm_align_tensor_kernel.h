@@ -92,11 +92,12 @@ __global__ __launch_bounds__(ALIGN_T_BLOCK) void align_tensor_kernel(const uint8
     if (frames) {
         const AlignFrameDev fr = frames[img_idx ? img_idx[n] : n];
         r.p0 = fr.p0; r.p1 = fr.p1; r.stride = fr.stride; r.cstride = fr.cstride; r.format = fr.format;
+        r.pd = (long long)((uintptr_t)fr.p1 - (uintptr_t)fr.p0);      // (a planar frame's p1 is its second plane; not read otherwise)
     } else {
-        r.p0 = base + f.off; r.p1 = nullptr; r.stride = f.stride; r.cstride = 0; r.format = src_format;
+        r.p0 = base + f.off; r.p1 = nullptr; r.stride = f.stride; r.cstride = 0; r.format = src_format; r.pd = 0;
     }
     if (CH == 1 && r.format == SDM_FRAME_NV12) r.format = SDM_FRAME_GRAY;        // Y as it is: the chroma plane is not read
-    const bool weigh = r.format >= SDM_FRAME_BGR && r.format <= SDM_FRAME_RGBA;
+    const bool weigh = (r.format >= SDM_FRAME_BGR && r.format <= SDM_FRAME_RGBA) || align_planar(r.format);
     // offsets inside a plane are 32-bit when rows * stride fit 31 bits
     const bool narrow = (long long)r.h * r.stride <= (long long)INT_MAX &&
                         (r.format != SDM_FRAME_NV12 || (long long)((r.h + 1) >> 1) * r.cstride <= (long long)INT_MAX);

@@ -252,7 +252,12 @@ int sdm_align_set_source_frames(sdm_ctx* c, const sdm_frame* frames, const void*
             d.p1 = uv ? (const uint8_t*)uv : (const uint8_t*)f.data + (size_t)f.height * (size_t)f.stride_bytes;
             d.cstride = f.stride_bytes;
         }
-        const int kind = f.format == SDM_FRAME_NV12 ? 0 : bpp;
+        if (frame_planar(f.format)) {
+            long long D;
+            if ((rc = frame_plane_distance(i, f, chroma ? chroma[i] : nullptr, D))) return rc;
+            d.p1 = (const uint8_t*)f.data + D;
+        }
+        const int kind = f.format == SDM_FRAME_NV12 || frame_planar(f.format) ? 0 : bpp;
         bpp_all = bpp_all < 0 ? kind : (bpp_all == kind ? kind : 0);
         if (!lowest || d.p0 < lowest) lowest = d.p0;
     }
@@ -276,7 +281,7 @@ int sdm_align_crops(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out
     sdm_ctx::Align& a = c->align;
     const bool external = a.base != nullptr, list = !a.fr.empty();
     if (list && a.fr_bpp == 0)
-        return fail(SDM_ERR_INVALID, "the frame-list source holds NV12 frames or frames of different pixel sizes: use sdm_align_crops_tensor");
+        return fail(SDM_ERR_INVALID, "the frame-list source holds NV12 or planar frames or frames of different pixel sizes: use sdm_align_crops_tensor");
     const int C = external ? a.C : list ? a.fr_bpp : 1;
     if (!out) return fail(SDM_ERR_INVALID, "no output");
     if (out_on_device && ((uintptr_t)out % (C == 4 ? 16 : 4)) != 0)

@@ -7,11 +7,20 @@
 int sdm_capi::frame_bpp(int format)
 {
     switch (format) {
-    case SDM_FRAME_GRAY: case SDM_FRAME_NV12: return 1;
+    case SDM_FRAME_GRAY: case SDM_FRAME_NV12: case SDM_FRAME_BGR_PLANAR: case SDM_FRAME_RGB_PLANAR: return 1;
     case SDM_FRAME_BGR: case SDM_FRAME_RGB: return 3;
     case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return 4;
     default: return 0;
     }
+}
+
+bool sdm_capi::frame_planar(int format) { return format == SDM_FRAME_BGR_PLANAR || format == SDM_FRAME_RGB_PLANAR; }
+
+int sdm_capi::frame_plane_distance(int i, const sdm_frame& f, const void* second, long long& D)
+{
+    D = second ? (long long)((intptr_t)second - (intptr_t)f.data) : (long long)f.height * f.stride_bytes;
+    if (D == 0) return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": the second plane of a planar frame lies on the first");
+    return SDM_OK;
 }
 
 int sdm_capi::check_frame(int i, const sdm_frame& f, bool allow_nv12)
@@ -26,9 +35,8 @@ int sdm_capi::check_frame(int i, const sdm_frame& f, bool allow_nv12)
     return SDM_OK;
 }
 
-extern "C" {
-
-int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_shift)
+// sdm_set_frames_device (planes null) and sdm_set_frames_device_planes
+static int set_frames_device(sdm_ctx* c, const sdm_frame* frames, const void* const* planes, int n, int gray_shift)
 {
     if (!c || !frames || n < 1) return fail(SDM_ERR_INVALID, "bad frame list");
     if (gray_shift != 14 && gray_shift != 15) return fail(SDM_ERR_INVALID, "gray_shift must be 14 (OpenCV 2.4 - 3.x) or 15");
@@ -40,11 +48,12 @@ int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_s
         const sdm_frame& f = frames[i];
         if ((rc = check_frame(i, f, true))) return rc;
         const int bpp = frame_bpp(f.format);
-        if (bpp == 1) continue;
+        if (bpp == 1 && !frame_planar(f.format)) continue;
         FrameConvDev d{};
+        if (frame_planar(f.format) && (rc = frame_plane_distance(i, f, planes ? planes[i] : nullptr, d.plane))) return rc;
         d.src = (const uint8_t*)f.data; d.dst_off = owned; d.w = f.width; d.h = f.height; d.pitch = f.stride_bytes;
         d.gstride = sdm_frames_gray_stride(f.width); d.bpp = bpp;
-        d.swap_rb = f.format == SDM_FRAME_RGB || f.format == SDM_FRAME_RGBA;
+        d.swap_rb = f.format == SDM_FRAME_RGB || f.format == SDM_FRAME_RGBA || f.format == SDM_FRAME_RGB_PLANAR;
         d.block0 = (unsigned)blocks;
         // (a lane numbers its chunk within the frame in 32 bits, the launch its workgroups in 31)
         if (sdm_frames_blocks(f.width, f.height) * 256 > (long long)INT_MAX || blocks + sdm_frames_blocks(f.width, f.height) > (long long)INT_MAX)
@@ -64,7 +73,7 @@ int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_s
     for (int i = 0, k = 0; i < n; ++i) {
         const sdm_frame& f = frames[i];
         vw[i] = f.width; vh[i] = f.height;
-        if (frame_bpp(f.format) == 1) { addr[i] = (const uint8_t*)f.data; vs[i] = f.stride_bytes; }
+        if (frame_bpp(f.format) == 1 && !frame_planar(f.format)) { addr[i] = (const uint8_t*)f.data; vs[i] = f.stride_bytes; }
         else { addr[i] = c->frames.gray.p + conv[k].dst_off; vs[i] = conv[k].gstride; ++k; }
         narrow = narrow || image_needs_generic(f.width, f.height, vs[i]);      // (the rule of every image entry point)
     }
@@ -87,6 +96,18 @@ int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_s
     c->img_w_host.swap(vw); c->img_h_host.swap(vh);
     c->narrow_images = narrow;
     return SDM_OK;
+}
+
+extern "C" {
+
+int sdm_set_frames_device(sdm_ctx* c, const sdm_frame* frames, int n, int gray_shift)
+{
+    return set_frames_device(c, frames, nullptr, n, gray_shift);
+}
+
+int sdm_set_frames_device_planes(sdm_ctx* c, const sdm_frame* frames, const void* const* planes, int n, int gray_shift)
+{
+    return set_frames_device(c, frames, planes, n, gray_shift);
 }
 
 int sdm_debug_download_image(sdm_ctx* c, int i, uint8_t* out)

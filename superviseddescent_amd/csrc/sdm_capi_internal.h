@@ -412,6 +412,10 @@ int upright_roll_cs(float roll_deg, double* cs);
 // frames refuses of frame i: format, null pointer, width / height, stride -- with allow_nv12 false (the pastes) an NV12 frame first
 int frame_bpp(int format);
 int check_frame(int i, const sdm_frame& frame, bool allow_nv12);
+// SDM_FRAME_BGR_PLANAR | SDM_FRAME_RGB_PLANAR (frame_bpp: 1, the bytes per pixel of a plane)
+bool frame_planar(int format);
+// D of a planar frame: second - data, or height * stride_bytes when second is null; 0 is refused
+int frame_plane_distance(int i, const sdm_frame& frame, const void* second, long long& D);
 // (sdm_capi_align.hip) the checks and the element stage's constants that sdm_align_crops_tensor and sdm_warp_crops_tensor share: the
 // specification, the output pointer, that the crop source covers every row's image with that image's size, the source itself and the
 // landmark subset of a template

@@ -15,7 +15,8 @@
 namespace {
 
 // what both forms refuse of the tensor, the opacity maps and the destination frames
-int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, bool nv12 = false)
+int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm_frame* frames, int n_frames, bool nv12 = false,
+                     void* const* dst_chroma = nullptr)
 {
     if (!in_dev) return fail(SDM_ERR_INVALID, "no tensor");
     if ((uintptr_t)in_dev % 16 != 0) return fail(SDM_ERR_INVALID, "the tensor must be 16-byte aligned");
@@ -28,6 +29,9 @@ int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm
     for (int i = 0; i < n_frames; ++i)                               // (the UV plane's row: (width + 1) / 2 byte pairs)
         if (frames[i].format == SDM_FRAME_NV12 && (long long)frames[i].stride_bytes < 2LL * ((frames[i].width + 1) / 2))
             return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < 2 * ((width + 1) / 2) of an NV12 frame");
+    long long D;
+    for (int i = 0; i < n_frames; ++i)                               // (a planar frame's second plane: not on the first)
+        if (frame_planar(frames[i].format) && (rc = frame_plane_distance(i, frames[i], dst_chroma ? dst_chroma[i] : nullptr, D))) return rc;
     return SDM_OK;
 }
 
@@ -59,13 +63,15 @@ int paste_frames_of_index(const int* image_index, int n_rows, int n_frames, std:
 
 // the device tables of a call in align.paste_tab: the frame table, the row -> frame index, the rows of every frame in ascending order,
 // and every row's place among them (enqueued; nothing waits: `blob`, the host side of the copy, lives until the call's synchronise);
-// for the NV12 calls the frames' UV planes behind them, 8-byte aligned -- an array of its own: the frame table is what it was
+// for the NV12 calls the frames' UV planes behind them, 8-byte aligned -- an array of its own; a planar frame's plane distance (from
+// its dst_chroma entry, the second plane, or the default) is in the frame table
 struct PasteTables {
     const PasteFrameDev* frames;
     uint8_t* const* chroma;
     const int* of_row;
     const int* list;
     const int* entry;
+    bool planar;                    // a planar colour frame is among the frames: the kernels' instances with that case
     std::vector<unsigned char> blob;
 };
 
@@ -78,6 +84,7 @@ int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_fra
     const size_t bytes = nv12 ? uv_at + (size_t)n_frames * sizeof(uint8_t*) : tab_bytes + (size_t)3 * N * sizeof(int);
     std::vector<unsigned char>& blob = out.blob;
     blob.assign(bytes, 0);
+    out.planar = false;
     PasteFrameDev* tab = (PasteFrameDev*)blob.data();
     int* of_row = (int*)(blob.data() + tab_bytes);
     int* list = of_row + N;
@@ -91,6 +98,9 @@ int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_fra
         d.p = (uint8_t*)const_cast<void*>(f.data);                 // (sdm_frame is the read-only view of the crop calls: written here)
         d.stride = f.stride_bytes; d.w = f.width; d.h = f.height; d.format = f.format;
         d.row_begin = count[i]; d.row_end = count[(size_t)i + 1]; d.pad = 0;
+        d.plane = 0;
+        out.planar = out.planar || frame_planar(f.format);
+        if (frame_planar(f.format)) frame_plane_distance(i, f, dst_chroma ? dst_chroma[i] : nullptr, d.plane);      // (checked: not 0)
     }
     if (nv12) {
         uint8_t** uv = (uint8_t**)(blob.data() + uv_at);
@@ -149,7 +159,7 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
         sdm_launch_paste_area_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, align_area_dev(filter), rows_dev, area_dev,
                                       (int*)(a.faces.p + N), c->stream);
     HIP_TRY(hipGetLastError());
-    sdm_launch_paste(tab.frames, tab.chroma, rows_dev, area_dev, tab.list, tab.entry, N, crop, c->stream);   // (tab.chroma: null unless nv12)
+    sdm_launch_paste(tab.frames, tab.chroma, rows_dev, area_dev, tab.list, tab.entry, N, crop, tab.planar, c->stream);   // (tab.chroma: null unless nv12)
     HIP_TRY(hipGetLastError());
     if (samples_host && !filter) {                                                      // (an NV12 call without a filter: plain bilinear)
         for (int r = 0; r < N; ++r) samples_host[r] = 1;
@@ -195,7 +205,7 @@ int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const 
         sdm_launch_warp_paste_area_counts(rows_dev, tris_dev, N, T, align_area_dev(filter), counts_dev, samples_dev, c->stream);
         HIP_TRY(hipGetLastError());
     }
-    sdm_launch_warp_paste(tab.frames, tab.chroma, rows_dev, tris_dev, counts_dev, T, tab.list, tab.entry, N, w.labels.p, crop, c->stream);   // (tab.chroma: null unless nv12)
+    sdm_launch_warp_paste(tab.frames, tab.chroma, rows_dev, tris_dev, counts_dev, T, tab.list, tab.entry, N, w.labels.p, crop, tab.planar, c->stream);   // (tab.chroma: null unless nv12)
     HIP_TRY(hipGetLastError());
     // the matrices and the rows' records (a filtered call: with the counts behind them, in the same copy), one synchronise
     if (!filter) samples_host = nullptr;
@@ -220,7 +230,7 @@ int paste_fit_call(sdm_ctx* c, const int* lm, const float* tmpl, int K, int cw, 
     if (!c) return fail(SDM_ERR_INVALID, "null context");
     int rc;
     if ((rc = align_check_call(c, lm, tmpl, K, cw, ch)) || (rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
-        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)) || (rc = align_check_rows(c)))
+        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12, dst_chroma)) || (rc = align_check_rows(c)))
         return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
@@ -243,7 +253,7 @@ int paste_at_call(sdm_ctx* c, const float* matrices_host, const int* image_index
     if (cw < 1 || cw > 1024 || ch < 1 || ch > 1024) return fail(SDM_ERR_INVALID, "crop width and height must be in [1, 1024]");
     int rc;
     if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
-        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)))
+        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12, dst_chroma)))
         return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;
@@ -279,7 +289,7 @@ int warp_paste_fit_call(sdm_ctx* c, const sdm_align_tensor* spec, const void* in
     if ((rc = warp_paste_check_mesh(c))) return rc;
     if (c->N < 1) return fail(SDM_ERR_INVALID, "no current rows (sdm_set_x, sdm_detect_batch or sdm_track_step first)");
     if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
-        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)) || (rc = align_check_rows(c)))
+        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12, dst_chroma)) || (rc = align_check_rows(c)))
         return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_rows(c, frames, n_frames, frame_of_row))) return rc;
@@ -299,7 +309,7 @@ int warp_paste_at_call(sdm_ctx* c, const float* points_host, const int* image_in
     if (!points_host) return fail(SDM_ERR_INVALID, "no points");
     if (n_rows < 1) return fail(SDM_ERR_INVALID, "n_rows must be >= 1");
     if ((rc = align_check_spec(spec)) || (filtered && (rc = align_check_filter(filter))) ||
-        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12)))
+        (rc = paste_check_args(in_dev, paste, frames, n_frames, nv12, dst_chroma)))
         return rc;
     std::vector<int> frame_of_row;
     if ((rc = paste_frames_of_index(image_index, n_rows, n_frames, frame_of_row))) return rc;

@@ -1,7 +1,8 @@
 // sdm_frames.hip -- colour frames that are already on the device -> the context's gray images (sdm_set_frames_device, include/sdm.h).
-// One launch converts every colour frame of a call: interleaved BGR / RGB / BGRA / RGBA of any size, pitch and pointer alignment
-// into gray images the context owns, with the arithmetic of bgr2gray_kernel (sdm_apply.hip; cv::cvtColor's fixed-point weights,
-// adaptive_vlhog.hpp:114-120).  The source is only read.
+// One launch converts every colour frame of a call: interleaved BGR / RGB / BGRA / RGBA and planar BGR / RGB (three planes of one byte
+// per pixel, any signed distance apart) of any size, pitch and pointer alignment into gray images the context owns, with the
+// arithmetic of bgr2gray_kernel (sdm_apply.hip; cv::cvtColor's fixed-point weights, adaptive_vlhog.hpp:114-120).  The source is
+// only read.
 #include "sdm_kernels.h"
 
 namespace {
@@ -43,6 +44,8 @@ __device__ __forceinline__ unsigned gray4_of_16(u32x4 q, int c0, int c1, int c2,
 //               (BGRA) 16-byte loads -- a chunk starts 48 c or 64 c bytes into its row, so it is as aligned as the row is
 //   byte path   the last, incomplete chunk of a row, and every chunk of a row that does not start on a 4-byte boundary: one byte
 //               load per channel, only of pixels that exist
+// A planar frame's chunk is 16 bytes of each plane: one 16-byte load per plane when the chunk is complete and the row start and the
+// plane distance are multiples of 4 (so all three row starts are 4-byte aligned), the byte path otherwise.
 // Either way the lane stores ONE 16-byte word: the owned gray images start on 16-byte boundaries with a row stride that is a
 // multiple of 16 (sdm_frames_gray_stride), so the store is aligned and the bytes behind the last pixel of a row land in that
 // row's own padding (written as zero, never read as pixels: the pixel kernels take w and the stride from the image table).
@@ -65,7 +68,23 @@ __global__ void __launch_bounds__(256) frames_to_gray_kernel(const FrameConvDev*
     gbytes rowp = (gbytes)f.src + (long long)row * f.pitch;
     const int npx = min(16, f.w - (int)(c * 16u));
     u32x4 out = {0u, 0u, 0u, 0u};
-    if (npx == 16 && ((size_t)rowp & 3) == 0) {
+    if (f.bpp == 1) {
+        // planar: the chunk is 16 bytes of each plane, f.plane bytes apart (64-bit, any sign); as aligned as the three row starts are
+        gbytes p0 = rowp + (size_t)c * 16, p1 = p0 + f.plane, p2 = p1 + f.plane;
+        if (npx == 16 && (((size_t)rowp | (size_t)f.plane) & 3) == 0) {
+            const u32x4 a = ((const __attribute__((address_space(1))) Quad*)p0)->v, b = ((const __attribute__((address_space(1))) Quad*)p1)->v,
+                        d = ((const __attribute__((address_space(1))) Quad*)p2)->v;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int s = 8 * (k & 3);
+                out[k >> 2] |= gray_of((a[k >> 2] >> s) & 255u, (b[k >> 2] >> s) & 255u, (d[k >> 2] >> s) & 255u, c0, c1, c2, half, shift) << s;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k < npx) out[k >> 2] |= gray_of(p0[k], p1[k], p2[k], c0, c1, c2, half, shift) << (8 * (k & 3));
+        }
+    } else if (npx == 16 && ((size_t)rowp & 3) == 0) {
         if (f.bpp == 3) {
             const __attribute__((address_space(1))) Quad* q = (const __attribute__((address_space(1))) Quad*)(rowp + (size_t)c * 48);
             const u32x4 a = q[0].v, b = q[1].v, d = q[2].v;

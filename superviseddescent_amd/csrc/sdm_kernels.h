@@ -227,7 +227,8 @@ void sdm_launch_subtract_templates(float* feat, long long ldf, const float* tmpl
 void sdm_launch_bgr2gray(const uint8_t* bgr, uint8_t* gray, long long n_pixels, int shift, hipStream_t stream);
 
 // ---- colour frames on the device -> owned gray images (sdm_frames.hip; sdm_set_frames_device) ----
-// one colour frame of a call: interleaved u8 pixels of bpp = 3 or 4 bytes, byte 0 = blue (swap_rb 0) or red (swap_rb 1); its gray
+// one colour frame of a call: interleaved u8 pixels of bpp = 3 or 4 bytes, byte 0 = blue (swap_rb 0) or red (swap_rb 1), or -- bpp = 1 --
+// three planes of one byte per pixel, `plane` bytes apart (any sign), plane 0 = blue or red; its gray
 // image goes to gray + dst_off (a multiple of 16) with a row stride of gstride = sdm_frames_gray_stride(w) bytes; block0 = the first
 // workgroup of the frame in the launch (256 chunks of 16 pixels per workgroup, ascending over the table)
 struct FrameConvDev {
@@ -237,6 +238,7 @@ struct FrameConvDev {
     int bpp, swap_rb;
     unsigned block0;
     int pad_;
+    long long plane;
 };
 inline int sdm_frames_gray_stride(int w) { return (int)(((long long)w + 15) / 16 * 16); }
 inline long long sdm_frames_blocks(int w, int h) { return (((long long)w + 15) / 16 * h + 255) / 256; }
@@ -439,7 +441,7 @@ void sdm_launch_align_warp(const uint8_t* img, const AlignFace* faces, int N, in
 
 // ---- crops as network input tensors (sdm_align_tensor.hip) ----
 // one frame of a frame-list crop source, used in place: plane 0 (Y, gray or the interleaved pixels), the interleaved UV plane of an
-// NV12 frame (null otherwise), their strides in bytes and the SDM_FRAME_* format
+// NV12 frame or the second plane of a planar colour frame (null otherwise), their strides in bytes and the SDM_FRAME_* format
 struct AlignFrameDev {
     const uint8_t* p0;
     const uint8_t* p1;

@@ -37,11 +37,12 @@ void sdm_launch_paste_prepare(AlignFace* faces, const int* frame_of_row, const P
 // the filtered calls' prepare stage.  area: the filter; area_rows: N records out; samples: N ints out, S of every row
 void sdm_launch_paste_area_prepare(AlignFace* faces, const int* frame_of_row, const PasteFrameDev* frames, int N, int cw, int ch, bool fitted,
                                    const AlignAreaDev& area, PasteRow* rows, PasteAreaRow* area_rows, int* samples, hipStream_t s);
-// the paste behind either prepare stage: paste_kernel_t<chroma != null, area_rows != null>.  list: the rows of every frame, ascending
+// the paste behind either prepare stage: paste_kernel_t<chroma != null, area_rows != null, planar>; planar: the frame list holds a planar
+// colour frame (only those instances carry the planar case of the pixel's load and store).  list: the rows of every frame, ascending
 // (PasteFrameDev::row_begin / row_end); entry_of_row: where row n stands in it.  chroma: null -- no frame is NV12 --, or one UV plane
 // per frame (read for NV12 frames only); area_rows: null -- plain bilinear --, or the filtered prepare stage's records
 void sdm_launch_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
-                      const int* entry_of_row, int N, const PasteCropDev& crop, hipStream_t s);
+                      const int* entry_of_row, int N, const PasteCropDev& crop, bool planar, hipStream_t s);
 // x: N x 2L; lm: the mesh's K landmark indices; tri: T triangles; faces, matrices: the N records (their FOLDED bit is read) and the
 // N x T x 6 floats of sdm_launch_warp_fit; frame_of_row: N checked indices into frames.  rows: N records; tris: N x T records
 void sdm_launch_warp_paste_prepare(const float* x, int N, int L, const int* lm, int K, const WarpTri* tri, int T, const WarpFace* faces,
@@ -56,4 +57,4 @@ void sdm_launch_warp_paste_area_counts(const WarpPasteRow* rows, const WarpPaste
 // null: the filtered calls take a list that may mix NV12 and the per-pixel formats)
 void sdm_launch_warp_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris,
                            const uint16_t* counts, int T, const int* list, const int* entry_of_row, int N, const uint8_t* labels,
-                           const PasteCropDev& crop, hipStream_t s);
+                           const PasteCropDev& crop, bool planar, hipStream_t s);

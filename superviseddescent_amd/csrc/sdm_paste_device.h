@@ -20,7 +20,8 @@
 struct PasteFrameDev {
     uint8_t* p;
     long long stride;
-    int w, h, format;           // SDM_FRAME_GRAY ... SDM_FRAME_RGBA
+    long long plane;            // planar colour: bytes from plane c to plane c + 1, of any sign (0 otherwise)
+    int w, h, format;           // SDM_FRAME_GRAY ... SDM_FRAME_RGBA, SDM_FRAME_NV12 (the block path), SDM_FRAME_*_PLANAR
     int row_begin, row_end;
     int pad;
 };
@@ -145,21 +146,31 @@ ALIGN_HD uint32_t paste_blend(uint32_t a, uint32_t q, uint32_t o) { return (a * 
 // the colour bytes stored once, byte by byte, if any opacity was not 0 (paste_store).
 struct PastePixel {
     uint8_t* p;
+    long long pd;               // planar colour: colour byte b is p[b * pd]; 0: the bytes are p[0 ... nb - 1]
     uint32_t o[3];
     int nb;                     // colour bytes: 1 | 3 (the alpha byte is neither read nor written)
     bool swap, any;
 };
 
+// PLANAR false: an instance for frame lists that hold no planar frame -- the planar case is not in its code (the kernels choose at the
+// launch; the host programs and every caller that names nothing take the general text)
+template <bool PLANAR = true>
 ALIGN_HD void paste_load(const PasteFrameDev& f, int X, int Y, PastePixel& s)
 {
-    const int bpp = f.format == SDM_FRAME_GRAY ? 1 : (f.format == SDM_FRAME_BGR || f.format == SDM_FRAME_RGB) ? 3 : 4;
-    s.nb = bpp == 1 ? 1 : 3;
+    const bool planar = PLANAR && align_planar(f.format);
+    const int bpp = f.format == SDM_FRAME_GRAY || planar ? 1 : (f.format == SDM_FRAME_BGR || f.format == SDM_FRAME_RGB) ? 3 : 4;
+    s.nb = f.format == SDM_FRAME_GRAY ? 1 : 3;
     s.p = f.p + ((long long)Y * f.stride + (long long)X * bpp);
+    s.pd = planar ? f.plane : 0;
     s.o[0] = s.o[1] = s.o[2] = 0u;
+    if (planar) {                                                   // one byte of each plane
+        s.o[0] = s.p[0]; s.o[1] = s.p[s.pd]; s.o[2] = s.p[s.pd + s.pd];
+    } else {
 #pragma unroll
-    for (int b = 0; b < 3; ++b)
-        if (b < s.nb) s.o[b] = s.p[b];
-    s.swap = f.format == SDM_FRAME_RGB || f.format == SDM_FRAME_RGBA;
+        for (int b = 0; b < 3; ++b)
+            if (b < s.nb) s.o[b] = s.p[b];
+    }
+    s.swap = align_red_first(f.format);
     s.any = false;
 }
 
@@ -177,9 +188,14 @@ ALIGN_HD void paste_apply(const PasteCropDev& c, const uint32_t bgr[3], uint32_t
     }
 }
 
+template <bool PLANAR = true>
 ALIGN_HD void paste_store(const PastePixel& s)
 {
     if (!s.any) return;
+    if (PLANAR && s.pd != 0) {
+        s.p[0] = (uint8_t)s.o[0]; s.p[s.pd] = (uint8_t)s.o[1]; s.p[s.pd + s.pd] = (uint8_t)s.o[2];
+        return;
+    }
 #pragma unroll
     for (int b = 0; b < 3; ++b)
         if (b < s.nb) s.p[b] = (uint8_t)s.o[b];
@@ -190,7 +206,7 @@ ALIGN_HD void paste_store(const PastePixel& s)
 // that holds the pixel applied in order, the colour bytes stored once if any opacity was not 0.  list: the row lists.  Shape: the paste's
 // rows, with paste_holds(shape, n, crop, X, Y, q) -- row n's footprint holds the pixel, at q -- and paste_taps(shape, crop, n, X, Y, q,
 // bgr, a): row n's colour and opacity for the pixel (a == 0: the row leaves it alone)
-template <class Shape>
+template <bool PLANAR = true, class Shape>
 ALIGN_HD void paste_owned(const PasteFrameDev& f, const Shape& shape, const int* list, int k, const PasteCropDev& c, int X, int Y, AlignPos q)
 {
     for (int j = f.row_begin; j < k; ++j) {
@@ -198,7 +214,7 @@ ALIGN_HD void paste_owned(const PasteFrameDev& f, const Shape& shape, const int*
         if (paste_holds(shape, list[j], c, X, Y, qj)) return;
     }
     PastePixel s;
-    paste_load(f, X, Y, s);
+    paste_load<PLANAR>(f, X, Y, s);
     for (int j = k; j < f.row_end; ++j) {
         const int n = list[j];
         if (j > k && !paste_holds(shape, n, c, X, Y, q)) continue;
@@ -206,7 +222,7 @@ ALIGN_HD void paste_owned(const PasteFrameDev& f, const Shape& shape, const int*
         paste_taps(shape, c, n, X, Y, q, bgr, a);
         paste_apply(c, bgr, a, s);
     }
-    paste_store(s);
+    paste_store<PLANAR>(s);
 }
 
 // NV12 destinations (include/sdm.h, "Pasting crops back into NV12 frames").  The unit is the 2 x 2 block of luma pixels that share one

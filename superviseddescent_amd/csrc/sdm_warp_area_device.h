@@ -64,6 +64,10 @@ ALIGN_HD void warp_area_sums(const AlignRow& r, const WarpAreaRec* rec, const in
                     align_area_add<3, 3, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
                 } else if constexpr (KIND == ALIGN_AREA_BGRA) {
                     align_area_add<4, 3, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
+                } else if constexpr (KIND == ALIGN_AREA_PLANAR) {
+                    align_area_add<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
+                    align_area_add<1, 1, WIDE, 0u>(r.p0 + r.pd, r.w, r.h, r.stride, q, acc[k] + 1);
+                    align_area_add<1, 1, WIDE, 0u>(r.p0 + r.pd + r.pd, r.w, r.h, r.stride, q, acc[k] + 2);
                 } else {
                     align_area_add<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
                     AlignPos qc;
@@ -97,6 +101,7 @@ ALIGN_HD void warp_area_segment(const AlignRow& r, const WarpAreaRec* rec, const
     case SDM_FRAME_GRAY: warp_area_sums<ALIGN_AREA_GRAY, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
     case SDM_FRAME_BGR: case SDM_FRAME_RGB: warp_area_sums<ALIGN_AREA_BGR, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
     case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: warp_area_sums<ALIGN_AREA_BGRA, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
+    case SDM_FRAME_BGR_PLANAR: case SDM_FRAME_RGB_PLANAR: warp_area_sums<ALIGN_AREA_PLANAR, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
     default: warp_area_sums<ALIGN_AREA_NV12, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
     }
 #pragma unroll
@@ -111,7 +116,7 @@ ALIGN_HD void warp_area_segment(const AlignRow& r, const WarpAreaRec* rec, const
 #pragma unroll
             for (int c = 0; c < 3; ++c) a[c] = warp_area_average(acc[k][c], n, rcp);
             if (r.format == SDM_FRAME_NV12) align_nv12_to_bgr(a[0], a[1], a[2], px[k]);
-            else if (r.format == SDM_FRAME_RGB || r.format == SDM_FRAME_RGBA) { px[k][0] = a[2]; px[k][1] = a[1]; px[k][2] = a[0]; }
+            else if (align_red_first(r.format)) { px[k][0] = a[2]; px[k][1] = a[1]; px[k][2] = a[0]; }
             else { px[k][0] = a[0]; px[k][1] = a[1]; px[k][2] = a[2]; }
         }
     }

@@ -122,7 +122,8 @@ __global__ __launch_bounds__(WPASTE_COUNTS_BLOCK) void warp_paste_area_counts_ke
 }
 
 // (the PasteMesh is built where it is used: a named one ahead of the walk renumbers registers in <false, false>)
-template <bool NV12, bool AREA>
+// PLANAR: the frame list holds a planar colour frame (paste_kernel_t's rule, csrc/sdm_align_paste.hip)
+template <bool NV12, bool AREA, bool PLANAR>
 __global__ __launch_bounds__(PASTE_BLOCK) void warp_paste_kernel_t(const PasteFrameDev* __restrict__ frames,
                                                                     PasteOpt<NV12, uint8_t* const* __restrict__> chroma,
                                                                     const WarpPasteRow* __restrict__ rows, const WarpPasteTri* __restrict__ tris,
@@ -177,9 +178,9 @@ __global__ __launch_bounds__(PASTE_BLOCK) void warp_paste_kernel_t(const PasteFr
                 if constexpr (AREA) {
                     PasteMeshAreaOwn own{PasteMeshArea{PasteMesh{rows, tris, T, labels}, counts, -1}, n, 0xffffffffu, lds, lds_counts};
                     own.area.tri = mine;
-                    paste_owned(f, own, list, k, c, X, Y, q);
+                    paste_owned<PLANAR>(f, own, list, k, c, X, Y, q);
                 } else {
-                    paste_owned(f, PasteMesh{rows, tris, T, labels}, list, k, c, X, Y, q);
+                    paste_owned<PLANAR>(f, PasteMesh{rows, tris, T, labels}, list, k, c, X, Y, q);
                 }
             }
         }
@@ -254,17 +255,26 @@ void sdm_launch_warp_paste_area_counts(const WarpPasteRow* rows, const WarpPaste
                        dim3(WPASTE_COUNTS_BLOCK), 0, s, rows, tris, N, T, area, counts, samples);
 }
 
-void sdm_launch_warp_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris,
-                           const uint16_t* counts, int T, const int* list, const int* entry_of_row, int N, const uint8_t* labels,
-                           const PasteCropDev& crop, hipStream_t s)
+template <bool PLANAR>
+static void launch_warp_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris,
+                              const uint16_t* counts, int T, const int* list, const int* entry_of_row, int N, const uint8_t* labels,
+                              const PasteCropDev& crop, hipStream_t s)
 {
     const dim3 grid((unsigned)N, (unsigned)paste_groups(crop)), block(PASTE_BLOCK);
     if (counts)
-        hipLaunchKernelGGL((warp_paste_kernel_t<true, true>), grid, block, 0, s, frames, chroma, rows, tris, counts, T, list, entry_of_row, labels, crop);
+        hipLaunchKernelGGL((warp_paste_kernel_t<true, true, PLANAR>), grid, block, 0, s, frames, chroma, rows, tris, counts, T, list, entry_of_row, labels, crop);
     else if (chroma)
-        hipLaunchKernelGGL((warp_paste_kernel_t<true, false>), grid, block, 0, s, frames, chroma, rows, tris, PasteNone{}, T, list, entry_of_row,
+        hipLaunchKernelGGL((warp_paste_kernel_t<true, false, PLANAR>), grid, block, 0, s, frames, chroma, rows, tris, PasteNone{}, T, list, entry_of_row,
                            labels, crop);
     else
-        hipLaunchKernelGGL((warp_paste_kernel_t<false, false>), grid, block, 0, s, frames, PasteNone{}, rows, tris, PasteNone{}, T, list,
+        hipLaunchKernelGGL((warp_paste_kernel_t<false, false, PLANAR>), grid, block, 0, s, frames, PasteNone{}, rows, tris, PasteNone{}, T, list,
                            entry_of_row, labels, crop);
+}
+
+void sdm_launch_warp_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris,
+                           const uint16_t* counts, int T, const int* list, const int* entry_of_row, int N, const uint8_t* labels,
+                           const PasteCropDev& crop, bool planar, hipStream_t s)
+{
+    if (planar) launch_warp_paste<true>(frames, chroma, rows, tris, counts, T, list, entry_of_row, N, labels, crop, s);
+    else launch_warp_paste<false>(frames, chroma, rows, tris, counts, T, list, entry_of_row, N, labels, crop, s);
 }

@@ -181,23 +181,25 @@ class Context:
         self._image_sizes = [(int(width), int(height))] * int(n_images)
         self._frames_keep = None
 
-    def set_frames_device(self, frames, formats=None, gray_shift: int = 14):
+    def set_frames_device(self, frames, formats=None, gray_shift: int = 14, chroma=None):
         """Frames that are already on the device as the image set (sdm_set_frames_device): image i is frame i.  ``frames``: a list
         of uint8 device tensors -- H x W gray, H x W x 3 ("bgr", default, or "rgb"), H x W x 4 ("bgra", default, or "rgba"); any row
         stride, so views into larger frames work -- and / or (ptr, w, h, stride_bytes, format) tuples (format by name or
         SDM_FRAME_*: "nv12" with ptr = the Y plane; foreign allocators); or one stacked tensor n x H x W [x C].  ``formats``: one
         name for all tensors or one per frame.  Gray and NV12 frames are used in place -- the context keeps a reference to the
         tensors until the image set is replaced; memory behind a tuple is the caller's to keep alive -- colour frames are converted
-        once, in one launch, with ``upload_images``' arithmetic.  torch's current stream is synchronised first: the library runs
-        on a stream of its own."""
-        desc = _lib.frame_descriptors(frames, formats)
+        once, in one launch, with ``upload_images``' arithmetic.  A 3 x H x W tensor named "bgr_planar" / "rgb_planar" (or one stacked
+        n x 3 x H x W tensor) is a planar colour frame, read where it lies whatever its row and channel strides
+        (``_lib.frame_planes``); ``chroma``: the second planes of planar tuples.  torch's current stream is synchronised first: the
+        library runs on a stream of its own."""
+        desc, planes = _lib.frame_planes(frames, formats, chroma)
         for t in ([frames] if _lib._is_tensor(frames) else frames):
             if getattr(t, "is_cuda", False):
                 import torch
                 torch.cuda.current_stream(t.device).synchronize()
                 break
         arr = (_lib.SdmFrame * len(desc))(*[_lib.SdmFrame(ctypes.c_void_p(p), w, h, st, f) for p, w, h, st, f in desc])
-        check(self._lib.sdm_set_frames_device(self._h, arr, len(desc), int(gray_shift)))
+        check(self._lib.sdm_set_frames_device_planes(self._h, arr, _lib.planes_array(planes), len(desc), int(gray_shift)))
         self._image_sizes = [(w, h) for _, w, h, _, _ in desc]
         self._frames_keep = frames
 
@@ -747,22 +749,20 @@ class Context:
 
     def align_set_source_frames(self, frames=None, formats=None, chroma=None):
         """A frame list as the crop source, used in place (sdm_align_set_source_frames): ``frames`` and ``formats`` as for
-        ``set_frames_device`` -- all six formats --, ``chroma``: None or one entry per frame, the device pointer (or a uint8 tensor) of
-        an NV12 frame's interleaved UV plane; None entries mean "directly behind the Y plane".  ``frames`` None: back to the
+        ``set_frames_device`` -- every format --, ``chroma``: None or one entry per frame, the device pointer (or a uint8 tensor) of
+        an NV12 frame's interleaved UV plane or of a planar colour tuple's second plane; None entries mean "directly behind the first
+        plane".  ``frames`` None: back to the
         context's images.  The memory must stay valid while crops are made from it.  Returns C of ``align_crops`` on this source
-        (the bytes per pixel all frames share), or None when only ``align_crops_tensor`` can read it (NV12, mixed pixel sizes)."""
+        (the bytes per pixel all frames share), or None when only ``align_crops_tensor`` can read it (NV12, planar colour, mixed pixel sizes)."""
         if frames is None:
             check(self._lib.sdm_align_set_source_frames(self._h, None, None, 0))
             self.align_channels = 1
             return 1
-        desc = _lib.frame_descriptors(frames, formats)
+        desc, planes = _lib.frame_planes(frames, formats, chroma)          # (a planar tensor's second plane comes from its strides)
         tensors = [frames] if _lib._is_tensor(frames) else list(frames)
-        uv = None
         if chroma is not None:
-            if len(chroma) != len(desc):
-                raise ValueError("one chroma entry (or None) per frame expected")
             tensors += [u for u in chroma if _lib._is_tensor(u)]
-            uv = (ctypes.c_void_p * len(desc))(*[None if u is None else int(u.data_ptr()) if _lib._is_tensor(u) else int(u) for u in chroma])
+        uv = _lib.planes_array(planes)
         for t in tensors:
             if getattr(t, "is_cuda", False):
                 import torch
@@ -770,7 +770,7 @@ class Context:
                 break
         arr = (_lib.SdmFrame * len(desc))(*[_lib.SdmFrame(ctypes.c_void_p(p), w, h, st, f) for p, w, h, st, f in desc])
         check(self._lib.sdm_align_set_source_frames(self._h, arr, uv, len(desc)))
-        kinds = {0 if f == _lib.SDM_FRAME_NV12 else _lib._FRAME_CHANNELS[f] for _, _, _, _, f in desc}
+        kinds = {0 if f == _lib.SDM_FRAME_NV12 or f in _lib._FRAME_PLANAR else _lib._FRAME_CHANNELS[f] for _, _, _, _, f in desc}
         C = kinds.pop() if len(kinds) == 1 else 0
         self.align_channels = C if C else 1
         return C if C else None
@@ -900,10 +900,10 @@ class Context:
                     tuple(alpha.shape) not in ((height, width), (n, height, width)):
                 raise ValueError(f"mask must be a contiguous uint8 {height} x {width} or {n} x {height} x {width} array or device tensor")
         paste = _lib.SdmAlignPaste(None if alpha is None else alpha.data_ptr(), int(alpha is not None and alpha.dim() == 3))
-        desc = _lib.frame_descriptors(frames, formats)
+        desc, planes = _lib.frame_planes(frames, formats)                  # (planes: planar tensors' second planes, for _paste_chroma)
         arr = (_lib.SdmFrame * len(desc))(*[_lib.SdmFrame(ctypes.c_void_p(p), w, h, st, f) for p, w, h, st, f in desc])
         torch.cuda.current_stream(y.device).synchronize()
-        return spec, paste, arr, n, width, height, (alpha, frames)
+        return spec, paste, arr, n, width, height, (alpha, frames), planes
 
     def _paste_rows(self, n):                                   # the fit forms: the tensor's rows are the context's current rows
         if int(getattr(self, "N", 0)) and n != self.N:          # (no rows yet: the library refuses the call)
@@ -926,16 +926,19 @@ class Context:
         raise ValueError('filter must be None, "area", "bilinear" or an SdmAlignFilter')
 
     @staticmethod
-    def _paste_chroma(chroma, arr, keep):
-        """The NV12 calls' UV planes: None unless a destination is NV12 or ``chroma`` is given -- then (the c_void_p array or None,
+    def _paste_chroma(chroma, arr, keep, planes=None):
+        """The NV12 calls' second planes: None unless a destination is NV12, ``chroma`` is given or a planar tensor's plane distance
+        is not the default (``planes``: what ``_lib.frame_planes`` found in the tensors' strides) -- then (the c_void_p array or None,
         what must stay alive).  ``chroma``: one entry per frame as ``align_set_source_frames`` takes it -- a device pointer, a uint8
-        tensor or None (directly behind the Y plane)."""
-        if chroma is None:
+        tensor or None (directly behind the first plane)."""
+        planes = list(planes or [None] * len(arr))
+        if chroma is None and all(p is None for p in planes):
             return (None, keep) if any(f.format == _lib.SDM_FRAME_NV12 for f in arr) else None
-        if len(chroma) != len(arr):
-            raise ValueError("one chroma entry (or None) per frame expected")
-        uv = (ctypes.c_void_p * len(arr))(*[None if u is None else int(u.data_ptr()) if _lib._is_tensor(u) else int(u) for u in chroma])
-        return uv, (keep, chroma)
+        if chroma is not None:
+            if len(chroma) != len(arr):
+                raise ValueError("one chroma entry (or None) per frame expected")
+            planes = [p if u is None else int(u.data_ptr()) if _lib._is_tensor(u) else int(u) for p, u in zip(planes, chroma)]
+        return (ctypes.c_void_p * len(arr))(*planes), (keep, chroma)
 
     def align_paste_tensor(self, landmark_index, template: np.ndarray, y, frames, formats=None, layout="nchw", mask=None, spec=None,
                            filter=None, max_samples=16, min_scale=1.0, chroma=None, **options):
@@ -956,11 +959,11 @@ class Context:
         t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
         if t.shape[0] != idx.size:
             raise ValueError("one template point (x, y) per landmark index expected")
-        spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
+        spec, paste, arr, n, width, height, keep, planes = self._paste_call(y, layout, frames, formats, mask, spec, options)
         self._paste_rows(n)
         mats = np.empty((n, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
-        nv12 = self._paste_chroma(chroma, arr, keep)
+        nv12 = self._paste_chroma(chroma, arr, keep, planes)
         if nv12 is not None:
             samples = np.empty(n, np.int32)
             check(self._lib.sdm_align_paste_tensor_nv12(self._h, idx.ctypes.data, t.ctypes.data, idx.size, width, height, ctypes.byref(spec),
@@ -987,13 +990,13 @@ class Context:
         (as for ``align_paste_tensor``: sdm_align_paste_tensor_at_filtered) it returns (flags, samples N int32: S of every row).  "nv12"
         destinations and ``chroma``: as for ``align_paste_tensor`` (sdm_align_paste_tensor_at_nv12)."""
         filter = self._paste_filter(filter, max_samples, min_scale)
-        spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
+        spec, paste, arr, n, width, height, keep, planes = self._paste_call(y, layout, frames, formats, mask, spec, options)
         m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 6)
         if m.shape[0] != n:
             raise ValueError(f"one matrix per row of the tensor expected: {m.shape[0]} for {n}")
         idx = self._paste_image_index(image_index, n)
         flags = np.empty(n, np.int32)
-        nv12 = self._paste_chroma(chroma, arr, keep)
+        nv12 = self._paste_chroma(chroma, arr, keep, planes)
         if nv12 is not None:
             samples = np.empty(n, np.int32)
             check(self._lib.sdm_align_paste_tensor_at_nv12(self._h, m.ctypes.data, None if idx is None else idx.ctypes.data, n, width, height,
@@ -1019,9 +1022,9 @@ class Context:
             raise ValueError(f"the tensor's crop is {width} x {height}, the mesh's {w} x {h}")
         return T
 
-    def _warp_paste_chroma(self, chroma, arr, keep):
+    def _warp_paste_chroma(self, chroma, arr, keep, planes=None):
         """the filtered calls take a mixed list: their UV planes, all None (behind the Y plane, read for NV12 frames only) by default"""
-        return self._paste_chroma(chroma, arr, keep) or (None, keep)
+        return self._paste_chroma(chroma, arr, keep, planes) or (None, keep)
 
     def warp_paste_tensor(self, y, frames, formats=None, layout="nchw", mask=None, spec=None, chroma=None, filter=None, max_samples=16,
                           min_scale=1.0, **options):
@@ -1036,19 +1039,19 @@ class Context:
         destinations may mix NV12 and the other formats -- which returns (matrices, flags, samples N x T x 2 int32: (Sx, Sy) of every
         triangle)."""
         filter = self._paste_filter(filter, max_samples, min_scale)
-        spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
+        spec, paste, arr, n, width, height, keep, planes = self._paste_call(y, layout, frames, formats, mask, spec, options)
         T = self._warp_paste_size(width, height)
         self._paste_rows(n)
         mats = np.empty((n, T, 2, 3), np.float32)
         flags = np.empty(n, np.int32)
         if filter is not None:
-            uv, keep = self._warp_paste_chroma(chroma, arr, keep)
+            uv, keep = self._warp_paste_chroma(chroma, arr, keep, planes)
             samples = np.empty((n, T, 2), np.int32)
             check(self._lib.sdm_warp_paste_tensor_filtered(self._h, ctypes.byref(spec), ctypes.byref(filter), ctypes.c_void_p(y.data_ptr()),
                                                            ctypes.byref(paste), arr, uv, len(arr), mats.ctypes.data, flags.ctypes.data,
                                                            samples.ctypes.data))
             return mats, flags, samples
-        nv12 = self._paste_chroma(chroma, arr, keep)
+        nv12 = self._paste_chroma(chroma, arr, keep, planes)
         if nv12 is not None:
             check(self._lib.sdm_warp_paste_tensor_nv12(self._h, ctypes.byref(spec), ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr,
                                                        nv12[0], len(arr), mats.ctypes.data, flags.ctypes.data))
@@ -1065,7 +1068,7 @@ class Context:
         "nv12" destinations and ``chroma``: as for ``warp_paste_tensor`` (sdm_warp_paste_tensor_at_nv12).  With a ``filter`` (as for
         ``warp_paste_tensor``: sdm_warp_paste_tensor_at_filtered) it returns (flags, samples N x T x 2 int32)."""
         filter = self._paste_filter(filter, max_samples, min_scale)
-        spec, paste, arr, n, width, height, keep = self._paste_call(y, layout, frames, formats, mask, spec, options)
+        spec, paste, arr, n, width, height, keep, planes = self._paste_call(y, layout, frames, formats, mask, spec, options)
         T = self._warp_paste_size(width, height)
         p = np.ascontiguousarray(points, np.float32)
         if p.ndim != 3 or p.shape[0] != n or p.shape[2] != 2:
@@ -1073,13 +1076,13 @@ class Context:
         idx = self._paste_image_index(image_index, n)
         flags = np.empty(n, np.int32)
         if filter is not None:
-            uv, keep = self._warp_paste_chroma(chroma, arr, keep)
+            uv, keep = self._warp_paste_chroma(chroma, arr, keep, planes)
             samples = np.empty((n, T, 2), np.int32)
             check(self._lib.sdm_warp_paste_tensor_at_filtered(self._h, p.ctypes.data, None if idx is None else idx.ctypes.data, n,
                                                               ctypes.byref(spec), ctypes.byref(filter), ctypes.c_void_p(y.data_ptr()),
                                                               ctypes.byref(paste), arr, uv, len(arr), flags.ctypes.data, samples.ctypes.data))
             return flags, samples
-        nv12 = self._paste_chroma(chroma, arr, keep)
+        nv12 = self._paste_chroma(chroma, arr, keep, planes)
         if nv12 is not None:
             check(self._lib.sdm_warp_paste_tensor_at_nv12(self._h, p.ctypes.data, None if idx is None else idx.ctypes.data, n, ctypes.byref(spec),
                                                           ctypes.c_void_p(y.data_ptr()), ctypes.byref(paste), arr, nv12[0], len(arr),
@@ -1354,8 +1357,9 @@ class HogTransform:
 
     def __init__(self, images, hog_params: Sequence[HoGParam], model_landmarks: Sequence[str],
                  right_eye_ids: Sequence[str], left_eye_ids: Sequence[str],
-                 img_index: Optional[np.ndarray] = None, images_resident: bool = False):
+                 img_index: Optional[np.ndarray] = None, images_resident: bool = False, formats=None, chroma=None):
         self.images = images
+        self.formats, self.chroma = formats, chroma    # device frames: as Context.set_frames_device takes them (planar names)
         self.images_resident = bool(images_resident)   # opt-in: the pixels do not change between calls with THIS object
         self.hog_params = list(hog_params)
         self.model_landmarks = list(model_landmarks)
@@ -1469,7 +1473,8 @@ class SupervisedDescentOptimiser:
         # very same projection object again, which this optimiser then holds a strong reference to.
         if not (projection.images_resident and self._bound is projection):
             if _device_frames(projection.images):
-                self.ctx.set_frames_device(projection.images)
+                named = {k: v for k in ("formats", "chroma") for v in [getattr(projection, k, None)] if v is not None}
+                self.ctx.set_frames_device(projection.images, **named)
             else:
                 self.ctx.upload_images(projection.images)
         self._bound = projection
@@ -1709,22 +1714,23 @@ class detection_model:
         return self.optimised_model.predict(np.atleast_2d(init), None, hog)[0]
 
     def detect_batch(self, images, faceboxes: np.ndarray, img_index: Optional[np.ndarray] = None, roll=None, chip: Optional[int] = None,
-                     guard: Optional[int] = None) -> np.ndarray:
+                     guard: Optional[int] = None, formats=None, chroma=None) -> np.ndarray:
         """Batched ``detect``: row i starts from align_mean(mean, faceboxes[i]) on image img_index[i].  ``images``: host images, or
         frames on the device as ``Context.set_frames_device`` takes them (gray, "bgr" / "bgra" tensors of any size and row stride;
-        (ptr, w, h, stride, format) tuples for the other formats) -- those are not downloaded.
+        (ptr, w, h, stride, format) tuples for the other formats; with ``formats`` "bgr_planar" / "rgb_planar", 3 x H x W tensors or
+        one n x 3 x H x W tensor, and ``chroma`` the second planes of planar tuples) -- those are not downloaded.
         ``roll`` (degrees, clockwise positive; one value or one per row) selects the upright path for rolled faces: every face is cut
         upright from its frame as a ``chip`` x ``chip`` image on the device, the cascade runs on the chips and the landmarks come
         back in frame coordinates (include/sdm.h, "Rolled faces").  ``chip`` defaults to the smallest multiple of 32 that is
         >= 1.75 x the largest box side, ``guard`` to ``chip // 8``; ``upright_info()`` returns the matrices and flags."""
         if roll is not None:
-            return self._detect_batch_upright(images, faceboxes, img_index, roll, chip, guard)
+            return self._detect_batch_upright(images, faceboxes, img_index, roll, chip, guard, formats, chroma)
         if chip is not None or guard is not None:
             raise ValueError("chip and guard go with roll")
         from .synth import align_mean
         init = np.stack([align_mean(self.mean, tuple(int(v) for v in b)) for b in np.asarray(faceboxes)])
         hog = HogTransform(images, self.hog_params, self.landmark_ids, self.right_eye_ids, self.left_eye_ids,
-                           img_index)
+                           img_index, formats=formats, chroma=chroma)
         return self.optimised_model.test(init, None, hog)
 
     @staticmethod
@@ -1733,12 +1739,13 @@ class detection_model:
         side = int(np.asarray(faceboxes).reshape(-1, 4)[:, 2:].max())
         return max(32, -(-(7 * side) // (4 * 32)) * 32)
 
-    def _detect_batch_upright(self, images, faceboxes, img_index, roll, chip, guard):
+    def _detect_batch_upright(self, images, faceboxes, img_index, roll, chip, guard, formats=None, chroma=None):
         opt = self.optimised_model
         boxes = np.asarray(faceboxes).reshape(-1, 4)
         chip = self.default_chip(boxes) if chip is None else int(chip)
         guard = chip // 8 if guard is None else int(guard)
-        hog = HogTransform(images, self.hog_params, self.landmark_ids, self.right_eye_ids, self.left_eye_ids, img_index)
+        hog = HogTransform(images, self.hog_params, self.landmark_ids, self.right_eye_ids, self.left_eye_ids, img_index,
+                           formats=formats, chroma=chroma)
         opt._bind(hog, boxes.shape[0])
         opt._load_regressors()
         c = opt.ctx
@@ -2136,11 +2143,12 @@ class Tracker:
     def stop(self, ids):
         self.ctx.track_stop(ids)
 
-    def step(self, ids, frames=None, image_index=None, fetch: bool = True, formats=None, gray_shift: int = 14, dt=None):
+    def step(self, ids, frames=None, image_index=None, fetch: bool = True, formats=None, gray_shift: int = 14, dt=None, chroma=None):
         """One frame for the streams ``ids``: row i belongs to stream ids[i] and reads frame ``image_index[i]`` (default i).
         ``frames``: host images (a list or an n x H x W stack, uploaded), a uint8 n x H x W tensor on the device (used in place),
         any other device input of ``Context.set_frames_device`` -- a list of gray or colour tensors of different sizes, pitched
-        views, a stacked n x H x W x C tensor, (ptr, w, h, stride, format) tuples; ``formats`` and ``gray_shift`` go with it --
+        views, a stacked n x H x W x C tensor, planar 3 x H x W tensors named "bgr_planar" / "rgb_planar" by ``formats``,
+        (ptr, w, h, stride, format) tuples; ``formats``, ``gray_shift`` and ``chroma`` (planar tuples' second planes) go with it --
         or None (the images already set on the context).  Returns (landmarks n x 2L -- None unless ``fetch`` --, lost masks n:
         0 = tracked, else the SDM_TRACK_LOST_* bits).
         ``dt`` (a tracker with ``smooth`` only; seconds since the streams' last step with ``dt``, one value or one per row): the
@@ -2155,7 +2163,8 @@ class Tracker:
         c = self.ctx
         self._bind()
         if frames is not None:
-            if hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False) and frames.dim() == 3 and frames.is_contiguous():
+            if hasattr(frames, "data_ptr") and getattr(frames, "is_cuda", False) and frames.dim() == 3 and frames.is_contiguous() and \
+                    _lib._one_planar_name(formats) is None:                     # (one 3 x H x W frame named planar is no stack of gray images)
                 if frames.dtype.itemsize != 1:
                     raise ValueError("device frames must be uint8")
                 import torch
@@ -2163,7 +2172,7 @@ class Tracker:
                 n, h, w = (int(v) for v in frames.shape)
                 c.set_images_device(frames.data_ptr(), n, w, h, w)
             elif _device_frames(frames):
-                c.set_frames_device(frames, formats, gray_shift)            # (colour, ragged, pitched: sdm_set_frames_device)
+                c.set_frames_device(frames, formats, gray_shift, chroma)    # (colour, ragged, pitched, planar: sdm_set_frames_device)
             else:
                 c.upload_images(frames)
             self.model.optimised_model._bound = None                        # (the context's images are no longer a bound projection's)

@@ -43,21 +43,44 @@ struct HoGParam {
 };
 
 /** A frame that is already on the device (sdm_frame of include/sdm.h): `data` is a device pointer of any alignment, `format` one of
- *  SDM_FRAME_GRAY / BGR / RGB / BGRA / RGBA / NV12 (data = the Y plane).  Gray and NV12 frames are read in place and must stay valid
- *  while they are the image set; colour frames are converted to gray once, on the device. */
+ *  SDM_FRAME_GRAY / BGR / RGB / BGRA / RGBA / NV12 (data = the Y plane) / BGR_PLANAR / RGB_PLANAR (data = plane 0 of 3 x H x W).  Gray
+ *  and NV12 frames are read in place and must stay valid while they are the image set; colour frames are converted to gray once, on the
+ *  device.  `second_plane`: a planar frame's plane 1 or an NV12 frame's UV plane where it does not lie directly behind the first
+ *  (include/sdm.h, "Planar colour frames"); nullptr: height * stride_bytes behind `data`. */
 struct DeviceFrame {
     const void* data;
     int width, height, stride_bytes, format;
+    const void* second_plane = nullptr;
 };
 
 namespace detail {
+
+// the second planes of a call (`chroma` / `dst_chroma` / `planes` of include/sdm.h): per frame the caller's entry, else the frame's own
+// second_plane; data() is null when no entry is set
+template <class P>
+struct SecondPlanes {
+    std::vector<P> v;
+    bool any = false;
+    SecondPlanes(const std::vector<DeviceFrame>& frames, const std::vector<P>* chroma)
+    {
+        for (size_t i = 0; i < frames.size(); ++i) {
+            P u = chroma && i < chroma->size() ? (*chroma)[i] : nullptr;
+            if (!u) u = const_cast<P>(frames[i].second_plane);
+            v.push_back(u);
+            any = any || u != nullptr;
+        }
+    }
+    const P* data() const { return any ? v.data() : nullptr; }
+};
 
 // frames on the device -> the handle's image set (sdm_set_frames_device): nothing crosses the host link
 inline void set_device_frames(superviseddescent::hip::Handle& h, const std::vector<DeviceFrame>& frames, int gray_shift = 14)
 {
     std::vector<sdm_frame> f;
     for (const auto& d : frames) f.push_back(sdm_frame{d.data, d.width, d.height, d.stride_bytes, d.format});
-    superviseddescent::hip::check(sdm_set_frames_device(h.get(), f.data(), (int)f.size(), gray_shift), "sdm_set_frames_device");
+    const SecondPlanes<const void*> planes(frames, nullptr);
+    superviseddescent::hip::check(sdm_set_frames_device_planes(h.get(), f.data(), planes.data(), (int)f.size(), gray_shift),
+                                  "sdm_set_frames_device_planes");
 }
 
 // single-channel u8 view of an image on the HOST (used only for lists that mix gray and colour images; all-colour lists are

@@ -178,7 +178,8 @@ inline aligned_tensor_result align_tensor_current_rows(sdm_ctx* c, int n, const 
     cv::Mat t = tmpl.isContinuous() ? tmpl : tmpl.clone();
     std::vector<sdm_frame> f;
     for (const auto& d : frames) f.push_back(sdm_frame{d.data, d.width, d.height, d.stride_bytes, d.format});
-    check(sdm_align_set_source_frames(c, f.empty() ? nullptr : f.data(), chroma.empty() ? nullptr : chroma.data(), (int)f.size()),
+    const SecondPlanes<const void*> planes(frames, &chroma);                  // (a frame's own second_plane where chroma names none)
+    check(sdm_align_set_source_frames(c, f.empty() ? nullptr : f.data(), planes.data(), (int)f.size()),
           "sdm_align_set_source_frames");
     sdm_align_tensor s{};
     s.dtype = spec.dtype; s.layout = spec.layout; s.channels = spec.channels; s.order = spec.order; s.gray_shift = spec.gray_shift;
@@ -303,16 +304,18 @@ inline paste_result paste_current_rows(sdm_ctx* c, int n, const std::vector<int>
     if (tmpl.rows != (int)landmark_index.size() || tmpl.cols != 2) throw std::runtime_error("paste_crops_tensor: one template point (x, y) per landmark");
     cv::Mat t = tmpl.isContinuous() ? tmpl : tmpl.clone();
     const std::vector<sdm_frame> f = paste_frames(frames);
+    if (chroma) paste_chroma(*chroma, f.size());                                // (its size check)
+    const SecondPlanes<void*> planes(frames, chroma);                           // (a frame's own second_plane where chroma names none)
     const sdm_align_tensor s = paste_spec(spec);
     const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
     paste_result res;
     res.matrices = cv::Mat(n, 6, CV_32FC1);
     res.flags.resize((size_t)n);
-    if (chroma) {
+    if (chroma || planes.any) {
         const sdm_align_filter fl = filter ? sdm_align_filter{filter->mode, filter->max_samples, filter->min_scale} : sdm_align_filter{};
         if (filter) res.samples.resize((size_t)n);
         check(sdm_align_paste_tensor_nv12(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height, &s,
-                                          filter ? &fl : nullptr, in_dev, &p, f.empty() ? nullptr : f.data(), paste_chroma(*chroma, f.size()),
+                                          filter ? &fl : nullptr, in_dev, &p, f.empty() ? nullptr : f.data(), planes.data(),
                                           (int)f.size(), res.matrices.ptr<float>(0), res.flags.data(), filter ? res.samples.data() : nullptr),
               "sdm_align_paste_tensor_nv12");
         return res;
@@ -441,14 +444,16 @@ inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>&
     res.matrices = matrices.isContinuous() ? matrices : matrices.clone();
     res.flags.resize((size_t)matrices.rows);
     const std::vector<sdm_frame> f = detail::paste_frames(frames);
+    if (chroma) detail::paste_chroma(*chroma, f.size());                        // (its size check)
+    const detail::SecondPlanes<void*> planes(frames, chroma);                   // (a frame's own second_plane where chroma names none)
     const sdm_align_tensor s = detail::paste_spec(spec);
     const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
-    if (chroma) {
+    if (chroma || planes.any) {
         const sdm_align_filter fl = filter ? sdm_align_filter{filter->mode, filter->max_samples, filter->min_scale} : sdm_align_filter{};
         if (filter) res.samples.resize((size_t)matrices.rows);
         check(sdm_align_paste_tensor_at_nv12(h.get(), res.matrices.ptr<float>(0), image_index.empty() ? nullptr : image_index.data(),
                                              matrices.rows, width, height, &s, filter ? &fl : nullptr, in_dev, &p,
-                                             f.empty() ? nullptr : f.data(), detail::paste_chroma(*chroma, f.size()), (int)f.size(),
+                                             f.empty() ? nullptr : f.data(), planes.data(), (int)f.size(),
                                              res.flags.data(), filter ? res.samples.data() : nullptr),
               "sdm_align_paste_tensor_at_nv12");
         return res;

@@ -98,7 +98,8 @@ inline warped_tensor_result warp_tensor_current_rows(sdm_ctx* c, int n, const Wa
                             mesh.n_triangles(), mesh.width, mesh.height), "sdm_warp_set_mesh");
     std::vector<sdm_frame> f;
     for (const auto& d : frames) f.push_back(sdm_frame{d.data, d.width, d.height, d.stride_bytes, d.format});
-    check(sdm_align_set_source_frames(c, f.empty() ? nullptr : f.data(), chroma.empty() ? nullptr : chroma.data(), (int)f.size()),
+    const SecondPlanes<const void*> planes(frames, &chroma);                  // (a frame's own second_plane where chroma names none)
+    check(sdm_align_set_source_frames(c, f.empty() ? nullptr : f.data(), planes.data(), (int)f.size()),
           "sdm_align_set_source_frames");
     sdm_align_tensor s{};
     s.dtype = spec.dtype; s.layout = spec.layout; s.channels = spec.channels; s.order = spec.order; s.gray_shift = spec.gray_shift;
@@ -206,6 +207,8 @@ inline warp_paste_result warp_paste_current_rows(sdm_ctx* c, int n, const WarpMe
 {
     warp_paste_set_mesh(c, mesh);
     const std::vector<sdm_frame> f = paste_frames(frames);
+    if (chroma) paste_chroma(*chroma, f.size());                                // (its size check)
+    const SecondPlanes<void*> planes(frames, chroma);                           // (a frame's own second_plane where chroma names none)
     const sdm_align_tensor s = paste_spec(spec);
     const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
     warp_paste_result res;
@@ -215,14 +218,14 @@ inline warp_paste_result warp_paste_current_rows(sdm_ctx* c, int n, const WarpMe
         const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
         if (samples) samples->assign((size_t)n * mesh.n_triangles() * 2, 0);
         superviseddescent::hip::check(sdm_warp_paste_tensor_filtered(c, &s, &fl, in_dev, &p, f.empty() ? nullptr : f.data(),
-                                                                     chroma ? paste_chroma(*chroma, f.size()) : nullptr, (int)f.size(),
+                                                                     planes.data(), (int)f.size(),
                                                                      res.matrices.ptr<float>(0), res.flags.data(),
                                                                      samples ? samples->data() : nullptr),
                                       "sdm_warp_paste_tensor_filtered");
         return res;
     }
-    if (chroma) {
-        superviseddescent::hip::check(sdm_warp_paste_tensor_nv12(c, &s, in_dev, &p, f.empty() ? nullptr : f.data(), paste_chroma(*chroma, f.size()),
+    if (chroma || planes.any) {
+        superviseddescent::hip::check(sdm_warp_paste_tensor_nv12(c, &s, in_dev, &p, f.empty() ? nullptr : f.data(), planes.data(),
                                                                  (int)f.size(), res.matrices.ptr<float>(0), res.flags.data()),
                                       "sdm_warp_paste_tensor_nv12");
         return res;
@@ -266,6 +269,8 @@ inline warp_paste_result warp_paste_points(detection_model& model, cv::Mat point
     detail::warp_paste_set_mesh(h.get(), mesh);
     cv::Mat pts = points.isContinuous() ? points : points.clone();
     const std::vector<sdm_frame> f = detail::paste_frames(frames);
+    if (chroma) detail::paste_chroma(*chroma, f.size());                        // (its size check)
+    const detail::SecondPlanes<void*> planes(frames, chroma);                   // (a frame's own second_plane where chroma names none)
     const sdm_align_tensor s = detail::paste_spec(spec);
     const sdm_align_paste p{mask.alpha_dev, mask.per_row ? 1 : 0};
     warp_paste_result res;
@@ -275,12 +280,12 @@ inline warp_paste_result warp_paste_points(detection_model& model, cv::Mat point
         const sdm_align_filter fl{filter->mode, filter->max_samples, filter->min_scale};
         if (samples) samples->assign((size_t)points.rows * mesh.n_triangles() * 2, 0);
         check(sdm_warp_paste_tensor_at_filtered(h.get(), pts.ptr<float>(0), index, points.rows, &s, &fl, in_dev, &p, f.empty() ? nullptr : f.data(),
-                                                chroma ? detail::paste_chroma(*chroma, f.size()) : nullptr, (int)f.size(), res.flags.data(),
+                                                planes.data(), (int)f.size(), res.flags.data(),
                                                 samples ? samples->data() : nullptr),
               "sdm_warp_paste_tensor_at_filtered");
-    } else if (chroma)
+    } else if (chroma || planes.any)
         check(sdm_warp_paste_tensor_at_nv12(h.get(), pts.ptr<float>(0), index, points.rows, &s, in_dev, &p, f.empty() ? nullptr : f.data(),
-                                            detail::paste_chroma(*chroma, f.size()), (int)f.size(), res.flags.data()),
+                                            planes.data(), (int)f.size(), res.flags.data()),
               "sdm_warp_paste_tensor_at_nv12");
     else
         check(sdm_warp_paste_tensor_at(h.get(), pts.ptr<float>(0), index, points.rows, &s, in_dev, &p, f.empty() ? nullptr : f.data(),
