@@ -168,7 +168,48 @@ int sdm_set_images_device(sdm_ctx* ctx, const uint8_t* dev_base, int n_images, i
                               the chroma plane behind it is never read; Y is taken as it is    */
 #define SDM_FRAME_BGR_PLANAR 16   /* three planes of 1 byte per pixel, B G R: "Planar colour frames" below */
 #define SDM_FRAME_RGB_PLANAR 17   /* three planes, R G B                                                    */
+#define SDM_FRAME_P010 7   /* as NV12, 16-bit little-endian words, the sample in bits 15..6:
+                              "YUV colour description and 10-bit surfaces" below (6 stays
+                              free: it has always been refused as an unknown format)           */
+#define SDM_FRAME_BASE(f)       ((f) & 0xff)
+#define SDM_FRAME_YUV_BT601     0x000    /* matrix, bits 8..11  */
+#define SDM_FRAME_YUV_BT709     0x100
+#define SDM_FRAME_YUV_BT2020    0x200    /* non-constant luminance */
+#define SDM_FRAME_YUV_FULL      0x1000   /* range, bit 12; absent: limited */
 typedef struct sdm_frame { const void* data; int width, height, stride_bytes, format; } sdm_frame;
+/* YUV colour description and 10-bit surfaces.  The colour description of a YUV frame rides in sdm_frame.format: the base
+ * (SDM_FRAME_BASE(format): SDM_FRAME_NV12 or SDM_FRAME_P010) or-ed with one matrix and, for full range, SDM_FRAME_YUV_FULL --
+ * SDM_FRAME_NV12 | SDM_FRAME_YUV_BT709 is what a 1080p or 4K decoder delivers, SDM_FRAME_P010 | SDM_FRAME_YUV_BT2020 an HDR stream,
+ * SDM_FRAME_NV12 | SDM_FRAME_YUV_FULL a camera or JPEG-derived frame.  Every call that takes an sdm_frame takes these values.
+ *   value 5   SDM_FRAME_NV12 with no flag is UNCHANGED on every path: BT.601 limited range with OpenCV's three-decimal constants (the
+ *       formulas at sdm_align_crops_tensor and "Pasting crops back into NV12 frames"), bit for bit.  SDM_FRAME_NV12 |
+ *       SDM_FRAME_YUV_BT601 IS value 5: an 8-bit BT.601 limited-range frame cannot ask for the derived constants (they differ from
+ *       OpenCV's in the fourth digit).  Every other (matrix, range, depth) uses constants derived by the one rule below.
+ *   constants   Kr, Kb = (0.299, 0.114) BT.601, (0.2126, 0.0722) BT.709, (0.2627, 0.0593) BT.2020; Kg = 1 - Kr - Kb.  Each integer
+ *       constant is floor(c * 2^20 + 0.5) of its real coefficient c, evaluated in double.
+ *   decode    d bits (8: NV12, 10: P010).  Limited: ys = 255 / (219 * 2^(d-8)), cs = 255 / (224 * 2^(d-8)), y0 = 16 * 2^(d-8); full:
+ *       ys = cs = 255 / (2^d - 1), y0 = 0.  y = max(Y - y0, 0) * CY, u = U - 2^(d-1), v = V - 2^(d-1);
+ *       R = clamp255((y + CVR v + 2^19) >> 20), B = clamp255((y + CUB u + 2^19) >> 20), G = clamp255((y - CVG v - CUG u + 2^19) >> 20)
+ *       with CY = ys, CVR = 2 (1 - Kr) cs, CUB = 2 (1 - Kb) cs, CVG = 2 Kr (1 - Kr) / Kg cs, CUG = 2 Kb (1 - Kb) / Kg cs, in int32 (every
+ *       sum is below 2^31).  BT.709 limited: 1220945 1879825 2215014 558796 223607 at 8 bits, 305236 469956 553753 139699 55902 at 10.
+ *   encode    (the pastes, 8 bits)  Y = (YR R + YG G + YB B + (y0 << 20) + 2^19) >> 20 with the coefficients K * (219 / 255 | 1);
+ *       U = clamp255((UB B - UG G - UR R + (128 << 20) + 2^19) >> 20) with 0.5, 0.5 Kg / (1 - Kb), 0.5 Kr / (1 - Kb), each times
+ *       (224 / 255 | 1); V the same with R in B's place and Kr in Kb's.  BT.709 full: Y 222927 749942 75707, U 524288 404150 120138,
+ *       V 524288 476214 48074.
+ *   P010      data = the Y plane, height rows of stride_bytes, one 16-bit little-endian word per pixel; the UV plane, (height + 1) / 2
+ *       rows of (width + 1) / 2 word pairs, lies behind it or where the second-plane array says.  A tap is word >> 6 (0 ... 1023, the low
+ *       six bits are ignored); the bilinear value is (sum of w s + 512) >> 10 at 10 bits for luma and for the UV pair, a luma tap outside
+ *       the plane reads 0, a chroma tap 512; the area sums add 10-bit taps.  The 10-bit decode gives the 8-bit (B, G, R); gray weights,
+ *       scale and bias, layouts and chroma siting (position / 2) are those of NV12.
+ *   gray      channels == 1 from NV12 with any flags is Y as it is; from P010 it is min(255, (Y10 + 2) >> 2) of the bilinear (or averaged)
+ *       10-bit luma.  As an image set, NV12 with any flags is read in place; a P010 frame is converted by the colour launch into a
+ *       context-owned gray image, min(255, ((word >> 6) + 2) >> 2) per luma word -- its UV plane is never read.
+ *   where     sources of sdm_align_crops_tensor[_filtered] and sdm_warp_crops_tensor[_filtered]: NV12 and P010 with flags.  Destinations
+ *       of the _nv12 pastes: NV12 with flags.  A P010 destination is refused; so is P010 in sdm_align_crops, as NV12 is.
+ *   refused   (SDM_ERR_INVALID, no state changed, nothing launched) a flag on a base that is not NV12 or P010, a matrix field above
+ *       0x200, any other set bit; a P010 frame with stride_bytes < 2 * width, a UV row shorter than 4 * ((width + 1) / 2) bytes, or an
+ *       odd pointer or stride of either plane.  Offsets inside a plane are 32-bit while height * stride_bytes <= INT_MAX bytes (and
+ *       the same for the UV plane), 64-bit beyond. */
 int sdm_set_frames_device(sdm_ctx* ctx, const sdm_frame* frames, int n_frames, int gray_shift);
 /* Planar colour frames -- 3 x H x W uint8, the layout of torch's decoders, colour transforms and image networks -- as a source and
  * as a destination of every call that takes an sdm_frame.  Nothing is repacked: the image set, the crops, the warps and the pastes

@@ -44,7 +44,7 @@ def timed(torch, stream, fn):
     return {"median_ms": float(np.median(ev)), "spread_ms": float(max(ev) - min(ev)), "host_median_ms": float(np.median(host)), "calls": CALLS}
 
 
-def child(rows, per_frame, size, lo, hi, filt):
+def child(rows, per_frame, size, lo, hi, filt, fmt="nv12"):
     sys.path.insert(0, ROOT)
     import torch
     from superviseddescent_amd import Context, feather_mask
@@ -55,7 +55,7 @@ def child(rows, per_frame, size, lo, hi, filt):
     bgr = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device="cuda").random_(0, 256)
     nv12 = torch.empty((n_frames, H + H // 2, W), dtype=torch.uint8, device="cuda").random_(0, 256)       # the UV plane behind Y
     f_bgr = [(bgr[i].data_ptr(), W, H, W * 3, "bgr") for i in range(n_frames)]
-    f_nv12 = [(nv12[i].data_ptr(), W, H, W, "nv12") for i in range(n_frames)]
+    f_nv12 = [(nv12[i].data_ptr(), W, H, W, fmt) for i in range(n_frames)]
     index = np.arange(rows) // per_frame
     width = rng.uniform(float(lo), float(hi), rows)
     s = width / size
@@ -73,7 +73,7 @@ def child(rows, per_frame, size, lo, hi, filt):
     if filt == "area":
         kw["filter"] = "area"
     res = {"device": torch.cuda.get_device_name(0), "rows": rows, "faces_per_frame": per_frame, "frames": n_frames, "crop": size,
-           "crop_width_in_frame": [lo, hi], "filter": filt}
+           "crop_width_in_frame": [lo, hi], "filter": filt, "format": fmt}
     res["bgr"] = timed(torch, stream, lambda: ctx.align_paste_tensor_at(mats, y, f_bgr, **kw))
     res["nv12"] = timed(torch, stream, lambda: ctx.align_paste_tensor_at(mats, y, f_nv12, **kw))
     res["bgr_again"] = timed(torch, stream, lambda: ctx.align_paste_tensor_at(mats, y, f_bgr, **kw))       # the two forms in turn: the
@@ -95,13 +95,14 @@ def child(rows, per_frame, size, lo, hi, filt):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_paste_nv12_timing.json"))
+    ap.add_argument("--format", default="nv12", help='the NV12 destinations\' name: "nv12" (value 5), "nv12:bt709", "nv12:bt2020:full", ...')
     ap.add_argument("--child", nargs=6, default=None)
     a = ap.parse_args()
     if a.child:
-        return child(*[int(v) for v in a.child[:5]], a.child[5])
+        return child(*[int(v) for v in a.child[:5]], a.child[5], a.format)
     runs = []
     for case in CASES:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + [str(v) for v in case], capture_output=True, text=True,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--format", a.format, "--child"] + [str(v) for v in case], capture_output=True, text=True,
                            timeout=240)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)
@@ -111,7 +112,7 @@ def main():
         print("%5d rows, %2d per frame, crop %3d, %s: BGR %8.3f ms  NV12 %8.3f ms  ratio %.2f  (%.3f / %.3f ns per frame pixel)" %
               (e["rows"], e["faces_per_frame"], e["crop"], e["filter"], e["bgr"]["median_ms"], e["nv12"]["median_ms"], e["nv12_over_bgr"],
                e["bgr"]["ns_per_frame_pixel"], e["nv12"]["ns_per_frame_pixel"]), flush=True)
-    doc = {"tensor": "C x C x 3 float16 NCHW RGB, mean / std, feathered opacity map", "frames": "1920 x 1080, BGR and NV12 (UV behind Y), in place",
+    doc = {"format": a.format, "tensor": "C x C x 3 float16 NCHW RGB, mean / std, feathered opacity map", "frames": "1920 x 1080, BGR and NV12 (UV behind Y), in place",
            "unit": "ms per call between two HIP events on the context's stream; host_median_ms: the host clock around the same call",
            "runs": runs}
     with open(a.out, "w") as f:

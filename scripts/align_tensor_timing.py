@@ -98,12 +98,13 @@ def main():
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "align_tensor_timing.json"))
+    ap.add_argument("--format", default="nv12", help='the YUV surfaces\' name: "nv12" (value 5), "nv12:bt709", "p010:bt709", ... (P010: 16-bit words)')
     a = ap.parse_args()
     profile = None
     if not a.quick and not a.no_profile:
         with tempfile.TemporaryDirectory() as d:
             p = subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", d, "--output-format", "csv", "--", sys.executable,
-                                os.path.abspath(__file__), "--quick"], capture_output=True, text=True, timeout=600)
+                                os.path.abspath(__file__), "--quick", "--format", a.format], capture_output=True, text=True, timeout=600)
             profile = {"returncode": p.returncode, "kernels": kernel_rows(d)}
             if p.returncode:
                 profile["stderr_tail"] = p.stderr[-2000:]
@@ -116,13 +117,18 @@ def main():
     stack = torch.from_numpy(colour).cuda()
     bgr = [torch.from_numpy(c).cuda() for c in colour]                       # 64 separate allocations, used in place
     H, W = gray.shape[1:]
-    surfaces = [torch.from_numpy(np.concatenate([g, rng.integers(0, 256, (H // 2, W), dtype=np.uint8)])).cuda() for g in gray]
-    nv12 = [(s.data_ptr(), W, H, W, "nv12") for s in surfaces]
+    if a.format.lower().startswith("p010"):                                  # the luma as 10-bit samples in bits 15..6, rows of 2 W bytes
+        surfaces = [torch.from_numpy(np.concatenate([(g.astype(np.uint16) << 8).view(np.uint8).reshape(H, 2 * W),
+                                                     rng.integers(0, 256, (H // 2, 2 * W), dtype=np.uint8)])).cuda() for g in gray]
+        nv12 = [(s.data_ptr(), W, H, 2 * W, a.format) for s in surfaces]
+    else:
+        surfaces = [torch.from_numpy(np.concatenate([g, rng.integers(0, 256, (H // 2, W), dtype=np.uint8)])).cuda() for g in gray]
+        nv12 = [(s.data_ptr(), W, H, W, a.format) for s in surfaces]
     ctx = Context(0)
     ctx.set_model_geometry(L, *ibug.eye_indices(IDS), [HoGParam(*p) for p in ibug.SHIPPED_HOG_PARAMS])
     sizes = [(4096, 200)] if a.quick else [(1, 1000), (256, 1000), (4096, 300)]
     res = {"crop": f"{SIZE} x {SIZE}", "tensor": "float16 N x 3 x H x W, RGB, mean / std", "landmarks": f"RCR-22, all {L}",
-           "unit": "ms per call, host clock, synchronised", "device": torch.cuda.get_device_name(0), "sizes": {}}
+           "unit": "ms per call, host clock, synchronised", "yuv_format": a.format, "device": torch.cuda.get_device_name(0), "sizes": {}}
     for n, calls in sizes:
         res["sizes"][str(n)] = run(ctx, n, calls, bgr, nv12, stack, gt, torch)
         print(n, json.dumps(res["sizes"][str(n)]), flush=True)

@@ -42,7 +42,7 @@ def timed(torch, stream, fn):
     return {"median_ms": float(np.median(ev)), "spread_ms": float(max(ev) - min(ev)), "host_median_ms": float(np.median(host)), "calls": CALLS}
 
 
-def child(rows, per_frame):
+def child(rows, per_frame, fmt="nv12"):
     sys.path.insert(0, ROOT)
     import torch
     from superviseddescent_amd import HoGParam, LinearRegressor, SupervisedDescentOptimiser, alignment_template, detection_model, ibug
@@ -60,7 +60,7 @@ def child(rows, per_frame):
     store = torch.empty((n_frames, H, W, 3), dtype=torch.uint8, device="cuda").random_(0, 256)
     nv12 = torch.empty((n_frames, H + H // 2, W), dtype=torch.uint8, device="cuda").random_(0, 256)        # the UV plane behind Y
     frames = [(store[i].data_ptr(), W, H, W * 3, "bgr") for i in range(n_frames)]
-    f_nv12 = [(nv12[i].data_ptr(), W, H, W, "nv12") for i in range(n_frames)]
+    f_nv12 = [(nv12[i].data_ptr(), W, H, W, fmt) for i in range(n_frames)]
     ctx.set_frames_device(frames)
     ctx.set_sample_image_index(np.arange(rows) // per_frame)
     # the rows of scripts/warp_paste_timing.py: the same generator, the same draws
@@ -111,16 +111,17 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "warp_paste_nv12_timing.json"))
     ap.add_argument("--reference", default=os.path.join(ROOT, "profiles", "warp_paste_timing.json"))
+    ap.add_argument("--format", default="nv12", help='the NV12 destinations\' name: "nv12" (value 5), "nv12:bt709", "nv12:bt2020:full", ...')
     ap.add_argument("--child", nargs=2, type=int, default=None)
     a = ap.parse_args()
     if a.child:
-        return child(*a.child)
+        return child(*a.child, a.format)
     recorded = {}
     if os.path.exists(a.reference):
         recorded = {(r["rows"], r["faces_per_frame"]): r["warp_paste"]["median_ms"] for r in json.load(open(a.reference))["runs"]}
     runs = []
     for rows, per_frame in CASES:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", str(rows), str(per_frame)], capture_output=True, text=True,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--format", a.format, "--child", str(rows), str(per_frame)], capture_output=True, text=True,
                            timeout=240)
         if r.returncode != 0:
             sys.stderr.write(r.stdout + r.stderr)

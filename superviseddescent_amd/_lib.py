@@ -86,6 +86,20 @@ FRAME_FORMATS = {"gray": SDM_FRAME_GRAY, "bgr": SDM_FRAME_BGR, "rgb": SDM_FRAME_
 SDM_FRAME_BGR_PLANAR, SDM_FRAME_RGB_PLANAR = 16, 17
 FRAME_FORMATS.update({"bgr_planar": SDM_FRAME_BGR_PLANAR, "rgb_planar": SDM_FRAME_RGB_PLANAR})
 _FRAME_PLANAR = (SDM_FRAME_BGR_PLANAR, SDM_FRAME_RGB_PLANAR)
+# YUV colour description and 10-bit surfaces (include/sdm.h): a YUV frame's name is base[:matrix][:range] -- "nv12:bt709",
+# "nv12:bt601:full", "p010:bt2020", "p010" -- and its value the base or-ed with the matrix and range bits; "nv12" alone stays 5
+SDM_FRAME_P010 = 7                                                        # (6 stays free: always refused as an unknown format)
+_FRAME_YUV_BASES = {"nv12": SDM_FRAME_NV12, "p010": SDM_FRAME_P010}       # (FRAME_FORMATS stays the table of the 8-bit formats)
+SDM_FRAME_YUV_BT601, SDM_FRAME_YUV_BT709, SDM_FRAME_YUV_BT2020, SDM_FRAME_YUV_FULL = 0x000, 0x100, 0x200, 0x1000
+FRAME_MATRICES = {"bt601": SDM_FRAME_YUV_BT601, "bt709": SDM_FRAME_YUV_BT709, "bt2020": SDM_FRAME_YUV_BT2020}
+FRAME_RANGES = {"limited": 0, "full": SDM_FRAME_YUV_FULL}
+
+
+def frame_base(code: int) -> int:
+    """SDM_FRAME_BASE of a format value."""
+    return int(code) & 0xff
+
+
 # (bytes per pixel of plane 0; a planar frame is not among the 1-byte frames an H x W tensor can be)
 _FRAME_CHANNELS = {SDM_FRAME_GRAY: 1, SDM_FRAME_NV12: 1, SDM_FRAME_BGR: 3, SDM_FRAME_RGB: 3, SDM_FRAME_BGRA: 4, SDM_FRAME_RGBA: 4}
 
@@ -205,11 +219,24 @@ def check_align_out(out, shape, dtype_name: str):
         raise ValueError("out must be on the device")
 
 
+# every name of a frame format, in lower case: the formats there always were, and base[:matrix][:range] of the YUV bases with each
+# part at most once and in that order (one look-up per frame: a list of thousands names its format once per frame)
+_FRAME_NAMES = dict(FRAME_FORMATS)
+for _base, _code in _FRAME_YUV_BASES.items():
+    for _m, _mbits in [("", 0)] + [(":" + k, v) for k, v in FRAME_MATRICES.items()]:
+        for _r, _rbits in [("", 0)] + [(":" + k, v) for k, v in FRAME_RANGES.items()]:
+            _FRAME_NAMES[_base + _m + _r] = _code | _mbits | _rbits
+
+
 def _frame_format(fmt) -> int:
     if isinstance(fmt, str):
-        if fmt.lower() not in FRAME_FORMATS:
-            raise ValueError(f"unknown frame format {fmt!r}: one of {sorted(FRAME_FORMATS)}")
-        return FRAME_FORMATS[fmt.lower()]
+        code = _FRAME_NAMES.get(fmt)
+        if code is None:
+            code = _FRAME_NAMES.get(fmt.lower())
+        if code is None:
+            raise ValueError(f"unknown frame format {fmt!r}: one of {sorted(FRAME_FORMATS) + ['p010']}, a YUV one as "
+                             f"base[:matrix][:range] with {sorted(FRAME_MATRICES)} and {sorted(FRAME_RANGES)}")
+        return code
     return int(fmt)
 
 
@@ -244,7 +271,8 @@ def _tensor_frame(ptr: int, shape, stride, fmt):
         (h, w), c = shape, 1
         row, px, ch = stride[0], stride[1], 1
         code = SDM_FRAME_GRAY if fmt is None else _frame_format(fmt)
-        if _FRAME_CHANNELS.get(code) != 1:
+        # (NV12 luma with any colour description; a P010 plane is 16-bit words: it comes as a (ptr, w, h, stride, "p010...") tuple)
+        if _FRAME_CHANNELS.get(code if frame_base(code) != SDM_FRAME_NV12 else SDM_FRAME_NV12) != 1:
             raise ValueError("an H x W frame is gray (or NV12 luma)")
     elif len(shape) == 3:
         h, w, c = shape

@@ -44,12 +44,14 @@ ALIGN_HD int align_area_samples(const float m[6], int flags, int mode, int max_s
     return S;
 }
 
-// x / d for x < 2^16 and d in [2, 256]: the high word of x * ceil(2^32 / d).  Exact: with e = ceil(2^32 / d) d - 2^32 < d the high word
-// is floor(x / d + x e / (2^32 d)), and x e < 2^24 keeps the second term below the 1 / d that x / d lacks to the next integer.
+// x / d for x < 2^16 (10-bit taps: x < 2^18) and d in [2, 256]: the high word of x * ceil(2^32 / d).  Exact: with
+// e = ceil(2^32 / d) d - 2^32 < d the high word is floor(x / d + x e / (2^32 d)), and x e < 2^24 (2^26) keeps the second term below the
+// 1 / d that x / d lacks to the next integer.
 ALIGN_HD uint32_t align_area_reciprocal(uint32_t d) { return 0xFFFFFFFFu / d + 1u; }
 ALIGN_HD uint32_t align_area_divide(uint32_t x, uint32_t rcp) { return (uint32_t)(((uint64_t)x * rcp) >> 32); }
 
-// (sum of S S values q <= 255 * 1024 + 512 S S) / (1024 S S): the sum stays below 2^26 + 2^17, the shifted sum below 2^16
+// (sum of S S values q <= 255 * 1024 + 512 S S) / (1024 S S): the sum stays below 2^26 + 2^17, the shifted sum below 2^16 (P010, q <=
+// 1023 * 1024: below 2^28 + 2^17 and 2^18)
 ALIGN_HD uint32_t align_area_average(uint32_t sum, uint32_t n, uint32_t rcp) { return align_area_divide((sum + 512u * n) >> 10, rcp); }
 
 // the NCH un-rounded values q of the element at q (align_taps), added to acc
@@ -62,12 +64,50 @@ ALIGN_HD void align_area_add(const uint8_t* p, int w, int h, int stride, const A
     for (int c = 0; c < NCH; ++c) acc[c] += v[c];
 }
 
+// align_area_add on the 10-bit taps of a P010 plane (E words per element)
+template <int E, bool WIDE>
+ALIGN_HD void align_area_add16(const uint8_t* p, int w, int h, int stride, const AlignPos& q, uint32_t fill, uint32_t acc[E])
+{
+    uint32_t v[E];
+    align_taps16<E, WIDE>(p, w, h, stride, q, fill, v);
+#pragma unroll
+    for (int c = 0; c < E; ++c) acc[c] += v[c];
+}
+
 // KIND: the source as the taps see it
 #define ALIGN_AREA_GRAY 0
 #define ALIGN_AREA_BGR  1      // 3 bytes per pixel
 #define ALIGN_AREA_BGRA 2      // 4 bytes per pixel, the fourth never read
 #define ALIGN_AREA_NV12 3
 #define ALIGN_AREA_PLANAR 4    // three planes of 1 byte per pixel, r.pd apart
+#define ALIGN_AREA_P010 5      // 10-bit taps: sums of at most 256 values <= 1023 * 1024, below 2^32
+#define ALIGN_AREA_P010_LUMA 6 // a one-channel tensor: the luma plane alone
+
+// KIND of a row's format
+ALIGN_HD int align_area_kind(int format)
+{
+    switch (SDM_FRAME_BASE(format)) {
+    case SDM_FRAME_GRAY: return ALIGN_AREA_GRAY;
+    case SDM_FRAME_BGR: case SDM_FRAME_RGB: return ALIGN_AREA_BGR;
+    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return ALIGN_AREA_BGRA;
+    case SDM_FRAME_BGR_PLANAR: case SDM_FRAME_RGB_PLANAR: return ALIGN_AREA_PLANAR;
+    case SDM_FRAME_P010: return (format & YUV_LUMA_ONLY) ? ALIGN_AREA_P010_LUMA : ALIGN_AREA_P010;
+    default: return ALIGN_AREA_NV12;
+    }
+}
+
+// the averaged values a of one pixel -- (g, -, -), (byte 0, 1, 2) or (Y, U, V) -- as (B, G, R): a YUV source is converted once, value 5
+// with the constants it always had
+ALIGN_HD void align_area_finish(int format, const uint32_t a[3], uint32_t px[3])
+{
+    const int base = SDM_FRAME_BASE(format);
+    if (base == SDM_FRAME_GRAY) px[0] = px[1] = px[2] = a[0];
+    else if (format == SDM_FRAME_NV12) align_nv12_to_bgr(a[0], a[1], a[2], px);
+    else if (format & YUV_LUMA_ONLY) px[0] = px[1] = px[2] = yuv_luma8_of_10(a[0]);
+    else if (base == SDM_FRAME_NV12 || base == SDM_FRAME_P010) yuv_to_bgr(yuv_tables.dec[yuv_decode_row(format)], a[0], a[1], a[2], px);
+    else if (align_red_first(format)) { px[0] = a[2]; px[1] = a[1]; px[2] = a[0]; }
+    else { px[0] = a[0]; px[1] = a[1]; px[2] = a[2]; }
+}
 
 // the sums over the S x S sub-samples of up to 4 consecutive crop pixels (row i, columns j0 ... j0 + npx - 1): acc[k] is (g, -, -),
 // (byte 0, 1, 2) or (Y, U, V); ok[k] turns false when one of pixel k's sub-samples is refused by the 2^20 rule
@@ -101,6 +141,14 @@ ALIGN_HD void align_area_sums(const AlignRow& r, int i, int j0, int npx, int S, 
                     align_area_add<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
                     align_area_add<1, 1, WIDE, 0u>(r.p0 + r.pd, r.w, r.h, r.stride, q, acc[k] + 1);
                     align_area_add<1, 1, WIDE, 0u>(r.p0 + r.pd + r.pd, r.w, r.h, r.stride, q, acc[k] + 2);
+                } else if constexpr (KIND == ALIGN_AREA_P010_LUMA) {
+                    align_area_add16<1, WIDE>(r.p0, r.w, r.h, r.stride, q, 0u, acc[k]);
+                } else if constexpr (KIND == ALIGN_AREA_P010) {
+                    align_area_add16<1, WIDE>(r.p0, r.w, r.h, r.stride, q, 0u, acc[k]);
+                    AlignPos qc;
+                    if (align_quantise(sx * 0.5f, sy * 0.5f, qc))
+                        align_area_add16<2, WIDE>(r.p1, cw, ch, r.cstride, qc, 512u, acc[k] + 1);
+                    else { acc[k][1] += 512u * 1024u; acc[k][2] += 512u * 1024u; }
                 } else {
                     align_area_add<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
                     AlignPos qc;
@@ -122,27 +170,27 @@ ALIGN_HD void align_area_segment(const AlignRow& r, int i, int j0, int npx, int 
     bool ok[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) { acc[k][0] = acc[k][1] = acc[k][2] = 0u; ok[k] = k < npx; }
-    switch (r.format) {
-    case SDM_FRAME_GRAY: align_area_sums<ALIGN_AREA_GRAY, WIDE>(r, i, j0, npx, S, acc, ok); break;
-    case SDM_FRAME_BGR: case SDM_FRAME_RGB: align_area_sums<ALIGN_AREA_BGR, WIDE>(r, i, j0, npx, S, acc, ok); break;
-    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: align_area_sums<ALIGN_AREA_BGRA, WIDE>(r, i, j0, npx, S, acc, ok); break;
-    case SDM_FRAME_BGR_PLANAR: case SDM_FRAME_RGB_PLANAR: align_area_sums<ALIGN_AREA_PLANAR, WIDE>(r, i, j0, npx, S, acc, ok); break;
+    const int kind = align_area_kind(r.format);
+    switch (kind) {
+    case ALIGN_AREA_GRAY: align_area_sums<ALIGN_AREA_GRAY, WIDE>(r, i, j0, npx, S, acc, ok); break;
+    case ALIGN_AREA_BGR: align_area_sums<ALIGN_AREA_BGR, WIDE>(r, i, j0, npx, S, acc, ok); break;
+    case ALIGN_AREA_BGRA: align_area_sums<ALIGN_AREA_BGRA, WIDE>(r, i, j0, npx, S, acc, ok); break;
+    case ALIGN_AREA_PLANAR: align_area_sums<ALIGN_AREA_PLANAR, WIDE>(r, i, j0, npx, S, acc, ok); break;
+    case ALIGN_AREA_P010: align_area_sums<ALIGN_AREA_P010, WIDE>(r, i, j0, npx, S, acc, ok); break;
+    case ALIGN_AREA_P010_LUMA: align_area_sums<ALIGN_AREA_P010_LUMA, WIDE>(r, i, j0, npx, S, acc, ok); break;
     default: align_area_sums<ALIGN_AREA_NV12, WIDE>(r, i, j0, npx, S, acc, ok); break;
     }
     const uint32_t n = (uint32_t)(S * S), rcp = align_area_reciprocal(n);
+    const bool one = kind == ALIGN_AREA_GRAY || kind == ALIGN_AREA_P010_LUMA;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         px[k][0] = px[k][1] = px[k][2] = 0u;
         if (!ok[k]) continue;
-        if (r.format == SDM_FRAME_GRAY) {
-            px[k][0] = px[k][1] = px[k][2] = align_area_average(acc[k][0], n, rcp);
-        } else {
-            uint32_t a[3];
+        uint32_t a[3] = {align_area_average(acc[k][0], n, rcp), 0u, 0u};
+        if (!one) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) a[c] = align_area_average(acc[k][c], n, rcp);
-            if (r.format == SDM_FRAME_NV12) align_nv12_to_bgr(a[0], a[1], a[2], px[k]);
-            else if (align_red_first(r.format)) { px[k][0] = a[2]; px[k][1] = a[1]; px[k][2] = a[0]; }
-            else { px[k][0] = a[0]; px[k][1] = a[1]; px[k][2] = a[2]; }
+            for (int c = 1; c < 3; ++c) a[c] = align_area_average(acc[k][c], n, rcp);
         }
+        align_area_finish(r.format, a, px[k]);
     }
 }

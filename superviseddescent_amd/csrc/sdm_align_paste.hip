@@ -68,7 +68,9 @@ __global__ __launch_bounds__(PASTE_PREPARE_BLOCK) void paste_area_prepare_kernel
 
 // (area_rows is a parameter of <true, false> too, null there).  PLANAR: the frame list holds a planar colour frame -- only then is the
 // planar case of paste_load / paste_store in the kernel's code, so the lists of the other formats run the text they always ran
-template <bool NV12, bool AREA, bool PLANAR>
+// YUV: an NV12 frame of the list carries a colour description -- the block path takes its constants from the frame's table row
+// (csrc/sdm_yuv_device.h); lists of value 5 alone run the text they always ran
+template <bool NV12, bool AREA, bool PLANAR, bool YUV>
 __global__ __launch_bounds__(PASTE_BLOCK) void paste_kernel_t(const PasteFrameDev* __restrict__ frames, PasteOpt<NV12, uint8_t* const* __restrict__> chroma,
                                                               const PasteRow* __restrict__ rows,
                                                               PasteOpt<NV12 || AREA, const PasteAreaRow* __restrict__> area_rows,
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(PASTE_BLOCK) void paste_kernel_t(const PasteFrameDe
     }
     const PasteFrameDev f = frames[r.frame];
     const int lx = threadIdx.x & (PASTE_TILE_W - 1), ly = threadIdx.x / PASTE_TILE_W;
-    if (!NV12 || f.format != SDM_FRAME_NV12) {
+    if (!NV12 || (YUV ? SDM_FRAME_BASE(f.format) : f.format) != SDM_FRAME_NV12) {
         const int tx = paste_tiles_x(r.x1 - r.x0), ty = paste_tiles_y(r.y1 - r.y0);
         for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
             const int X = r.x0 + paste_tile_x(t, tx) + lx, Y = r.y0 + paste_tile_y(t, tx) + ly;
@@ -108,8 +110,8 @@ __global__ __launch_bounds__(PASTE_BLOCK) void paste_kernel_t(const PasteFrameDe
         for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
             const int BX = bx0 + paste_tile_x(t, tx) + lx, BY = by0 + paste_tile_y(t, tx) + ly;
             if (BX < bx1 && BY < by1) {
-                if constexpr (AREA) paste_owned_block(f, uv, PasteRigidArea{rows, area_rows}, list, k, c, BX, BY);
-                else paste_owned_block(f, uv, PasteRigid{rows}, list, k, c, BX, BY);
+                if constexpr (AREA) paste_owned_block<YUV>(f, uv, PasteRigidArea{rows, area_rows}, list, k, c, BX, BY);
+                else paste_owned_block<YUV>(f, uv, PasteRigid{rows}, list, k, c, BX, BY);
             }
         }
     }
@@ -131,24 +133,27 @@ void sdm_launch_paste_area_prepare(AlignFace* faces, const int* frame_of_row, co
                        0, s, faces, frame_of_row, frames, N, cw, ch, fitted ? 1 : 0, area, rows, area_rows, samples);
 }
 
-template <bool PLANAR>
+// (YUV is a choice of the NV12 launches alone: without NV12 frames there is no block path)
+template <bool PLANAR, bool YUV>
 static void launch_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
                          const int* entry_of_row, int N, const PasteCropDev& crop, hipStream_t s)
 {
     const dim3 grid((unsigned)N, (unsigned)paste_groups(crop)), block(PASTE_BLOCK);
     if (chroma && area_rows)
-        hipLaunchKernelGGL((paste_kernel_t<true, true, PLANAR>), grid, block, 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
+        hipLaunchKernelGGL((paste_kernel_t<true, true, PLANAR, YUV>), grid, block, 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
     else if (chroma)
-        hipLaunchKernelGGL((paste_kernel_t<true, false, PLANAR>), grid, block, 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
+        hipLaunchKernelGGL((paste_kernel_t<true, false, PLANAR, YUV>), grid, block, 0, s, frames, chroma, rows, area_rows, list, entry_of_row, crop);
     else if (area_rows)
-        hipLaunchKernelGGL((paste_kernel_t<false, true, PLANAR>), grid, block, 0, s, frames, PasteNone{}, rows, area_rows, list, entry_of_row, crop);
+        hipLaunchKernelGGL((paste_kernel_t<false, true, PLANAR, false>), grid, block, 0, s, frames, PasteNone{}, rows, area_rows, list, entry_of_row, crop);
     else
-        hipLaunchKernelGGL((paste_kernel_t<false, false, PLANAR>), grid, block, 0, s, frames, PasteNone{}, rows, PasteNone{}, list, entry_of_row, crop);
+        hipLaunchKernelGGL((paste_kernel_t<false, false, PLANAR, false>), grid, block, 0, s, frames, PasteNone{}, rows, PasteNone{}, list, entry_of_row, crop);
 }
 
 void sdm_launch_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
-                      const int* entry_of_row, int N, const PasteCropDev& crop, bool planar, hipStream_t s)
+                      const int* entry_of_row, int N, const PasteCropDev& crop, bool planar, bool yuv, hipStream_t s)
 {
-    if (planar) launch_paste<true>(frames, chroma, rows, area_rows, list, entry_of_row, N, crop, s);
-    else launch_paste<false>(frames, chroma, rows, area_rows, list, entry_of_row, N, crop, s);
+    if (planar && yuv) launch_paste<true, true>(frames, chroma, rows, area_rows, list, entry_of_row, N, crop, s);
+    else if (planar) launch_paste<true, false>(frames, chroma, rows, area_rows, list, entry_of_row, N, crop, s);
+    else if (yuv) launch_paste<false, true>(frames, chroma, rows, area_rows, list, entry_of_row, N, crop, s);
+    else launch_paste<false, false>(frames, chroma, rows, area_rows, list, entry_of_row, N, crop, s);
 }

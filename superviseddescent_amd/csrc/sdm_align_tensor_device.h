@@ -1,5 +1,6 @@
 // sdm_align_tensor_device.h -- the per-pixel arithmetic of the crop tensors (include/sdm.h: sdm_align_crops_tensor, its filtered form and
-// sdm_warp_crops_tensor): positions, taps, the integer bilinear blend, the NV12 conversion, the channel rules and the element formula.
+// sdm_warp_crops_tensor): positions, taps (bytes, and the 16-bit words of P010), the integer bilinear blend, the NV12 conversion (a
+// described YUV frame's: sdm_yuv_device.h), the channel rules and the element formula.
 // The one pixel fetch of the three calls is here: align_fetch_segment takes four source positions (the warp's, one matrix per pixel),
 // align_segment forms them from a row's one matrix, and align_taps is the weighted tap sum under both align_bilinear and the area
 // sums of sdm_align_area_device.h.  Plain C++ behind one macro, so the same text is the device code of the kernel frame
@@ -10,6 +11,7 @@
 // else is int32 / uint32 arithmetic.
 #pragma once
 #include "../../include/sdm.h"
+#include "sdm_yuv_device.h"
 
 #include <math.h>
 #include <stdint.h>
@@ -31,9 +33,9 @@ struct AlignRow {
     float m[6];                 // crop -> source
     int w, h, stride;           // plane 0: pixels, rows, bytes per row
     int cstride;                // NV12: bytes per row of the UV plane
-    int format;                 // SDM_FRAME_*
+    int format;                 // SDM_FRAME_*, a YUV frame's with its matrix and range bits
     const uint8_t* p0;          // plane 0 (gray, Y or interleaved pixels)
-    const uint8_t* p1;          // NV12: the interleaved UV plane
+    const uint8_t* p1;          // NV12, P010: the interleaved UV plane
     long long pd;               // planar colour: bytes from plane c to plane c + 1, of any sign
 };
 
@@ -137,6 +139,56 @@ ALIGN_HD void align_bilinear(const uint8_t* p, int w, int h, int stride, const A
     for (int c = 0; c < NCH; ++c) out[c] = (out[c] + 512u) >> 10;
 }
 
+// P010 ("YUV colour description and 10-bit surfaces"): the taps (x0, y) and (x0 + 1, y) of a plane of w x h elements of E 16-bit words,
+// each word >> 6, v[t * E + c]; FILL for a tap outside.  stride in bytes; the last byte read is the last byte of an element inside the
+// plane.
+template <int E, bool WIDE>
+ALIGN_HD void align_tap_row16(const uint8_t* p, int w, int h, int stride, int x0, int y, uint32_t fill, uint32_t v[2 * E])
+{
+#pragma unroll
+    for (int k = 0; k < 2 * E; ++k) v[k] = fill;
+    if (y < 0 || y >= h) return;
+    if (x0 >= 0 && x0 + 1 < w) {
+        const uint8_t* s = align_at<WIDE>(p, y, stride, x0 * 2 * E);
+        uint32_t t[E];
+        memcpy(t, s, 4 * E);
+#pragma unroll
+        for (int k = 0; k < E; ++k) { v[2 * k] = (t[k] & 0xffffu) >> 6; v[2 * k + 1] = t[k] >> 22; }
+        return;
+    }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const int xx = x0 + t;
+        if (xx < 0 || xx >= w) continue;
+#pragma unroll
+        for (int c = 0; c < E; ++c) {
+            uint16_t word;
+            memcpy(&word, align_at<WIDE>(p, y, stride, (xx * E + c) * 2), 2);
+            v[t * E + c] = (uint32_t)word >> 6;
+        }
+    }
+}
+
+// align_taps on 10-bit taps: E un-rounded sums, at most 1023 * 1024
+template <int E, bool WIDE>
+ALIGN_HD void align_taps16(const uint8_t* p, int w, int h, int stride, const AlignPos& q, uint32_t fill, uint32_t sum[E])
+{
+    uint32_t r0[2 * E], r1[2 * E];
+    align_tap_row16<E, WIDE>(p, w, h, stride, q.x0, q.y0, fill, r0);
+    align_tap_row16<E, WIDE>(p, w, h, stride, q.x0, q.y0 + 1, fill, r1);
+    const uint32_t w00 = (32 - q.fx) * (32 - q.fy), w10 = q.fx * (32 - q.fy), w01 = (32 - q.fx) * q.fy, w11 = q.fx * q.fy;
+#pragma unroll
+    for (int c = 0; c < E; ++c) sum[c] = w00 * r0[c] + w10 * r0[E + c] + w01 * r1[c] + w11 * r1[E + c];
+}
+
+template <int E, bool WIDE>
+ALIGN_HD void align_bilinear16(const uint8_t* p, int w, int h, int stride, const AlignPos& q, uint32_t fill, uint32_t out[E])
+{
+    align_taps16<E, WIDE>(p, w, h, stride, q, fill, out);
+#pragma unroll
+    for (int c = 0; c < E; ++c) out[c] = (out[c] + 512u) >> 10;
+}
+
 ALIGN_HD uint32_t align_clamp255(int v) { return (uint32_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
 
 // BT.601 limited range, the constants of OpenCV's COLOR_YUV2BGR_NV12 (20 fractional bits).  Every term stays below 2^30 in magnitude:
@@ -163,7 +215,7 @@ ALIGN_HD void align_fetch_segment(const AlignRow& r, const float sx[4], const fl
         ok[k] = on[k] && align_quantise(sx[k], sy[k], q[k]);
         px[k][0] = px[k][1] = px[k][2] = 0u;
     }
-    switch (r.format) {
+    switch (SDM_FRAME_BASE(r.format)) {
     case SDM_FRAME_GRAY:
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -196,17 +248,49 @@ ALIGN_HD void align_fetch_segment(const AlignRow& r, const float sx[4], const fl
             }
         break;
     }
-    default: {   // SDM_FRAME_NV12
+    case SDM_FRAME_P010: {
+        // 10-bit taps, the decode of the frame's description; a one-channel tensor takes the luma alone
         const int cw = (r.w + 1) >> 1, ch = (r.h + 1) >> 1;
+        const bool luma = (r.format & YUV_LUMA_ONLY) != 0;
+        const YuvDecode t = yuv_tables.dec[yuv_decode_row(r.format)];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ok[k]) {
+                uint32_t y[1], uv[2] = {512u, 512u};
+                align_bilinear16<1, WIDE>(r.p0, r.w, r.h, r.stride, q[k], 0u, y);
+                if (luma) { px[k][0] = px[k][1] = px[k][2] = yuv_luma8_of_10(y[0]); continue; }
+                AlignPos qc;
+                if (align_quantise(sx[k] * 0.5f, sy[k] * 0.5f, qc))
+                    align_bilinear16<2, WIDE>(r.p1, cw, ch, r.cstride, qc, 512u, uv);
+                yuv_to_bgr(t, y[0], uv[0], uv[1], px[k]);
+            }
+        break;
+    }
+    default: {   // SDM_FRAME_NV12: value 5 with the constants it always had, a described frame with its table row
+        const int cw = (r.w + 1) >> 1, ch = (r.h + 1) >> 1;
+        if (r.format == SDM_FRAME_NV12) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (ok[k]) {
+                    uint32_t y[1], uv[2] = {128u, 128u};
+                    align_bilinear<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q[k], y);
+                    AlignPos qc;
+                    if (align_quantise(sx[k] * 0.5f, sy[k] * 0.5f, qc))       // (exact halves: never refused behind an accepted luma position)
+                        align_bilinear<2, 2, WIDE, 128u>(r.p1, cw, ch, r.cstride, qc, uv);
+                    align_nv12_to_bgr(y[0], uv[0], uv[1], px[k]);
+                }
+            break;
+        }
+        const YuvDecode t = yuv_tables.dec[yuv_decode_row(r.format)];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (ok[k]) {
                 uint32_t y[1], uv[2] = {128u, 128u};
                 align_bilinear<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q[k], y);
                 AlignPos qc;
-                if (align_quantise(sx[k] * 0.5f, sy[k] * 0.5f, qc))       // (exact halves: never refused behind an accepted luma position)
+                if (align_quantise(sx[k] * 0.5f, sy[k] * 0.5f, qc))
                     align_bilinear<2, 2, WIDE, 128u>(r.p1, cw, ch, r.cstride, qc, uv);
-                align_nv12_to_bgr(y[0], uv[0], uv[1], px[k]);
+                yuv_to_bgr(t, y[0], uv[0], uv[1], px[k]);
             }
         break;
     }

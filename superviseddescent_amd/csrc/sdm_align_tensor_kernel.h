@@ -96,11 +96,14 @@ __global__ __launch_bounds__(ALIGN_T_BLOCK) void align_tensor_kernel(const uint8
     } else {
         r.p0 = base + f.off; r.p1 = nullptr; r.stride = f.stride; r.cstride = 0; r.format = src_format; r.pd = 0;
     }
-    if (CH == 1 && r.format == SDM_FRAME_NV12) r.format = SDM_FRAME_GRAY;        // Y as it is: the chroma plane is not read
+    const int fbase = SDM_FRAME_BASE(r.format);
+    if (CH == 1 && fbase == SDM_FRAME_NV12) r.format = SDM_FRAME_GRAY;          // Y as it is, whatever the description: the chroma plane is not read
+    if (CH == 1 && fbase == SDM_FRAME_P010) r.format |= YUV_LUMA_ONLY;          // the 10-bit luma alone
     const bool weigh = (r.format >= SDM_FRAME_BGR && r.format <= SDM_FRAME_RGBA) || align_planar(r.format);
-    // offsets inside a plane are 32-bit when rows * stride fit 31 bits
+    // offsets inside a plane are 32-bit when rows * stride (bytes) fit 31 bits
+    const bool two = fbase == SDM_FRAME_P010 || (CH != 1 && fbase == SDM_FRAME_NV12);
     const bool narrow = (long long)r.h * r.stride <= (long long)INT_MAX &&
-                        (r.format != SDM_FRAME_NV12 || (long long)((r.h + 1) >> 1) * r.cstride <= (long long)INT_MAX);
+                        (!two || (long long)((r.h + 1) >> 1) * r.cstride <= (long long)INT_MAX);
     uint32_t px[4][3];
     if (narrow) p.template pixels<false>(a, f, r, i, j0, npx, out_w, px);
     else p.template pixels<true>(a, f, r, i, j0, npx, out_w, px);

@@ -245,11 +245,11 @@ int sdm_align_set_source_frames(sdm_ctx* c, const sdm_frame* frames, const void*
         const int bpp = frame_bpp(f.format);
         AlignFrameDev& d = tab[i];
         d.p0 = (const uint8_t*)f.data; d.p1 = nullptr; d.stride = f.stride_bytes; d.cstride = 0; d.format = f.format; d.pad = 0;
-        if (f.format == SDM_FRAME_NV12) {
-            if ((long long)f.stride_bytes < 2ll * ((f.width + 1) / 2))
-                return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": an NV12 frame needs stride_bytes >= 2 * ((width + 1) / 2)");
+        const int fbase = SDM_FRAME_BASE(f.format);
+        if (fbase == SDM_FRAME_NV12 || fbase == SDM_FRAME_P010) {
             const void* uv = chroma ? chroma[i] : nullptr;
             d.p1 = uv ? (const uint8_t*)uv : (const uint8_t*)f.data + (size_t)f.height * (size_t)f.stride_bytes;
+            if ((rc = check_frame_uv(i, f, d.p1))) return rc;
             d.cstride = f.stride_bytes;
         }
         if (frame_planar(f.format)) {
@@ -257,7 +257,7 @@ int sdm_align_set_source_frames(sdm_ctx* c, const sdm_frame* frames, const void*
             if ((rc = frame_plane_distance(i, f, chroma ? chroma[i] : nullptr, D))) return rc;
             d.p1 = (const uint8_t*)f.data + D;
         }
-        const int kind = f.format == SDM_FRAME_NV12 || frame_planar(f.format) ? 0 : bpp;
+        const int kind = fbase == SDM_FRAME_NV12 || fbase == SDM_FRAME_P010 || frame_planar(f.format) ? 0 : bpp;
         bpp_all = bpp_all < 0 ? kind : (bpp_all == kind ? kind : 0);
         if (!lowest || d.p0 < lowest) lowest = d.p0;
     }
@@ -281,7 +281,7 @@ int sdm_align_crops(sdm_ctx* c, const int* lm, const float* tmpl, int K, int out
     sdm_ctx::Align& a = c->align;
     const bool external = a.base != nullptr, list = !a.fr.empty();
     if (list && a.fr_bpp == 0)
-        return fail(SDM_ERR_INVALID, "the frame-list source holds NV12 or planar frames or frames of different pixel sizes: use sdm_align_crops_tensor");
+        return fail(SDM_ERR_INVALID, "the frame-list source holds NV12, P010 or planar frames or frames of different pixel sizes: use sdm_align_crops_tensor");
     const int C = external ? a.C : list ? a.fr_bpp : 1;
     if (!out) return fail(SDM_ERR_INVALID, "no output");
     if (out_on_device && ((uintptr_t)out % (C == 4 ? 16 : 4)) != 0)

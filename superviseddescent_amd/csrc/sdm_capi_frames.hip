@@ -4,10 +4,17 @@
 
 #include <limits.h>
 
+// 0: not a format -- an unknown base; a matrix or range bit on a base that is not NV12 or P010; a matrix field above BT.2020; any other
+// set bit ("YUV colour description and 10-bit surfaces")
 int sdm_capi::frame_bpp(int format)
 {
-    switch (format) {
+    const int base = SDM_FRAME_BASE(format);
+    if (format < 0 || (format & ~(0xff | 0xf00 | SDM_FRAME_YUV_FULL))) return 0;
+    if ((format & ~0xff) && base != SDM_FRAME_NV12 && base != SDM_FRAME_P010) return 0;
+    if ((format & 0xf00) > SDM_FRAME_YUV_BT2020) return 0;
+    switch (base) {
     case SDM_FRAME_GRAY: case SDM_FRAME_NV12: case SDM_FRAME_BGR_PLANAR: case SDM_FRAME_RGB_PLANAR: return 1;
+    case SDM_FRAME_P010: return 2;
     case SDM_FRAME_BGR: case SDM_FRAME_RGB: return 3;
     case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: return 4;
     default: return 0;
@@ -15,6 +22,22 @@ int sdm_capi::frame_bpp(int format)
 }
 
 bool sdm_capi::frame_planar(int format) { return format == SDM_FRAME_BGR_PLANAR || format == SDM_FRAME_RGB_PLANAR; }
+
+bool sdm_capi::frame_in_place(int format) { const int b = SDM_FRAME_BASE(format); return b == SDM_FRAME_GRAY || b == SDM_FRAME_NV12; }
+
+int sdm_capi::check_frame_uv(int i, const sdm_frame& f, const void* uv)
+{
+    const std::string at = "frame " + std::to_string(i) + ": ";
+    const int base = SDM_FRAME_BASE(f.format);
+    if (base == SDM_FRAME_NV12 && (long long)f.stride_bytes < 2ll * ((f.width + 1) / 2))
+        return fail(SDM_ERR_INVALID, at + "an NV12 frame needs stride_bytes >= 2 * ((width + 1) / 2)");
+    if (base == SDM_FRAME_P010) {
+        if ((long long)f.stride_bytes < 4ll * ((f.width + 1) / 2))
+            return fail(SDM_ERR_INVALID, at + "a P010 frame needs stride_bytes >= 4 * ((width + 1) / 2)");
+        if ((uintptr_t)uv & 1) return fail(SDM_ERR_INVALID, at + "the UV plane of a P010 frame must be 2-byte aligned");
+    }
+    return SDM_OK;
+}
 
 int sdm_capi::frame_plane_distance(int i, const sdm_frame& f, const void* second, long long& D)
 {
@@ -26,12 +49,14 @@ int sdm_capi::frame_plane_distance(int i, const sdm_frame& f, const void* second
 int sdm_capi::check_frame(int i, const sdm_frame& f, bool allow_nv12)
 {
     const std::string at = "frame " + std::to_string(i) + ": ";
-    if (!allow_nv12 && f.format == SDM_FRAME_NV12) return fail(SDM_ERR_INVALID, at + "an NV12 frame cannot be pasted into");
     const int bpp = frame_bpp(f.format);
+    if (!allow_nv12 && bpp && SDM_FRAME_BASE(f.format) == SDM_FRAME_NV12) return fail(SDM_ERR_INVALID, at + "an NV12 frame cannot be pasted into");
     if (!bpp) return fail(SDM_ERR_INVALID, at + "unknown format");
     if (!f.data) return fail(SDM_ERR_INVALID, at + "null pointer");
     if (f.width < 1 || f.height < 1) return fail(SDM_ERR_INVALID, at + "width and height must be >= 1");
     if ((long long)f.stride_bytes < (long long)f.width * bpp) return fail(SDM_ERR_INVALID, at + "stride_bytes < width * bytes per pixel");
+    if (SDM_FRAME_BASE(f.format) == SDM_FRAME_P010 && ((((uintptr_t)f.data) | (uintptr_t)(unsigned)f.stride_bytes) & 1))
+        return fail(SDM_ERR_INVALID, at + "the pointer and stride_bytes of a P010 frame must be even");
     return SDM_OK;
 }
 
@@ -48,7 +73,7 @@ static int set_frames_device(sdm_ctx* c, const sdm_frame* frames, const void* co
         const sdm_frame& f = frames[i];
         if ((rc = check_frame(i, f, true))) return rc;
         const int bpp = frame_bpp(f.format);
-        if (bpp == 1 && !frame_planar(f.format)) continue;
+        if (frame_in_place(f.format)) continue;
         FrameConvDev d{};
         if (frame_planar(f.format) && (rc = frame_plane_distance(i, f, planes ? planes[i] : nullptr, d.plane))) return rc;
         d.src = (const uint8_t*)f.data; d.dst_off = owned; d.w = f.width; d.h = f.height; d.pitch = f.stride_bytes;
@@ -73,7 +98,7 @@ static int set_frames_device(sdm_ctx* c, const sdm_frame* frames, const void* co
     for (int i = 0, k = 0; i < n; ++i) {
         const sdm_frame& f = frames[i];
         vw[i] = f.width; vh[i] = f.height;
-        if (frame_bpp(f.format) == 1 && !frame_planar(f.format)) { addr[i] = (const uint8_t*)f.data; vs[i] = f.stride_bytes; }
+        if (frame_in_place(f.format)) { addr[i] = (const uint8_t*)f.data; vs[i] = f.stride_bytes; }
         else { addr[i] = c->frames.gray.p + conv[k].dst_off; vs[i] = conv[k].gstride; ++k; }
         narrow = narrow || image_needs_generic(f.width, f.height, vs[i]);      // (the rule of every image entry point)
     }

@@ -414,6 +414,11 @@ int frame_bpp(int format);
 int check_frame(int i, const sdm_frame& frame, bool allow_nv12);
 // SDM_FRAME_BGR_PLANAR | SDM_FRAME_RGB_PLANAR (frame_bpp: 1, the bytes per pixel of a plane)
 bool frame_planar(int format);
+// GRAY and NV12 (any colour description): the image set reads plane 0 where it lies
+bool frame_in_place(int format);
+// what the calls that read or write the UV plane refuse of an NV12 or P010 frame: a UV row that does not fit stride_bytes; P010: an odd
+// UV pointer (uv: the plane's address)
+int check_frame_uv(int i, const sdm_frame& frame, const void* uv);
 // D of a planar frame: second - data, or height * stride_bytes when second is null; 0 is refused
 int frame_plane_distance(int i, const sdm_frame& frame, const void* second, long long& D);
 // (sdm_capi_align.hip) the checks and the element stage's constants that sdm_align_crops_tensor and sdm_warp_crops_tensor share: the

@@ -24,10 +24,13 @@ int paste_check_args(const void* in_dev, const sdm_align_paste* paste, const sdm
     if (paste->alpha_per_row != 0 && paste->alpha_per_row != 1) return fail(SDM_ERR_INVALID, "alpha_per_row must be 0 or 1");
     if (!frames || n_frames < 1) return fail(SDM_ERR_INVALID, "bad frame list");
     int rc;
-    for (int i = 0; i < n_frames; ++i)
+    for (int i = 0; i < n_frames; ++i) {
         if ((rc = check_frame(i, frames[i], nv12))) return rc;
+        if (SDM_FRAME_BASE(frames[i].format) == SDM_FRAME_P010)
+            return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": a P010 frame cannot be pasted into (10-bit destinations are not implemented)");
+    }
     for (int i = 0; i < n_frames; ++i)                               // (the UV plane's row: (width + 1) / 2 byte pairs)
-        if (frames[i].format == SDM_FRAME_NV12 && (long long)frames[i].stride_bytes < 2LL * ((frames[i].width + 1) / 2))
+        if (SDM_FRAME_BASE(frames[i].format) == SDM_FRAME_NV12 && (long long)frames[i].stride_bytes < 2LL * ((frames[i].width + 1) / 2))
             return fail(SDM_ERR_INVALID, "frame " + std::to_string(i) + ": stride_bytes < 2 * ((width + 1) / 2) of an NV12 frame");
     long long D;
     for (int i = 0; i < n_frames; ++i)                               // (a planar frame's second plane: not on the first)
@@ -72,6 +75,7 @@ struct PasteTables {
     const int* list;
     const int* entry;
     bool planar;                    // a planar colour frame is among the frames: the kernels' instances with that case
+    bool yuv;                       // an NV12 frame with a colour description is among them: the instances that read its table row
     std::vector<unsigned char> blob;
 };
 
@@ -85,6 +89,7 @@ int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_fra
     std::vector<unsigned char>& blob = out.blob;
     blob.assign(bytes, 0);
     out.planar = false;
+    out.yuv = false;
     PasteFrameDev* tab = (PasteFrameDev*)blob.data();
     int* of_row = (int*)(blob.data() + tab_bytes);
     int* list = of_row + N;
@@ -100,13 +105,14 @@ int paste_tables(sdm_ctx* c, const std::vector<int>& frame_of_row, const sdm_fra
         d.row_begin = count[i]; d.row_end = count[(size_t)i + 1]; d.pad = 0;
         d.plane = 0;
         out.planar = out.planar || frame_planar(f.format);
+        out.yuv = out.yuv || (SDM_FRAME_BASE(f.format) == SDM_FRAME_NV12 && f.format != SDM_FRAME_NV12);
         if (frame_planar(f.format)) frame_plane_distance(i, f, dst_chroma ? dst_chroma[i] : nullptr, d.plane);      // (checked: not 0)
     }
     if (nv12) {
         uint8_t** uv = (uint8_t**)(blob.data() + uv_at);
         for (int i = 0; i < n_frames; ++i) {
             const sdm_frame& f = frames[i];
-            uv[i] = f.format != SDM_FRAME_NV12 ? nullptr
+            uv[i] = SDM_FRAME_BASE(f.format) != SDM_FRAME_NV12 ? nullptr
                     : dst_chroma && dst_chroma[i] ? (uint8_t*)dst_chroma[i]
                                                   : (uint8_t*)const_cast<void*>(f.data) + (size_t)f.height * (size_t)f.stride_bytes;
         }
@@ -159,7 +165,7 @@ int paste_run(sdm_ctx* c, bool fitted, const std::vector<int>& frame_of_row, int
         sdm_launch_paste_area_prepare(a.faces.p, tab.of_row, tab.frames, N, cw, ch, fitted, align_area_dev(filter), rows_dev, area_dev,
                                       (int*)(a.faces.p + N), c->stream);
     HIP_TRY(hipGetLastError());
-    sdm_launch_paste(tab.frames, tab.chroma, rows_dev, area_dev, tab.list, tab.entry, N, crop, tab.planar, c->stream);   // (tab.chroma: null unless nv12)
+    sdm_launch_paste(tab.frames, tab.chroma, rows_dev, area_dev, tab.list, tab.entry, N, crop, tab.planar, tab.yuv, c->stream);   // (tab.chroma: null unless nv12)
     HIP_TRY(hipGetLastError());
     if (samples_host && !filter) {                                                      // (an NV12 call without a filter: plain bilinear)
         for (int r = 0; r < N; ++r) samples_host[r] = 1;
@@ -205,7 +211,7 @@ int warp_paste_run(sdm_ctx* c, const float* x, const AlignSourceDev& src, const 
         sdm_launch_warp_paste_area_counts(rows_dev, tris_dev, N, T, align_area_dev(filter), counts_dev, samples_dev, c->stream);
         HIP_TRY(hipGetLastError());
     }
-    sdm_launch_warp_paste(tab.frames, tab.chroma, rows_dev, tris_dev, counts_dev, T, tab.list, tab.entry, N, w.labels.p, crop, tab.planar, c->stream);   // (tab.chroma: null unless nv12)
+    sdm_launch_warp_paste(tab.frames, tab.chroma, rows_dev, tris_dev, counts_dev, T, tab.list, tab.entry, N, w.labels.p, crop, tab.planar, tab.yuv, c->stream);   // (tab.chroma: null unless nv12)
     HIP_TRY(hipGetLastError());
     // the matrices and the rows' records (a filtered call: with the counts behind them, in the same copy), one synchronise
     if (!filter) samples_host = nullptr;

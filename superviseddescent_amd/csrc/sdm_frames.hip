@@ -1,6 +1,7 @@
 // sdm_frames.hip -- colour frames that are already on the device -> the context's gray images (sdm_set_frames_device, include/sdm.h).
-// One launch converts every colour frame of a call: interleaved BGR / RGB / BGRA / RGBA and planar BGR / RGB (three planes of one byte
-// per pixel, any signed distance apart) of any size, pitch and pointer alignment into gray images the context owns, with the
+// One launch converts every colour frame of a call: interleaved BGR / RGB / BGRA / RGBA, planar BGR / RGB (three planes of one byte
+// per pixel, any signed distance apart) and the luma plane of P010 (16-bit words, gray = min(255, ((word >> 6) + 2) >> 2): include/sdm.h,
+// "YUV colour description and 10-bit surfaces") of any size, pitch and pointer alignment into gray images the context owns, with the
 // arithmetic of bgr2gray_kernel (sdm_apply.hip; cv::cvtColor's fixed-point weights, adaptive_vlhog.hpp:114-120).  The source is
 // only read.
 #include "sdm_kernels.h"
@@ -83,6 +84,24 @@ __global__ void __launch_bounds__(256) frames_to_gray_kernel(const FrameConvDev*
 #pragma unroll
             for (int k = 0; k < 16; ++k)
                 if (k < npx) out[k >> 2] |= gray_of(p0[k], p1[k], p2[k], c0, c1, c2, half, shift) << (8 * (k & 3));
+        }
+    } else if (f.bpp == 2) {
+        // P010 luma: 16 words of 16 bits, the sample in bits 15..6; gray = min(255, ((word >> 6) + 2) >> 2).  The UV plane is not read.
+        gbytes p = rowp + (size_t)c * 32;
+        if (npx == 16 && ((size_t)rowp & 3) == 0) {
+            const __attribute__((address_space(1))) Quad* q = (const __attribute__((address_space(1))) Quad*)p;
+            const u32x4 a = q[0].v, b = q[1].v;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const unsigned pair = k < 8 ? a[k >> 1] : b[(k - 8) >> 1];
+                const unsigned word = (k & 1) ? pair >> 16 : pair & 0xffffu;
+                out[k >> 2] |= min(255u, ((word >> 6) + 2u) >> 2) << (8 * (k & 3));
+            }
+        } else {
+            const __attribute__((address_space(1))) uint16_t* w16 = (const __attribute__((address_space(1))) uint16_t*)p;
+#pragma unroll
+            for (int k = 0; k < 16; ++k)
+                if (k < npx) out[k >> 2] |= min(255u, (((unsigned)w16[k] >> 6) + 2u) >> 2) << (8 * (k & 3));
         }
     } else if (npx == 16 && ((size_t)rowp & 3) == 0) {
         if (f.bpp == 3) {

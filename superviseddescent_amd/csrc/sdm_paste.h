@@ -40,9 +40,10 @@ void sdm_launch_paste_area_prepare(AlignFace* faces, const int* frame_of_row, co
 // the paste behind either prepare stage: paste_kernel_t<chroma != null, area_rows != null, planar>; planar: the frame list holds a planar
 // colour frame (only those instances carry the planar case of the pixel's load and store).  list: the rows of every frame, ascending
 // (PasteFrameDev::row_begin / row_end); entry_of_row: where row n stands in it.  chroma: null -- no frame is NV12 --, or one UV plane
-// per frame (read for NV12 frames only); area_rows: null -- plain bilinear --, or the filtered prepare stage's records
+// per frame (read for NV12 frames only); area_rows: null -- plain bilinear --, or the filtered prepare stage's records.  yuv: an NV12
+// frame of the list carries a colour description (a matrix or range bit): the instances whose block path reads its table row
 void sdm_launch_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const PasteRow* rows, const PasteAreaRow* area_rows, const int* list,
-                      const int* entry_of_row, int N, const PasteCropDev& crop, bool planar, hipStream_t s);
+                      const int* entry_of_row, int N, const PasteCropDev& crop, bool planar, bool yuv, hipStream_t s);
 // x: N x 2L; lm: the mesh's K landmark indices; tri: T triangles; faces, matrices: the N records (their FOLDED bit is read) and the
 // N x T x 6 floats of sdm_launch_warp_fit; frame_of_row: N checked indices into frames.  rows: N records; tris: N x T records
 void sdm_launch_warp_paste_prepare(const float* x, int N, int L, const int* lm, int K, const WarpTri* tri, int T, const WarpFace* faces,
@@ -57,4 +58,4 @@ void sdm_launch_warp_paste_area_counts(const WarpPasteRow* rows, const WarpPaste
 // null: the filtered calls take a list that may mix NV12 and the per-pixel formats)
 void sdm_launch_warp_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris,
                            const uint16_t* counts, int T, const int* list, const int* entry_of_row, int N, const uint8_t* labels,
-                           const PasteCropDev& crop, bool planar, hipStream_t s);
+                           const PasteCropDev& crop, bool planar, bool yuv, hipStream_t s);

@@ -21,7 +21,7 @@ struct PasteFrameDev {
     uint8_t* p;
     long long stride;
     long long plane;            // planar colour: bytes from plane c to plane c + 1, of any sign (0 otherwise)
-    int w, h, format;           // SDM_FRAME_GRAY ... SDM_FRAME_RGBA, SDM_FRAME_NV12 (the block path), SDM_FRAME_*_PLANAR
+    int w, h, format;           // SDM_FRAME_GRAY ... SDM_FRAME_RGBA, SDM_FRAME_NV12 with its matrix and range bits (the block path), SDM_FRAME_*_PLANAR
     int row_begin, row_end;
     int pad;
 };
@@ -271,10 +271,17 @@ ALIGN_HD void paste_block_load(const PasteFrameDev& f, uint8_t* chroma, const Pa
     s.wrote = 0;
 }
 
-// a row's colour and opacity (a != 0) on pixel i: the luma blend; the opacity-weighted colour sums of the row's chroma rule
-ALIGN_HD void paste_block_luma(const PasteCropDev& c, const uint32_t bgr[3], uint32_t a, int i, PasteBlock& s, uint32_t sum[3], uint32_t& A)
+// a row's colour and opacity (a != 0) on pixel i: the luma blend; the opacity-weighted colour sums of the row's chroma rule.
+// YUV false: every NV12 frame of the call is value 5, the constants are in the code as they always were; YUV true: a frame of the call
+// carries a colour description ("YUV colour description and 10-bit surfaces"), the constants are enc, the frame's table row (value 5's
+// included)
+template <bool YUV = false>
+ALIGN_HD void paste_block_luma(const PasteCropDev& c, const uint32_t bgr[3], uint32_t a, int i, PasteBlock& s, uint32_t sum[3], uint32_t& A,
+                               const YuvEncode* enc = nullptr)
 {
-    const uint32_t yq = c.channels == 3 ? paste_nv12_luma(bgr) : bgr[0];
+    uint32_t yq;
+    if constexpr (YUV) yq = c.channels == 3 ? yuv_luma(*enc, bgr) : bgr[0];
+    else yq = c.channels == 3 ? paste_nv12_luma(bgr) : bgr[0];
     const uint32_t o = s.luma >> (8 * i) & 255u;
     s.luma = (s.luma & ~(255u << (8 * i))) | paste_blend(a, yq, o) << (8 * i);
     s.wrote |= 1 << i;
@@ -284,14 +291,16 @@ ALIGN_HD void paste_block_luma(const PasteCropDev& c, const uint32_t bgr[3], uin
 }
 
 // a row's chroma: the opacity-weighted mean colour of the block's pixels, converted, blended with the mean opacity over cnt
-ALIGN_HD void paste_block_chroma(const uint32_t sum[3], uint32_t A, PasteBlock& s)
+template <bool YUV = false>
+ALIGN_HD void paste_block_chroma(const uint32_t sum[3], uint32_t A, PasteBlock& s, const YuvEncode* enc = nullptr)
 {
     if (!s.uv || A == 0u) return;
     const uint32_t m[3] = {(sum[0] + A / 2u) / A, (sum[1] + A / 2u) / A, (sum[2] + A / 2u) / A};
     const uint32_t ac = (A + s.cnt / 2u) / s.cnt;
     if (ac == 0u) return;
     uint32_t uq, vq;
-    paste_nv12_chroma(m, uq, vq);
+    if constexpr (YUV) yuv_chroma(*enc, m, uq, vq);
+    else paste_nv12_chroma(m, uq, vq);
     s.u = paste_blend(ac, uq, s.u);
     s.v = paste_blend(ac, vq, s.v);
     s.wrote |= 16;
@@ -326,7 +335,7 @@ ALIGN_HD int paste_block_holds(const PasteFrameDev& f, const Shape& shape, int n
 // at a time, the block's state is five registers.
 // paste_owned_block_state: the rule up to the store -- false: not this entry's block; true: s is the block as it is to be stored (what the
 // host program of tests/cpp reads the written bytes from).
-template <class Shape>
+template <bool YUV = false, class Shape>
 ALIGN_HD bool paste_owned_block_state(const PasteFrameDev& f, uint8_t* chroma, const Shape& shape, const int* list, int k, const PasteCropDev& c,
                                       int BX, int BY, PasteBlock& s)
 {
@@ -334,6 +343,7 @@ ALIGN_HD bool paste_owned_block_state(const PasteFrameDev& f, uint8_t* chroma, c
     for (int j = f.row_begin; j < k; ++j)
         if (paste_block_holds(f, shape, list[j], c, BX, BY)) return false;
     paste_block_load(f, chroma, c, BX, BY, s);
+    const YuvEncode* const enc = YUV ? &yuv_tables.enc[yuv_encode_row(f.format)] : nullptr;
     for (int j = k; j < f.row_end; ++j) {
         const int n = list[j];
         uint32_t sum[3] = {0u, 0u, 0u}, A = 0u;
@@ -344,17 +354,17 @@ ALIGN_HD bool paste_owned_block_state(const PasteFrameDev& f, uint8_t* chroma, c
             if (!(s.in >> i & 1) || !paste_holds(shape, n, c, X, Y, q)) continue;
             uint32_t bgr[3], a;
             paste_taps(shape, c, n, X, Y, q, bgr, a);
-            if (a != 0u) paste_block_luma(c, bgr, a, i, s, sum, A);
+            if (a != 0u) paste_block_luma<YUV>(c, bgr, a, i, s, sum, A, enc);
         }
-        paste_block_chroma(sum, A, s);
+        paste_block_chroma<YUV>(sum, A, s, enc);
     }
     return true;
 }
 
-template <class Shape>
+template <bool YUV = false, class Shape>
 ALIGN_HD void paste_owned_block(const PasteFrameDev& f, uint8_t* chroma, const Shape& shape, const int* list, int k, const PasteCropDev& c,
                                 int BX, int BY)
 {
     PasteBlock s;
-    if (paste_owned_block_state(f, chroma, shape, list, k, c, BX, BY, s)) paste_block_store(s);
+    if (paste_owned_block_state<YUV>(f, chroma, shape, list, k, c, BX, BY, s)) paste_block_store(s);
 }

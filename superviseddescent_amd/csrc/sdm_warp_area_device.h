@@ -68,6 +68,14 @@ ALIGN_HD void warp_area_sums(const AlignRow& r, const WarpAreaRec* rec, const in
                     align_area_add<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
                     align_area_add<1, 1, WIDE, 0u>(r.p0 + r.pd, r.w, r.h, r.stride, q, acc[k] + 1);
                     align_area_add<1, 1, WIDE, 0u>(r.p0 + r.pd + r.pd, r.w, r.h, r.stride, q, acc[k] + 2);
+                } else if constexpr (KIND == ALIGN_AREA_P010_LUMA) {
+                    align_area_add16<1, WIDE>(r.p0, r.w, r.h, r.stride, q, 0u, acc[k]);
+                } else if constexpr (KIND == ALIGN_AREA_P010) {
+                    align_area_add16<1, WIDE>(r.p0, r.w, r.h, r.stride, q, 0u, acc[k]);
+                    AlignPos qc;
+                    if (align_quantise(sx * 0.5f, sy * 0.5f, qc))
+                        align_area_add16<2, WIDE>(r.p1, cw, ch, r.cstride, qc, 512u, acc[k] + 1);
+                    else { acc[k][1] += 512u * 1024u; acc[k][2] += 512u * 1024u; }
                 } else {
                     align_area_add<1, 1, WIDE, 0u>(r.p0, r.w, r.h, r.stride, q, acc[k]);
                     AlignPos qc;
@@ -97,27 +105,27 @@ ALIGN_HD void warp_area_segment(const AlignRow& r, const WarpAreaRec* rec, const
     bool ok[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) { acc[k][0] = acc[k][1] = acc[k][2] = 0u; ok[k] = lab[k] >= 0; }
-    switch (r.format) {
-    case SDM_FRAME_GRAY: warp_area_sums<ALIGN_AREA_GRAY, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
-    case SDM_FRAME_BGR: case SDM_FRAME_RGB: warp_area_sums<ALIGN_AREA_BGR, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
-    case SDM_FRAME_BGRA: case SDM_FRAME_RGBA: warp_area_sums<ALIGN_AREA_BGRA, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
-    case SDM_FRAME_BGR_PLANAR: case SDM_FRAME_RGB_PLANAR: warp_area_sums<ALIGN_AREA_PLANAR, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
+    const int kind = align_area_kind(r.format);
+    switch (kind) {
+    case ALIGN_AREA_GRAY: warp_area_sums<ALIGN_AREA_GRAY, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
+    case ALIGN_AREA_BGR: warp_area_sums<ALIGN_AREA_BGR, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
+    case ALIGN_AREA_BGRA: warp_area_sums<ALIGN_AREA_BGRA, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
+    case ALIGN_AREA_PLANAR: warp_area_sums<ALIGN_AREA_PLANAR, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
+    case ALIGN_AREA_P010: warp_area_sums<ALIGN_AREA_P010, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
+    case ALIGN_AREA_P010_LUMA: warp_area_sums<ALIGN_AREA_P010_LUMA, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
     default: warp_area_sums<ALIGN_AREA_NV12, WIDE>(r, rec, lab, i, j0, acc, cnt, ok); break;
     }
+    const bool one = kind == ALIGN_AREA_GRAY || kind == ALIGN_AREA_P010_LUMA;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         px[k][0] = px[k][1] = px[k][2] = 0u;
         if (!ok[k]) continue;
         const uint32_t n = cnt[k], rcp = n > 1u ? align_area_reciprocal(n) : 0u;
-        if (r.format == SDM_FRAME_GRAY) {
-            px[k][0] = px[k][1] = px[k][2] = warp_area_average(acc[k][0], n, rcp);
-        } else {
-            uint32_t a[3];
+        uint32_t a[3] = {warp_area_average(acc[k][0], n, rcp), 0u, 0u};
+        if (!one) {
 #pragma unroll
-            for (int c = 0; c < 3; ++c) a[c] = warp_area_average(acc[k][c], n, rcp);
-            if (r.format == SDM_FRAME_NV12) align_nv12_to_bgr(a[0], a[1], a[2], px[k]);
-            else if (align_red_first(r.format)) { px[k][0] = a[2]; px[k][1] = a[1]; px[k][2] = a[0]; }
-            else { px[k][0] = a[0]; px[k][1] = a[1]; px[k][2] = a[2]; }
+            for (int c = 1; c < 3; ++c) a[c] = warp_area_average(acc[k][c], n, rcp);
         }
+        align_area_finish(r.format, a, px[k]);
     }
 }

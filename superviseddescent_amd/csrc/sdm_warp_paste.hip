@@ -123,7 +123,9 @@ __global__ __launch_bounds__(WPASTE_COUNTS_BLOCK) void warp_paste_area_counts_ke
 
 // (the PasteMesh is built where it is used: a named one ahead of the walk renumbers registers in <false, false>)
 // PLANAR: the frame list holds a planar colour frame (paste_kernel_t's rule, csrc/sdm_align_paste.hip)
-template <bool NV12, bool AREA, bool PLANAR>
+// YUV: an NV12 frame of the list carries a colour description -- the block path takes its constants from the frame's table row
+// (csrc/sdm_yuv_device.h); lists of value 5 alone run the text they always ran
+template <bool NV12, bool AREA, bool PLANAR, bool YUV>
 __global__ __launch_bounds__(PASTE_BLOCK) void warp_paste_kernel_t(const PasteFrameDev* __restrict__ frames,
                                                                     PasteOpt<NV12, uint8_t* const* __restrict__> chroma,
                                                                     const WarpPasteRow* __restrict__ rows, const WarpPasteTri* __restrict__ tris,
@@ -149,7 +151,7 @@ __global__ __launch_bounds__(PASTE_BLOCK) void warp_paste_kernel_t(const PasteFr
     }
     __syncthreads();
     const int lx = threadIdx.x & (PASTE_TILE_W - 1), ly = threadIdx.x / PASTE_TILE_W;
-    if (!NV12 || f.format != SDM_FRAME_NV12) {
+    if (!NV12 || (YUV ? SDM_FRAME_BASE(f.format) : f.format) != SDM_FRAME_NV12) {
         const int tx = paste_tiles_x(bw), ty = paste_tiles_y(bh);
         for (long long t = blockIdx.y; t < (long long)tx * ty; t += gridDim.y) {
             const int X0 = r.x0 + paste_tile_x(t, tx), Y = r.y0 + paste_tile_y(t, tx) + ly;
@@ -227,10 +229,10 @@ __global__ __launch_bounds__(PASTE_BLOCK) void warp_paste_kernel_t(const PasteFr
             // (a lane whose block the row does not hold -- beyond bx1 too: nothing was open -- leaves before any ownership test)
             if (winners != 0xffffffffu) {
                 if constexpr (AREA)
-                    paste_owned_block(f, uv, PasteMeshAreaOwn{PasteMeshArea{PasteMesh{rows, tris, T, labels}, counts, -1}, n, winners, lds, lds_counts},
+                    paste_owned_block<YUV>(f, uv, PasteMeshAreaOwn{PasteMeshArea{PasteMesh{rows, tris, T, labels}, counts, -1}, n, winners, lds, lds_counts},
                                       list, k, c, BX, BY);
                 else
-                    paste_owned_block(f, uv, PasteMeshOwn{PasteMesh{rows, tris, T, labels}, n, winners, lds}, list, k, c, BX, BY);
+                    paste_owned_block<YUV>(f, uv, PasteMeshOwn{PasteMesh{rows, tris, T, labels}, n, winners, lds}, list, k, c, BX, BY);
             }
         }
     }
@@ -255,26 +257,28 @@ void sdm_launch_warp_paste_area_counts(const WarpPasteRow* rows, const WarpPaste
                        dim3(WPASTE_COUNTS_BLOCK), 0, s, rows, tris, N, T, area, counts, samples);
 }
 
-template <bool PLANAR>
+template <bool PLANAR, bool YUV>
 static void launch_warp_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris,
                               const uint16_t* counts, int T, const int* list, const int* entry_of_row, int N, const uint8_t* labels,
                               const PasteCropDev& crop, hipStream_t s)
 {
     const dim3 grid((unsigned)N, (unsigned)paste_groups(crop)), block(PASTE_BLOCK);
     if (counts)
-        hipLaunchKernelGGL((warp_paste_kernel_t<true, true, PLANAR>), grid, block, 0, s, frames, chroma, rows, tris, counts, T, list, entry_of_row, labels, crop);
+        hipLaunchKernelGGL((warp_paste_kernel_t<true, true, PLANAR, YUV>), grid, block, 0, s, frames, chroma, rows, tris, counts, T, list, entry_of_row, labels, crop);
     else if (chroma)
-        hipLaunchKernelGGL((warp_paste_kernel_t<true, false, PLANAR>), grid, block, 0, s, frames, chroma, rows, tris, PasteNone{}, T, list, entry_of_row,
+        hipLaunchKernelGGL((warp_paste_kernel_t<true, false, PLANAR, YUV>), grid, block, 0, s, frames, chroma, rows, tris, PasteNone{}, T, list, entry_of_row,
                            labels, crop);
     else
-        hipLaunchKernelGGL((warp_paste_kernel_t<false, false, PLANAR>), grid, block, 0, s, frames, PasteNone{}, rows, tris, PasteNone{}, T, list,
+        hipLaunchKernelGGL((warp_paste_kernel_t<false, false, PLANAR, false>), grid, block, 0, s, frames, PasteNone{}, rows, tris, PasteNone{}, T, list,
                            entry_of_row, labels, crop);
 }
 
 void sdm_launch_warp_paste(const PasteFrameDev* frames, uint8_t* const* chroma, const WarpPasteRow* rows, const WarpPasteTri* tris,
                            const uint16_t* counts, int T, const int* list, const int* entry_of_row, int N, const uint8_t* labels,
-                           const PasteCropDev& crop, bool planar, hipStream_t s)
+                           const PasteCropDev& crop, bool planar, bool yuv, hipStream_t s)
 {
-    if (planar) launch_warp_paste<true>(frames, chroma, rows, tris, counts, T, list, entry_of_row, N, labels, crop, s);
-    else launch_warp_paste<false>(frames, chroma, rows, tris, counts, T, list, entry_of_row, N, labels, crop, s);
+    if (planar && yuv) launch_warp_paste<true, true>(frames, chroma, rows, tris, counts, T, list, entry_of_row, N, labels, crop, s);
+    else if (planar) launch_warp_paste<true, false>(frames, chroma, rows, tris, counts, T, list, entry_of_row, N, labels, crop, s);
+    else if (yuv) launch_warp_paste<false, true>(frames, chroma, rows, tris, counts, T, list, entry_of_row, N, labels, crop, s);
+    else launch_warp_paste<false, false>(frames, chroma, rows, tris, counts, T, list, entry_of_row, N, labels, crop, s);
 }

@@ -190,7 +190,10 @@ class Context:
         tensors until the image set is replaced; memory behind a tuple is the caller's to keep alive -- colour frames are converted
         once, in one launch, with ``upload_images``' arithmetic.  A 3 x H x W tensor named "bgr_planar" / "rgb_planar" (or one stacked
         n x 3 x H x W tensor) is a planar colour frame, read where it lies whatever its row and channel strides
-        (``_lib.frame_planes``); ``chroma``: the second planes of planar tuples.  torch's current stream is synchronised first: the
+        (``_lib.frame_planes``); ``chroma``: the second planes of planar tuples.  A YUV frame's name is base[:matrix][:range] --
+        "nv12:bt709" (1080p and above), "nv12:bt601:full", "p010:bt2020" (16-bit words, the sample in bits 15..6; converted to
+        gray here, read in place by the crop and warp calls); "nv12" alone keeps BT.601 limited range with OpenCV's constants
+        (include/sdm.h, "YUV colour description and 10-bit surfaces").  torch's current stream is synchronised first: the
         library runs on a stream of its own."""
         desc, planes = _lib.frame_planes(frames, formats, chroma)
         for t in ([frames] if _lib._is_tensor(frames) else frames):
@@ -770,7 +773,8 @@ class Context:
                 break
         arr = (_lib.SdmFrame * len(desc))(*[_lib.SdmFrame(ctypes.c_void_p(p), w, h, st, f) for p, w, h, st, f in desc])
         check(self._lib.sdm_align_set_source_frames(self._h, arr, uv, len(desc)))
-        kinds = {0 if f == _lib.SDM_FRAME_NV12 or f in _lib._FRAME_PLANAR else _lib._FRAME_CHANNELS[f] for _, _, _, _, f in desc}
+        kinds = {0 if _lib.frame_base(f) in (_lib.SDM_FRAME_NV12, _lib.SDM_FRAME_P010) or f in _lib._FRAME_PLANAR else _lib._FRAME_CHANNELS[f]
+                 for _, _, _, _, f in desc}
         C = kinds.pop() if len(kinds) == 1 else 0
         self.align_channels = C if C else 1
         return C if C else None
@@ -933,7 +937,7 @@ class Context:
         tensor or None (directly behind the first plane)."""
         planes = list(planes or [None] * len(arr))
         if chroma is None and all(p is None for p in planes):
-            return (None, keep) if any(f.format == _lib.SDM_FRAME_NV12 for f in arr) else None
+            return (None, keep) if any(_lib.frame_base(f.format) == _lib.SDM_FRAME_NV12 for f in arr) else None
         if chroma is not None:
             if len(chroma) != len(arr):
                 raise ValueError("one chroma entry (or None) per frame expected")

@@ -53,6 +53,15 @@ struct DeviceFrame {
     const void* second_plane = nullptr;
 };
 
+/** DeviceFrame::format of a YUV frame with its colour description (include/sdm.h, "YUV colour description and 10-bit surfaces"):
+ *  `base` SDM_FRAME_NV12 or SDM_FRAME_P010 (16-bit words; data and second_plane even), `matrix` SDM_FRAME_YUV_BT601 / _BT709 / _BT2020,
+ *  `full_range` for camera and JPEG-derived frames.  yuv_format(SDM_FRAME_NV12) is SDM_FRAME_NV12 itself, whose constants are the ones
+ *  it always had; a 1080p or 4K stream is yuv_format(SDM_FRAME_NV12, SDM_FRAME_YUV_BT709). */
+constexpr int yuv_format(int base, int matrix = SDM_FRAME_YUV_BT601, bool full_range = false)
+{
+    return base | matrix | (full_range ? SDM_FRAME_YUV_FULL : 0);
+}
+
 namespace detail {
 
 // the second planes of a call (`chroma` / `dst_chroma` / `planes` of include/sdm.h): per frame the caller's entry, else the frame's own
