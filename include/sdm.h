@@ -1191,6 +1191,57 @@ int sdm_warp_paste_tensor_at_filtered(sdm_ctx* ctx, const float* points_host, co
                                       const sdm_align_paste* paste, const sdm_frame* dst_frames, void* const* dst_chroma, int n_frames,
                                       int* flags_host, int* samples_host);
 
+/* Landmark region masks: from the current rows, one crop_height x crop_width uint8 opacity map per row, in CROP space, on the device --
+ * polygons over named landmarks (or the convex hull of a set of landmarks), minus holes, grown and feathered.  The bytes are what
+ * sdm_align_paste.alpha_dev with alpha_per_row = 1 takes: "paste only inside the face outline", "the mouth only", "everything but the
+ * eyes", or a per-face prior channel of a network.  Two launches behind the fit for all rows (the vertices, the pixels).  Every float
+ * operation is float32 and rounded on its own, nothing is contracted, except where double is named; division and square root are
+ * correctly rounded.
+ *   fit, W   the fit is that of sdm_align_crops: the same kernel, the same M, the same flags (the _at form: row n of matrices_host, and no
+ *           PARTIAL is evaluated -- it knows no frame).  W (frame -> crop) is the inverse of the float32 M computed as in "Pasting
+ *           crops back".  SDM_ALIGN_DEGENERATE as there: the fit flags it, an entry of M is not finite, d == 0, or an entry of W is not
+ *           finite; the row's map is all zeros.
+ *   region   a list of 1 to 8 polygons.  Polygon g has sizes[g] landmark indices into [0, L), 3 <= sizes[g] <= 128, one polygon after the
+ *           other in vertex_index; their sum P is at most 256.  The last n_holes polygons are holes, 0 <= n_holes < n_polygons.  Bit g of
+ *           hull_bits makes polygon g the convex hull of its points.  |grow| <= 1024, 0 <= feather <= 1024.
+ *   vertices   p_k = (x[i_k], x[L + i_k]) of the row (the _at form: row n of points_host, P points in the polygons' order);
+ *           q_k = ((W00 px + W01 py) + W02, (W10 px + W11 py) + W12).  A row that is not DEGENERATE and has a q that is not finite or
+ *           has |qx| or |qy| > 2^20 gets an all-zero map and SDM_REGION_NONFINITE.
+ *   hull    the q sorted by (x, then y), comparisons exact, exact duplicates dropped; Andrew's monotone chain with
+ *           turn(o, a, b) = sign of (double)(ax - ox) * (double)(by - oy) - (double)(ay - oy) * (double)(bx - ox), the four differences
+ *           taken in float32 first (the products are exact in double: the sign is exact); pop while the turn is <= 0; the lower chain,
+ *           then the upper chain.  One or two vertices may remain (all points equal, or all collinear): the rules below hold for m >= 1.
+ *   signed distance of crop pixel (column c, row r) to a polygon q_0 ... q_{m-1}: P = ((float)c, (float)r), D2 = +inf, wn = 0; for
+ *           k = 0 ... m - 1 with a = q_k, b = q_{(k + 1) mod m}:
+ *               ex = bx - ax; ey = by - ay; wx = Px - ax; wy = Py - ay;  ee = (ex ex) + (ey ey)
+ *               t  = ee > 0 ? fminf(fmaxf(((wx ex) + (wy ey)) / ee, 0), 1) : 0
+ *               dx = wx - (t ex); dy = wy - (t ey);  D2 = fminf(D2, (dx dx) + (dy dy));  cr = (ex wy) - (ey wx)
+ *               if (ay <= Py) { if (by > Py && cr > 0) ++wn; } else if (by <= Py && cr < 0) --wn;
+ *           sd = sqrtf(D2), negated when wn != 0: the non-zero winding rule (a closed mouth's folded inner-lip polygon stays filled).
+ *   map     s = +inf; every polygon that is no hole: s = fminf(s, sd); every hole, in order: s = fmaxf(s, -sd); wr = fmaxf(feather, 1.0f);
+ *           a = 0.5f + ((grow - s) / wr), clamped to [0, 1]; byte = rintf(a * 255.0f).  The ramp is centred on the contour moved outwards
+ *           by grow; feather 0 is a one-pixel antialiased edge.
+ *   out_dev   N * crop_height * crop_width bytes, dense, 16-byte aligned, row n at n * crop_height * crop_width.  Nothing else is written.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched: what sdm_align_crops_tensor refuses of landmark_index, template_xy,
+ * K, the crop size and the rows (fit form); region NULL, sizes NULL, counts, sizes, P or n_holes outside the ranges above; a hull bit at
+ * or beyond n_polygons; vertex_index NULL or an index outside [0, L); grow or feather not finite or outside their ranges; out_dev NULL
+ * or not 16-byte aligned; _at form: matrices_host or points_host NULL, n_rows < 1, crop_width or crop_height outside [1, 1024]. */
+#define SDM_REGION_NONFINITE 16
+typedef struct sdm_region_mask {
+    const int* sizes;           /* n_polygons vertex counts, the holes last                                          */
+    int n_polygons, n_holes;
+    unsigned hull_bits;         /* bit g: polygon g is the convex hull of its points                                 */
+    float grow, feather;        /* crop pixels                                                                       */
+} sdm_region_mask;
+/* the current rows.  matrices_host (N x 6) and flags_host (N) may be NULL; they come back in one copy behind the call's one synchronise. */
+int sdm_align_region_mask(sdm_ctx* ctx, const int* landmark_index, const float* template_xy, int K, int crop_width, int crop_height,
+                          const int* vertex_index /* P */, const sdm_region_mask* region, uint8_t* out_dev,
+                          float* matrices_host /* N x 6, may be NULL */, int* flags_host /* may be NULL */);
+/* explicit matrices (what an earlier crop call returned) and frame-space points: no landmark state, no geometry, no images needed */
+int sdm_align_region_mask_at(sdm_ctx* ctx, const float* matrices_host /* n_rows x 6 */, const float* points_host /* n_rows x P x 2, frame */,
+                             int n_rows, int crop_width, int crop_height, const sdm_region_mask* region, uint8_t* out_dev,
+                             int* flags_host /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

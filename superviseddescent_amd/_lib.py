@@ -47,6 +47,7 @@ EXPORTED = [
     "sdm_align_paste_tensor_nv12", "sdm_align_paste_tensor_at_nv12",
     "sdm_warp_paste_tensor_nv12", "sdm_warp_paste_tensor_at_nv12",
     "sdm_warp_paste_tensor_filtered", "sdm_warp_paste_tensor_at_filtered",
+    "sdm_align_region_mask", "sdm_align_region_mask_at",
 ]
 
 # multi-stream tracking (include/sdm.h, sdm_track_*)
@@ -62,6 +63,10 @@ SDM_UPRIGHT_PARTIAL, SDM_UPRIGHT_NEAR_EDGE = 1, 2
 
 # aligned face crops (include/sdm.h, sdm_align_*)
 SDM_ALIGN_DEGENERATE, SDM_ALIGN_PARTIAL = 1, 2
+
+# landmark region masks (include/sdm.h, "Landmark region masks"): a vertex is not finite or beyond 2^20 in the crop
+SDM_REGION_NONFINITE = 16
+REGION_MAX_POLYGONS, REGION_MAX_SIZE, REGION_MAX_POINTS = 8, 128, 256
 
 # crops as network input tensors (include/sdm.h, sdm_align_crops_tensor)
 SDM_ALIGN_U8, SDM_ALIGN_F16, SDM_ALIGN_F32 = 0, 1, 2
@@ -129,6 +134,29 @@ class SdmAlignPaste(ctypes.Structure):
     there is one map per row."""
 
     _fields_ = [("alpha_dev", ctypes.c_void_p), ("alpha_per_row", ctypes.c_int)]
+
+
+class SdmRegionMask(ctypes.Structure):
+    """``sdm_region_mask``: the polygons' vertex counts (the holes last), which polygons are convex hulls, grow and feather."""
+
+    _fields_ = [("sizes", ctypes.POINTER(ctypes.c_int)), ("n_polygons", ctypes.c_int), ("n_holes", ctypes.c_int),
+                ("hull_bits", ctypes.c_uint), ("grow", ctypes.c_float), ("feather", ctypes.c_float)]
+
+
+def region_mask(sizes, n_holes=0, hull=(), grow=0.0, feather=0.0):
+    """The ``sdm_region_mask`` of the named options and what must stay alive beside it.  Pure host code.  ``sizes``: the vertex count of
+    every polygon, the ``n_holes`` holes last; ``hull``: the positions of the polygons that are the convex hull of their points;
+    ``grow`` / ``feather``: crop pixels.  The ranges are the library's to refuse; what cannot be expressed is refused here."""
+    sizes = [int(v) for v in sizes]
+    if not 1 <= len(sizes) <= REGION_MAX_POLYGONS:
+        raise ValueError(f"a region has 1 to {REGION_MAX_POLYGONS} polygons, not {len(sizes)}")
+    bits = 0
+    for g in hull:
+        if not 0 <= int(g) < len(sizes):
+            raise ValueError(f"hull names polygon {g}: there are {len(sizes)}")
+        bits |= 1 << int(g)
+    arr = (ctypes.c_int * len(sizes))(*sizes)
+    return SdmRegionMask(arr, len(sizes), int(n_holes), bits, float(grow), float(feather)), arr
 
 
 def align_filter(mode="area", max_samples=16, min_scale=1.0) -> SdmAlignFilter:
@@ -587,6 +615,10 @@ def lib() -> ctypes.CDLL:
             "sdm_warp_paste_tensor_at_filtered": [c_void_p, c_void_p, c_void_p, c_int, ctypes.POINTER(SdmAlignTensor),
                                                   ctypes.POINTER(SdmAlignFilter), c_void_p, ctypes.POINTER(SdmAlignPaste),
                                                   ctypes.POINTER(SdmFrame), c_void_p, c_int, c_void_p, c_void_p],
+            "sdm_align_region_mask": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, ctypes.POINTER(SdmRegionMask), c_void_p,
+                                      c_void_p, c_void_p],
+            "sdm_align_region_mask_at": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, ctypes.POINTER(SdmRegionMask), c_void_p,
+                                         c_void_p],
         }
         for name, args in sigs.items():
             fn = getattr(L, name)

@@ -292,9 +292,13 @@ struct sdm_ctx {
         int fr_bpp = 0;
         // the paste (sdm_capi_paste.hip): a call's frame table, row -> frame index and row lists in one block, and the rows' records
         DevBuf<unsigned char> paste_tab, paste_rows;
+        // the landmark region masks (sdm_capi_mask.hip): a call's matrices and points (_at form), the rows' records, the hulls' sort
+        // buffer and the vertex lists in one block
+        DevBuf<unsigned char> region;
         void release()
         {
             in.release(); faces.release(); crops.release(); owned.release(); fr_dev.release(); paste_tab.release(); paste_rows.release();
+            region.release();
             base = nullptr; n = 0; C = 1; fr.clear();
         }
     } align;

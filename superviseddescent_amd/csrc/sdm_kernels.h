@@ -467,6 +467,18 @@ void sdm_launch_align_area(const uint8_t* base, const AlignFace* faces, const Al
                            int N, int out_w, int out_h, int dtype, int layout, int channels, const AlignTensorDev& spec,
                            const AlignAreaDev& area, int* samples, void* out, hipStream_t s);
 
+// ---- landmark region masks (sdm_region_mask.hip; the records: sdm_region_mask_device.h) ----
+struct RegionDev;
+struct RegionRow;
+// the rows' records, vertex lists and counts.  faces: the fit's N records (M and flags in, the final flags out) with the landmark state x
+// (N x 2L) and the P vertex indices vidx -- or null: mats (N x 6) and points (N x P x 2) of the _at form.  rows: N records out;
+// sorted: N x P x 2 floats, verts: N x 2P x 2 floats of workspace
+void sdm_launch_region_prepare(AlignFace* faces, const float* x, int L, const int* vidx, const float* mats, const float* points, int N,
+                               const RegionDev& region, RegionRow* rows, float* sorted, float* verts, hipStream_t s);
+// out: N x ch x cw bytes, dense, 16-byte aligned
+void sdm_launch_region_raster(const RegionRow* rows, const float* verts, int N, int cw, int ch, const RegionDev& region, uint8_t* out,
+                              hipStream_t s);
+
 // ---- upright-normalised detect and tracking (sdm_upright.hip) ----
 // per row: the chip -> frame matrix M and its inverse W (float32, rounded from the double rotation), the SDM_UPRIGHT_* flags and the
 // row's frame in the context's image set

@@ -30,7 +30,7 @@ from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib
+from . import _lib, ibug
 from ._lib import SdmError, SdmHogParam, check
 
 
@@ -1019,6 +1019,71 @@ class Context:
                                                            ctypes.byref(paste), arr, len(arr), flags.ctypes.data, samples.ctypes.data))
         return flags, samples
 
+    # -- landmark region masks (csrc/sdm_region_mask.hip) ----------------------------------------------
+    def _region_out(self, n, width, height, out):
+        """The N x height x width uint8 device tensor of a region mask call: ``out`` checked, or a new one.  torch's stream is
+        synchronised: the library runs on its own."""
+        import torch
+        shape = (int(n), int(height), int(width))
+        if out is None:
+            if n < 1 or not (1 <= width <= 1024 and 1 <= height <= 1024):            # (the library refuses the call; nothing to allocate)
+                out = torch.empty(16, dtype=torch.uint8, device=f"cuda:{self.device}")
+            else:
+                out = torch.empty(shape, dtype=torch.uint8, device=f"cuda:{self.device}")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == shape):
+            raise ValueError(f"out must be a contiguous uint8 device tensor of shape {shape}")
+        torch.cuda.current_stream(out.device).synchronize()
+        return out
+
+    @staticmethod
+    def _region_polygons(polygons, holes, hull, grow, feather):
+        """(the ``sdm_region_mask``, what keeps it alive, the P vertex entries in order) of ``polygons`` followed by ``holes`` -- each a
+        sequence of vertex entries --; ``hull``: positions in that joined list"""
+        polys = [list(p) for p in polygons] + [list(p) for p in holes]
+        region, keep = _lib.region_mask([len(p) for p in polys], len(list(holes)), hull, grow, feather)
+        return region, keep, [v for p in polys for v in p]
+
+    def align_region_mask(self, landmark_index, template: np.ndarray, width: int, height: int, polygons, holes=(), hull=(), grow=0.0,
+                          feather=0.0, out=None):
+        """One crop-space opacity map per current row from its landmarks (include/sdm.h, sdm_align_region_mask): the fit of
+        ``align_crops_tensor`` on ``landmark_index`` / ``template``, then the union of ``polygons`` minus ``holes`` -- each a sequence of
+        landmark indices in order, 3 to 128 of them, at most 8 polygons and 256 indices in all; ``hull``: the positions (in
+        ``polygons`` followed by ``holes``) of the polygons that are the convex hull of their landmarks -- moved outwards by ``grow``
+        pixels with a linear ramp ``feather`` pixels wide (0: a one-pixel antialiased edge).  ``out``: a contiguous uint8 device
+        tensor N x height x width, written in place; default: a new one.  Returns (maps, matrices N x 2 x 3 float32 crop -> source,
+        flags N int32: SDM_ALIGN_* bits and SDM_REGION_NONFINITE) -- the maps are what ``mask=`` of ``align_paste_tensor`` takes."""
+        idx = np.ascontiguousarray(landmark_index, np.int32).reshape(-1)
+        t = np.ascontiguousarray(template, np.float32).reshape(-1, 2)
+        if t.shape[0] != idx.size:
+            raise ValueError("one template point (x, y) per landmark index expected")
+        region, keep, verts = self._region_polygons(polygons, holes, hull, grow, feather)
+        vidx = np.ascontiguousarray(verts, np.int32).reshape(-1)
+        n = int(getattr(self, "N", 0))
+        out = self._region_out(n, width, height, out)
+        mats = np.empty((n, 2, 3), np.float32)
+        flags = np.empty(n, np.int32)
+        check(self._lib.sdm_align_region_mask(self._h, idx.ctypes.data, t.ctypes.data, idx.size, int(width), int(height), vidx.ctypes.data,
+                                              ctypes.byref(region), ctypes.c_void_p(out.data_ptr()), mats.ctypes.data, flags.ctypes.data))
+        return out, mats, flags
+
+    def align_region_mask_at(self, matrices, points, width: int, height: int, sizes, n_holes=0, hull=(), grow=0.0, feather=0.0, out=None):
+        """``align_region_mask`` for rows that are no longer current (sdm_align_region_mask_at): ``matrices`` N x 2 x 3 as an earlier crop
+        call returned them, ``points`` N x P x 2 float32 frame positions of the polygons' vertices, one polygon after the other;
+        ``sizes``: the vertex count of every polygon, the ``n_holes`` holes last; ``hull``: positions in ``sizes``.  No landmark state,
+        geometry or image is needed.  Returns (maps N x height x width uint8 on the device, flags N int32)."""
+        m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 6)
+        region, keep = _lib.region_mask(sizes, n_holes, hull, grow, feather)
+        p = np.ascontiguousarray(points, np.float32)
+        P = sum(int(v) for v in sizes)
+        if p.ndim != 3 or p.shape != (m.shape[0], P, 2):
+            raise ValueError(f"points must be {m.shape[0]} x {P} x 2, one (x, y) per vertex of every row")
+        n = m.shape[0]
+        out = self._region_out(n, width, height, out)
+        flags = np.empty(n, np.int32)
+        check(self._lib.sdm_align_region_mask_at(self._h, m.ctypes.data, p.ctypes.data, n, int(width), int(height), ctypes.byref(region),
+                                                 ctypes.c_void_p(out.data_ptr()), flags.ctypes.data))
+        return out, flags
+
     # -- warped face tensors pasted back into frames (csrc/sdm_warp_paste.hip) -------------------------
     def _warp_paste_size(self, width, height):
         T, w, h = getattr(self, "warp_mesh", (0, 0, 0))
@@ -1947,6 +2012,73 @@ class detection_model:
         if template is None:
             template = alignment_template(self.mean, idx, width, height, margin)
         return c.align_paste_tensor(idx, template, y, frames, formats, layout, mask, **options)
+
+    def _region_index(self, regions, holes):
+        """(polygons, holes, hull positions) as landmark positions of this model.  A region is a list of id names in order,
+        ("hull", ids), or the name of a preset of ``ibug.REGIONS`` / ``ibug.REGIONS_RCR22`` (``ibug.region_preset``)."""
+        if isinstance(regions, str) or (isinstance(regions, tuple) and len(regions) == 2 and regions[0] == "hull"):
+            regions = [regions]
+        if isinstance(holes, str) or (isinstance(holes, tuple) and len(holes) == 2 and holes[0] == "hull"):
+            holes = [holes]
+        polys, hull = [], []
+        for g, region in enumerate(list(regions) + list(holes)):
+            if isinstance(region, str):
+                region = ibug.region_preset(region, self.landmark_ids)
+            if isinstance(region, tuple) and len(region) == 2 and region[0] == "hull":
+                hull.append(g)
+                region = region[1]
+            ids = [str(i) for i in region]
+            missing = [i for i in ids if i not in self.landmark_ids]
+            if missing:
+                raise ValueError(f"landmark ids not in this model: {missing}")
+            polys.append([self.landmark_ids.index(i) for i in ids])
+        n = len(list(regions))
+        return polys[:n], polys[n:], hull
+
+    def region_masks(self, size, regions, holes=(), grow: float = 0.0, feather: float = 0.0, landmark_ids: Optional[Sequence[str]] = None,
+                     template: Optional[np.ndarray] = None, margin: float = 0.2, matrices=None, points=None, out=None):
+        """One crop-space opacity map per current row, drawn from its landmarks on the device (include/sdm.h, "Landmark region masks"):
+        the union of ``regions`` minus ``holes``, moved outwards by ``grow`` crop pixels, with a linear ramp ``feather`` pixels wide.  A
+        region is a list of landmark id names in order (a polygon), ``("hull", ids)`` (the convex hull of those landmarks) or a preset
+        name of :data:`ibug.REGIONS` / :data:`ibug.REGIONS_RCR22` ("face", "right_eye", "mouth_outer", ...).  ``size``,
+        ``landmark_ids``, ``template``, ``margin``: as in :meth:`aligned_crops_tensor`, with the same defaults, so that
+        ``paste_crops_tensor(net(x), mask=region_masks(112, ["face"], feather=6)[0], ...)`` lines up with the crop.  ``matrices``
+        (N x 2 x 3, as a crop call returned them) with ``points`` (:meth:`region_points` of that moment) draws rows that are no longer
+        current.  ``out``: a contiguous uint8 device tensor N x height x width.  Returns (maps N x height x width uint8 on the device,
+        matrices, flags N: SDM_ALIGN_* bits and SDM_REGION_NONFINITE); a flagged row's map is all zeros."""
+        c = self.optimised_model.ctx
+        width, height = (int(size), int(size)) if np.isscalar(size) else (int(size[0]), int(size[1]))
+        polys, hole_polys, hull = self._region_index(regions, holes)
+        if (matrices is None) != (points is None):
+            raise ValueError("matrices and points go together")
+        if matrices is not None:
+            m = np.ascontiguousarray(matrices, np.float32).reshape(-1, 2, 3)
+            maps, flags = c.align_region_mask_at(m, points, width, height, [len(p) for p in polys + hole_polys], len(hole_polys), hull, grow,
+                                                 feather, out)
+            return maps, m, flags
+        if not getattr(c, "N", 0):
+            raise RuntimeError("run detect_batch or Tracker.step first")
+        ids = self.landmark_ids if landmark_ids is None else [str(i) for i in landmark_ids]
+        missing = [i for i in ids if i not in self.landmark_ids]
+        if missing:
+            raise ValueError(f"landmark ids not in this model: {missing}")
+        idx = [self.landmark_ids.index(i) for i in ids]
+        if template is None:
+            template = alignment_template(self.mean, idx, width, height, margin)
+        return c.align_region_mask(idx, template, width, height, polys, hole_polys, hull, grow, feather, out)
+
+    def region_points(self, regions, holes=()) -> np.ndarray:
+        """N x P x 2 float32: (x, y) of the vertices of ``regions`` followed by ``holes`` (as :meth:`region_masks` takes them) of the
+        current rows, one polygon after the other -- what ``points=`` of :meth:`region_masks` takes later, the counterpart of
+        :meth:`warp_points`."""
+        c = self.optimised_model.ctx
+        polys, hole_polys, _ = self._region_index(regions, holes)
+        if not getattr(c, "N", 0):
+            raise RuntimeError("run detect_batch or Tracker.step first")
+        x = np.asarray(c.get_x(), np.float32)
+        L = x.shape[1] // 2
+        idx = np.asarray([v for p in polys + hole_polys for v in p], np.int64)
+        return np.ascontiguousarray(np.stack([x[:, idx], x[:, L + idx]], -1))
 
     def _warp_mesh_of(self, width, height, landmark_ids, template, triangles, margin):
         ids = self.landmark_ids if landmark_ids is None else [str(i) for i in landmark_ids]

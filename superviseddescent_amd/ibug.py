@@ -38,6 +38,43 @@ RCR22_IDS = ["9", "31", "32", "36", "37", "38", "39", "40", "41", "42", "43", "4
 RIGHT_EYE_IDS = ["37", "40"]
 LEFT_EYE_IDS = ["43", "46"]
 
+# Landmark regions for ``detection_model.region_masks``: a region is a list of ibug ids in polygon order, or ("hull", ids) -- the convex
+# hull of those landmarks.  68-point model: the face outline runs down the jaw (1 ... 17) and back over the brows (27 ... 18).
+REGIONS = {
+    "face": [str(i) for i in list(range(1, 18)) + list(range(27, 17, -1))],
+    "right_eye": [str(i) for i in range(37, 43)],
+    "left_eye": [str(i) for i in range(43, 49)],
+    "right_brow": [str(i) for i in range(18, 23)],
+    "left_brow": [str(i) for i in range(23, 28)],
+    "mouth_outer": [str(i) for i in range(49, 61)],
+    "mouth_inner": [str(i) for i in range(61, 69)],
+    "nose": ["28", "32", "33", "34", "35", "36"],
+}
+# RCR-22 has no jaw contour beyond the chin: its face is the hull of all its landmarks, its outer mouth the four it has
+REGIONS_RCR22 = {
+    "face": ("hull", list(RCR22_IDS)),
+    "right_eye": [str(i) for i in range(37, 43)],
+    "left_eye": [str(i) for i in range(43, 49)],
+    "mouth_outer": ["49", "52", "55", "58"],
+}
+
+
+def region_preset(name, ids):
+    """The preset region ``name`` for a model with the landmark ``ids``: that of ``REGIONS`` if the model has all its ids, else that of
+    ``REGIONS_RCR22``; raises ValueError naming the ids the model lacks."""
+    tables = [t for t in (REGIONS, REGIONS_RCR22) if name in t]
+    if not tables:
+        raise ValueError(f"unknown region {name!r}: one of {sorted(set(REGIONS) | set(REGIONS_RCR22))}")
+    lacking = []
+    for t in tables:
+        region = t[name]
+        want = region[1] if isinstance(region, tuple) else region
+        lacking = [i for i in want if i not in ids]
+        if not lacking:
+            return region
+    raise ValueError(f"region {name!r} needs landmark ids this model lacks: {lacking}")
+
+
 VARIANT_DALALTRIGGS = 0  # VlHogVariantDalalTriggs, include/rcr/hog.h:72
 VARIANT_UOCTTI = 1       # VlHogVariantUoctti
 

@@ -496,5 +496,112 @@ inline paste_result paste_crops_tensor(cv::Mat matrices, const std::vector<int>&
     return paste_crops_tensor(matrices, image_index, width, height, spec, in_dev, frames, mask, &filter, &chroma);
 }
 
+/** A landmark region (sdm_region_mask of include/sdm.h, "Landmark region masks"): the union of `polygons` minus `holes` -- each the
+ *  positions of 3 to 128 landmarks in order --, moved outwards by `grow` crop pixels, with a linear ramp `feather` pixels wide.
+ *  `hull`: the positions, in polygons followed by holes, of the polygons that are the convex hull of their landmarks. */
+struct RegionMask {
+    std::vector<std::vector<int>> polygons, holes;
+    std::vector<int> hull;
+    float grow = 0.0f, feather = 0.0f;
+};
+
+struct region_masks_result {
+    cv::Mat matrices;              // rows x 6 CV_32FC1: the crop -> frame map of every row
+    std::vector<int> flags;        // SDM_ALIGN_DEGENERATE / SDM_ALIGN_PARTIAL / SDM_REGION_NONFINITE bits; a flagged row's map is zeros
+};
+
+namespace detail {
+
+// the region as the C calls take it: the vertex counts (holes last), the hull bits, and the vertex indices one polygon after the other
+struct RegionArgs {
+    std::vector<int> sizes, vertex_index;
+    sdm_region_mask region{};
+    explicit RegionArgs(const RegionMask& r)
+    {
+        for (const auto* list : {&r.polygons, &r.holes})
+            for (const auto& p : *list) {
+                sizes.push_back((int)p.size());
+                vertex_index.insert(vertex_index.end(), p.begin(), p.end());
+            }
+        unsigned bits = 0;
+        for (int g : r.hull) {
+            if (g < 0 || g >= (int)sizes.size()) throw std::runtime_error("region_masks: hull names a polygon that is not there");
+            bits |= 1u << g;
+        }
+        region = sdm_region_mask{sizes.data(), (int)sizes.size(), (int)r.holes.size(), bits, r.grow, r.feather};
+    }
+    RegionArgs(const RegionArgs&) = delete;
+    RegionArgs& operator=(const RegionArgs&) = delete;
+};
+
+inline region_masks_result region_masks_current_rows(sdm_ctx* c, int n, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
+                                                     int height, const RegionMask& region, uint8_t* out_dev)
+{
+    using superviseddescent::hip::check;
+    if (tmpl.rows != (int)landmark_index.size() || tmpl.cols != 2) throw std::runtime_error("region_masks: one template point (x, y) per landmark");
+    cv::Mat t = tmpl.isContinuous() ? tmpl : tmpl.clone();
+    const RegionArgs a(region);
+    region_masks_result res;
+    res.matrices = cv::Mat(n, 6, CV_32FC1);
+    res.flags.resize((size_t)n);
+    check(sdm_align_region_mask(c, landmark_index.data(), t.ptr<float>(0), (int)landmark_index.size(), width, height,
+                                a.vertex_index.empty() ? nullptr : a.vertex_index.data(), &a.region, out_dev, res.matrices.ptr<float>(0),
+                                res.flags.data()),
+          "sdm_align_region_mask");
+    return res;
+}
+
+}  // namespace detail
+
+/** One crop-space opacity map per stream of the tracker's last step, drawn from its landmarks on the device: `out_dev` -- rows * height *
+ *  width bytes of 16-byte aligned device memory, row n at n * height * width -- is what PasteMask{out_dev, true} takes.  The fit is that
+ *  of aligned_crops_tensor on `landmark_index` / `tmpl`, so the maps line up with its crops. */
+inline region_masks_result region_masks(tracker& tr, const std::vector<int>& landmark_index, cv::Mat tmpl, int width, int height,
+                                        const RegionMask& region, uint8_t* out_dev)
+{
+    if (tr.rows().rows < 1) throw std::runtime_error("region_masks: step the tracker first");
+    return detail::region_masks_current_rows(tr.context(), tr.rows().rows, landmark_index, tmpl, width, height, region, out_dev);
+}
+
+/** The same for landmark rows on device frames (as the detection_model overload of paste_crops_tensor: a handle of its own, the frames as
+ *  its image set, the rows uploaded). */
+inline region_masks_result region_masks(detection_model& model, const std::vector<DeviceFrame>& frames, cv::Mat rows,
+                                        const std::vector<int>& image_index, const std::vector<int>& landmark_index, cv::Mat tmpl, int width,
+                                        int height, const RegionMask& region, uint8_t* out_dev)
+{
+    using superviseddescent::hip::check;
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    sdm_ctx* c = h.get();
+    detail::configure(h, {}, model.get_hog_params(), model.get_landmark_ids(), model.get_right_eye_ids(), model.get_left_eye_ids(), false);
+    detail::set_device_frames(h, frames);
+    cv::Mat x = rows.isContinuous() ? rows : rows.clone();
+    if (x.cols != 2 * (int)model.get_landmark_ids().size()) throw std::runtime_error("region_masks: rows must hold 2L coordinates");
+    if (image_index.empty()) check(sdm_set_sample_image_index(c, nullptr, 0), "sdm_set_sample_image_index");
+    else check(sdm_set_sample_image_index(c, image_index.data(), (int)image_index.size()), "sdm_set_sample_image_index");
+    check(sdm_set_x(c, x.ptr<float>(0), x.rows), "sdm_set_x");
+    return detail::region_masks_current_rows(c, x.rows, landmark_index, tmpl, width, height, region, out_dev);
+}
+
+/** The explicit form (sdm_align_region_mask_at): `matrices` rows x 6 CV_32FC1 as an earlier crop call returned them, `points` rows x 2P
+ *  CV_32FC1 -- (x, y) of every vertex in the frame, one polygon after the other --; of `region`'s polygons only the sizes are read.  No
+ *  model, no landmark state.  The result's matrices are the ones given. */
+inline region_masks_result region_masks(cv::Mat matrices, cv::Mat points, int width, int height, const RegionMask& region, uint8_t* out_dev)
+{
+    using superviseddescent::hip::check;
+    const detail::RegionArgs a(region);
+    if (matrices.type() != CV_32FC1 || matrices.cols != 6 || matrices.rows < 1) throw std::runtime_error("region_masks: matrices must be rows x 6 CV_32FC1");
+    if (points.type() != CV_32FC1 || points.rows != matrices.rows || points.cols != 2 * (int)a.vertex_index.size())
+        throw std::runtime_error("region_masks: points must be rows x 2P CV_32FC1");
+    superviseddescent::hip::Handle h(superviseddescent::hip::device());
+    region_masks_result res;
+    res.matrices = matrices.isContinuous() ? matrices : matrices.clone();
+    res.flags.resize((size_t)matrices.rows);
+    cv::Mat p = points.isContinuous() ? points : points.clone();
+    check(sdm_align_region_mask_at(h.get(), res.matrices.ptr<float>(0), p.ptr<float>(0), matrices.rows, width, height, &a.region, out_dev,
+                                   res.flags.data()),
+          "sdm_align_region_mask_at");
+    return res;
+}
+
 }  // namespace rcr
 #endif /* RCR_ALIGNMENT_HPP_ */
