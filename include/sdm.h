@@ -676,6 +676,50 @@ int sdm_track_step_filtered(sdm_ctx* ctx, const int* ids, int n, const float* dt
  * output may be NULL.  Neither the state nor the current rows x are touched. */
 int sdm_track_get_filtered(sdm_ctx* ctx, const int* ids, int n, float* filtered_host, float* derivative_host, int* primed_host);
 
+/* Tracking, motion-compensated: a step starts from where the face WAS, and the cascade pulls a shape in only from about as far as its
+ * training perturbations reached (a few percent of the face box).  A head turn, a hand-held phone or a slow camera moves a face further
+ * between two frames.  With a motion mode configured every step first estimates each tracked stream's translation between its last
+ * frame and the new one by block matching on a small chip, and starts the cascade from the shifted landmarks.  Off by default: with no
+ * mode configured every call runs the launches it ran before and gives the same bits.  All arithmetic is integer except where stated.
+ *   parameters   search S in [1, 16] chip pixels, scale finite in [0.5, 4], min_gain in [0, 255]; the chip side is C = 32.
+ *   state        per slot: valid, the grid (k, ox, oy) and a 32 x 32 u8 reference chip.  sdm_track_configure_motion allocates it, all
+ *                slots invalid; sdm_track_start and sdm_track_start_rolled invalidate the slots they name.
+ *   block mean   B(X, Y, k) = (sum_{u, v < k} g(X + u, Y + v) + k^2 / 2) / k^2 (integer divisions), g the gray byte of the row's context
+ *                image in the step's image set (sdm_set_sample_image_index; the image the upright chip reads: gray and NV12 luma in
+ *                place, colour and P010 as converted), 0 outside the image.
+ *   store        one launch behind the commit, for every row of the step.  Lost mask != 0: valid = 0.  Otherwise, from the committed RAW
+ *                row p with x0, x1, y0, y1 the min and max of its coordinates, in float32 with every operation rounded:
+ *                  side = fmaxf(x1 - x0, y1 - y0) * scale;  k = min(64, max(1, (int)ceilf(side / 32.0f)))
+ *                  cx = (int)floorf((x0 + x1) * 0.5f) with the float clamped to +-2^20 first, cy likewise;  ox = cx - 16 k, oy = cy - 16 k
+ *                  chip[j][i] = B(ox + i k, oy + j k, k) for i, j < 32;  valid = 1
+ *   search       one launch ahead of the gather, for every row whose slot is TRACKED and valid, in the NEW image of the row:
+ *                  cur[j][i] = B(ox - S k + i k, oy - S k + j k, k) for i, j < 32 + 2 S
+ *                  SAD(dx, dy) = sum_{i, j < 32} |cur[S + dy + j][S + dx + i] - chip[j][i]| for dx, dy in [-S, S]
+ *                  best = the lexicographic minimum of (SAD, dx^2 + dy^2, dy, dx);  zero = SAD(0, 0)
+ *                  shift = (dx k, dy k) of best if best.SAD * 256 <= zero * (256 - min_gain), else (0, 0)
+ *                Every sum stays below 2^31.  A STARTED slot or one without a valid chip gets the shift (0, 0) and is not searched.
+ *   use          the shift is added, as float32 with one rounded add per coordinate, to the slot's landmarks AS THE GATHER READS THEM:
+ *                SDM_TRACK_INIT_PREVIOUS, SDM_TRACK_INIT_REALIGN and the upright tracker's p ahead of its roll, centre and W.  The slot
+ *                table is not modified; the SCALE rule's init is the shifted init.  With the shift (0, 0) a row's step is bit-identical
+ *                to a step without the mode.
+ *   filter       sdm_track_step and sdm_track_step_filtered both run the two launches; the store reads the raw rows, the One-Euro state
+ *                is not touched by either.
+ * Refused with SDM_ERR_INVALID, no state changed, nothing launched: a parameter outside its range, an unknown mode, a call before
+ * sdm_track_configure, sdm_track_get_motion without a mode, an id out of range or named twice.
+ * Out of scope: sub-chip-pixel refinement, a rotation or scale search, and any lost rule built on the SAD values -- they are returned so
+ * that such a rule can be studied. */
+enum {
+    SDM_TRACK_MOTION_OFF = 0,
+    SDM_TRACK_MOTION_SAD = 1            /* the block matching above */
+};
+/* Needs sdm_track_configure; allocates the state for its capacity, all slots invalid.  mode OFF frees the state (the parameters are
+ * not looked at).  A later sdm_track_configure switches the mode off. */
+int sdm_track_configure_motion(sdm_ctx* ctx, int mode, int search, float scale, int min_gain);
+/* Of the named slots: motion_host n x 6 ints -- the last step's shift (dx, dy) in pixels, the best SAD, SAD(0, 0), k and whether the
+ * row was searched (all 0 when it was not, or never stepped) --, grid_host n x 3 ints (k, ox, oy) and chips_host n x 32 x 32 bytes, zeros
+ * where a slot holds no valid chip.  Each may be NULL.  No state is touched. */
+int sdm_track_get_motion(sdm_ctx* ctx, const int* ids, int n, int* motion_host, int* grid_host, uint8_t* chips_host);
+
 /* Aligned face crops of the current rows (after sdm_detect_batch, sdm_track_step or sdm_set_x): for every row n of x (N x 2L, what
  * sdm_get_x returns) an out_width x out_height x C u8 crop in which the face stands in a canonical position -- the input of
  * recognition, expression or attribute networks -- without the landmarks or the frames leaving the device.

@@ -39,6 +39,7 @@ EXPORTED = [
     "sdm_set_frames_device", "sdm_set_frames_device_planes", "sdm_debug_download_image",
     "sdm_upright_configure", "sdm_detect_batch_upright", "sdm_upright_get", "sdm_track_configure_upright", "sdm_track_start_rolled",
     "sdm_track_configure_filter", "sdm_track_step_filtered", "sdm_track_get_filtered",
+    "sdm_track_configure_motion", "sdm_track_get_motion",
     "sdm_warp_delaunay", "sdm_warp_set_mesh", "sdm_warp_get_labels", "sdm_warp_crops_tensor",
     "sdm_warp_crops_tensor_filtered",
     "sdm_align_paste_tensor", "sdm_align_paste_tensor_at",
@@ -57,6 +58,9 @@ SDM_TRACK_LOST_NONFINITE, SDM_TRACK_LOST_SMALL, SDM_TRACK_LOST_OUTSIDE, SDM_TRAC
 
 # the tracker's temporal landmark filter (include/sdm.h, "Tracking, filtered")
 SDM_TRACK_FILTER_OFF, SDM_TRACK_FILTER_ONE_EURO = 0, 1
+
+# the tracker's motion-compensated initialisation (include/sdm.h, "Tracking, motion-compensated")
+SDM_TRACK_MOTION_OFF, SDM_TRACK_MOTION_SAD = 0, 1
 
 # upright-normalised detect and tracking (include/sdm.h, "Rolled faces")
 SDM_UPRIGHT_PARTIAL, SDM_UPRIGHT_NEAR_EDGE = 1, 2
@@ -579,6 +583,8 @@ def lib() -> ctypes.CDLL:
             "sdm_track_configure_filter": [c_void_p, c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float],
             "sdm_track_step_filtered": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
             "sdm_track_get_filtered": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+            "sdm_track_configure_motion": [c_void_p, c_int, c_int, ctypes.c_float, c_int],
+            "sdm_track_get_motion": [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
             "sdm_warp_delaunay": [c_void_p, c_int, c_void_p, c_int, c_int_p],
             "sdm_warp_set_mesh": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int],
             "sdm_warp_get_labels": [c_void_p, c_void_p],

@@ -265,10 +265,22 @@ struct sdm_ctx {
         DevBuf<int> primed;                // S
         DevBuf<float> filter_out;          // scratch of sdm_track_get_filtered: 2 x n x 2L + n ints
         void filter_off() { filter = 0; filter_state.release(); primed.release(); filter_out.release(); }
+        // the motion-compensated initialisation (sdm_track_configure_motion, csrc/sdm_track_motion.hip): per slot {valid, k, ox, oy}, the
+        // 32 x 32 reference chip and the last search's result; per row of a step the shift the gather adds
+        int motion = 0;                    // SDM_TRACK_MOTION_*
+        int motion_search = 0, motion_min_gain = 0;
+        float motion_scale = 0.f;
+        DevBuf<int> motion_state;          // S x 4
+        DevBuf<uint8_t> motion_chips;      // S x 32 x 32
+        DevBuf<int> motion_last;           // S x 6
+        DevBuf<float> motion_shift;        // n x 2
+        DevBuf<int> motion_out;            // scratch of sdm_track_get_motion: n x (6 + 3) ints + n x 1024 bytes
+        void motion_off() { motion = 0; motion_state.release(); motion_chips.release(); motion_last.release(); motion_shift.release(); motion_out.release(); }
         void release()
         {
             mean.release(); x.release(); box.release(); status.release(); init.release(); ids.release(); masks.release(); cs.release();
             filter_off();
+            motion_off();
             upright = false;
             if (pin) { hipError_t e = hipHostFree(pin); (void)e; }
             pin = nullptr; pin_cap = 0; S = 0;

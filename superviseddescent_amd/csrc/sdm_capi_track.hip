@@ -64,6 +64,7 @@ int sdm_track_configure(sdm_ctx* c, int capacity, const float* mean, int init_mo
     HIP_TRY(hipStreamSynchronize(c->stream));
     sdm_ctx::Track& t = c->track;
     t.filter_off();                                // (the filter's state belongs to the slots that go: sdm_track_configure_filter again)
+    t.motion_off();                                // (and the motion state: sdm_track_configure_motion again)
     int rc;
     if ((rc = t.mean.ensure(M)) || (rc = t.x.ensure((size_t)capacity * M)) || (rc = t.box.ensure((size_t)capacity * 4)) ||
         (rc = t.status.ensure((size_t)capacity)))
@@ -111,6 +112,7 @@ static int track_start_common(sdm_ctx* c, const int* ids, const int* boxes, cons
     HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (cs_ints + (size_t)5 * n) * sizeof(int), hipMemcpyHostToDevice, c->stream));
     sdm_launch_track_start(t.ids.p + cs_ints, t.ids.p + cs_ints + n, n, t.box.p, t.status.p, c->stream);
     if (t.filter) sdm_launch_track_filter_unprime(t.ids.p + cs_ints, n, t.primed.p, c->stream);
+    if (t.motion) sdm_launch_track_motion_invalidate(t.ids.p + cs_ints, n, t.motion_state.p, c->stream);
     if (slots_cs) sdm_launch_upright_slot_cs(t.ids.p + cs_ints, roll_deg ? (const double*)t.ids.p : nullptr, n, t.cs.p, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));      // (the pinned staging is reused by the next call)
@@ -173,24 +175,36 @@ static int track_step_common(sdm_ctx* c, const int* ids, int n, const float* dt,
         (rc = t.masks.ensure((size_t)n + 1)) || (rc = ensure_pinned(t, in_ints + n + 1)))
         return rc;
     if (t.upright && (rc = upright_ensure(c, n))) return rc;
+    if (t.motion && (rc = t.motion_shift.ensure((size_t)2 * n))) return rc;
     // the rows become the current x, as after sdm_set_x + sdm_detect_batch
     if (n != c->N) { c->have_targets = false; c->feat_level = -1; c->have_patch_idx = false; }
     c->N = n; c->cur = 0;
     memcpy(t.pin, ids, (size_t)n * sizeof(int));
     if (dt) memcpy(t.pin + n, dt, (size_t)n * sizeof(float));
     HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, in_ints * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    const int* row_image = c->idx_identity ? nullptr : c->img_idx.p;
+    const float* shift = nullptr;
+    if (t.motion) {
+        // the translation of every tracked row's face between its slot's chip and the new image, ahead of the gather
+        sdm_launch_track_motion_search(t.ids.p, n, t.status.p, t.motion_state.p, t.motion_chips.p, frame_set(c), row_image, t.motion_search,
+                                       t.motion_min_gain, t.motion_shift.p, t.motion_last.p, c->stream);
+        HIP_TRY(hipGetLastError());
+        shift = t.motion_shift.p;
+    }
     if (t.upright) {
         // upright mode: the rows' chips and their init in chip coordinates, the cascade on the chips, the result back in the frame
         UprightSetupDev a{};
         a.ids = t.ids.p; a.slot_status = t.status.p; a.slot_box = t.box.p; a.slot_cs = t.cs.p; a.slot_x = t.x.p; a.mean = t.mean.p;
         a.mb = make_float4(t.mean_bounds[0], t.mean_bounds[1], t.mean_bounds[2], t.mean_bounds[3]);
+        a.shift = shift;
         sdm_ctx::Upright& u = c->upright;
-        sdm_launch_upright_setup(a, n, c->L, u.chip, frame_set(c), c->idx_identity ? nullptr : c->img_idx.p, c->eyes, u.rows.p, u.off.p,
+        sdm_launch_upright_setup(a, n, c->L, u.chip, frame_set(c), row_image, c->eyes, u.rows.p, u.off.p,
                                  u.w.p, u.h.p, u.stride.p, c->x[0].p, t.init.p, c->stream);
         HIP_TRY(hipGetLastError());
         if ((rc = upright_run(c, n))) return rc;
     } else {
-    sdm_launch_track_gather(t.ids.p, n, c->L, t.mode, t.status.p, t.box.p, t.x.p, t.mean.p, t.mean_bounds, c->x[0].p, t.init.p, c->stream);
+    sdm_launch_track_gather(t.ids.p, n, c->L, t.mode, t.status.p, t.box.p, t.x.p, t.mean.p, t.mean_bounds, c->x[0].p, t.init.p, c->stream,
+                            shift);
     HIP_TRY(hipGetLastError());
     // the cascade: exactly sdm_detect_batch's level sequence (fused or unfused per level)
     c->chain_timers = true; c->ev_fresh = false;
@@ -201,6 +215,12 @@ static int track_step_common(sdm_ctx* c, const int* ids, int n, const float* dt,
     sdm_launch_track_commit(t.ids.p, n, c->L, c->x[c->cur].p, t.init.p, c->idx_identity ? nullptr : c->img_idx.p, c->img_w.p, c->img_h.p,
                             c->eyes, t.min_size, t.max_scale, t.x.p, t.status.p, t.masks.p, c->status.p, c->stream);
     HIP_TRY(hipGetLastError());
+    if (t.motion) {
+        // the tracked rows' grids and reference chips from the committed raw rows; a lost row's slot is invalidated
+        sdm_launch_track_motion_store(t.ids.p, n, c->L, c->x[c->cur].p, t.masks.p, frame_set(c), row_image, t.motion_scale, t.motion_state.p,
+                                      t.motion_chips.p, c->stream);
+        HIP_TRY(hipGetLastError());
+    }
     int* masks = t.pin + in_ints;
     HIP_TRY(hipMemcpyAsync(masks, t.masks.p, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     if (landmarks_host)
@@ -283,6 +303,56 @@ int sdm_track_get_filtered(sdm_ctx* c, const int* ids, int n, float* filtered_ho
     if (filtered_host) HIP_TRY(hipMemcpyAsync(filtered_host, out_f, nM * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (derivative_host) HIP_TRY(hipMemcpyAsync(derivative_host, out_d, nM * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     if (primed_host) HIP_TRY(hipMemcpyAsync(primed_host, out_p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SDM_OK;
+}
+
+int sdm_track_configure_motion(sdm_ctx* c, int mode, int search, float scale, int min_gain)
+{
+    int rc = track_ready(c);
+    if (rc) return rc;
+    sdm_ctx::Track& t = c->track;
+    if (mode != SDM_TRACK_MOTION_OFF && mode != SDM_TRACK_MOTION_SAD) return fail(SDM_ERR_INVALID, "unknown motion mode");
+    if (mode == SDM_TRACK_MOTION_SAD) {
+        if (search < 1 || search > 16) return fail(SDM_ERR_INVALID, "search must lie in [1, 16] chip pixels");
+        if (!std::isfinite(scale) || !(scale >= 0.5f && scale <= 4.f)) return fail(SDM_ERR_INVALID, "scale must be finite and lie in [0.5, 4]");
+        if (min_gain < 0 || min_gain > 255) return fail(SDM_ERR_INVALID, "min_gain must lie in [0, 255]");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (mode == SDM_TRACK_MOTION_OFF) { t.motion_off(); return SDM_OK; }
+    const size_t S = (size_t)t.S;
+    if ((rc = t.motion_state.ensure(4 * S)) || (rc = t.motion_chips.ensure(1024 * S)) || (rc = t.motion_last.ensure(6 * S))) { t.motion_off(); return rc; }
+    HIP_TRY(hipMemsetAsync(t.motion_state.p, 0, 4 * S * sizeof(int), c->stream));         // every slot invalid
+    HIP_TRY(hipMemsetAsync(t.motion_chips.p, 0, 1024 * S, c->stream));
+    HIP_TRY(hipMemsetAsync(t.motion_last.p, 0, 6 * S * sizeof(int), c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    t.motion = mode; t.motion_search = search; t.motion_scale = scale; t.motion_min_gain = min_gain;
+    return SDM_OK;
+}
+
+int sdm_track_get_motion(sdm_ctx* c, const int* ids, int n, int* motion_host, int* grid_host, uint8_t* chips_host)
+{
+    int rc = track_ready(c);
+    if (rc) return rc;
+    sdm_ctx::Track& t = c->track;
+    if (t.motion == SDM_TRACK_MOTION_OFF) return fail(SDM_ERR_INVALID, "no motion mode configured (sdm_track_configure_motion)");
+    if ((rc = check_ids(c, ids, n))) return rc;
+    if (!motion_host && !grid_host && !chips_host) return SDM_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    // scratch: n x 6 and n x 3 ints (9 n, padded to a multiple of 4 ints), then the n chips
+    const size_t head = ((size_t)9 * n + 3) & ~(size_t)3;
+    if ((rc = t.motion_out.ensure(head + (size_t)256 * n)) || (rc = t.ids.ensure((size_t)n)) || (rc = ensure_pinned(t, (size_t)n))) return rc;
+    memcpy(t.pin, ids, (size_t)n * sizeof(int));
+    HIP_TRY(hipMemcpyAsync(t.ids.p, t.pin, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    int* out_m = t.motion_out.p;
+    int* out_g = out_m + (size_t)6 * n;
+    uint8_t* out_c = (uint8_t*)(t.motion_out.p + head);
+    sdm_launch_track_motion_get(t.ids.p, n, t.motion_state.p, t.motion_chips.p, t.motion_last.p, out_m, out_g, out_c, c->stream);
+    HIP_TRY(hipGetLastError());
+    if (motion_host) HIP_TRY(hipMemcpyAsync(motion_host, out_m, (size_t)6 * n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (grid_host) HIP_TRY(hipMemcpyAsync(grid_host, out_g, (size_t)3 * n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (chips_host) HIP_TRY(hipMemcpyAsync(chips_host, out_c, (size_t)1024 * n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SDM_OK;
 }

@@ -404,9 +404,11 @@ void sdm_launch_pose_gather(const float* xl, int L, int N, const int* lm, int K,
 // ---- multi-stream tracking (sdm_track.hip): the hand-offs between the slot table and the detect cascade's state x ----
 // slot table: slot_x S x 2L, slot_box S x 4 (x, y, w, h), slot_status S (SDM_TRACK_*, include/sdm.h)
 void sdm_launch_track_start(const int* ids, const int* boxes, int n, int* slot_box, int* slot_status, hipStream_t s);
-// x (and init, when not null): n x 2L; mean_bounds = {min, max of the mean's x, min, max of its y}
+// x (and init, when not null): n x 2L; mean_bounds = {min, max of the mean's x, min, max of its y}; shift (may be null): n x 2 floats
+// added to a tracked slot's landmarks as they are read (sdm_track_motion.hip)
 void sdm_launch_track_gather(const int* ids, int n, int L, int mode, const int* slot_status, const int* slot_box, const float* slot_x,
-                             const float* mean, const float mean_bounds[4], float* x, float* init, hipStream_t s);
+                             const float* mean, const float mean_bounds[4], float* x, float* init, hipStream_t s,
+                             const float* shift = nullptr);
 // masks: n + 1 ints, masks[n] = *status_word (the context's kernel status, read behind the cascade)
 void sdm_launch_track_commit(const int* ids, int n, int L, const float* x, const float* init, const int* img_idx, const int* img_w,
                              const int* img_h, const EyeIdxDev& eyes, float min_size, float max_scale_change, float* slot_x,
@@ -419,6 +421,19 @@ void sdm_launch_track_filter_unprime(const int* ids, int n, int* primed, hipStre
 // out_f, out_d: n x 2L, zeros where a slot is not primed; out_primed: n
 void sdm_launch_track_filter_get(const int* ids, int n, int L, const float* state_d, const float* state_f, const int* primed, float* out_f,
                                  float* out_d, int* out_primed, hipStream_t s);
+// the motion-compensated initialisation (sdm_track_motion.hip).  state: S x {valid, k, ox, oy}; chips: S x 32 x 32 bytes; last: S x
+// {dx_px, dy_px, sad_best, sad_zero, k, searched}; frames: the context's images, img_idx: row -> image (null: identity)
+// behind the commit: x the step's committed raw rows (n x 2L), masks the commit's
+void sdm_launch_track_motion_store(const int* ids, int n, int L, const float* x, const int* masks, const ImageSetDev& frames,
+                                   const int* img_idx, float scale, int* state, uint8_t* chips, hipStream_t s);
+// ahead of the gather: shift n x 2 floats, (0, 0) for a row that is not searched
+void sdm_launch_track_motion_search(const int* ids, int n, const int* slot_status, const int* state, const uint8_t* chips,
+                                    const ImageSetDev& frames, const int* img_idx, int search, int min_gain, float* shift, int* last,
+                                    hipStream_t s);
+void sdm_launch_track_motion_invalidate(const int* ids, int n, int* state, hipStream_t s);
+// out_motion n x 6, out_grid n x 3, out_chips n x 32 x 32 (zeros where a slot holds no chip)
+void sdm_launch_track_motion_get(const int* ids, int n, const int* state, const uint8_t* chips, const int* last, int* out_motion,
+                                 int* out_grid, uint8_t* out_chips, hipStream_t s);
 
 // ---- aligned face crops (sdm_align.hip) ----
 // per row: the crop -> source matrix (float32, rounded from the double fit), the SDM_ALIGN_* flags and the row's image
@@ -495,6 +510,7 @@ struct UprightSetupDev {
     const int* boxes; const double* cs;
     const int* ids; const int* slot_status; const int* slot_box; const double* slot_cs; const float* slot_x;
     const float* mean; float4 mb;
+    const float* shift;        // the tracker's motion shift, n x 2 floats added to a tracked slot's landmarks as they are read; may be null
 };
 inline int sdm_upright_chip_stride(int chip) { return (chip + 15) & ~15; }
 // rows: n records; chip_*: entries 0 .. n - 1 of the chips' image table (chip i at i * stride * chip); x, init (may be null): n x 2L

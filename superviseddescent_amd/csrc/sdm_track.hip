@@ -61,12 +61,15 @@ __global__ void track_start_kernel(const int* __restrict__ ids, const int* __res
 
 __global__ __launch_bounds__(64) void track_gather_kernel(const int* __restrict__ ids, int L, int mode, const int* __restrict__ slot_status,
                                                           const int* __restrict__ slot_box, const float* __restrict__ slot_x,
-                                                          const float* __restrict__ mean, float4 mb, float* __restrict__ x,
-                                                          float* __restrict__ init)
+                                                          const float* __restrict__ mean, float4 mb, const float* __restrict__ shift,
+                                                          float* __restrict__ x, float* __restrict__ init)
 {
     const int i = blockIdx.x, lane = threadIdx.x, M = 2 * L;
     const int id = ids[i];
     const float* prev = slot_x + (long long)id * M;
+    // the motion search's shift of a tracked slot's landmarks as they are read (csrc/sdm_track_motion.hip); (0, 0) and no pointer: the bits
+    const float sx = shift ? shift[2 * i] : 0.0f, sy = shift ? shift[2 * i + 1] : 0.0f;
+    const bool moved = sx != 0.0f || sy != 0.0f;
     float* xo = x + (long long)i * M;
     float* io = init ? init + (long long)i * M : nullptr;
     const int st = slot_status[id];           // (uniform over the wave: every branch below is taken by all lanes or none)
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(64) void track_gather_kernel(const int* __restrict_
         }
     } else if (mode == SDM_TRACK_INIT_PREVIOUS) {
         for (int j = lane; j < M; j += 64) {
-            const float v = prev[j];
+            const float v = moved ? prev[j] + (j < L ? sx : sy) : prev[j];
             xo[j] = v;
             if (io) io[j] = v;
         }
@@ -89,6 +92,7 @@ __global__ __launch_bounds__(64) void track_gather_kernel(const int* __restrict_
         // the mean in the enclosing box of the previous landmarks: x0[j] = ((m[j] - mx0) / (mx1 - mx0)) * (bx1 - bx0) + bx0
         float bx0, bx1, by0, by1;
         row_bounds(prev, L, lane, bx0, bx1, by0, by1);
+        if (moved) { bx0 = bx0 + sx; bx1 = bx1 + sx; by0 = by0 + sy; by1 = by1 + sy; }      // (min / max of the shifted row: the add is monotonic)
         for (int j = lane; j < M; j += 64) {
             const float m = mean[j];
             const float v = j < L ? ((m - mb.x) / (mb.y - mb.x)) * (bx1 - bx0) + bx0 : ((m - mb.z) / (mb.w - mb.z)) * (by1 - by0) + by0;
@@ -146,10 +150,11 @@ void sdm_launch_track_start(const int* ids, const int* boxes, int n, int* slot_b
 }
 
 void sdm_launch_track_gather(const int* ids, int n, int L, int mode, const int* slot_status, const int* slot_box, const float* slot_x,
-                             const float* mean, const float mean_bounds[4], float* x, float* init, hipStream_t s)
+                             const float* mean, const float mean_bounds[4], float* x, float* init, hipStream_t s, const float* shift)
 {
     const float4 mb = make_float4(mean_bounds[0], mean_bounds[1], mean_bounds[2], mean_bounds[3]);
-    hipLaunchKernelGGL(track_gather_kernel, dim3((unsigned)n), dim3(64), 0, s, ids, L, mode, slot_status, slot_box, slot_x, mean, mb, x, init);
+    hipLaunchKernelGGL(track_gather_kernel, dim3((unsigned)n), dim3(64), 0, s, ids, L, mode, slot_status, slot_box, slot_x, mean, mb, shift, x,
+                       init);
 }
 
 void sdm_launch_track_commit(const int* ids, int n, int L, const float* x, const float* init, const int* img_idx, const int* img_w,

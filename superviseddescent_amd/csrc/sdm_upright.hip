@@ -61,6 +61,11 @@ __global__ __launch_bounds__(64) void upright_setup_kernel(UprightSetupDev a, in
     const int* box = nullptr;
     const float* prev = nullptr;
     double c = 1.0, s = 0.0;
+    // the motion search's shift of a tracked slot's landmarks p, ahead of the roll, the centre and W (csrc/sdm_track_motion.hip)
+    const float mx = a.shift ? a.shift[2 * i] : 0.0f, my = a.shift ? a.shift[2 * i + 1] : 0.0f;
+    const bool moved = mx != 0.0f || my != 0.0f;
+#define UP_PX(j) (moved ? prev[j] + mx : prev[j])
+#define UP_PY(j) (moved ? prev[(j) + L] + my : prev[(j) + L])
     if (a.ids) {
         const int id = a.ids[i];
         if (a.slot_status[id] == SDM_TRACK_STARTED) { box = a.slot_box + 4 * id; c = a.slot_cs[2 * id]; s = a.slot_cs[2 * id + 1]; }
@@ -75,8 +80,8 @@ __global__ __launch_bounds__(64) void upright_setup_kernel(UprightSetupDev a, in
     } else {
         // the roll of a tracked slot: its eye line, the eye centres as device_ied_rows forms them (float32 sums in index order)
         float rx = 0.0f, ry = 0.0f, lx = 0.0f, ly = 0.0f;
-        for (int k = 0; k < eyes.nre; ++k) { rx += prev[eyes.re[k]]; ry += prev[eyes.re[k] + L]; }
-        for (int k = 0; k < eyes.nle; ++k) { lx += prev[eyes.le[k]]; ly += prev[eyes.le[k] + L]; }
+        for (int k = 0; k < eyes.nre; ++k) { rx += UP_PX(eyes.re[k]); ry += UP_PY(eyes.re[k]); }
+        for (int k = 0; k < eyes.nle; ++k) { lx += UP_PX(eyes.le[k]); ly += UP_PY(eyes.le[k]); }
         rx /= (float)eyes.nre; ry /= (float)eyes.nre;
         lx /= (float)eyes.nle; ly /= (float)eyes.nle;
         const float dxf = lx - rx, dyf = ly - ry;
@@ -86,7 +91,7 @@ __global__ __launch_bounds__(64) void upright_setup_kernel(UprightSetupDev a, in
         else { c = dx / n; s = dy / n; }
         float b0 = INFINITY, b1 = -INFINITY, b2 = INFINITY, b3 = -INFINITY;
         for (int j = lane; j < L; j += 64) {
-            const float vx = prev[j], vy = prev[L + j];
+            const float vx = UP_PX(j), vy = UP_PY(j);
             b0 = fminf(b0, vx); b1 = fmaxf(b1, vx);
             b2 = fminf(b2, vy); b3 = fmaxf(b3, vy);
         }
@@ -129,7 +134,7 @@ __global__ __launch_bounds__(64) void upright_setup_kernel(UprightSetupDev a, in
         // the realign rule of sdm_track.hip on q = W p
         float b0 = INFINITY, b1 = -INFINITY, b2 = INFINITY, b3 = -INFINITY;
         for (int j = lane; j < L; j += 64) {
-            const float vx = prev[j], vy = prev[L + j];
+            const float vx = UP_PX(j), vy = UP_PY(j);
             const float qx = up_px(r.w, vx, vy), qy = up_py(r.w, vx, vy);
             b0 = fminf(b0, qx); b1 = fmaxf(b1, qx);
             b2 = fminf(b2, qy); b3 = fmaxf(b3, qy);
@@ -143,6 +148,8 @@ __global__ __launch_bounds__(64) void upright_setup_kernel(UprightSetupDev a, in
             if (io) io[j] = v;
         }
     }
+#undef UP_PX
+#undef UP_PY
 }
 
 // taps (x0, y) and (x0 + 1, y) of one frame row: one 2-byte load when both lie inside the row, byte loads at its ends, 0 outside the

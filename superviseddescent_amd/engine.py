@@ -75,6 +75,12 @@ _DEV_OPTIONS = ("hog_no_pack", "hog_two_load", "hog_split_store", "detect_unfuse
                 "gram_xblocks", "solve_upd_min_tiles", "solve_fine_head", "solve_bs_cap", "solve_shard_emulate")
 
 
+# the tracker's motion search takes the best offset only when its SAD is at most (256 - MOTION_MIN_GAIN) / 256 of staying in place's.
+# Of {0, 16, 32, 64} none leaves 90 % of the rows of a slowly moving face (up to 3 pixels per frame) at shift (0, 0) -- 58, 63, 68 and
+# 78 % were measured --, so the default is the largest of the four
+MOTION_MIN_GAIN = 64
+
+
 class Context:
     """Owner of one ``sdm_ctx`` (one GPU, one stream).  Thin, 1:1 with the C-ABI."""
 
@@ -644,6 +650,26 @@ class Context:
         p = np.empty(i.size, np.int32)
         check(self._lib.sdm_track_get_filtered(self._h, i.ctypes.data, i.size, f.ctypes.data, d.ctypes.data, p.ctypes.data))
         return f, d, p
+
+    # -- the tracker's motion-compensated initialisation (csrc/sdm_track_motion.hip) ----------------
+    def track_configure_motion(self, search: Optional[int] = 8, scale: float = 1.25, min_gain: int = MOTION_MIN_GAIN):
+        """Block matching ahead of every step (include/sdm.h, "Tracking, motion-compensated"): ``search`` 1 ... 16 chip pixels,
+        ``scale`` in [0.5, 4] (the chip's side in face sizes), ``min_gain`` 0 ... 255 (how much, in 256ths, the best offset must beat
+        staying in place); every slot invalid.  ``search`` None: the mode off."""
+        if search is None:
+            check(self._lib.sdm_track_configure_motion(self._h, _lib.SDM_TRACK_MOTION_OFF, 0, 0.0, 0))
+        else:
+            check(self._lib.sdm_track_configure_motion(self._h, _lib.SDM_TRACK_MOTION_SAD, int(search), float(scale), int(min_gain)))
+
+    def track_get_motion(self, ids):
+        """Of the streams ``ids``: (motion n x 6 int32 -- the last step's shift dx, dy in pixels, best SAD, SAD(0, 0), k, searched --,
+        grid n x 3 int32 (k, ox, oy), chips n x 32 x 32 uint8); zeros where a stream holds nothing."""
+        i = self._ids(ids)
+        m = np.empty((i.size, 6), np.int32)
+        g = np.empty((i.size, 3), np.int32)
+        ch = np.empty((i.size, 32, 32), np.uint8)
+        check(self._lib.sdm_track_get_motion(self._h, i.ctypes.data, i.size, m.ctypes.data, g.ctypes.data, ch.ctypes.data))
+        return m, g, ch
 
     # -- upright-normalised detect and tracking (csrc/sdm_upright.hip) ------------------------------
     def upright_configure(self, chip: int, guard: int):
@@ -1852,7 +1878,7 @@ class detection_model:
         return c.pose_get_x()
 
     def tracker(self, capacity: int, init: str = "realign", min_size: float = 8.0, max_scale_change: float = 1.5,
-                chip: Optional[int] = None, guard: Optional[int] = None, smooth=None) -> "Tracker":
+                chip: Optional[int] = None, guard: Optional[int] = None, smooth=None, motion=None) -> "Tracker":
         """Multi-stream tracking on the optimiser's context: ``capacity`` stream slots whose landmarks stay on the device from
         frame to frame (see :class:`Tracker`).  ``init``: how a tracked stream's next frame starts -- "previous" (its landmarks,
         the reference's ``detect(image, initialisation)``) or "realign" (the mean shape in their enclosing box).  A stream is
@@ -1863,8 +1889,11 @@ class detection_model:
         (required) and ``guard`` (default ``chip // 8``) as for ``detect_batch(roll=...)``.
         ``smooth=(min_cutoff, beta)`` or ``(min_cutoff, beta, d_cutoff)``: a One-Euro filter on what ``step(..., dt=...)`` returns
         and leaves as the current rows -- ``min_cutoff`` (Hz) sets how steady a still face is, ``beta`` how fast the filter lets go
-        when the face moves (in face sizes per second), ``d_cutoff`` defaults to 1 Hz.  Tracking itself is not changed by it."""
-        return Tracker(self, capacity, init, min_size, max_scale_change, chip, guard, smooth)
+        when the face moves (in face sizes per second), ``d_cutoff`` defaults to 1 Hz.  Tracking itself is not changed by it.
+        ``motion=True`` or ``(search, scale, min_gain)``: before the cascade every tracked stream's translation since its last frame
+        is estimated by block matching on a 32 x 32 chip of block means and its start is shifted by it (include/sdm.h, "Tracking,
+        motion-compensated") -- for faces that move by more than a few percent of their size per frame.  Defaults (8, 1.25, 64)."""
+        return Tracker(self, capacity, init, min_size, max_scale_change, chip, guard, smooth, motion)
 
     def aligned_crops(self, size, landmark_ids: Optional[Sequence[str]] = None, template: Optional[np.ndarray] = None,
                       margin: float = 0.2, source=None, out=None):
@@ -2222,8 +2251,9 @@ class Tracker:
     _MODES = {"previous": _lib.SDM_TRACK_INIT_PREVIOUS, "realign": _lib.SDM_TRACK_INIT_REALIGN}
 
     def __init__(self, model: detection_model, capacity: int, init: str = "realign", min_size: float = 8.0,
-                 max_scale_change: float = 1.5, chip: Optional[int] = None, guard: Optional[int] = None, smooth=None):
+                 max_scale_change: float = 1.5, chip: Optional[int] = None, guard: Optional[int] = None, smooth=None, motion=None):
         self.smooth = self._smooth(smooth)
+        self.motion_params = self._motion(motion)
         if init not in self._MODES and init != "upright":
             raise ValueError('init must be "previous", "realign" or "upright"')
         if init == "upright" and chip is None:
@@ -2239,6 +2269,30 @@ class Tracker:
             self.ctx.track_configure_upright(init == "upright")
         if self.smooth is not None:
             self.ctx.track_configure_filter(*self.smooth)
+        if self.motion_params is not None:
+            self.ctx.track_configure_motion(*self.motion_params)
+
+    @staticmethod
+    def _motion(motion):
+        """(search, scale, min_gain) as (int, float, int), or None; True: the defaults"""
+        if motion is None or motion is False:
+            return None
+        if motion is True:
+            return (8, 1.25, MOTION_MIN_GAIN)
+        try:
+            v = tuple(motion)
+        except TypeError:
+            raise ValueError("motion is True or (search, scale, min_gain)") from None
+        if len(v) != 3:
+            raise ValueError("motion is True or (search, scale, min_gain)")
+        try:
+            ok = float(v[0]) == int(v[0]) and float(v[2]) == int(v[2]) and 1 <= int(v[0]) <= 16 and 0.5 <= float(v[1]) <= 4.0 and \
+                0 <= int(v[2]) <= 255
+        except (TypeError, ValueError, OverflowError):
+            ok = False
+        if not ok:
+            raise ValueError("motion needs search in 1 ... 16, scale in [0.5, 4] and min_gain in 0 ... 255")
+        return (int(v[0]), float(v[1]), int(v[2]))
 
     @staticmethod
     def _smooth(smooth):
@@ -2319,6 +2373,13 @@ class Tracker:
     def get(self, ids):
         """(landmarks n x 2L, status n: SDM_TRACK_FREE / STARTED / TRACKED / LOST) of the streams ``ids``."""
         return self.ctx.track_get(ids)
+
+    def motion(self, ids):
+        """(motion n x 6 int32: the last step's shift dx, dy in pixels, best SAD, SAD(0, 0), k, searched; grid n x 3 int32: k, ox, oy;
+        chips n x 32 x 32 uint8) of the streams ``ids`` -- a tracker with ``motion`` only."""
+        if self.motion_params is None:
+            raise ValueError("motion needs a tracker with motion=True or (search, scale, min_gain)")
+        return self.ctx.track_get_motion(ids)
 
     def get_filtered(self, ids):
         """(filtered rows n x 2L, their derivative in pixels per second n x 2L, primed flags n) of the streams ``ids``; a stream

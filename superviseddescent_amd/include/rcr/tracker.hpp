@@ -15,6 +15,10 @@
 // Faces in video: tr.smooth(1.0f, 5.0f) puts a One-Euro filter behind the tracker (include/sdm.h, "Tracking, filtered"), and
 // tr.step(ids, frames, dt) returns the filtered landmarks and leaves them as the context's current rows -- crops, warps, pastes and
 // poses follow them; raw_rows() holds what the cascade gave.  Tracking itself is not changed by the filter.
+//
+// Faces that move fast: tr.motion() makes every step estimate each tracked stream's translation since its last frame by block
+// matching on a 32 x 32 chip of block means and start the cascade from the shifted landmarks (include/sdm.h, "Tracking,
+// motion-compensated"); tr.last_motion(ids) returns what the search found.
 #pragma once
 
 #ifndef RCR_TRACKER_HPP_
@@ -95,6 +99,35 @@ public:
     void smooth_off()
     {
         superviseddescent::hip::check(sdm_track_configure_filter(handle.get(), SDM_TRACK_FILTER_OFF, 0.f, 0.f, 0.f), "sdm_track_configure_filter");
+    }
+
+    /** What the last step's search found for one stream: the shift in pixels, the best SAD, SAD(0, 0), the cell size k and whether
+     *  the stream was searched (a started stream, or one without a valid chip, is not: all zeros). */
+    struct motion_result { int dx, dy, sad_best, sad_zero, k, searched; };
+
+    /** Motion-compensated initialisation: search 1 ... 16 chip pixels, scale in [0.5, 4] (the chip's side in face sizes), min_gain
+     *  0 ... 255 (how much, in 256ths, the best offset must beat staying in place).  Every stream's chip starts empty. */
+    void motion(int search = 8, float scale = 1.25f, int min_gain = 64)
+    {
+        superviseddescent::hip::check(sdm_track_configure_motion(handle.get(), SDM_TRACK_MOTION_SAD, search, scale, min_gain),
+                                      "sdm_track_configure_motion");
+    }
+    /** The mode off again. */
+    void motion_off()
+    {
+        superviseddescent::hip::check(sdm_track_configure_motion(handle.get(), SDM_TRACK_MOTION_OFF, 0, 0.f, 0), "sdm_track_configure_motion");
+    }
+    /** The last step's search results of the streams `ids`; grids (n x {k, ox, oy}) and chips (n x 32 x 32 bytes) when asked for. */
+    std::vector<motion_result> last_motion(const std::vector<int>& ids, std::vector<int>* grids = nullptr, std::vector<uint8_t>* chips = nullptr)
+    {
+        std::vector<int> m(ids.size() * 6);
+        if (grids) grids->resize(ids.size() * 3);
+        if (chips) chips->resize(ids.size() * 1024);
+        superviseddescent::hip::check(sdm_track_get_motion(handle.get(), ids.data(), (int)ids.size(), m.data(), grids ? grids->data() : nullptr,
+                                                           chips ? chips->data() : nullptr), "sdm_track_get_motion");
+        std::vector<motion_result> out(ids.size());
+        for (size_t i = 0; i < ids.size(); ++i) out[i] = {m[6 * i], m[6 * i + 1], m[6 * i + 2], m[6 * i + 3], m[6 * i + 4], m[6 * i + 5]};
+        return out;
     }
 
     void stop(const std::vector<int>& ids)

@@ -140,9 +140,11 @@ def make_samples(boxes: np.ndarray, gt68: np.ndarray, landmark_ids, n_perturb: i
     return x_star, x0, img_index
 
 
-def make_tracks(n_streams: int, n_frames: int, seed: int = SEED + 7, size: int = IMAGE_SIZE):
+def make_tracks(n_streams: int, n_frames: int, seed: int = SEED + 7, size: int = IMAGE_SIZE, max_step: float = 3.0,
+                max_scale: float = 0.03):
     """Synthetic video for the tracker: ``n_streams`` faces, each drawn as ``make_faces`` draws one (its own smooth background,
-    landmark blobs, fresh per-pixel noise every frame), whose box moves by up to 3 pixels and scales by up to 3 % per frame and
+    landmark blobs, fresh per-pixel noise every frame), whose box moves by up to ``max_step`` pixels (3) in x and in y and scales by
+    up to ``max_scale`` (3 %) per frame and
     stays at least 10 pixels inside the frame together with every ground-truth landmark.  The boxes stand in for a face
     detector.  Returns (frames uint8 [n_frames, n_streams, size, size], gt68 float32 [n_frames, n_streams, 136], boxes int32
     [n_frames, n_streams, 4] (x, y, w, h)); stream s of frame t is image s of frames[t]."""
@@ -175,8 +177,8 @@ def make_tracks(n_streams: int, n_frames: int, seed: int = SEED + 7, size: int =
     boxes = np.empty((n_frames, n_streams, 4), np.int32)
     for t in range(n_frames):
         if t > 0:
-            step = rng.uniform(-3.0, 3.0, (n_streams, 2))
-            scale = rng.uniform(0.97, 1.03, n_streams)
+            step = rng.uniform(-float(max_step), float(max_step), (n_streams, 2))
+            scale = rng.uniform(1.0 - float(max_scale), 1.0 + float(max_scale), n_streams)
         for s in range(n_streams):
             if t > 0:
                 w[s] = min(max(w[s] * scale[s], 112.0), float(w_max))
