@@ -307,6 +307,102 @@ def unmet(name, dec=None):
     return conditions(dec, [(frames[i]["w"], frames[i]["h"]) for i in idx], borders, beyond, far)
 
 
+# ---- case 9: the tracker's motion-compensated initialisation (csrc/sdm_track_motion.hip) on these frames ---------------------------------
+# Every stream of a case is stored on the case's pixels; then every image's content moves by MOTION_MOVE times the least common multiple of
+# the cell sizes of the streams on it -- a whole number of every such stream's cells -- and the streams are searched there.
+MOTION = (8, 1.25, 0)                              # (search, scale, min_gain)
+MOTION_MOVE = (2, -1)
+
+
+def motion_cases():
+    """name -> (host images, boxes of the streams, rows -> images, the frames on the device, the borders the case names,
+    beyond(X, Y, pitch) -> bool: a tap of the case's kind, the image whose streams must take a non-zero shift or None).  A stream whose face
+    is centred outside its image is lost in step 1, stores nothing and is not stepped again."""
+    imgs, fb = faces()
+    every = "left right top bottom"
+    cases = {}
+    img, b = tall(65600)
+    bx = np.array(list(b[:4]) + [(4, 65535, 56, 56), (-22, 65600 - 60, 64, 64)], np.int32)       # (the last one: a chip across the bottom)
+    cases["tall 65600"] = ([img], bx, np.zeros(len(bx), np.int32), [TALL[65600]], every, lambda X, Y, p: Y >= 65536, None)
+    img, b = wide()
+    bx = np.array(list(b[:5]) + [tuple(b[5]), (20000, -30, 60, 60)], np.int32)           # (the last one: a chip across the top)
+    cases["wide"] = ([img], bx, np.zeros(len(bx), np.int32), [WIDE], every, lambda X, Y, p: X >= 65536, None)
+    # (no tap inside a frame of 80 rows lies beyond INT_MAX itself where h * pitch just passes it: the last rows, as the detect cases ask)
+    for name, f in (("over INT_MAX", CASE2), ("pitch to 2^31", CASE1["pitch to 2^31"])):
+        cases[name] = ([imgs[0]], fb, np.zeros(5, np.int32), [f], every, lambda X, Y, p: Y * p + X > INT_MAX - 8 * p, None)
+    bx = np.array([fb[k % 5] for k in range(len(FAR_ORDER))], np.int32)
+    cases["far apart"] = (imgs, bx, FAR_ORDER, FAR, every, lambda X, Y, p: X >= 0, 0)
+    idx3 = np.array([2, 1, 0, 2, 1, 0, 2], np.int32)
+    cases["stack"] = (imgs, np.array([fb[(2 * k) % 5] for k in range(7)], np.int32), idx3, STACK, every,
+                      lambda X, Y, p: Y * p > 2 ** 24, None)
+    return cases
+
+
+def motion_moved(images, idx, ks):
+    """the images of step 2: image j's content moved by MOTION_MOVE x lcm(cell sizes of the streams on j) pixels (what leaves one edge
+    comes in at the other); idx, ks: the image and the cell size of every stored stream"""
+    out = []
+    for j, im in enumerate(images):
+        kk = [int(k) for k, i in zip(ks, idx) if i == j]
+        step = int(np.lcm.reduce(kk)) if kk else 1
+        assert not kk or max(abs(v) for v in MOTION_MOVE) * step <= MOTION[0] * min(kk)      # within every stream's reach
+        out.append(np.ascontiguousarray(np.roll(im, (MOTION_MOVE[1] * step, MOTION_MOVE[0] * step), axis=(0, 1))))
+    return out
+
+
+def motion_unmet(name, grids, shifts):
+    """What keeps a motion case from passing by accident, from the restatement alone.  grids: stream -> (k, ox, oy) of the stored
+    streams; shifts: stream -> the (dx, dy) pixels the restatement's search takes in step 2.  A stored chip with a tap INSIDE its image
+    beyond the case's boundary; a chip across each border the case names; a window that starts left of its image (ox - S k < 0) on the
+    case's frame of the largest pitch; on the far case a stream of the far frame that takes a non-zero shift; everywhere a stream that
+    takes one.  Returns the names of the conditions that are NOT met."""
+    import track_motion_ref as R
+    images, boxes, idx, frames, borders, beyond, far = motion_cases()[name]
+    S = MOTION[0]
+    cross = dict(left=False, right=False, top=False, bottom=False)
+    deep, negative = False, False
+    widest = max(f["pitch"] for f in frames)
+    for i, (k, ox, oy) in grids.items():
+        f = frames[idx[i]]
+        x0, y0, x1, y1 = max(ox, 0), max(oy, 0), min(ox + R.C * k, f["w"]), min(oy + R.C * k, f["h"])
+        if x1 <= x0 or y1 <= y0:
+            continue
+        cross["left"] |= ox < 0
+        cross["right"] |= ox + R.C * k > f["w"]
+        cross["top"] |= oy < 0
+        cross["bottom"] |= oy + R.C * k > f["h"]
+        deep |= bool(beyond(x1 - 1, y1 - 1, f["pitch"]))
+        negative |= f["pitch"] == widest and ox - S * k < 0
+    missing = ["a chip across the %s border" % b for b in borders.split() if not cross[b]]
+    if not deep:
+        missing.append("a stored chip with a tap beyond the boundary")
+    if not negative:
+        missing.append("a window with a negative first column on the frame of the largest pitch")
+    if not any(np.any(np.asarray(s) != 0) for s in shifts.values()):
+        missing.append("a stream that takes a non-zero shift")
+    if far is not None and not any(np.any(np.asarray(s) != 0) for i, s in shifts.items() if idx[i] == far):
+        missing.append("a stream of the far frame that takes a non-zero shift")
+    return missing
+
+
+def motion_plan(name, rows, lost):
+    """From the rows and lost masks of step 1 (the device's; aligned(boxes) stands in for them without one): (the restatement after its
+    store and search, its motion state of every stream between the two, the streams that go on, the images of step 2, the shifts the
+    restatement's search takes there n x 2, the unmet conditions)"""
+    import track_motion_ref as R
+    images, boxes, idx, frames, borders, beyond, far = motion_cases()[name]
+    n = len(boxes)
+    ids = np.arange(n)
+    ref = R.Motion(n, *MOTION)
+    ref.store_step(ids, rows, lost, images, idx)
+    stored = ref.get(ids)
+    keep = ids[np.asarray(lost) == 0]
+    moved = motion_moved(images, idx[keep], ref.grid[keep, 0])
+    shifts = ref.search_step(keep, np.ones(len(keep), bool), moved, idx[keep])
+    grids = {int(i): tuple(int(v) for v in ref.grid[i]) for i in keep}
+    return ref, stored, keep, moved, shifts, motion_unmet(name, grids, {int(i): s for i, s in zip(keep, shifts)})
+
+
 # ==== the paste cases of tests/test_gpu_frame_geometry_paste.py =========================================================================
 # The four kernels that WRITE into the caller's frames -- the rigid, the filtered, the NV12 and the piecewise-affine paste -- on the
 # frames above, the format swapped in.  A case: dict(case, family, frames, idx (row -> frame), mats or points, cw, ch, dtype, layout,

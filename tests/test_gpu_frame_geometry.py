@@ -1,6 +1,6 @@
 """Frame geometry beyond 256 x 256 (tests/frame_geometry_cases.py): pitches that carry the byte offset inside an image past 2^16,
 2^24 and up to and over 2^31, frames of 65 535 and 65 600 rows and of 70 000 columns, frames of one set more than 2^32 bytes apart,
-the converter on frames of many workgroups, and the crops and the tracker on the same sets.  Every frame is a view into ONE device
+the converter on frames of many workgroups, and the crops, the tracker and its motion search on the same sets.  Every frame is a view into ONE device
 buffer of 255s, so a read of padding differs from the black canvas; the same pixels as dense host arrays go through the CPU
 references: the oracle (integer decisions bit for bit, feature rows within the bound of test_gpu_packing.py), align_ref and
 align_tensor_ref (bit for bit), track_ref (the lost mask), orc.bgr2gray (bit for bit).
@@ -16,6 +16,7 @@ import pytest
 import align_ref as A
 import align_tensor_ref as T
 import frame_geometry_cases as G
+import track_motion_ref as R
 import track_ref as TR
 from oracle import sdm_oracle as orc
 from superviseddescent_amd import HoGParam, LinearRegressor, SupervisedDescentOptimiser, alignment_template, detection_model, ibug
@@ -75,6 +76,17 @@ def test_case_table():
         assert G.conditions(dec, [(f["w"], f["h"])] * len(boxes), borders, beyond) == [], which
         lost = TR.lost_mask(rows, rows, f["w"], f["h"], 8.0, 1.5, RE, LE)
         assert lost[far_stream] == 0 and lost[-1] == TR.OUTSIDE and not lost[:-1].any(), (which, lost)
+    # the motion cases: their conditions on the restatement, the streams' first rows standing in for the device's
+    for name, (images, boxes, idx, frames, borders, beyond, far) in G.motion_cases().items():
+        rows = G.aligned(boxes)
+        sizes = np.array([(frames[i]["w"], frames[i]["h"]) for i in idx])
+        lost = TR.lost_mask(rows, rows, sizes[:, 0], sizes[:, 1], 8.0, 1.5, RE, LE)
+        assert (lost == 0).sum() >= 3, name
+        assert G.motion_plan(name, rows, lost)[5] == [], (name, G.motion_plan(name, rows, lost)[5])
+        assert all(f in G.all_frames() for f in frames) and len(images) == len(frames)
+    # ... and one that lacks the interior stream is caught: nothing on the far frame takes a shift
+    grids = {1: (2, -40, -30), 0: (3, 2, 1)}                           # (stream 1 on the far frame, stream 0 on another)
+    assert G.motion_unmet("far apart", grids, {1: (0, 0), 0: (6, -3)}) == ["a stream of the far frame that takes a non-zero shift"]
     # case 7's rows
     assert case7_unmet(G.oracle_level([nv12_pixels(k)[0] for k in (0, 0, 1, 1)], CASE7_IDX, G.aligned(case7_boxes()), 0)[1]) == []
     # ... and a case that lacks one is caught: without its last three boxes the wide frame has no patch beyond column 65 536
@@ -453,3 +465,68 @@ def test_case8_tracker(model, big, which):
     if which != "tall 65535":
         assert centre > 65536
     assert l1[n - 1] & TR.OUTSIDE and np.isfinite(r1).all()
+
+
+# ---- case 9: the tracker's motion-compensated initialisation on the tall, the wide, the far and the stacked frames ---------------------------
+MOTION_CASES = [("tall 65600", "gray"), ("wide", "gray"), ("over INT_MAX", "gray"), ("over INT_MAX", "nv12"), ("pitch to 2^31", "gray"),
+                ("far apart", "gray"), ("stack", "gray")]
+
+
+@gpu
+@pytest.mark.parametrize("name,fmt", MOTION_CASES, ids=["%s-%s" % c for c in MOTION_CASES])
+def test_case9_tracker_motion(model, big, name, fmt):
+    """step 1 on the case's pixels; step 2 on the same frames rewritten, every image's content moved by whole cells of the streams on
+    it.  Chips, grids, last results and the stepped rows against tests/track_motion_ref.py, the stepped rows against detect from the
+    shifted initialisation on the dense host arrays, and every device result against the same tracker on those arrays."""
+    import torch
+    images, boxes, idx, frames, borders, beyond, far = G.motion_cases()[name]
+    n = len(boxes)
+    ids = np.arange(n)
+    MIN_SIZE, MAX_SCALE = 8.0, 1.5
+    frames = [dict(f, fmt=fmt) for f in frames]
+    pixels = [(im, nv12_pixels(k)[1]) if fmt == "nv12" else im for k, im in enumerate(images)]
+    sizes = np.array([(frames[i]["w"], frames[i]["h"]) for i in idx])
+    ctx = model.optimised_model.ctx
+    # a pitch beyond the fused kernels' is served by the generic pixel kernel, which shares no bits with them: where the case's frames
+    # need it, a one-column image at the end of the host set makes that set take it too (image_needs_generic: w < 2)
+    generic = any(f["pitch"] > G.MAX_STRIDE or f["pitch"] * f["h"] > G.INT_MAX for f in frames)
+    extra = [np.zeros((4, 1), np.uint8)] if generic else []
+    runs, plan = [], None
+    with placed(big, frames, pixels) as lst:
+        for on_device in (True, False):
+            tr = model.tracker(n, init="previous", min_size=MIN_SIZE, max_scale_change=MAX_SCALE, motion=G.MOTION)
+            tr.start(ids, boxes)
+            r1, l1 = tr.step(ids, lst if on_device else images + extra, image_index=idx)
+            m1 = tr.motion(ids)
+            if plan is None:
+                plan = G.motion_plan(name, r1, l1)
+            ref, stored, keep, moved, shifts, unmet = plan
+            if on_device:
+                for f, a in zip(frames, moved):                        # the luma rewritten in place, the pitch bytes untouched
+                    views_of(big, f)[0].copy_(torch.from_numpy(a).cuda())
+                torch.cuda.synchronize()
+            r2, l2 = tr.step(keep, lst if on_device else moved + extra, image_index=idx[keep])
+            runs.append((r1, l1, m1, r2, l2, tr.motion(ids)))
+        ref, stored, keep, moved, shifts, unmet = plan
+        # detect from the shifted initialisation on the dense host arrays
+        init = R.shifted(runs[0][0][keep], shifts)
+        ctx.upload_images(moved + extra)
+        ctx.set_sample_image_index(idx[keep])
+        ctx.set_x(init)
+        detected = ctx.detect_batch()
+        ctx.set_sample_image_index(None)
+        ctx.upload_images([np.zeros((4, 4), np.uint8)])
+    dev, host = runs
+    for a, b in zip(dev[:2] + dev[2] + dev[3:5] + dev[5], host[:2] + host[2] + host[3:5] + host[5]):
+        assert a.dtype == b.dtype and a.tobytes() == b.tobytes()
+    r1, l1, m1, r2, l2, m2 = dev
+    assert unmet == [], (name, unmet)
+    assert np.array_equal(l1, TR.lost_mask(G.aligned(boxes), r1, sizes[:, 0], sizes[:, 1], MIN_SIZE, MAX_SCALE, RE, LE))
+    for got, want in zip(m1, stored):
+        assert np.array_equal(got, want)
+    print("%s %s: cell sizes %s, shifts %s" % (name, fmt, ref.grid[keep, 0].tolist(), shifts.tolist()))
+    assert np.array_equal(bits(r2), bits(detected))
+    assert np.array_equal(l2, TR.lost_mask(init, r2, sizes[keep, 0], sizes[keep, 1], MIN_SIZE, MAX_SCALE, RE, LE))
+    ref.store_step(keep, r2, l2, moved, idx[keep])
+    for got, want in zip(m2, ref.get(ids)):
+        assert np.array_equal(got, want)

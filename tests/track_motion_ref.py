@@ -32,12 +32,15 @@ def block_means(img, X0, Y0, k, n):
     """n x n uint8: (sum of the k x k taps from (X0 + i k, Y0 + j k) + k^2 / 2) / k^2, a tap outside the image 0"""
     img = np.asarray(img)
     h, w = img.shape
-    region = np.zeros((n * k, n * k), np.int64)
+    sums = np.zeros((n, n), np.int64)
     xa, xb = max(X0, 0), min(X0 + n * k, w)
     ya, yb = max(Y0, 0), min(Y0 + n * k, h)
     if xa < xb and ya < yb:
-        region[ya - Y0:yb - Y0, xa - X0:xb - X0] = img[ya:yb, xa:xb]
-    sums = region.reshape(n, k, n, k).sum(axis=(1, 3))
+        # only the cells the image overlaps are laid out (a window of 64 x 64 cells of 64 x 64 taps mostly lies outside a frame)
+        ca, cb, ra, rb = (xa - X0) // k, (xb - X0 + k - 1) // k, (ya - Y0) // k, (yb - Y0 + k - 1) // k
+        region = np.zeros(((rb - ra) * k, (cb - ca) * k), np.int64)
+        region[ya - Y0 - ra * k:yb - Y0 - ra * k, xa - X0 - ca * k:xb - X0 - ca * k] = img[ya:yb, xa:xb]
+        sums[ra:rb, ca:cb] = region.reshape(rb - ra, k, cb - ca, k).sum(axis=(1, 3))
     return ((sums + (k * k) // 2) // (k * k)).astype(np.uint8)
 
 
